@@ -6,7 +6,13 @@ Workload (BASELINE.json configs[2], the configuration the metric is quoted on): 
 Re 1e6, dt 0.05/res - exactly what `FluidSimulator.create(5, 4096, ...)` builds in the reference.
 Synthetic: the scene comes from the NumPy scene builder, the state starts at zero.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--res R] [--no-cpu] [--sweeps S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--res R] [--dump-outputs DIR] [--full [--no-cpu] [--sweeps S]]
+
+A plain run sets up, warms up, times the K steps and prints the headline (steps/s, ms_per_step).  --full adds everything else the line
+used to carry: the box's stream / issue rates, the spread over extra timed blocks, per-kernel HIP-event profiles and HBM roofline
+fractions, the isolated Jacobi sweeps, the state checksum and Poisson residual, and the CPU-oracle leg with its in-run parity check.
+--dump-outputs DIR (one GPU) writes the fields the last timed step left (v, p [, dye]) as DIR/<name>.npy; every single-GPU mode starts
+its timed steps after W + 40 untimed steps, so the files of two builds run with the same arguments compare field for field.
 
 N > 1, one rank per GPU; the grid is cut into N y-slabs (strong scaling: same res 4096 grid), ghost rows travel over RCCL inside
 libfs_hip.  Two ways to start it, same result:
@@ -62,7 +68,28 @@ def parse():
                          "odd widths) falls back to the kernel with the largest share of the step and says so in roofline.selection")
     ap.add_argument("--force-dist", action="store_true",
                     help="debug: take the multi-process code path (gloo rendezvous + RCCL communicator) even with one rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: box rates, timed blocks, per-kernel profile and roofline, "
+                         "isolated Jacobi sweeps, state checksum, Poisson residual, CPU-oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the fields the last timed step left (what field_to_numpy() returns) as DIR/<name>.npy; one GPU only")
     return ap.parse_args()
+
+
+DUMP_LIMIT = 64_000_000     # bytes of .npy files --dump-outputs may write in all
+
+
+def dump_outputs(fields, out_dir, limit=DUMP_LIMIT, seed=0):
+    """Write `fields` (name -> (X, Y[, C]) array) as <out_dir>/<name>.npy in their own float type.  When the whole fields exceed `limit`
+    bytes, every field keeps the same x columns (axis 0): a sorted sample drawn with `seed`, as many columns as fit.  Same shape and seed,
+    same columns."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    nx = next(iter(fields.values())).shape[0]
+    keep = min(nx, (limit - 4096) // sum(a[0].nbytes for a in fields.values()))      # (4 KiB for the .npy headers)
+    cols = None if keep >= nx else np.sort(np.random.default_rng(seed).choice(nx, keep, replace=False))
+    for name, a in fields.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a if cols is None else np.ascontiguousarray(a[cols]))
 
 
 def algorithmic_bytes(mask, esize=4):
@@ -333,6 +360,8 @@ def spawn_ranks(n):
 
 def main():
     args = parse()
+    if args.dump_outputs and (max(args.gpus, int(os.environ.get("WORLD_SIZE", 1))) > 1 or args.force_dist):
+        raise SystemExit("bench.py: --dump-outputs needs a single-GPU run (--gpus 1, no --force-dist)")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1 and not args.force_dist:
         raise SystemExit(spawn_ranks(args.gpus))
     rank = int(os.environ.get("RANK", 0))
@@ -395,7 +424,7 @@ def main():
     # what THIS box streams at (the pool's boxes differ by several per cent): ~30 ms of float4 read and of float4 copy on two buffers the
     # size of a 2-channel field of the headline grid (268 MB each: beyond the Infinity Cache), before anything is timed
     box = None
-    if hasattr(dev, "box_rates"):
+    if args.full and hasattr(dev, "box_rates"):
         rd, cp = dev.box_rates(2 * 8192 * 4096 * 4, 30.0)
         box = {"read_GBps": round(rd, 1), "copy_GBps": round(cp, 1), "buffer_MB": 268.4, "note": "float4 read / copy measured in this run on this GPU before the timed region"}
         if hasattr(dev, "box_valu_rate"):      # what one SIMD of this box issues per second: the issue-bound K3+K4 pass is priced against it (roofline.valu_issue)
@@ -419,13 +448,21 @@ def main():
     settle = 3 * SETTLE + 2 * TRIAL     # (every N takes the same budget - state_checksum is compared across --gpus 1/2/4/8 - and `after_steps` says how many)
     later = 0
     exchange_trial = None
+    # N = 1: the timed steps start after warmup + SETTLE untimed steps in every mode, whatever the capture took, so what they compute
+    # (--dump-outputs) depends on the arguments alone.  The graph starts at the phase of the buffer rotation it was captured in: `lead`
+    # eager steps of the timed region bring the padded state back to it.
+    phase0 = lead = 0
     if world == 1 and not args.force_dist and not args.no_graph:
         done = sim.capture_period(budget=SETTLE)       # one period of the buffer rotation (2 or 6 steps) as a hipGraph
-        later = settle - done
+        for _ in range(SETTLE - done):
+            sim.step()
+        later = settle - SETTLE
         if sim._graph is not None:
             graph, gperiod = sim._graph[1], sim._graph[2]
             glong = sim._graph_long        # the same period repeated to >= 16 steps in one graph: ~5 us of idle time per replay, whatever it holds
             launch = f"hipGraph replay of {gperiod}-step periods" + (f" ({glong[1]} steps per graph)" if glong else "")
+            phase0 = (SETTLE - done) % gperiod
+            lead = min((gperiod - phase0) % gperiod, args.steps)
     elif (world > 1 or args.force_dist) and not args.no_tape:
         done = [0]
 
@@ -452,8 +489,9 @@ def main():
         if tape is not None:
             launch = f"tape replay of {tape['nsteps']}-step periods ({len(tape['ops'])} operations, C++ loop)"
     else:
-        for _ in range(settle):
+        for _ in range(SETTLE):
             sim.step()
+        later = settle - SETTLE
     pu = sim._solver.pressure_updater
     launch += "; pressure: " + (getattr(pu, "form", None) or ("two red-black iterations per pass (fs_rbsor_pair)" if getattr(pu, "_pair", False)
                                                               else "one fused red-black iteration per launch"))
@@ -463,12 +501,16 @@ def main():
             nsteps %= glong[1]
         dev.replay(graph, nsteps // gperiod)
 
-    lists_before = dev.tile_list_stats() if hasattr(dev, "tile_list_stats") else None
+    lists_before = dev.tile_list_stats() if args.full and hasattr(dev, "tile_list_stats") else None
     dev.barrier()                      # device sync + all ranks arrived
     t0 = time.perf_counter()
     if graph is not None:
-        replay_graphs(args.steps)
-        for _ in range(args.steps % gperiod):
+        for _ in range(lead):
+            sim.step()
+        if args.steps - lead >= gperiod and sim._signature() != sim._graph[0]:      # (checked while the GPU runs the lead steps)
+            raise SystemExit("bench: the state is not at the phase of the captured graph; replaying it would compute garbage")
+        replay_graphs(args.steps - lead)
+        for _ in range((args.steps - lead) % gperiod):
             sim.step()
     elif tape is not None:
         dev.replay_tape(tape, args.steps // tape["nsteps"])
@@ -481,6 +523,30 @@ def main():
     elapsed = max(dev.allgather_scalars(time.perf_counter() - t0))      # max over ranks
     steps_per_s = args.steps / elapsed
     lists_after = dev.tile_list_stats() if lists_before else None
+    flushed = False
+    if args.dump_outputs:
+        dump_outputs(sim.field_to_numpy(), args.dump_outputs)
+        # (the download launched what a deferred pass still owed: the captured graph no longer starts from this state, --full steps on eagerly)
+        flushed = sim._limit_pending() != sim._pending_after_step
+    abytes, counts = algorithmic_bytes(mask, esize)
+    out = {
+        # BASELINE.json's metric string for the headline configuration; `value` is its steps/sec part, the Poisson-sweep
+        # GB/s (% of the HBM roofline) part is in `poisson_jacobi_sweep` (and per kernel in `kernels`) of a --full run
+        "metric": "simulation steps/sec + Poisson-sweep HBM GB/s (% roofline), res 4096\u00b2, 1/2/4/8 GPU"
+                  if (res, args.bc, args.scheme, args.jacobi, args.dye, args.dtype) == (4096, 5, "cip", 0, False, "f32")
+                  else f"simulation steps/sec (bc{args.bc} res {res} {args.scheme}{' jacobi' + str(args.jacobi) if args.jacobi else ''}{' +dye' if args.dye else ''}{' f64' if args.dtype == 'f64' else ''})",
+        "value": round(steps_per_s, 3), "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 / steps_per_s, 4), "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": f"bc={args.bc} res={res} ({2 * res}x{res} cells) scheme={args.scheme} vc={vc} "
+                               f"{'Jacobi(' + str(args.jacobi) + ')' if args.jacobi else 'RB-SOR(1.3, 2 iters)'} Re={re:g} dt={'0.05/res' if not args.dt else args.dt}"
+                               + ("; BASELINE.json configs[2]" if (res, args.bc, args.scheme, args.jacobi) == (4096, 5, "cip", 0) else ""),
+                   "cells": counts["cells"], "fluid_cells": counts["fluid"], "parallelism": f"y-slab x{world}",
+                   "launch": launch},
+    }
+    if not args.full:
+        finish(dev, rdzv, rank, out)
+        return
 
     # Short timed regions (the driver's --steps 20 is 16 ms of work) say little about the spread: for K < 120 another 120 steps follow in
     # blocks of the whole replay periods of K, each timed like the first, and min / median / max per step are reported NEXT TO the
@@ -502,9 +568,9 @@ def main():
         return max(dev.allgather_scalars(time.perf_counter() - t))
     spread = [1e3 * elapsed / args.steps]
     extra_steps = 0 if args.steps >= 120 else 120
-    used = (period - args.steps % period) % period          # finish the period the K steps ended in (eager, untimed)
+    used = (period - (phase0 + args.steps) % period) % period          # finish the period the K steps ended in (eager, untimed)
     bsteps = max((args.steps // period) * period, period)
-    if used <= extra_steps:
+    if used <= extra_steps and not flushed:
         for _ in range(used):
             sim.step()
         while used + bsteps <= extra_steps:
@@ -542,7 +608,6 @@ def main():
     v_f, p_f = sim._solver.get_fields()[:2]
     r_sum, r_cnt = dev.poisson_residual(dt, dx, p_f, v_f)
     residual = {"rms": float(np.sqrt(r_sum / max(r_cnt, 1.0))), "cells": int(r_cnt)}
-    abytes, counts = algorithmic_bytes(mask, esize)
     # HBM bytes per launch from rocprofv3 PMC passes of this same workload (tools/profile.sh -> profiles/*.json), if present
     pmc_traffic, pmc_valu, traffic_source = {}, {}, None
     pmc_file = os.path.join(REPO, "profiles", "pmc_traffic.json")
@@ -699,21 +764,9 @@ def main():
             four.update(equiv(us / 4))
             jac["four_sweeps_per_pass"] = four
 
-    out = {
-        # BASELINE.json's metric string for the headline configuration; `value` is its steps/sec part, the Poisson-sweep
-        # GB/s (% of the HBM roofline) part is in `poisson_jacobi_sweep` (and per kernel in `kernels`)
-        "metric": "simulation steps/sec + Poisson-sweep HBM GB/s (% roofline), res 4096\u00b2, 1/2/4/8 GPU"
-                  if (res, args.bc, args.scheme, args.jacobi, args.dye, args.dtype) == (4096, 5, "cip", 0, False, "f32")
-                  else f"simulation steps/sec (bc{args.bc} res {res} {args.scheme}{' jacobi' + str(args.jacobi) if args.jacobi else ''}{' +dye' if args.dye else ''}{' f64' if args.dtype == 'f64' else ''})",
-        "value": round(steps_per_s, 3), "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(1e3 / steps_per_s, 4), "ms_per_step_min": round(spread[0], 4), "ms_per_step_median": round(spread[len(spread) // 2], 4),
-        "ms_per_step_max": round(spread[-1], 4), "timed_blocks": len(blocks), "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": f"bc={args.bc} res={res} ({2 * res}x{res} cells) scheme={args.scheme} vc={vc} "
-                               f"{'Jacobi(' + str(args.jacobi) + ')' if args.jacobi else 'RB-SOR(1.3, 2 iters)'} Re={re:g} dt={'0.05/res' if not args.dt else args.dt}"
-                               + ("; BASELINE.json configs[2]" if (res, args.bc, args.scheme, args.jacobi) == (4096, 5, "cip", 0) else ""),
-                   "cells": counts["cells"], "fluid_cells": counts["fluid"], "parallelism": f"y-slab x{world}",
-                   "launch": launch},
+    out.update({
+        "ms_per_step_min": round(spread[0], 4), "ms_per_step_median": round(spread[len(spread) // 2], 4),
+        "ms_per_step_max": round(spread[-1], 4), "timed_blocks": len(blocks),
         "box": box,
         # compact launch lists (one hipMalloc + stream sync each, at the first launch of a geometry / slab row range): all built during the warm-up -
         # none inside the timed region, and no launch of the captured / taped period had to fall back to its dense grid
@@ -729,7 +782,7 @@ def main():
             "KB_per_neighbour": round(dev.n_exchanged_bytes / max(total_steps, 1) / 1024, 1),
             "overlapped_fraction": round(dev.n_overlapped / max(dev.n_exchanges, 1), 2),
             "halo_rows": dev.halo},
-    }
+    })
     if dominant:
         kd = kernels[dominant]
         if dominant in ("cip_grad_advect_rt", "cip_step"):
@@ -784,6 +837,10 @@ def main():
         out["cpu_baseline"] = cpu_baseline(args, create_scene_arrays(args.bc, res), sim, dt, step_bytes)
         if not (out["cpu_baseline"]["parity_in_run"]["bit_identical"] and all(out["cpu_baseline"]["parity_in_run"]["graded_sweep_vs_oracle"].values())):
             raise SystemExit("bench: GPU and CPU oracle disagree after the same steps from the same state: " + json.dumps(out["cpu_baseline"]))
+    finish(dev, rdzv, rank, out)
+
+
+def finish(dev, rdzv, rank, out):
     dev.barrier()
     dev.close()
     if rdzv is not None:

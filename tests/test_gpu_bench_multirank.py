@@ -12,7 +12,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--res", "256", "--steps", "10", "--warmup", "4", "--sweeps", "20", "--no-cpu", "--trial-steps", "24"]      # (the trial's default of 120 steps per mode is for real links)
+ARGS = ["--full", "--res", "256", "--steps", "10", "--warmup", "4", "--sweeps", "20", "--no-cpu", "--trial-steps", "24"]      # (the trial's default of 120 steps per mode is for real links)
 
 
 def _single():
@@ -107,7 +107,7 @@ def test_bench_line_contract_with_the_large_grid_step(hip_lib):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["FS_RBPAIR_SPLIT"] = "2"
     env["FS_SMALL_CELLS"] = "0"          # (below 2 M cells the pair and fs_cip_step run 2-row tiles in one launch: the big grids' tile heights here)
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--res", "512", "--bc", "2", "--steps", "12", "--warmup", "4", "--sweeps", "20",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--res", "512", "--bc", "2", "--steps", "12", "--warmup", "4", "--sweeps", "20",
                           "--cpu-seconds", "2", "--roofline-kernel", "cip_step"], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -137,10 +137,42 @@ def test_bench_line_contract_with_the_large_grid_step(hip_lib):
 def test_roofline_kernel_falls_back_by_name_when_the_workload_never_launches_it(hip_lib):
     """An upwind run (BASELINE configs[0]'s scheme) has no cip_step: the line says so and prices a kernel the run did launch."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--res", "200", "--bc", "1", "--scheme", "upwind", "--vc", "0", "--re", "1000",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--res", "200", "--bc", "1", "--scheme", "upwind", "--vc", "0", "--re", "1000",
                           "--dt", "0.0005", "--steps", "10", "--warmup", "2", "--sweeps", "0", "--no-cpu"], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip()][0])
     rf = d["roofline"]
     assert rf["kernel"] in d["kernels"] and rf["kernel"] != "cip_step" and "not launched by this workload" in rf["selection"]
     assert rf["gpu_kernels"] and all(k.startswith("fs::k_") for k in rf["gpu_kernels"])
+
+
+@pytest.mark.parametrize("extra,dye", [([], False), (["--no-graph", "--dye"], True)])
+def test_plain_line_and_dumped_outputs_equal_the_oracle(extra, dye, tmp_path, hip_lib):
+    """A plain run (no --full) prints the headline and nothing that needs runs of its own; --dump-outputs writes the fields its last timed
+    step left.  Every single-GPU mode starts its K timed steps after W + 40 untimed ones, so the files hold the state after W + 40 + K steps
+    whatever the graph capture took: bit for bit the CPU oracle's after as many steps."""
+    import numpy as np
+    from fs.boundary_condition import create_scene_arrays
+    from oracle import oracle as O
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    res, warmup, steps = 64, 3, 9
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--res", str(res), "--steps", str(steps), "--warmup", str(warmup),
+                          "--dump-outputs", str(tmp_path)] + extra, capture_output=True, text=True, timeout=600, env=env)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d["unit"] == "steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == steps and d["warmup"] == warmup
+    assert d["value"] > 0 and abs(d["ms_per_step"] - 1e3 / d["value"]) <= 1e-4
+    for moved in ("box", "kernels", "roofline", "poisson_jacobi_sweep", "state_checksum", "poisson_residual", "cpu_baseline", "timed_blocks"):
+        assert moved not in d, moved
+    const, mask, dyec = create_scene_arrays(5, res)
+    ref = O.make_simulator(const, mask, dyec if dye else None, scheme="cip", dt=0.05 / res, dx=1.0 / res, re=1.0e6, vor_eps=5.0,
+                           updater=("rbsor", 1.3, 2))
+    for _ in range(warmup + 40 + steps):
+        ref.update()
+    expect = ref.fields()
+    assert sorted(f.name for f in tmp_path.iterdir()) == sorted(k + ".npy" for k in expect)
+    for k, e in expect.items():
+        got = np.load(tmp_path / (k + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, e, equal_nan=True), k

@@ -52,15 +52,13 @@ def test_scene_hash_bc2_res8192():
     assert (_sha(mask), _sha(const), _sha(dye)) == (e["sha_mask"], e["sha_bc_const"], e["sha_bc_dye"])
 
 
-REF_ASSETS = "/root/reference"
+REF_ASSETS = GOLDEN       # the reference's obstacle image, kept as a test fixture: tests/golden/images/bc_mask/dragon.png
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_ASSETS, "images", "bc_mask", "dragon.png")),
-                    reason="scene 6 needs the reference's dragon.png (present in the build container only; not copied)")
 @pytest.mark.parametrize("res", [16, 32, 48])
 def test_scene6_from_the_reference_asset(res, monkeypatch):
     """the image-obstacle scene (reference fs/boundary_condition.py:171-198, 482-524) built by the product's
-    scene builder from the reference's own asset (looked up through FS_ASSET_DIR, never copied) equals the arrays the
+    scene builder from the reference's own asset (looked up through FS_ASSET_DIR; the package ships no copy) equals the arrays the
     reference builder produced (tests/golden/scenes.npz), bit for bit."""
     from fs.boundary_condition import create_scene_arrays
     monkeypatch.setenv("FS_ASSET_DIR", REF_ASSETS)
@@ -72,7 +70,6 @@ def test_scene6_from_the_reference_asset(res, monkeypatch):
     assert 0 < int((mask[2:-2, 2:-2] == 1).sum()) < mask[2:-2, 2:-2].size      # the dragon is there, and it is not everything
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_ASSETS, "images", "bc_mask", "dragon.png")), reason="needs the reference asset")
 def test_scene6_hash_at_reference_size(monkeypatch):
     from fs.boundary_condition import create_scene_arrays
     monkeypatch.setenv("FS_ASSET_DIR", REF_ASSETS)

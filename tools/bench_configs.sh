@@ -8,7 +8,7 @@ set -u
 TAG=${1:-r2}
 OUT=gpurun_out/bench_$TAG
 mkdir -p $OUT
-run() { name=$1; shift; python3 bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name rc=$? $(head -c 300 $OUT/$name.json)"; }
+run() { name=$1; shift; python3 bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name rc=$? $(head -c 300 $OUT/$name.json)"; }
 run cfg0_bc1_res200_upwind   --bc 1 --res 200 --scheme upwind --vc 0 --re 1000 --dt 0.0005 --steps 20000 --warmup 200 --sweeps 0 --cpu-seconds 5
 run cfg1_bc2_res1600_jacobi50 --bc 2 --res 1600 --jacobi 50 --steps 400 --warmup 40 --sweeps 0 --cpu-seconds 8
 run cfg2_bc5_res4096_cip_vc  --steps 200 --warmup 40

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""stdin: bench.py's JSON line -> one short line (steps/s, launch form, per-kernel us x launches per step)"""
+"""stdin: the JSON line of `bench.py --full` -> one short line (steps/s, launch form, per-kernel us x launches per step)"""
 import json
 import sys
 d = json.loads(sys.stdin.read())

@@ -6,7 +6,7 @@ TAG=${1:-r6}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS="bench.py --steps 20 --warmup 10 --no-cpu --no-graph --sweeps 40"
+ARGS="bench.py --full --steps 20 --warmup 10 --no-cpu --no-graph --sweeps 40"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- python3 $ARGS > $OUT/bench_trace.json 2> $OUT/trace.err
 timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -o p -- python3 $ARGS > /dev/null 2> $OUT/pmc_fetch.err
 timeout 300 rocprofv3 --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum --kernel-trace --output-format csv -d $OUT/pmc_write -o p -- python3 $ARGS > /dev/null 2> $OUT/pmc_write.err

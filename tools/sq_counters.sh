@@ -5,7 +5,7 @@ set -u
 TAG=${1:-r3}; OUT=gpurun_out/sq_$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAVES --kernel-trace --output-format csv -d $OUT -o p -- \
-    python3 bench.py --steps 6 --warmup 6 --no-cpu --no-graph --sweeps 10 > $OUT/bench.json 2> $OUT/err.txt
+    python3 bench.py --full --steps 6 --warmup 6 --no-cpu --no-graph --sweeps 10 > $OUT/bench.json 2> $OUT/err.txt
 python3 - "$OUT" <<'PY' | tee $OUT/summary.txt
 import csv, glob, collections, sys
 agg = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.Counter()
