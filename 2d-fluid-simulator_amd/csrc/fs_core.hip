@@ -683,6 +683,7 @@ int fs_destroy(fs_ctx *ctx)
     if (ctx->d_lazyflags) hipFree(ctx->d_lazyflags);
     if (ctx->d_pairlist) hipFree(ctx->d_pairlist);
     if (ctx->d_partial) hipFree(ctx->d_partial);
+    if (ctx->d_stats) hipFree(ctx->d_stats);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     delete ctx;
     return FS_OK;

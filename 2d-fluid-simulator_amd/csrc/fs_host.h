@@ -102,6 +102,8 @@ struct fs_ctx {
     unsigned *d_sync = nullptr;   // k_velocity_bc_limit / k_dye_bc_limit: arrive / depart counters of the grid barrier of their rare path [0, 1] (zero between launches)
     double *d_partial = nullptr;   // per-block partial (sum, count) pairs of the residual reduction
     size_t partial_cap = 0;        // pairs
+    double *d_stats = nullptr;     // fs_flow_stats: per-workgroup partial vectors of FS_FLOW_NSTAT doubles, then the combined vector
+    size_t stats_cap = 0;          // vectors
     // graphs
     bool capturing = false;
     std::vector<hipGraphExec_t> graphs;

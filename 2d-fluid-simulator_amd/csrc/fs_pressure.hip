@@ -1,6 +1,9 @@
 // fs_pressure.hip - C-ABI entry points of the pressure kernels: Jacobi sweeps (single, lazily bounded pairs / quads / finishing pass), red-black
-// SOR (half sweeps, one fused iteration, two iterations per pass), the Poisson source pair and the residual.
+// SOR (half sweeps, one fused iteration, two iterations per pass), the Poisson source pair, the residual and the flow diagnostics.
 #include "fs_launch.h"
+#include "fs_stats.h"
+
+static_assert(fs::STATS_N == FS_FLOW_NSTAT, "fs_stats.h and include/fs_hip.h disagree on the slots");
 
 using namespace fs;
 
@@ -360,6 +363,45 @@ int fs_poisson_residual(fs_ctx *ctx, double dt, double dx, const fs_field *p, co
     FS_HIP(hipStreamSynchronize(ctx->stream));
     *sum_sq = h[0];
     *count = h[1];
+    return FS_OK;
+}
+
+int fs_flow_stats(fs_ctx *ctx, double dx, const fs_field *v, const fs_field *p, const int *box, double *out)
+{
+    FS_REQUIRE(ctx && out, "null argument");
+    FS_FIELD(v, 2); FS_FIELD(p, 1);
+    if (ctx->capturing || ctx->tape_rec) { set_error("flow stats during graph capture / tape recording"); return FS_ERR_STATE; }
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    int b[4] = {0, 0, 0, 0};      // empty box: no force
+    if (box) {
+        FS_REQUIRE(0 <= box[0] && box[0] <= box[2] && box[2] <= ctx->X && 0 <= box[1] && box[1] <= box[3] && box[3] <= ctx->Y,
+                   "body box must satisfy 0 <= x0 <= x1 <= X and 0 <= y0 <= y1 <= Y");
+        for (int k = 0; k < 4; ++k) b[k] = box[k];
+    }
+    const int row_begin = ctx->halo, row_end = ctx->halo + ctx->nyl;
+    // rows per workgroup: doubled from STATS_G while the grid keeps >= 2048 workgroups (8 per CU), at most STATS_ROWS
+    const int nx = (ctx->X + 255) / 256, ny = row_end - row_begin;
+    int rpw = STATS_G;
+    while (rpw < STATS_ROWS && (size_t)nx * ((ny + 2 * rpw - 1) / (2 * rpw)) >= 2048) rpw *= 2;
+    const dim3 grid(nx, (ny + rpw - 1) / rpw);
+    const size_t nblocks = (size_t)grid.x * grid.y;
+    if (nblocks + 1 > ctx->stats_cap) {
+        if (ctx->d_stats) { FS_HIP(hipStreamSynchronize(ctx->stream)); FS_HIP(hipFree(ctx->d_stats)); ctx->d_stats = nullptr; ctx->stats_cap = 0; }
+        FS_HIP(hipMalloc(&ctx->d_stats, (nblocks + 1) * STATS_N * sizeof(double)));
+        ctx->stats_cap = nblocks + 1;
+    }
+    double *partial = ctx->d_stats, *total = ctx->d_stats + nblocks * STATS_N;
+    int rc;
+    FS_DISPATCH(ctx, {
+        rc = launch(ctx, "flow_stats", [=] {
+            FS_KLAUNCH((k_flow_stats<T>), grid, dim3(256), 0, ctx->stream, ctx->grid(), row_begin, row_end, rpw, dx, b[0], b[1], b[2], b[3],
+                       (const T *)v->d, (const T *)p->d, partial);
+            FS_KLAUNCH((k_flow_stats_final), dim3(1), dim3(256), 0, ctx->stream, (const double *)partial, (int)nblocks, total);
+        });
+    })
+    if (rc) return rc;
+    FS_HIP(hipMemcpyAsync(out, total, STATS_N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
     return FS_OK;
 }
 

@@ -272,6 +272,26 @@ def get_boundary_condition(num, resolution, *, enable_dye):
     return cv.finish(enable_dye)
 
 
+def default_body_box(num, resolution):
+    """Body box (x0, y0, x1, y1), global cells, half-open, for the force diagnostics of FluidSimulator.flow_stats: the bounding box of the
+    scene's obstacle cells grown by one cell of fluid on each side, kept off the channel walls (the two floor and ceiling rows):
+      1: the cylinder;  3: all the random cylinders together;  5: the staggered array of square posts (right of the slotted mid wall;
+      the inlet block and the mid wall are not in it);  6: the image obstacle.
+    Scenes 2 and 4 have no body: ValueError."""
+    if num not in (1, 3, 5, 6):
+        raise ValueError(f"scene {num} has no body to measure a force on (scenes 1, 3, 5 and 6 have one)")
+    _, mask, _ = create_scene_arrays(num, resolution)
+    X, Y = mask.shape
+    solid = mask == WALL
+    solid[:, :2] = solid[:, Y - 2:] = False         # floor and ceiling
+    x_lo = X // 2 + X // 64 if num == 5 else 0      # scene 5: right of the mid wall (_scene5)
+    solid[:x_lo] = False
+    xs, ys = np.nonzero(solid)
+    if xs.size == 0:
+        raise ValueError(f"scene {num} at resolution {resolution} has no obstacle cell")
+    return (max(int(xs.min()) - 1, x_lo), max(int(ys.min()) - 1, 2), min(int(xs.max()) + 2, X), min(int(ys.max()) + 2, Y - 2))
+
+
 def _make_creator(num):
     def create(resolution, *, enable_dye):
         return get_boundary_condition(num, resolution, enable_dye=enable_dye)

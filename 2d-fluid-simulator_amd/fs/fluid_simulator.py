@@ -5,6 +5,8 @@
 `pressure_updater=` is an extension (the reference hard-codes RB-SOR): ("jacobi", n_iter) or
 ("rbsor", omega, n_iter) or a ready PressureUpdater factory.
 """
+import math
+
 from .advection import advect_kk_scheme, advect_upwind
 from .boundary_condition import get_boundary_condition
 from .pressure_updater import JacobiPressureUpdater, RedBlackSorPressureUpdater
@@ -40,6 +42,24 @@ def _compose(num, resolution, dt, dx, re, vor_eps, scheme, enable_dye, pressure_
     cls = DyeMacSolver if enable_dye else MacSolver
     adv = advect_upwind if scheme == "upwind" else advect_kk_scheme
     return cls(bc, pu, adv, dt, dx, re, vc)
+
+
+def derive_flow_stats(raw, dx, dt, with_force):
+    """The public diagnostics from the slots of runtime.DeviceBase.flow_stats (see FluidSimulator.flow_stats)."""
+    n = raw["fluid_cells"]
+    out = {
+        "kinetic_energy": 0.5 * dx * dx * raw["sum_s2"],
+        "enstrophy": 0.5 * dx * dx * raw["sum_om2"],
+        "max_speed": math.sqrt(raw["max_s2"]),          # (sums of squares and maxima are >= 0, NaN or +Inf: math.sqrt passes NaN / Inf on)
+        "cfl": raw["max_a"] * dt / dx,
+        "div_rms": math.sqrt(raw["sum_dv2"] / n) if n > 0 else 0.0,
+        "div_max": raw["max_abs_dv"],
+        "nonfinite": int(raw["nonfinite"]),
+        "fluid_cells": int(n),
+    }
+    if with_force:
+        out["force_x"], out["force_y"] = raw["force_x"], raw["force_y"]
+    return out
 
 
 class FluidSimulator:
@@ -217,6 +237,21 @@ class FluidSimulator:
     def field_to_numpy(self):
         fields = self._solver.get_fields()
         return {"v": fields[0].to_numpy(), "p": fields[1].to_numpy()}
+
+    # -- diagnostics (new; the reference's user watches the window instead) ----------------------------------------------
+    def flow_stats(self, body_box=None):
+        """Scalar diagnostics of the fields get_fields() returns, computed on the GPU in one pass (include/fs_hip.h fs_flow_stats):
+          kinetic_energy = 0.5 dx^2 sum_F (u^2 + w^2)     enstrophy = 0.5 dx^2 sum_F omega^2 (central differences)
+          max_speed, cfl = max_F (|u| + |w|) dt / dx     div_rms, div_max: central-difference divergence over the fluid cells
+          nonfinite: not-wall cells whose u, w or p is NaN or +-Inf (a blown-up run also shows NaN / Inf in the other values)
+          fluid_cells; and with body_box = (x0, y0, x1, y1) (global cells, half-open; fs.boundary_condition.default_body_box gives one
+          per obstacle scene) force_x / force_y: the PRESSURE force per unit depth on the wall cells inside the box, summed over the faces
+          they share with fluid cells.  The viscous part is omitted (negligible at the Reynolds numbers of the scenes).
+        Changes nothing the trajectory depends on: no field, no swap, no captured graph (a deferred limit_field of v stays deferred unless
+        it would change a cell, runtime.DeviceBase.flow_stats).  Not allowed during a graph capture."""
+        s = self._solver
+        v, p = s.get_fields()[:2]
+        return derive_flow_stats(self._dev.flow_stats(s.dx, v, p, body_box), s.dx, s.dt, body_box is not None)
 
     # -- visualisation (fs/fluid_simulator.py:22-58): device kernels; like the reference these return the image FIELD ----
     def get_norm_field(self):

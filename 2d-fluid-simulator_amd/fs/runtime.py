@@ -834,6 +834,45 @@ class DeviceBase:
         s, n = self._p_residual(dt, dx, p._h, vc._h)
         return self._p_allreduce([s, n]) if self.nranks > 1 else (s, n)
 
+    # slots of fs_flow_stats (include/fs_hip.h), in ABI order; those of _STAT_MAX combine by maximum, the others by sum
+    STAT_SLOTS = ("fluid_cells", "sum_s2", "sum_om2", "sum_dv2", "max_s2", "max_a", "max_abs_dv", "nonfinite", "force_x", "force_y")
+    _STAT_MAX = (4, 5, 6)
+
+    def flow_stats(self, dx, v, p, box=None):
+        """{slot: value} of fs_flow_stats over the GLOBAL grid (include/fs_hip.h): kinetic-energy, enstrophy and divergence sums, maxima,
+        the non-finite count and the pressure force on the wall cells of `box` = (x0, y0, x1, y1) in global cells (half-open; None: no force).
+        Across slabs the sums add and the maxima take the maximum; a NaN maximum on any rank makes the global one NaN.  Alters no field.
+        A limit_field v still owes (limit_field) stays deferred while the buffer's flag is down - the pass would change no cell, and the
+        solver's buffers keep the state their captured graphs expect; with the flag up it is launched first, as a download would.  Not
+        allowed during a graph capture (FsError; the library refuses as well)."""
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("flow_stats during a graph capture: the statistics are a download (sample between captures / replays)")
+        # Skipping the owed pass relies on the flag being conservative - up whenever a stored cell may have x*x + y*y > 99 (csrc/fs_device.h,
+        # "hot" flag: raised by every kernel that stores such a velocity, by uploads and unpacked ghost rows).  A deferred pass has
+        # limit * limit > 99.01 (limit_field), and fs_limit_field exits on the same flag words fs_field_hot reads: with the flag down the
+        # pass changes no cell.  Whoever changes the flag's rules must keep this true or flush unconditionally here.
+        if v.pending_limit is not None and self.field_hot(v):
+            self.flush_limit(v)
+        if self.nranks > 1:
+            stale = [f for f in (v, p) if f.valid < 1]
+            if stale:
+                self.exchange_many(stale)
+        if box is not None:
+            box = tuple(int(b) for b in box)
+            if len(box) != 4:
+                raise ValueError("box must be (x0, y0, x1, y1)")
+        s = [float(x) for x in self._p_flow_stats(dx, v._h, p._h, box)]
+        if self.nranks > 1:
+            mx = [s[k] for k in self._STAT_MAX]
+            sums = [k for k in range(len(s)) if k not in self._STAT_MAX]
+            tot = self._p_allreduce([s[k] for k in sums] + [1.0 if m != m else 0.0 for m in mx])     # (+ per maximum: ranks that hold NaN)
+            for k, x in zip(sums, tot):
+                s[k] = x
+            top = self._p_max_over_ranks([0.0 if m != m else m for m in mx])      # (a plain maximum would drop NaN: it is carried by the sum)
+            for n, (k, x) in enumerate(zip(self._STAT_MAX, top)):
+                s[k] = float("nan") if tot[len(sums) + n] > 0 else float(x)
+        return dict(zip(self.STAT_SLOTS, s))
+
 
 class Device(DeviceBase):
     """DeviceBase bound to libfs_hip.so (HIP kernels on one MI355X; RCCL for the ghost rows)."""
@@ -985,6 +1024,12 @@ class Device(DeviceBase):
         s, n = ctypes.c_double(), ctypes.c_double()
         _lib.call("fs_poisson_residual", self._ctx, dt, dx, ph, vh, ctypes.byref(s), ctypes.byref(n))
         return s.value, n.value
+
+    def _p_flow_stats(self, dx, vh, ph, box):
+        out = (ctypes.c_double * len(self.STAT_SLOTS))()
+        b = None if box is None else (ctypes.c_int * 4)(*box)
+        _lib.call("fs_flow_stats", self._ctx, dx, vh, ph, b, out)
+        return list(out)
 
     def _p_allreduce(self, values):
         arr = (ctypes.c_double * len(values))(*values)

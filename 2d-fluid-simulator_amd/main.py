@@ -6,6 +6,8 @@ The reference opens a GGUI window and steps forever; here the loop runs `--steps
   * write the visualisation the window would show (`-vis`, main.py:94-107) as PNG frames every `--frame-every` steps
   * write / read a full-state checkpoint (new: the reference cannot resume - its dump lacks the CIP gradient
     fields and the `next` buffers).
+  * sample scalar flow diagnostics (energy, enstrophy, CFL, divergence, non-finite cells, pressure force on a body) into a CSV
+    every `--stats-every` steps, and stop at the first non-finite sample (`--stop-on-nonfinite`, exit status 3).
 """
 import argparse
 import os
@@ -47,6 +49,14 @@ def build_parser():
     p.add_argument("--out", type=str, default="output")
     p.add_argument("--save-state", type=str, default=None, help="write a full-state checkpoint (.npz) after the last step")
     p.add_argument("--load-state", type=str, default=None, help="resume from a checkpoint written by --save-state")
+    p.add_argument("--stats-every", type=int, default=0,
+                   help="sample the flow diagnostics (FluidSimulator.flow_stats) at the first step and every N steps into --stats-file")
+    p.add_argument("--stats-file", type=str, default=None, help="CSV of the samples: step,time,<keys> (default: <out>/stats.csv)")
+    p.add_argument("--body", type=str, default=None,
+                   help="x0,y0,x1,y1 (global cells, half-open): add the pressure force on the wall cells in this box to the samples; "
+                        "'auto': the scene's obstacle (scenes 1, 3, 5, 6; fs.boundary_condition.default_body_box)")
+    p.add_argument("--stop-on-nonfinite", action="store_true",
+                   help="exit with status 3 at the first sample that finds NaN / Inf in v or p")
     return p
 
 
@@ -95,6 +105,47 @@ def frame(sim, vis):
     return sim.get_dye_field().to_numpy()
 
 
+class StatsWriter:
+    """--stats-every: one CSV row per sample (step, simulated time, the keys of FluidSimulator.flow_stats; floats at full precision)."""
+
+    def __init__(self, sim, path, dt, box, stop_on_nonfinite):
+        self.sim, self.dt, self.box, self.stop = sim, dt, box, stop_on_nonfinite
+        path.parent.mkdir(parents=True, exist_ok=True)
+        self.fh = open(path, "w")
+        self.keys = None
+
+    def sample(self, step):
+        """Write one row -> the number of non-finite cells found."""
+        d = self.sim.flow_stats(self.box)
+        if self.keys is None:
+            self.keys = list(d)
+            self.fh.write(",".join(["step", "time"] + self.keys) + "\n")
+        self.fh.write(",".join([str(step), repr(step * self.dt)] + [repr(d[k]) for k in self.keys]) + "\n")
+        self.fh.flush()
+        return d["nonfinite"]
+
+    def close(self):
+        self.fh.close()
+
+
+def _body_box(parser, spec, num, res):
+    if spec is None:
+        return None
+    if spec == "auto":
+        from fs.boundary_condition import default_body_box
+        try:
+            return default_body_box(num, res)
+        except ValueError as e:
+            parser.error(f"--body auto: {e}")
+    try:
+        box = tuple(int(x) for x in spec.split(","))
+    except ValueError:
+        box = ()
+    if len(box) != 4 or not (0 <= box[0] <= box[2] <= 2 * res and 0 <= box[1] <= box[3] <= res):
+        parser.error(f"--body {spec}: expected x0,y0,x1,y1 with 0 <= x0 <= x1 <= {2 * res} and 0 <= y0 <= y1 <= {res}, or 'auto'")
+    return box
+
+
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
@@ -113,6 +164,9 @@ def main(argv=None):
             _find_obstacle_image()
         except FileNotFoundError as e:      # the obstacle image is an asset of the reference repository and is not shipped here
             parser.error(f"-bc 6: {e}")
+    if (args.body is not None or args.stop_on_nonfinite or args.stats_file) and args.stats_every <= 0:
+        parser.error("--body, --stats-file and --stop-on-nonfinite need --stats-every N")
+    box = _body_box(parser, args.body, args.boundary_condition, res)
     print(f"Boundary Condition: {args.boundary_condition}\ndt: {dt}\nRe: {args.reynolds_num}\nResolution: {res}\n"
           f"Scheme: {args.advection_scheme}\nVorticity confinement: {vor_eps}")
     fs.runtime.init(gpu=args.gpu, dtype="f64" if args.f64 else "f32")
@@ -121,8 +175,21 @@ def main(argv=None):
     out = Path(args.out)
     step0 = load_state(sim, args.load_state) if args.load_state else 0
     dev = sim._solver._bc.device
+    stats = None
+    if args.stats_every > 0:
+        stats = StatsWriter(sim, Path(args.stats_file) if args.stats_file else out / "stats.csv", dt, box, args.stop_on_nonfinite)
+
+    def sample(step):
+        if stats.sample(step) > 0 and stats.stop:
+            stats.close()
+            print(f"step {step}: non-finite values (NaN / Inf) in v or p; stopping (--stop-on-nonfinite)", file=sys.stderr)
+            dev.close()
+            sys.exit(3)
+
     t0 = time.perf_counter()
     step, last = step0, step0 + args.steps
+    if stats:
+        sample(step)
     while step < last:
         if args.frame_every and step % args.frame_every == 0:
             from PIL import Image
@@ -135,8 +202,12 @@ def main(argv=None):
             nxt = min(nxt, (step // args.frame_every + 1) * args.frame_every)
         if args.dump_every:
             nxt = min(nxt, (step // args.dump_every + 1) * args.dump_every)
+        if stats:
+            nxt = min(nxt, (step // args.stats_every + 1) * args.stats_every)
         sim.run(nxt - step, graph=args.graph)
         step = nxt
+        if stats and step % args.stats_every == 0:
+            sample(step)
         if args.dump_every and step % args.dump_every == 0:
             out.mkdir(exist_ok=True)
             np.savez(str(out / f"step_{step:06}.npz"), **sim.field_to_numpy())
@@ -145,6 +216,8 @@ def main(argv=None):
     print(f"{args.steps} steps in {el:.3f} s = {args.steps / el:.1f} steps/s")
     if args.save_state:
         save_state(sim, args.save_state, step0 + args.steps)
+    if stats:
+        stats.close()
     dev.close()
 
 

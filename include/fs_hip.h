@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 9
+#define FS_ABI_VERSION 10
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -254,6 +254,25 @@ int fs_rbsor_halfsweep_src(fs_ctx *ctx, double omega, int parity, fs_field *pn, 
  * (predict_p(p) - p)^2 and the cell count, accumulated in double.  Does not alter any field.       */
 int fs_poisson_residual(fs_ctx *ctx, double dt, double dx, const fs_field *p, const fs_field *vc,
                         double *sum_sq, double *count);
+
+/* Flow diagnostics (new; the reference only draws the flow): ONE pass over the owned rows of v, p and the mask -> this rank's
+ * FS_FLOW_NSTAT partials in `out` (cross-rank combination is the caller's: sums add, maxima take the maximum and propagate NaN).
+ * Arithmetic in double on the stored values; F = fluid cells (mask 0), N = not-wall cells (mask != 1); u = v[..., 0], w = v[..., 1];
+ * u(i, j) etc. are clamped samples (fs/differentiation.py:4-9 sample()), stored wall-cell values enter the stencils as they are:
+ *   s2 = u*u + w*w    om = ((w(i+1,j) - w(i-1,j)) - (u(i,j+1) - u(i,j-1))) / (2.0*dx)
+ *   a = fabs(u) + fabs(w)    dv = ((u(i+1,j) - u(i-1,j)) + (w(i,j+1) - w(i,j-1))) / (2.0*dx)
+ *   slot 0 fluid_cells   sum   count of F          slot 5 max_a       max   max_F a
+ *   slot 1 sum_s2        sum   sum_F s2            slot 6 max_abs_dv  max   max_F |dv|
+ *   slot 2 sum_om2       sum   sum_F om^2          slot 7 nonfinite   sum   cells of N whose u, w or p is NaN or +-Inf
+ *   slot 3 sum_dv2       sum   sum_F dv^2          slot 8 force_x     sum   pressure force per unit depth on the wall cells of the box
+ *   slot 4 max_s2        max   max_F s2            slot 9 force_y     sum   (0 without a box)
+ * Force: for each wall cell inside the half-open box [x0, x1) x [y0, y1) (`box` = x0, y0, x1, y1 in global cells, or NULL) and each of
+ * its 4 neighbours that is fluid (neighbours beyond the domain edge do not exist): fluid at (i+1, j): force_x -= p(i+1,j)*dx;
+ * (i-1, j): force_x += p(i-1,j)*dx; (i, j+1): force_y -= p(i,j+1)*dx; (i, j-1): force_y += p(i,j-1)*dx.  Viscous stress is omitted.
+ * Maxima start at 0 and propagate NaN.  On a slab, v and p must be valid one ghost row deep.  Deterministic (no atomics: two-stage
+ * reduction in a fixed order); refused with FS_ERR_STATE during graph capture / tape recording.  Does not alter any field.          */
+#define FS_FLOW_NSTAT 10
+int fs_flow_stats(fs_ctx *ctx, double dx, const fs_field *v, const fs_field *p, const int *box, double *out);
 
 /* ---- pointwise -------------------------------------------------------------------------------- */
 /* limit_field   fs/solver.py:38-43 ;  clamp_field   fs/solver.py:46-49                           */
