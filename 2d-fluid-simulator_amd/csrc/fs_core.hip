@@ -672,6 +672,9 @@ int fs_destroy(fs_ctx *ctx)
     for (fs_field *f : ctx->fields) { if (f->d) hipFree(f->d); if (f->hot) hipFree(f->hot); delete f; }
     for (fs_field *f : ctx->deferred_free) { if (f->d) hipFree(f->d); if (f->hot) hipFree(f->hot); delete f; }
     ctx->fields.clear();
+    for (fs_history *h : ctx->histories) history_release(h);
+    for (fs_history *h : ctx->deferred_hist) history_release(h);
+    ctx->histories.clear();
     if (ctx->d_mask) hipFree(ctx->d_mask);
     if (ctx->d_bc_const) hipFree(ctx->d_bc_const);
     if (ctx->d_bc_dye) hipFree(ctx->d_bc_dye);
@@ -1426,6 +1429,8 @@ int fs_graph_end(fs_ctx *ctx, int *graph_id)
     const hipError_t ec = hipStreamEndCapture(ctx->stream, &g);
     for (fs_field *f : ctx->deferred_free) field_release(f);          // fields dropped while the capture was open (fs_field_free)
     ctx->deferred_free.clear();
+    for (fs_history *h : ctx->deferred_hist) history_release(h);      // likewise history rings (fs_history_free)
+    ctx->deferred_hist.clear();
     if (ec != hipSuccess) return hip_fail(ec, "hipStreamEndCapture", __FILE__, __LINE__);
     hipGraphExec_t ex = nullptr;
     hipError_t e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);

@@ -18,6 +18,7 @@
 #include "fs_rbpair.h"
 #include "fs_jquad.h"
 #include "fs_k34n.h"
+#include "fs_history.h"
 
 namespace fs {
 
@@ -126,6 +127,8 @@ struct fs_ctx {
     fs::Comm *comm = nullptr;
     std::set<fs_field *> fields;  // live fields, released with the context
     std::vector<fs_field *> deferred_free;   // fs_field_free during a hipGraph capture: released when the capture ends
+    std::set<fs_history *> histories;        // live history rings (fs_history_create), released with the context
+    std::vector<fs_history *> deferred_hist; // fs_history_free during a hipGraph capture: released when the capture ends
     // tuning knobs (env FS_MARCH=0: one-cell-per-lane kernels only)
     bool use_march = true;
     bool use_pairs = true;     // lanes of 2 cells: even widths (every `res`); use_march: the quad kernels, X % 4 == 0
@@ -166,7 +169,21 @@ struct fs_field {
     unsigned *hot = nullptr;   // device words: [0] "may hold a speed above 9.95" (fs_device.h; meaningful for 2-channel fields), [1], [2] the same, raised by the op list of a k_velocity_bc_limit launch of parity 0 / 1
 };
 
+// per-step history ring (fs_history_*, fs_history.h): probe and face lists of this context's owned rows, the ring and its device counters
+struct fs_history {
+    fs_ctx *ctx = nullptr;
+    int np = 0, nf = 0, cap = 0, every = 1, threads = 256;
+    int nparts = 0;                 // workgroups of the split face sum (HIST_SPLIT; 0: the record launch sums the faces)
+    double *d_partial = nullptr;    // [nparts][2]
+    fs::HistProbe *d_probes = nullptr;
+    fs::HistFace *d_faces = nullptr;
+    double *d_ring = nullptr;       // [cap][2 + 3 np]
+    long long *d_state = nullptr;   // [HIST_STATE]
+};
+
 namespace fs {
+
+void history_release(fs_history *h);      // fs_pressure.hip
 
 // HIP-event pair around a span of stream work that is not one kernel launch (fs_api.hip; the ghost-row exchange chain of fs_comm.hip)
 ProfRec prof_span_begin(fs_ctx *c, const char *name, hipStream_t stream);

@@ -1,9 +1,22 @@
 // fs_pressure.hip - C-ABI entry points of the pressure kernels: Jacobi sweeps (single, lazily bounded pairs / quads / finishing pass), red-black
-// SOR (half sweeps, one fused iteration, two iterations per pass), the Poisson source pair, the residual and the flow diagnostics.
+// SOR (half sweeps, one fused iteration, two iterations per pass), the Poisson source pair, the residual, the flow diagnostics and the
+// per-step history ring.
 #include "fs_launch.h"
 #include "fs_stats.h"
 
 static_assert(fs::STATS_N == FS_FLOW_NSTAT, "fs_stats.h and include/fs_hip.h disagree on the slots");
+
+namespace fs {
+void history_release(fs_history *h)
+{
+    if (h->d_probes) hipFree(h->d_probes);
+    if (h->d_faces) hipFree(h->d_faces);
+    if (h->d_ring) hipFree(h->d_ring);
+    if (h->d_state) hipFree(h->d_state);
+    if (h->d_partial) hipFree(h->d_partial);
+    delete h;
+}
+}  // namespace fs
 
 using namespace fs;
 
@@ -402,6 +415,109 @@ int fs_flow_stats(fs_ctx *ctx, double dx, const fs_field *v, const fs_field *p, 
     if (rc) return rc;
     FS_HIP(hipMemcpyAsync(out, total, STATS_N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_history_create(fs_ctx *ctx, int npoints, const int *points, int nfaces, const int *faces, int capacity, int every, fs_history **out)
+{
+    FS_REQUIRE(ctx && out, "null argument");
+    FS_REQUIRE(npoints >= 0 && nfaces >= 0 && (points || npoints == 0) && (faces || nfaces == 0), "bad point / face list");
+    FS_REQUIRE(capacity >= 1 && every >= 1, "capacity and every must be >= 1");
+    FS_REQUIRE((2 + 3 * (long long)npoints) * capacity < (1LL << 40), "ring too large");
+    if (ctx->capturing || ctx->tape_rec) { set_error("history create during graph capture / tape recording"); return FS_ERR_STATE; }
+    // a probe / face outside the owned rows would read a ghost row (stale between exchanges) or count a face twice across slabs
+    const int jo = ctx->y0, je = ctx->y0 + ctx->nyl;
+    auto local = [&](int x, int y) -> long long { return (long long)(y - ctx->y0 + ctx->halo) * ctx->P + x; };      // row-major element of (x, y)
+    std::vector<HistProbe> hp(npoints);
+    for (int k = 0; k < npoints; ++k) {
+        const int x = points[2 * k], y = points[2 * k + 1];
+        FS_REQUIRE(0 <= x && x < ctx->X && jo <= y && y < je, "probe outside this context's owned rows");
+        const int j = y - ctx->y0 + ctx->halo;
+        hp[k].u = (unsigned)(((long long)j * 2 + 0) * ctx->P + x);      // fs_device.h idx<2>
+        hp[k].w = (unsigned)(((long long)j * 2 + 1) * ctx->P + x);
+        hp[k].p = (unsigned)local(x, y);
+    }
+    std::vector<HistFace> hf(nfaces);
+    for (int k = 0; k < nfaces; ++k) {
+        const int x = faces[3 * k], y = faces[3 * k + 1], d = faces[3 * k + 2];
+        FS_REQUIRE(0 <= x && x < ctx->X && jo <= y && y < je, "face outside this context's owned rows");
+        FS_REQUIRE(0 <= d && d <= 3, "face direction must be 0 (+x), 1 (-x), 2 (+y) or 3 (-y)");
+        hf[k].p = (unsigned)local(x, y);
+        hf[k].dir = d;
+    }
+    FS_HIP(hipSetDevice(ctx->device));
+    fs_history *h = new fs_history();
+    h->ctx = ctx; h->np = npoints; h->nf = nfaces; h->cap = capacity; h->every = every;
+    h->nparts = nfaces > HIST_SPLIT ? (nfaces + HIST_FACES_PER_WG - 1) / HIST_FACES_PER_WG : 0;
+    const size_t ring = (size_t)capacity * (2 + 3 * (size_t)npoints) * sizeof(double);
+    hipError_t e = hipMalloc(&h->d_state, HIST_STATE * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc(&h->d_ring, ring);
+    if (e == hipSuccess && h->nparts) e = hipMalloc(&h->d_partial, 2 * (size_t)h->nparts * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&h->d_probes, std::max<size_t>(1, hp.size()) * sizeof(HistProbe));
+    if (e == hipSuccess) e = hipMalloc(&h->d_faces, std::max<size_t>(1, hf.size()) * sizeof(HistFace));
+    if (e == hipSuccess) e = hipMemsetAsync(h->d_state, 0, HIST_STATE * sizeof(long long), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->d_ring, 0, ring, ctx->stream);
+    if (e == hipSuccess && npoints) e = hipMemcpyAsync(h->d_probes, hp.data(), hp.size() * sizeof(HistProbe), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && nfaces) e = hipMemcpyAsync(h->d_faces, hf.data(), hf.size() * sizeof(HistFace), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { history_release(h); return hip_fail(e, "fs_history_create", __FILE__, __LINE__); }
+    ctx->histories.insert(h);
+    *out = h;
+    return FS_OK;
+}
+
+int fs_history_record(fs_ctx *ctx, fs_history *h, double dx, double limit, const fs_field *v, const fs_field *p)
+{
+    FS_REQUIRE(ctx && h, "null argument");
+    FS_REQUIRE(h->ctx == ctx && ctx->histories.count(h), "history from another context or freed");
+    FS_FIELD(v, 2); FS_FIELD(p, 1);
+    // everything the launch needs is in `h` and the fields: no allocation, copy or synchronisation here (the closure is captured / taped)
+    const HistProbe *pr = h->d_probes;
+    const HistFace *fc = h->d_faces;
+    const int np = h->np, nf = h->nf, every = h->every, cap = h->cap, threads = h->threads, nparts = h->nparts;
+    double *ring = h->d_ring, *partial = h->d_partial;
+    long long *state = h->d_state;
+    FS_DISPATCH(ctx, {
+        return launch(ctx, "history_record", [=] {
+            if (nparts)
+                FS_KLAUNCH((k_history_faces<T>), dim3(nparts), dim3(HIST_FACES_PER_WG), 0, ctx->stream, (const T *)p->d, fc, nf, dx, every, cap,
+                           (const long long *)state, partial);
+            FS_KLAUNCH((k_history_record<T>), dim3(1), dim3(threads), 0, ctx->stream, (const T *)v->d, (const T *)p->d, pr, np, fc, nf,
+                       (const double *)partial, nparts, dx, limit, every, cap, ring, state);
+        });
+    })
+}
+
+int fs_history_read(fs_ctx *ctx, fs_history *h, double *out, int max_records, int *n_records, long long *launches, int *dropped)
+{
+    FS_REQUIRE(ctx && h && n_records, "null argument");
+    FS_REQUIRE(h->ctx == ctx && ctx->histories.count(h), "history from another context or freed");
+    if (ctx->capturing || ctx->tape_rec) { set_error("history read during graph capture / tape recording"); return FS_ERR_STATE; }
+    FS_HIP(hipSetDevice(ctx->device));
+    long long st[HIST_STATE];
+    FS_HIP(hipMemcpyAsync(st, h->d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    *n_records = (int)st[1];
+    if (launches) *launches = st[0];
+    if (dropped) *dropped = (int)st[2];
+    if (!out) return FS_OK;
+    FS_REQUIRE(max_records >= st[1], "out holds fewer records than the ring");
+    if (st[1] > 0)
+        FS_HIP(hipMemcpyAsync(out, h->d_ring, (size_t)st[1] * (2 + 3 * (size_t)h->np) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipMemsetAsync(h->d_state + 1, 0, 2 * sizeof(long long), ctx->stream));       // written, dropped; the launch count runs on
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_history_free(fs_ctx *ctx, fs_history *h)
+{
+    if (!h) return FS_OK;
+    FS_REQUIRE(ctx && h->ctx == ctx && ctx->histories.count(h), "history from another context or freed");
+    ctx->histories.erase(h);
+    if (ctx->capturing) { ctx->deferred_hist.push_back(h); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
+    history_release(h);
     return FS_OK;
 }
 

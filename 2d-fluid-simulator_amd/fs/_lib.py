@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FS_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libfs_hip.so")     # FS_LIB: A/B builds (tools/)
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _lib = None
 
@@ -78,6 +78,10 @@ _PROTOS = {
     "fs_rbsor_halfsweep_src": [_c_vp, _c_dbl, _c_int, _c_vp, _c_vp, _c_vp] + _ROWS,
     "fs_poisson_residual": [_c_vp, _c_dbl, _c_dbl, _c_vp, _c_vp, _P(_c_dbl), _P(_c_dbl)],
     "fs_flow_stats": [_c_vp, _c_dbl, _c_vp, _c_vp, _P(_c_int), _P(_c_dbl)],
+    "fs_history_create": [_c_vp, _c_int, _P(_c_int), _c_int, _P(_c_int), _c_int, _c_int, _P(_c_vp)],
+    "fs_history_record": [_c_vp, _c_vp, _c_dbl, _c_dbl, _c_vp, _c_vp],
+    "fs_history_read": [_c_vp, _c_vp, _P(_c_dbl), _c_int, _P(_c_int), _P(ctypes.c_longlong), _P(_c_int)],
+    "fs_history_free": [_c_vp, _c_vp],
     "fs_limit_field": [_c_vp, _c_dbl, _c_vp] + _ROWS,
     "fs_clamp_field": [_c_vp, _c_dbl, _c_dbl, _c_vp] + _ROWS,
     "fs_cip_advect_dye_clamped": [_c_vp, _c_dbl, _c_dbl] + [_c_vp] * 7 + _ROWS,

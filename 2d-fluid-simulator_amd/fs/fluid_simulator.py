@@ -7,8 +7,11 @@
 """
 import math
 
+import numpy as np
+
 from .advection import advect_kk_scheme, advect_upwind
 from .boundary_condition import get_boundary_condition
+from .history import Recorder, body_faces, check_probes
 from .pressure_updater import JacobiPressureUpdater, RedBlackSorPressureUpdater
 from .solver import CipMacSolver, DyeCipMacSolver, DyeMacSolver, MacSolver
 from .vorticity_confinement import VorticityConfinement
@@ -76,9 +79,23 @@ class FluidSimulator:
         self._eager_seen = False   # one step has run outside a capture (the library's compact launch lists exist)
         self._pending_after_step = (False, False)
         self._since_hot_check = 0
+        self._recorder = None      # fs.history.Recorder while record_history() is on
+        self._last_recorder = None  # ... and after stop_history(): what history() still returns
+
+    def _update(self):
+        """One solver step, then the history record if a recorder is attached: what step(), the periods capture_period() captures and the
+        slab periods tape_period() logs all run (so a graph or tape holds the record exactly when _signature() says so)."""
+        self._solver.update()
+        rec = self._recorder
+        if rec is not None:
+            if rec.room() <= 0 and not getattr(self._dev, "capturing", False):
+                rec.drain()          # (eager steps beyond the ring: run() drains between its chunks instead)
+            v, p = self._solver.get_fields()[:2]
+            self._dev.history_record(rec.hist, self._solver.dx, v, p)
+            rec.issued += 1
 
     def step(self):
-        self._solver.update()
+        self._update()
         self._eager_seen = True        # (captures call the solver directly: see capture_period)
         self._pending_after_step = self._limit_pending()
         self._since_hot_check += 1
@@ -125,6 +142,8 @@ class FluidSimulator:
                     sig.append((f.serial, f.user_data, f.static_id, f.pending_limit, f.pending_clamp, f.bc_parity))      # (pending_limit: a deferred limit_field, runtime.DeviceBase.limit_field)
         for spare in (getattr(s, "_v_spare", None), getattr(s, "_dye_spare", None)) + tuple(getattr(s.pressure_updater, "_spare", None) or ()):
             sig.append((spare.serial, spare.static_id, spare.bc_parity) if spare is not None else 0)
+        if self._recorder is not None:
+            sig.append(self._recorder.token)        # (graphs / tapes with the record launch in them are never replayed without it, or vice versa)
         return tuple(sig)
 
     _LONG_STEPS = 16     # steps per long-form graph (capture_period)
@@ -137,7 +156,26 @@ class FluidSimulator:
 
         A graph is valid for one phase of the solver's buffer rotation (self._signature()).  A chunk that is not a multiple of the
         period ends in another phase; graphs are therefore cached per phase (at most `period` of them exist) instead of being
-        re-captured - and leaked - chunk after chunk, and a capture is only started when the chunk is long enough to pay for it."""
+        re-captured - and leaked - chunk after chunk, and a capture is only started when the chunk is long enough to pay for it.
+
+        With a history recorder attached (record_history) the run is cut into chunks that fit the recorder's ring, which is drained between
+        them: no record is ever dropped."""
+        rec = self._recorder
+        if rec is None:
+            return self._run_chunk(nsteps, graph)
+        while nsteps > 0:
+            m = min(nsteps, rec.room())
+            if m <= 0:
+                rec.drain()
+                continue
+            self._run_chunk(m, graph)
+            nsteps -= m
+
+    def _replayed(self, steps):
+        if self._recorder is not None:
+            self._recorder.issued += steps
+
+    def _run_chunk(self, nsteps, graph):
         dev = self._dev
         self._check_hot()
         if graph and dev.nranks > 1 and nsteps >= 24:
@@ -157,6 +195,7 @@ class FluidSimulator:
             if tape is not None:
                 per = tape["nsteps"]
                 dev.replay_tape(tape, nsteps // per)
+                self._replayed(nsteps - nsteps % per)
                 self._steps += nsteps - nsteps % per
                 nsteps %= per
         if not graph or dev.nranks > 1 or not hasattr(dev, "capture"):
@@ -176,8 +215,10 @@ class FluidSimulator:
             self._graph, self._graph_long = (self._signature(), gid, period), long
             if long is not None:
                 dev.replay(long[0], nsteps // long[1])
+                self._replayed(nsteps - nsteps % long[1])
                 nsteps %= long[1]
             dev.replay(gid, nsteps // period)
+            self._replayed(nsteps - nsteps % period)
             nsteps %= period
         for _ in range(nsteps):
             self.step()
@@ -217,14 +258,14 @@ class FluidSimulator:
             if done + period > budget:
                 break
             sig = self._signature()
-            gid = dev.capture(lambda: [self._solver.update() for _ in range(period)])       # host-side swaps happen, nothing executes
+            gid = dev.capture(lambda: [self._update() for _ in range(period)])       # host-side swaps happen, nothing executes
             back = self._signature() == sig
             dev.replay(gid, 1)                                                    # now the captured steps run once
             done += period
             if back:
                 long, reps = None, -(-self._LONG_STEPS // period)
                 if reps > 1 and done + reps * period <= budget:
-                    lid = dev.capture(lambda: [self._solver.update() for _ in range(reps * period)])
+                    lid = dev.capture(lambda: [self._update() for _ in range(reps * period)])
                     dev.replay(lid, 1)
                     done += reps * period
                     long = (lid, reps * period)
@@ -252,6 +293,73 @@ class FluidSimulator:
         s = self._solver
         v, p = s.get_fields()[:2]
         return derive_flow_stats(self._dev.flow_stats(s.dx, v, p, body_box), s.dx, s.dt, body_box is not None)
+
+    # -- per-step history (new): probe values and the pressure force on a body, recorded on the device -----------------------------
+    def record_history(self, probes=(), body_box=None, every=1, capacity=None, start_step=0):
+        """From the next step on, record after every step k (counted from here, k = 1, 2, ...) with k % every == 0: u, w and p at the
+        fluid cells `probes` = [(x, y), ...] and, with body_box = (x0, y0, x1, y1), the pressure force on the body as flow_stats(body_box)
+        computes it - gathered by one small launch per step that is captured into the replayed graphs (and recorded into slab tapes), into
+        a device ring of `capacity` records (default: 16 MB of them, at least 64) that run() drains between chunks.  Record k is numbered
+        start_step + k.  Changes no field and no trajectory; a recorder already attached is stopped first.  history() returns the records.
+        Not allowed during a graph capture."""
+        dev, s = self._dev, self._solver
+        if getattr(dev, "capturing", False):
+            raise RuntimeError("record_history during a graph capture")
+        every = int(every)
+        if every < 1:
+            raise ValueError("every must be >= 1")
+        mask = s._bc.mask
+        pts = check_probes(mask, probes)
+        if body_box is not None:
+            body_box = tuple(int(b) for b in body_box)
+            faces = body_faces(mask, body_box)
+        else:
+            faces = np.zeros((0, 3), np.int32)
+        if len(pts) == 0 and body_box is None:
+            raise ValueError("record_history needs probes, a body_box or both")
+        if capacity is None:
+            capacity = max(64, (16 << 20) // (8 * (2 + 3 * len(pts))))
+        if int(capacity) < 1:
+            raise ValueError("capacity must be >= 1")
+        self.stop_history()
+        hist = dev.history_create(pts, faces, int(capacity), every)
+        self._recorder = Recorder(dev, hist, pts, body_box, every, start_step, s.dt)
+        self._last_recorder = None
+
+    def history(self):
+        """Everything recorded since record_history(): {"step": int64[n], "time": f64[n] (step * dt), "probes": int32[P, 2],
+        "u", "w", "p": f64[n, P], and with a body box "force_x", "force_y": f64[n]}.  Drains the device ring (a download)."""
+        rec = self._recorder or self._last_recorder
+        if rec is None:
+            raise RuntimeError("no history: call record_history() first")
+        if rec is self._recorder:
+            rec.drain()
+        return rec.data()
+
+    def stop_history(self):
+        """Drain and detach the recorder: the cached graphs and tapes that hold its launch are freed, then its device ring.  history() still
+        returns what it recorded until the next record_history()."""
+        rec = self._recorder
+        if rec is None:
+            return
+        dev = self._dev
+        if getattr(dev, "capturing", False):
+            raise RuntimeError("stop_history during a graph capture")
+        try:
+            rec.drain()
+        finally:
+            tok = rec.token
+            for sig in [k for k in self._graphs if tok in k]:
+                gid, _, long = self._graphs.pop(sig)
+                dev.free_graph(gid)
+                if long is not None:
+                    dev.free_graph(long[0])
+            for key in [k for k in self._tapes if tok in k[0]]:
+                dev.free_tape(self._tapes.pop(key))
+            if self._graph is not None and tok in self._graph[0]:
+                self._graph = self._graph_long = None
+            dev.history_free(rec.hist)
+            self._recorder, self._last_recorder = None, rec
 
     # -- visualisation (fs/fluid_simulator.py:22-58): device kernels; like the reference these return the image FIELD ----
     def get_norm_field(self):

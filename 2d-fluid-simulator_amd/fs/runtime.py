@@ -873,6 +873,70 @@ class DeviceBase:
                 s[k] = float("nan") if tot[len(sums) + n] > 0 else float(x)
         return dict(zip(self.STAT_SLOTS, s))
 
+    # ---- per-step history (include/fs_hip.h fs_history_*): probe values and body faces gathered by one launch per step ------------------
+    def history_create(self, points, faces, capacity, every):
+        """A device ring of `capacity` records for FluidSimulator.record_history: points (P, 2) global probe cells, faces (n, 3) global
+        (x, y, dir) of fs.history.body_faces.  A slab keeps the probes and faces whose cell lies in its owned rows: the record reads no ghost
+        row, needs no exchange and sits in a tape as an ordinary kernel op.  Not allowed during a graph capture."""
+        from .history import owned
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("history_create during a graph capture")
+        points = np.asarray(points, np.int32).reshape(-1, 2)
+        faces = np.asarray(faces, np.int32).reshape(-1, 3)
+        mine = owned(points, self.y0, self.nyl)
+        h = self._p_history_create(np.ascontiguousarray(points[mine]), np.ascontiguousarray(faces[owned(faces, self.y0, self.nyl)]),
+                                   int(capacity), int(every))
+        hist = History(h, len(points), mine, int(capacity), int(every))
+        self._handle_serial[id(h)] = hist.serial        # (its name in the op keys of a logged period)
+        return hist
+
+    def history_record(self, hist, dx, v, p):
+        """Append the record of the current v and p (every `every`-th call).  A limit_field v still owes stays deferred: the kernel limits
+        the probe values as the pass would store them.  Not a _run: no flush, no exchange, no ghost row - on slabs a kernel op of its own
+        in the logged period (writes no field)."""
+        args = (hist._h, float(dx), float(v.pending_limit) if v.pending_limit is not None else 0.0, v._h, p._h)
+        if self._oplog is not None:
+            self._oplog.append(("k", "history_record", args, ()))
+        self._p_kernel("history_record", *args)
+
+    def history_read(self, hist):
+        """Empty the ring -> (forces (n, 2), probes (n, P, 3): u, w, p; launches so far, records dropped).  Across slabs the forces add
+        and each probe comes from the rank that owns it (the others contribute -0.0, which leaves every value's bits alone).  Collective on
+        slab runs; not allowed during a graph capture."""
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("history_read during a graph capture: the ring is read between captures / replays")
+        rec, launches, dropped = self._p_history_read(hist._h, len(hist.mine), hist.capacity)
+        n = rec.shape[0]
+        if self.nranks > 1:
+            if not self._p_same_over_ranks([n, launches]):
+                raise RuntimeError("history_read: the ranks hold different numbers of records")
+            full = np.full((n + 1, 2 + 3 * hist.nprobes), -0.0)        # (+ one row: the ranks' dropped counts)
+            full[:n, :2] = rec[:, :2]
+            cols = (2 + 3 * np.repeat(hist.mine, 3) + np.tile(np.arange(3), len(hist.mine))).astype(np.int64)
+            full[:n, cols] = rec[:, 2:]
+            full[n, 0] = float(dropped)
+            tot = self._p_allreduce_array(full.ravel()).reshape(full.shape)
+            dropped, rec = int(tot[n, 0]), tot[:n]
+        return rec[:, :2].copy(), rec[:, 2:].reshape(n, hist.nprobes, 3).copy(), int(launches), int(dropped)
+
+    def history_free(self, hist):
+        if hist._h is not None:
+            self._handle_serial.pop(id(hist._h), None)
+            self._p_history_free(hist._h)
+            hist._h = None
+
+    def _p_allreduce_array(self, a):
+        """Sum of a float64 array over all ranks (collective): _p_allreduce on a list, for backends without an array primitive."""
+        return np.asarray(self._p_allreduce([float(x) for x in a]), np.float64)
+
+
+class History:
+    """A device history ring (DeviceBase.history_create): handle, the global probe count, which of them this rank owns, capacity, every."""
+
+    def __init__(self, h, nprobes, mine, capacity, every):
+        self._h, self.nprobes, self.mine, self.capacity, self.every = h, nprobes, np.asarray(mine, np.int64), capacity, every
+        self.serial = next(_serials)
+
 
 class Device(DeviceBase):
     """DeviceBase bound to libfs_hip.so (HIP kernels on one MI355X; RCCL for the ghost rows)."""
@@ -1030,6 +1094,28 @@ class Device(DeviceBase):
         b = None if box is None else (ctypes.c_int * 4)(*box)
         _lib.call("fs_flow_stats", self._ctx, dx, vh, ph, b, out)
         return list(out)
+
+    def _p_history_create(self, points, faces, capacity, every):
+        h = ctypes.c_void_p()
+        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if a.size else None
+        _lib.call("fs_history_create", self._ctx, len(points), ip(points), len(faces), ip(faces), capacity, every, ctypes.byref(h))
+        return h
+
+    def _p_history_read(self, h, nlocal, capacity):
+        out = np.empty((capacity, 2 + 3 * nlocal), np.float64)
+        n, launches, dropped = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_int()
+        _lib.call("fs_history_read", self._ctx, h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), capacity, ctypes.byref(n),
+                  ctypes.byref(launches), ctypes.byref(dropped))
+        return out[:n.value], launches.value, dropped.value
+
+    def _p_history_free(self, h):
+        if self._ctx is not None:
+            _lib.call("fs_history_free", self._ctx, h)
+
+    def _p_allreduce_array(self, a):
+        a = np.ascontiguousarray(a, np.float64).copy()
+        _lib.call("fs_allreduce_sum", self._ctx, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), a.size)
+        return a
 
     def _p_allreduce(self, values):
         arr = (ctypes.c_double * len(values))(*values)

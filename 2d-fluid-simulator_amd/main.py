@@ -8,6 +8,8 @@ The reference opens a GGUI window and steps forever; here the loop runs `--steps
     fields and the `next` buffers).
   * sample scalar flow diagnostics (energy, enstrophy, CFL, divergence, non-finite cells, pressure force on a body) into a CSV
     every `--stats-every` steps, and stop at the first non-finite sample (`--stop-on-nonfinite`, exit status 3).
+  * record u, w, p at probe cells (`--probe x,y`) and the pressure force on a body (`--body`) every `--history-every` steps on the
+    GPU, written to `--history-file` (.npz) at the end of the run.
 """
 import argparse
 import os
@@ -53,10 +55,16 @@ def build_parser():
                    help="sample the flow diagnostics (FluidSimulator.flow_stats) at the first step and every N steps into --stats-file")
     p.add_argument("--stats-file", type=str, default=None, help="CSV of the samples: step,time,<keys> (default: <out>/stats.csv)")
     p.add_argument("--body", type=str, default=None,
-                   help="x0,y0,x1,y1 (global cells, half-open): add the pressure force on the wall cells in this box to the samples; "
-                        "'auto': the scene's obstacle (scenes 1, 3, 5, 6; fs.boundary_condition.default_body_box)")
+                   help="x0,y0,x1,y1 (global cells, half-open): add the pressure force on the wall cells in this box to the samples "
+                        "and the history; 'auto': the scene's obstacle (scenes 1, 3, 5, 6; fs.boundary_condition.default_body_box)")
     p.add_argument("--stop-on-nonfinite", action="store_true",
                    help="exit with status 3 at the first sample that finds NaN / Inf in v or p")
+    p.add_argument("--history-every", type=int, default=0,
+                   help="record the probes (--probe) and the body force (--body) after every N-th step on the GPU (FluidSimulator.record_history)")
+    p.add_argument("--probe", type=str, action="append", default=[], metavar="X,Y",
+                   help="a fluid cell (global x,y) whose u, w, p go into the history; may be repeated")
+    p.add_argument("--history-file", type=str, default=None,
+                   help=".npz of the history: step, time, probes, u, w, p[, force_x, force_y] (default: <out>/history.npz)")
     return p
 
 
@@ -146,6 +154,14 @@ def _body_box(parser, spec, num, res):
     return box
 
 
+def _probe(parser, spec):
+    try:
+        x, y = (int(c) for c in spec.split(","))
+    except ValueError:
+        parser.error(f"--probe {spec}: expected x,y (global cell)")
+    return x, y
+
+
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
@@ -164,9 +180,16 @@ def main(argv=None):
             _find_obstacle_image()
         except FileNotFoundError as e:      # the obstacle image is an asset of the reference repository and is not shipped here
             parser.error(f"-bc 6: {e}")
-    if (args.body is not None or args.stop_on_nonfinite or args.stats_file) and args.stats_every <= 0:
-        parser.error("--body, --stats-file and --stop-on-nonfinite need --stats-every N")
+    if (args.stop_on_nonfinite or args.stats_file) and args.stats_every <= 0:
+        parser.error("--stats-file and --stop-on-nonfinite need --stats-every N")
+    if args.body is not None and args.stats_every <= 0 and args.history_every <= 0:
+        parser.error("--body needs --stats-every N or --history-every N")
+    if (args.probe or args.history_file) and args.history_every <= 0:
+        parser.error("--probe and --history-file need --history-every N")
+    if args.history_every > 0 and not args.probe and args.body is None:
+        parser.error("--history-every needs --probe X,Y or --body")
     box = _body_box(parser, args.body, args.boundary_condition, res)
+    probes = [_probe(parser, spec) for spec in args.probe]
     print(f"Boundary Condition: {args.boundary_condition}\ndt: {dt}\nRe: {args.reynolds_num}\nResolution: {res}\n"
           f"Scheme: {args.advection_scheme}\nVorticity confinement: {vor_eps}")
     fs.runtime.init(gpu=args.gpu, dtype="f64" if args.f64 else "f32")
@@ -175,6 +198,19 @@ def main(argv=None):
     out = Path(args.out)
     step0 = load_state(sim, args.load_state) if args.load_state else 0
     dev = sim._solver._bc.device
+    history_file = None
+    if args.history_every > 0:
+        history_file = Path(args.history_file) if args.history_file else out / "history.npz"
+        try:
+            sim.record_history(probes, box, every=args.history_every, start_step=step0)
+        except ValueError as e:
+            parser.error(f"--probe: {e}")
+
+    def write_history():
+        if history_file is not None:
+            history_file.parent.mkdir(parents=True, exist_ok=True)
+            np.savez(str(history_file), **sim.history())
+
     stats = None
     if args.stats_every > 0:
         stats = StatsWriter(sim, Path(args.stats_file) if args.stats_file else out / "stats.csv", dt, box, args.stop_on_nonfinite)
@@ -183,6 +219,7 @@ def main(argv=None):
         if stats.sample(step) > 0 and stats.stop:
             stats.close()
             print(f"step {step}: non-finite values (NaN / Inf) in v or p; stopping (--stop-on-nonfinite)", file=sys.stderr)
+            write_history()
             dev.close()
             sys.exit(3)
 
@@ -218,6 +255,7 @@ def main(argv=None):
         save_state(sim, args.save_state, step0 + args.steps)
     if stats:
         stats.close()
+    write_history()
     dev.close()
 
 

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 10
+#define FS_ABI_VERSION 11
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -273,6 +273,28 @@ int fs_poisson_residual(fs_ctx *ctx, double dt, double dx, const fs_field *p, co
  * reduction in a fixed order); refused with FS_ERR_STATE during graph capture / tape recording.  Does not alter any field.          */
 #define FS_FLOW_NSTAT 10
 int fs_flow_stats(fs_ctx *ctx, double dx, const fs_field *v, const fs_field *p, const int *box, double *out);
+
+/* Per-step history (new): a ring of `capacity` records on the device, appended to by ONE small launch per step that can be captured in
+ * a hipGraph and recorded in a tape (csrc/fs_history.h).  Record layout, doubles: [force_x, force_y, u0, w0, p0, u1, w1, p1, ...].
+ *   points: npoints (x, y) GLOBAL cells - the probes, in record order;
+ *   faces:  nfaces (x, y, dir): the FLUID cell of a face of a body and the direction wall -> fluid; dir 0 +x: force_x -= p*dx,
+ *           1 -x: force_x += p*dx, 2 +y: force_y -= p*dx, 3 -y: force_y += p*dx (the terms of fs_flow_stats, per face).
+ * Every point and face must lie in this context's OWNED rows (FS_ERR_ARG otherwise): on slabs each rank takes its own share, and the
+ * ranks' records combine by adding the forces and taking each probe from the rank that owns it.  Pass the faces sorted by (y, x, dir):
+ * the force is summed in a fixed order from that list.
+ * fs_history_record: launch n (counted from 0) appends a record when (n + 1) % every == 0 - if the ring is full the record is counted as
+ *   dropped instead.  limit > 0: v still owes limit_field(limit) (a deferred pass): the probes' (u, w) are limited as that pass would
+ *   store them.  Reads the owned rows of v and p only (no ghost row); changes no field.
+ * fs_history_read: synchronises, copies the records in the ring (oldest first) to `out` (max_records >= the count, or `out` NULL: counts
+ *   only, nothing is reset), then empties the ring: *n_records, *dropped and the launch count (never reset) describe the ring before.
+ *   FS_ERR_STATE during graph capture / tape recording.
+ * fs_history_free: a graph or tape that holds the launch must not be replayed afterwards; during a capture the release is deferred to
+ *   its end (as fs_field_free).                                                                                                        */
+typedef struct fs_history fs_history;
+int fs_history_create(fs_ctx *ctx, int npoints, const int *points, int nfaces, const int *faces, int capacity, int every, fs_history **out);
+int fs_history_record(fs_ctx *ctx, fs_history *h, double dx, double limit, const fs_field *v, const fs_field *p);
+int fs_history_read(fs_ctx *ctx, fs_history *h, double *out, int max_records, int *n_records, long long *launches, int *dropped);
+int fs_history_free(fs_ctx *ctx, fs_history *h);
 
 /* ---- pointwise -------------------------------------------------------------------------------- */
 /* limit_field   fs/solver.py:38-43 ;  clamp_field   fs/solver.py:46-49                           */
