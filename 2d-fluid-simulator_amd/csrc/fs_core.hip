@@ -675,6 +675,9 @@ int fs_destroy(fs_ctx *ctx)
     for (fs_history *h : ctx->histories) history_release(h);
     for (fs_history *h : ctx->deferred_hist) history_release(h);
     ctx->histories.clear();
+    for (fs_mean *m : ctx->means) mean_release(m);
+    for (fs_mean *m : ctx->deferred_mean) mean_release(m);
+    ctx->means.clear();
     if (ctx->d_mask) hipFree(ctx->d_mask);
     if (ctx->d_bc_const) hipFree(ctx->d_bc_const);
     if (ctx->d_bc_dye) hipFree(ctx->d_bc_dye);
@@ -1431,6 +1434,8 @@ int fs_graph_end(fs_ctx *ctx, int *graph_id)
     ctx->deferred_free.clear();
     for (fs_history *h : ctx->deferred_hist) history_release(h);      // likewise history rings (fs_history_free)
     ctx->deferred_hist.clear();
+    for (fs_mean *m : ctx->deferred_mean) mean_release(m);            // and time averages (fs_mean_free)
+    ctx->deferred_mean.clear();
     if (ec != hipSuccess) return hip_fail(ec, "hipStreamEndCapture", __FILE__, __LINE__);
     hipGraphExec_t ex = nullptr;
     hipError_t e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);

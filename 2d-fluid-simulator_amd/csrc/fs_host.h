@@ -129,6 +129,8 @@ struct fs_ctx {
     std::vector<fs_field *> deferred_free;   // fs_field_free during a hipGraph capture: released when the capture ends
     std::set<fs_history *> histories;        // live history rings (fs_history_create), released with the context
     std::vector<fs_history *> deferred_hist; // fs_history_free during a hipGraph capture: released when the capture ends
+    std::set<fs_mean *> means;               // live time averages (fs_mean_create), released with the context
+    std::vector<fs_mean *> deferred_mean;    // fs_mean_free during a hipGraph capture: released when the capture ends
     // tuning knobs (env FS_MARCH=0: one-cell-per-lane kernels only)
     bool use_march = true;
     bool use_pairs = true;     // lanes of 2 cells: even widths (every `res`); use_march: the quad kernels, X % 4 == 0
@@ -181,9 +183,19 @@ struct fs_history {
     long long *d_state = nullptr;   // [HIST_STATE]
 };
 
+// time averages (fs_mean_*, fs_mean.h): the accumulator planes over this context's owned rows and the device counters
+struct fs_mean {
+    fs_ctx *ctx = nullptr;
+    long long every = 1, start = 0;
+    size_t plane = 0;               // doubles from one plane to the next: nyl * P + MEAN_PAD
+    double *d_sums = nullptr;       // [MEAN_PLANES][plane]
+    long long *d_state = nullptr;   // [MEAN_STATE]
+};
+
 namespace fs {
 
 void history_release(fs_history *h);      // fs_pressure.hip
+void mean_release(fs_mean *m);            // fs_pressure.hip
 
 // HIP-event pair around a span of stream work that is not one kernel launch (fs_api.hip; the ghost-row exchange chain of fs_comm.hip)
 ProfRec prof_span_begin(fs_ctx *c, const char *name, hipStream_t stream);

@@ -1,10 +1,12 @@
 // fs_pressure.hip - C-ABI entry points of the pressure kernels: Jacobi sweeps (single, lazily bounded pairs / quads / finishing pass), red-black
 // SOR (half sweeps, one fused iteration, two iterations per pass), the Poisson source pair, the residual, the flow diagnostics and the
-// per-step history ring.
+// per-step history ring and the time averages.
 #include "fs_launch.h"
 #include "fs_stats.h"
+#include "fs_mean.h"
 
 static_assert(fs::STATS_N == FS_FLOW_NSTAT, "fs_stats.h and include/fs_hip.h disagree on the slots");
+static_assert(fs::MEAN_PLANES == FS_MEAN_NPLANE, "fs_mean.h and include/fs_hip.h disagree on the planes");
 
 namespace fs {
 void history_release(fs_history *h)
@@ -15,6 +17,12 @@ void history_release(fs_history *h)
     if (h->d_state) hipFree(h->d_state);
     if (h->d_partial) hipFree(h->d_partial);
     delete h;
+}
+void mean_release(fs_mean *m)
+{
+    if (m->d_sums) hipFree(m->d_sums);
+    if (m->d_state) hipFree(m->d_state);
+    delete m;
 }
 }  // namespace fs
 
@@ -518,6 +526,163 @@ int fs_history_free(fs_ctx *ctx, fs_history *h)
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
     history_release(h);
+    return FS_OK;
+}
+
+// ---- time averages (fs_mean.h) ---------------------------------------------------------------------------------------------------------
+#define FS_MEAN_HANDLE(m) FS_REQUIRE((m)->ctx == ctx && ctx->means.count(m), "mean from another context or freed")
+#define FS_MEAN_NO_CAPTURE(what) \
+    if (ctx->capturing || ctx->tape_rec) { set_error("mean " what " during graph capture / tape recording"); return FS_ERR_STATE; }
+
+// workgroups of 256 lanes x `w` columns and `rpw` rows over the owned rows: rows per workgroup doubled from `g0` while the grid keeps >= 2048
+// workgroups (8 per CU), at most MEAN_ROWS - a non-sampling launch is a counter read per workgroup, so the grid stays in the thousands
+static dim3 mean_grid(const fs_ctx *ctx, int w, int g0, int *rpw)
+{
+    const int nx = (ctx->X + 256 * w - 1) / (256 * w), ny = ctx->nyl;
+    int r = g0;
+    while (r < MEAN_ROWS && (size_t)nx * ((ny + 2 * r - 1) / (2 * r)) >= 2048) r *= 2;
+    *rpw = r;
+    return dim3(nx, (ny + r - 1) / r);
+}
+
+int fs_mean_create(fs_ctx *ctx, long long every, long long start, fs_mean **out)
+{
+    FS_REQUIRE(ctx && out, "null argument");
+    FS_REQUIRE(every >= 1 && start >= 0, "every must be >= 1 and start >= 0");
+    FS_MEAN_NO_CAPTURE("create")
+    FS_HIP(hipSetDevice(ctx->device));
+    fs_mean *m = new fs_mean();
+    m->ctx = ctx; m->every = every; m->start = start;
+    m->plane = (size_t)ctx->nyl * ctx->P + MEAN_PAD;
+    const size_t bytes = MEAN_PLANES * m->plane * sizeof(double);
+    hipError_t e = hipMalloc(&m->d_state, MEAN_STATE * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc(&m->d_sums, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(m->d_state, 0, MEAN_STATE * sizeof(long long), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(m->d_sums, 0, bytes, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { mean_release(m); return hip_fail(e, "fs_mean_create", __FILE__, __LINE__); }
+    ctx->means.insert(m);
+    *out = m;
+    return FS_OK;
+}
+
+int fs_mean_accumulate(fs_ctx *ctx, fs_mean *m, double limit, const fs_field *v, const fs_field *p)
+{
+    FS_REQUIRE(ctx && m, "null argument");
+    FS_MEAN_HANDLE(m);
+    FS_FIELD(v, 2); FS_FIELD(p, 1);
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    // everything the launches need is in `m` and the fields: no allocation, copy or synchronisation here (the closure is captured / taped)
+    const int jb = ctx->halo, je = ctx->halo + ctx->nyl, w = ctx->X % 2 == 0 ? 2 : 1;
+    int rpw;
+    const dim3 grid = mean_grid(ctx, w, MEAN_G, &rpw);
+    const long long every = m->every, start = m->start;
+    long long *state = m->d_state;
+    double *sums = m->d_sums;
+    const size_t plane = m->plane;
+    FS_DISPATCH(ctx, {
+        return launch(ctx, "mean_accumulate", [=] {
+            if (w == 2)
+                FS_KLAUNCH((k_mean_accumulate<T, 2>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, limit, start, every,
+                           (const long long *)state, (const T *)v->d, (const T *)p->d, sums, plane);
+            else
+                FS_KLAUNCH((k_mean_accumulate<T, 1>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, limit, start, every,
+                           (const long long *)state, (const T *)v->d, (const T *)p->d, sums, plane);
+            FS_KLAUNCH((k_mean_tick), dim3(1), dim3(64), 0, ctx->stream, start, every, state);
+        });
+    })
+}
+
+static int mean_counters(fs_ctx *ctx, fs_mean *m, long long *st)
+{
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemcpyAsync(st, m->d_state, MEAN_STATE * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_mean_finalize(fs_ctx *ctx, fs_mean *m, fs_field *v_out, fs_field *p_out)
+{
+    FS_REQUIRE(ctx && m, "null argument");
+    FS_MEAN_HANDLE(m);
+    FS_FIELD(v_out, 2); FS_FIELD(p_out, 1);
+    FS_MEAN_NO_CAPTURE("finalize")
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    long long st[MEAN_STATE];
+    if (int rc = mean_counters(ctx, m, st)) return rc;
+    if (st[1] < 1) { set_error("mean finalize: no sample accumulated yet"); return FS_ERR_STATE; }
+    const int jb = ctx->halo, je = ctx->halo + ctx->nyl, w = ctx->X % 2 == 0 ? 2 : 1;
+    int rpw;
+    const dim3 grid = mean_grid(ctx, w, 1, &rpw);
+    const long long *state = m->d_state;
+    const double *sums = m->d_sums;
+    const size_t plane = m->plane;
+    FS_DISPATCH(ctx, {
+        return launch(ctx, "mean_finalize", [=] {
+            if (w == 2)
+                FS_KLAUNCH((k_mean_finalize<T, 2>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, state, sums, plane, (T *)v_out->d,
+                           (T *)p_out->d, v_out->hot);
+            else
+                FS_KLAUNCH((k_mean_finalize<T, 1>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, state, sums, plane, (T *)v_out->d,
+                           (T *)p_out->d, v_out->hot);
+        });
+    })
+}
+
+int fs_mean_read(fs_ctx *ctx, fs_mean *m, double *sums_out, long long *launches, long long *samples)
+{
+    FS_REQUIRE(ctx && m, "null argument");
+    FS_MEAN_HANDLE(m);
+    FS_MEAN_NO_CAPTURE("read")
+    long long st[MEAN_STATE];
+    if (int rc = mean_counters(ctx, m, st)) return rc;
+    if (launches) *launches = st[0];
+    if (samples) *samples = st[1];
+    if (!sums_out) return FS_OK;
+    // per plane: nyl device rows of pitch P -> dense rows of X
+    for (int k = 0; k < MEAN_PLANES; ++k)
+        FS_HIP(hipMemcpy2DAsync(sums_out + (size_t)k * ctx->nyl * ctx->X, (size_t)ctx->X * sizeof(double), m->d_sums + k * m->plane,
+                                (size_t)ctx->P * sizeof(double), (size_t)ctx->X * sizeof(double), (size_t)ctx->nyl, hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_mean_write(fs_ctx *ctx, fs_mean *m, const double *sums_in, long long launches, long long samples)
+{
+    FS_REQUIRE(ctx && m && sums_in, "null argument");
+    FS_MEAN_HANDLE(m);
+    FS_REQUIRE(launches >= 0 && samples >= 0 && samples <= launches, "counters must satisfy 0 <= samples <= launches");
+    FS_MEAN_NO_CAPTURE("write")
+    FS_HIP(hipSetDevice(ctx->device));
+    const long long st[MEAN_STATE] = {launches, samples};
+    for (int k = 0; k < MEAN_PLANES; ++k)
+        FS_HIP(hipMemcpy2DAsync(m->d_sums + k * m->plane, (size_t)ctx->P * sizeof(double), sums_in + (size_t)k * ctx->nyl * ctx->X,
+                                (size_t)ctx->X * sizeof(double), (size_t)ctx->X * sizeof(double), (size_t)ctx->nyl, hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipMemcpyAsync(m->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
+    return FS_OK;
+}
+
+int fs_mean_reset(fs_ctx *ctx, fs_mean *m)
+{
+    FS_REQUIRE(ctx && m, "null argument");
+    FS_MEAN_HANDLE(m);
+    FS_MEAN_NO_CAPTURE("reset")
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemsetAsync(m->d_sums, 0, MEAN_PLANES * m->plane * sizeof(double), ctx->stream));
+    FS_HIP(hipMemsetAsync(m->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
+    return FS_OK;
+}
+
+int fs_mean_free(fs_ctx *ctx, fs_mean *m)
+{
+    if (!m) return FS_OK;
+    FS_REQUIRE(ctx && m->ctx == ctx && ctx->means.count(m), "mean from another context or freed");
+    ctx->means.erase(m);
+    if (ctx->capturing) { ctx->deferred_mean.push_back(m); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
+    mean_release(m);
     return FS_OK;
 }
 

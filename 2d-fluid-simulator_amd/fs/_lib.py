@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FS_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libfs_hip.so")     # FS_LIB: A/B builds (tools/)
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _lib = None
 
@@ -82,6 +82,13 @@ _PROTOS = {
     "fs_history_record": [_c_vp, _c_vp, _c_dbl, _c_dbl, _c_vp, _c_vp],
     "fs_history_read": [_c_vp, _c_vp, _P(_c_dbl), _c_int, _P(_c_int), _P(ctypes.c_longlong), _P(_c_int)],
     "fs_history_free": [_c_vp, _c_vp],
+    "fs_mean_create": [_c_vp, ctypes.c_longlong, ctypes.c_longlong, _P(_c_vp)],
+    "fs_mean_accumulate": [_c_vp, _c_vp, _c_dbl, _c_vp, _c_vp],
+    "fs_mean_finalize": [_c_vp, _c_vp, _c_vp, _c_vp],
+    "fs_mean_read": [_c_vp, _c_vp, _P(_c_dbl), _P(ctypes.c_longlong), _P(ctypes.c_longlong)],
+    "fs_mean_write": [_c_vp, _c_vp, _P(_c_dbl), ctypes.c_longlong, ctypes.c_longlong],
+    "fs_mean_reset": [_c_vp, _c_vp],
+    "fs_mean_free": [_c_vp, _c_vp],
     "fs_limit_field": [_c_vp, _c_dbl, _c_vp] + _ROWS,
     "fs_clamp_field": [_c_vp, _c_dbl, _c_dbl, _c_vp] + _ROWS,
     "fs_cip_advect_dye_clamped": [_c_vp, _c_dbl, _c_dbl] + [_c_vp] * 7 + _ROWS,

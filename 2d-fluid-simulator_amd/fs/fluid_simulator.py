@@ -10,6 +10,7 @@ import math
 import numpy as np
 
 from .advection import advect_kk_scheme, advect_upwind
+from .averages import Averager, derive_averages
 from .boundary_condition import get_boundary_condition
 from .history import Recorder, body_faces, check_probes
 from .pressure_updater import JacobiPressureUpdater, RedBlackSorPressureUpdater
@@ -81,10 +82,12 @@ class FluidSimulator:
         self._since_hot_check = 0
         self._recorder = None      # fs.history.Recorder while record_history() is on
         self._last_recorder = None  # ... and after stop_history(): what history() still returns
+        self._averager = None      # fs.averages.Averager while start_averaging() is on
 
     def _update(self):
-        """One solver step, then the history record if a recorder is attached: what step(), the periods capture_period() captures and the
-        slab periods tape_period() logs all run (so a graph or tape holds the record exactly when _signature() says so)."""
+        """One solver step, then the history record if a recorder is attached and the accumulation of the time averages if an averager is:
+        what step(), the periods capture_period() captures and the slab periods tape_period() logs all run (so a graph or tape holds these
+        launches exactly when _signature() says so)."""
         self._solver.update()
         rec = self._recorder
         if rec is not None:
@@ -93,6 +96,10 @@ class FluidSimulator:
             v, p = self._solver.get_fields()[:2]
             self._dev.history_record(rec.hist, self._solver.dx, v, p)
             rec.issued += 1
+        avg = self._averager
+        if avg is not None:
+            v, p = self._solver.get_fields()[:2]
+            self._dev.mean_accumulate(avg.mean, v, p)
 
     def step(self):
         self._update()
@@ -144,6 +151,8 @@ class FluidSimulator:
             sig.append((spare.serial, spare.static_id, spare.bc_parity) if spare is not None else 0)
         if self._recorder is not None:
             sig.append(self._recorder.token)        # (graphs / tapes with the record launch in them are never replayed without it, or vice versa)
+        if self._averager is not None:
+            sig.append(self._averager.token)        # (likewise the accumulation launch of the time averages)
         return tuple(sig)
 
     _LONG_STEPS = 16     # steps per long-form graph (capture_period)
@@ -348,18 +357,100 @@ class FluidSimulator:
         try:
             rec.drain()
         finally:
-            tok = rec.token
-            for sig in [k for k in self._graphs if tok in k]:
-                gid, _, long = self._graphs.pop(sig)
-                dev.free_graph(gid)
-                if long is not None:
-                    dev.free_graph(long[0])
-            for key in [k for k in self._tapes if tok in k[0]]:
-                dev.free_tape(self._tapes.pop(key))
-            if self._graph is not None and tok in self._graph[0]:
-                self._graph = self._graph_long = None
+            self._drop_cached(rec.token)
             dev.history_free(rec.hist)
             self._recorder, self._last_recorder = None, rec
+
+    def _drop_cached(self, tok):
+        """Free the cached graphs and tapes whose signature holds `tok` (they contain a launch on a device object about to be freed)."""
+        dev = self._dev
+        for sig in [k for k in self._graphs if tok in k]:
+            gid, _, long = self._graphs.pop(sig)
+            dev.free_graph(gid)
+            if long is not None:
+                dev.free_graph(long[0])
+        for key in [k for k in self._tapes if tok in k[0]]:
+            dev.free_tape(self._tapes.pop(key))
+        if self._graph is not None and tok in self._graph[0]:
+            self._graph = self._graph_long = None
+
+    # -- time averages (new): means and second moments of u, w, p accumulated on the device -------------------------------------------
+    def start_averaging(self, every=1, start_step=0):
+        """From the next step on, add u, w, p and their products uu, ww, uw, pp of every not-wall cell to double sums on the device after
+        every step k (counted from here, k = 1, 2, ...) with k > start_step and (k - start_step) % every == 0.  The launch is part of the
+        step: it is captured into the replayed graphs and recorded into slab tapes, and run() is not cut into chunks by it.  Costs 56 bytes
+        per cell of device memory, and a sampling step moves more bytes for the sums than for the flow (choose `every` accordingly).
+        Changes no field and no trajectory.  averages() returns the result.  Raises while an average is attached already; not allowed during
+        a graph capture."""
+        dev = self._dev
+        if getattr(dev, "capturing", False):
+            raise RuntimeError("start_averaging during a graph capture")
+        if self._averager is not None:
+            raise RuntimeError("an average is attached already: stop_averaging() first (or reset_averages())")
+        every, start_step = int(every), int(start_step)
+        if every < 1:
+            raise ValueError("every must be >= 1")
+        if start_step < 0:
+            raise ValueError("start_step must be >= 0")
+        self._averager = Averager(dev, dev.mean_create(every, start_step), every, start_step)
+
+    def _avg(self):
+        if self._averager is None:
+            raise RuntimeError("no average: call start_averaging() first")
+        return self._averager
+
+    def averages(self, local=False):
+        """The averages so far (a download of 56 bytes per cell): {"samples": int, "steps": int (steps since start_averaging), "u", "w",
+        "p": means, "uu", "ww", "uw": central second moments <a b> - <a><b> (the Reynolds stresses), "p_rms", "tke": 0.5 (uu + ww),
+        "mask"}: float64 arrays of shape (X, Y) (mask: uint8), wall cells 0 (fs.averages.derive_averages).  On slabs the global arrays are
+        assembled on every rank (collective); local=True: this rank's owned rows only.  Raises while there is no sample."""
+        avg = self._avg()
+        dev = self._dev
+        sums, launches, samples = dev.mean_read(avg.mean, local=local)
+        if samples == 0:
+            raise RuntimeError(f"no samples yet ({launches} steps since start_averaging(every={avg.every}, start_step={avg.start_step}))")
+        mask = np.asarray(self._solver._bc.mask)
+        if local:
+            mask = mask[:, dev.y0:dev.y0 + dev.nyl]
+        out = {"samples": samples, "steps": launches}
+        out.update(derive_averages(sums, samples, mask))
+        out["mask"] = mask.copy()
+        return out
+
+    def mean_fields(self):
+        """The mean flow as device fields (v: 2 channels, p: 1 channel; wall cells 0), for everything that takes fields: the visualisation
+        kernels, to_numpy, DeviceBase.flow_stats.  New fields on every call; the caller owns them."""
+        from ._lib import FsError
+        from .runtime import Field
+        avg = self._avg()
+        dev = self._dev
+        if getattr(dev, "capturing", False):
+            raise FsError("mean_fields / mean_flow_stats during a graph capture: they allocate and download")
+        v, p = Field(dev, 2), Field(dev, 1)      # (not dev.alloc: scratch fields stay out of the ghost-row bookkeeping state of the tapes)
+        dev.mean_finalize(avg.mean, v, p)
+        return v, p
+
+    def mean_flow_stats(self, body_box=None):
+        """flow_stats() of the MEAN flow: the kinetic energy of the mean motion, the mean pressure force on a body ... (the CFL number and
+        the divergence of a mean field are diagnostics of the average, not of a step).  Not allowed during a graph capture."""
+        s = self._solver
+        v, p = self.mean_fields()
+        return derive_flow_stats(self._dev.flow_stats(s.dx, v, p, body_box), s.dx, s.dt, body_box is not None)
+
+    def reset_averages(self):
+        """Sums and sample count back to zero; the step count and the phase of `every` / `start_step` run on."""
+        self._dev.mean_reset(self._avg().mean)
+
+    def stop_averaging(self):
+        """Detach the average and free its device memory; the cached graphs and tapes that hold its launch are freed first.  Nothing is kept
+        on the host: call averages() before.  Inside a graph capture the device memory is released when the capture ends."""
+        avg = self._averager
+        if avg is None:
+            return
+        if not getattr(self._dev, "capturing", False):      # (inside a capture no graph can be freed: theirs stay cached, never matched again)
+            self._drop_cached(avg.token)
+        self._dev.mean_free(avg.mean)
+        self._averager = None
 
     # -- visualisation (fs/fluid_simulator.py:22-58): device kernels; like the reference these return the image FIELD ----
     def get_norm_field(self):

@@ -929,6 +929,93 @@ class DeviceBase:
         """Sum of a float64 array over all ranks (collective): _p_allreduce on a list, for backends without an array primitive."""
         return np.asarray(self._p_allreduce([float(x) for x in a]), np.float64)
 
+    # ---- time averages (include/fs_hip.h fs_mean_*): seven planes of double sums over the owned rows, fed by one launch per step -----------
+    MEAN_PLANES = 7     # S_u, S_w, S_p, S_uu, S_ww, S_uw, S_pp (fs.averages.SUMS)
+
+    def mean_create(self, every=1, start=0):
+        """Device accumulators for FluidSimulator.start_averaging: 56 bytes per owned cell, zeroed.  Launch n (from 0) of mean_accumulate
+        samples when n + 1 > start and (n + 1 - start) % every == 0.  Not allowed during a graph capture."""
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("mean_create during a graph capture")
+        every, start = int(every), int(start)
+        if every < 1 or start < 0:
+            raise ValueError("every must be >= 1 and start >= 0")
+        h = self._p_mean_create(every, start)
+        mean = Mean(h, every, start)
+        self._handle_serial[id(h)] = mean.serial        # (its name in the op keys of a logged period)
+        return mean
+
+    def mean_accumulate(self, mean, v, p):
+        """Add the current v and p to the sums when this launch is a sampling one; the counters advance on the device.  A limit_field v
+        still owes stays deferred: the kernel limits the values as the pass would store them.  Not a _run: no flush, no exchange, no ghost
+        row - on slabs a kernel op of its own in the logged period (writes no field)."""
+        args = (mean._h, float(v.pending_limit) if v.pending_limit is not None else 0.0, v._h, p._h)
+        if self._oplog is not None:
+            self._oplog.append(("k", "mean_accumulate", args, ()))
+        self._p_kernel("mean_accumulate", *args)
+
+    def mean_read(self, mean, local=False):
+        """-> (sums float64 (7, X, Y) in the order of fs.averages.SUMS, launches, samples).  On slabs the ranks' owned rows are assembled
+        like Field.to_numpy (allgather; local=True: this slab's rows only) and all ranks must report the same counters.  Collective on
+        slab runs; not allowed during a graph capture."""
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("mean_read during a graph capture: the sums are a download (read between captures / replays)")
+        mine, launches, samples = self._p_mean_read(mean._h)
+        launches, samples = int(launches), int(samples)
+        if self.nranks > 1 and not self._p_same_over_ranks([launches, samples]):
+            raise RuntimeError("mean_read: the ranks hold different launch / sample counts")
+        if local or self.nranks == 1:
+            return mine, launches, samples
+        if self.allgather is None:
+            raise RuntimeError("mean_read() on a slab needs runtime.init(allgather=...) or local=True")
+        return np.concatenate(self.allgather(mine), axis=2), launches, samples
+
+    def mean_write(self, mean, sums, launches, samples):
+        """Restore what mean_read returned (resume): sums is the GLOBAL (7, X, Y) array, each slab keeps its owned rows."""
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("mean_write during a graph capture")
+        sums = np.asarray(sums, np.float64)
+        if sums.shape != (self.MEAN_PLANES, self.nx, self.ny):
+            raise ValueError(f"expected sums of shape {(self.MEAN_PLANES, self.nx, self.ny)}, got {sums.shape}")
+        launches, samples = int(launches), int(samples)
+        if not 0 <= samples <= launches:
+            raise ValueError("counters must satisfy 0 <= samples <= launches")
+        self._p_mean_write(mean._h, np.ascontiguousarray(sums[:, :, self.y0:self.y0 + self.nyl]), launches, samples)
+
+    def mean_reset(self, mean):
+        """Sums and sample count to zero; the launch count runs on.  Not allowed during a graph capture."""
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("mean_reset during a graph capture")
+        self._p_mean_reset(mean._h)
+
+    def mean_finalize(self, mean, v_out, p_out):
+        """The means as fields: S_u / n, S_w / n into the 2-channel v_out, S_p / n into the 1-channel p_out (n = samples, > 0), wall cells
+        0, in the fields' precision.  Owned rows only: on slabs the targets' ghost rows are stale afterwards (valid = 0), and whatever reads
+        them exchanges first.  Not allowed during a graph capture."""
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("mean_finalize during a graph capture")
+        for f in (v_out, p_out):
+            f.pending_limit = f.pending_clamp = None      # (every owned cell is overwritten)
+        self._p_mean_finalize(mean._h, v_out._h, p_out._h)
+        for f in (v_out, p_out):
+            f.valid = 0 if self.nranks > 1 else self.halo
+            f.user_data = True
+            f.static_id = next(_serials)
+
+    def mean_free(self, mean):
+        if mean._h is not None:
+            self._handle_serial.pop(id(mean._h), None)
+            self._p_mean_free(mean._h)
+            mean._h = None
+
+
+class Mean:
+    """Device accumulators of a time average (DeviceBase.mean_create): handle, every, start."""
+
+    def __init__(self, h, every, start):
+        self._h, self.every, self.start = h, every, start
+        self.serial = next(_serials)
+
 
 class History:
     """A device history ring (DeviceBase.history_create): handle, the global probe count, which of them this rank owns, capacity, every."""
@@ -1111,6 +1198,31 @@ class Device(DeviceBase):
     def _p_history_free(self, h):
         if self._ctx is not None:
             _lib.call("fs_history_free", self._ctx, h)
+
+    def _p_mean_create(self, every, start):
+        h = ctypes.c_void_p()
+        _lib.call("fs_mean_create", self._ctx, every, start, ctypes.byref(h))
+        return h
+
+    def _p_mean_read(self, h):
+        out = np.empty((self.MEAN_PLANES, self.nyl, self.nx), np.float64)       # (the library's layout: x contiguous)
+        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
+        _lib.call("fs_mean_read", self._ctx, h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(launches), ctypes.byref(samples))
+        return out.transpose(0, 2, 1), launches.value, samples.value
+
+    def _p_mean_write(self, h, sums, launches, samples):
+        a = np.ascontiguousarray(sums.transpose(0, 2, 1), np.float64)
+        _lib.call("fs_mean_write", self._ctx, h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), launches, samples)
+
+    def _p_mean_reset(self, h):
+        _lib.call("fs_mean_reset", self._ctx, h)
+
+    def _p_mean_finalize(self, h, vh, ph):
+        _lib.call("fs_mean_finalize", self._ctx, h, vh, ph)
+
+    def _p_mean_free(self, h):
+        if self._ctx is not None:
+            _lib.call("fs_mean_free", self._ctx, h)
 
     def _p_allreduce_array(self, a):
         a = np.ascontiguousarray(a, np.float64).copy()

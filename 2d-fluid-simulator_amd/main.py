@@ -10,6 +10,8 @@ The reference opens a GGUI window and steps forever; here the loop runs `--steps
     every `--stats-every` steps, and stop at the first non-finite sample (`--stop-on-nonfinite`, exit status 3).
   * record u, w, p at probe cells (`--probe x,y`) and the pressure force on a body (`--body`) every `--history-every` steps on the
     GPU, written to `--history-file` (.npz) at the end of the run.
+  * average u, w, p and their second moments over time on the GPU (`--mean-every`, `--mean-start`), written to `--mean-file` (.npz) at
+    the end of the run; the sums travel with `--save-state` / `--load-state`, so an average continues over restarts.
 """
 import argparse
 import os
@@ -65,6 +67,13 @@ def build_parser():
                    help="a fluid cell (global x,y) whose u, w, p go into the history; may be repeated")
     p.add_argument("--history-file", type=str, default=None,
                    help=".npz of the history: step, time, probes, u, w, p[, force_x, force_y] (default: <out>/history.npz)")
+    p.add_argument("--mean-every", type=int, default=0,
+                   help="accumulate time averages of u, w, p and their second moments after every N-th step on the GPU "
+                        "(FluidSimulator.start_averaging; 0: off)")
+    p.add_argument("--mean-start", type=int, default=0, help="steps of the averaged run (restarts included) to leave out before the first sample")
+    p.add_argument("--mean-file", type=str, default=None,
+                   help=".npz of the averages: samples, steps, u, w, p, uu, ww, uw, p_rms, tke, mask, dt, dx, every, start "
+                        "(default: <out>/mean.npz)")
     return p
 
 
@@ -74,9 +83,30 @@ def _npz_path(path):
     return path if path.endswith(".npz") else path + ".npz"
 
 
+def saved_mean(path):
+    """(every, start) of the time average a checkpoint holds, or None."""
+    z = np.load(_npz_path(path))
+    return (int(z["mean.every"]), int(z["mean.start"])) if "mean.sums" in z.files else None
+
+
+def load_mean(sim, path):
+    """Restore the sums and counters of the checkpoint's time average into the attached one -> whether the checkpoint held any."""
+    z = np.load(_npz_path(path))
+    if "mean.sums" not in z.files:
+        return False
+    avg = sim._averager
+    avg.dev.mean_write(avg.mean, z["mean.sums"], int(z["mean.launches"]), int(z["mean.samples"]))
+    return True
+
+
 def save_state(sim, path, step):
     s = sim._solver
     arrays = {"step": np.array(step)}
+    avg = getattr(sim, "_averager", None)
+    if avg is not None:
+        sums, launches, samples = avg.dev.mean_read(avg.mean)
+        arrays.update({"mean.sums": sums, "mean.launches": np.array(launches), "mean.samples": np.array(samples),
+                       "mean.every": np.array(avg.every), "mean.start": np.array(avg.start_step)})
     for name in _STATE:
         if hasattr(s, name):
             arrays[f"{name}.current"] = getattr(s, name).current.to_numpy()
@@ -100,6 +130,25 @@ def load_state(sim, path):
         vc.vorticity.from_numpy(z["vorticity"])
         vc.vorticity_abs.from_numpy(z["vorticity_abs"])
     return int(z["step"])
+
+
+def mean_frame(sim, vis):
+    """The -vis 0 / 1 / 2 image of the mean flow (FluidSimulator.mean_fields), downloaded as an (X, Y, 3) array."""
+    dev = sim._dev
+    v, p = sim.mean_fields()
+    if vis == 0:
+        dev.vis_norm(sim.rgb_buf, v, p)
+    elif vis == 1:
+        dev.vis_pressure(sim.rgb_buf, p)
+    else:
+        dev.vis_vorticity(sim._solver.dx, sim.rgb_buf, v)
+    return sim.rgb_buf.to_numpy()
+
+
+def save_png(img, path):
+    from PIL import Image
+    img = np.clip(img, 0.0, 1.0)
+    Image.fromarray((np.flip(img.transpose(1, 0, 2), axis=0) * 255).astype(np.uint8)).save(path)
 
 
 def frame(sim, vis):
@@ -188,6 +237,16 @@ def main(argv=None):
         parser.error("--probe and --history-file need --history-every N")
     if args.history_every > 0 and not args.probe and args.body is None:
         parser.error("--history-every needs --probe X,Y or --body")
+    if args.mean_every < 0 or args.mean_start < 0:
+        parser.error("--mean-every and --mean-start must be >= 0")
+    if (args.mean_start or args.mean_file) and args.mean_every <= 0:
+        parser.error("--mean-start and --mean-file need --mean-every N")
+    if args.mean_every > 0 and args.load_state:
+        held = saved_mean(args.load_state)
+        if held is not None and held != (args.mean_every, args.mean_start):
+            print(f"--load-state {args.load_state}: its time average was taken with --mean-every {held[0]} --mean-start {held[1]}, "
+                  f"not {args.mean_every} / {args.mean_start}; continue with those or average without the checkpoint's sums", file=sys.stderr)
+            sys.exit(2)
     box = _body_box(parser, args.body, args.boundary_condition, res)
     probes = [_probe(parser, spec) for spec in args.probe]
     print(f"Boundary Condition: {args.boundary_condition}\ndt: {dt}\nRe: {args.reynolds_num}\nResolution: {res}\n"
@@ -211,6 +270,27 @@ def main(argv=None):
             history_file.parent.mkdir(parents=True, exist_ok=True)
             np.savez(str(history_file), **sim.history())
 
+    mean_file = None
+    if args.mean_every > 0:
+        mean_file = Path(args.mean_file) if args.mean_file else out / "mean.npz"
+        sim.start_averaging(every=args.mean_every, start_step=args.mean_start)
+        if args.load_state and load_mean(sim, args.load_state):
+            print(f"time average: continuing the checkpoint's ({sim._dev.mean_read(sim._averager.mean)[2]} samples so far)")
+
+    def write_mean():
+        if mean_file is None:
+            return
+        try:
+            avg = sim.averages()
+        except RuntimeError as e:
+            print(f"time average: {e}; no file written", file=sys.stderr)
+            return
+        mean_file.parent.mkdir(parents=True, exist_ok=True)
+        np.savez(str(mean_file), dt=np.array(dt), dx=np.array(dx), every=np.array(args.mean_every), start=np.array(args.mean_start), **avg)
+        if args.frame_every and args.visualization != 3:      # (-vis 3 is the dye: it is not averaged)
+            out.mkdir(exist_ok=True)
+            save_png(mean_frame(sim, args.visualization), out / "mean_vis.png")
+
     stats = None
     if args.stats_every > 0:
         stats = StatsWriter(sim, Path(args.stats_file) if args.stats_file else out / "stats.csv", dt, box, args.stop_on_nonfinite)
@@ -220,6 +300,7 @@ def main(argv=None):
             stats.close()
             print(f"step {step}: non-finite values (NaN / Inf) in v or p; stopping (--stop-on-nonfinite)", file=sys.stderr)
             write_history()
+            write_mean()
             dev.close()
             sys.exit(3)
 
@@ -229,10 +310,8 @@ def main(argv=None):
         sample(step)
     while step < last:
         if args.frame_every and step % args.frame_every == 0:
-            from PIL import Image
             out.mkdir(exist_ok=True)
-            img = np.clip(frame(sim, args.visualization), 0.0, 1.0)
-            Image.fromarray((np.flip(img.transpose(1, 0, 2), axis=0) * 255).astype(np.uint8)).save(out / f"{step:06}.png")
+            save_png(frame(sim, args.visualization), out / f"{step:06}.png")
         # steps until the next frame / dump / end: one chunk (a hipGraph replay with --graph, a plain loop otherwise)
         nxt = last
         if args.frame_every:
@@ -256,6 +335,7 @@ def main(argv=None):
     if stats:
         stats.close()
     write_history()
+    write_mean()
     dev.close()
 
 

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 11
+#define FS_ABI_VERSION 12
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -295,6 +295,34 @@ int fs_history_create(fs_ctx *ctx, int npoints, const int *points, int nfaces, c
 int fs_history_record(fs_ctx *ctx, fs_history *h, double dx, double limit, const fs_field *v, const fs_field *p);
 int fs_history_read(fs_ctx *ctx, fs_history *h, double *out, int max_records, int *n_records, long long *launches, int *dropped);
 int fs_history_free(fs_ctx *ctx, fs_history *h);
+
+/* Time averages (new): first and second moments of u, w and p summed on the device by a launch that can be captured in a hipGraph and
+ * recorded in a tape (csrc/fs_mean.h).  State: FS_MEAN_NPLANE planes of double over this context's OWNED rows, in the order S_u, S_w, S_p,
+ * S_uu, S_ww, S_uw, S_pp (56 bytes per cell), and two device counters: launches since creation and samples accumulated.
+ * create:     every >= 1, start >= 0; sums and counters zero.  An allocation that does not fit returns FS_ERR_HIP.
+ * accumulate: launch n (counted from 0) samples when n + 1 > start and (n + 1 - start) % every == 0; it then adds, on every not-wall cell
+ *             (mask != 1) of the owned rows, (double)u, (double)w, (double)p and the products (double)u * (double)u, w * w, u * w, p * p, each
+ *             formed and added in double - one lane per cell, samples in stream order: the sums are deterministic and an IEEE double loop
+ *             over the sampled fields reproduces them bit for bit.  limit > 0: v still owes limit_field(limit) (a deferred pass): u, w are
+ *             limited as that pass would store them.  Wall cells keep their sums.  Reads no ghost row, changes no field; a launch that
+ *             does not sample reads one counter per workgroup.  The counters advance on the device behind the launch.
+ * finalize:   (T)(S_u / n), (T)(S_w / n) into the 2-channel v_out and (T)(S_p / n) into the 1-channel p_out on the not-wall cells of the
+ *             owned rows, 0 on wall cells; n = samples (FS_ERR_STATE when 0).  Ghost rows of the targets are not written.
+ * read:       synchronises; sums_out (NULL: counters only) receives [FS_MEAN_NPLANE][ny_local][X] doubles, x contiguous.
+ * write:      the inverse of read (resume): sums_in in the same layout, 0 <= samples <= launches.
+ * reset:      sums and the sample count to zero; the launch count (and with it the phase of `every` / `start`) runs on.
+ * free:       a graph or tape that holds the launch must not be replayed afterwards; during a capture the release is deferred to its end
+ *             (as fs_history_free).
+ * create, finalize, read, write and reset return FS_ERR_STATE during graph capture / tape recording.                                   */
+#define FS_MEAN_NPLANE 7
+typedef struct fs_mean fs_mean;
+int fs_mean_create(fs_ctx *ctx, long long every, long long start, fs_mean **out);
+int fs_mean_accumulate(fs_ctx *ctx, fs_mean *m, double limit, const fs_field *v, const fs_field *p);
+int fs_mean_finalize(fs_ctx *ctx, fs_mean *m, fs_field *v_out, fs_field *p_out);
+int fs_mean_read(fs_ctx *ctx, fs_mean *m, double *sums_out, long long *launches, long long *samples);
+int fs_mean_write(fs_ctx *ctx, fs_mean *m, const double *sums_in, long long launches, long long samples);
+int fs_mean_reset(fs_ctx *ctx, fs_mean *m);
+int fs_mean_free(fs_ctx *ctx, fs_mean *m);
 
 /* ---- pointwise -------------------------------------------------------------------------------- */
 /* limit_field   fs/solver.py:38-43 ;  clamp_field   fs/solver.py:46-49                           */
