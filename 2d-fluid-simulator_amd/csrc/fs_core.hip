@@ -1,5 +1,5 @@
 // fs_core.hip - C-ABI entry points (include/fs_hip.h): contexts, fields, scene upload, boundary kernels, pointwise passes, visualisation,
-// hipGraph capture, command tapes, profiling, box-rate probes.  Transport kernels: fs_transport.hip; pressure kernels: fs_pressure.hip.
+// tracer particles, hipGraph capture, command tapes, profiling, box-rate probes.  Transport kernels: fs_transport.hip; pressure kernels: fs_pressure.hip.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +11,7 @@
 #include <unordered_map>
 
 #include "fs_launch.h"
+#include "fs_tracer.h"
 
 namespace fs {
 
@@ -22,6 +23,14 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line)
     snprintf(buf, sizeof buf, "HIP error %d (%s) in %s at %s:%d", (int)e, hipGetErrorString(e), what, file, line);
     g_err = buf;
     return FS_ERR_HIP;
+}
+
+static void tracer_release(fs_tracer *t)
+{
+    if (t->d_pos) hipFree(t->d_pos);
+    if (t->d_int) hipFree(t->d_int);
+    if (t->d_count) hipFree(t->d_count);
+    delete t;
 }
 
 // ---- f64-multiply division (fs_device.h f64div): the identity checked ON THE DEVICE for one divisor -------------------------------
@@ -678,6 +687,9 @@ int fs_destroy(fs_ctx *ctx)
     for (fs_mean *m : ctx->means) mean_release(m);
     for (fs_mean *m : ctx->deferred_mean) mean_release(m);
     ctx->means.clear();
+    for (fs_tracer *t : ctx->tracers) tracer_release(t);
+    for (fs_tracer *t : ctx->deferred_tracer) tracer_release(t);
+    ctx->tracers.clear();
     if (ctx->d_mask) hipFree(ctx->d_mask);
     if (ctx->d_bc_const) hipFree(ctx->d_bc_const);
     if (ctx->d_bc_dye) hipFree(ctx->d_bc_dye);
@@ -1411,6 +1423,130 @@ int fs_vis_dye(fs_ctx *ctx, fs_field *rgb, const fs_field *dye, int row_begin, i
     return visualize(ctx, 3, 1.0, rgb, dye, nullptr, row_begin, row_end);
 }
 
+// ---- tracer particles (fs_tracer.h) -------------------------------------------------------------------------
+static_assert(TR_LEFT == FS_TRACER_LEFT && TR_WALL == FS_TRACER_WALL && TR_EXPIRED == FS_TRACER_EXPIRED, "fs_tracer.h and include/fs_hip.h disagree");
+#define FS_TRACER_HANDLE(t) FS_REQUIRE((t)->ctx == ctx && ctx->tracers.count(t), "tracer set from another context or freed")
+#define FS_TRACER_NO_CAPTURE(what) \
+    if (ctx->capturing || ctx->tape_rec) { set_error("tracer " what " during graph capture / tape recording"); return FS_ERR_STATE; }
+
+static TracerDev tracer_dev(const fs_tracer *t)
+{
+    const size_t n = (size_t)t->n;
+    return TracerDev{t->n, t->d_pos, t->d_pos + n, t->d_int, t->d_int + n, t->d_int + 2 * n, t->d_pos + 2 * n, t->d_pos + 3 * n, t->d_count};
+}
+
+int fs_tracer_create(fs_ctx *ctx, int n, const double *seeds_xy, int respawn, int max_age, fs_tracer **out)
+{
+    FS_REQUIRE(ctx && seeds_xy && out, "null argument");
+    FS_REQUIRE(n >= 1, "a tracer set needs at least one particle");
+    FS_REQUIRE(max_age >= 0, "max_age must be >= 0");
+    FS_TRACER_NO_CAPTURE("create")
+    if (ctx->comm || ctx->halo != 0 || ctx->y0 != 0 || ctx->nyl != ctx->Y) {
+        set_error("tracer particles need a single-context grid: on slabs they would have to migrate between ranks");
+        return FS_ERR_UNSUPPORTED;
+    }
+    // (fs_create admits no grid below 4 x 4: the corner index range [0, X - 2] x [0, Y - 2] of the interpolation is never empty)
+    std::vector<double> pos(4 * (size_t)n);
+    for (int k = 0; k < n; ++k) {
+        const double x = seeds_xy[2 * k], y = seeds_xy[2 * k + 1];
+        FS_REQUIRE(x >= 0.0 && x < (double)ctx->X && y >= 0.0 && y < (double)ctx->Y, "tracer seed outside the domain");
+        pos[k] = pos[2 * (size_t)n + k] = x;
+        pos[(size_t)n + k] = pos[3 * (size_t)n + k] = y;
+    }
+    FS_HIP(hipSetDevice(ctx->device));
+    fs_tracer *t = new fs_tracer();
+    t->ctx = ctx; t->n = n; t->respawn = respawn ? 1 : 0; t->max_age = max_age;
+    hipError_t e = hipMalloc(&t->d_pos, pos.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&t->d_int, 3 * (size_t)n * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&t->d_count, sizeof(long long));
+    if (e == hipSuccess) e = hipMemcpyAsync(t->d_pos, pos.data(), pos.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_int, 0, 3 * (size_t)n * sizeof(int), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_count, 0, sizeof(long long), ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // (the source is this frame's memory)
+    if (e != hipSuccess) { tracer_release(t); return hip_fail(e, "fs_tracer_create", __FILE__, __LINE__); }
+    ctx->tracers.insert(t);
+    *out = t;
+    return FS_OK;
+}
+
+int fs_tracer_advance(fs_ctx *ctx, fs_tracer *t, double h, double limit, const fs_field *v)
+{
+    FS_REQUIRE(ctx && t, "null argument");
+    FS_TRACER_HANDLE(t);
+    FS_FIELD(v, 2);
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    // everything the launch needs is in `t` and the field: no allocation, copy or synchronisation here (the closure is captured)
+    const TracerDev td = tracer_dev(t);
+    const dim3 grid((t->n + TRACER_WG - 1) / TRACER_WG);
+    const int Y = ctx->Y, respawn = t->respawn, max_age = t->max_age;
+    FS_DISPATCH(ctx, {
+        return launch(ctx, "tracer_advance", [=] {
+            if (limit > 0.0)
+                FS_KLAUNCH((k_tracer_advance<T, true>), grid, dim3(TRACER_WG), 0, ctx->stream, ctx->grid(), Y, h, limit, respawn, max_age, td, (const T *)v->d);
+            else
+                FS_KLAUNCH((k_tracer_advance<T, false>), grid, dim3(TRACER_WG), 0, ctx->stream, ctx->grid(), Y, h, limit, respawn, max_age, td, (const T *)v->d);
+        });
+    })
+}
+
+int fs_tracer_read(fs_ctx *ctx, fs_tracer *t, double *pos, int *ints, long long *launches)
+{
+    FS_REQUIRE(ctx && t, "null argument");
+    FS_TRACER_HANDLE(t);
+    FS_TRACER_NO_CAPTURE("read")
+    FS_HIP(hipSetDevice(ctx->device));
+    const size_t n = (size_t)t->n;
+    if (pos) FS_HIP(hipMemcpyAsync(pos, t->d_pos, 4 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (ints) FS_HIP(hipMemcpyAsync(ints, t->d_int, 3 * n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (launches) FS_HIP(hipMemcpyAsync(launches, t->d_count, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_tracer_write(fs_ctx *ctx, fs_tracer *t, const double *pos, const int *ints, long long launches)
+{
+    FS_REQUIRE(ctx && t && pos && ints, "null argument");
+    FS_TRACER_HANDLE(t);
+    FS_REQUIRE(launches >= 0, "launches must be >= 0");
+    FS_TRACER_NO_CAPTURE("write")
+    const size_t n = (size_t)t->n;
+    for (size_t k = 0; k < n; ++k)
+        FS_REQUIRE(ints[k] >= 0 && ints[n + k] >= 0 && ints[n + k] <= 3 && ints[2 * n + k] >= 0, "tracer state: age / respawns < 0 or status outside 0 .. 3");
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemcpyAsync(t->d_pos, pos, 4 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipMemcpyAsync(t->d_int, ints, 3 * n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipMemcpyAsync(t->d_count, &launches, sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));      // (the sources are the caller's / this frame's memory)
+    return FS_OK;
+}
+
+int fs_tracer_draw(fs_ctx *ctx, fs_tracer *t, double r, double g, double b, fs_field *rgb)
+{
+    FS_REQUIRE(ctx && t, "null argument");
+    FS_TRACER_HANDLE(t);
+    FS_FIELD(rgb, 3);
+    const TracerDev td = tracer_dev(t);
+    const dim3 grid((t->n + TRACER_WG - 1) / TRACER_WG);
+    const int Y = ctx->Y;
+    FS_DISPATCH(ctx, {
+        return launch(ctx, "tracer_draw", [=] {
+            FS_KLAUNCH((k_tracer_draw<T>), grid, dim3(TRACER_WG), 0, ctx->stream, ctx->grid(), Y, td, (T)r, (T)g, (T)b, (T *)rgb->d);
+        });
+    })
+}
+
+int fs_tracer_free(fs_ctx *ctx, fs_tracer *t)
+{
+    if (!t) return FS_OK;
+    FS_REQUIRE(ctx && t->ctx == ctx && ctx->tracers.count(t), "tracer set from another context or freed");
+    ctx->tracers.erase(t);
+    if (ctx->capturing) { ctx->deferred_tracer.push_back(t); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
+    tracer_release(t);
+    return FS_OK;
+}
+
 // ---- hipGraph capture ---------------------------------------------------------------------------------------
 int fs_graph_begin(fs_ctx *ctx)
 {
@@ -1436,6 +1572,8 @@ int fs_graph_end(fs_ctx *ctx, int *graph_id)
     ctx->deferred_hist.clear();
     for (fs_mean *m : ctx->deferred_mean) mean_release(m);            // and time averages (fs_mean_free)
     ctx->deferred_mean.clear();
+    for (fs_tracer *t : ctx->deferred_tracer) tracer_release(t);      // and tracer sets (fs_tracer_free)
+    ctx->deferred_tracer.clear();
     if (ec != hipSuccess) return hip_fail(ec, "hipStreamEndCapture", __FILE__, __LINE__);
     hipGraphExec_t ex = nullptr;
     hipError_t e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);

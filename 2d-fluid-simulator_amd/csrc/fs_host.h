@@ -131,6 +131,8 @@ struct fs_ctx {
     std::vector<fs_history *> deferred_hist; // fs_history_free during a hipGraph capture: released when the capture ends
     std::set<fs_mean *> means;               // live time averages (fs_mean_create), released with the context
     std::vector<fs_mean *> deferred_mean;    // fs_mean_free during a hipGraph capture: released when the capture ends
+    std::set<fs_tracer *> tracers;           // live tracer sets (fs_tracer_create), released with the context
+    std::vector<fs_tracer *> deferred_tracer;  // fs_tracer_free during a hipGraph capture: released when the capture ends
     // tuning knobs (env FS_MARCH=0: one-cell-per-lane kernels only)
     bool use_march = true;
     bool use_pairs = true;     // lanes of 2 cells: even widths (every `res`); use_march: the quad kernels, X % 4 == 0
@@ -190,6 +192,15 @@ struct fs_mean {
     size_t plane = 0;               // doubles from one plane to the next: nyl * P + MEAN_PAD
     double *d_sums = nullptr;       // [MEAN_PLANES][plane]
     long long *d_state = nullptr;   // [MEAN_STATE]
+};
+
+// tracer particles (fs_tracer_*, fs_tracer.h): the particle arrays and the launch counter
+struct fs_tracer {
+    fs_ctx *ctx = nullptr;
+    int n = 0, respawn = 1, max_age = 0;
+    double *d_pos = nullptr;        // [4][n]: x, y, x_seed, y_seed
+    int *d_int = nullptr;           // [3][n]: age, status, respawns
+    long long *d_count = nullptr;   // launches since creation
 };
 
 namespace fs {

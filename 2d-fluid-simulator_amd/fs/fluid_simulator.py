@@ -15,6 +15,7 @@ from .boundary_condition import get_boundary_condition
 from .history import Recorder, body_faces, check_probes
 from .pressure_updater import JacobiPressureUpdater, RedBlackSorPressureUpdater
 from .solver import CipMacSolver, DyeCipMacSolver, DyeMacSolver, MacSolver
+from .tracers import Tracers, check_seeds
 from .vorticity_confinement import VorticityConfinement
 
 _WALL_COLOR = (0.5, 0.7, 0.5)   # fs/fluid_simulator.py:17 (applied by the visualisation kernels, csrc/fs_kernels.h k_visualize)
@@ -83,11 +84,12 @@ class FluidSimulator:
         self._recorder = None      # fs.history.Recorder while record_history() is on
         self._last_recorder = None  # ... and after stop_history(): what history() still returns
         self._averager = None      # fs.averages.Averager while start_averaging() is on
+        self._tracers = None       # fs.tracers.Tracers while seed_tracers() is on
 
     def _update(self):
-        """One solver step, then the history record if a recorder is attached and the accumulation of the time averages if an averager is:
-        what step(), the periods capture_period() captures and the slab periods tape_period() logs all run (so a graph or tape holds these
-        launches exactly when _signature() says so)."""
+        """One solver step, then the history record if a recorder is attached, the accumulation of the time averages if an averager is and
+        the advance of the tracer particles if a set is: what step(), the periods capture_period() captures and the slab periods
+        tape_period() logs all run (so a graph or tape holds these launches exactly when _signature() says so)."""
         self._solver.update()
         rec = self._recorder
         if rec is not None:
@@ -100,6 +102,9 @@ class FluidSimulator:
         if avg is not None:
             v, p = self._solver.get_fields()[:2]
             self._dev.mean_accumulate(avg.mean, v, p)
+        tr = self._tracers
+        if tr is not None:
+            self._dev.tracer_advance(tr.set, self._solver.dt / self._solver.dx, self._solver.get_fields()[0])
 
     def step(self):
         self._update()
@@ -153,6 +158,8 @@ class FluidSimulator:
             sig.append(self._recorder.token)        # (graphs / tapes with the record launch in them are never replayed without it, or vice versa)
         if self._averager is not None:
             sig.append(self._averager.token)        # (likewise the accumulation launch of the time averages)
+        if self._tracers is not None:
+            sig.append(self._tracers.token)         # (and the advance of the tracer particles)
         return tuple(sig)
 
     _LONG_STEPS = 16     # steps per long-form graph (capture_period)
@@ -451,6 +458,61 @@ class FluidSimulator:
             self._drop_cached(avg.token)
         self._dev.mean_free(avg.mean)
         self._averager = None
+
+    # -- tracer particles (new): pathlines and streaklines advanced on the device ------------------------------------------------------
+    def seed_tracers(self, seeds, respawn=True, max_age=0):
+        """From the next step on, N passive particles ride the step: seeds float64 (N, 2) in CELL units (cell (i, j) covers [i, i + 1) x
+        [j, j + 1); fs.tracers.seed_line / seed_grid / seed_random build them), each inside the domain in a fluid or inflow cell
+        (ValueError naming the first offender otherwise).  After every step each alive particle takes one midpoint step in the velocity
+        the step left (include/fs_hip.h fs_tracer_advance).  A particle that leaves the domain or enters an outflow cell (LEFT), enters a
+        wall cell (WALL) or reaches max_age > 0 steps (EXPIRED) starts again at its seed with respawn=True - a steady release: streaklines -
+        and keeps its fate as status with respawn=False - pathlines.  The launch is part of the step: it is captured into the replayed
+        graphs, and run() is not cut into chunks by it.  48 bytes per particle; changes no field and no trajectory.  tracers() returns the
+        state.  Raises while a set is attached already and during a graph capture; single-GPU contexts only (FsError on slabs)."""
+        from ._lib import FsError
+        dev, s = self._dev, self._solver
+        if getattr(dev, "capturing", False):
+            raise RuntimeError("seed_tracers during a graph capture")
+        if self._tracers is not None:
+            raise RuntimeError("a tracer set is attached already: stop_tracers() first")
+        if dev.nranks > 1:
+            raise FsError("tracer particles need a single-GPU context: on slabs they would have to migrate between ranks (not implemented)")
+        max_age = int(max_age)
+        if max_age < 0:
+            raise ValueError("max_age must be >= 0")
+        seeds = check_seeds(np.asarray(s._bc.mask), seeds)
+        self._tracers = Tracers(dev, dev.tracer_create(seeds, respawn, max_age), seeds, respawn, max_age)
+
+    def _trc(self):
+        if self._tracers is None:
+            raise RuntimeError("no tracers: call seed_tracers() first")
+        return self._tracers
+
+    def tracers(self):
+        """The particles now (one download): {"x", "y": float64 (N,) in cell units, "age": int32 steps since the seed or the last respawn
+        (fs.tracers.residence_time), "status": int32 fs.tracers.FATE_*, "respawns": int32, "seeds": float64 (N, 2), "steps": steps since
+        seed_tracers()}.  Not allowed during a graph capture."""
+        tr = self._trc()
+        return tr.dev.tracer_read(tr.set)
+
+    def draw_tracers(self, rgb_field=None, color=(1, 1, 1)):
+        """Overlay the alive particles on an image field (default: self.rgb_buf, i.e. after any get_*_field()): pixel (floor x, floor y)
+        takes `color`.  Returns the field."""
+        tr = self._trc()
+        rgb = self.rgb_buf if rgb_field is None else rgb_field
+        tr.dev.tracer_draw(tr.set, rgb, color)
+        return rgb
+
+    def stop_tracers(self):
+        """Detach the tracer set and free its device memory; the cached graphs that hold its launch are freed first.  Nothing is kept on
+        the host: call tracers() before.  Inside a graph capture the device memory is released when the capture ends."""
+        tr = self._tracers
+        if tr is None:
+            return
+        if not getattr(self._dev, "capturing", False):      # (inside a capture no graph can be freed: theirs stay cached, never matched again)
+            self._drop_cached(tr.token)
+        self._dev.tracer_free(tr.set)
+        self._tracers = None
 
     # -- visualisation (fs/fluid_simulator.py:22-58): device kernels; like the reference these return the image FIELD ----
     def get_norm_field(self):

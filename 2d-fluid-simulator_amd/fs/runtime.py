@@ -1008,6 +1008,88 @@ class DeviceBase:
             self._p_mean_free(mean._h)
             mean._h = None
 
+    # ---- tracer particles (include/fs_hip.h fs_tracer_*): N particles in double cell coordinates, advanced by one launch per step -------
+    def tracer_create(self, seeds, respawn=True, max_age=0):
+        """A device tracer set for FluidSimulator.seed_tracers: seeds float64 (N, 2) in cell units, N >= 1, inside the domain (whether
+        the cells are fluid is fs.tracers.check_seeds' business).  48 bytes per particle.  Single-context grids only (FsError on a slab);
+        not allowed during a graph capture."""
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("tracer_create during a graph capture")
+        if self.nranks > 1:
+            raise _lib.FsError("tracer particles need a single-GPU context: on slabs they would have to migrate between ranks (not implemented)")
+        seeds = np.ascontiguousarray(seeds, np.float64)
+        if seeds.ndim != 2 or seeds.shape[1] != 2 or len(seeds) < 1:
+            raise ValueError(f"seeds must have shape (N, 2) with N >= 1, got {seeds.shape}")
+        max_age = int(max_age)
+        if max_age < 0:
+            raise ValueError("max_age must be >= 0")
+        h = self._p_tracer_create(seeds, bool(respawn), max_age)
+        tr = TracerSet(h, len(seeds), bool(respawn), max_age)
+        self._handle_serial[id(h)] = tr.serial
+        return tr
+
+    def tracer_advance(self, tr, h, v):
+        """One midpoint step h = dt / dx of every alive particle in the velocity field v; the launch counter advances on the device.  A
+        limit_field v still owes stays deferred: the kernel limits the corner values as the pass would store them.  Not a _run: no flush,
+        no exchange (writes no field)."""
+        args = (tr._h, float(h), float(v.pending_limit) if v.pending_limit is not None else 0.0, v._h)
+        if self._oplog is not None:
+            self._oplog.append(("k", "tracer_advance", args, ()))
+        self._p_kernel("tracer_advance", *args)
+
+    def tracer_read(self, tr):
+        """-> {"x", "y": float64 (N,), "age", "status", "respawns": int32 (N,), "seeds": float64 (N, 2), "steps": launches so far}: one
+        download.  Not allowed during a graph capture."""
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("tracer_read during a graph capture: the state is a download (read between captures / replays)")
+        pos, ints, launches = self._p_tracer_read(tr._h, tr.n)
+        return {"x": pos[0].copy(), "y": pos[1].copy(), "age": ints[0].copy(), "status": ints[1].copy(), "respawns": ints[2].copy(),
+                "seeds": np.ascontiguousarray(pos[2:4].T), "steps": int(launches)}
+
+    def tracer_write(self, tr, state):
+        """Restore what tracer_read returned (checkpoints): the same keys, arrays of the set's N."""
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("tracer_write during a graph capture")
+        n = tr.n
+        seeds = np.asarray(state["seeds"], np.float64)
+        if seeds.shape != (n, 2):
+            raise ValueError(f"expected seeds of shape {(n, 2)}, got {seeds.shape}")
+        pos = np.empty((4, n), np.float64)
+        ints = np.empty((3, n), np.int32)
+        for row, key in ((0, "x"), (1, "y")):
+            a = np.asarray(state[key], np.float64)
+            if a.shape != (n,):
+                raise ValueError(f"expected {key} of shape {(n,)}, got {a.shape}")
+            pos[row] = a
+        pos[2], pos[3] = seeds[:, 0], seeds[:, 1]
+        for row, key in enumerate(("age", "status", "respawns")):
+            a = np.asarray(state[key])
+            if a.shape != (n,):
+                raise ValueError(f"expected {key} of shape {(n,)}, got {a.shape}")
+            ints[row] = a
+        if (ints[0] < 0).any() or (ints[2] < 0).any() or (ints[1] < 0).any() or (ints[1] > 3).any() or int(state["steps"]) < 0:
+            raise ValueError("tracer state: age, respawns and steps must be >= 0 and status in 0 .. 3")
+        self._p_tracer_write(tr._h, pos, ints, int(state["steps"]))
+
+    def tracer_draw(self, tr, rgb, color=(1.0, 1.0, 1.0)):
+        """Store `color` into pixel (floor x, floor y) of the 3-channel field rgb for every alive particle."""
+        r, g, b = (float(c) for c in color)
+        self._p_kernel("tracer_draw", tr._h, r, g, b, rgb._h)
+
+    def tracer_free(self, tr):
+        if tr._h is not None:
+            self._handle_serial.pop(id(tr._h), None)
+            self._p_tracer_free(tr._h)
+            tr._h = None
+
+
+class TracerSet:
+    """A device tracer set (DeviceBase.tracer_create): handle, particle count, respawn, max_age."""
+
+    def __init__(self, h, n, respawn, max_age):
+        self._h, self.n, self.respawn, self.max_age = h, n, respawn, max_age
+        self.serial = next(_serials)
+
 
 class Mean:
     """Device accumulators of a time average (DeviceBase.mean_create): handle, every, start."""
@@ -1223,6 +1305,26 @@ class Device(DeviceBase):
     def _p_mean_free(self, h):
         if self._ctx is not None:
             _lib.call("fs_mean_free", self._ctx, h)
+
+    def _p_tracer_create(self, seeds, respawn, max_age):
+        h = ctypes.c_void_p()
+        _lib.call("fs_tracer_create", self._ctx, len(seeds), seeds.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(respawn), max_age,
+                  ctypes.byref(h))
+        return h
+
+    def _p_tracer_read(self, h, n):
+        pos, ints, launches = np.empty((4, n), np.float64), np.empty((3, n), np.int32), ctypes.c_longlong()
+        _lib.call("fs_tracer_read", self._ctx, h, pos.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                  ints.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.byref(launches))
+        return pos, ints, launches.value
+
+    def _p_tracer_write(self, h, pos, ints, launches):
+        _lib.call("fs_tracer_write", self._ctx, h, pos.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                  ints.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), launches)
+
+    def _p_tracer_free(self, h):
+        if self._ctx is not None:
+            _lib.call("fs_tracer_free", self._ctx, h)
 
     def _p_allreduce_array(self, a):
         a = np.ascontiguousarray(a, np.float64).copy()

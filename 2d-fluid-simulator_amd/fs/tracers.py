@@ -1,0 +1,113 @@
+"""Host side of the tracer particles (new; the reference has none): seed builders, the seed check, fate codes and the residence time.
+Pure NumPy: testable without a device.
+
+The advance itself is a device launch per step (csrc/fs_tracer.h, include/fs_hip.h fs_tracer_*), driven by FluidSimulator.seed_tracers /
+tracers / draw_tracers / stop_tracers.  Positions are float64 in CELL units: cell (i, j) covers [i, i + 1) x [j, j + 1) and its stored value
+sits at (i + 0.5, j + 0.5)."""
+import numpy as np
+
+FLUID, WALL, INFLOW, OUTFLOW = 0, 1, 2, 3
+# status of a particle (fs_tracer_read): alive, or the fate that ended it when the set does not respawn
+FATE_ALIVE, FATE_LEFT, FATE_WALL, FATE_EXPIRED = 0, 1, 2, 3
+KEYS = ("x", "y", "age", "status", "respawns", "seeds", "steps")      # what FluidSimulator.tracers() returns
+
+
+def _as_seeds(seeds):
+    seeds = np.asarray(seeds, np.float64)
+    if seeds.ndim != 2 or seeds.shape[1] != 2:
+        raise ValueError(f"seeds must have shape (N, 2), got {seeds.shape}")
+    return seeds
+
+
+def _inside(mask, seeds):
+    X, Y = mask.shape
+    x, y = seeds[:, 0], seeds[:, 1]
+    return (x >= 0) & (x < X) & (y >= 0) & (y < Y)        # (False for NaN)
+
+
+def fluid_only(mask, seeds):
+    """The seeds that lie inside the domain in a FLUID or INFLOW cell (the filter the seed builders share) -> (kept seeds, dropped count)."""
+    mask, seeds = np.asarray(mask), _as_seeds(seeds)
+    ok = _inside(mask, seeds)
+    cells = np.floor(seeds[ok]).astype(np.int64)
+    m = mask[cells[:, 0], cells[:, 1]]
+    ok[np.nonzero(ok)[0][(m != FLUID) & (m != INFLOW)]] = False
+    return np.ascontiguousarray(seeds[ok]), int(len(seeds) - ok.sum())
+
+
+def check_seeds(mask, seeds):
+    """Seeds as a contiguous float64 (N, 2) array, N >= 1, every one inside the domain and in a FLUID or INFLOW cell; ValueError naming
+    the first offender otherwise."""
+    mask, seeds = np.asarray(mask), _as_seeds(seeds)
+    if len(seeds) < 1:
+        raise ValueError("a tracer set needs at least one seed")
+    X, Y = mask.shape
+    inside = _inside(mask, seeds)
+    if not inside.all():
+        k = int(np.nonzero(~inside)[0][0])
+        raise ValueError(f"seed {k} at ({seeds[k, 0]!r}, {seeds[k, 1]!r}) lies outside the domain [0, {X}) x [0, {Y})")
+    cells = np.floor(seeds).astype(np.int64)
+    m = mask[cells[:, 0], cells[:, 1]]
+    bad = (m != FLUID) & (m != INFLOW)
+    if bad.any():
+        k = int(np.nonzero(bad)[0][0])
+        kind = {WALL: "a wall", OUTFLOW: "an outflow"}.get(int(m[k]), f"a mask-{int(m[k])}")
+        raise ValueError(f"seed {k} at ({seeds[k, 0]!r}, {seeds[k, 1]!r}) lies in {kind} cell ({cells[k, 0]}, {cells[k, 1]})")
+    return np.ascontiguousarray(seeds)
+
+
+def seed_line(p0, p1, n):
+    """n points from p0 to p1 (both included; n == 1: the midpoint), float64 (n, 2), cell units."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    p0, p1 = np.asarray(p0, np.float64), np.asarray(p1, np.float64)
+    if p0.shape != (2,) or p1.shape != (2,):
+        raise ValueError("p0 and p1 must be (x, y)")
+    t = np.array([0.5]) if n == 1 else np.arange(n, dtype=np.float64) / np.float64(n - 1)
+    return p0[None, :] + t[:, None] * (p1 - p0)[None, :]
+
+
+def seed_grid(box, nx, ny):
+    """nx x ny points at the centres of an even partition of box = (x0, y0, x1, y1), float64 (nx * ny, 2), x varying slowest."""
+    x0, y0, x1, y1 = (float(b) for b in box)
+    nx, ny = int(nx), int(ny)
+    if nx < 1 or ny < 1:
+        raise ValueError("nx and ny must be >= 1")
+    xs = x0 + (np.arange(nx, dtype=np.float64) + 0.5) * ((x1 - x0) / nx)
+    ys = y0 + (np.arange(ny, dtype=np.float64) + 0.5) * ((y1 - y0) / ny)
+    gx, gy = np.meshgrid(xs, ys, indexing="ij")
+    return np.stack([gx.ravel(), gy.ravel()], axis=1)
+
+
+def seed_random(mask, n, rng_seed=0):
+    """n points, each uniform inside a FLUID cell drawn uniformly from all FLUID cells (np.random.default_rng(rng_seed): the same seeds for
+    the same arguments), float64 (n, 2)."""
+    mask = np.asarray(mask)
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    cells = np.argwhere(mask == FLUID)
+    if len(cells) == 0:
+        raise ValueError("the mask has no fluid cell")
+    rng = np.random.default_rng(rng_seed)
+    pick = cells[rng.integers(0, len(cells), n)]
+    cell = pick.astype(np.float64)
+    # (a cell index plus a float64 just below 1 can round up to the next integer: keep the point inside its cell)
+    return np.minimum(cell + rng.random((n, 2)), np.nextafter(cell + 1.0, 0.0))
+
+
+def residence_time(age, dt):
+    """Simulated time since a particle was seeded or last respawned: age * dt."""
+    return np.asarray(age, np.float64) * np.float64(dt)
+
+
+class Tracers:
+    """One tracer set of a FluidSimulator (seed_tracers): the device set and its parameters."""
+
+    def __init__(self, dev, set_, seeds, respawn, max_age):
+        self.dev, self.set, self.seeds, self.respawn, self.max_age = dev, set_, seeds, bool(respawn), int(max_age)
+
+    @property
+    def token(self):
+        return ("tracer", self.set.serial)

@@ -12,6 +12,9 @@ The reference opens a GGUI window and steps forever; here the loop runs `--steps
     GPU, written to `--history-file` (.npz) at the end of the run.
   * average u, w, p and their second moments over time on the GPU (`--mean-every`, `--mean-start`), written to `--mean-file` (.npz) at
     the end of the run; the sums travel with `--save-state` / `--load-state`, so an average continues over restarts.
+  * follow tracer particles on the GPU (`--tracers N`, `--tracer-line x0,y0,x1,y1,n`): pathlines (`--tracer-once`) or streaklines, written
+    to `--tracer-file` (.npz) at the end of the run and every `--tracer-dump-every` steps, drawn into the `-vis` frames; the particle state
+    travels with `--save-state` / `--load-state`.
 """
 import argparse
 import os
@@ -74,6 +77,19 @@ def build_parser():
     p.add_argument("--mean-file", type=str, default=None,
                    help=".npz of the averages: samples, steps, u, w, p, uu, ww, uw, p_rms, tke, mask, dt, dx, every, start "
                         "(default: <out>/mean.npz)")
+    p.add_argument("--tracers", type=int, default=0,
+                   help="follow N tracer particles seeded at random in fluid cells (FluidSimulator.seed_tracers; 0: none unless --tracer-line)")
+    p.add_argument("--tracer-seed", type=int, default=None, help="seed of the random generator behind --tracers (default 0)")
+    p.add_argument("--tracer-line", type=str, action="append", default=[], metavar="X0,Y0,X1,Y1,N",
+                   help="N tracer seeds on the line from (X0, Y0) to (X1, Y1), cell units; seeds that are not in a fluid cell are dropped; "
+                        "may be repeated")
+    p.add_argument("--tracer-once", action="store_true",
+                   help="a particle that leaves, hits a wall or expires stays where it was (pathlines); default: it starts again at its seed "
+                        "(streaklines)")
+    p.add_argument("--tracer-max-age", type=int, default=None, help="a particle expires after this many steps (default 0: never)")
+    p.add_argument("--tracer-file", type=str, default=None,
+                   help=".npz of the particles after the last step: x, y, age, status, respawns, seeds, steps (default: <out>/tracers.npz)")
+    p.add_argument("--tracer-dump-every", type=int, default=0, help="also write <out>/tracers_<step>.npz every N steps")
     return p
 
 
@@ -99,9 +115,46 @@ def load_mean(sim, path):
     return True
 
 
+def saved_tracers(path):
+    """(respawn, max_age, N) of the tracer set a checkpoint holds, or None."""
+    z = np.load(_npz_path(path))
+    return (bool(z["tracer.respawn"]), int(z["tracer.max_age"]), len(z["tracer.x"])) if "tracer.x" in z.files else None
+
+
+def load_tracers(sim, path):
+    """Seed the checkpoint's tracer set and restore its state -> whether the checkpoint held one."""
+    from fs.tracers import KEYS
+    z = np.load(_npz_path(path))
+    if "tracer.x" not in z.files:
+        return False
+    sim.seed_tracers(z["tracer.seeds"], respawn=bool(z["tracer.respawn"]), max_age=int(z["tracer.max_age"]))
+    tr = sim._tracers
+    tr.dev.tracer_write(tr.set, {k: z[f"tracer.{k}"] for k in KEYS})
+    return True
+
+
+def tracer_seeds(mask, n_random, rng_seed, lines):
+    """The seeds the flags ask for: --tracers N random ones, then every --tracer-line (x0, y0, x1, y1, n) without the points that do not
+    lie in a fluid cell -> (seeds (N, 2), messages about dropped points)."""
+    from fs.tracers import fluid_only, seed_line, seed_random
+    parts, notes = [], []
+    if n_random > 0:
+        parts.append(seed_random(mask, n_random, rng_seed))
+    for x0, y0, x1, y1, n in lines:
+        kept, dropped = fluid_only(mask, seed_line((x0, y0), (x1, y1), n))
+        if dropped:
+            notes.append(f"--tracer-line {x0:g},{y0:g},{x1:g},{y1:g},{n}: dropped {dropped} of {n} seeds (not in a fluid cell)")
+        parts.append(kept)
+    return (np.concatenate(parts) if parts else np.zeros((0, 2))), notes
+
+
 def save_state(sim, path, step):
     s = sim._solver
     arrays = {"step": np.array(step)}
+    tr = getattr(sim, "_tracers", None)
+    if tr is not None:
+        arrays.update({f"tracer.{k}": np.asarray(a) for k, a in tr.dev.tracer_read(tr.set).items()})
+        arrays.update({"tracer.respawn": np.array(tr.respawn), "tracer.max_age": np.array(tr.max_age)})
     avg = getattr(sim, "_averager", None)
     if avg is not None:
         sums, launches, samples = avg.dev.mean_read(avg.mean)
@@ -152,14 +205,19 @@ def save_png(img, path):
 
 
 def frame(sim, vis):
-    """The image the reference's window would show (main.py:93-107), downloaded as an (X, Y, 3) array."""
+    """The image the reference's window would show (main.py:93-107), with the tracer particles on top when there are any, downloaded as an
+    (X, Y, 3) array."""
     if vis == 0:
-        return sim.get_norm_field().to_numpy()
-    if vis == 1:
-        return sim.get_pressure_field().to_numpy()
-    if vis == 2:
-        return sim.get_vorticity_field().to_numpy()
-    return sim.get_dye_field().to_numpy()
+        img = sim.get_norm_field()
+    elif vis == 1:
+        img = sim.get_pressure_field()
+    elif vis == 2:
+        img = sim.get_vorticity_field()
+    else:
+        img = sim.get_dye_field()
+    if getattr(sim, "_tracers", None) is not None:
+        sim.draw_tracers(img)
+    return img.to_numpy()
 
 
 class StatsWriter:
@@ -201,6 +259,17 @@ def _body_box(parser, spec, num, res):
     if len(box) != 4 or not (0 <= box[0] <= box[2] <= 2 * res and 0 <= box[1] <= box[3] <= res):
         parser.error(f"--body {spec}: expected x0,y0,x1,y1 with 0 <= x0 <= x1 <= {2 * res} and 0 <= y0 <= y1 <= {res}, or 'auto'")
     return box
+
+
+def _tracer_line(parser, spec):
+    c = spec.split(",")
+    try:
+        x0, y0, x1, y1, n = float(c[0]), float(c[1]), float(c[2]), float(c[3]), int(c[4])
+        if len(c) != 5 or n < 1:
+            raise ValueError
+    except (ValueError, IndexError):
+        parser.error(f"--tracer-line {spec}: expected x0,y0,x1,y1,n (cell units, n >= 1)")
+    return x0, y0, x1, y1, n
 
 
 def _probe(parser, spec):
@@ -247,6 +316,20 @@ def main(argv=None):
             print(f"--load-state {args.load_state}: its time average was taken with --mean-every {held[0]} --mean-start {held[1]}, "
                   f"not {args.mean_every} / {args.mean_start}; continue with those or average without the checkpoint's sums", file=sys.stderr)
             sys.exit(2)
+    tracing = args.tracers > 0 or bool(args.tracer_line)
+    if args.tracers < 0 or args.tracer_dump_every < 0 or (args.tracer_max_age is not None and args.tracer_max_age < 0):
+        parser.error("--tracers, --tracer-max-age and --tracer-dump-every must be >= 0")
+    if not tracing and (args.tracer_seed is not None or args.tracer_once or args.tracer_max_age is not None or args.tracer_file
+                        or args.tracer_dump_every):
+        parser.error("--tracer-seed, --tracer-once, --tracer-max-age, --tracer-file and --tracer-dump-every need --tracers N or --tracer-line")
+    lines = [_tracer_line(parser, spec) for spec in args.tracer_line]
+    max_age = args.tracer_max_age or 0
+    if tracing and args.load_state:
+        held = saved_tracers(args.load_state)
+        if held is not None and held[:2] != (not args.tracer_once, max_age):
+            print(f"--load-state {args.load_state}: its tracers ran with{'out' if held[0] else ''} --tracer-once and --tracer-max-age {held[1]}; "
+                  "continue with those or drop the tracer flags", file=sys.stderr)
+            sys.exit(2)
     box = _body_box(parser, args.body, args.boundary_condition, res)
     probes = [_probe(parser, spec) for spec in args.probe]
     print(f"Boundary Condition: {args.boundary_condition}\ndt: {dt}\nRe: {args.reynolds_num}\nResolution: {res}\n"
@@ -291,6 +374,25 @@ def main(argv=None):
             out.mkdir(exist_ok=True)
             save_png(mean_frame(sim, args.visualization), out / "mean_vis.png")
 
+    tracer_file = None
+    if tracing:
+        tracer_file = Path(args.tracer_file) if args.tracer_file else out / "tracers.npz"
+        if args.load_state and load_tracers(sim, args.load_state):
+            print(f"tracers: continuing the checkpoint's {sim._tracers.set.n} particles (the seed flags are not used)")
+        else:
+            seeds, notes = tracer_seeds(np.asarray(sim._solver._bc.mask), args.tracers, args.tracer_seed or 0, lines)
+            for note in notes:
+                print(note)
+            if len(seeds) == 0:
+                print("tracers: no seed lies in a fluid cell", file=sys.stderr)
+                dev.close()
+                sys.exit(2)
+            sim.seed_tracers(seeds, respawn=not args.tracer_once, max_age=max_age)
+
+    def write_tracers(path):
+        path.parent.mkdir(parents=True, exist_ok=True)
+        np.savez(str(path), **sim.tracers())
+
     stats = None
     if args.stats_every > 0:
         stats = StatsWriter(sim, Path(args.stats_file) if args.stats_file else out / "stats.csv", dt, box, args.stop_on_nonfinite)
@@ -301,6 +403,8 @@ def main(argv=None):
             print(f"step {step}: non-finite values (NaN / Inf) in v or p; stopping (--stop-on-nonfinite)", file=sys.stderr)
             write_history()
             write_mean()
+            if tracer_file is not None:
+                write_tracers(tracer_file)
             dev.close()
             sys.exit(3)
 
@@ -320,6 +424,8 @@ def main(argv=None):
             nxt = min(nxt, (step // args.dump_every + 1) * args.dump_every)
         if stats:
             nxt = min(nxt, (step // args.stats_every + 1) * args.stats_every)
+        if args.tracer_dump_every:
+            nxt = min(nxt, (step // args.tracer_dump_every + 1) * args.tracer_dump_every)
         sim.run(nxt - step, graph=args.graph)
         step = nxt
         if stats and step % args.stats_every == 0:
@@ -327,6 +433,8 @@ def main(argv=None):
         if args.dump_every and step % args.dump_every == 0:
             out.mkdir(exist_ok=True)
             np.savez(str(out / f"step_{step:06}.npz"), **sim.field_to_numpy())
+        if args.tracer_dump_every and step % args.tracer_dump_every == 0:
+            write_tracers(out / f"tracers_{step:06}.npz")
     dev.sync()
     el = time.perf_counter() - t0
     print(f"{args.steps} steps in {el:.3f} s = {args.steps / el:.1f} steps/s")
@@ -336,6 +444,8 @@ def main(argv=None):
         stats.close()
     write_history()
     write_mean()
+    if tracer_file is not None:
+        write_tracers(tracer_file)
     dev.close()
 
 

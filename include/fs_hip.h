@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 12
+#define FS_ABI_VERSION 13
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -323,6 +323,43 @@ int fs_mean_read(fs_ctx *ctx, fs_mean *m, double *sums_out, long long *launches,
 int fs_mean_write(fs_ctx *ctx, fs_mean *m, const double *sums_in, long long launches, long long samples);
 int fs_mean_reset(fs_ctx *ctx, fs_mean *m);
 int fs_mean_free(fs_ctx *ctx, fs_mean *m);
+
+/* Tracer particles (new): n passive particles advanced on the device by one launch per step that can be captured in a hipGraph
+ * (csrc/fs_tracer.h).  Positions are doubles in CELL units: cell (i, j) covers [i, i + 1) x [j, j + 1), its stored value sits at
+ * (i + 0.5, j + 0.5).  State per particle: x, y, age (steps), status (FS_TRACER_ALIVE / _LEFT / _WALL / _EXPIRED), respawns, and the
+ * constant seed; plus one device counter of launches.  Single-context grids only: on a slab context (or with a communicator) create
+ * returns FS_ERR_UNSUPPORTED - particles that cross slab boundaries would have to migrate.
+ * create:   n >= 1 seeds as [n][2] doubles (x, y), each inside [0, X) x [0, Y) (FS_ERR_ARG otherwise; whether the cell is fluid is the
+ *           caller's business); respawn != 0: a particle that meets a fate starts again at its seed; max_age > 0: fate EXPIRED at that age.
+ * advance:  every particle with status 0 takes one midpoint step h = dt / dx in the 2-channel field v:
+ *             V(x, y): bilinear in the four stored values around (x - 0.5, y - 0.5), i0 = clamp(floor(x - 0.5), 0, X - 2), tx = min(max(
+ *             x - 0.5 - i0, 0), 1), likewise in y; V = (1 - ty) ((1 - tx) a00 + tx a10) + ty ((1 - tx) a01 + tx a11) on values promoted to
+ *             double; wall cells take part with what they store.  limit > 0: v still owes limit_field(limit) (a deferred pass): every
+ *             corner's (u, w) is limited first, in the field's precision, as that pass would store it.
+ *             k1 = V(x, y); (xm, ym) = (x, y) + (0.5 h) k1; not inside -> LEFT.  k2 = V(xm, ym); (xn, yn) = (x, y) + h k2; not inside ->
+ *             LEFT.  Mask of cell (floor xn, floor yn): 1 -> WALL, 3 -> LEFT, else the particle moves there.  age += 1; max_age > 0 and
+ *             age >= max_age and no other fate -> EXPIRED.
+ *           With respawn a fate puts the particle back on its seed (age 0, respawns + 1, status 0); without, status takes the fate's code,
+ *           LEFT / WALL keep the last valid position, EXPIRED keeps (xn, yn), and the particle is never touched again.  Every operation is
+ *           one IEEE double operation in the order written (no FMA): an IEEE double loop reproduces the state bit for bit.  No atomics;
+ *           changes no field; the counter advances on the device.
+ * read:     synchronises; pos (may be NULL) receives [4][n] doubles: x, y, x_seed, y_seed; ints (may be NULL) [3][n]: age, status, respawns.
+ * write:    the inverse of read (checkpoints): status in 0 .. 3, age and respawns >= 0, launches >= 0.
+ * draw:     stores (r, g, b) into pixel (floor x, floor y) of the 3-channel field rgb for every particle with status 0.
+ * free:     a graph that holds the launch must not be replayed afterwards; during a capture the release is deferred to its end (as
+ *           fs_history_free).
+ * create, read and write return FS_ERR_STATE during graph capture / tape recording.                                                    */
+#define FS_TRACER_ALIVE 0
+#define FS_TRACER_LEFT 1
+#define FS_TRACER_WALL 2
+#define FS_TRACER_EXPIRED 3
+typedef struct fs_tracer fs_tracer;
+int fs_tracer_create(fs_ctx *ctx, int n, const double *seeds_xy, int respawn, int max_age, fs_tracer **out);
+int fs_tracer_advance(fs_ctx *ctx, fs_tracer *t, double h, double limit, const fs_field *v);
+int fs_tracer_read(fs_ctx *ctx, fs_tracer *t, double *pos, int *ints, long long *launches);
+int fs_tracer_write(fs_ctx *ctx, fs_tracer *t, const double *pos, const int *ints, long long launches);
+int fs_tracer_draw(fs_ctx *ctx, fs_tracer *t, double r, double g, double b, fs_field *rgb);
+int fs_tracer_free(fs_ctx *ctx, fs_tracer *t);
 
 /* ---- pointwise -------------------------------------------------------------------------------- */
 /* limit_field   fs/solver.py:38-43 ;  clamp_field   fs/solver.py:46-49                           */

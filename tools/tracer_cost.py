@@ -1,0 +1,130 @@
+"""Cost of the tracer particles: us per step of FluidSimulator.run(graph=True) without tracers and with N particles, alternated in one
+process so that clock drift hits both alike; median of the repetitions, one JSON line per configuration.  A last line gives the time of one
+advance launch (HIP events around eager launches) for seeds in random order and for the same seeds sorted by cell, the bytes the byte model
+counts for it and the float4 copy rate of this GPU measured in the same process.
+
+Byte model of one launch: 44 B of state per alive particle (x, y, age, status read; x, y, age written) plus the cache lines its gathers
+touch - the eight corner values of a stage (four row segments of the velocity field) and one mask byte.  The second stage moves the point by
+a fraction of a cell and mostly stays on the first stage's lines; lines are 128 B.  Two counts frame the traffic: every particle fetching
+its own lines (no reuse between particles) and every distinct line fetched once (perfect reuse).
+
+  python tools/tracer_cost.py --bc 1 --res 400 --n 16384 --steps 4000 --reps 3
+  python tools/tracer_cost.py --bc 5 --res 4096 --n 1048576 --steps 300 --reps 3
+  rocprofv3 --kernel-trace --stats -- python tools/tracer_cost.py --bc 5 --res 4096 --n 1048576 --steps 100 --reps 1 --only-on   (kernel time)
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "2d-fluid-simulator_amd"))
+
+LINE = 128
+
+
+def gather_lines(seeds, X, Y, pitch, esize):
+    """(lines summed over the particles, distinct lines) of the first stage's gathers and the mask byte, from the field layout
+    [row][channel][pitch] (csrc/fs_device.h) and a mask pitch of `pitch` bytes."""
+    fx, fy = seeds[:, 0] - 0.5, seeds[:, 1] - 0.5
+    i0 = np.clip(np.floor(fx).astype(np.int64), 0, X - 2)
+    j0 = np.clip(np.floor(fy).astype(np.int64), 0, Y - 2)
+    ids = []
+    for dj in (0, 1):
+        for c in (0, 1):
+            base = ((j0 + dj) * 2 + c) * pitch + i0
+            ids.append(np.stack([base * esize // LINE, (base + 1) * esize // LINE], 1))
+    ids = np.concatenate(ids, 1)                                    # (n, 8) line ids of the velocity field
+    per = int(((np.diff(np.sort(ids, 1), axis=1) != 0).sum(1) + 1).sum())      # distinct lines of each particle, summed
+    m = (np.floor(seeds[:, 1]).astype(np.int64) * pitch + np.floor(seeds[:, 0]).astype(np.int64)) // LINE
+    return per + len(seeds), len(np.unique(ids)) + len(np.unique(m))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--bc", type=int, default=1)
+    ap.add_argument("--res", type=int, default=400)
+    ap.add_argument("--n", type=int, default=1 << 14)
+    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--scheme", default="cip")
+    ap.add_argument("--vc", type=float, default=5.0)
+    ap.add_argument("--f64", action="store_true")
+    ap.add_argument("--only-on", action="store_true", help="run with the tracers only (profiling)")
+    a = ap.parse_args()
+    import fs
+    from fs.tracers import seed_random
+    fs.runtime.init(gpu=0, dtype="f64" if a.f64 else "f32")
+    res = a.res
+    sim = fs.FluidSimulator.create(a.bc, res, 0.05 / res, 1.0 / res, 1e6, a.vc or None, a.scheme)
+    dev = sim._solver._bc.device
+    mask = np.asarray(sim._solver._bc.mask)
+    X, Y = mask.shape
+    seeds = seed_random(mask, a.n, 1)
+    configs = [True] if a.only_on else [False, True]
+    sim.run(64)
+    rates = {c: [] for c in configs}
+    for _ in range(a.reps):
+        for on in configs:
+            if on:
+                sim.seed_tracers(seeds)
+            sim.run(64)                              # (captures the graphs of this mode)
+            dev.sync()
+            t0 = time.perf_counter()
+            sim.run(a.steps)
+            dev.sync()
+            rates[on].append(a.steps / (time.perf_counter() - t0))
+            if on:
+                st = sim.tracers()
+                sim.stop_tracers()
+                assert st["steps"] == a.steps + 64, st["steps"]
+    base = float(np.median(rates[False])) if False in rates else None
+    for on in configs:
+        med = float(np.median(rates[on]))
+        out = {"bc": a.bc, "res": res, "dtype": "f64" if a.f64 else "f32", "steps": a.steps, "tracers": a.n if on else 0,
+               "steps_per_s": [round(r, 1) for r in rates[on]], "us_per_step": round(1e6 / med, 3)}
+        if on and base:
+            out.update(cost_us_per_step=round(1e6 / med - 1e6 / base, 3), cost_percent=round(100.0 * (base / med - 1.0), 2))
+        print(json.dumps(out), flush=True)
+    # one launch in isolation: 20 advances timed by HIP events, seeds in random order and sorted by cell (row, then column)
+    v = sim._solver.get_fields()[0]
+    h = sim._solver.dt / sim._solver.dx
+    esize = 8 if a.f64 else 4
+    pitch = (X + 63) // 64 * 64
+    order = np.lexsort((np.floor(seeds[:, 0]), np.floor(seeds[:, 1])))
+    launch_us = {}
+    for label, s in (("random", seeds), ("sorted", seeds[order])):
+        tr = dev.tracer_create(s, respawn=True)
+        for _ in range(3):
+            dev.tracer_advance(tr, h, v)
+        dev.sync()
+        dev.profile_reset()
+        dev.profile(True)
+        for _ in range(20):
+            dev.tracer_advance(tr, h, v)
+        dev.sync()
+        n, ms = dev.profile_report()["tracer_advance"]
+        dev.profile(False)
+        dev.profile_reset()
+        dev.tracer_free(tr)
+        launch_us[label] = 1e3 * ms / n
+    per, distinct = gather_lines(seeds, X, Y, pitch, esize)
+    state = 44 * a.n
+    hi, lo = state + per * LINE, state + distinct * LINE
+    rd, cp = dev.box_rates(2 * 8192 * 4096 * 4, 30.0)
+    t = launch_us["random"] * 1e-6
+    print(json.dumps({"bc": a.bc, "res": res, "tracers": a.n, "launch_us_random": round(launch_us["random"], 2),
+                      "launch_us_sorted": round(launch_us["sorted"], 2), "note": "one tracer_advance launch between two HIP events",
+                      "state_MB": round(state / 1e6, 3), "model_MB_no_reuse": round(hi / 1e6, 3), "model_MB_distinct_lines": round(lo / 1e6, 3),
+                      "GBps_no_reuse": round(hi / t / 1e9, 1), "GBps_distinct_lines": round(lo / t / 1e9, 1),
+                      "ns_per_particle": round(1e3 * launch_us["random"] / a.n, 4),
+                      "box_read_GBps": round(rd, 1), "box_copy_GBps": round(cp, 1), "frac_of_box_copy_no_reuse": round(hi / t / 1e9 / cp, 4),
+                      "frac_of_box_copy_distinct_lines": round(lo / t / 1e9 / cp, 4)}), flush=True)
+    dev.close()
+
+
+if __name__ == "__main__":
+    main()
