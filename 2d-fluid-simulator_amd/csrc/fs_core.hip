@@ -30,6 +30,9 @@ static void tracer_release(fs_tracer *t)
     if (t->d_pos) hipFree(t->d_pos);
     if (t->d_int) hipFree(t->d_int);
     if (t->d_count) hipFree(t->d_count);
+    if (t->d_spos) hipFree(t->d_spos);
+    if (t->d_sint) hipFree(t->d_sint);
+    if (t->d_bins) hipFree(t->d_bins);
     delete t;
 }
 
@@ -1424,7 +1427,8 @@ int fs_vis_dye(fs_ctx *ctx, fs_field *rgb, const fs_field *dye, int row_begin, i
 }
 
 // ---- tracer particles (fs_tracer.h) -------------------------------------------------------------------------
-static_assert(TR_LEFT == FS_TRACER_LEFT && TR_WALL == FS_TRACER_WALL && TR_EXPIRED == FS_TRACER_EXPIRED, "fs_tracer.h and include/fs_hip.h disagree");
+static_assert(TR_LEFT == FS_TRACER_LEFT && TR_WALL == FS_TRACER_WALL && TR_EXPIRED == FS_TRACER_EXPIRED && TRACER_SORT_W == FS_TRACER_SORT_BIN_CELLS,
+              "fs_tracer.h and include/fs_hip.h disagree");
 #define FS_TRACER_HANDLE(t) FS_REQUIRE((t)->ctx == ctx && ctx->tracers.count(t), "tracer set from another context or freed")
 #define FS_TRACER_NO_CAPTURE(what) \
     if (ctx->capturing || ctx->tape_rec) { set_error("tracer " what " during graph capture / tape recording"); return FS_ERR_STATE; }
@@ -1432,7 +1436,7 @@ static_assert(TR_LEFT == FS_TRACER_LEFT && TR_WALL == FS_TRACER_WALL && TR_EXPIR
 static TracerDev tracer_dev(const fs_tracer *t)
 {
     const size_t n = (size_t)t->n;
-    return TracerDev{t->n, t->d_pos, t->d_pos + n, t->d_int, t->d_int + n, t->d_int + 2 * n, t->d_pos + 2 * n, t->d_pos + 3 * n, t->d_count};
+    return TracerDev{t->n, t->d_pos, t->d_pos + n, t->d_int, t->d_int + n, t->d_int + 2 * n, t->d_pos + 2 * n, t->d_pos + 3 * n, t->d_count, t->d_int + 3 * n};
 }
 
 int fs_tracer_create(fs_ctx *ctx, int n, const double *seeds_xy, int respawn, int max_age, fs_tracer **out)
@@ -1453,14 +1457,17 @@ int fs_tracer_create(fs_ctx *ctx, int n, const double *seeds_xy, int respawn, in
         pos[k] = pos[2 * (size_t)n + k] = x;
         pos[(size_t)n + k] = pos[3 * (size_t)n + k] = y;
     }
+    std::vector<int> ident((size_t)n);
+    for (int k = 0; k < n; ++k) ident[k] = k;
     FS_HIP(hipSetDevice(ctx->device));
     fs_tracer *t = new fs_tracer();
     t->ctx = ctx; t->n = n; t->respawn = respawn ? 1 : 0; t->max_age = max_age;
     hipError_t e = hipMalloc(&t->d_pos, pos.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&t->d_int, 3 * (size_t)n * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&t->d_int, 4 * (size_t)n * sizeof(int));      // (id with the set: a graph captured before the first sort stays valid)
     if (e == hipSuccess) e = hipMalloc(&t->d_count, sizeof(long long));
     if (e == hipSuccess) e = hipMemcpyAsync(t->d_pos, pos.data(), pos.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(t->d_int, 0, 3 * (size_t)n * sizeof(int), ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(t->d_int + 3 * (size_t)n, ident.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(t->d_count, 0, sizeof(long long), ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // (the source is this frame's memory)
     if (e != hipSuccess) { tracer_release(t); return hip_fail(e, "fs_tracer_create", __FILE__, __LINE__); }
@@ -1496,10 +1503,30 @@ int fs_tracer_read(fs_ctx *ctx, fs_tracer *t, double *pos, int *ints, long long 
     FS_TRACER_NO_CAPTURE("read")
     FS_HIP(hipSetDevice(ctx->device));
     const size_t n = (size_t)t->n;
-    if (pos) FS_HIP(hipMemcpyAsync(pos, t->d_pos, 4 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (ints) FS_HIP(hipMemcpyAsync(ints, t->d_int, 3 * n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     if (launches) FS_HIP(hipMemcpyAsync(launches, t->d_count, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    if (!t->permuted || (!pos && !ints)) {
+        if (pos) FS_HIP(hipMemcpyAsync(pos, t->d_pos, 4 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (ints) FS_HIP(hipMemcpyAsync(ints, t->d_int, 3 * n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        FS_HIP(hipStreamSynchronize(ctx->stream));
+        return FS_OK;
+    }
+    // slot order on the device, seed order for the caller: out[id[k]] = in[k] on the host (the seeds are in seed order already)
+    std::vector<double> hp(pos ? 2 * n : 0);
+    std::vector<int> hi((ints ? 3 * n : 0) + n);
+    int *id = hi.data() + (ints ? 3 * n : 0);
+    if (pos) {
+        FS_HIP(hipMemcpyAsync(hp.data(), t->d_pos, 2 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        FS_HIP(hipMemcpyAsync(pos + 2 * n, t->d_pos + 2 * n, 2 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (ints) FS_HIP(hipMemcpyAsync(hi.data(), t->d_int, 3 * n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipMemcpyAsync(id, t->d_int + 3 * n, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     FS_HIP(hipStreamSynchronize(ctx->stream));
+    for (size_t k = 0; k < n; ++k) {
+        const size_t s = (size_t)id[k];
+        if (id[k] < 0 || s >= n) { set_error("fs_tracer_read: the slot -> seed index array is not a permutation"); return FS_ERR_STATE; }
+        if (pos) { pos[s] = hp[k]; pos[n + s] = hp[n + k]; }
+        if (ints) { ints[s] = hi[k]; ints[n + s] = hi[n + k]; ints[2 * n + s] = hi[2 * n + k]; }
+    }
     return FS_OK;
 }
 
@@ -1516,7 +1543,116 @@ int fs_tracer_write(fs_ctx *ctx, fs_tracer *t, const double *pos, const int *int
     FS_HIP(hipMemcpyAsync(t->d_pos, pos, 4 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     FS_HIP(hipMemcpyAsync(t->d_int, ints, 3 * n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     FS_HIP(hipMemcpyAsync(t->d_count, &launches, sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    std::vector<int> ident;
+    if (t->permuted) {      // the state arrives in seed order: slot k holds seed k again
+        ident.resize(n);
+        for (size_t k = 0; k < n; ++k) ident[k] = (int)k;
+        FS_HIP(hipMemcpyAsync(t->d_int + 3 * n, ident.data(), n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    }
     FS_HIP(hipStreamSynchronize(ctx->stream));      // (the sources are the caller's / this frame's memory)
+    t->permuted = false;
+    return FS_OK;
+}
+
+// Scratch of the sort, allocated at the first one: the arrays in the new order, the keys and the bins.
+static int tracer_sort_scratch(fs_ctx *ctx, fs_tracer *t)
+{
+    if (t->d_bins) return FS_OK;
+    const size_t n = (size_t)t->n;
+    const int NB = (ctx->X + TRACER_SORT_W - 1) / TRACER_SORT_W;
+    FS_REQUIRE((long long)ctx->Y * NB + 1 < (1ll << 30), "grid too large for the tracer sort");
+    const int nbins = ctx->Y * NB + 1, nblocks = (nbins + TRACER_SCAN_TILE - 1) / TRACER_SCAN_TILE;
+    hipError_t e = hipMalloc(&t->d_spos, 2 * n * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&t->d_sint, 5 * n * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&t->d_bins, ((size_t)nbins + nblocks) * sizeof(int));
+    if (e != hipSuccess) {
+        if (t->d_spos) hipFree(t->d_spos);
+        if (t->d_sint) hipFree(t->d_sint);
+        t->d_spos = nullptr; t->d_sint = nullptr; t->d_bins = nullptr;
+        return hip_fail(e, "fs_tracer_sort (scratch)", __FILE__, __LINE__);
+    }
+    t->nbins = nbins; t->nblocks = nblocks;
+    return FS_OK;
+}
+
+int fs_tracer_sort(fs_ctx *ctx, fs_tracer *t)
+{
+    FS_REQUIRE(ctx && t, "null argument");
+    FS_TRACER_HANDLE(t);
+    FS_TRACER_NO_CAPTURE("sort")
+    FS_HIP(hipSetDevice(ctx->device));
+    int rc = tracer_sort_scratch(ctx, t); if (rc) return rc;
+    const TracerDev td = tracer_dev(t);
+    const size_t n = (size_t)t->n;
+    const int X = ctx->X, Y = ctx->Y, NB = (X + TRACER_SORT_W - 1) / TRACER_SORT_W, nbins = t->nbins, nblocks = t->nblocks;
+    const dim3 grid((t->n + TRACER_WG - 1) / TRACER_WG), wg(TRACER_WG);
+    double *sx = t->d_spos, *sy = t->d_spos + n;
+    int *si = t->d_sint, *key = t->d_sint + 4 * n, *bins = t->d_bins, *sums = t->d_bins + nbins;
+    hipStream_t st = ctx->stream;
+    FS_HIP(hipMemsetAsync(bins, 0, (size_t)nbins * sizeof(int), st));      // (a failed zeroing must not pass for a sort)
+    rc = launch(ctx, "tracer_sort_count", [=] {
+        FS_KLAUNCH(k_tracer_sort_count, grid, wg, 0, st, X, Y, NB, td, key, bins);
+    });
+    if (rc) return rc;
+    rc = launch(ctx, "tracer_sort_scan", [=] {
+        FS_KLAUNCH(k_tracer_scan_blocks, dim3(nblocks), wg, 0, st, nbins, bins, sums);
+        FS_KLAUNCH(k_tracer_scan_sums, dim3(1), wg, 0, st, nblocks, sums);
+        FS_KLAUNCH(k_tracer_scan_add, dim3((nbins + TRACER_WG - 1) / TRACER_WG), wg, 0, st, nbins, bins, (const int *)sums);
+    });
+    if (rc) return rc;
+    rc = launch(ctx, "tracer_sort_scatter", [=] {
+        FS_KLAUNCH(k_tracer_sort_scatter, grid, wg, 0, st, td, (const int *)key, bins, sx, sy, si);
+    });
+    if (rc) return rc;
+    rc = launch(ctx, "tracer_sort_copy", [=] {
+        FS_KLAUNCH(k_tracer_sort_copy, grid, wg, 0, st, td, (const double *)sx, (const double *)sy, (const int *)si);
+    });
+    if (rc) return rc;
+    t->permuted = true;
+    return FS_OK;
+}
+
+int fs_tracer_order(fs_ctx *ctx, fs_tracer *t, int *ids)
+{
+    FS_REQUIRE(ctx && t && ids, "null argument");
+    FS_TRACER_HANDLE(t);
+    FS_TRACER_NO_CAPTURE("order")
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemcpyAsync(ids, t->d_int + 3 * (size_t)t->n, (size_t)t->n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_tracer_fields(fs_ctx *ctx, fs_tracer *t, int *count, long long *age_sum)
+{
+    FS_REQUIRE(ctx && t && count && age_sum, "null argument");
+    FS_TRACER_HANDLE(t);
+    FS_TRACER_NO_CAPTURE("fields")
+    FS_HIP(hipSetDevice(ctx->device));
+    const size_t cells = (size_t)ctx->X * ctx->Y;
+    // one allocation for the call: the 8-byte sums first, then the counts
+    unsigned long long *d_age = nullptr;
+    FS_HIP(hipMalloc(&d_age, cells * (sizeof(unsigned long long) + sizeof(int))));
+    int *d_cnt = (int *)(d_age + cells);
+    const TracerDev td = tracer_dev(t);
+    const dim3 grid((t->n + TRACER_WG - 1) / TRACER_WG);
+    const int X = ctx->X, Y = ctx->Y;
+    hipStream_t st = ctx->stream;
+    const hipError_t ez = hipMemsetAsync(d_age, 0, cells * (sizeof(unsigned long long) + sizeof(int)), st);
+    if (ez != hipSuccess) { hipFree(d_age); return hip_fail(ez, "fs_tracer_fields (zeroing)", __FILE__, __LINE__); }
+    int rc = launch(ctx, "tracer_fields", [=] {
+        FS_KLAUNCH(k_tracer_fields, grid, dim3(TRACER_WG), 0, st, X, Y, td, d_cnt, d_age);
+    });
+    hipError_t e = hipSuccess;
+    if (rc == FS_OK) {
+        e = hipMemcpyAsync(count, d_cnt, cells * sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(age_sum, d_age, cells * sizeof(long long), hipMemcpyDeviceToHost, st);
+    }
+    const hipError_t es = hipStreamSynchronize(st);
+    hipFree(d_age);
+    if (rc) return rc;
+    if (e != hipSuccess) return hip_fail(e, "fs_tracer_fields (download)", __FILE__, __LINE__);
+    if (es != hipSuccess) return hip_fail(es, "fs_tracer_fields", __FILE__, __LINE__);
     return FS_OK;
 }
 

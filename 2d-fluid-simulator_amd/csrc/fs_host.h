@@ -199,8 +199,14 @@ struct fs_tracer {
     fs_ctx *ctx = nullptr;
     int n = 0, respawn = 1, max_age = 0;
     double *d_pos = nullptr;        // [4][n]: x, y, x_seed, y_seed
-    int *d_int = nullptr;           // [3][n]: age, status, respawns
+    int *d_int = nullptr;           // [4][n]: age, status, respawns, id (slot -> seed index)
     long long *d_count = nullptr;   // launches since creation
+    // fs_tracer_sort (allocated at the first sort, freed with the set)
+    bool permuted = false;          // a sort has run since creation / the last write: id may differ from the identity
+    double *d_spos = nullptr;       // [2][n]: x, y in the new order
+    int *d_sint = nullptr;          // [5][n]: age, status, respawns, id in the new order; the key of every slot
+    int *d_bins = nullptr;          // [nbins] counts / cursors, then [nblocks] totals of the scan's tiles
+    int nbins = 0, nblocks = 0;
 };
 
 namespace fs {

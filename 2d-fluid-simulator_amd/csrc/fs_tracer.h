@@ -21,6 +21,19 @@
 // Shape: three dependent gather rounds (8 corner values, 8 corner values, 1 mask byte) with a handful of f64 operations between them - the
 // launch is as long as the chain of one wave, so one particle per lane and as many waves as the registers allow: 256-lane workgroups, the
 // eight loads of a stage are issued before the first use (the limit's inputs are those same loads).  Resources and times: DESIGN.md 4aa.
+//
+// Slots and identity.  The particle arrays are indexed by SLOT; id[slot] is the particle's seed index (the identity until the first sort).
+// The seeds stay in seed order and are read as xs[id[k]] on the respawn path only.  fs_tracer_sort reorders the slots by a coarse cell key
+// so that the gathers of neighbouring lanes fall into the same cache lines (4aa: 2 759 -> 240 us per advance of 2^24 particles):
+//   key = floor(y) * NB + floor(x) / W, NB = ceil(X / W), W = TRACER_SORT_W cells (one 128-byte line of an f32 row); a particle that is
+//   not alive, or not inside the domain (NaN included), has key = Y * NB and goes last.
+// A counting sort in separate launches, none of which waits for another workgroup: zero the bins (a memset), k_tracer_sort_count (key per
+// slot + one integer atomic per particle), an exclusive scan of the Y * NB + 1 bins in three launches (k_tracer_scan_blocks: every
+// workgroup scans TRACER_SCAN_TILE bins and stores its total; k_tracer_scan_sums: ONE workgroup scans the totals; k_tracer_scan_add),
+// k_tracer_sort_scatter (a returning integer atomic on the bin's cursor gives the destination slot in scratch arrays; the order inside a
+// bin is whatever the atomics make it - nothing observable depends on it, every reader goes through id) and k_tracer_sort_copy back into
+// the arrays the captured advance launches point to.  k_tracer_fields bins the alive, inside particles by CELL: count (int) and the sum of
+// their ages (64-bit) with integer atomics - exact and the same from run to run.  Resources and times: DESIGN.md 4ab.
 #pragma once
 #include "fs_kernels.h"
 
@@ -28,6 +41,8 @@ namespace fs {
 
 constexpr int TRACER_WG = 256;
 constexpr int TR_ALIVE = 0, TR_LEFT = 1, TR_WALL = 2, TR_EXPIRED = 3;
+constexpr int TRACER_SORT_W = 32;                                   // cells per sort bin along x (FS_TRACER_SORT_BIN_CELLS)
+constexpr int TRACER_SCAN_ITEMS = 8, TRACER_SCAN_TILE = TRACER_WG * TRACER_SCAN_ITEMS;      // bins per lane / per workgroup of the scan
 
 struct TracerDev {
     int n;
@@ -35,6 +50,7 @@ struct TracerDev {
     int *age, *status, *respawns;
     const double *xs, *ys;
     long long *count;
+    int *id;      // slot -> seed index
 };
 
 __device__ __forceinline__ bool tracer_inside(double x, double y, double X, double Y) { return x >= 0.0 && x < X && y >= 0.0 && y < Y; }
@@ -101,8 +117,9 @@ __global__ __launch_bounds__(TRACER_WG) void k_tracer_advance(Grid g, int Y, dou
     }
     if (fate == TR_ALIVE && max_age > 0 && age >= max_age) fate = TR_EXPIRED;
     if (fate != TR_ALIVE && respawn) {
-        t.x[k] = t.xs[k];
-        t.y[k] = t.ys[k];
+        const int s = t.id[k];
+        t.x[k] = t.xs[s];
+        t.y[k] = t.ys[s];
         t.age[k] = 0;
         t.respawns[k] = t.respawns[k] + 1;
         return;
@@ -126,6 +143,129 @@ __global__ __launch_bounds__(TRACER_WG) void k_tracer_draw(Grid g, int Y, Tracer
     rgb[idx<3, T>(g, 0, i, j)] = r;
     rgb[idx<3, T>(g, 1, i, j)] = gg;
     rgb[idx<3, T>(g, 2, i, j)] = b;
+}
+
+// ---- fs_tracer_sort: counting sort of the slots by the coarse cell key ------------------------------------------------------------------
+__device__ __forceinline__ int tracer_sort_key(double x, double y, int status, int X, int Y, int NB)
+{
+    if (status != TR_ALIVE || !tracer_inside(x, y, (double)X, (double)Y)) return Y * NB;
+    return (int)floor(y) * NB + (int)floor(x) / TRACER_SORT_W;
+}
+
+// key[k] and bins[key] += 1 (bins zeroed before)
+__global__ __launch_bounds__(TRACER_WG) void k_tracer_sort_count(int X, int Y, int NB, TracerDev t, int *__restrict__ key, int *__restrict__ bins)
+{
+    const int k = blockIdx.x * TRACER_WG + threadIdx.x;
+    if (k >= t.n) return;
+    const int b = tracer_sort_key(t.x[k], t.y[k], t.status[k], X, Y, NB);
+    key[k] = b;
+    atomicAdd(&bins[b], 1);
+}
+
+// exclusive scan of one workgroup's values (one per lane) through LDS -> the lane's prefix; total: the workgroup's sum
+__device__ __forceinline__ int tracer_wg_scan(int v, int *lds, int &total)
+{
+    const int l = threadIdx.x;
+    lds[l] = v;
+    __syncthreads();
+#pragma unroll
+    for (int d = 1; d < TRACER_WG; d <<= 1) {
+        const int a = l >= d ? lds[l - d] : 0;
+        __syncthreads();
+        lds[l] += a;
+        __syncthreads();
+    }
+    total = lds[TRACER_WG - 1];
+    const int incl = lds[l];
+    __syncthreads();
+    return incl - v;
+}
+
+// bins[b * TILE ..) -> their exclusive prefix inside the tile, sums[b] = the tile's total
+__global__ __launch_bounds__(TRACER_WG) void k_tracer_scan_blocks(int nbins, int *__restrict__ bins, int *__restrict__ sums)
+{
+    __shared__ int lds[TRACER_WG];
+    const int base = blockIdx.x * TRACER_SCAN_TILE + threadIdx.x * TRACER_SCAN_ITEMS;
+    int v[TRACER_SCAN_ITEMS], s = 0;
+#pragma unroll
+    for (int q = 0; q < TRACER_SCAN_ITEMS; ++q) {
+        v[q] = base + q < nbins ? bins[base + q] : 0;
+        s += v[q];
+    }
+    int total;
+    int run = tracer_wg_scan(s, lds, total);
+#pragma unroll
+    for (int q = 0; q < TRACER_SCAN_ITEMS; ++q) {
+        if (base + q < nbins) bins[base + q] = run;
+        run += v[q];
+    }
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// ONE workgroup: sums[0 .. m) -> their exclusive prefix, in rounds of 256 with a running carry
+__global__ __launch_bounds__(TRACER_WG) void k_tracer_scan_sums(int m, int *__restrict__ sums)
+{
+    __shared__ int lds[TRACER_WG];
+    int carry = 0;
+    for (int b0 = 0; b0 < m; b0 += TRACER_WG) {
+        const int i = b0 + threadIdx.x;
+        const int v = i < m ? sums[i] : 0;
+        int total;
+        const int ex = tracer_wg_scan(v, lds, total);
+        if (i < m) sums[i] = carry + ex;
+        carry += total;
+    }
+}
+
+__global__ __launch_bounds__(TRACER_WG) void k_tracer_scan_add(int nbins, int *__restrict__ bins, const int *__restrict__ sums)
+{
+    const int i = blockIdx.x * TRACER_WG + threadIdx.x;
+    if (i < nbins) bins[i] += sums[i / TRACER_SCAN_TILE];
+}
+
+// slot k -> slot bins[key[k]]++ of the scratch arrays (sx, sy: doubles; si: [4][n] ints age, status, respawns, id)
+__global__ __launch_bounds__(TRACER_WG) void k_tracer_sort_scatter(TracerDev t, const int *__restrict__ key, int *__restrict__ bins,
+                                                                   double *__restrict__ sx, double *__restrict__ sy, int *__restrict__ si)
+{
+    const int k = blockIdx.x * TRACER_WG + threadIdx.x;
+    if (k >= t.n) return;
+    const double x = t.x[k], y = t.y[k];
+    const int age = t.age[k], status = t.status[k], respawns = t.respawns[k], id = t.id[k];
+    const int d = atomicAdd(&bins[key[k]], 1);
+    if (d < 0 || d >= t.n) return;      // (cannot happen: the cursors end at the next bin's start; never store outside the arrays)
+    const size_t n = (size_t)t.n;
+    sx[d] = x;
+    sy[d] = y;
+    si[d] = age;
+    si[n + d] = status;
+    si[2 * n + d] = respawns;
+    si[3 * n + d] = id;
+}
+
+__global__ __launch_bounds__(TRACER_WG) void k_tracer_sort_copy(TracerDev t, const double *__restrict__ sx, const double *__restrict__ sy,
+                                                                const int *__restrict__ si)
+{
+    const int k = blockIdx.x * TRACER_WG + threadIdx.x;
+    if (k >= t.n) return;
+    const size_t n = (size_t)t.n;
+    t.x[k] = sx[k];
+    t.y[k] = sy[k];
+    t.age[k] = si[k];
+    t.status[k] = si[n + k];
+    t.respawns[k] = si[2 * n + k];
+    t.id[k] = si[3 * n + k];
+}
+
+// ---- fs_tracer_fields: per-cell count and age sum of the alive particles inside the domain (arrays [Y][X], zeroed before) ----------------
+__global__ __launch_bounds__(TRACER_WG) void k_tracer_fields(int X, int Y, TracerDev t, int *__restrict__ count, unsigned long long *__restrict__ age_sum)
+{
+    const int k = blockIdx.x * TRACER_WG + threadIdx.x;
+    if (k >= t.n || t.status[k] != TR_ALIVE) return;
+    const double x = t.x[k], y = t.y[k];
+    if (!tracer_inside(x, y, (double)X, (double)Y)) return;
+    const size_t c = (size_t)(int)floor(y) * X + (int)floor(x);
+    atomicAdd(&count[c], 1);
+    atomicAdd(&age_sum[c], (unsigned long long)(long long)t.age[k]);
 }
 
 }  // namespace fs

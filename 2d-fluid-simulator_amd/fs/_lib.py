@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FS_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libfs_hip.so")     # FS_LIB: A/B builds (tools/)
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _lib = None
 
@@ -94,6 +94,9 @@ _PROTOS = {
     "fs_tracer_read": [_c_vp, _c_vp, _P(_c_dbl), _P(_c_int), _P(ctypes.c_longlong)],
     "fs_tracer_write": [_c_vp, _c_vp, _P(_c_dbl), _P(_c_int), ctypes.c_longlong],
     "fs_tracer_draw": [_c_vp, _c_vp, _c_dbl, _c_dbl, _c_dbl, _c_vp],
+    "fs_tracer_sort": [_c_vp, _c_vp],
+    "fs_tracer_order": [_c_vp, _c_vp, _P(_c_int)],
+    "fs_tracer_fields": [_c_vp, _c_vp, _P(_c_int), _P(ctypes.c_longlong)],
     "fs_tracer_free": [_c_vp, _c_vp],
     "fs_limit_field": [_c_vp, _c_dbl, _c_vp] + _ROWS,
     "fs_clamp_field": [_c_vp, _c_dbl, _c_dbl, _c_vp] + _ROWS,

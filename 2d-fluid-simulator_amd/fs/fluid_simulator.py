@@ -105,9 +105,18 @@ class FluidSimulator:
         tr = self._tracers
         if tr is not None:
             self._dev.tracer_advance(tr.set, self._solver.dt / self._solver.dx, self._solver.get_fields()[0])
+            tr.issued += 1
+
+    def _sort_if_due(self):
+        """The scheduled device sort of the tracer particles (seed_tracers(sort_every=K)): after every K-th step, between launch sequences -
+        never inside a capture."""
+        tr = self._tracers
+        if tr is not None and tr.due() and not getattr(self._dev, "capturing", False):
+            tr.sort()
 
     def step(self):
         self._update()
+        self._sort_if_due()
         self._eager_seen = True        # (captures call the solver directly: see capture_period)
         self._pending_after_step = self._limit_pending()
         self._since_hot_check += 1
@@ -175,23 +184,36 @@ class FluidSimulator:
         re-captured - and leaked - chunk after chunk, and a capture is only started when the chunk is long enough to pay for it.
 
         With a history recorder attached (record_history) the run is cut into chunks that fit the recorder's ring, which is drained between
-        them: no record is ever dropped."""
-        rec = self._recorder
-        if rec is None:
+        them: no record is ever dropped.  With a sort schedule for the tracer particles (seed_tracers(sort_every=K)) it is also cut at
+        every K-th step since seed_tracers, where the particles are sorted between two chunks; the two cuts compose."""
+        rec, tr = self._recorder, self._tracers
+        cut = tr is not None and tr.sort_every > 0
+        if rec is None and not cut:
             return self._run_chunk(nsteps, graph)
         while nsteps > 0:
-            m = min(nsteps, rec.room())
-            if m <= 0:
-                rec.drain()
-                continue
-            self._run_chunk(m, graph)
+            m = nsteps
+            if rec is not None:
+                m = min(m, rec.room())
+                if m <= 0:
+                    rec.drain()
+                    continue
+            if cut:
+                m = min(m, tr.to_next_sort())
+            self._run_chunk(m, graph, reuse=cut)       # (its eager steps sort when they land on the K-th step themselves)
             nsteps -= m
+            self._sort_if_due()
 
     def _replayed(self, steps):
         if self._recorder is not None:
             self._recorder.issued += steps
+        if self._tracers is not None:
+            self._tracers.issued += steps
 
-    def _run_chunk(self, nsteps, graph):
+    def _run_chunk(self, nsteps, graph, reuse=False):
+        """reuse (the chunks a sort schedule cuts): a chunk that starts in a phase of the buffer rotation no cached graph belongs to takes
+        eager steps until it reaches one that has a graph, instead of capturing a graph per phase; and a cached period without its long
+        form - the first chunk was too short for it - gets it when a later chunk has the steps.  So the chunked run caches what the
+        uncut run caches."""
         dev = self._dev
         self._check_hot()
         if graph and dev.nranks > 1 and nsteps >= 24:
@@ -222,6 +244,23 @@ class FluidSimulator:
             self._counted_step()        # (the cached graphs start from the state a step leaves behind, see capture_period)
             nsteps -= 1
         entry = self._graphs.get(self._signature())
+        if reuse and entry is None and self._graphs:
+            seek = max(e[1] for e in self._graphs.values()) - 1
+            while entry is None and seek > 0 and nsteps > 0:
+                self.step()
+                nsteps -= 1
+                seek -= 1
+                entry = self._graphs.get(self._signature())
+        if reuse and entry is not None and entry[2] is None:
+            gid, period = entry[:2]
+            reps = -(-self._LONG_STEPS // period)
+            if reps > 1 and nsteps >= reps * period:
+                sig = self._signature()
+                lid = dev.capture(lambda: [self._update() for _ in range(reps * period)])
+                dev.replay(lid, 1)
+                nsteps -= reps * period
+                entry = (gid, period, (lid, reps * period))
+                self._graphs[sig] = entry
         if entry is None and nsteps >= 16:          # (periods 1 - 6 need at most 16 steps to be found; 12 - an odd red-black count with the pair pass
             # on top of the fused transport - is only tried when the chunk has 28)
             nsteps -= self.capture_period(budget=nsteps)
@@ -460,15 +499,24 @@ class FluidSimulator:
         self._averager = None
 
     # -- tracer particles (new): pathlines and streaklines advanced on the device ------------------------------------------------------
-    def seed_tracers(self, seeds, respawn=True, max_age=0):
+    def seed_tracers(self, seeds, respawn=True, max_age=0, sort_every=0):
         """From the next step on, N passive particles ride the step: seeds float64 (N, 2) in CELL units (cell (i, j) covers [i, i + 1) x
         [j, j + 1); fs.tracers.seed_line / seed_grid / seed_random build them), each inside the domain in a fluid or inflow cell
         (ValueError naming the first offender otherwise).  After every step each alive particle takes one midpoint step in the velocity
         the step left (include/fs_hip.h fs_tracer_advance).  A particle that leaves the domain or enters an outflow cell (LEFT), enters a
         wall cell (WALL) or reaches max_age > 0 steps (EXPIRED) starts again at its seed with respawn=True - a steady release: streaklines -
         and keeps its fate as status with respawn=False - pathlines.  The launch is part of the step: it is captured into the replayed
-        graphs, and run() is not cut into chunks by it.  48 bytes per particle; changes no field and no trajectory.  tracers() returns the
-        state.  Raises while a set is attached already and during a graph capture; single-GPU contexts only (FsError on slabs)."""
+        graphs, and run() is not cut into chunks by it.  52 bytes per particle; changes no field and no trajectory.  tracers() returns the
+        state.  Raises while a set is attached already and during a graph capture; single-GPU contexts only (FsError on slabs).
+
+        sort_every = K > 0: after every K-th step counted from here the particle slots are sorted by cell on the device (sort_tracers), so
+        that the advance keeps gathering from neighbouring cache lines while the flow mixes the particles - measured worth it from 2^20
+        particles on, not below.  The sort runs between launch sequences, never inside a graph: step() sorts after its
+        step, run() cuts its chunks at the multiples of K; capture_period() and captured steps never sort.  A run() chunk shorter than 16
+        steps does not capture a graph, so an interval below 16 keeps a fresh simulator eager, step by step.  Recommended: K = 32, which
+        measured best at 2^20 and 2^24 particles (bc5 res 4096: 2.74 -> 0.30 ms and 165 -> 75 us per step; DESIGN.md 4ab has all the
+        measured intervals).  Costs 36 more bytes per particle and 4 per sort bin from the first sort on.  0 (default): never - exactly
+        the behaviour without this argument.  Sorting changes nothing tracers(), draw_tracers(), tracer_fields() or a checkpoint shows."""
         from ._lib import FsError
         dev, s = self._dev, self._solver
         if getattr(dev, "capturing", False):
@@ -477,11 +525,13 @@ class FluidSimulator:
             raise RuntimeError("a tracer set is attached already: stop_tracers() first")
         if dev.nranks > 1:
             raise FsError("tracer particles need a single-GPU context: on slabs they would have to migrate between ranks (not implemented)")
-        max_age = int(max_age)
+        max_age, sort_every = int(max_age), int(sort_every)
         if max_age < 0:
             raise ValueError("max_age must be >= 0")
+        if sort_every < 0:
+            raise ValueError("sort_every must be >= 0")
         seeds = check_seeds(np.asarray(s._bc.mask), seeds)
-        self._tracers = Tracers(dev, dev.tracer_create(seeds, respawn, max_age), seeds, respawn, max_age)
+        self._tracers = Tracers(dev, dev.tracer_create(seeds, respawn, max_age), seeds, respawn, max_age, sort_every)
 
     def _trc(self):
         if self._tracers is None:
@@ -494,6 +544,24 @@ class FluidSimulator:
         seed_tracers()}.  Not allowed during a graph capture."""
         tr = self._trc()
         return tr.dev.tracer_read(tr.set)
+
+    def sort_tracers(self):
+        """Sort the particle slots by cell on the device now (DeviceBase.tracer_sort): what seed_tracers(sort_every=K) does every K steps.
+        Nothing observable changes, and the cached graphs stay valid.  Not allowed during a graph capture."""
+        if getattr(self._dev, "capturing", False):
+            raise RuntimeError("sort_tracers during a graph capture")
+        self._trc().sort()
+
+    def tracer_fields(self):
+        """Where the particles are now, per cell, binned on the device: {"count": int32 (X, Y), alive particles in the cell; "age_sum":
+        int64 (X, Y), the sum of their ages in steps (fs.tracers.residence_map(count, age_sum, dt) is the residence-time map); "steps":
+        steps since seed_tracers()}.  Exact and repeatable (integer atomics); 12 bytes per cell on the device for the call and in the
+        download.  Not allowed during a graph capture."""
+        if getattr(self._dev, "capturing", False):
+            raise RuntimeError("tracer_fields during a graph capture")
+        tr = self._trc()
+        count, age_sum = tr.dev.tracer_fields(tr.set)
+        return {"count": count, "age_sum": age_sum, "steps": tr.dev.tracer_read_steps(tr.set)}
 
     def draw_tracers(self, rgb_field=None, color=(1, 1, 1)):
         """Overlay the alive particles on an image field (default: self.rgb_buf, i.e. after any get_*_field()): pixel (floor x, floor y)

@@ -1011,8 +1011,8 @@ class DeviceBase:
     # ---- tracer particles (include/fs_hip.h fs_tracer_*): N particles in double cell coordinates, advanced by one launch per step -------
     def tracer_create(self, seeds, respawn=True, max_age=0):
         """A device tracer set for FluidSimulator.seed_tracers: seeds float64 (N, 2) in cell units, N >= 1, inside the domain (whether
-        the cells are fluid is fs.tracers.check_seeds' business).  48 bytes per particle.  Single-context grids only (FsError on a slab);
-        not allowed during a graph capture."""
+        the cells are fluid is fs.tracers.check_seeds' business).  52 bytes per particle (+ 36 and 4 per sort bin once tracer_sort has
+        run).  Single-context grids only (FsError on a slab); not allowed during a graph capture."""
         if getattr(self, "capturing", False):
             raise _lib.FsError("tracer_create during a graph capture")
         if self.nranks > 1:
@@ -1037,14 +1037,53 @@ class DeviceBase:
             self._oplog.append(("k", "tracer_advance", args, ()))
         self._p_kernel("tracer_advance", *args)
 
-    def tracer_read(self, tr):
+    def tracer_read(self, tr, raw=False):
         """-> {"x", "y": float64 (N,), "age", "status", "respawns": int32 (N,), "seeds": float64 (N, 2), "steps": launches so far}: one
-        download.  Not allowed during a graph capture."""
+        download, in SEED order (entry k belongs to seed k) whatever tracer_sort has done on the device.  raw=True: x, y, age, status
+        and respawns in the device's SLOT order instead, plus "id": int32 (N,), the seed index of the particle in each slot (the seeds
+        stay in seed order: the seed of slot k is seeds[id[k]]).  Not allowed during a graph capture."""
         if getattr(self, "capturing", False):
             raise _lib.FsError("tracer_read during a graph capture: the state is a download (read between captures / replays)")
         pos, ints, launches = self._p_tracer_read(tr._h, tr.n)
-        return {"x": pos[0].copy(), "y": pos[1].copy(), "age": ints[0].copy(), "status": ints[1].copy(), "respawns": ints[2].copy(),
-                "seeds": np.ascontiguousarray(pos[2:4].T), "steps": int(launches)}
+        out = {"x": pos[0].copy(), "y": pos[1].copy(), "age": ints[0].copy(), "status": ints[1].copy(), "respawns": ints[2].copy(),
+               "seeds": np.ascontiguousarray(pos[2:4].T), "steps": int(launches)}
+        if raw:
+            ids = self._p_tracer_order(tr._h, tr.n)
+            for k in ("x", "y", "age", "status", "respawns"):
+                out[k] = out[k][ids]
+            out["id"] = ids
+        return out
+
+    def tracer_read_steps(self, tr):
+        """Launches of the advance so far (the "steps" of tracer_read) without the particle download."""
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("tracer_read during a graph capture: the state is a download (read between captures / replays)")
+        return int(self._p_tracer_read(tr._h, 0)[2])
+
+    def _tracer_host_call(self, what):
+        if getattr(self, "capturing", False):
+            raise _lib.FsError(f"{what} during a graph capture")
+        if self.nranks > 1:
+            raise _lib.FsError("tracer particles need a single-GPU context: on slabs they would have to migrate between ranks (not implemented)")
+
+    def tracer_sort(self, tr):
+        """Reorder the particle slots on the device by cell (fs.tracers.sort_key: rows of bins SORT_BIN_CELLS cells wide; dead and
+        outside particles last) so that the advance gathers from neighbouring cache lines.  Changes nothing tracer_read() or any other
+        call shows, and no device address: graphs that hold the advance stay valid.  A handful of launches outside any graph (profiled
+        as tracer_sort_*); not allowed during a graph capture."""
+        DeviceBase._tracer_host_call(self, "tracer_sort")
+        self._p_tracer_sort(tr._h)
+
+    def tracer_order(self, tr):
+        """-> int32 (N,): the seed index of the particle in each device slot (arange(N) until the first tracer_sort)."""
+        DeviceBase._tracer_host_call(self, "tracer_order")
+        return self._p_tracer_order(tr._h, tr.n)
+
+    def tracer_fields(self, tr):
+        """-> (count int32 (X, Y), age_sum int64 (X, Y)): per cell, the number of alive particles inside it and the sum of their ages.
+        One launch with integer atomics (exact, repeatable) + the download; 12 bytes per cell of device memory during the call."""
+        DeviceBase._tracer_host_call(self, "tracer_fields")
+        return self._p_tracer_fields(tr._h)
 
     def tracer_write(self, tr, state):
         """Restore what tracer_read returned (checkpoints): the same keys, arrays of the set's N."""
@@ -1313,7 +1352,11 @@ class Device(DeviceBase):
         return h
 
     def _p_tracer_read(self, h, n):
-        pos, ints, launches = np.empty((4, n), np.float64), np.empty((3, n), np.int32), ctypes.c_longlong()
+        launches = ctypes.c_longlong()
+        if n == 0:      # the launch counter alone
+            _lib.call("fs_tracer_read", self._ctx, h, None, None, ctypes.byref(launches))
+            return None, None, launches.value
+        pos, ints = np.empty((4, n), np.float64), np.empty((3, n), np.int32)
         _lib.call("fs_tracer_read", self._ctx, h, pos.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                   ints.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.byref(launches))
         return pos, ints, launches.value
@@ -1321,6 +1364,20 @@ class Device(DeviceBase):
     def _p_tracer_write(self, h, pos, ints, launches):
         _lib.call("fs_tracer_write", self._ctx, h, pos.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                   ints.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), launches)
+
+    def _p_tracer_sort(self, h):
+        _lib.call("fs_tracer_sort", self._ctx, h)
+
+    def _p_tracer_order(self, h, n):
+        ids = np.empty(n, np.int32)
+        _lib.call("fs_tracer_order", self._ctx, h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+        return ids
+
+    def _p_tracer_fields(self, h):
+        count, age = np.empty((self.ny, self.nx), np.int32), np.empty((self.ny, self.nx), np.int64)       # (the library's layout: x contiguous)
+        _lib.call("fs_tracer_fields", self._ctx, h, count.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                  age.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)))
+        return np.ascontiguousarray(count.T), np.ascontiguousarray(age.T)
 
     def _p_tracer_free(self, h):
         if self._ctx is not None:

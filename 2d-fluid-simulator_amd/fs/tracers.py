@@ -10,6 +10,7 @@ FLUID, WALL, INFLOW, OUTFLOW = 0, 1, 2, 3
 # status of a particle (fs_tracer_read): alive, or the fate that ended it when the set does not respawn
 FATE_ALIVE, FATE_LEFT, FATE_WALL, FATE_EXPIRED = 0, 1, 2, 3
 KEYS = ("x", "y", "age", "status", "respawns", "seeds", "steps")      # what FluidSimulator.tracers() returns
+SORT_BIN_CELLS = 32      # cells per bin along x of the device sort (include/fs_hip.h FS_TRACER_SORT_BIN_CELLS): one 128-byte line of an f32 row
 
 
 def _as_seeds(seeds):
@@ -102,11 +103,51 @@ def residence_time(age, dt):
     return np.asarray(age, np.float64) * np.float64(dt)
 
 
-class Tracers:
-    """One tracer set of a FluidSimulator (seed_tracers): the device set and its parameters."""
+def sort_key(x, y, status, X, Y):
+    """The key the device sort (FluidSimulator.sort_tracers, include/fs_hip.h fs_tracer_sort) orders the particle slots by, int64 (N,):
+    floor(y) * NB + floor(x) // SORT_BIN_CELLS with NB = ceil(X / SORT_BIN_CELLS) for an alive particle inside [0, X) x [0, Y); Y * NB for
+    one that is not alive, or outside the domain, or at a NaN position - these go last."""
+    x, y, status = np.asarray(x, np.float64), np.asarray(y, np.float64), np.asarray(status)
+    X, Y = int(X), int(Y)
+    nb = -(-X // SORT_BIN_CELLS)
+    ok = (status == FATE_ALIVE) & (x >= 0) & (x < X) & (y >= 0) & (y < Y)        # (False for NaN)
+    key = np.full(x.shape, Y * nb, np.int64)
+    key[ok] = np.floor(y[ok]).astype(np.int64) * nb + np.floor(x[ok]).astype(np.int64) // SORT_BIN_CELLS
+    return key
 
-    def __init__(self, dev, set_, seeds, respawn, max_age):
+
+def residence_map(count, age_sum, dt):
+    """Mean simulated time the particles now in each cell have spent since their seed or last respawn: age_sum / count * dt, float64 in
+    the shape of `count` (FluidSimulator.tracer_fields gives (X, Y)), NaN where count == 0."""
+    count, age_sum = np.asarray(count), np.asarray(age_sum)
+    if count.shape != age_sum.shape:
+        raise ValueError(f"count {count.shape} and age_sum {age_sum.shape} differ in shape")
+    out = np.full(count.shape, np.nan, np.float64)
+    has = count > 0
+    out[has] = age_sum[has].astype(np.float64) / count[has].astype(np.float64) * np.float64(dt)
+    return out
+
+
+class Tracers:
+    """One tracer set of a FluidSimulator (seed_tracers): the device set and its parameters; `issued`: advances issued since seed_tracers
+    (what sort_every counts), `sorts`: device sorts so far."""
+
+    def __init__(self, dev, set_, seeds, respawn, max_age, sort_every=0):
         self.dev, self.set, self.seeds, self.respawn, self.max_age = dev, set_, seeds, bool(respawn), int(max_age)
+        self.sort_every, self.issued, self.sorts, self.sorted_at = int(sort_every), 0, 0, 0
+
+    def to_next_sort(self):
+        """Steps until the next scheduled sort (>= 1), or None without a schedule."""
+        return self.sort_every - self.issued % self.sort_every if self.sort_every > 0 else None
+
+    def due(self):
+        """The schedule asks for a sort now: `issued` is a positive multiple of sort_every that has not been sorted at."""
+        return self.sort_every > 0 and self.issued % self.sort_every == 0 and self.sorted_at != self.issued
+
+    def sort(self):
+        self.dev.tracer_sort(self.set)
+        self.sorts += 1
+        self.sorted_at = self.issued
 
     @property
     def token(self):

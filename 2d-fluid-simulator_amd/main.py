@@ -14,7 +14,8 @@ The reference opens a GGUI window and steps forever; here the loop runs `--steps
     the end of the run; the sums travel with `--save-state` / `--load-state`, so an average continues over restarts.
   * follow tracer particles on the GPU (`--tracers N`, `--tracer-line x0,y0,x1,y1,n`): pathlines (`--tracer-once`) or streaklines, written
     to `--tracer-file` (.npz) at the end of the run and every `--tracer-dump-every` steps, drawn into the `-vis` frames; the particle state
-    travels with `--save-state` / `--load-state`.
+    travels with `--save-state` / `--load-state`.  `--tracer-sort-every K` sorts the particles by cell on the GPU every K steps (large sets
+    stay fast; no result changes); `--tracer-fields` writes the per-cell particle count, age sum and residence time (`--tracer-fields-file`).
 """
 import argparse
 import os
@@ -90,6 +91,13 @@ def build_parser():
     p.add_argument("--tracer-file", type=str, default=None,
                    help=".npz of the particles after the last step: x, y, age, status, respawns, seeds, steps (default: <out>/tracers.npz)")
     p.add_argument("--tracer-dump-every", type=int, default=0, help="also write <out>/tracers_<step>.npz every N steps")
+    p.add_argument("--tracer-sort-every", type=int, default=0,
+                   help="sort the particles by cell on the GPU every K steps, which keeps the advance of large sets (from about 2^20 particles) "
+                        "fast while the flow mixes them; changes no result.  32 measured best; below 16 --graph replays nothing (default 0: never)")
+    p.add_argument("--tracer-fields", action="store_true",
+                   help="write the per-cell particle count, age sum and residence time (count, age_sum, residence, step) after the last step, "
+                        "and <out>/tracer_fields_<step>.npz next to every --tracer-dump-every dump")
+    p.add_argument("--tracer-fields-file", type=str, default=None, help=".npz of --tracer-fields (default: <out>/tracer_fields.npz)")
     return p
 
 
@@ -121,13 +129,14 @@ def saved_tracers(path):
     return (bool(z["tracer.respawn"]), int(z["tracer.max_age"]), len(z["tracer.x"])) if "tracer.x" in z.files else None
 
 
-def load_tracers(sim, path):
-    """Seed the checkpoint's tracer set and restore its state -> whether the checkpoint held one."""
+def load_tracers(sim, path, sort_every=0):
+    """Seed the checkpoint's tracer set and restore its state -> whether the checkpoint held one.  The state is in seed order: whether the
+    run that wrote it sorted its particles, and whether this one will (sort_every), makes no difference."""
     from fs.tracers import KEYS
     z = np.load(_npz_path(path))
     if "tracer.x" not in z.files:
         return False
-    sim.seed_tracers(z["tracer.seeds"], respawn=bool(z["tracer.respawn"]), max_age=int(z["tracer.max_age"]))
+    sim.seed_tracers(z["tracer.seeds"], respawn=bool(z["tracer.respawn"]), max_age=int(z["tracer.max_age"]), sort_every=sort_every)
     tr = sim._tracers
     tr.dev.tracer_write(tr.set, {k: z[f"tracer.{k}"] for k in KEYS})
     return True
@@ -317,11 +326,15 @@ def main(argv=None):
                   f"not {args.mean_every} / {args.mean_start}; continue with those or average without the checkpoint's sums", file=sys.stderr)
             sys.exit(2)
     tracing = args.tracers > 0 or bool(args.tracer_line)
-    if args.tracers < 0 or args.tracer_dump_every < 0 or (args.tracer_max_age is not None and args.tracer_max_age < 0):
-        parser.error("--tracers, --tracer-max-age and --tracer-dump-every must be >= 0")
+    if args.tracers < 0 or args.tracer_dump_every < 0 or (args.tracer_max_age is not None and args.tracer_max_age < 0) or args.tracer_sort_every < 0:
+        parser.error("--tracers, --tracer-max-age, --tracer-dump-every and --tracer-sort-every must be >= 0")
     if not tracing and (args.tracer_seed is not None or args.tracer_once or args.tracer_max_age is not None or args.tracer_file
                         or args.tracer_dump_every):
         parser.error("--tracer-seed, --tracer-once, --tracer-max-age, --tracer-file and --tracer-dump-every need --tracers N or --tracer-line")
+    if not tracing and (args.tracer_sort_every or args.tracer_fields or args.tracer_fields_file):
+        parser.error("--tracer-sort-every, --tracer-fields and --tracer-fields-file need --tracers N or --tracer-line")
+    if args.tracer_fields_file and not args.tracer_fields:
+        parser.error("--tracer-fields-file needs --tracer-fields")
     lines = [_tracer_line(parser, spec) for spec in args.tracer_line]
     max_age = args.tracer_max_age or 0
     if tracing and args.load_state:
@@ -377,7 +390,7 @@ def main(argv=None):
     tracer_file = None
     if tracing:
         tracer_file = Path(args.tracer_file) if args.tracer_file else out / "tracers.npz"
-        if args.load_state and load_tracers(sim, args.load_state):
+        if args.load_state and load_tracers(sim, args.load_state, args.tracer_sort_every):
             print(f"tracers: continuing the checkpoint's {sim._tracers.set.n} particles (the seed flags are not used)")
         else:
             seeds, notes = tracer_seeds(np.asarray(sim._solver._bc.mask), args.tracers, args.tracer_seed or 0, lines)
@@ -387,11 +400,20 @@ def main(argv=None):
                 print("tracers: no seed lies in a fluid cell", file=sys.stderr)
                 dev.close()
                 sys.exit(2)
-            sim.seed_tracers(seeds, respawn=not args.tracer_once, max_age=max_age)
+            sim.seed_tracers(seeds, respawn=not args.tracer_once, max_age=max_age, sort_every=args.tracer_sort_every)
+    fields_file = None
+    if tracing and args.tracer_fields:
+        fields_file = Path(args.tracer_fields_file) if args.tracer_fields_file else out / "tracer_fields.npz"
 
-    def write_tracers(path):
+    def write_tracers(path, fields_path=None, step=None):
         path.parent.mkdir(parents=True, exist_ok=True)
         np.savez(str(path), **sim.tracers())
+        if fields_path is not None:
+            from fs.tracers import residence_map
+            f = sim.tracer_fields()
+            fields_path.parent.mkdir(parents=True, exist_ok=True)
+            np.savez(str(fields_path), count=f["count"], age_sum=f["age_sum"], residence=residence_map(f["count"], f["age_sum"], dt),
+                     step=np.array(step))
 
     stats = None
     if args.stats_every > 0:
@@ -404,7 +426,7 @@ def main(argv=None):
             write_history()
             write_mean()
             if tracer_file is not None:
-                write_tracers(tracer_file)
+                write_tracers(tracer_file, fields_file, step)
             dev.close()
             sys.exit(3)
 
@@ -434,7 +456,7 @@ def main(argv=None):
             out.mkdir(exist_ok=True)
             np.savez(str(out / f"step_{step:06}.npz"), **sim.field_to_numpy())
         if args.tracer_dump_every and step % args.tracer_dump_every == 0:
-            write_tracers(out / f"tracers_{step:06}.npz")
+            write_tracers(out / f"tracers_{step:06}.npz", out / f"tracer_fields_{step:06}.npz" if fields_file is not None else None, step)
     dev.sync()
     el = time.perf_counter() - t0
     print(f"{args.steps} steps in {el:.3f} s = {args.steps / el:.1f} steps/s")
@@ -445,7 +467,7 @@ def main(argv=None):
     write_history()
     write_mean()
     if tracer_file is not None:
-        write_tracers(tracer_file)
+        write_tracers(tracer_file, fields_file, step0 + args.steps)
     dev.close()
 
 

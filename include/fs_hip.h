@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 13
+#define FS_ABI_VERSION 14
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -344,11 +344,24 @@ int fs_mean_free(fs_ctx *ctx, fs_mean *m);
  *           one IEEE double operation in the order written (no FMA): an IEEE double loop reproduces the state bit for bit.  No atomics;
  *           changes no field; the counter advances on the device.
  * read:     synchronises; pos (may be NULL) receives [4][n] doubles: x, y, x_seed, y_seed; ints (may be NULL) [3][n]: age, status, respawns.
- * write:    the inverse of read (checkpoints): status in 0 .. 3, age and respawns >= 0, launches >= 0.
+ *           Always in SEED order (entry k belongs to seed k), whatever fs_tracer_sort has done to the device arrays.
+ * write:    the inverse of read (checkpoints): status in 0 .. 3, age and respawns >= 0, launches >= 0.  Seed order; the slot order on the
+ *           device is the seed order again afterwards.
+ * sort:     reorders the particle SLOTS on the device by key = floor(y) * NB + floor(x) / FS_TRACER_SORT_BIN_CELLS, NB = ceil(X /
+ *           FS_TRACER_SORT_BIN_CELLS); a particle that is not alive, or not inside the domain (NaN included), has key = Y * NB.  Afterwards
+ *           the keys are non-decreasing along the slots; the order inside a bin is unspecified.  A counting sort in a handful of launches
+ *           (integer atomics; profiled as tracer_sort_count / _scan / _scatter / _copy); its scratch (36 bytes per particle + 4 bytes per
+ *           bin) is allocated at the first sort and freed with the set.  Changes nothing any other entry point shows except order, and no
+ *           device address: a graph that holds the advance launch stays valid.
+ * order:    synchronises; ids receives [n] ints: the seed index of the particle in slot k (the identity until the first sort).
+ * fields:   one launch: every alive particle inside the domain adds 1 to the count and its age to the age sum of cell (floor x, floor y).
+ *           count receives [Y][X] ints, age_sum [Y][X] 64-bit sums (x contiguous, the library's layout).  Integer atomics: exact and
+ *           repeatable.  12 bytes per cell of device memory for the duration of the call.
  * draw:     stores (r, g, b) into pixel (floor x, floor y) of the 3-channel field rgb for every particle with status 0.
  * free:     a graph that holds the launch must not be replayed afterwards; during a capture the release is deferred to its end (as
  *           fs_history_free).
- * create, read and write return FS_ERR_STATE during graph capture / tape recording.                                                    */
+ * create, read, write, sort, order and fields return FS_ERR_STATE during graph capture / tape recording.                               */
+#define FS_TRACER_SORT_BIN_CELLS 32
 #define FS_TRACER_ALIVE 0
 #define FS_TRACER_LEFT 1
 #define FS_TRACER_WALL 2
@@ -359,6 +372,9 @@ int fs_tracer_advance(fs_ctx *ctx, fs_tracer *t, double h, double limit, const f
 int fs_tracer_read(fs_ctx *ctx, fs_tracer *t, double *pos, int *ints, long long *launches);
 int fs_tracer_write(fs_ctx *ctx, fs_tracer *t, const double *pos, const int *ints, long long launches);
 int fs_tracer_draw(fs_ctx *ctx, fs_tracer *t, double r, double g, double b, fs_field *rgb);
+int fs_tracer_sort(fs_ctx *ctx, fs_tracer *t);
+int fs_tracer_order(fs_ctx *ctx, fs_tracer *t, int *ids);
+int fs_tracer_fields(fs_ctx *ctx, fs_tracer *t, int *count, long long *age_sum);
 int fs_tracer_free(fs_ctx *ctx, fs_tracer *t);
 
 /* ---- pointwise -------------------------------------------------------------------------------- */

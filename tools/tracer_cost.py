@@ -3,6 +3,11 @@ process so that clock drift hits both alike; median of the repetitions, one JSON
 advance launch (HIP events around eager launches) for seeds in random order and for the same seeds sorted by cell, the bytes the byte model
 counts for it and the float4 copy rate of this GPU measured in the same process.
 
+--sort-every K[,K...] adds one configuration per interval (FluidSimulator.seed_tracers(sort_every=K); 0 is the unsorted set), alternated
+with the others, and two more lines: the time of one device sort (HIP events around one tracer_sort: of the randomly ordered set, and of
+the set it has just sorted), the advance right after it and 1, 8, 32, ... steps of the running flow later, each pass of the sort from the
+launch profile; and the time of one tracer_fields call with the share that is not the launch (allocation, zeroing, download).
+
 Byte model of one launch: 44 B of state per alive particle (x, y, age, status read; x, y, age written) plus the cache lines its gathers
 touch - the eight corner values of a stage (four row segments of the velocity field) and one mask byte.  The second stage moves the point by
 a fraction of a cell and mostly stays on the first stage's lines; lines are 128 B.  Two counts frame the traffic: every particle fetching
@@ -10,6 +15,7 @@ its own lines (no reuse between particles) and every distinct line fetched once 
 
   python tools/tracer_cost.py --bc 1 --res 400 --n 16384 --steps 4000 --reps 3
   python tools/tracer_cost.py --bc 5 --res 4096 --n 1048576 --steps 300 --reps 3
+  python tools/tracer_cost.py --bc 5 --res 4096 --n 16777216 --steps 1024 --reps 3 --sort-every 0,8,32,128,512
   rocprofv3 --kernel-trace --stats -- python tools/tracer_cost.py --bc 5 --res 4096 --n 1048576 --steps 100 --reps 1 --only-on   (kernel time)
 """
 import argparse
@@ -43,6 +49,53 @@ def gather_lines(seeds, X, Y, pitch, esize):
     return per + len(seeds), len(np.unique(ids)) + len(np.unique(m))
 
 
+def _profiled(dev, fn):
+    """{profile name: us per launch} of what fn() launches."""
+    dev.sync()
+    dev.profile_reset()
+    dev.profile(True)
+    fn()
+    dev.sync()
+    rep = dev.profile_report()
+    dev.profile(False)
+    dev.profile_reset()
+    return {k: 1e3 * ms / n for k, (n, ms) in rep.items() if n}
+
+
+def sort_lines(sim, dev, seeds, a):
+    """One device sort in isolation, the advance after it as the flow carries the particles on, and one tracer_fields call."""
+    sim.seed_tracers(seeds)
+    sim.run(64)
+    tr = sim._tracers.set
+    before = _profiled(dev, sim.step)["tracer_advance"]
+    spans = []
+    for _ in range(2):                       # the randomly ordered set, then the set just sorted
+        dev.sync()
+        dev.span_begin()
+        dev.tracer_sort(tr)
+        spans.append(1e3 * dev.span_end())
+    passes = {k: round(v, 2) for k, v in _profiled(dev, lambda: dev.tracer_sort(tr)).items() if k.startswith("tracer_sort")}
+    decay, done = {}, 0
+    for after in (1, 8, 32, 128, 512, 2048):
+        if after - done - 1 > a.steps * 4:
+            break
+        sim.run(after - done - 1)
+        decay[str(after)] = round(_profiled(dev, sim.step)["tracer_advance"], 2)
+        done = after
+    print(json.dumps({"bc": a.bc, "res": a.res, "tracers": a.n, "note": "one tracer_sort between two HIP events; tracer_advance of one eager step",
+                      "sort_us_random_order": round(spans[0], 2), "sort_us_sorted_order": round(spans[1], 2), "sort_passes_us_sorted_order": passes,
+                      "advance_us_before_sort": round(before, 2), "advance_us_steps_after_sort": decay}), flush=True)
+    dev.sync()
+    t0 = time.perf_counter()
+    f = sim.tracer_fields()
+    wall = 1e6 * (time.perf_counter() - t0)
+    launch = _profiled(dev, sim.tracer_fields)["tracer_fields"]
+    print(json.dumps({"bc": a.bc, "res": a.res, "tracers": a.n, "note": "one tracer_fields call (host clock) and its launch (zeroing + kernel, HIP events)",
+                      "fields_call_us": round(wall, 1), "fields_launch_us": round(launch, 2), "fields_other_share": round(1.0 - launch / wall, 4),
+                      "cells_occupied": int((f["count"] > 0).sum())}), flush=True)
+    sim.stop_tracers()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bc", type=int, default=1)
@@ -54,7 +107,9 @@ def main():
     ap.add_argument("--vc", type=float, default=5.0)
     ap.add_argument("--f64", action="store_true")
     ap.add_argument("--only-on", action="store_true", help="run with the tracers only (profiling)")
+    ap.add_argument("--sort-every", default="", help="comma-separated sort intervals to measure as configurations of their own (0: unsorted)")
     a = ap.parse_args()
+    intervals = [int(k) for k in a.sort_every.split(",") if k != ""]
     import fs
     from fs.tracers import seed_random
     fs.runtime.init(gpu=0, dtype="f64" if a.f64 else "f32")
@@ -64,13 +119,14 @@ def main():
     mask = np.asarray(sim._solver._bc.mask)
     X, Y = mask.shape
     seeds = seed_random(mask, a.n, 1)
-    configs = [True] if a.only_on else [False, True]
+    # a configuration: False (no tracers), True (the unsorted set) or ("sort", K)
+    configs = ([] if a.only_on else [False]) + ([("sort", k) for k in intervals] if intervals else [True])
     sim.run(64)
     rates = {c: [] for c in configs}
     for _ in range(a.reps):
         for on in configs:
             if on:
-                sim.seed_tracers(seeds)
+                sim.seed_tracers(seeds, sort_every=on[1] if on is not True else 0)
             sim.run(64)                              # (captures the graphs of this mode)
             dev.sync()
             t0 = time.perf_counter()
@@ -86,9 +142,16 @@ def main():
         med = float(np.median(rates[on]))
         out = {"bc": a.bc, "res": res, "dtype": "f64" if a.f64 else "f32", "steps": a.steps, "tracers": a.n if on else 0,
                "steps_per_s": [round(r, 1) for r in rates[on]], "us_per_step": round(1e6 / med, 3)}
+        if on is not True and on:
+            out["sort_every"] = on[1]
         if on and base:
-            out.update(cost_us_per_step=round(1e6 / med - 1e6 / base, 3), cost_percent=round(100.0 * (base / med - 1.0), 2))
+            # the surcharge of every repetition against the same repetition's run without tracers: its spread is the yardstick of a gain
+            per_rep = [1e6 / r - 1e6 / b for r, b in zip(rates[on], rates[False])]
+            out.update(cost_us_per_step=round(1e6 / med - 1e6 / base, 3), cost_percent=round(100.0 * (base / med - 1.0), 2),
+                       cost_us_per_step_min=round(min(per_rep), 3), cost_us_per_step_max=round(max(per_rep), 3))
         print(json.dumps(out), flush=True)
+    if intervals:
+        sort_lines(sim, dev, seeds, a)
     # one launch in isolation: 20 advances timed by HIP events, seeds in random order and sorted by cell (row, then column)
     v = sim._solver.get_fields()[0]
     h = sim._solver.dt / sim._solver.dx
