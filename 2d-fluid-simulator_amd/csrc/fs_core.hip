@@ -33,6 +33,11 @@ static void tracer_release(fs_tracer *t)
     if (t->d_spos) hipFree(t->d_spos);
     if (t->d_sint) hipFree(t->d_sint);
     if (t->d_bins) hipFree(t->d_bins);
+    if (t->d_vel) hipFree(t->d_vel);
+    if (t->d_svel) hipFree(t->d_svel);
+    if (t->d_dep) hipFree(t->d_dep);
+    if (t->d_acc) hipFree(t->d_acc);
+    if (t->d_acc_state) hipFree(t->d_acc_state);
     delete t;
 }
 
@@ -693,6 +698,7 @@ int fs_destroy(fs_ctx *ctx)
     for (fs_tracer *t : ctx->tracers) tracer_release(t);
     for (fs_tracer *t : ctx->deferred_tracer) tracer_release(t);
     ctx->tracers.clear();
+    for (void *b : ctx->deferred_accum) hipFree(b);
     if (ctx->d_mask) hipFree(ctx->d_mask);
     if (ctx->d_bc_const) hipFree(ctx->d_bc_const);
     if (ctx->d_bc_dye) hipFree(ctx->d_bc_dye);
@@ -1486,6 +1492,18 @@ int fs_tracer_advance(fs_ctx *ctx, fs_tracer *t, double h, double limit, const f
     const TracerDev td = tracer_dev(t);
     const dim3 grid((t->n + TRACER_WG - 1) / TRACER_WG);
     const int Y = ctx->Y, respawn = t->respawn, max_age = t->max_age;
+    if (t->inertial) {
+        const size_t n = (size_t)t->n;
+        const TracerInertial q{t->d_vel, t->d_vel + n, t->d_vel + 2 * n, t->d_vel + 3 * n, t->gx, t->gy, t->d_dep};
+        FS_DISPATCH(ctx, {
+            return launch(ctx, "tracer_advance_inertial", [=] {
+                if (limit > 0.0)
+                    FS_KLAUNCH((k_tracer_advance_inertial<T, true>), grid, dim3(TRACER_WG), 0, ctx->stream, ctx->grid(), Y, h, limit, respawn, max_age, td, q, (const T *)v->d);
+                else
+                    FS_KLAUNCH((k_tracer_advance_inertial<T, false>), grid, dim3(TRACER_WG), 0, ctx->stream, ctx->grid(), Y, h, limit, respawn, max_age, td, q, (const T *)v->d);
+            });
+        })
+    }
     FS_DISPATCH(ctx, {
         return launch(ctx, "tracer_advance", [=] {
             if (limit > 0.0)
@@ -1494,6 +1512,29 @@ int fs_tracer_advance(fs_ctx *ctx, fs_tracer *t, double h, double limit, const f
                 FS_KLAUNCH((k_tracer_advance<T, false>), grid, dim3(TRACER_WG), 0, ctx->stream, ctx->grid(), Y, h, limit, respawn, max_age, td, (const T *)v->d);
         });
     })
+}
+
+// id (slot -> seed index) on the host, synchronised; FS_ERR_STATE when an entry lies outside 0 .. n - 1
+static int tracer_ids(fs_ctx *ctx, const fs_tracer *t, const char *who, std::vector<int> &id)
+{
+    const size_t n = (size_t)t->n;
+    id.resize(n);
+    FS_HIP(hipMemcpyAsync(id.data(), t->d_int + 3 * n, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    for (size_t k = 0; k < n; ++k)
+        if (id[k] < 0 || (size_t)id[k] >= n) { set_error(std::string(who) + ": the slot -> seed index array is not a permutation"); return FS_ERR_STATE; }
+    return FS_OK;
+}
+
+// `rows` arrays of n doubles from slot order into seed order (out[id[k]] = in[k]) or back (out[k] = in[id[k]])
+static void tracer_reorder(const std::vector<int> &id, int rows, const double *in, double *out, bool to_seed)
+{
+    const size_t n = id.size();
+    for (int r = 0; r < rows; ++r)
+        for (size_t k = 0; k < n; ++k) {
+            if (to_seed) out[r * n + (size_t)id[k]] = in[r * n + k];
+            else out[r * n + k] = in[r * n + (size_t)id[k]];
+        }
 }
 
 int fs_tracer_read(fs_ctx *ctx, fs_tracer *t, double *pos, int *ints, long long *launches)
@@ -1540,6 +1581,17 @@ int fs_tracer_write(fs_ctx *ctx, fs_tracer *t, const double *pos, const int *int
     for (size_t k = 0; k < n; ++k)
         FS_REQUIRE(ints[k] >= 0 && ints[n + k] >= 0 && ints[n + k] <= 3 && ints[2 * n + k] >= 0, "tracer state: age / respawns < 0 or status outside 0 .. 3");
     FS_HIP(hipSetDevice(ctx->device));
+    std::vector<double> hv;
+    if (t->inertial && t->permuted) {      // pu, pw follow their particles back into seed order; alpha, tau from the host copy.  Staged
+        hv.resize(4 * n);                  // on the host first: no upload is issued before the last step here that can fail
+        std::vector<double> sv(2 * n);
+        std::vector<int> id;
+        FS_HIP(hipMemcpyAsync(sv.data(), t->d_vel, 2 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        int rc = tracer_ids(ctx, t, "fs_tracer_write", id); if (rc) return rc;
+        tracer_reorder(id, 2, sv.data(), hv.data(), true);
+        std::copy(t->h_resp.begin(), t->h_resp.end(), hv.begin() + 2 * n);
+    }
+    if (!hv.empty()) FS_HIP(hipMemcpyAsync(t->d_vel, hv.data(), 4 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     FS_HIP(hipMemcpyAsync(t->d_pos, pos, 4 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     FS_HIP(hipMemcpyAsync(t->d_int, ints, 3 * n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     FS_HIP(hipMemcpyAsync(t->d_count, &launches, sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
@@ -1564,11 +1616,13 @@ static int tracer_sort_scratch(fs_ctx *ctx, fs_tracer *t)
     const int nbins = ctx->Y * NB + 1, nblocks = (nbins + TRACER_SCAN_TILE - 1) / TRACER_SCAN_TILE;
     hipError_t e = hipMalloc(&t->d_spos, 2 * n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&t->d_sint, 5 * n * sizeof(int));
+    if (e == hipSuccess && t->inertial) e = hipMalloc(&t->d_svel, 4 * n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&t->d_bins, ((size_t)nbins + nblocks) * sizeof(int));
     if (e != hipSuccess) {
         if (t->d_spos) hipFree(t->d_spos);
         if (t->d_sint) hipFree(t->d_sint);
-        t->d_spos = nullptr; t->d_sint = nullptr; t->d_bins = nullptr;
+        if (t->d_svel) hipFree(t->d_svel);
+        t->d_spos = nullptr; t->d_sint = nullptr; t->d_svel = nullptr; t->d_bins = nullptr;
         return hip_fail(e, "fs_tracer_sort (scratch)", __FILE__, __LINE__);
     }
     t->nbins = nbins; t->nblocks = nblocks;
@@ -1600,12 +1654,16 @@ int fs_tracer_sort(fs_ctx *ctx, fs_tracer *t)
         FS_KLAUNCH(k_tracer_scan_add, dim3((nbins + TRACER_WG - 1) / TRACER_WG), wg, 0, st, nbins, bins, (const int *)sums);
     });
     if (rc) return rc;
+    double *vel = t->d_vel, *sv = t->d_svel;
+    const bool carry = t->inertial;
     rc = launch(ctx, "tracer_sort_scatter", [=] {
-        FS_KLAUNCH(k_tracer_sort_scatter, grid, wg, 0, st, td, (const int *)key, bins, sx, sy, si);
+        if (carry) FS_KLAUNCH(k_tracer_sort_scatter_inertial, grid, wg, 0, st, td, (const int *)key, bins, sx, sy, si, (const double *)vel, sv);
+        else FS_KLAUNCH(k_tracer_sort_scatter, grid, wg, 0, st, td, (const int *)key, bins, sx, sy, si);
     });
     if (rc) return rc;
     rc = launch(ctx, "tracer_sort_copy", [=] {
-        FS_KLAUNCH(k_tracer_sort_copy, grid, wg, 0, st, td, (const double *)sx, (const double *)sy, (const int *)si);
+        if (carry) FS_KLAUNCH(k_tracer_sort_copy_inertial, grid, wg, 0, st, td, (const double *)sx, (const double *)sy, (const int *)si, vel, (const double *)sv);
+        else FS_KLAUNCH(k_tracer_sort_copy, grid, wg, 0, st, td, (const double *)sx, (const double *)sy, (const int *)si);
     });
     if (rc) return rc;
     t->permuted = true;
@@ -1671,6 +1729,223 @@ int fs_tracer_draw(fs_ctx *ctx, fs_tracer *t, double r, double g, double b, fs_f
     })
 }
 
+// ---- inertial sets ------------------------------------------------------------------------------------------
+int fs_tracer_create_inertial(fs_ctx *ctx, int n, const double *seeds_xy, const double *alpha, const double *tau, double gx, double gy, int respawn,
+                              int max_age, int deposits, fs_tracer **out)
+{
+    FS_REQUIRE(ctx && seeds_xy && alpha && tau && out, "null argument");
+    FS_REQUIRE(n >= 1, "a tracer set needs at least one particle");
+    FS_REQUIRE(std::isfinite(gx) && std::isfinite(gy), "gravity must be finite");
+    for (int k = 0; k < n; ++k) {
+        FS_REQUIRE(alpha[k] > 0.0 && alpha[k] <= 1.0, "alpha must lie in (0, 1]");
+        FS_REQUIRE(tau[k] >= 0.0 && std::isfinite(tau[k]), "tau must be finite and >= 0");
+    }
+    fs_tracer *t = nullptr;
+    int rc = fs_tracer_create(ctx, n, seeds_xy, respawn, max_age, &t);
+    if (rc) return rc;
+    const size_t N = (size_t)n, cells = (size_t)ctx->X * ctx->Y;
+    std::vector<double> vel(4 * N, 0.0);
+    std::copy(alpha, alpha + N, vel.begin() + 2 * N);
+    std::copy(tau, tau + N, vel.begin() + 3 * N);
+    hipError_t e = hipMalloc(&t->d_vel, vel.size() * sizeof(double));
+    if (e == hipSuccess && deposits) e = hipMalloc(&t->d_dep, cells * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpyAsync(t->d_vel, vel.data(), vel.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && deposits) e = hipMemsetAsync(t->d_dep, 0, cells * sizeof(int), ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // (the source is this frame's memory)
+    if (e != hipSuccess) { ctx->tracers.erase(t); tracer_release(t); return hip_fail(e, "fs_tracer_create_inertial", __FILE__, __LINE__); }
+    t->inertial = true; t->gx = gx; t->gy = gy;
+    t->h_resp.assign(vel.begin() + 2 * N, vel.end());
+    *out = t;
+    return FS_OK;
+}
+
+#define FS_TRACER_INERTIAL(t) FS_REQUIRE((t)->inertial, "not an inertial tracer set (fs_tracer_create_inertial)")
+
+int fs_tracer_read_vel(fs_ctx *ctx, fs_tracer *t, double *vel)
+{
+    FS_REQUIRE(ctx && t && vel, "null argument");
+    FS_TRACER_HANDLE(t);
+    FS_TRACER_INERTIAL(t);
+    FS_TRACER_NO_CAPTURE("read_vel")
+    FS_HIP(hipSetDevice(ctx->device));
+    const size_t n = (size_t)t->n;
+    if (!t->permuted) {
+        FS_HIP(hipMemcpyAsync(vel, t->d_vel, 2 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        FS_HIP(hipStreamSynchronize(ctx->stream));
+        return FS_OK;
+    }
+    std::vector<double> sv(2 * n);
+    std::vector<int> id;
+    FS_HIP(hipMemcpyAsync(sv.data(), t->d_vel, 2 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    int rc = tracer_ids(ctx, t, "fs_tracer_read_vel", id); if (rc) return rc;
+    tracer_reorder(id, 2, sv.data(), vel, true);
+    return FS_OK;
+}
+
+int fs_tracer_write_vel(fs_ctx *ctx, fs_tracer *t, const double *vel)
+{
+    FS_REQUIRE(ctx && t && vel, "null argument");
+    FS_TRACER_HANDLE(t);
+    FS_TRACER_INERTIAL(t);
+    FS_TRACER_NO_CAPTURE("write_vel")
+    FS_HIP(hipSetDevice(ctx->device));
+    const size_t n = (size_t)t->n;
+    if (!t->permuted) {
+        FS_HIP(hipMemcpyAsync(t->d_vel, vel, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        FS_HIP(hipStreamSynchronize(ctx->stream));      // (the source is the caller's memory)
+        return FS_OK;
+    }
+    std::vector<double> sv(2 * n);
+    std::vector<int> id;
+    int rc = tracer_ids(ctx, t, "fs_tracer_write_vel", id); if (rc) return rc;
+    tracer_reorder(id, 2, vel, sv.data(), false);
+    FS_HIP(hipMemcpyAsync(t->d_vel, sv.data(), 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_tracer_deposits(fs_ctx *ctx, fs_tracer *t, int *out)
+{
+    FS_REQUIRE(ctx && t && out, "null argument");
+    FS_TRACER_HANDLE(t);
+    FS_REQUIRE(t->d_dep, "the tracer set records no deposits (fs_tracer_create_inertial with deposits != 0)");
+    FS_TRACER_NO_CAPTURE("deposits")
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemcpyAsync(out, t->d_dep, (size_t)ctx->X * ctx->Y * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_tracer_deposits_write(fs_ctx *ctx, fs_tracer *t, const int *in)
+{
+    FS_REQUIRE(ctx && t && in, "null argument");
+    FS_TRACER_HANDLE(t);
+    FS_REQUIRE(t->d_dep, "the tracer set records no deposits (fs_tracer_create_inertial with deposits != 0)");
+    FS_TRACER_NO_CAPTURE("deposits_write")
+    const size_t cells = (size_t)ctx->X * ctx->Y;
+    for (size_t c = 0; c < cells; ++c) FS_REQUIRE(in[c] >= 0, "deposit counts must be >= 0");
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemcpyAsync(t->d_dep, in, cells * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));      // (the source is the caller's memory)
+    return FS_OK;
+}
+
+// ---- accumulated occupancy ----------------------------------------------------------------------------------
+#define FS_TRACER_ACCUM(t) FS_REQUIRE((t)->d_acc, "the tracer set has no accumulator (fs_tracer_accum_create)")
+
+int fs_tracer_accum_create(fs_ctx *ctx, fs_tracer *t, long long every, long long start)
+{
+    FS_REQUIRE(ctx && t, "null argument");
+    FS_TRACER_HANDLE(t);
+    FS_REQUIRE(every >= 1 && start >= 0, "every must be >= 1 and start >= 0");
+    FS_TRACER_NO_CAPTURE("accum_create")
+    if (t->d_acc) { set_error("the tracer set has an accumulator already: fs_tracer_accum_free first"); return FS_ERR_STATE; }
+    FS_HIP(hipSetDevice(ctx->device));
+    const size_t cells = (size_t)ctx->X * ctx->Y;
+    hipError_t e = hipMalloc(&t->d_acc, 2 * cells * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc(&t->d_acc_state, 2 * sizeof(long long));
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_acc, 0, 2 * cells * sizeof(unsigned long long), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_acc_state, 0, 2 * sizeof(long long), ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(t->d_acc_state, t->d_count, sizeof(long long), hipMemcpyDeviceToDevice, ctx->stream);      // base
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        if (t->d_acc) hipFree(t->d_acc);
+        if (t->d_acc_state) hipFree(t->d_acc_state);
+        t->d_acc = nullptr; t->d_acc_state = nullptr;
+        return hip_fail(e, "fs_tracer_accum_create", __FILE__, __LINE__);
+    }
+    t->acc_every = every; t->acc_start = start;
+    return FS_OK;
+}
+
+int fs_tracer_accum_add(fs_ctx *ctx, fs_tracer *t)
+{
+    FS_REQUIRE(ctx && t, "null argument");
+    FS_TRACER_HANDLE(t);
+    FS_TRACER_ACCUM(t);
+    const TracerDev td = tracer_dev(t);
+    const dim3 grid((t->n + TRACER_WG - 1) / TRACER_WG);
+    const int X = ctx->X, Y = ctx->Y;
+    const long long every = t->acc_every, start = t->acc_start;
+    long long *state = t->d_acc_state;
+    unsigned long long *occ = t->d_acc, *age = t->d_acc + (size_t)X * Y;
+    return launch(ctx, "tracer_accumulate", [=] {
+        FS_KLAUNCH(k_tracer_accumulate, grid, dim3(TRACER_WG), 0, ctx->stream, X, Y, td, start, every, state, occ, age);
+    });
+}
+
+int fs_tracer_accum_read(fs_ctx *ctx, fs_tracer *t, long long *occupancy, long long *age_sum, long long *launches, long long *samples)
+{
+    FS_REQUIRE(ctx && t, "null argument");
+    FS_TRACER_HANDLE(t);
+    FS_TRACER_ACCUM(t);
+    FS_TRACER_NO_CAPTURE("accum_read")
+    FS_HIP(hipSetDevice(ctx->device));
+    const size_t cells = (size_t)ctx->X * ctx->Y;
+    long long st[2] = {0, 0}, count = 0;
+    if (occupancy) FS_HIP(hipMemcpyAsync(occupancy, t->d_acc, cells * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    if (age_sum) FS_HIP(hipMemcpyAsync(age_sum, t->d_acc + cells, cells * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipMemcpyAsync(st, t->d_acc_state, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipMemcpyAsync(&count, t->d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    if (launches) *launches = count - st[0];
+    if (samples) *samples = st[1];
+    return FS_OK;
+}
+
+int fs_tracer_accum_write(fs_ctx *ctx, fs_tracer *t, const long long *occupancy, const long long *age_sum, long long launches, long long samples)
+{
+    FS_REQUIRE(ctx && t && occupancy && age_sum, "null argument");
+    FS_TRACER_HANDLE(t);
+    FS_TRACER_ACCUM(t);
+    FS_REQUIRE(samples >= 0 && samples <= launches, "counters must satisfy 0 <= samples <= launches");
+    FS_TRACER_NO_CAPTURE("accum_write")
+    FS_HIP(hipSetDevice(ctx->device));
+    const size_t cells = (size_t)ctx->X * ctx->Y;
+    for (size_t c = 0; c < cells; ++c) FS_REQUIRE(occupancy[c] >= 0 && age_sum[c] >= 0, "accumulated counts must be >= 0");
+    long long count = 0;
+    FS_HIP(hipMemcpyAsync(&count, t->d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    FS_REQUIRE(launches <= count, "the accumulator cannot be older than the set: launches exceeds the set's launch count (fs_tracer_write first)");
+    const long long st[2] = {count - launches, samples};
+    FS_HIP(hipMemcpyAsync(t->d_acc, occupancy, cells * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipMemcpyAsync(t->d_acc + cells, age_sum, cells * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipMemcpyAsync(t->d_acc_state, st, sizeof st, hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));      // (the sources are the caller's / this frame's memory)
+    return FS_OK;
+}
+
+int fs_tracer_accum_reset(fs_ctx *ctx, fs_tracer *t)
+{
+    FS_REQUIRE(ctx && t, "null argument");
+    FS_TRACER_HANDLE(t);
+    FS_TRACER_ACCUM(t);
+    FS_TRACER_NO_CAPTURE("accum_reset")
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemsetAsync(t->d_acc, 0, 2 * (size_t)ctx->X * ctx->Y * sizeof(unsigned long long), ctx->stream));
+    FS_HIP(hipMemsetAsync(t->d_acc_state + 1, 0, sizeof(long long), ctx->stream));      // (the base stays: the phase runs on)
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_tracer_accum_free(fs_ctx *ctx, fs_tracer *t)
+{
+    if (!t) return FS_OK;
+    FS_REQUIRE(ctx && t->ctx == ctx && ctx->tracers.count(t), "tracer set from another context or freed");
+    if (!t->d_acc) return FS_OK;
+    if (ctx->capturing) {      // (no synchronisation / hipFree inside a capture)
+        ctx->deferred_accum.push_back(t->d_acc);
+        ctx->deferred_accum.push_back(t->d_acc_state);
+    } else {
+        hipSetDevice(ctx->device);
+        hipStreamSynchronize(ctx->stream);
+        hipFree(t->d_acc);
+        hipFree(t->d_acc_state);
+    }
+    t->d_acc = nullptr; t->d_acc_state = nullptr;
+    return FS_OK;
+}
+
 int fs_tracer_free(fs_ctx *ctx, fs_tracer *t)
 {
     if (!t) return FS_OK;
@@ -1710,6 +1985,8 @@ int fs_graph_end(fs_ctx *ctx, int *graph_id)
     ctx->deferred_mean.clear();
     for (fs_tracer *t : ctx->deferred_tracer) tracer_release(t);      // and tracer sets (fs_tracer_free)
     ctx->deferred_tracer.clear();
+    for (void *b : ctx->deferred_accum) hipFree(b);                   // and accumulators (fs_tracer_accum_free)
+    ctx->deferred_accum.clear();
     if (ec != hipSuccess) return hip_fail(ec, "hipStreamEndCapture", __FILE__, __LINE__);
     hipGraphExec_t ex = nullptr;
     hipError_t e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);

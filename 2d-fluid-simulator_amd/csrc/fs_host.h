@@ -133,6 +133,7 @@ struct fs_ctx {
     std::vector<fs_mean *> deferred_mean;    // fs_mean_free during a hipGraph capture: released when the capture ends
     std::set<fs_tracer *> tracers;           // live tracer sets (fs_tracer_create), released with the context
     std::vector<fs_tracer *> deferred_tracer;  // fs_tracer_free during a hipGraph capture: released when the capture ends
+    std::vector<void *> deferred_accum;        // fs_tracer_accum_free during a hipGraph capture: device blocks released when the capture ends
     // tuning knobs (env FS_MARCH=0: one-cell-per-lane kernels only)
     bool use_march = true;
     bool use_pairs = true;     // lanes of 2 cells: even widths (every `res`); use_march: the quad kernels, X % 4 == 0
@@ -207,6 +208,17 @@ struct fs_tracer {
     int *d_sint = nullptr;          // [5][n]: age, status, respawns, id in the new order; the key of every slot
     int *d_bins = nullptr;          // [nbins] counts / cursors, then [nblocks] totals of the scan's tiles
     int nbins = 0, nblocks = 0;
+    // inertial sets (fs_tracer_create_inertial)
+    bool inertial = false;
+    double gx = 0.0, gy = 0.0;
+    double *d_vel = nullptr;        // [4][n]: pu, pw, alpha, tau (slot order)
+    double *d_svel = nullptr;       // [4][n]: the same in the new order (with the sort's scratch)
+    std::vector<double> h_resp;     // [2][n]: alpha, tau in SEED order (fs_tracer_write puts the slots back into seed order)
+    int *d_dep = nullptr;           // [Y][X] deposit counts, or nullptr (deposits off)
+    // accumulated occupancy (fs_tracer_accum_*): one per set
+    unsigned long long *d_acc = nullptr;      // [2][Y][X]: occupancy, age_sum
+    long long *d_acc_state = nullptr;         // [0] base: the launch count when attached, [1] samples
+    long long acc_every = 1, acc_start = 0;
 };
 
 namespace fs {

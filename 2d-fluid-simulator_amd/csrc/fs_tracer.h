@@ -34,6 +34,28 @@
 // bin is whatever the atomics make it - nothing observable depends on it, every reader goes through id) and k_tracer_sort_copy back into
 // the arrays the captured advance launches point to.  k_tracer_fields bins the alive, inside particles by CELL: count (int) and the sum of
 // their ages (64-bit) with integer atomics - exact and the same from run to run.  Resources and times: DESIGN.md 4ab.
+//
+// Inertial sets (fs_tracer_create_inertial).  Beyond the passive state a particle carries its velocity pu, pw (double, the field's velocity
+// units), alpha in (0, 1] and tau >= 0 (double); the set carries gravity (gx, gy).  alpha = -expm1(-dt / tau) comes from the host (1 for
+// tau == 0): the device evaluates no transcendental function.  k_tracer_advance_inertial, one launch per step, one lane per alive particle:
+//   (U, W) = V(x, y)                       tracer_velocity<T, LIM>, as above
+//   age == 0: pu = U; pw = W               a particle is released with the fluid's velocity at its position (creation and every respawn)
+//   su = tau gx; sw = tau gy               settling velocity
+//   pu = pu + alpha ((U + su) - pu)        the exact integral of dv/dt = (U - v) / tau + g over one step with U frozen
+//   pw = pw + alpha ((W + sw) - pw)
+//   xn = x + h pu; yn = y + h pw           with the NEW velocity; not inside (NaN included) -> LEFT before any index is formed
+//   mask(floor xn, floor yn): 1 -> WALL, 3 -> LEFT, else the particle moves; age += 1; max_age as above
+// Fates as for passive sets; a respawn also stores pu = pw = 0 (never read: age 0 overwrites them), without respawn the updated pu, pw are
+// stored in every case.  One gather stage and one mask byte, not two gather stages: as tau -> 0 (alpha = 1) the scheme is the forward-Euler
+// tracer x + h V(x), NOT the passive set's midpoint rule.  A particle may cross more than one cell per step, as a passive one may.
+// Deposition (dep != nullptr): a particle whose fate is WALL adds 1 to cell (floor xn, floor yn) of an int plane [Y][X] with one integer
+// atomic, respawn or not - exact and the same from run to run.  The sort carries pu, pw, alpha, tau with the slots (32 more bytes of scratch).
+//
+// k_tracer_accumulate (fs_tracer_accum_*; passive and inertial sets): behind the advance, gated ON THE DEVICE from the set's launch counter
+// by fs_mean_accumulate's rule - with n1 = count - base (launches since the accumulator was attached, this step's included) the launch
+// samples when n1 > start and (n1 - start) % every == 0.  A sampling launch does what k_tracer_fields does, into resident 64-bit planes
+// occupancy and age_sum [Y][X]; lane 0 counts the sample.  A launch that does not sample reads the two counters per workgroup and returns.
+// Resources and times: DESIGN.md 4ac.
 #pragma once
 #include "fs_kernels.h"
 
@@ -127,6 +149,65 @@ __global__ __launch_bounds__(TRACER_WG) void k_tracer_advance(Grid g, int Y, dou
     t.x[k] = px;
     t.y[k] = py;
     t.age[k] = age;
+    if (fate != TR_ALIVE) t.status[k] = fate;
+}
+
+// the additional state of an inertial set: slot-indexed pu, pw, alpha, tau; gravity; the deposit plane [Y][X] or nullptr
+struct TracerInertial {
+    double *pu, *pw;
+    const double *alpha, *tau;
+    double gx, gy;
+    int *dep;
+};
+
+template <typename T, bool LIM>
+__global__ __launch_bounds__(TRACER_WG) void k_tracer_advance_inertial(Grid g, int Y, double h, double limit, int respawn, int max_age, TracerDev t,
+                                                                       TracerInertial q, const T *__restrict__ v)
+{
+    const int k = blockIdx.x * TRACER_WG + threadIdx.x;
+    if (k == 0) t.count[0] = t.count[0] + 1;        // (nothing in the kernel depends on it)
+    if (k >= t.n || t.status[k] != TR_ALIVE) return;
+    const double x = t.x[k], y = t.y[k];
+    const int age0 = t.age[k];
+    double pu = q.pu[k], pw = q.pw[k];
+    const double alpha = q.alpha[k], tau = q.tau[k];
+    const double X = (double)g.X, Yd = (double)Y;
+    double px = x, py = y;      // where the particle stays when it is not respawned
+    int fate = TR_ALIVE;
+    double U, W;
+    tracer_velocity<T, LIM>(g, Y, v, (T)limit, x, y, U, W);
+    if (age0 == 0) { pu = U; pw = W; }
+    const double su = tau * q.gx, sw = tau * q.gy;
+    pu = pu + alpha * ((U + su) - pu);
+    pw = pw + alpha * ((W + sw) - pw);
+    const double xn = x + h * pu, yn = y + h * pw;
+    if (!tracer_inside(xn, yn, X, Yd)) fate = TR_LEFT;
+    else {
+        const int i = (int)floor(xn), j = (int)floor(yn);
+        const uint8_t m = mask_at(g, i, j);
+        if (m == 1) {
+            fate = TR_WALL;
+            if (q.dep) atomicAdd(&q.dep[(size_t)j * g.X + i], 1);      // (inside: 0 <= i < X, 0 <= j < Y)
+        } else if (m == 3) fate = TR_LEFT;
+        else { px = xn; py = yn; }
+    }
+    const int age = age0 + 1;
+    if (fate == TR_ALIVE && max_age > 0 && age >= max_age) fate = TR_EXPIRED;
+    if (fate != TR_ALIVE && respawn) {
+        const int s = t.id[k];
+        t.x[k] = t.xs[s];
+        t.y[k] = t.ys[s];
+        t.age[k] = 0;
+        t.respawns[k] = t.respawns[k] + 1;
+        q.pu[k] = 0.0;
+        q.pw[k] = 0.0;
+        return;
+    }
+    t.x[k] = px;
+    t.y[k] = py;
+    t.age[k] = age;
+    q.pu[k] = pu;
+    q.pw[k] = pw;
     if (fate != TR_ALIVE) t.status[k] = fate;
 }
 
@@ -256,6 +337,49 @@ __global__ __launch_bounds__(TRACER_WG) void k_tracer_sort_copy(TracerDev t, con
     t.id[k] = si[3 * n + k];
 }
 
+// the same for an inertial set: pu, pw, alpha, tau (vel [4][n]) travel with the slot through sv [4][n]
+__global__ __launch_bounds__(TRACER_WG) void k_tracer_sort_scatter_inertial(TracerDev t, const int *__restrict__ key, int *__restrict__ bins,
+                                                                            double *__restrict__ sx, double *__restrict__ sy, int *__restrict__ si,
+                                                                            const double *__restrict__ vel, double *__restrict__ sv)
+{
+    const int k = blockIdx.x * TRACER_WG + threadIdx.x;
+    if (k >= t.n) return;
+    const size_t n = (size_t)t.n;
+    const double x = t.x[k], y = t.y[k];
+    const int age = t.age[k], status = t.status[k], respawns = t.respawns[k], id = t.id[k];
+    const double q0 = vel[k], q1 = vel[n + k], q2 = vel[2 * n + k], q3 = vel[3 * n + k];
+    const int d = atomicAdd(&bins[key[k]], 1);
+    if (d < 0 || d >= t.n) return;      // (cannot happen: the cursors end at the next bin's start; never store outside the arrays)
+    sx[d] = x;
+    sy[d] = y;
+    si[d] = age;
+    si[n + d] = status;
+    si[2 * n + d] = respawns;
+    si[3 * n + d] = id;
+    sv[d] = q0;
+    sv[n + d] = q1;
+    sv[2 * n + d] = q2;
+    sv[3 * n + d] = q3;
+}
+
+__global__ __launch_bounds__(TRACER_WG) void k_tracer_sort_copy_inertial(TracerDev t, const double *__restrict__ sx, const double *__restrict__ sy,
+                                                                         const int *__restrict__ si, double *__restrict__ vel, const double *__restrict__ sv)
+{
+    const int k = blockIdx.x * TRACER_WG + threadIdx.x;
+    if (k >= t.n) return;
+    const size_t n = (size_t)t.n;
+    t.x[k] = sx[k];
+    t.y[k] = sy[k];
+    t.age[k] = si[k];
+    t.status[k] = si[n + k];
+    t.respawns[k] = si[2 * n + k];
+    t.id[k] = si[3 * n + k];
+    vel[k] = sv[k];
+    vel[n + k] = sv[n + k];
+    vel[2 * n + k] = sv[2 * n + k];
+    vel[3 * n + k] = sv[3 * n + k];
+}
+
 // ---- fs_tracer_fields: per-cell count and age sum of the alive particles inside the domain (arrays [Y][X], zeroed before) ----------------
 __global__ __launch_bounds__(TRACER_WG) void k_tracer_fields(int X, int Y, TracerDev t, int *__restrict__ count, unsigned long long *__restrict__ age_sum)
 {
@@ -265,6 +389,24 @@ __global__ __launch_bounds__(TRACER_WG) void k_tracer_fields(int X, int Y, Trace
     if (!tracer_inside(x, y, (double)X, (double)Y)) return;
     const size_t c = (size_t)(int)floor(y) * X + (int)floor(x);
     atomicAdd(&count[c], 1);
+    atomicAdd(&age_sum[c], (unsigned long long)(long long)t.age[k]);
+}
+
+
+// ---- fs_tracer_accum_*: the same binning into resident 64-bit planes, on the launches the rule selects ----------------------------------
+// state: [0] base - the set's launch count when the accumulator was attached, [1] samples.  Runs behind the advance: count is final here.
+__global__ __launch_bounds__(TRACER_WG) void k_tracer_accumulate(int X, int Y, TracerDev t, long long start, long long every, long long *state,
+                                                                 unsigned long long *__restrict__ occupancy, unsigned long long *__restrict__ age_sum)
+{
+    const long long n1 = t.count[0] - state[0];
+    if (!(n1 > start && (n1 - start) % every == 0)) return;      // (the same in every lane of every workgroup)
+    const int k = blockIdx.x * TRACER_WG + threadIdx.x;
+    if (k == 0) state[1] = state[1] + 1;            // (no lane reads it)
+    if (k >= t.n || t.status[k] != TR_ALIVE) return;
+    const double x = t.x[k], y = t.y[k];
+    if (!tracer_inside(x, y, (double)X, (double)Y)) return;
+    const size_t c = (size_t)(int)floor(y) * X + (int)floor(x);
+    atomicAdd(&occupancy[c], 1ull);
     atomicAdd(&age_sum[c], (unsigned long long)(long long)t.age[k]);
 }
 

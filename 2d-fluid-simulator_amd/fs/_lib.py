@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FS_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libfs_hip.so")     # FS_LIB: A/B builds (tools/)
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _lib = None
 
@@ -98,6 +98,17 @@ _PROTOS = {
     "fs_tracer_order": [_c_vp, _c_vp, _P(_c_int)],
     "fs_tracer_fields": [_c_vp, _c_vp, _P(_c_int), _P(ctypes.c_longlong)],
     "fs_tracer_free": [_c_vp, _c_vp],
+    "fs_tracer_create_inertial": [_c_vp, _c_int, _P(_c_dbl), _P(_c_dbl), _P(_c_dbl), _c_dbl, _c_dbl, _c_int, _c_int, _c_int, _P(_c_vp)],
+    "fs_tracer_read_vel": [_c_vp, _c_vp, _P(_c_dbl)],
+    "fs_tracer_write_vel": [_c_vp, _c_vp, _P(_c_dbl)],
+    "fs_tracer_deposits": [_c_vp, _c_vp, _P(_c_int)],
+    "fs_tracer_deposits_write": [_c_vp, _c_vp, _P(_c_int)],
+    "fs_tracer_accum_create": [_c_vp, _c_vp, ctypes.c_longlong, ctypes.c_longlong],
+    "fs_tracer_accum_add": [_c_vp, _c_vp],
+    "fs_tracer_accum_read": [_c_vp, _c_vp, _P(ctypes.c_longlong), _P(ctypes.c_longlong), _P(ctypes.c_longlong), _P(ctypes.c_longlong)],
+    "fs_tracer_accum_write": [_c_vp, _c_vp, _P(ctypes.c_longlong), _P(ctypes.c_longlong), ctypes.c_longlong, ctypes.c_longlong],
+    "fs_tracer_accum_reset": [_c_vp, _c_vp],
+    "fs_tracer_accum_free": [_c_vp, _c_vp],
     "fs_limit_field": [_c_vp, _c_dbl, _c_vp] + _ROWS,
     "fs_clamp_field": [_c_vp, _c_dbl, _c_dbl, _c_vp] + _ROWS,
     "fs_cip_advect_dye_clamped": [_c_vp, _c_dbl, _c_dbl] + [_c_vp] * 7 + _ROWS,

@@ -15,7 +15,7 @@ from .boundary_condition import get_boundary_condition
 from .history import Recorder, body_faces, check_probes
 from .pressure_updater import JacobiPressureUpdater, RedBlackSorPressureUpdater
 from .solver import CipMacSolver, DyeCipMacSolver, DyeMacSolver, MacSolver
-from .tracers import Tracers, check_seeds
+from .tracers import TracerAccumulation, Tracers, check_seeds, response
 from .vorticity_confinement import VorticityConfinement
 
 _WALL_COLOR = (0.5, 0.7, 0.5)   # fs/fluid_simulator.py:17 (applied by the visualisation kernels, csrc/fs_kernels.h k_visualize)
@@ -106,6 +106,8 @@ class FluidSimulator:
         if tr is not None:
             self._dev.tracer_advance(tr.set, self._solver.dt / self._solver.dx, self._solver.get_fields()[0])
             tr.issued += 1
+            if tr.accumulation is not None:
+                self._dev.tracer_accum_add(tr.set)      # (behind the advance: gated on the device from the set's launch counter)
 
     def _sort_if_due(self):
         """The scheduled device sort of the tracer particles (seed_tracers(sort_every=K)): after every K-th step, between launch sequences -
@@ -169,6 +171,8 @@ class FluidSimulator:
             sig.append(self._averager.token)        # (likewise the accumulation launch of the time averages)
         if self._tracers is not None:
             sig.append(self._tracers.token)         # (and the advance of the tracer particles)
+            if self._tracers.accumulation is not None:
+                sig.append(self._tracers.accumulation.token)      # (and the accumulation launch behind it)
         return tuple(sig)
 
     _LONG_STEPS = 16     # steps per long-form graph (capture_period)
@@ -499,7 +503,7 @@ class FluidSimulator:
         self._averager = None
 
     # -- tracer particles (new): pathlines and streaklines advanced on the device ------------------------------------------------------
-    def seed_tracers(self, seeds, respawn=True, max_age=0, sort_every=0):
+    def seed_tracers(self, seeds, respawn=True, max_age=0, sort_every=0, tau=None, gravity=(0.0, 0.0), deposits=False):
         """From the next step on, N passive particles ride the step: seeds float64 (N, 2) in CELL units (cell (i, j) covers [i, i + 1) x
         [j, j + 1); fs.tracers.seed_line / seed_grid / seed_random build them), each inside the domain in a fluid or inflow cell
         (ValueError naming the first offender otherwise).  After every step each alive particle takes one midpoint step in the velocity
@@ -516,7 +520,17 @@ class FluidSimulator:
         steps does not capture a graph, so an interval below 16 keeps a fresh simulator eager, step by step.  Recommended: K = 32, which
         measured best at 2^20 and 2^24 particles (bc5 res 4096: 2.74 -> 0.30 ms and 165 -> 75 us per step; DESIGN.md 4ab has all the
         measured intervals).  Costs 36 more bytes per particle and 4 per sort bin from the first sort on.  0 (default): never - exactly
-        the behaviour without this argument.  Sorting changes nothing tracers(), draw_tracers(), tracer_fields() or a checkpoint shows."""
+        the behaviour without this argument.  Sorting changes nothing tracers(), draw_tracers(), tracer_fields() or a checkpoint shows.
+
+        tau (None: the passive set above, through the same code as ever): a scalar or an (N,) array of response times >= 0 in the solver's
+        time units makes the particles INERTIAL - dust, droplets, sediment.  Each carries a velocity v_p that relaxes to the fluid's:
+        dv_p/dt = (V - v_p) / tau + gravity, integrated exactly over a step with V frozen at the particle's position (v_p += alpha (V +
+        tau gravity - v_p), alpha = fs.tracers.response(tau, dt)), then x += dt / dx * v_p.  A particle is released with the fluid's
+        velocity.  One gather per step: as tau -> 0 this is the forward-Euler tracer, not the midpoint rule of the passive set, and a
+        particle may cross more than one cell per step, as a passive one may.  gravity = (gx, gy) in velocity per time; fs.tracers.
+        stokes_number(tau, speed, length) tells how inertial a tau is.  deposits=True: every wall hit is counted in the wall cell the
+        particle would have entered, respawn or not (tracer_deposits()).  84 bytes per particle (68 more from the first sort on), 4 per
+        cell with deposits.  gravity or deposits without tau raise ValueError.  tracers() gains "u", "w" and "tau"."""
         from ._lib import FsError
         dev, s = self._dev, self._solver
         if getattr(dev, "capturing", False):
@@ -530,8 +544,23 @@ class FluidSimulator:
             raise ValueError("max_age must be >= 0")
         if sort_every < 0:
             raise ValueError("sort_every must be >= 0")
+        gravity = tuple(float(g) for g in np.asarray(gravity, np.float64).ravel())
+        if len(gravity) != 2 or not all(np.isfinite(g) for g in gravity):
+            raise ValueError("gravity must be two finite numbers (gx, gy)")
+        if tau is None and (gravity != (0.0, 0.0) or deposits):
+            raise ValueError("gravity and deposits belong to inertial particles: pass tau (0 for particles without inertia)")
         seeds = check_seeds(np.asarray(s._bc.mask), seeds)
-        self._tracers = Tracers(dev, dev.tracer_create(seeds, respawn, max_age), seeds, respawn, max_age, sort_every)
+        if tau is None:
+            self._tracers = Tracers(dev, dev.tracer_create(seeds, respawn, max_age), seeds, respawn, max_age, sort_every)
+            return
+        tau = np.asarray(tau, np.float64)
+        if tau.ndim == 0:
+            tau = np.full(len(seeds), tau, np.float64)
+        if tau.shape != (len(seeds),):
+            raise ValueError(f"tau must be a scalar or have shape {(len(seeds),)}, got {tau.shape}")
+        alpha = response(tau, s.dt)          # (ValueError for a tau that is negative or not finite)
+        tset = dev.tracer_create_inertial(seeds, alpha, tau, gravity, respawn, max_age, deposits)
+        self._tracers = Tracers(dev, tset, seeds, respawn, max_age, sort_every, tau=tau.copy(), gravity=gravity, deposits=deposits)
 
     def _trc(self):
         if self._tracers is None:
@@ -541,9 +570,15 @@ class FluidSimulator:
     def tracers(self):
         """The particles now (one download): {"x", "y": float64 (N,) in cell units, "age": int32 steps since the seed or the last respawn
         (fs.tracers.residence_time), "status": int32 fs.tracers.FATE_*, "respawns": int32, "seeds": float64 (N, 2), "steps": steps since
-        seed_tracers()}.  Not allowed during a graph capture."""
+        seed_tracers()}; an inertial set (seed_tracers(tau=...)) adds "u", "w": float64 (N,), the particle velocity in the field's units
+        (what the last step left; a particle at age 0 takes the fluid's on its next step), and "tau": float64 (N,).  Not allowed during a
+        graph capture."""
         tr = self._trc()
-        return tr.dev.tracer_read(tr.set)
+        out = tr.dev.tracer_read(tr.set)
+        if tr.tau is not None:
+            out["u"], out["w"] = tr.dev.tracer_read_vel(tr.set)
+            out["tau"] = tr.tau.copy()
+        return out
 
     def sort_tracers(self):
         """Sort the particle slots by cell on the device now (DeviceBase.tracer_sort): what seed_tracers(sort_every=K) does every K steps.
@@ -571,12 +606,77 @@ class FluidSimulator:
         tr.dev.tracer_draw(tr.set, rgb, color)
         return rgb
 
+    def tracer_deposits(self):
+        """Wall hits per wall cell since seed_tracers(tau=..., deposits=True): int32 (X, Y), exact and repeatable (integer atomics).  A
+        particle that hits a wall is counted in the wall cell it would have entered, whether it respawns or not."""
+        if getattr(self._dev, "capturing", False):
+            raise RuntimeError("tracer_deposits during a graph capture")
+        tr = self._trc()
+        if not tr.deposits:
+            raise RuntimeError("the tracer set records no deposits: seed_tracers(tau=..., deposits=True)")
+        return tr.dev.tracer_deposits(tr.set)
+
+    def accumulate_tracers(self, every=1, start_step=0):
+        """From the next step on, add the per-cell particle count and age sum (what tracer_fields() snapshots) to 64-bit sums on the device
+        after every step k (counted from here, k = 1, 2, ...) with k > start_step and (k - start_step) % every == 0.  The launch goes
+        behind the advance and is part of the step: it is captured into the replayed graphs, decides on the device whether it samples, and
+        run() is not cut into chunks by it.  16 bytes per cell; exact: the sum of the tracer_fields() snapshots at the sampled steps.
+        Passive and inertial sets alike.  tracer_accumulation() returns the result.  Raises without a tracer set, while an accumulation is
+        attached already and during a graph capture."""
+        dev = self._dev
+        if getattr(dev, "capturing", False):
+            raise RuntimeError("accumulate_tracers during a graph capture")
+        tr = self._trc()
+        if tr.accumulation is not None:
+            raise RuntimeError("an accumulation is attached already: stop_tracer_accumulation() first (or reset_tracer_accumulation())")
+        every, start_step = int(every), int(start_step)
+        if every < 1:
+            raise ValueError("every must be >= 1")
+        if start_step < 0:
+            raise ValueError("start_step must be >= 0")
+        tr.accumulation = TracerAccumulation(dev.tracer_accum_create(tr.set, every, start_step), every, start_step)
+
+    def _tacc(self):
+        tr = self._trc()
+        if tr.accumulation is None:
+            raise RuntimeError("no accumulation: call accumulate_tracers() first")
+        return tr
+
+    def tracer_accumulation(self):
+        """The accumulated occupancy so far (a download of 16 bytes per cell): {"occupancy": int64 (X, Y), alive particles seen in the cell
+        summed over the sampled steps; "age_sum": int64 (X, Y), the sum of their ages (fs.tracers.residence_map(occupancy, age_sum, dt):
+        the mean residence time, fs.tracers.concentration(occupancy, samples): the mean particles per cell); "samples": sampled steps;
+        "steps": steps since accumulate_tracers()}.  Not allowed during a graph capture."""
+        if getattr(self._dev, "capturing", False):
+            raise RuntimeError("tracer_accumulation during a graph capture")
+        tr = self._tacc()
+        occ, age, launches, samples = tr.dev.tracer_accum_read(tr.set)
+        return {"occupancy": occ, "age_sum": age, "samples": samples, "steps": launches}
+
+    def reset_tracer_accumulation(self):
+        """Sums and sample count back to zero; the step count and the phase of `every` / `start_step` run on."""
+        tr = self._tacc()
+        tr.dev.tracer_accum_reset(tr.set)
+
+    def stop_tracer_accumulation(self):
+        """Detach the accumulation and free its device memory; the cached graphs that hold its launch are freed first.  Nothing is kept
+        on the host: call tracer_accumulation() before.  Inside a graph capture the device memory is released when the capture ends."""
+        tr = self._tracers
+        if tr is None or tr.accumulation is None:
+            return
+        if not getattr(self._dev, "capturing", False):      # (inside a capture no graph can be freed: theirs stay cached, never matched again)
+            self._drop_cached(tr.accumulation.token)
+        self._dev.tracer_accum_free(tr.set)
+        tr.accumulation = None
+
     def stop_tracers(self):
-        """Detach the tracer set and free its device memory; the cached graphs that hold its launch are freed first.  Nothing is kept on
-        the host: call tracers() before.  Inside a graph capture the device memory is released when the capture ends."""
+        """Detach the tracer set (and its accumulation) and free its device memory; the cached graphs that hold its launch are freed
+        first.  Nothing is kept on the host: call tracers() before.  Inside a graph capture the device memory is released when the capture
+        ends."""
         tr = self._tracers
         if tr is None:
             return
+        self.stop_tracer_accumulation()
         if not getattr(self._dev, "capturing", False):      # (inside a capture no graph can be freed: theirs stay cached, never matched again)
             self._drop_cached(tr.token)
         self._dev.tracer_free(tr.set)

@@ -1115,11 +1115,132 @@ class DeviceBase:
         r, g, b = (float(c) for c in color)
         self._p_kernel("tracer_draw", tr._h, r, g, b, rgb._h)
 
+    # ---- inertial tracer sets, deposits, accumulated occupancy (include/fs_hip.h fs_tracer_create_inertial ... fs_tracer_accum_*) ---------
+    def tracer_create_inertial(self, seeds, alpha, tau, gravity=(0.0, 0.0), respawn=True, max_age=0, deposits=False):
+        """A device set of inertial particles for FluidSimulator.seed_tracers(tau=...): as tracer_create, plus alpha (N,) in (0, 1] (the
+        response of one step, fs.tracers.response(tau, dt)), tau (N,) finite and >= 0 in the solver's time units, gravity (gx, gy) in
+        velocity per time; deposits: the set owns an int32 plane that counts the wall hits per wall cell.  84 bytes per particle (+ 68 and
+        4 per sort bin once tracer_sort has run) and 4 per cell with deposits."""
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("tracer_create_inertial during a graph capture")
+        if self.nranks > 1:
+            raise _lib.FsError("tracer particles need a single-GPU context: on slabs they would have to migrate between ranks (not implemented)")
+        seeds = np.ascontiguousarray(seeds, np.float64)
+        if seeds.ndim != 2 or seeds.shape[1] != 2 or len(seeds) < 1:
+            raise ValueError(f"seeds must have shape (N, 2) with N >= 1, got {seeds.shape}")
+        n = len(seeds)
+        alpha, tau = np.ascontiguousarray(alpha, np.float64), np.ascontiguousarray(tau, np.float64)
+        if alpha.shape != (n,) or tau.shape != (n,):
+            raise ValueError(f"alpha and tau must have shape {(n,)}, got {alpha.shape} and {tau.shape}")
+        if not ((alpha > 0.0) & (alpha <= 1.0)).all():
+            raise ValueError("alpha must lie in (0, 1]")
+        if not (np.isfinite(tau) & (tau >= 0.0)).all():
+            raise ValueError("tau must be finite and >= 0")
+        gravity = tuple(float(g) for g in gravity)
+        if len(gravity) != 2 or not all(np.isfinite(g) for g in gravity):
+            raise ValueError("gravity must be two finite numbers (gx, gy)")
+        max_age = int(max_age)
+        if max_age < 0:
+            raise ValueError("max_age must be >= 0")
+        h = self._p_tracer_create_inertial(seeds, alpha, tau, gravity, bool(respawn), max_age, bool(deposits))
+        tr = TracerSet(h, n, bool(respawn), max_age)
+        tr.inertial, tr.deposits, tr.gravity, tr.tau, tr.alpha = True, bool(deposits), gravity, tau.copy(), alpha.copy()
+        self._handle_serial[id(h)] = tr.serial
+        return tr
+
+    def tracer_read_vel(self, tr):
+        """-> (pu, pw) float64 (N,): the particle velocities of an inertial set in SEED order (one download)."""
+        DeviceBase._tracer_host_call(self, "tracer_read_vel")
+        if not getattr(tr, "inertial", False):
+            raise ValueError("not an inertial tracer set")
+        vel = self._p_tracer_read_vel(tr._h, tr.n)
+        return vel[0].copy(), vel[1].copy()
+
+    def tracer_write_vel(self, tr, pu, pw):
+        """Restore what tracer_read_vel returned (checkpoints; after tracer_write)."""
+        DeviceBase._tracer_host_call(self, "tracer_write_vel")
+        if not getattr(tr, "inertial", False):
+            raise ValueError("not an inertial tracer set")
+        vel = np.empty((2, tr.n), np.float64)
+        for row, (key, a) in enumerate((("u", pu), ("w", pw))):
+            a = np.asarray(a, np.float64)
+            if a.shape != (tr.n,):
+                raise ValueError(f"expected {key} of shape {(tr.n,)}, got {a.shape}")
+            vel[row] = a
+        self._p_tracer_write_vel(tr._h, vel)
+
+    def tracer_deposits(self, tr):
+        """-> int32 (X, Y): wall hits per wall cell since creation (a set created with deposits=True)."""
+        DeviceBase._tracer_host_call(self, "tracer_deposits")
+        if not getattr(tr, "deposits", False):
+            raise ValueError("the tracer set records no deposits (deposits=True)")
+        return self._p_tracer_deposits(tr._h)
+
+    def tracer_deposits_write(self, tr, plane):
+        """Restore what tracer_deposits returned (checkpoints)."""
+        DeviceBase._tracer_host_call(self, "tracer_deposits_write")
+        if not getattr(tr, "deposits", False):
+            raise ValueError("the tracer set records no deposits (deposits=True)")
+        plane = np.asarray(plane)
+        if plane.shape != (self.nx, self.ny) or (plane < 0).any():
+            raise ValueError(f"expected deposits >= 0 of shape {(self.nx, self.ny)}, got {plane.shape}")
+        self._p_tracer_deposits_write(tr._h, plane.astype(np.int32))
+
+    def tracer_accum_create(self, tr, every=1, start=0):
+        """Attach the accumulated-occupancy planes to a set (passive or inertial): 16 bytes per cell, zeroed.  With n advances since this
+        call before a step's, tracer_accum_add samples behind that step's advance when n + 1 > start and (n + 1 - start) % every == 0.
+        -> TracerAccum (one per set)."""
+        DeviceBase._tracer_host_call(self, "tracer_accum_create")
+        every, start = int(every), int(start)
+        if every < 1 or start < 0:
+            raise ValueError("every must be >= 1 and start >= 0")
+        if getattr(tr, "accum", None) is not None:
+            raise RuntimeError("the tracer set has an accumulator already")
+        self._p_tracer_accum("create", tr._h, every, start)
+        tr.accum = TracerAccum(tr, every, start)
+        return tr.accum
+
+    def tracer_accum_add(self, tr):
+        """The accumulation launch behind tracer_advance (gated on the device; part of captured steps).  Not a _run: writes no field."""
+        args = (tr._h,)
+        if self._oplog is not None:
+            self._oplog.append(("k", "tracer_accum_add", args, ()))
+        self._p_kernel("tracer_accum_add", *args)
+
+    def tracer_accum_read(self, tr):
+        """-> (occupancy int64 (X, Y), age_sum int64 (X, Y), launches, samples)."""
+        DeviceBase._tracer_host_call(self, "tracer_accum_read")
+        return self._p_tracer_accum_read(tr._h)
+
+    def tracer_accum_write(self, tr, occupancy, age_sum, launches, samples):
+        """Restore what tracer_accum_read returned (checkpoints; after tracer_write, which sets the launch count the phase hangs on)."""
+        DeviceBase._tracer_host_call(self, "tracer_accum_write")
+        occupancy, age_sum = np.asarray(occupancy), np.asarray(age_sum)
+        for name, a in (("occupancy", occupancy), ("age_sum", age_sum)):
+            if a.shape != (self.nx, self.ny) or (a < 0).any():
+                raise ValueError(f"expected {name} >= 0 of shape {(self.nx, self.ny)}, got {a.shape}")
+        launches, samples = int(launches), int(samples)
+        if not 0 <= samples <= launches:
+            raise ValueError("counters must satisfy 0 <= samples <= launches")
+        self._p_tracer_accum_write(tr._h, occupancy.astype(np.int64), age_sum.astype(np.int64), launches, samples)
+
+    def tracer_accum_reset(self, tr):
+        """Planes and sample count to zero; the phase of every / start runs on."""
+        DeviceBase._tracer_host_call(self, "tracer_accum_reset")
+        self._p_tracer_accum("reset", tr._h)
+
+    def tracer_accum_free(self, tr):
+        """Detach the accumulator (inside a capture the device memory is released when the capture ends)."""
+        if getattr(tr, "accum", None) is not None and tr._h is not None:
+            self._p_tracer_accum("free", tr._h)
+        tr.accum = None
+
     def tracer_free(self, tr):
         if tr._h is not None:
             self._handle_serial.pop(id(tr._h), None)
-            self._p_tracer_free(tr._h)
+            self._p_tracer_free(tr._h)       # (the library releases an attached accumulator with the set)
             tr._h = None
+            tr.accum = None
 
 
 class TracerSet:
@@ -1127,6 +1248,16 @@ class TracerSet:
 
     def __init__(self, h, n, respawn, max_age):
         self._h, self.n, self.respawn, self.max_age = h, n, respawn, max_age
+        self.inertial, self.deposits, self.gravity, self.tau, self.alpha = False, False, (0.0, 0.0), None, None      # (tracer_create_inertial)
+        self.accum = None          # TracerAccum while tracer_accum_create's planes are attached
+        self.serial = next(_serials)
+
+
+class TracerAccum:
+    """The accumulated-occupancy planes of a tracer set (DeviceBase.tracer_accum_create): every, start and an identity of its own."""
+
+    def __init__(self, tr, every, start):
+        self.set, self.every, self.start = tr, every, start
         self.serial = next(_serials)
 
 
@@ -1382,6 +1513,46 @@ class Device(DeviceBase):
     def _p_tracer_free(self, h):
         if self._ctx is not None:
             _lib.call("fs_tracer_free", self._ctx, h)
+
+    def _p_tracer_create_inertial(self, seeds, alpha, tau, gravity, respawn, max_age, deposits):
+        h = ctypes.c_void_p()
+        dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        _lib.call("fs_tracer_create_inertial", self._ctx, len(seeds), dp(seeds), dp(alpha), dp(tau), gravity[0], gravity[1], int(respawn), max_age,
+                  int(deposits), ctypes.byref(h))
+        return h
+
+    def _p_tracer_read_vel(self, h, n):
+        vel = np.empty((2, n), np.float64)
+        _lib.call("fs_tracer_read_vel", self._ctx, h, vel.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        return vel
+
+    def _p_tracer_write_vel(self, h, vel):
+        _lib.call("fs_tracer_write_vel", self._ctx, h, vel.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+
+    def _p_tracer_deposits(self, h):
+        plane = np.empty((self.ny, self.nx), np.int32)       # (the library's layout: x contiguous)
+        _lib.call("fs_tracer_deposits", self._ctx, h, plane.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+        return np.ascontiguousarray(plane.T)
+
+    def _p_tracer_deposits_write(self, h, plane):
+        a = np.ascontiguousarray(plane.T, np.int32)
+        _lib.call("fs_tracer_deposits_write", self._ctx, h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+
+    def _p_tracer_accum(self, what, h, *args):
+        if self._ctx is not None:
+            _lib.call("fs_tracer_accum_" + what, self._ctx, h, *args)
+
+    def _p_tracer_accum_read(self, h):
+        occ, age = np.empty((self.ny, self.nx), np.int64), np.empty((self.ny, self.nx), np.int64)
+        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
+        lp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))
+        _lib.call("fs_tracer_accum_read", self._ctx, h, lp(occ), lp(age), ctypes.byref(launches), ctypes.byref(samples))
+        return np.ascontiguousarray(occ.T), np.ascontiguousarray(age.T), launches.value, samples.value
+
+    def _p_tracer_accum_write(self, h, occupancy, age_sum, launches, samples):
+        occ, age = np.ascontiguousarray(occupancy.T, np.int64), np.ascontiguousarray(age_sum.T, np.int64)
+        lp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))
+        _lib.call("fs_tracer_accum_write", self._ctx, h, lp(occ), lp(age), launches, samples)
 
     def _p_allreduce_array(self, a):
         a = np.ascontiguousarray(a, np.float64).copy()

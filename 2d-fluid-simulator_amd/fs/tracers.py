@@ -10,6 +10,7 @@ FLUID, WALL, INFLOW, OUTFLOW = 0, 1, 2, 3
 # status of a particle (fs_tracer_read): alive, or the fate that ended it when the set does not respawn
 FATE_ALIVE, FATE_LEFT, FATE_WALL, FATE_EXPIRED = 0, 1, 2, 3
 KEYS = ("x", "y", "age", "status", "respawns", "seeds", "steps")      # what FluidSimulator.tracers() returns
+INERTIAL_KEYS = ("u", "w", "tau")      # ... and on top of them for an inertial set (seed_tracers(tau=...)): particle velocity, response time
 SORT_BIN_CELLS = 32      # cells per bin along x of the device sort (include/fs_hip.h FS_TRACER_SORT_BIN_CELLS): one 128-byte line of an f32 row
 
 
@@ -128,13 +129,63 @@ def residence_map(count, age_sum, dt):
     return out
 
 
+def response(tau, dt):
+    """alpha = 1 - exp(-dt / tau), the fraction of the way to the fluid's velocity (plus tau g) an inertial particle of response time tau
+    covers in one step dt - the exact integral of dv/dt = (U - v) / tau + g with U frozen.  -expm1(-dt / tau) in float64: no
+    cancellation for tau >> dt; 1 for tau == 0 (the particle takes the fluid's velocity at once) and wherever exp(-dt / tau) rounds
+    away; in (0, 1] for every finite tau >= 0 the format can tell from infinity.  Scalar or array -> the same shape."""
+    dt = float(dt)
+    if not (dt > 0.0 and np.isfinite(dt)):
+        raise ValueError("dt must be finite and > 0")
+    t = np.asarray(tau, np.float64)
+    if not (np.isfinite(t) & (t >= 0.0)).all():
+        raise ValueError("tau must be finite and >= 0")
+    out = np.ones(t.shape, np.float64)
+    pos = t > 0.0
+    with np.errstate(over="ignore", under="ignore"):
+        out[pos] = -np.expm1(-np.float64(dt) / t[pos])
+    if not (out > 0.0).all():
+        raise ValueError("tau is too large for this dt: the response of one step rounds to 0")
+    return out if out.ndim else np.float64(out)
+
+
+def stokes_number(tau, speed, length):
+    """St = tau * speed / length: the response time over the flow's time scale (length / speed, e.g. body size / inflow speed, in the
+    solver's units).  St << 1: the particle follows the fluid; St >> 1: it goes straight."""
+    length = np.asarray(length, np.float64)
+    if (length <= 0).any():
+        raise ValueError("length must be > 0")
+    return np.asarray(tau, np.float64) * np.asarray(speed, np.float64) / length
+
+
+def concentration(occupancy, samples):
+    """Mean particles per cell over the sampled steps: occupancy / samples (FluidSimulator.tracer_accumulation), float64."""
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError("no samples")
+    return np.asarray(occupancy).astype(np.float64) / np.float64(samples)
+
+
+class TracerAccumulation:
+    """The accumulated occupancy of a FluidSimulator's tracer set (accumulate_tracers): the device accumulator and its parameters."""
+
+    def __init__(self, accum, every, start_step):
+        self.accum, self.every, self.start_step = accum, int(every), int(start_step)
+
+    @property
+    def token(self):
+        return ("tracer_accum", self.accum.serial)
+
+
 class Tracers:
     """One tracer set of a FluidSimulator (seed_tracers): the device set and its parameters; `issued`: advances issued since seed_tracers
     (what sort_every counts), `sorts`: device sorts so far."""
 
-    def __init__(self, dev, set_, seeds, respawn, max_age, sort_every=0):
+    def __init__(self, dev, set_, seeds, respawn, max_age, sort_every=0, tau=None, gravity=(0.0, 0.0), deposits=False):
         self.dev, self.set, self.seeds, self.respawn, self.max_age = dev, set_, seeds, bool(respawn), int(max_age)
         self.sort_every, self.issued, self.sorts, self.sorted_at = int(sort_every), 0, 0, 0
+        self.tau, self.gravity, self.deposits = tau, tuple(gravity), bool(deposits)      # tau: float64 (N,) - an inertial set - or None
+        self.accumulation = None       # TracerAccumulation while accumulate_tracers() is on
 
     def to_next_sort(self):
         """Steps until the next scheduled sort (>= 1), or None without a schedule."""

@@ -16,6 +16,9 @@ The reference opens a GGUI window and steps forever; here the loop runs `--steps
     to `--tracer-file` (.npz) at the end of the run and every `--tracer-dump-every` steps, drawn into the `-vis` frames; the particle state
     travels with `--save-state` / `--load-state`.  `--tracer-sort-every K` sorts the particles by cell on the GPU every K steps (large sets
     stay fast; no result changes); `--tracer-fields` writes the per-cell particle count, age sum and residence time (`--tracer-fields-file`).
+  * give the particles inertia (`--tracer-tau T[,T2,...]`: response times that cycle over the particles as size classes, `--tracer-gravity
+    gx,gy`), count where they hit the walls (`--tracer-deposits`) and accumulate the per-cell occupancy over the run on the GPU
+    (`--tracer-accumulate-every K`, `--tracer-accumulate-start S`); all of it travels with `--save-state` / `--load-state`.
 """
 import argparse
 import os
@@ -98,6 +101,16 @@ def build_parser():
                    help="write the per-cell particle count, age sum and residence time (count, age_sum, residence, step) after the last step, "
                         "and <out>/tracer_fields_<step>.npz next to every --tracer-dump-every dump")
     p.add_argument("--tracer-fields-file", type=str, default=None, help=".npz of --tracer-fields (default: <out>/tracer_fields.npz)")
+    p.add_argument("--tracer-tau", type=str, default=None, metavar="T[,T2,...]",
+                   help="inertial particles: response time(s) >= 0 in simulated time; several values cycle over the particles (size classes); "
+                        "0: no inertia (FluidSimulator.seed_tracers(tau=...)); the particle files gain u, w, tau")
+    p.add_argument("--tracer-gravity", type=str, default=None, metavar="GX,GY", help="gravity on the inertial particles, velocity per time (needs --tracer-tau)")
+    p.add_argument("--tracer-deposits", action="store_true",
+                   help="count the wall hits of the inertial particles per wall cell (needs --tracer-tau); written as `deposits` with --tracer-fields")
+    p.add_argument("--tracer-accumulate-every", type=int, default=0,
+                   help="accumulate the per-cell particle count and age sum on the GPU after every K-th step (FluidSimulator.accumulate_tracers); "
+                        "written as occupancy, accumulated_age_sum, samples with --tracer-fields (default 0: off)")
+    p.add_argument("--tracer-accumulate-start", type=int, default=None, help="steps to skip before --tracer-accumulate-every samples (default 0)")
     return p
 
 
@@ -129,17 +142,68 @@ def saved_tracers(path):
     return (bool(z["tracer.respawn"]), int(z["tracer.max_age"]), len(z["tracer.x"])) if "tracer.x" in z.files else None
 
 
-def load_tracers(sim, path, sort_every=0):
+def saved_inertial(path):
+    """What a checkpoint's tracer set holds beyond a passive one's: {"tau": (N,) array or None, "gravity": (gx, gy), "deposits": bool,
+    "accumulate": (every, start) or None}, or None without a tracer set."""
+    z = np.load(_npz_path(path))
+    if "tracer.x" not in z.files:
+        return None
+    inertial = "tracer.tau" in z.files
+    return {"tau": np.asarray(z["tracer.tau"], np.float64) if inertial else None,
+            "gravity": tuple(float(g) for g in z["tracer.gravity"]) if inertial else (0.0, 0.0),
+            "deposits": "tracer.deposits" in z.files,
+            "accumulate": (int(z["tracer.accum.every"]), int(z["tracer.accum.start"])) if "tracer.accum.occupancy" in z.files else None}
+
+
+def tracer_taus(values, n):
+    """--tracer-tau's values cycled over n particles (size classes): particle k has values[k % len(values)]."""
+    return np.resize(np.asarray(values, np.float64), n)
+
+
+def load_tracers(sim, path, sort_every=0, accumulate=None):
     """Seed the checkpoint's tracer set and restore its state -> whether the checkpoint held one.  The state is in seed order: whether the
-    run that wrote it sorted its particles, and whether this one will (sort_every), makes no difference."""
+    run that wrote it sorted its particles, and whether this one will (sort_every), makes no difference.  An inertial set comes back with
+    its response times, gravity, particle velocities and deposit plane; accumulate = (every, start): the accumulation is attached and, when
+    the checkpoint holds one, continued."""
     from fs.tracers import KEYS
     z = np.load(_npz_path(path))
     if "tracer.x" not in z.files:
         return False
-    sim.seed_tracers(z["tracer.seeds"], respawn=bool(z["tracer.respawn"]), max_age=int(z["tracer.max_age"]), sort_every=sort_every)
+    inertial = {}
+    if "tracer.tau" in z.files:
+        inertial = {"tau": z["tracer.tau"], "gravity": tuple(float(g) for g in z["tracer.gravity"]), "deposits": "tracer.deposits" in z.files}
+    sim.seed_tracers(z["tracer.seeds"], respawn=bool(z["tracer.respawn"]), max_age=int(z["tracer.max_age"]), sort_every=sort_every, **inertial)
     tr = sim._tracers
     tr.dev.tracer_write(tr.set, {k: z[f"tracer.{k}"] for k in KEYS})
+    if inertial:
+        tr.dev.tracer_write_vel(tr.set, z["tracer.u"], z["tracer.w"])
+        if inertial["deposits"]:
+            tr.dev.tracer_deposits_write(tr.set, z["tracer.deposits"])
+    if accumulate is not None:
+        sim.accumulate_tracers(every=accumulate[0], start_step=accumulate[1])
+        if "tracer.accum.occupancy" in z.files:
+            tr.dev.tracer_accum_write(tr.set, z["tracer.accum.occupancy"], z["tracer.accum.age_sum"], int(z["tracer.accum.steps"]),
+                                      int(z["tracer.accum.samples"]))
     return True
+
+
+def tracer_state_arrays(tr):
+    """The checkpoint's arrays for a tracer set (fs.tracers.Tracers).  A passive set: the keys of tracer_read and respawn, max_age - the
+    format it always had; an inertial set adds u, w, tau, gravity and, when it has them, the deposit plane; an attached accumulation adds
+    its planes, counters and parameters."""
+    arrays = {f"tracer.{k}": np.asarray(a) for k, a in tr.dev.tracer_read(tr.set).items()}
+    arrays.update({"tracer.respawn": np.array(tr.respawn), "tracer.max_age": np.array(tr.max_age)})
+    if tr.tau is not None:
+        u, w = tr.dev.tracer_read_vel(tr.set)
+        arrays.update({"tracer.u": u, "tracer.w": w, "tracer.tau": np.asarray(tr.tau, np.float64), "tracer.gravity": np.array(tr.gravity, np.float64)})
+        if tr.deposits:
+            arrays["tracer.deposits"] = tr.dev.tracer_deposits(tr.set)
+    acc = tr.accumulation
+    if acc is not None:
+        occ, age, launches, samples = tr.dev.tracer_accum_read(tr.set)
+        arrays.update({"tracer.accum.occupancy": occ, "tracer.accum.age_sum": age, "tracer.accum.steps": np.array(launches),
+                       "tracer.accum.samples": np.array(samples), "tracer.accum.every": np.array(acc.every), "tracer.accum.start": np.array(acc.start_step)})
+    return arrays
 
 
 def tracer_seeds(mask, n_random, rng_seed, lines):
@@ -162,8 +226,7 @@ def save_state(sim, path, step):
     arrays = {"step": np.array(step)}
     tr = getattr(sim, "_tracers", None)
     if tr is not None:
-        arrays.update({f"tracer.{k}": np.asarray(a) for k, a in tr.dev.tracer_read(tr.set).items()})
-        arrays.update({"tracer.respawn": np.array(tr.respawn), "tracer.max_age": np.array(tr.max_age)})
+        arrays.update(tracer_state_arrays(tr))
     avg = getattr(sim, "_averager", None)
     if avg is not None:
         sums, launches, samples = avg.dev.mean_read(avg.mean)
@@ -281,6 +344,16 @@ def _tracer_line(parser, spec):
     return x0, y0, x1, y1, n
 
 
+def _tracer_floats(parser, flag, spec, count=None):
+    try:
+        vals = [float(c) for c in spec.split(",")]
+        if not vals or (count is not None and len(vals) != count) or not all(np.isfinite(v) for v in vals):
+            raise ValueError
+    except ValueError:
+        parser.error(f"{flag} {spec}: expected {'%d finite numbers' % count if count else 'finite numbers'} separated by commas")
+    return vals
+
+
 def _probe(parser, spec):
     try:
         x, y = (int(c) for c in spec.split(","))
@@ -335,6 +408,21 @@ def main(argv=None):
         parser.error("--tracer-sort-every, --tracer-fields and --tracer-fields-file need --tracers N or --tracer-line")
     if args.tracer_fields_file and not args.tracer_fields:
         parser.error("--tracer-fields-file needs --tracer-fields")
+    if not tracing and (args.tracer_tau is not None or args.tracer_gravity is not None or args.tracer_deposits or args.tracer_accumulate_every
+                        or args.tracer_accumulate_start is not None):
+        parser.error("--tracer-tau, --tracer-gravity, --tracer-deposits, --tracer-accumulate-every and --tracer-accumulate-start need --tracers N "
+                     "or --tracer-line")
+    if args.tracer_tau is None and (args.tracer_gravity is not None or args.tracer_deposits):
+        parser.error("--tracer-gravity and --tracer-deposits need --tracer-tau (0 for particles without inertia)")
+    if args.tracer_accumulate_every < 0 or (args.tracer_accumulate_start is not None and args.tracer_accumulate_start < 0):
+        parser.error("--tracer-accumulate-every and --tracer-accumulate-start must be >= 0")
+    if args.tracer_accumulate_start is not None and not args.tracer_accumulate_every:
+        parser.error("--tracer-accumulate-start needs --tracer-accumulate-every K")
+    taus = _tracer_floats(parser, "--tracer-tau", args.tracer_tau) if args.tracer_tau is not None else None
+    if taus is not None and min(taus) < 0:
+        parser.error(f"--tracer-tau {args.tracer_tau}: response times must be >= 0")
+    gravity = tuple(_tracer_floats(parser, "--tracer-gravity", args.tracer_gravity, 2)) if args.tracer_gravity is not None else (0.0, 0.0)
+    accumulate = (args.tracer_accumulate_every, args.tracer_accumulate_start or 0) if args.tracer_accumulate_every else None
     lines = [_tracer_line(parser, spec) for spec in args.tracer_line]
     max_age = args.tracer_max_age or 0
     if tracing and args.load_state:
@@ -343,6 +431,22 @@ def main(argv=None):
             print(f"--load-state {args.load_state}: its tracers ran with{'out' if held[0] else ''} --tracer-once and --tracer-max-age {held[1]}; "
                   "continue with those or drop the tracer flags", file=sys.stderr)
             sys.exit(2)
+        more = saved_inertial(args.load_state)
+        if more is not None:
+            want_tau = tracer_taus(taus, held[2]) if taus is not None else None
+            same_tau = (want_tau is None) == (more["tau"] is None) and (want_tau is None or np.array_equal(want_tau, more["tau"]))
+            if not same_tau or more["gravity"] != gravity or more["deposits"] != bool(args.tracer_deposits):
+                was = "passive tracers" if more["tau"] is None else (f"inertial tracers (--tracer-tau of {len(np.unique(more['tau']))} value(s), "
+                                                                     f"--tracer-gravity {more['gravity'][0]:g},{more['gravity'][1]:g}, "
+                                                                     f"with{'' if more['deposits'] else 'out'} --tracer-deposits)")
+                print(f"--load-state {args.load_state}: it holds {was}; continue with those flags or drop the tracer flags", file=sys.stderr)
+                sys.exit(2)
+            if more["accumulate"] is not None and more["accumulate"] != accumulate:
+                now = "no accumulation" if accumulate is None else f"{accumulate[0]} / {accumulate[1]}"
+                print(f"--load-state {args.load_state}: it holds an occupancy accumulated with --tracer-accumulate-every {more['accumulate'][0]} "
+                      f"--tracer-accumulate-start {more['accumulate'][1]}, not {now}; continue with those flags (the sums would be lost otherwise) "
+                      "or drop the tracer flags", file=sys.stderr)
+                sys.exit(2)
     box = _body_box(parser, args.body, args.boundary_condition, res)
     probes = [_probe(parser, spec) for spec in args.probe]
     print(f"Boundary Condition: {args.boundary_condition}\ndt: {dt}\nRe: {args.reynolds_num}\nResolution: {res}\n"
@@ -390,7 +494,7 @@ def main(argv=None):
     tracer_file = None
     if tracing:
         tracer_file = Path(args.tracer_file) if args.tracer_file else out / "tracers.npz"
-        if args.load_state and load_tracers(sim, args.load_state, args.tracer_sort_every):
+        if args.load_state and load_tracers(sim, args.load_state, args.tracer_sort_every, accumulate):
             print(f"tracers: continuing the checkpoint's {sim._tracers.set.n} particles (the seed flags are not used)")
         else:
             seeds, notes = tracer_seeds(np.asarray(sim._solver._bc.mask), args.tracers, args.tracer_seed or 0, lines)
@@ -400,7 +504,13 @@ def main(argv=None):
                 print("tracers: no seed lies in a fluid cell", file=sys.stderr)
                 dev.close()
                 sys.exit(2)
-            sim.seed_tracers(seeds, respawn=not args.tracer_once, max_age=max_age, sort_every=args.tracer_sort_every)
+            if taus is None:
+                sim.seed_tracers(seeds, respawn=not args.tracer_once, max_age=max_age, sort_every=args.tracer_sort_every)
+            else:
+                sim.seed_tracers(seeds, respawn=not args.tracer_once, max_age=max_age, sort_every=args.tracer_sort_every,
+                                 tau=tracer_taus(taus, len(seeds)), gravity=gravity, deposits=args.tracer_deposits)
+            if accumulate is not None:
+                sim.accumulate_tracers(every=accumulate[0], start_step=accumulate[1])
     fields_file = None
     if tracing and args.tracer_fields:
         fields_file = Path(args.tracer_fields_file) if args.tracer_fields_file else out / "tracer_fields.npz"
@@ -412,8 +522,14 @@ def main(argv=None):
             from fs.tracers import residence_map
             f = sim.tracer_fields()
             fields_path.parent.mkdir(parents=True, exist_ok=True)
+            more = {}
+            if sim._tracers.deposits:
+                more["deposits"] = sim.tracer_deposits()
+            if sim._tracers.accumulation is not None:
+                acc = sim.tracer_accumulation()
+                more.update(occupancy=acc["occupancy"], accumulated_age_sum=acc["age_sum"], samples=np.array(acc["samples"]))
             np.savez(str(fields_path), count=f["count"], age_sum=f["age_sum"], residence=residence_map(f["count"], f["age_sum"], dt),
-                     step=np.array(step))
+                     step=np.array(step), **more)
 
     stats = None
     if args.stats_every > 0:

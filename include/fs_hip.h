@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 14
+#define FS_ABI_VERSION 15
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -376,6 +376,53 @@ int fs_tracer_sort(fs_ctx *ctx, fs_tracer *t);
 int fs_tracer_order(fs_ctx *ctx, fs_tracer *t, int *ids);
 int fs_tracer_fields(fs_ctx *ctx, fs_tracer *t, int *count, long long *age_sum);
 int fs_tracer_free(fs_ctx *ctx, fs_tracer *t);
+
+/* Inertial tracer sets, wall deposition and accumulated occupancy (new; csrc/fs_tracer.h).  An inertial set is a tracer set whose particles
+ * also carry a velocity pu, pw (double, the field's velocity units), a response alpha in (0, 1] and a response time tau >= 0; the set
+ * carries gravity (gx, gy) in velocity per time.  Every fs_tracer_* call above works on it; fs_tracer_advance dispatches on the set's kind.
+ * create_inertial: as create, plus alpha [n] and tau [n] (seed order; FS_ERR_ARG unless 0 < alpha <= 1, tau finite and >= 0, gravity
+ *           finite).  The caller computes alpha = -expm1(-dt / tau), 1 for tau == 0: the device evaluates no transcendental function.
+ *           deposits != 0: the set owns an int plane [Y][X], zeroed.  Slab contexts: FS_ERR_UNSUPPORTED.
+ * advance (inertial set): every particle with status 0, each line ONE IEEE double operation in the order written, no FMA:
+ *             (U, W) = V(x, y) exactly as above (same bilinear form, clamps and handling of a deferred limit_field)
+ *             age == 0: pu = U; pw = W            (released with the fluid's velocity: creation and every respawn)
+ *             su = tau gx; sw = tau gy; pu = pu + alpha ((U + su) - pu); pw = pw + alpha ((W + sw) - pw)
+ *             xn = x + h pu; yn = y + h pw; not inside [0, X) x [0, Y) (NaN included) -> LEFT before any index is formed
+ *             mask of cell (floor xn, floor yn): 1 -> WALL, 3 -> LEFT, else the particle moves there; age and max_age as above.
+ *           Fates as above; a respawn also stores pu = pw = 0 (never read), without respawn the updated pu, pw are stored in every case.
+ *           With deposits a particle whose fate is WALL adds 1 to cell (floor xn, floor yn) of the plane (one integer atomic), respawn or
+ *           not.  One gather stage: as tau -> 0 this is the forward-Euler tracer, not the midpoint rule of a passive set; a particle may
+ *           cross more than one cell per step.  Profiled as tracer_advance_inertial.
+ * read_vel / write_vel: synchronise; vel is [2][n] doubles pu, pw in SEED order.
+ * write (inertial set): pu, pw follow their particles back into seed order; alpha and tau are those of create_inertial.
+ * sort (inertial set): carries pu, pw, alpha, tau with the slots (32 more bytes of scratch per particle).
+ * deposits / deposits_write: synchronise; [Y][X] ints (x contiguous); FS_ERR_ARG for a set without the plane, or counts < 0.
+ * accum_create: attaches to the set (passive or inertial) two resident 64-bit planes [Y][X], occupancy and age_sum, zeroed, and a sample
+ *           counter; every >= 1, start >= 0.  One accumulator per set: FS_ERR_STATE while one is attached.
+ * accum_add: one launch, to be issued behind fs_tracer_advance; can be captured.  Gated on the device from the set's launch counter by the
+ *           rule of fs_mean_accumulate: with n launches of the advance before this step's since accum_create, the launch samples when
+ *           n + 1 > start and (n + 1 - start) % every == 0.  A sampling launch adds, for every alive particle inside the domain, 1 to
+ *           occupancy and its age to age_sum of cell (floor x, floor y) (integer atomics: exact, the sum of the fs_tracer_fields snapshots
+ *           at the sampled steps) and counts the sample.  Profiled as tracer_accumulate.
+ * accum_read: synchronises; occupancy, age_sum (each may be NULL) [Y][X] 64-bit; launches: advances since accum_create; samples.
+ * accum_write: the inverse (checkpoints; after fs_tracer_write): 0 <= samples <= launches <= the set's launch count.
+ * accum_reset: planes and samples to zero; the phase of every / start runs on.
+ * accum_free: a graph that holds the launch must not be replayed afterwards; during a capture the release is deferred to its end.
+ *           fs_tracer_free releases the accumulator with the set.
+ * create_inertial, read_vel, write_vel, deposits, deposits_write, accum_create, accum_read, accum_write and accum_reset return FS_ERR_STATE
+ * during graph capture / tape recording.                                                                                              */
+int fs_tracer_create_inertial(fs_ctx *ctx, int n, const double *seeds_xy, const double *alpha, const double *tau, double gx, double gy, int respawn,
+                              int max_age, int deposits, fs_tracer **out);
+int fs_tracer_read_vel(fs_ctx *ctx, fs_tracer *t, double *vel);
+int fs_tracer_write_vel(fs_ctx *ctx, fs_tracer *t, const double *vel);
+int fs_tracer_deposits(fs_ctx *ctx, fs_tracer *t, int *out);
+int fs_tracer_deposits_write(fs_ctx *ctx, fs_tracer *t, const int *in);
+int fs_tracer_accum_create(fs_ctx *ctx, fs_tracer *t, long long every, long long start);
+int fs_tracer_accum_add(fs_ctx *ctx, fs_tracer *t);
+int fs_tracer_accum_read(fs_ctx *ctx, fs_tracer *t, long long *occupancy, long long *age_sum, long long *launches, long long *samples);
+int fs_tracer_accum_write(fs_ctx *ctx, fs_tracer *t, const long long *occupancy, const long long *age_sum, long long launches, long long samples);
+int fs_tracer_accum_reset(fs_ctx *ctx, fs_tracer *t);
+int fs_tracer_accum_free(fs_ctx *ctx, fs_tracer *t);
 
 /* ---- pointwise -------------------------------------------------------------------------------- */
 /* limit_field   fs/solver.py:38-43 ;  clamp_field   fs/solver.py:46-49                           */
