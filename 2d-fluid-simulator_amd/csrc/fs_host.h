@@ -89,6 +89,8 @@ struct fs_ctx {
     int rbpair_split = 1;                    // plain and boundary workgroups of that pass (and of the four-sweep Jacobi pass) as two compact
                                              // launches: env FS_RBPAIR_SPLIT = 0 never, 1 on grids of 8 M cells or more, 2 always
     size_t small_cells = (size_t)1 << 21;    // 2-row tiles on grids below this many cells (env FS_SMALL_CELLS; 0: never): res 800 +4.7 %, res 1024 (2 M cells) +0.3 %
+    size_t diag_wgs = 2048;                  // fs_flow_stats and the averages take more rows per workgroup while the grid keeps this many workgroups
+                                             // (8 per CU; env FS_DIAG_WGS, values below 1 are 1: the most rows on every grid; fs_launch.h diag_rows)
     uint32_t *d_pairlist = nullptr; int n_pairlist[2] = {0, 0};   // wave-tile rows of the two-sweep kernel's general path, without / with its
                                                                    // vertical-recipe tile path (fs_march.h k_pair_list): [2][nwx * rows] + 2 counters
     int nwx = 0;                   // wave columns of 62 quads across a row

@@ -63,6 +63,15 @@ inline int launch(fs_ctx *c, const char *name, F &&f)
 // tiles of half the height halve that chain (round 4, tools/r4_chain.py; env FS_SMALL_CELLS=0: the big grids' tile heights everywhere)
 static inline bool small_tiles(const fs_ctx *c) { return (size_t)c->X * c->Y < c->small_cells; }
 
+// Rows per workgroup of the diagnostics' kernels (k_flow_stats, k_mean_accumulate, k_mean_finalize: `nx` workgroups across, `ny` owned rows):
+// doubled from `r0` while the grid keeps >= diag_wgs workgroups (2048: 8 per CU; env FS_DIAG_WGS), at most `rmax`
+static inline int diag_rows(const fs_ctx *c, int nx, int ny, int r0, int rmax)
+{
+    int r = r0;
+    while (r < rmax && (size_t)nx * ((ny + 2 * r - 1) / (2 * r)) >= c->diag_wgs) r *= 2;
+    return r;
+}
+
 // a launch over every row of a single-GPU grid (what may clear a buffer's "hot" word [3], fs_device.h)
 static inline int whole_grid(const fs_ctx *c, int jb, int je) { return c->halo == 0 && jb == 0 && je == c->rows ? 1 : 0; }
 

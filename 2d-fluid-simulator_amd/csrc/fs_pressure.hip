@@ -387,6 +387,9 @@ int fs_poisson_residual(fs_ctx *ctx, double dt, double dx, const fs_field *p, co
     return FS_OK;
 }
 
+// rows per workgroup of k_flow_stats: STATS_G on small grids, up to STATS_ROWS (fs_launch.h diag_rows)
+static int stats_rows(const fs_ctx *ctx) { return diag_rows(ctx, (ctx->X + 255) / 256, ctx->nyl, STATS_G, STATS_ROWS); }
+
 int fs_flow_stats(fs_ctx *ctx, double dx, const fs_field *v, const fs_field *p, const int *box, double *out)
 {
     FS_REQUIRE(ctx && out, "null argument");
@@ -400,10 +403,8 @@ int fs_flow_stats(fs_ctx *ctx, double dx, const fs_field *v, const fs_field *p, 
         for (int k = 0; k < 4; ++k) b[k] = box[k];
     }
     const int row_begin = ctx->halo, row_end = ctx->halo + ctx->nyl;
-    // rows per workgroup: doubled from STATS_G while the grid keeps >= 2048 workgroups (8 per CU), at most STATS_ROWS
     const int nx = (ctx->X + 255) / 256, ny = row_end - row_begin;
-    int rpw = STATS_G;
-    while (rpw < STATS_ROWS && (size_t)nx * ((ny + 2 * rpw - 1) / (2 * rpw)) >= 2048) rpw *= 2;
+    const int rpw = stats_rows(ctx);
     const dim3 grid(nx, (ny + rpw - 1) / rpw);
     const size_t nblocks = (size_t)grid.x * grid.y;
     if (nblocks + 1 > ctx->stats_cap) {
@@ -534,15 +535,25 @@ int fs_history_free(fs_ctx *ctx, fs_history *h)
 #define FS_MEAN_NO_CAPTURE(what) \
     if (ctx->capturing || ctx->tape_rec) { set_error("mean " what " during graph capture / tape recording"); return FS_ERR_STATE; }
 
-// workgroups of 256 lanes x `w` columns and `rpw` rows over the owned rows: rows per workgroup doubled from `g0` while the grid keeps >= 2048
-// workgroups (8 per CU), at most MEAN_ROWS - a non-sampling launch is a counter read per workgroup, so the grid stays in the thousands
+// workgroups of 256 lanes x `w` columns and `rpw` rows over the owned rows: rows per workgroup from `g0` up to MEAN_ROWS (fs_launch.h
+// diag_rows) - a non-sampling launch is a counter read per workgroup, so the grid stays in the thousands
+static int mean_width(const fs_ctx *ctx) { return ctx->X % 2 == 0 ? 2 : 1; }      // columns per lane: W of k_mean_accumulate / k_mean_finalize
 static dim3 mean_grid(const fs_ctx *ctx, int w, int g0, int *rpw)
 {
     const int nx = (ctx->X + 256 * w - 1) / (256 * w), ny = ctx->nyl;
-    int r = g0;
-    while (r < MEAN_ROWS && (size_t)nx * ((ny + 2 * r - 1) / (2 * r)) >= 2048) r *= 2;
+    const int r = diag_rows(ctx, nx, ny, g0, MEAN_ROWS);
     *rpw = r;
     return dim3(nx, (ny + r - 1) / r);
+}
+
+// diagnostic: the rows per workgroup the next fs_flow_stats / fs_mean_accumulate / fs_mean_finalize launches of this context take
+int fs_diag_rows(fs_ctx *ctx, int *flow_stats_rows, int *mean_accumulate_rows, int *mean_finalize_rows)
+{
+    FS_REQUIRE(ctx && flow_stats_rows && mean_accumulate_rows && mean_finalize_rows, "null argument");
+    *flow_stats_rows = stats_rows(ctx);
+    mean_grid(ctx, mean_width(ctx), MEAN_G, mean_accumulate_rows);
+    mean_grid(ctx, mean_width(ctx), 1, mean_finalize_rows);
+    return FS_OK;
 }
 
 int fs_mean_create(fs_ctx *ctx, long long every, long long start, fs_mean **out)
@@ -573,7 +584,7 @@ int fs_mean_accumulate(fs_ctx *ctx, fs_mean *m, double limit, const fs_field *v,
     FS_FIELD(v, 2); FS_FIELD(p, 1);
     if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
     // everything the launches need is in `m` and the fields: no allocation, copy or synchronisation here (the closure is captured / taped)
-    const int jb = ctx->halo, je = ctx->halo + ctx->nyl, w = ctx->X % 2 == 0 ? 2 : 1;
+    const int jb = ctx->halo, je = ctx->halo + ctx->nyl, w = mean_width(ctx);
     int rpw;
     const dim3 grid = mean_grid(ctx, w, MEAN_G, &rpw);
     const long long every = m->every, start = m->start;
@@ -611,7 +622,7 @@ int fs_mean_finalize(fs_ctx *ctx, fs_mean *m, fs_field *v_out, fs_field *p_out)
     long long st[MEAN_STATE];
     if (int rc = mean_counters(ctx, m, st)) return rc;
     if (st[1] < 1) { set_error("mean finalize: no sample accumulated yet"); return FS_ERR_STATE; }
-    const int jb = ctx->halo, je = ctx->halo + ctx->nyl, w = ctx->X % 2 == 0 ? 2 : 1;
+    const int jb = ctx->halo, je = ctx->halo + ctx->nyl, w = mean_width(ctx);
     int rpw;
     const dim3 grid = mean_grid(ctx, w, 1, &rpw);
     const long long *state = m->d_state;

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FS_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libfs_hip.so")     # FS_LIB: A/B builds (tools/)
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _lib = None
 
@@ -89,6 +89,7 @@ _PROTOS = {
     "fs_mean_write": [_c_vp, _c_vp, _P(_c_dbl), ctypes.c_longlong, ctypes.c_longlong],
     "fs_mean_reset": [_c_vp, _c_vp],
     "fs_mean_free": [_c_vp, _c_vp],
+    "fs_diag_rows": [_c_vp] + [_P(_c_int)] * 3,
     "fs_tracer_create": [_c_vp, _c_int, _P(_c_dbl), _c_int, _c_int, _P(_c_vp)],
     "fs_tracer_advance": [_c_vp, _c_vp, _c_dbl, _c_dbl, _c_vp],
     "fs_tracer_read": [_c_vp, _c_vp, _P(_c_dbl), _P(_c_int), _P(ctypes.c_longlong)],

@@ -1389,6 +1389,13 @@ class Device(DeviceBase):
         _lib.call("fs_cip_step_tiles", self._ctx, *[ctypes.byref(x) for x in v])
         return tuple(x.value for x in v)
 
+    def diag_rows(self):
+        """{"flow_stats", "mean_accumulate", "mean_finalize"}: the rows per workgroup the next launches of the diagnostics take on this
+        context (fs_diag_rows; they grow with the grid, FS_DIAG_WGS moves the size at which they do)."""
+        v = [ctypes.c_int() for _ in range(3)]
+        _lib.call("fs_diag_rows", self._ctx, *[ctypes.byref(x) for x in v])
+        return dict(zip(("flow_stats", "mean_accumulate", "mean_finalize"), (x.value for x in v)))
+
     @property
     def jacobi_quad_ok(self):
         """The mask admits the four-sweep Jacobi pass (single GPU)."""

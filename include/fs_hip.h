@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 15
+#define FS_ABI_VERSION 16
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -323,6 +323,10 @@ int fs_mean_read(fs_ctx *ctx, fs_mean *m, double *sums_out, long long *launches,
 int fs_mean_write(fs_ctx *ctx, fs_mean *m, const double *sums_in, long long launches, long long samples);
 int fs_mean_reset(fs_ctx *ctx, fs_mean *m);
 int fs_mean_free(fs_ctx *ctx, fs_mean *m);
+/* diagnostic: the rows per workgroup that the next fs_flow_stats, fs_mean_accumulate and fs_mean_finalize launches of this context take
+ * (4 - 32, 4 - 8 and 1 - 8: more on larger grids; env FS_DIAG_WGS, read by fs_create, moves the grid size at which they grow).  Launches
+ * nothing: allowed during graph capture / tape recording. */
+int fs_diag_rows(fs_ctx *ctx, int *flow_stats_rows, int *mean_accumulate_rows, int *mean_finalize_rows);
 
 /* Tracer particles (new): n passive particles advanced on the device by one launch per step that can be captured in a hipGraph
  * (csrc/fs_tracer.h).  Positions are doubles in CELL units: cell (i, j) covers [i, i + 1) x [j, j + 1), its stored value sits at

@@ -70,3 +70,13 @@ def fluid_dead_buffers(solver):
     if getattr(solver, "_fused_dye", False):
         out.add("dye.next")
     return out
+
+
+def diag_floor(nx, ny, r0, want):
+    """A value of FS_DIAG_WGS at which a diagnostic kernel takes `want` rows per workgroup on a grid of nx workgroups across and ny rows: the
+    rule doubles the rows from r0 while nx * ceil(ny / (2 r)) stays at or above the floor (csrc/fs_launch.h diag_rows).  `want` = r0: one
+    above what the first doubling needs; otherwise what the last doubling needs - the next one then fails when ny > want (the callers
+    assert through Device.diag_rows() what was taken)."""
+    if want == r0:
+        return nx * -(-ny // (2 * r0)) + 1
+    return max(1, nx * -(-ny // want))

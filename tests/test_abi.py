@@ -32,6 +32,17 @@ def test_binding_table_matches_header():
     assert _lib.load().fs_abi_version() == _lib.ABI_VERSION
 
 
+def test_diag_rows_is_declared_bound_and_versioned():
+    import ctypes
+    from fs import _lib
+    assert "fs_diag_rows" in _header_symbols()
+    assert "fs_diag_rows" in _lib.EXPORTS
+    assert _lib.load().fs_diag_rows.argtypes == [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_int)] * 3
+    text = open(os.path.join(REPO, "include", "fs_hip.h")).read()
+    assert int(re.search(r"#define FS_ABI_VERSION (\d+)", text).group(1)) == _lib.ABI_VERSION >= 16
+    assert "fs_diag_rows" in open(os.path.join(REPO, "INTEGRATION.md")).read()
+
+
 def test_missing_extension_fails_loudly(monkeypatch, tmp_path):
     from fs import _lib
     monkeypatch.setattr(_lib, "_lib", None)

@@ -1,6 +1,7 @@
 """Flow diagnostics on the GPU (include/fs_hip.h fs_flow_stats, FluidSimulator.flow_stats): the kernel against the NumPy f64 restatement
 (tests/flow_stats_ref.py) on golden and developed states, closed forms uploaded by hand, NaN handling, determinism, no side effect on the
-trajectory (eager, replayed graphs, a pending deferred limit pass), refusal during a capture, and slab contexts on one GPU."""
+trajectory (eager, replayed graphs, a pending deferred limit pass), refusal during a capture, and slab contexts on one GPU; and the kernel
+with 8, 16 and 32 rows per workgroup - the forms of large grids - forced onto small grids by FS_DIAG_WGS."""
 import os
 import threading
 
@@ -8,7 +9,7 @@ import numpy as np
 import pytest
 from conftest import GOLDEN
 from flow_stats_ref import SLOTS, compare, flow_stats_ref
-from helpers import dead_buffers, make_product, traj_config
+from helpers import dead_buffers, diag_floor, make_product, traj_config
 
 pytestmark = pytest.mark.gpu
 
@@ -306,11 +307,14 @@ def _ordered_sum(col):
     return t
 
 
-def _slab_worker(rank, world, halo, g, cfg, steps, box, Dev, results, errors):
+def _slab_worker(rank, world, halo, g, cfg, steps, box, Dev, results, errors, want_rows=None):
     try:
         from fs.boundary_condition import BoundaryCondition
         X, Y = g["bc_mask"].shape
         dev = Dev(X, Y, np.float64 if cfg["fp64"] else np.float32, rank, halo)
+        if want_rows is not None:
+            assert dev.diag_rows()["flow_stats"] == want_rows, (f"rank {rank} ({dev.nyl} rows): {dev.diag_rows()['flow_stats']} rows per "
+                                                                f"workgroup, not {want_rows}: the test does not cover it")
         bc = BoundaryCondition(g["bc_const"], g["bc_mask"], device=dev)
         import fs
         dt, dx, re = cfg["dt"], cfg["dx"], cfg["re"]
@@ -350,6 +354,10 @@ def _scene_case(bc, res):
                                               ("traj_bc1_upwind_vc0.npz", 4, 2), ("traj_f64_bc1_cip_vc0.npz", 2, 4),
                                               ((5, 64), 3, 2), ((5, 64), 3, 3), ((1, 64), 5, 2)])
 def test_slab_contexts_match_single_context(fname, world, halo, hip_lib):
+    _slab_case(fname, world, halo)
+
+
+def _slab_case(fname, world, halo, want_rows=None):
     import fs
     from fs.boundary_condition import default_body_box
     if isinstance(fname, tuple):
@@ -371,7 +379,7 @@ def test_slab_contexts_match_single_context(fname, world, halo, hip_lib):
     Dev = _slab_device_cls(world, shared)
     results, errors, threads = [None] * world, [], []
     for r in range(world):
-        t = threading.Thread(target=_slab_worker, args=(r, world, halo, g, cfg, steps, box, Dev, results, errors))
+        t = threading.Thread(target=_slab_worker, args=(r, world, halo, g, cfg, steps, box, Dev, results, errors, want_rows))
         t._fs_shared = shared
         threads.append(t)
         t.start()
@@ -383,3 +391,194 @@ def test_slab_contexts_match_single_context(fname, world, halo, hip_lib):
         assert not bad, (r, bad)
     assert [results[r] for r in range(world)] == [results[0]] * world      # every rank holds the same global values
     assert set(results[0]) == set(SLOTS)
+
+
+# ---- 8, 16 and 32 rows per workgroup: the forms of large grids, forced onto small ones by FS_DIAG_WGS ------------------------------------
+# A workgroup takes `rpw` rows in load groups of 4 (csrc/fs_stats.h STATS_G) and carries rows j - 1 and j in registers from one group to the
+# next; without the switch every grid below 2048 workgroups takes rpw = 4, one group per workgroup.
+STATS_G, STATS_ROWS = 4, 32
+RPW = (4, 8, 16, 32)
+# the smallest heights at which a workgroup of 8 / 16 / 32 rows has two groups, its last group 1, 3 or 4 rows, the last workgroup one row
+HEIGHTS = (9, 12, 13, 16, 17, 33, 37, 64, 65, 70)
+WIDTHS = (33, 300)          # (300: two column blocks, the second partly outside the grid)
+
+
+def _forced_device(monkeypatch, mask, dtype, rpw):
+    """A device on `mask` whose fs_flow_stats launches take `rpw` rows per workgroup."""
+    X, Y = mask.shape
+    monkeypatch.setenv("FS_DIAG_WGS", str(diag_floor(-(-X // 256), Y, STATS_G, rpw)))
+    dev = _custom(mask, dtype)
+    got = dev.diag_rows()["flow_stats"]
+    if got != rpw:
+        dev.close()
+        raise AssertionError(f"{X} x {Y}: k_flow_stats would take {got} rows per workgroup, not {rpw}: the test does not cover it")
+    return dev
+
+
+def _rpws(Y):
+    return [r for r in RPW if r == STATS_G or Y > r]          # (Y <= rpw: one workgroup, one partial group - nothing to distinguish)
+
+
+def _random_mask(rng, X, Y):
+    """Walls, inflow and outflow cells, and a solid block."""
+    mask = (rng.random((X, Y)) < 0.25).astype(np.uint8)
+    mask[rng.random((X, Y)) < 0.05] = 2
+    mask[rng.random((X, Y)) < 0.05] = 3
+    i, j = rng.integers(0, X - 6), rng.integers(0, Y - 6)
+    mask[i:i + 6, j:j + 6] = 1
+    return mask
+
+
+def _thin_wall_mask(rng, X, Y):
+    """Fluid with a few inflow / outflow cells and one-cell-thin horizontal walls in the first and the last row of every load group - among
+    them the first and the last row of every workgroup of 8, 16 and 32 rows - with fluid above and below (the two kinds of rows use
+    different columns).  Wider grids carry a second set across the edge of the first column block."""
+    mask = np.zeros((X, Y), np.uint8)
+    mask[rng.random((X, Y)) < 0.02] = 2
+    mask[rng.random((X, Y)) < 0.02] = 3
+    spans = [((2, 12), (16, 26))] + ([((250, 258), (262, 270))] if X >= 272 else [])
+    for j in range(Y):
+        for last_row, first_row in spans:
+            for (a, b), rem in ((first_row, 0), (last_row, STATS_G - 1)):
+                if j % STATS_G == rem:
+                    mask[a:b, j] = 1
+                    mask[(a + b) // 2:(a + b) // 2 + 2, j] = 0          # (a gap of two cells: more faces that push along x)
+                    for jn in (j - 1, j + 1):
+                        if 0 <= jn < Y:
+                            mask[a:b, jn] = 0
+    return mask
+
+
+def _boxes(X, Y):
+    """Body boxes over the walls whose y0 / y1 lie on multiples of 4, 8 and 32, one row above and one row below them."""
+    ys = sorted({0, Y} | {m + d for m in (4, 8, 32) for d in (-1, 0, 1) if m + d < Y})
+    return [(1, y0, X - 1, y1) for y0 in ys for y1 in ys if y0 < y1]
+
+
+def _integer_fields(rng, X, Y, dtype):
+    dt_ = np.float32 if dtype == "f32" else np.float64
+    return rng.integers(-8, 9, (X, Y, 2)).astype(dt_), rng.integers(-8, 9, (X, Y)).astype(dt_)
+
+
+def _slots(d):
+    return [float(d[k]) for k in SLOTS]
+
+
+@pytest.mark.parametrize("Y", HEIGHTS)
+@pytest.mark.parametrize("X", WIDTHS)
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+def test_rows_per_workgroup_random_fields(dtype, X, Y, hip_lib, monkeypatch):
+    rng = np.random.default_rng(X * 1000 + Y)
+    dt_ = np.float32 if dtype == "f32" else np.float64
+    mask = _random_mask(rng, X, Y)
+    va, pa = (rng.standard_normal((X, Y, 2)) * 3).astype(dt_), rng.standard_normal((X, Y)).astype(dt_)
+    dx = 1.0 / 48
+    boxes = [None, (0, 0, X, Y), (3, 3, X - 2, Y - 2)]
+    exp = [flow_stats_ref(va, pa, mask, dx, box) for box in boxes]
+    assert exp[1]["force_x"] != 0.0 and exp[1]["force_y"] != 0.0 and exp[0]["fluid_cells"] > 0
+    for rpw in _rpws(Y):
+        dev = _forced_device(monkeypatch, mask, dtype, rpw)
+        try:
+            v, p = dev.alloc(2), dev.alloc(1)
+            v.from_numpy(va)
+            p.from_numpy(pa)
+            for box, e in zip(boxes, exp):
+                got = dev.flow_stats(dx, v, p, box)
+                print(f"rpw {rpw} box {box}: {_slots(got)}")
+                assert not compare(got, e), (rpw, box, compare(got, e))
+        finally:
+            dev.close()
+
+
+@pytest.mark.parametrize("Y", HEIGHTS)
+@pytest.mark.parametrize("X", WIDTHS)
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+def test_rows_per_workgroup_integer_fields_exact(dtype, X, Y, hip_lib, monkeypatch):
+    """u, w, p integers in [-8, 8] and dx = 1/64: every term and every sum is exact in double, whatever the order - the ten slots equal the
+    reference's and each other's across the rows per workgroup."""
+    rng = np.random.default_rng(X * 1000 + Y + 7)
+    mask = _thin_wall_mask(rng, X, Y)
+    va, pa = _integer_fields(rng, X, Y, dtype)
+    dx = 1.0 / 64
+    boxes = _boxes(X, Y)
+    exp = [flow_stats_ref(va, pa, mask, dx, box) for box in boxes]
+    whole = boxes.index((1, 0, X - 1, Y))
+    assert exp[whole]["force_x"] != 0.0 and exp[whole]["force_y"] != 0.0, "the forces vanish: the case does not cover them"
+    results = {}
+    for rpw in _rpws(Y):
+        dev = _forced_device(monkeypatch, mask, dtype, rpw)
+        try:
+            v, p = dev.alloc(2), dev.alloc(1)
+            v.from_numpy(va)
+            p.from_numpy(pa)
+            results[rpw] = [_slots(dev.flow_stats(dx, v, p, box)) for box in boxes]
+        finally:
+            dev.close()
+        for box, got, e in zip(boxes, results[rpw], exp):
+            assert got == _slots(e), (rpw, box, got, _slots(e))
+    assert all(r == results[STATS_G] for r in results.values())
+
+
+def test_natural_size_takes_eight_rows(hip_lib, monkeypatch):
+    """16384 x 264 with the switch unset: 64 * ceil(264 / 8) = 2112 >= 2048 > 64 * ceil(264 / 16) - 8 rows per workgroup by the rule itself;
+    1024 x 512 stays at 4 / 4 / 1: the default floor."""
+    from fs.runtime import Device
+    monkeypatch.delenv("FS_DIAG_WGS", raising=False)
+    small = Device(1024, 512, "f32")
+    try:
+        assert small.diag_rows() == {"flow_stats": 4, "mean_accumulate": 4, "mean_finalize": 1}
+    finally:
+        small.close()
+    X, Y = 16384, 264
+    rng = np.random.default_rng(16384)
+    mask = _thin_wall_mask(rng, X, Y)
+    va, pa = _integer_fields(rng, X, Y, "f32")
+    dx, box = 1.0 / 64, (1, 7, X - 1, Y - 9)
+    dev = _custom(mask, "f32")
+    try:
+        assert dev.diag_rows()["flow_stats"] == 8, f"{dev.diag_rows()}: not 8 rows per workgroup: the test does not cover it"
+        v, p = dev.alloc(2), dev.alloc(1)
+        v.from_numpy(va)
+        p.from_numpy(pa)
+        got = dev.flow_stats(dx, v, p, box)
+    finally:
+        dev.close()
+    exp = flow_stats_ref(va, pa, mask, dx, box)
+    assert exp["force_x"] != 0.0 and exp["force_y"] != 0.0
+    assert _slots(got) == _slots(exp), (_slots(got), _slots(exp))
+
+
+def test_the_switch_reaches_the_launch(hip_lib, monkeypatch):
+    """Random f32 fields summed by workgroups of 32 rows and of 4: the terms are the same, the trees are not - at least one of the three
+    sums differs in its last bits.  If none does, the forced rows did not reach the kernel."""
+    X, Y, dx = 300, 70, 1.0 / 48
+    rng = np.random.default_rng(300070)
+    mask = _random_mask(rng, X, Y)
+    va, pa = (rng.standard_normal((X, Y, 2)) * 3).astype(np.float32), rng.standard_normal((X, Y)).astype(np.float32)
+    got = {}
+    for rpw in (4, 32):
+        dev = _forced_device(monkeypatch, mask, "f32", rpw)
+        try:
+            v, p = dev.alloc(2), dev.alloc(1)
+            v.from_numpy(va)
+            p.from_numpy(pa)
+            got[rpw] = dev.flow_stats(dx, v, p, (0, 0, X, Y))
+        finally:
+            dev.close()
+    assert not compare(got[32], got[4]), compare(got[32], got[4])
+    sums = ("sum_s2", "sum_om2", "sum_dv2")
+    assert any(got[32][k] != got[4][k] for k in sums), "32 and 4 rows per workgroup gave the same bits in every sum"
+
+
+# slabs of 22 / 21 rows (3 ranks) and 13 / 12 rows (5 ranks): partial last groups behind whole ones, ghost rows of depth 2 and 3 beyond them
+@pytest.mark.parametrize("rpw", [8, 32])
+@pytest.mark.parametrize("fname,world,halo", [((5, 64), 3, 2), ((5, 64), 3, 3), ((1, 64), 5, 2)])
+def test_slab_contexts_rows_per_workgroup(fname, world, halo, rpw, hip_lib, monkeypatch):
+    from fs.boundary_condition import create_scene_arrays
+    from fs.runtime import slab_rows
+    X, Y = create_scene_arrays(*fname)[1].shape
+    heights = [slab_rows(Y, r, world)[1] for r in range(world)]
+    floors = {diag_floor(-(-X // 256), n, STATS_G, rpw) for n in heights}
+    assert len(floors) == 1, f"slabs of {heights} rows need different floors for {rpw} rows per workgroup: {floors}"
+    monkeypatch.setenv("FS_DIAG_WGS", str(floors.pop()))
+    _slab_case(fname, world, halo, want_rows=rpw)

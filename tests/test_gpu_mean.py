@@ -1,7 +1,8 @@
 """Time averages on the GPU (csrc/fs_mean.h k_mean_accumulate / k_mean_tick / k_mean_finalize, include/fs_hip.h fs_mean_*,
 FluidSimulator.start_averaging): the seven sums bit for bit against a NumPy f64 loop over the downloads of an eagerly stepped twin
 (tests/mean_ref.py), unchanged trajectories and launch counts, the finalized mean fields, the deferred limit pass, odd sizes and random
-masks, the capture rules, slab contexts on one GPU with tape replays, resume through mean_read / mean_write."""
+masks, the capture rules, slab contexts on one GPU with tape replays, resume through mean_read / mean_write; and the kernels with 8 rows
+per workgroup (finalize: 2, 4 and 8) - the forms of large grids - forced onto small grids by FS_DIAG_WGS."""
 import ctypes
 import os
 import threading
@@ -9,7 +10,7 @@ import threading
 import numpy as np
 import pytest
 from conftest import GOLDEN
-from helpers import make_product, traj_config
+from helpers import diag_floor, make_product, traj_config
 from mean_ref import accumulate_ref, new_sums, run_reference, sampling_launches
 
 pytestmark = pytest.mark.gpu
@@ -148,6 +149,10 @@ def test_finalize_and_mean_flow_stats(fname, hip_lib):
 
 
 def test_deferred_limit_reaches_the_sums(hip_lib):
+    _deferred_limit_case()
+
+
+def _deferred_limit_case(want_rows=None):
     import fs
     from fs.solver import VELOCITY_LIMIT
     g, cfg = _load("traj_bc1_upwind_vc0.npz")          # (MacSolver: its end-of-step limit_field is always deferred)
@@ -155,6 +160,8 @@ def test_deferred_limit_reaches_the_sums(hip_lib):
     sim = make_product(g, cfg)
     dev = sim._dev
     try:
+        if want_rows is not None:
+            assert dev.diag_rows()["mean_accumulate"] == want_rows, f"{dev.diag_rows()}: the test does not cover {want_rows} rows per workgroup"
         mask = g["bc_mask"]
         v = np.zeros(mask.shape + (2,), np.float32)
         v[mask == 0] = (3.0 * VELOCITY_LIMIT, -2.0 * VELOCITY_LIMIT)
@@ -189,11 +196,19 @@ def _random_scene(rng, X, Y):
 def test_odd_sizes_and_random_masks(X, Y, dtype, hip_lib):
     """Uploads of random fields on random masks, three samples against NumPy: the widths of tests/test_gpu_odd_res.py (2 res for res 51, 75,
     81, 125: not multiples of 4, odd heights), odd widths (the one-column path) and a width of more than two workgroups."""
+    _odd_sizes_case(X, Y, dtype)
+
+
+def _odd_sizes_case(X, Y, dtype, want_rows=None):
     from fs.runtime import Device
     rng = np.random.default_rng(X * 1000 + Y)
     dt_ = np.float32 if dtype == "f32" else np.float64
     dev = Device(X, Y, dtype)
     try:
+        if want_rows is not None:
+            rows = dev.diag_rows()
+            assert (rows["mean_accumulate"], rows["mean_finalize"]) == want_rows, (f"{X} x {Y}: {rows}, not {want_rows} rows per workgroup "
+                                                                                   "(accumulate, finalize): the test does not cover it")
         mask = _random_scene(rng, X, Y)
         dev.upload_scene(mask, np.zeros((X, Y, 2), dt_))
         v, p = dev.alloc(2), dev.alloc(1)
@@ -212,6 +227,7 @@ def test_odd_sizes_and_random_masks(X, Y, dtype, hip_lib):
         assert np.all(sums[:, mask == 1] == 0.0)
         vo, po = dev.alloc(2), dev.alloc(1)
         dev.mean_finalize(m, vo, po)
+        assert np.array_equal(vo.to_numpy()[..., 0], np.where(mask == 1, dt_(0), (sums[0] / 3.0).astype(dt_)))
         assert np.array_equal(vo.to_numpy()[..., 1], np.where(mask == 1, dt_(0), (sums[1] / 3.0).astype(dt_)))
         assert np.array_equal(po.to_numpy(), np.where(mask == 1, dt_(0), (sums[2] / 3.0).astype(dt_)))
         # write / read round trip, reset
@@ -324,7 +340,7 @@ def test_resume_equals_uninterrupted_run(hip_lib):
 
 
 # ---- slab contexts on one GPU (the thread harness of test_gpu_slab_threads.py), tape replays -------------------------------------
-def _slab_means(const, mask, cfg, world, halo, every, start, steps):
+def _slab_means(const, mask, cfg, world, halo, every, start, steps, want_rows=None):
     import fs
     from test_gpu_slab_threads import _make_device_cls
     shared = {"barrier": threading.Barrier(world), "box": [None] * world, "radii": [None] * world}
@@ -336,6 +352,9 @@ def _slab_means(const, mask, cfg, world, halo, every, start, steps):
             dt, dx, re = cfg["dt"], cfg["dx"], cfg["re"]
             X, Y = mask.shape
             dev = Dev(X, Y, np.float32, rank, halo)
+            if want_rows is not None:
+                rows = dev.diag_rows()
+                assert (rows["mean_accumulate"], rows["mean_finalize"]) == want_rows, f"rank {rank}: {rows}: the test does not cover {want_rows}"
             bc = fs.BoundaryCondition(const, mask, device=dev)
             vc = fs.VorticityConfinement(bc, dt, dx, cfg["vor_eps"])
             pu = fs.RedBlackSorPressureUpdater(bc, dt, dx, 1.3, 2)
@@ -362,6 +381,10 @@ def _slab_means(const, mask, cfg, world, halo, every, start, steps):
 @pytest.mark.parametrize("world,halo", [(2, 4), (3, 4)])
 def test_slab_contexts_match_single_context(world, halo, hip_lib):
     """bc5 at res 45: 90 x 45 cells, slabs of 23 + 22 / 15 + 15 + 15 rows - partial row groups of the kernel in every slab layout."""
+    _slab_case(world, halo)
+
+
+def _slab_case(world, halo, want_rows=None):
     import fs
     from fs.averages import derive_averages
     from fs.boundary_condition import BoundaryCondition, create_scene_arrays
@@ -380,7 +403,7 @@ def test_slab_contexts_match_single_context(world, halo, hip_lib):
     finally:
         _close(one)
     assert (launches, samples) == (70, 21) and np.abs(exp[5]).max() > 0.0
-    res_ = _slab_means(const, mask, cfg, world, halo, every, start, steps)
+    res_ = _slab_means(const, mask, cfg, world, halo, every, start, steps, want_rows)
     assert all(r[3] > 0 for r in res_), "no tape was replayed"
     assert any(r[4] % 2 for r in res_), "every slab holds whole row groups: the partial group is not covered"
     assert all(r[1:3] == (launches, samples) for r in res_)
@@ -388,3 +411,77 @@ def test_slab_contexts_match_single_context(world, halo, hip_lib):
     _assert_sums_equal(got, exp, "assembled slab ")
     u = np.concatenate([r[5] for r in res_], axis=1)
     assert np.array_equal(u, derive_averages(exp, samples, mask)["u"])
+
+
+# ---- 8 rows per workgroup: the forms of large grids, forced onto small ones by FS_DIAG_WGS ------------------------------------------------
+# k_mean_accumulate takes 4 or 8 rows per workgroup in load groups of 4 (csrc/fs_mean.h MEAN_G), k_mean_finalize 1, 2, 4 or 8; without the
+# switch every grid below 2048 workgroups takes 4 and 1.  Both kernels double by the same rule, so that the accumulation takes 8 rows exactly
+# where the finalize pass does: the floors for 2 and 4 rows of the finalize pass leave the accumulation at 4.
+MEAN_G, MEAN_ROWS = 4, 8
+
+
+def _mean_floor(X, Y, finalize_rows):
+    return diag_floor(-(-X // (512 if X % 2 == 0 else 256)), Y, 1, finalize_rows)
+
+
+@pytest.mark.parametrize("finalize_rows", [2, 4, 8])
+@pytest.mark.parametrize("X,Y,dtype", [(102, 9, "f32"), (102, 13, "f32"), (101, 13, "f32"), (101, 37, "f32"), (1026, 37, "f32"),
+                                       (102, 13, "f64"), (101, 37, "f64")])
+def test_odd_sizes_rows_per_workgroup(X, Y, dtype, finalize_rows, hip_lib, monkeypatch):
+    """Heights of 9, 13 and 37 rows: a workgroup of 8 rows holds two load groups, the last workgroup a partial one (1 and 5 rows)."""
+    monkeypatch.setenv("FS_DIAG_WGS", str(_mean_floor(X, Y, finalize_rows)))
+    _odd_sizes_case(X, Y, dtype, want_rows=(MEAN_ROWS if finalize_rows == MEAN_ROWS else MEAN_G, finalize_rows))
+
+
+def test_deferred_limit_reaches_the_sums_eight_rows(hip_lib, monkeypatch):
+    monkeypatch.setenv("FS_DIAG_WGS", "1")
+    _deferred_limit_case(want_rows=MEAN_ROWS)
+
+
+def test_slab_contexts_eight_rows(hip_lib, monkeypatch):
+    """Three slabs of 15 rows: a whole workgroup of 8 rows and one of 7, whose second group holds 3."""
+    monkeypatch.setenv("FS_DIAG_WGS", "1")
+    _slab_case(3, 4, want_rows=(MEAN_ROWS, MEAN_ROWS))
+
+
+def test_simulator_with_the_most_rows_per_workgroup(hip_lib, monkeypatch):
+    """FS_DIAG_WGS=1 through FluidSimulator (32 / 8 / 8 rows per workgroup) against a twin with the switch unset (4 / 4 / 1): the averages
+    and the fields bit for bit, flow_stats within the reduction order."""
+    import fs
+    from flow_stats_ref import compare, flow_stats_ref
+    from fs.boundary_condition import default_body_box
+    g, cfg = _load("traj_bc5_cip_vc5.npz")
+    fs.runtime.init(gpu=0, dtype="f32")
+    monkeypatch.delenv("FS_DIAG_WGS", raising=False)
+    b = make_product(g, cfg)
+    monkeypatch.setenv("FS_DIAG_WGS", "1")
+    a = make_product(g, cfg)
+    try:
+        assert a._dev.diag_rows() == {"flow_stats": 32, "mean_accumulate": 8, "mean_finalize": 8}, "the switch did not reach the context"
+        assert b._dev.diag_rows() == {"flow_stats": 4, "mean_accumulate": 4, "mean_finalize": 1}
+        for sim in (a, b):
+            sim.start_averaging(every=3)
+            sim.run(43, graph=True)
+        assert a._graphs, "the run replayed no graph"
+        oa, ob = a.averages(), b.averages()
+        assert set(oa) == set(ob) and oa["samples"] == 14
+        for k in oa:
+            assert np.array_equal(oa[k], ob[k], equal_nan=True), f"averages: {k}"
+        sa, sb = _read(a), _read(b)
+        assert sa[1:] == sb[1:] == (43, 14)
+        _assert_sums_equal(sa[0], sb[0], "most rows per workgroup: ")
+        assert np.abs(sa[0][5]).max() > 0.0
+        box = default_body_box(cfg["bc"], cfg["res"])
+        va, pa = a._solver.get_fields()[:2]
+        vb, pb = b._solver.get_fields()[:2]
+        ra, rb = a._dev.flow_stats(cfg["dx"], va, pa, box), b._dev.flow_stats(cfg["dx"], vb, pb, box)
+        fa, fb = a.field_to_numpy(), b.field_to_numpy()
+        ref = flow_stats_ref(fb["v"], fb["p"], g["bc_mask"], cfg["dx"], box)
+        assert not compare(rb, ref), compare(rb, ref)
+        assert not compare(ra, dict(rb, _force_scale=ref["_force_scale"])), compare(ra, rb)
+        assert rb["force_x"] != 0.0 and rb["sum_om2"] > 0.0
+        for k in fa:
+            assert np.array_equal(fa[k], fb[k], equal_nan=True), f"{k}: the fields differ"
+    finally:
+        _close(a)
+        _close(b)
