@@ -696,6 +696,9 @@ int fs_destroy(fs_ctx *ctx)
     for (fs_mean *m : ctx->means) mean_release(m);
     for (fs_mean *m : ctx->deferred_mean) mean_release(m);
     ctx->means.clear();
+    for (fs_loads *l : ctx->loads) loads_release(l);
+    for (fs_loads *l : ctx->deferred_loads) loads_release(l);
+    ctx->loads.clear();
     for (fs_tracer *t : ctx->tracers) tracer_release(t);
     for (fs_tracer *t : ctx->deferred_tracer) tracer_release(t);
     ctx->tracers.clear();
@@ -1984,6 +1987,8 @@ int fs_graph_end(fs_ctx *ctx, int *graph_id)
     ctx->deferred_hist.clear();
     for (fs_mean *m : ctx->deferred_mean) mean_release(m);            // and time averages (fs_mean_free)
     ctx->deferred_mean.clear();
+    for (fs_loads *l : ctx->deferred_loads) loads_release(l);         // and body trackers (fs_loads_free)
+    ctx->deferred_loads.clear();
     for (fs_tracer *t : ctx->deferred_tracer) tracer_release(t);      // and tracer sets (fs_tracer_free)
     ctx->deferred_tracer.clear();
     for (void *b : ctx->deferred_accum) hipFree(b);                   // and accumulators (fs_tracer_accum_free)

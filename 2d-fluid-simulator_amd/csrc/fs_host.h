@@ -133,6 +133,8 @@ struct fs_ctx {
     std::vector<fs_history *> deferred_hist; // fs_history_free during a hipGraph capture: released when the capture ends
     std::set<fs_mean *> means;               // live time averages (fs_mean_create), released with the context
     std::vector<fs_mean *> deferred_mean;    // fs_mean_free during a hipGraph capture: released when the capture ends
+    std::set<fs_loads *> loads;              // live body trackers (fs_loads_create), released with the context
+    std::vector<fs_loads *> deferred_loads;  // fs_loads_free during a hipGraph capture: released when the capture ends
     std::set<fs_tracer *> tracers;           // live tracer sets (fs_tracer_create), released with the context
     std::vector<fs_tracer *> deferred_tracer;  // fs_tracer_free during a hipGraph capture: released when the capture ends
     std::vector<void *> deferred_accum;        // fs_tracer_accum_free during a hipGraph capture: device blocks released when the capture ends
@@ -197,6 +199,20 @@ struct fs_mean {
     long long *d_state = nullptr;   // [MEAN_STATE]
 };
 
+namespace fs { struct LoadFace; }      // fs_loads.h (included by fs_pressure.hip alone)
+// body surface loads (fs_loads_*, fs_loads.h): the face list of this context's owned rows, the per-face sums, the ring and the device counters
+struct fs_loads {
+    fs_ctx *ctx = nullptr;
+    int nf = 0, cap = 0;
+    long long every = 1, start = 0;
+    int nparts = 0;                 // workgroups of the split form (LOADS_SPLIT; 0: one workgroup does the whole launch)
+    double *d_partial = nullptr;    // [nparts][LOADS_REC]
+    fs::LoadFace *d_faces = nullptr;
+    double *d_sums = nullptr;       // [LOADS_SUMS][nf]
+    double *d_ring = nullptr;       // [cap][LOADS_REC]
+    long long *d_state = nullptr;   // [LOADS_STATE]
+};
+
 // tracer particles (fs_tracer_*, fs_tracer.h): the particle arrays and the launch counter
 struct fs_tracer {
     fs_ctx *ctx = nullptr;
@@ -227,6 +243,7 @@ namespace fs {
 
 void history_release(fs_history *h);      // fs_pressure.hip
 void mean_release(fs_mean *m);            // fs_pressure.hip
+void loads_release(fs_loads *l);          // fs_pressure.hip
 
 // HIP-event pair around a span of stream work that is not one kernel launch (fs_api.hip; the ghost-row exchange chain of fs_comm.hip)
 ProfRec prof_span_begin(fs_ctx *c, const char *name, hipStream_t stream);

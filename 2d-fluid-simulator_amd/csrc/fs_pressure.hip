@@ -1,11 +1,13 @@
 // fs_pressure.hip - C-ABI entry points of the pressure kernels: Jacobi sweeps (single, lazily bounded pairs / quads / finishing pass), red-black
 // SOR (half sweeps, one fused iteration, two iterations per pass), the Poisson source pair, the residual, the flow diagnostics and the
-// per-step history ring and the time averages.
+// per-step history ring, the body surface loads and the time averages.
 #include "fs_launch.h"
 #include "fs_stats.h"
 #include "fs_mean.h"
+#include "fs_loads.h"
 
 static_assert(fs::STATS_N == FS_FLOW_NSTAT, "fs_stats.h and include/fs_hip.h disagree on the slots");
+static_assert(fs::LOADS_REC == FS_LOADS_NREC && fs::LOADS_SUMS == FS_LOADS_NSUM, "fs_loads.h and include/fs_hip.h disagree on the record / the sums");
 static_assert(fs::MEAN_PLANES == FS_MEAN_NPLANE, "fs_mean.h and include/fs_hip.h disagree on the planes");
 
 namespace fs {
@@ -17,6 +19,15 @@ void history_release(fs_history *h)
     if (h->d_state) hipFree(h->d_state);
     if (h->d_partial) hipFree(h->d_partial);
     delete h;
+}
+void loads_release(fs_loads *l)
+{
+    if (l->d_faces) hipFree(l->d_faces);
+    if (l->d_sums) hipFree(l->d_sums);
+    if (l->d_ring) hipFree(l->d_ring);
+    if (l->d_state) hipFree(l->d_state);
+    if (l->d_partial) hipFree(l->d_partial);
+    delete l;
 }
 void mean_release(fs_mean *m)
 {
@@ -527,6 +538,156 @@ int fs_history_free(fs_ctx *ctx, fs_history *h)
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
     history_release(h);
+    return FS_OK;
+}
+
+// ---- body surface loads (fs_loads.h) -----------------------------------------------------------------------------------------------------
+#define FS_LOADS_HANDLE(l) FS_REQUIRE((l)->ctx == ctx && ctx->loads.count(l), "loads from another context or freed")
+#define FS_LOADS_NO_CAPTURE(what) \
+    if (ctx->capturing || ctx->tape_rec) { set_error("loads " what " during graph capture / tape recording"); return FS_ERR_STATE; }
+
+int fs_loads_create(fs_ctx *ctx, int nfaces, const int *faces, const double *centre_xy, int capacity, long long every, long long start,
+                    fs_loads **out)
+{
+    FS_REQUIRE(ctx && out && faces && centre_xy, "null argument");
+    FS_REQUIRE(nfaces >= 1, "nfaces must be >= 1");
+    FS_REQUIRE(capacity >= 1 && every >= 1 && start >= 0, "capacity and every must be >= 1 and start >= 0");
+    FS_REQUIRE(std::isfinite(centre_xy[0]) && std::isfinite(centre_xy[1]), "the centre must be finite");
+    FS_LOADS_NO_CAPTURE("create")
+    // a face outside the owned rows would read a ghost row (stale between exchanges) or be counted twice across slabs
+    const int jo = ctx->y0, je = ctx->y0 + ctx->nyl;
+    const double cx = centre_xy[0], cy = centre_xy[1];
+    std::vector<LoadFace> lf(nfaces);
+    for (int k = 0; k < nfaces; ++k) {
+        const int x = faces[3 * k], y = faces[3 * k + 1], d = faces[3 * k + 2];
+        FS_REQUIRE(0 <= x && x < ctx->X && jo <= y && y < je, "face outside this context's owned rows");
+        FS_REQUIRE(0 <= d && d <= 3, "face direction must be 0 (+x), 1 (-x), 2 (+y) or 3 (-y)");
+        const long long j = y - ctx->y0 + ctx->halo;
+        lf[k].u = (unsigned)((j * 2 + 0) * ctx->P + x);      // fs_device.h idx<2>
+        lf[k].w = (unsigned)((j * 2 + 1) * ctx->P + x);
+        lf[k].p = (unsigned)(j * ctx->P + x);
+        lf[k].dir = d;
+        const double xm = d == 0 ? (double)x : d == 1 ? (double)x + 1.0 : (double)x + 0.5;      // the face midpoint, cell units
+        const double ym = d == 2 ? (double)y : d == 3 ? (double)y + 1.0 : (double)y + 0.5;
+        lf[k].rx = xm - cx;
+        lf[k].ry = ym - cy;
+    }
+    FS_HIP(hipSetDevice(ctx->device));
+    fs_loads *l = new fs_loads();
+    l->ctx = ctx; l->nf = nfaces; l->cap = capacity; l->every = every; l->start = start;
+    l->nparts = nfaces > LOADS_SPLIT ? (nfaces + LOADS_WG - 1) / LOADS_WG : 0;
+    const size_t ring = (size_t)capacity * LOADS_REC * sizeof(double), sums = (size_t)LOADS_SUMS * nfaces * sizeof(double);
+    hipError_t e = hipMalloc(&l->d_state, LOADS_STATE * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc(&l->d_ring, ring);
+    if (e == hipSuccess) e = hipMalloc(&l->d_sums, sums);
+    if (e == hipSuccess && l->nparts) e = hipMalloc(&l->d_partial, (size_t)LOADS_REC * l->nparts * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&l->d_faces, lf.size() * sizeof(LoadFace));
+    if (e == hipSuccess) e = hipMemsetAsync(l->d_state, 0, LOADS_STATE * sizeof(long long), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(l->d_ring, 0, ring, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(l->d_sums, 0, sums, ctx->stream);
+    if (e == hipSuccess && l->nparts) e = hipMemsetAsync(l->d_partial, 0, (size_t)LOADS_REC * l->nparts * sizeof(double), ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(l->d_faces, lf.data(), lf.size() * sizeof(LoadFace), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { loads_release(l); return hip_fail(e, "fs_loads_create", __FILE__, __LINE__); }
+    ctx->loads.insert(l);
+    *out = l;
+    return FS_OK;
+}
+
+int fs_loads_record(fs_ctx *ctx, fs_loads *l, double dx, double inv_re, double limit, const fs_field *v, const fs_field *p)
+{
+    FS_REQUIRE(ctx && l, "null argument");
+    FS_LOADS_HANDLE(l);
+    FS_FIELD(v, 2); FS_FIELD(p, 1);
+    // everything the launches need is in `l` and the fields: no allocation, copy or synchronisation here (the closure is captured / taped)
+    const LoadFace *fc = l->d_faces;
+    const int nf = l->nf, cap = l->cap, nparts = l->nparts;
+    const size_t stride = (size_t)l->nf;
+    const long long every = l->every, start = l->start;
+    double *sums = l->d_sums, *ring = l->d_ring, *partial = l->d_partial;
+    long long *state = l->d_state;
+    FS_DISPATCH(ctx, {
+        return launch(ctx, "loads_record", [=] {
+            if (nparts) {
+                FS_KLAUNCH((k_loads_faces<T>), dim3(nparts), dim3(LOADS_WG), 0, ctx->stream, (const T *)v->d, (const T *)p->d, fc, nf, stride, dx,
+                           inv_re, limit, start, every, (const long long *)state, sums, partial);
+                FS_KLAUNCH((k_loads_record), dim3(1), dim3(LOADS_WG), 0, ctx->stream, (const double *)partial, nparts, start, every, cap, ring, state);
+            } else {
+                FS_KLAUNCH((k_loads_one<T>), dim3(1), dim3(LOADS_WG), 0, ctx->stream, (const T *)v->d, (const T *)p->d, fc, nf, stride, dx, inv_re,
+                           limit, start, every, cap, sums, ring, state);
+            }
+        });
+    })
+}
+
+int fs_loads_read(fs_ctx *ctx, fs_loads *l, double *ring_out, int max_records, int *n_records, long long *launches, long long *samples,
+                  int *dropped)
+{
+    FS_REQUIRE(ctx && l && n_records, "null argument");
+    FS_LOADS_HANDLE(l);
+    FS_LOADS_NO_CAPTURE("read")
+    FS_HIP(hipSetDevice(ctx->device));
+    long long st[LOADS_STATE];
+    FS_HIP(hipMemcpyAsync(st, l->d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    *n_records = (int)st[2];
+    if (launches) *launches = st[0];
+    if (samples) *samples = st[1];
+    if (dropped) *dropped = (int)st[3];
+    if (!ring_out) return FS_OK;
+    FS_REQUIRE(max_records >= st[2], "ring_out holds fewer records than the ring");
+    if (st[2] > 0)
+        FS_HIP(hipMemcpyAsync(ring_out, l->d_ring, (size_t)st[2] * LOADS_REC * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipMemsetAsync(l->d_state + 2, 0, 2 * sizeof(long long), ctx->stream));       // written, dropped; launches and samples run on
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_loads_sums_read(fs_ctx *ctx, fs_loads *l, double *sums_out)
+{
+    FS_REQUIRE(ctx && l && sums_out, "null argument");
+    FS_LOADS_HANDLE(l);
+    FS_LOADS_NO_CAPTURE("sums_read")
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemcpyAsync(sums_out, l->d_sums, (size_t)LOADS_SUMS * l->nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_loads_sums_write(fs_ctx *ctx, fs_loads *l, const double *sums_in, long long launches, long long samples)
+{
+    FS_REQUIRE(ctx && l && sums_in, "null argument");
+    FS_LOADS_HANDLE(l);
+    FS_REQUIRE(launches >= 0 && samples >= 0 && samples <= launches, "counters must satisfy 0 <= samples <= launches");
+    FS_LOADS_NO_CAPTURE("sums_write")
+    FS_HIP(hipSetDevice(ctx->device));
+    const long long st[2] = {launches, samples};
+    FS_HIP(hipMemcpyAsync(l->d_sums, sums_in, (size_t)LOADS_SUMS * l->nf * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipMemcpyAsync(l->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
+    return FS_OK;
+}
+
+int fs_loads_reset(fs_ctx *ctx, fs_loads *l)
+{
+    FS_REQUIRE(ctx && l, "null argument");
+    FS_LOADS_HANDLE(l);
+    FS_LOADS_NO_CAPTURE("reset")
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemsetAsync(l->d_sums, 0, (size_t)LOADS_SUMS * l->nf * sizeof(double), ctx->stream));
+    FS_HIP(hipMemsetAsync(l->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
+    return FS_OK;
+}
+
+int fs_loads_free(fs_ctx *ctx, fs_loads *l)
+{
+    if (!l) return FS_OK;
+    FS_REQUIRE(ctx && l->ctx == ctx && ctx->loads.count(l), "loads from another context or freed");
+    ctx->loads.erase(l);
+    if (ctx->capturing) { ctx->deferred_loads.push_back(l); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
+    loads_release(l);
     return FS_OK;
 }
 

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FS_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libfs_hip.so")     # FS_LIB: A/B builds (tools/)
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _lib = None
 
@@ -82,6 +82,13 @@ _PROTOS = {
     "fs_history_record": [_c_vp, _c_vp, _c_dbl, _c_dbl, _c_vp, _c_vp],
     "fs_history_read": [_c_vp, _c_vp, _P(_c_dbl), _c_int, _P(_c_int), _P(ctypes.c_longlong), _P(_c_int)],
     "fs_history_free": [_c_vp, _c_vp],
+    "fs_loads_create": [_c_vp, _c_int, _P(_c_int), _P(_c_dbl), _c_int, ctypes.c_longlong, ctypes.c_longlong, _P(_c_vp)],
+    "fs_loads_record": [_c_vp, _c_vp, _c_dbl, _c_dbl, _c_dbl, _c_vp, _c_vp],
+    "fs_loads_read": [_c_vp, _c_vp, _P(_c_dbl), _c_int, _P(_c_int), _P(ctypes.c_longlong), _P(ctypes.c_longlong), _P(_c_int)],
+    "fs_loads_sums_read": [_c_vp, _c_vp, _P(_c_dbl)],
+    "fs_loads_sums_write": [_c_vp, _c_vp, _P(_c_dbl), ctypes.c_longlong, ctypes.c_longlong],
+    "fs_loads_reset": [_c_vp, _c_vp],
+    "fs_loads_free": [_c_vp, _c_vp],
     "fs_mean_create": [_c_vp, ctypes.c_longlong, ctypes.c_longlong, _P(_c_vp)],
     "fs_mean_accumulate": [_c_vp, _c_vp, _c_dbl, _c_vp, _c_vp],
     "fs_mean_finalize": [_c_vp, _c_vp, _c_vp, _c_vp],

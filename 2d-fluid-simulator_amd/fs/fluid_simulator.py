@@ -13,6 +13,7 @@ from .advection import advect_kk_scheme, advect_upwind
 from .averages import Averager, derive_averages
 from .boundary_condition import get_boundary_condition
 from .history import Recorder, body_faces, check_probes
+from .loads import Tracker, body_centroid, face_geometry
 from .pressure_updater import JacobiPressureUpdater, RedBlackSorPressureUpdater
 from .solver import CipMacSolver, DyeCipMacSolver, DyeMacSolver, MacSolver
 from .tracers import TracerAccumulation, Tracers, check_seeds, response
@@ -85,11 +86,14 @@ class FluidSimulator:
         self._last_recorder = None  # ... and after stop_history(): what history() still returns
         self._averager = None      # fs.averages.Averager while start_averaging() is on
         self._tracers = None       # fs.tracers.Tracers while seed_tracers() is on
+        self._tracker = None       # fs.loads.Tracker while track_body() is on
+        self._last_tracker = None  # ... and after stop_body(): what body_loads() / body_surface() still return
 
     def _update(self):
-        """One solver step, then the history record if a recorder is attached, the accumulation of the time averages if an averager is and
-        the advance of the tracer particles if a set is: what step(), the periods capture_period() captures and the slab periods
-        tape_period() logs all run (so a graph or tape holds these launches exactly when _signature() says so)."""
+        """One solver step, then the history record if a recorder is attached, the accumulation of the time averages if an averager is,
+        the body tracker's launches if one is and the advance of the tracer particles if a set is: what step(), the periods
+        capture_period() captures and the slab periods tape_period() logs all run (so a graph or tape holds these launches exactly when
+        _signature() says so)."""
         self._solver.update()
         rec = self._recorder
         if rec is not None:
@@ -102,6 +106,13 @@ class FluidSimulator:
         if avg is not None:
             v, p = self._solver.get_fields()[:2]
             self._dev.mean_accumulate(avg.mean, v, p)
+        bt = self._tracker
+        if bt is not None:
+            if bt.room() <= 0 and not getattr(self._dev, "capturing", False):
+                bt.drain()           # (eager steps beyond the ring: run() drains between its chunks instead)
+            v, p = self._solver.get_fields()[:2]
+            self._dev.loads_record(bt.loads, self._solver.dx, 1.0 / self._solver.re, v, p)
+            bt.issued += 1
         tr = self._tracers
         if tr is not None:
             self._dev.tracer_advance(tr.set, self._solver.dt / self._solver.dx, self._solver.get_fields()[0])
@@ -169,6 +180,8 @@ class FluidSimulator:
             sig.append(self._recorder.token)        # (graphs / tapes with the record launch in them are never replayed without it, or vice versa)
         if self._averager is not None:
             sig.append(self._averager.token)        # (likewise the accumulation launch of the time averages)
+        if self._tracker is not None:
+            sig.append(self._tracker.token)         # (and the launches of the body tracker)
         if self._tracers is not None:
             sig.append(self._tracers.token)         # (and the advance of the tracer particles)
             if self._tracers.accumulation is not None:
@@ -187,20 +200,24 @@ class FluidSimulator:
         period ends in another phase; graphs are therefore cached per phase (at most `period` of them exist) instead of being
         re-captured - and leaked - chunk after chunk, and a capture is only started when the chunk is long enough to pay for it.
 
-        With a history recorder attached (record_history) the run is cut into chunks that fit the recorder's ring, which is drained between
-        them: no record is ever dropped.  With a sort schedule for the tracer particles (seed_tracers(sort_every=K)) it is also cut at
-        every K-th step since seed_tracers, where the particles are sorted between two chunks; the two cuts compose."""
-        rec, tr = self._recorder, self._tracers
+        With a history recorder (record_history) or a body tracker (track_body) attached the run is cut into chunks that fit their
+        rings - the smaller room of the two - and whichever is full is drained between them: no record is ever dropped.  With a sort
+        schedule for the tracer particles (seed_tracers(sort_every=K)) it is also cut at every K-th step since seed_tracers, where the
+        particles are sorted between two chunks; the two cuts compose."""
+        tr = self._tracers
+        rings = [r for r in (self._recorder, self._tracker) if r is not None]      # (each with a device ring: room() / drain())
         cut = tr is not None and tr.sort_every > 0
-        if rec is None and not cut:
+        if not rings and not cut:
             return self._run_chunk(nsteps, graph)
         while nsteps > 0:
             m = nsteps
-            if rec is not None:
-                m = min(m, rec.room())
-                if m <= 0:
-                    rec.drain()
-                    continue
+            full = [r for r in rings if r.room() <= 0]
+            if full:
+                for r in full:
+                    r.drain()
+                continue
+            for r in rings:
+                m = min(m, r.room())
             if cut:
                 m = min(m, tr.to_next_sort())
             self._run_chunk(m, graph, reuse=cut)       # (its eager steps sort when they land on the K-th step themselves)
@@ -212,6 +229,8 @@ class FluidSimulator:
             self._recorder.issued += steps
         if self._tracers is not None:
             self._tracers.issued += steps
+        if self._tracker is not None:
+            self._tracker.issued += steps
 
     def _run_chunk(self, nsteps, graph, reuse=False):
         """reuse (the chunks a sort schedule cuts): a chunk that starts in a phase of the buffer rotation no cached graph belongs to takes
@@ -346,7 +365,8 @@ class FluidSimulator:
           nonfinite: not-wall cells whose u, w or p is NaN or +-Inf (a blown-up run also shows NaN / Inf in the other values)
           fluid_cells; and with body_box = (x0, y0, x1, y1) (global cells, half-open; fs.boundary_condition.default_body_box gives one
           per obstacle scene) force_x / force_y: the PRESSURE force per unit depth on the wall cells inside the box, summed over the faces
-          they share with fluid cells.  The viscous part is omitted (negligible at the Reynolds numbers of the scenes).
+          they share with fluid cells.  The viscous part is not in these two numbers: body_snapshot() / track_body() give the friction
+          force, the moment and the distributions along the surface (at -re 100 about a fifth of a cylinder's drag is friction).
         Changes nothing the trajectory depends on: no field, no swap, no captured graph (a deferred limit_field of v stays deferred unless
         it would change a cell, runtime.DeviceBase.flow_stats).  Not allowed during a graph capture."""
         s = self._solver
@@ -423,6 +443,127 @@ class FluidSimulator:
             dev.free_tape(self._tapes.pop(key))
         if self._graph is not None and tok in self._graph[0]:
             self._graph = self._graph_long = None
+
+    # -- body surface loads (new): pressure + viscous force, moment, per-face pressure and wall shear statistics ---------------------------
+    def _body_faces(self, body_box, center):
+        mask = self._solver._bc.mask
+        body_box = tuple(int(b) for b in body_box)
+        if len(body_box) != 4:
+            raise ValueError("body_box must be (x0, y0, x1, y1)")
+        faces = body_faces(mask, body_box)
+        if len(faces) == 0:
+            raise ValueError(f"body box {body_box} holds no face between a wall cell and a fluid cell")
+        centre = body_centroid(mask, body_box) if center is None else tuple(float(c) for c in np.asarray(center, np.float64).ravel())
+        if len(centre) != 2 or not all(np.isfinite(c) for c in centre):
+            raise ValueError("center must be two finite numbers (cx, cy) in cell units")
+        return body_box, faces, centre
+
+    def track_body(self, body_box, center=None, every=1, start_step=0, capacity=None):
+        """From the next step on, sample the loads on the body in body_box = (x0, y0, x1, y1) after every step k (counted from here,
+        k = 1, 2, ...) with k > start_step and (k - start_step) % every == 0: the pressure force (the faces and terms of flow_stats), the
+        VISCOUS force - per face inv_re * u_t, the wall shear tau = u_t / (re dx) times the face length dx, with u_t the fluid cell's
+        tangential velocity: the no-slip point is the centre of the wall cell, one dx away, the distance the solver's own Laplacian uses -
+        and the moments of both about `center` (cell units; default: fs.loads.body_centroid), positive counter-clockwise.  Each sample
+        also adds p, p^2, tau, tau^2 of every face to per-face sums on the device (32 bytes per face).  The launches go behind the history
+        and average launches of the step, are captured into the replayed graphs (and recorded into slab tapes), and write 6 doubles per
+        sample into a device ring of `capacity` records (default 65536) that run() drains between chunks.  Changes no field and no
+        trajectory.  body_loads() returns the series, body_surface() the distributions.  Raises while a tracker is attached already; not
+        allowed during a graph capture."""
+        dev, s = self._dev, self._solver
+        if getattr(dev, "capturing", False):
+            raise RuntimeError("track_body during a graph capture")
+        if self._tracker is not None:
+            raise RuntimeError("a body tracker is attached already: stop_body() first")
+        every, start_step = int(every), int(start_step)
+        if every < 1:
+            raise ValueError("every must be >= 1")
+        if start_step < 0:
+            raise ValueError("start_step must be >= 0")
+        capacity = 65536 if capacity is None else int(capacity)
+        if capacity < 1:
+            raise ValueError("capacity must be >= 1")
+        body_box, faces, centre = self._body_faces(body_box, center)
+        lo = dev.loads_create(faces, centre, capacity, every, start_step)
+        self._tracker = Tracker(dev, lo, faces, body_box, centre, every, start_step, s.dt)
+        self._last_tracker = None
+
+    def _body(self):
+        bt = self._tracker or self._last_tracker
+        if bt is None:
+            raise RuntimeError("no body tracker: call track_body() first")
+        if bt is self._tracker:
+            if getattr(self._dev, "capturing", False):
+                raise RuntimeError("body_loads / body_surface during a graph capture")
+            bt.drain()
+        return bt
+
+    def body_loads(self):
+        """Every sample since track_body(): {"step": int64[n], "time" (step * dt), "pressure_x", "pressure_y", "viscous_x", "viscous_y",
+        "force_x", "force_y" (pressure + viscous), "moment_pressure", "moment_viscous", "moment": f64[n]} - forces and moments per unit
+        depth at density 1.  Drains the device ring (a download)."""
+        return self._body().data()
+
+    def body_surface(self):
+        """The distributions along the surface: {"faces": int32 (F, 3), "x", "y" (face midpoints, cell units), "nx", "ny" (normal wall ->
+        fluid), "theta" (angle of the midpoint about the centre), "p_mean", "p_rms", "tau_mean", "tau_rms": f64 (F,) over the samples so far
+        (rms: root of the central second moment, clipped at 0; NaN before the first sample), "samples", "sums": the raw (4, F) S_p, S_pp,
+        S_t, S_tt}.  fs.loads.pressure_coefficient / skin_friction turn them into Cp and Cf."""
+        return self._body().surface()
+
+    def reset_body_surface(self):
+        """Per-face sums and sample count back to zero; the step count (the phase of `every` / `start_step`) and the series run on."""
+        if self._tracker is None:
+            raise RuntimeError("no body tracker: call track_body() first")
+        if getattr(self._dev, "capturing", False):
+            raise RuntimeError("reset_body_surface during a graph capture")
+        self._tracker.drain()
+        self._dev.loads_reset(self._tracker.loads)
+        self._tracker.samples = 0
+
+    def stop_body(self):
+        """Drain and detach the body tracker: the cached graphs and tapes that hold its launches are freed, then its device memory.
+        body_loads() and body_surface() still return what it gathered until the next track_body()."""
+        bt = self._tracker
+        if bt is None:
+            return
+        dev = self._dev
+        if getattr(dev, "capturing", False):
+            raise RuntimeError("stop_body during a graph capture")
+        try:
+            bt.drain()
+            bt.close()
+        finally:
+            self._drop_cached(bt.token)
+            dev.loads_free(bt.loads)
+            self._tracker, self._last_tracker = None, bt
+
+    def body_snapshot(self, body_box, center=None):
+        """The loads of the fields as they are now: the keys of body_loads() without step / time as floats, plus "faces", "x", "y", "nx",
+        "ny", "theta" and the per-face "p" and "tau".  One temporary tracker, one eager launch, a read and a free: changes no field, no
+        graph and no attached tracker, and leaves a deferred limit_field deferred (the kernel limits the values it reads).  Not allowed
+        during a graph capture."""
+        dev, s = self._dev, self._solver
+        if getattr(dev, "capturing", False):
+            raise RuntimeError("body_snapshot during a graph capture")
+        body_box, faces, centre = self._body_faces(body_box, center)
+        v, p = s.get_fields()[:2]
+        lo = dev.loads_create(faces, centre, 1, 1, 0)
+        try:
+            one = Tracker(dev, lo, faces, body_box, centre, 1, 0, s.dt)
+            saved, dev._oplog = getattr(dev, "_oplog", None), None      # (never part of a logged period)
+            try:
+                dev.loads_record(lo, s.dx, 1.0 / s.re, v, p)
+            finally:
+                dev._oplog = saved
+            one.drain()
+            data, sums = one.data(), one.sums()
+        finally:
+            dev.loads_free(lo)
+        out = {k: float(a[0]) for k, a in data.items() if k not in ("step", "time")}
+        out["faces"] = faces.copy()
+        out.update(face_geometry(faces, centre))
+        out["p"], out["tau"] = sums[0].copy(), sums[2].copy()
+        return out
 
     # -- time averages (new): means and second moments of u, w, p accumulated on the device -------------------------------------------
     def start_averaging(self, every=1, start_step=0):

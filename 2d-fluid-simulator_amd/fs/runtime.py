@@ -546,7 +546,8 @@ class DeviceBase:
 
     def _issue(self, op):
         if op[0] == "k":
-            self._p_kernel(op[1], *op[2])
+            if op[1] != "loads_idle":     # (a slab that owns no face of a tracked body: the place of loads_record in the other ranks' tapes)
+                self._p_kernel(op[1], *op[2])
         elif op[0] == "begin":
             self._p_exchange_begin(op[1], op[2])
         elif op[0] == "wait":
@@ -925,6 +926,111 @@ class DeviceBase:
             self._p_history_free(hist._h)
             hist._h = None
 
+    # ---- body surface loads (include/fs_hip.h fs_loads_*): force, moment and per-face pressure / shear sums, one launch sequence per step -----
+    LOADS_REC = 6       # Fpx, Fpy, Fvx, Fvy, Mp, Mv
+    LOADS_SUMS = 4      # S_p, S_pp, S_t, S_tt per face
+
+    def loads_create(self, faces, centre, capacity, every=1, start=0):
+        """A device body tracker for FluidSimulator.track_body: faces (F, 3) global (x, y, dir) of fs.history.body_faces, F >= 1, centre
+        (cx, cy) in cell units, a ring of `capacity` records.  Launch n (from 0) of loads_record samples when n + 1 > start and
+        (n + 1 - start) % every == 0.  A slab keeps the faces whose fluid cell lies in its owned rows: the launch reads no ghost row, needs
+        no exchange and sits in a tape as an ordinary kernel op.  Not allowed during a graph capture."""
+        from .history import owned
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("loads_create during a graph capture")
+        faces = np.asarray(faces, np.int32).reshape(-1, 3)
+        centre = np.asarray(centre, np.float64).ravel()
+        capacity, every, start = int(capacity), int(every), int(start)
+        if len(faces) < 1:
+            raise ValueError("a body tracker needs at least one face")
+        if centre.shape != (2,) or not np.all(np.isfinite(centre)):
+            raise ValueError("centre must be two finite numbers (cx, cy)")
+        if every < 1 or start < 0 or capacity < 1:
+            raise ValueError("every and capacity must be >= 1 and start >= 0")
+        mine = owned(faces, self.y0, self.nyl)
+        # (a slab whose rows touch no face of the body still needs a handle: the counters advance on every rank)
+        h = self._p_loads_create(np.ascontiguousarray(faces[mine]), centre, capacity, every, start) if len(mine) else None
+        lo = Loads(h, len(faces), mine, capacity, every, start)
+        if h is not None:
+            self._handle_serial[id(h)] = lo.serial        # (its name in the op keys of a logged period)
+        return lo
+
+    def loads_record(self, lo, dx, inv_re, v, p):
+        """One launch sequence of the tracker on the current v and p; whether it samples is decided on the device.  A limit_field v still
+        owes stays deferred: the kernel limits the values as the pass would store them.  Not a _run: no flush, no exchange, no ghost row - on
+        slabs a kernel op of its own in the logged period (writes no field)."""
+        if lo._h is None:
+            # this slab owns no face of the body: nothing to launch, but the logged period keeps the shape it has on the other ranks
+            # (tape_period compiles a tape only when all ranks' tapes have the same length)
+            if self._oplog is not None:
+                self._oplog.append(("k", "loads_idle", (), ()))
+            return
+        args = (lo._h, float(dx), float(inv_re), float(v.pending_limit) if v.pending_limit is not None else 0.0, v._h, p._h)
+        if self._oplog is not None:
+            self._oplog.append(("k", "loads_record", args, ()))
+        self._p_kernel("loads_record", *args)
+
+    def loads_read(self, lo):
+        """Empty the ring -> (records (n, 6): Fpx, Fpy, Fvx, Fvy, Mp, Mv; launches, samples, records dropped).  Across slabs the records
+        add, and the ranks that hold faces must agree on the counters (a slab without a face of the body holds none).  Collective on slab
+        runs; not allowed during a graph capture."""
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("loads_read during a graph capture: the ring is read between captures / replays")
+        if lo._h is not None:
+            rec, launches, samples, dropped = self._p_loads_read(lo._h, lo.capacity)
+        else:
+            rec, launches, samples, dropped = np.zeros((0, self.LOADS_REC)), 0, 0, 0
+        n = rec.shape[0]
+        if self.nranks > 1:
+            top = [int(x) for x in self._p_max_over_ranks([n, launches, samples])]
+            odd = lo._h is not None and top != [n, launches, samples]
+            n, launches, samples = top
+            full = np.full((n + 1, self.LOADS_REC), -0.0)        # (+ one row: the ranks' dropped counts, and who disagrees)
+            if lo._h is not None and not odd:
+                full[:n] = rec
+            full[n, 0], full[n, 1] = float(dropped), float(odd)
+            tot = self._p_allreduce_array(full.ravel()).reshape(full.shape)
+            if tot[n, 1] > 0:
+                raise RuntimeError("loads_read: the ranks hold different launch / sample / record counts")
+            dropped, rec = int(tot[n, 0]), tot[:n]
+        return rec.copy(), int(launches), int(samples), int(dropped)
+
+    def loads_sums(self, lo, write=None, launches=None, samples=None):
+        """-> the per-face sums, float64 (4, F): S_p, S_pp, S_t, S_tt in the order of the GLOBAL face list.  On slabs every face comes from
+        the rank that owns it (the others contribute -0.0, which leaves every value's bits alone; collective).  write=(4, F) array with
+        launches, samples: the inverse (resume) - each slab keeps its own faces.  Not allowed during a graph capture."""
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("loads_sums during a graph capture")
+        if write is not None:
+            write = np.asarray(write, np.float64)
+            if write.shape != (self.LOADS_SUMS, lo.nfaces):
+                raise ValueError(f"expected sums of shape {(self.LOADS_SUMS, lo.nfaces)}, got {write.shape}")
+            launches, samples = int(launches), int(samples)
+            if not 0 <= samples <= launches:
+                raise ValueError("counters must satisfy 0 <= samples <= launches")
+            if lo._h is not None:
+                self._p_loads_sums_write(lo._h, np.ascontiguousarray(write[:, lo.mine]), launches, samples)
+            return None
+        full = np.full((self.LOADS_SUMS, lo.nfaces), -0.0) if self.nranks > 1 else np.zeros((self.LOADS_SUMS, lo.nfaces))
+        if lo._h is not None:
+            full[:, lo.mine] = self._p_loads_sums_read(lo._h, len(lo.mine))
+        if self.nranks > 1:
+            full = self._p_allreduce_array(full.ravel()).reshape(full.shape)
+        return full
+
+    def loads_reset(self, lo):
+        """Sums and sample count to zero; the launch count runs on.  Not allowed during a graph capture."""
+        if getattr(self, "capturing", False):
+            raise _lib.FsError("loads_reset during a graph capture")
+        if lo._h is not None:
+            self._p_loads_reset(lo._h)
+
+    def loads_free(self, lo):
+        if lo._h is not None:
+            self._handle_serial.pop(id(lo._h), None)
+            self._p_loads_free(lo._h)
+            lo._h = None
+
     def _p_allreduce_array(self, a):
         """Sum of a float64 array over all ranks (collective): _p_allreduce on a list, for backends without an array primitive."""
         return np.asarray(self._p_allreduce([float(x) for x in a]), np.float64)
@@ -1269,6 +1375,15 @@ class Mean:
         self.serial = next(_serials)
 
 
+class Loads:
+    """A device body tracker (DeviceBase.loads_create): handle (None on a slab that owns no face), the global face count, which faces
+    this rank owns, capacity, every, start."""
+
+    def __init__(self, h, nfaces, mine, capacity, every, start):
+        self._h, self.nfaces, self.mine, self.capacity, self.every, self.start = h, nfaces, np.asarray(mine, np.int64), capacity, every, start
+        self.serial = next(_serials)
+
+
 class History:
     """A device history ring (DeviceBase.history_create): handle, the global probe count, which of them this rank owns, capacity, every."""
 
@@ -1457,6 +1572,36 @@ class Device(DeviceBase):
     def _p_history_free(self, h):
         if self._ctx is not None:
             _lib.call("fs_history_free", self._ctx, h)
+
+    def _p_loads_create(self, faces, centre, capacity, every, start):
+        h = ctypes.c_void_p()
+        c = (ctypes.c_double * 2)(float(centre[0]), float(centre[1]))
+        _lib.call("fs_loads_create", self._ctx, len(faces), faces.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if faces.size else None, c,
+                  capacity, every, start, ctypes.byref(h))
+        return h
+
+    def _p_loads_read(self, h, capacity):
+        out = np.empty((capacity, self.LOADS_REC), np.float64)
+        n, launches, samples, dropped = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_int()
+        _lib.call("fs_loads_read", self._ctx, h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), capacity, ctypes.byref(n),
+                  ctypes.byref(launches), ctypes.byref(samples), ctypes.byref(dropped))
+        return out[:n.value], launches.value, samples.value, dropped.value
+
+    def _p_loads_sums_read(self, h, nlocal):
+        out = np.empty((self.LOADS_SUMS, nlocal), np.float64)
+        _lib.call("fs_loads_sums_read", self._ctx, h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        return out
+
+    def _p_loads_sums_write(self, h, sums, launches, samples):
+        a = np.ascontiguousarray(sums, np.float64)
+        _lib.call("fs_loads_sums_write", self._ctx, h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), launches, samples)
+
+    def _p_loads_reset(self, h):
+        _lib.call("fs_loads_reset", self._ctx, h)
+
+    def _p_loads_free(self, h):
+        if self._ctx is not None:
+            _lib.call("fs_loads_free", self._ctx, h)
 
     def _p_mean_create(self, every, start):
         h = ctypes.c_void_p()

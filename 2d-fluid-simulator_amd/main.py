@@ -19,6 +19,10 @@ The reference opens a GGUI window and steps forever; here the loop runs `--steps
   * give the particles inertia (`--tracer-tau T[,T2,...]`: response times that cycle over the particles as size classes, `--tracer-gravity
     gx,gy`), count where they hit the walls (`--tracer-deposits`) and accumulate the per-cell occupancy over the run on the GPU
     (`--tracer-accumulate-every K`, `--tracer-accumulate-start S`); all of it travels with `--save-state` / `--load-state`.
+  * track the complete load on a body (`--body` with `--loads-every N`): pressure and viscous force, their moments about `--loads-center`,
+    and the mean / rms pressure and wall shear of every face of the surface, gathered on the GPU and written to `--loads-file` (.npz) at
+    the end of the run, with Cd, Cl, Cm, Cp and Cf when `--loads-ref U,L` gives the reference speed and length; the per-face sums and
+    counters travel with `--save-state` / `--load-state`.
 """
 import argparse
 import os
@@ -111,6 +115,16 @@ def build_parser():
                    help="accumulate the per-cell particle count and age sum on the GPU after every K-th step (FluidSimulator.accumulate_tracers); "
                         "written as occupancy, accumulated_age_sum, samples with --tracer-fields (default 0: off)")
     p.add_argument("--tracer-accumulate-start", type=int, default=None, help="steps to skip before --tracer-accumulate-every samples (default 0)")
+    p.add_argument("--loads-every", type=int, default=0,
+                   help="track the loads on the --body after every N-th step on the GPU (FluidSimulator.track_body): pressure + viscous "
+                        "force, moments, per-face pressure and wall shear statistics (0: off)")
+    p.add_argument("--loads-start", type=int, default=0, help="steps of the tracked run (restarts included) to leave out before the first sample")
+    p.add_argument("--loads-center", type=str, default=None, metavar="X,Y", help="reference point of the moments, cell units (default: the body's centroid)")
+    p.add_argument("--loads-ref", type=str, default=None, metavar="U,L",
+                   help="reference speed and length (in the units of dx): adds cd, cl, cm, cp_mean, cf_mean to the loads file")
+    p.add_argument("--loads-file", type=str, default=None,
+                   help=".npz of the loads: the series of FluidSimulator.body_loads, the arrays of body_surface, center, box, re, dx "
+                        "(default: <out>/loads.npz)")
     return p
 
 
@@ -133,6 +147,23 @@ def load_mean(sim, path):
         return False
     avg = sim._averager
     avg.dev.mean_write(avg.mean, z["mean.sums"], int(z["mean.launches"]), int(z["mean.samples"]))
+    return True
+
+
+def saved_loads(path):
+    """(box, centre, every, start) of the body tracker a checkpoint holds, or None."""
+    z = np.load(_npz_path(path))
+    if "loads.sums" not in z.files:
+        return None
+    return (tuple(int(b) for b in z["loads.box"]), tuple(float(c) for c in z["loads.center"]), int(z["loads.every"]), int(z["loads.start"]))
+
+
+def load_loads(sim, path):
+    """Restore the per-face sums and counters of the checkpoint's body tracker into the attached one -> whether the checkpoint held any."""
+    z = np.load(_npz_path(path))
+    if "loads.sums" not in z.files:
+        return False
+    sim._tracker.restore(z["loads.sums"], int(z["loads.launches"]), int(z["loads.samples"]))
     return True
 
 
@@ -232,6 +263,12 @@ def save_state(sim, path, step):
         sums, launches, samples = avg.dev.mean_read(avg.mean)
         arrays.update({"mean.sums": sums, "mean.launches": np.array(launches), "mean.samples": np.array(samples),
                        "mean.every": np.array(avg.every), "mean.start": np.array(avg.start_step)})
+    bt = getattr(sim, "_tracker", None)
+    if bt is not None:
+        bt.drain()
+        arrays.update({"loads.sums": bt.sums(), "loads.launches": np.array(bt.issued), "loads.samples": np.array(bt.samples),
+                       "loads.box": np.array(bt.box), "loads.center": np.array(bt.centre, np.float64), "loads.every": np.array(bt.every),
+                       "loads.start": np.array(bt.start_step)})
     for name in _STATE:
         if hasattr(s, name):
             arrays[f"{name}.current"] = getattr(s, name).current.to_numpy()
@@ -382,8 +419,18 @@ def main(argv=None):
             parser.error(f"-bc 6: {e}")
     if (args.stop_on_nonfinite or args.stats_file) and args.stats_every <= 0:
         parser.error("--stats-file and --stop-on-nonfinite need --stats-every N")
-    if args.body is not None and args.stats_every <= 0 and args.history_every <= 0:
-        parser.error("--body needs --stats-every N or --history-every N")
+    if args.body is not None and args.stats_every <= 0 and args.history_every <= 0 and args.loads_every <= 0:
+        parser.error("--body needs --stats-every N, --history-every N or --loads-every N")
+    if args.loads_every < 0 or args.loads_start < 0:
+        parser.error("--loads-every and --loads-start must be >= 0")
+    if (args.loads_start or args.loads_center or args.loads_ref or args.loads_file) and args.loads_every <= 0:
+        parser.error("--loads-start, --loads-center, --loads-ref and --loads-file need --loads-every N")
+    if args.loads_every > 0 and args.body is None:
+        parser.error("--loads-every needs --body")
+    loads_center = tuple(_tracer_floats(parser, "--loads-center", args.loads_center, 2)) if args.loads_center else None
+    loads_ref = tuple(_tracer_floats(parser, "--loads-ref", args.loads_ref, 2)) if args.loads_ref else None
+    if loads_ref is not None and (loads_ref[0] == 0.0 or loads_ref[1] <= 0.0):
+        parser.error(f"--loads-ref {args.loads_ref}: the speed must not be 0 and the length must be > 0")
     if (args.probe or args.history_file) and args.history_every <= 0:
         parser.error("--probe and --history-file need --history-every N")
     if args.history_every > 0 and not args.probe and args.body is None:
@@ -491,6 +538,40 @@ def main(argv=None):
             out.mkdir(exist_ok=True)
             save_png(mean_frame(sim, args.visualization), out / "mean_vis.png")
 
+    loads_file = None
+    if args.loads_every > 0:
+        loads_file = Path(args.loads_file) if args.loads_file else out / "loads.npz"
+        try:
+            sim.track_body(box, center=loads_center, every=args.loads_every, start_step=args.loads_start)
+        except ValueError as e:
+            parser.error(f"--body / --loads-center: {e}")
+        if args.load_state:
+            held = saved_loads(args.load_state)
+            bt = sim._tracker
+            if held is not None and held != (tuple(bt.box), tuple(bt.centre), bt.every, bt.start_step):
+                print(f"--load-state {args.load_state}: its body loads were tracked with --body {','.join(map(str, held[0]))} --loads-center "
+                      f"{held[1][0]!r},{held[1][1]!r} --loads-every {held[2]} --loads-start {held[3]}; continue with those or track without "
+                      "the checkpoint's sums", file=sys.stderr)
+                dev.close()
+                sys.exit(2)
+            if load_loads(sim, args.load_state):
+                print(f"body loads: continuing the checkpoint's ({sim._tracker.samples} samples so far)")
+
+    def write_loads():
+        if loads_file is None:
+            return
+        from fs.loads import coefficients, pressure_coefficient, skin_friction
+        loads, surf = sim.body_loads(), sim.body_surface()
+        more = {}
+        if loads_ref is not None:
+            u_ref, length = loads_ref
+            more = {"cd": coefficients(loads["force_x"], u_ref, length), "cl": coefficients(loads["force_y"], u_ref, length),
+                    "cm": coefficients(loads["moment"], u_ref, length * length), "cp_mean": pressure_coefficient(surf["p_mean"], u_ref),
+                    "cf_mean": skin_friction(surf["tau_mean"], u_ref), "ref": np.array(loads_ref)}
+        loads_file.parent.mkdir(parents=True, exist_ok=True)
+        np.savez(str(loads_file), center=np.array(sim._tracker.centre), box=np.array(sim._tracker.box), re=np.array(args.reynolds_num),
+                 dx=np.array(dx), dt=np.array(dt), every=np.array(args.loads_every), start=np.array(args.loads_start), **loads, **surf, **more)
+
     tracer_file = None
     if tracing:
         tracer_file = Path(args.tracer_file) if args.tracer_file else out / "tracers.npz"
@@ -541,6 +622,7 @@ def main(argv=None):
             print(f"step {step}: non-finite values (NaN / Inf) in v or p; stopping (--stop-on-nonfinite)", file=sys.stderr)
             write_history()
             write_mean()
+            write_loads()
             if tracer_file is not None:
                 write_tracers(tracer_file, fields_file, step)
             dev.close()
@@ -582,6 +664,7 @@ def main(argv=None):
         stats.close()
     write_history()
     write_mean()
+    write_loads()
     if tracer_file is not None:
         write_tracers(tracer_file, fields_file, step0 + args.steps)
     dev.close()

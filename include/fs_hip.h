@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 16
+#define FS_ABI_VERSION 17
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -268,7 +268,7 @@ int fs_poisson_residual(fs_ctx *ctx, double dt, double dx, const fs_field *p, co
  *   slot 4 max_s2        max   max_F s2            slot 9 force_y     sum   (0 without a box)
  * Force: for each wall cell inside the half-open box [x0, x1) x [y0, y1) (`box` = x0, y0, x1, y1 in global cells, or NULL) and each of
  * its 4 neighbours that is fluid (neighbours beyond the domain edge do not exist): fluid at (i+1, j): force_x -= p(i+1,j)*dx;
- * (i-1, j): force_x += p(i-1,j)*dx; (i, j+1): force_y -= p(i,j+1)*dx; (i, j-1): force_y += p(i,j-1)*dx.  Viscous stress is omitted.
+ * (i-1, j): force_x += p(i-1,j)*dx; (i, j+1): force_y -= p(i,j+1)*dx; (i, j-1): force_y += p(i,j-1)*dx.  Viscous stress is omitted here: fs_loads_* below adds it.
  * Maxima start at 0 and propagate NaN.  On a slab, v and p must be valid one ghost row deep.  Deterministic (no atomics: two-stage
  * reduction in a fixed order); refused with FS_ERR_STATE during graph capture / tape recording.  Does not alter any field.          */
 #define FS_FLOW_NSTAT 10
@@ -295,6 +295,44 @@ int fs_history_create(fs_ctx *ctx, int npoints, const int *points, int nfaces, c
 int fs_history_record(fs_ctx *ctx, fs_history *h, double dx, double limit, const fs_field *v, const fs_field *p);
 int fs_history_read(fs_ctx *ctx, fs_history *h, double *out, int max_records, int *n_records, long long *launches, int *dropped);
 int fs_history_free(fs_ctx *ctx, fs_history *h);
+
+/* Body surface loads (new): pressure force, viscous force and their moments on a body per sampling step, and running first and second
+ * moments of the per-face pressure and wall shear, by launches that can be captured in a hipGraph and recorded in a tape (csrc/fs_loads.h).
+ *   faces:     nfaces >= 1 (x, y, dir) as fs_history_create: the FLUID cell and the direction wall -> fluid (0 +x, 1 -x, 2 +y, 3 -y), in this
+ *              context's OWNED rows (FS_ERR_ARG otherwise; on slabs each rank takes its share and the ranks' records add).
+ *   centre_xy: (cx, cy) in cell units, finite: the moments' reference point.  Face midpoint (xm, ym): dir 0 (x, y + 0.5), 1 (x + 1, y + 0.5),
+ *              2 (x + 0.5, y), 3 (x + 0.5, y + 1); lever arms ax = (xm - cx) * dx, ay = (ym - cy) * dx.
+ * Per face on a sampling launch, each line one IEEE double operation per operator, in this order, no FMA:
+ *   pk = (double)p[cell];  (u, w) = v[cell], through limit_field's per-cell function in the field's precision when limit > 0 (a deferred pass);
+ *   ut = (double)w for dir 0, 1 and (double)u for dir 2, 3;  tv = inv_re * ut;  tk = tv / dx  (wall shear: the no-slip point is the wall
+ *   cell's centre, one dx from the fluid value - the distance of the solver's Laplacian);
+ *   S_p += pk; S_pp += pk * pk; S_t += tk; S_tt += tk * tk  (the face's four sums);
+ *   tp = pk * dx; (fpx, fpy) = (-tp, 0), (+tp, 0), (0, -tp), (0, +tp) for dir 0..3 (the terms of fs_flow_stats);
+ *   (fvx, fvy) = (0, tv) for dir 0, 1 and (tv, 0) for dir 2, 3;  mp = ax * fpy - ay * fpx;  mv = ax * fvy - ay * fvx.
+ * A record is FS_LOADS_NREC doubles [Fpx, Fpy, Fvx, Fvy, Mp, Mv], each the sum of its face terms in a fixed order (no atomics).
+ * record:     launch n (counted from 0) samples when n + 1 > start and (n + 1 - start) % every == 0.  A sampling launch adds to the per-face
+ *             sums and appends its record to the ring - or counts it as dropped when the ring holds `capacity` records.  Reads the owned
+ *             rows of v and p only, changes no field; a launch that does not sample reads the counters.  The counters advance on the device.
+ * read:       synchronises, copies the ring (oldest first) to ring_out (max_records >= the count; NULL: counters only, nothing is reset),
+ *             then empties it: *n_records and *dropped describe the ring before; launches and samples run on.
+ * sums_read:  sums_out receives [FS_LOADS_NSUM][nfaces] doubles: S_p, S_pp, S_t, S_tt in the order of `faces`.
+ * sums_write: the inverse, with both counters (resume): 0 <= samples <= launches.
+ * reset:      sums and sample count to zero; the launch count (the phase of `every` / `start`) runs on.
+ * free:       a graph or tape that holds the launch must not be replayed afterwards; during a capture the release is deferred to its end.
+ * create, read, sums_read, sums_write and reset return FS_ERR_STATE during graph capture / tape recording; a non-finite centre, every < 1,
+ * start < 0, capacity < 1 and nfaces < 1 return FS_ERR_ARG.                                                                             */
+#define FS_LOADS_NREC 6
+#define FS_LOADS_NSUM 4
+typedef struct fs_loads fs_loads;
+int fs_loads_create(fs_ctx *ctx, int nfaces, const int *faces, const double *centre_xy, int capacity, long long every, long long start,
+                    fs_loads **out);
+int fs_loads_record(fs_ctx *ctx, fs_loads *l, double dx, double inv_re, double limit, const fs_field *v, const fs_field *p);
+int fs_loads_read(fs_ctx *ctx, fs_loads *l, double *ring_out, int max_records, int *n_records, long long *launches, long long *samples,
+                  int *dropped);
+int fs_loads_sums_read(fs_ctx *ctx, fs_loads *l, double *sums_out);
+int fs_loads_sums_write(fs_ctx *ctx, fs_loads *l, const double *sums_in, long long launches, long long samples);
+int fs_loads_reset(fs_ctx *ctx, fs_loads *l);
+int fs_loads_free(fs_ctx *ctx, fs_loads *l);
 
 /* Time averages (new): first and second moments of u, w and p summed on the device by a launch that can be captured in a hipGraph and
  * recorded in a tape (csrc/fs_mean.h).  State: FS_MEAN_NPLANE planes of double over this context's OWNED rows, in the order S_u, S_w, S_p,
