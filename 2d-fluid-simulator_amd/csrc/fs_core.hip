@@ -1,5 +1,5 @@
 // fs_core.hip - C-ABI entry points (include/fs_hip.h): contexts, fields, scene upload, boundary kernels, pointwise passes, visualisation,
-// tracer particles, hipGraph capture, command tapes, profiling, box-rate probes.  Transport kernels: fs_transport.hip; pressure kernels: fs_pressure.hip.
+// tracer particles, hipGraph capture, command tapes, profiling, box-rate probes.  Transport kernels: fs_transport.hip; pressure kernels: fs_pressure.hip; diagnostics, history, loads, averages: fs_diag.hip.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -688,21 +688,16 @@ int fs_destroy(fs_ctx *ctx)
     free_ops(ctx->ops_vel); free_ops(ctx->ops_prs); free_ops(ctx->ops_dye);
     tile_lists_free(ctx);
     for (fs_field *f : ctx->fields) { if (f->d) hipFree(f->d); if (f->hot) hipFree(f->hot); delete f; }
-    for (fs_field *f : ctx->deferred_free) { if (f->d) hipFree(f->d); if (f->hot) hipFree(f->hot); delete f; }
     ctx->fields.clear();
     for (fs_history *h : ctx->histories) history_release(h);
-    for (fs_history *h : ctx->deferred_hist) history_release(h);
     ctx->histories.clear();
     for (fs_mean *m : ctx->means) mean_release(m);
-    for (fs_mean *m : ctx->deferred_mean) mean_release(m);
     ctx->means.clear();
     for (fs_loads *l : ctx->loads) loads_release(l);
-    for (fs_loads *l : ctx->deferred_loads) loads_release(l);
     ctx->loads.clear();
     for (fs_tracer *t : ctx->tracers) tracer_release(t);
-    for (fs_tracer *t : ctx->deferred_tracer) tracer_release(t);
     ctx->tracers.clear();
-    for (void *b : ctx->deferred_accum) hipFree(b);
+    ctx->release_deferred();      // (what a capture that never ended left behind)
     if (ctx->d_mask) hipFree(ctx->d_mask);
     if (ctx->d_bc_const) hipFree(ctx->d_bc_const);
     if (ctx->d_bc_dye) hipFree(ctx->d_bc_dye);
@@ -908,7 +903,7 @@ int fs_field_free(fs_field *f)
     ctx->fields.erase(f);
     // inside a hipGraph capture neither the synchronisation nor hipFree is legal (either invalidates the capture): a field dropped by
     // the host language's garbage collector at that moment is released when the capture ends
-    if (ctx->capturing) { ctx->deferred_free.push_back(f); return FS_OK; }
+    if (ctx->capturing) { ctx->deferred_release.push_back([f] { field_release(f); }); return FS_OK; }
     hipStreamSynchronize(ctx->stream);
     field_release(f);
     return FS_OK;
@@ -1938,8 +1933,7 @@ int fs_tracer_accum_free(fs_ctx *ctx, fs_tracer *t)
     FS_REQUIRE(ctx && t->ctx == ctx && ctx->tracers.count(t), "tracer set from another context or freed");
     if (!t->d_acc) return FS_OK;
     if (ctx->capturing) {      // (no synchronisation / hipFree inside a capture)
-        ctx->deferred_accum.push_back(t->d_acc);
-        ctx->deferred_accum.push_back(t->d_acc_state);
+        ctx->deferred_release.push_back([acc = t->d_acc, state = t->d_acc_state] { hipFree(acc); hipFree(state); });
     } else {
         hipSetDevice(ctx->device);
         hipStreamSynchronize(ctx->stream);
@@ -1955,7 +1949,7 @@ int fs_tracer_free(fs_ctx *ctx, fs_tracer *t)
     if (!t) return FS_OK;
     FS_REQUIRE(ctx && t->ctx == ctx && ctx->tracers.count(t), "tracer set from another context or freed");
     ctx->tracers.erase(t);
-    if (ctx->capturing) { ctx->deferred_tracer.push_back(t); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
+    if (ctx->capturing) { ctx->deferred_release.push_back([t] { tracer_release(t); }); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
     tracer_release(t);
@@ -1981,18 +1975,7 @@ int fs_graph_end(fs_ctx *ctx, int *graph_id)
     hipGraph_t g = nullptr;
     ctx->capturing = false;
     const hipError_t ec = hipStreamEndCapture(ctx->stream, &g);
-    for (fs_field *f : ctx->deferred_free) field_release(f);          // fields dropped while the capture was open (fs_field_free)
-    ctx->deferred_free.clear();
-    for (fs_history *h : ctx->deferred_hist) history_release(h);      // likewise history rings (fs_history_free)
-    ctx->deferred_hist.clear();
-    for (fs_mean *m : ctx->deferred_mean) mean_release(m);            // and time averages (fs_mean_free)
-    ctx->deferred_mean.clear();
-    for (fs_loads *l : ctx->deferred_loads) loads_release(l);         // and body trackers (fs_loads_free)
-    ctx->deferred_loads.clear();
-    for (fs_tracer *t : ctx->deferred_tracer) tracer_release(t);      // and tracer sets (fs_tracer_free)
-    ctx->deferred_tracer.clear();
-    for (void *b : ctx->deferred_accum) hipFree(b);                   // and accumulators (fs_tracer_accum_free)
-    ctx->deferred_accum.clear();
+    ctx->release_deferred();      // fields, history rings, time averages, body trackers, tracer sets and accumulators freed while the capture was open
     if (ec != hipSuccess) return hip_fail(ec, "hipStreamEndCapture", __FILE__, __LINE__);
     hipGraphExec_t ex = nullptr;
     hipError_t e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);

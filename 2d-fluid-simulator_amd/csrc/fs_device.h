@@ -209,4 +209,12 @@ template <int C, bool P2 = false, typename T>
 __device__ __forceinline__ T fdiff_y(const T *f, const Grid &g, const Konst<T> &k, int c, int i, int j)
 { return qdiv<P2>(smp<C>(f, g, c, i, j + 1) - smp<C>(f, g, c, i, j), k.dx, k.inv_dx); }
 
+// the sampling rule of everything that rides the step with an `every` and a `start` (time averages, body loads; fs_tracer.h k_tracer_accumulate
+// writes it on its own count):
+// with n launches before this one, launch n samples when n + 1 > start and (n + 1 - start) % every == 0 (host side: fs/riders.py)
+__device__ __forceinline__ bool samples_at(long long n, long long start, long long every)
+{
+    return n + 1 > start && (n + 1 - start) % every == 0;
+}
+
 }  // namespace fs

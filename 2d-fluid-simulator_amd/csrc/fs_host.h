@@ -128,16 +128,18 @@ struct fs_ctx {
     // comm
     fs::Comm *comm = nullptr;
     std::set<fs_field *> fields;  // live fields, released with the context
-    std::vector<fs_field *> deferred_free;   // fs_field_free during a hipGraph capture: released when the capture ends
     std::set<fs_history *> histories;        // live history rings (fs_history_create), released with the context
-    std::vector<fs_history *> deferred_hist; // fs_history_free during a hipGraph capture: released when the capture ends
     std::set<fs_mean *> means;               // live time averages (fs_mean_create), released with the context
-    std::vector<fs_mean *> deferred_mean;    // fs_mean_free during a hipGraph capture: released when the capture ends
     std::set<fs_loads *> loads;              // live body trackers (fs_loads_create), released with the context
-    std::vector<fs_loads *> deferred_loads;  // fs_loads_free during a hipGraph capture: released when the capture ends
     std::set<fs_tracer *> tracers;           // live tracer sets (fs_tracer_create), released with the context
-    std::vector<fs_tracer *> deferred_tracer;  // fs_tracer_free during a hipGraph capture: released when the capture ends
-    std::vector<void *> deferred_accum;        // fs_tracer_accum_free during a hipGraph capture: device blocks released when the capture ends
+    // a *_free during a hipGraph capture (neither a synchronisation nor hipFree is legal there: either invalidates the capture) leaves its
+    // release here; fs_graph_end and fs_destroy run the list in the order of the calls
+    std::vector<std::function<void()>> deferred_release;
+    void release_deferred()
+    {
+        for (auto &release : deferred_release) release();
+        deferred_release.clear();
+    }
     // tuning knobs (env FS_MARCH=0: one-cell-per-lane kernels only)
     bool use_march = true;
     bool use_pairs = true;     // lanes of 2 cells: even widths (every `res`); use_march: the quad kernels, X % 4 == 0
@@ -199,7 +201,7 @@ struct fs_mean {
     long long *d_state = nullptr;   // [MEAN_STATE]
 };
 
-namespace fs { struct LoadFace; }      // fs_loads.h (included by fs_pressure.hip alone)
+namespace fs { struct LoadFace; }      // fs_loads.h (included by fs_diag.hip alone)
 // body surface loads (fs_loads_*, fs_loads.h): the face list of this context's owned rows, the per-face sums, the ring and the device counters
 struct fs_loads {
     fs_ctx *ctx = nullptr;
@@ -241,9 +243,9 @@ struct fs_tracer {
 
 namespace fs {
 
-void history_release(fs_history *h);      // fs_pressure.hip
-void mean_release(fs_mean *m);            // fs_pressure.hip
-void loads_release(fs_loads *l);          // fs_pressure.hip
+void history_release(fs_history *h);      // fs_diag.hip
+void mean_release(fs_mean *m);            // fs_diag.hip
+void loads_release(fs_loads *l);          // fs_diag.hip
 
 // HIP-event pair around a span of stream work that is not one kernel launch (fs_api.hip; the ghost-row exchange chain of fs_comm.hip)
 ProfRec prof_span_begin(fs_ctx *c, const char *name, hipStream_t stream);

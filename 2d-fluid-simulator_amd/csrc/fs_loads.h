@@ -34,11 +34,6 @@ constexpr int LOADS_STATE = 4;           // device counters (long long): [0] lau
 struct LoadFace { unsigned u, w, p; int dir; double rx, ry; };      // element offsets of the fluid cell; midpoint - centre in cell units
 static_assert(sizeof(LoadFace) == 32, "LoadFace is the 32-byte face record of the byte model");
 
-__device__ __forceinline__ bool loads_samples(long long n, long long start, long long every)
-{
-    return n + 1 > start && (n + 1 - start) % every == 0;      // the rule of k_mean_accumulate
-}
-
 // one face on a sampling launch: the four sums of face k, and the six terms added to t[]
 template <typename T>
 __device__ __forceinline__ void loads_face(const T *v, const T *p, const LoadFace f, int k, size_t stride, double dx, double inv_re, double limit,
@@ -114,7 +109,7 @@ __global__ __launch_bounds__(LOADS_WG) void k_loads_one(const T *v, const T *p, 
 {
     __shared__ double lds[LOADS_REC * LOADS_WG / 64];
     const long long n = state[0];                      // (every lane reads it before lane 0 writes it, behind the barrier below)
-    const bool sample = loads_samples(n, start, every);
+    const bool sample = samples_at(n, start, every);
     double t[LOADS_REC] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (sample) {                                      // (the same branch in every lane: block_sum6 holds a barrier)
         for (int k = threadIdx.x; k < nf; k += LOADS_WG) loads_face(v, p, faces[k], k, stride, dx, inv_re, limit, sums, t);
@@ -131,7 +126,7 @@ __global__ __launch_bounds__(LOADS_WG) void k_loads_faces(const T *v, const T *p
                                                           double *partial)
 {
     __shared__ double lds[LOADS_REC * LOADS_WG / 64];
-    if (!loads_samples(state[0], start, every)) return;      // (the same in every lane of every workgroup)
+    if (!samples_at(state[0], start, every)) return;      // (the same in every lane of every workgroup)
     double t[LOADS_REC] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     const int k = blockIdx.x * LOADS_WG + threadIdx.x;
     if (k < nf) loads_face(v, p, faces[k], k, stride, dx, inv_re, limit, sums, t);
@@ -148,7 +143,7 @@ __global__ __launch_bounds__(LOADS_WG) void k_loads_record(const double *partial
 {
     __shared__ double lds[LOADS_REC * LOADS_WG / 64];
     const long long n = state[0];
-    const bool sample = loads_samples(n, start, every);
+    const bool sample = samples_at(n, start, every);
     double t[LOADS_REC] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (sample) {
         for (int b = threadIdx.x; b < nparts; b += LOADS_WG) {

@@ -44,18 +44,12 @@ constexpr size_t MEAN_PAD = FS_MEAN_PAD;
 template <typename S, int W>
 struct alignas(sizeof(S) * W) MeanPack { S v[W]; };
 
-__device__ __forceinline__ bool mean_samples(long long launches, long long start, long long every)
-{
-    const long long n1 = launches + 1;
-    return n1 > start && (n1 - start) % every == 0;
-}
-
 // local rows [jb, je) are the owned rows; a workgroup takes `rpw` of them and 256 W columns.  limit > 0: v owes limit_field(limit)
 template <typename T, int W>
 __global__ __launch_bounds__(256) void k_mean_accumulate(Grid g, int jb, int je, int rpw, double limit, long long start, long long every,
                                                          const long long *state, const T *v, const T *p, double *sums, size_t plane)
 {
-    if (!mean_samples(state[0], start, every)) return;      // (the same in every lane of every workgroup: k_mean_tick writes behind this launch)
+    if (!samples_at(state[0], start, every)) return;      // (the same in every lane of every workgroup: k_mean_tick writes behind this launch)
     const int i = (blockIdx.x * 256 + threadIdx.x) * W;
     if (i >= g.X) return;
     using TP = MeanPack<T, W>;
@@ -119,7 +113,7 @@ __global__ __launch_bounds__(64) void k_mean_tick(long long start, long long eve
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const long long n = state[0];
-    if (mean_samples(n, start, every)) state[1] = state[1] + 1;
+    if (samples_at(n, start, every)) state[1] = state[1] + 1;
     state[0] = n + 1;
 }
 

@@ -1,41 +1,6 @@
 // fs_pressure.hip - C-ABI entry points of the pressure kernels: Jacobi sweeps (single, lazily bounded pairs / quads / finishing pass), red-black
-// SOR (half sweeps, one fused iteration, two iterations per pass), the Poisson source pair, the residual, the flow diagnostics and the
-// per-step history ring, the body surface loads and the time averages.
+// SOR (half sweeps, one fused iteration, two iterations per pass), the Poisson source pair and the residual.
 #include "fs_launch.h"
-#include "fs_stats.h"
-#include "fs_mean.h"
-#include "fs_loads.h"
-
-static_assert(fs::STATS_N == FS_FLOW_NSTAT, "fs_stats.h and include/fs_hip.h disagree on the slots");
-static_assert(fs::LOADS_REC == FS_LOADS_NREC && fs::LOADS_SUMS == FS_LOADS_NSUM, "fs_loads.h and include/fs_hip.h disagree on the record / the sums");
-static_assert(fs::MEAN_PLANES == FS_MEAN_NPLANE, "fs_mean.h and include/fs_hip.h disagree on the planes");
-
-namespace fs {
-void history_release(fs_history *h)
-{
-    if (h->d_probes) hipFree(h->d_probes);
-    if (h->d_faces) hipFree(h->d_faces);
-    if (h->d_ring) hipFree(h->d_ring);
-    if (h->d_state) hipFree(h->d_state);
-    if (h->d_partial) hipFree(h->d_partial);
-    delete h;
-}
-void loads_release(fs_loads *l)
-{
-    if (l->d_faces) hipFree(l->d_faces);
-    if (l->d_sums) hipFree(l->d_sums);
-    if (l->d_ring) hipFree(l->d_ring);
-    if (l->d_state) hipFree(l->d_state);
-    if (l->d_partial) hipFree(l->d_partial);
-    delete l;
-}
-void mean_release(fs_mean *m)
-{
-    if (m->d_sums) hipFree(m->d_sums);
-    if (m->d_state) hipFree(m->d_state);
-    delete m;
-}
-}  // namespace fs
 
 using namespace fs;
 
@@ -395,466 +360,6 @@ int fs_poisson_residual(fs_ctx *ctx, double dt, double dx, const fs_field *p, co
     FS_HIP(hipStreamSynchronize(ctx->stream));
     *sum_sq = h[0];
     *count = h[1];
-    return FS_OK;
-}
-
-// rows per workgroup of k_flow_stats: STATS_G on small grids, up to STATS_ROWS (fs_launch.h diag_rows)
-static int stats_rows(const fs_ctx *ctx) { return diag_rows(ctx, (ctx->X + 255) / 256, ctx->nyl, STATS_G, STATS_ROWS); }
-
-int fs_flow_stats(fs_ctx *ctx, double dx, const fs_field *v, const fs_field *p, const int *box, double *out)
-{
-    FS_REQUIRE(ctx && out, "null argument");
-    FS_FIELD(v, 2); FS_FIELD(p, 1);
-    if (ctx->capturing || ctx->tape_rec) { set_error("flow stats during graph capture / tape recording"); return FS_ERR_STATE; }
-    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
-    int b[4] = {0, 0, 0, 0};      // empty box: no force
-    if (box) {
-        FS_REQUIRE(0 <= box[0] && box[0] <= box[2] && box[2] <= ctx->X && 0 <= box[1] && box[1] <= box[3] && box[3] <= ctx->Y,
-                   "body box must satisfy 0 <= x0 <= x1 <= X and 0 <= y0 <= y1 <= Y");
-        for (int k = 0; k < 4; ++k) b[k] = box[k];
-    }
-    const int row_begin = ctx->halo, row_end = ctx->halo + ctx->nyl;
-    const int nx = (ctx->X + 255) / 256, ny = row_end - row_begin;
-    const int rpw = stats_rows(ctx);
-    const dim3 grid(nx, (ny + rpw - 1) / rpw);
-    const size_t nblocks = (size_t)grid.x * grid.y;
-    if (nblocks + 1 > ctx->stats_cap) {
-        if (ctx->d_stats) { FS_HIP(hipStreamSynchronize(ctx->stream)); FS_HIP(hipFree(ctx->d_stats)); ctx->d_stats = nullptr; ctx->stats_cap = 0; }
-        FS_HIP(hipMalloc(&ctx->d_stats, (nblocks + 1) * STATS_N * sizeof(double)));
-        ctx->stats_cap = nblocks + 1;
-    }
-    double *partial = ctx->d_stats, *total = ctx->d_stats + nblocks * STATS_N;
-    int rc;
-    FS_DISPATCH(ctx, {
-        rc = launch(ctx, "flow_stats", [=] {
-            FS_KLAUNCH((k_flow_stats<T>), grid, dim3(256), 0, ctx->stream, ctx->grid(), row_begin, row_end, rpw, dx, b[0], b[1], b[2], b[3],
-                       (const T *)v->d, (const T *)p->d, partial);
-            FS_KLAUNCH((k_flow_stats_final), dim3(1), dim3(256), 0, ctx->stream, (const double *)partial, (int)nblocks, total);
-        });
-    })
-    if (rc) return rc;
-    FS_HIP(hipMemcpyAsync(out, total, STATS_N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    return FS_OK;
-}
-
-int fs_history_create(fs_ctx *ctx, int npoints, const int *points, int nfaces, const int *faces, int capacity, int every, fs_history **out)
-{
-    FS_REQUIRE(ctx && out, "null argument");
-    FS_REQUIRE(npoints >= 0 && nfaces >= 0 && (points || npoints == 0) && (faces || nfaces == 0), "bad point / face list");
-    FS_REQUIRE(capacity >= 1 && every >= 1, "capacity and every must be >= 1");
-    FS_REQUIRE((2 + 3 * (long long)npoints) * capacity < (1LL << 40), "ring too large");
-    if (ctx->capturing || ctx->tape_rec) { set_error("history create during graph capture / tape recording"); return FS_ERR_STATE; }
-    // a probe / face outside the owned rows would read a ghost row (stale between exchanges) or count a face twice across slabs
-    const int jo = ctx->y0, je = ctx->y0 + ctx->nyl;
-    auto local = [&](int x, int y) -> long long { return (long long)(y - ctx->y0 + ctx->halo) * ctx->P + x; };      // row-major element of (x, y)
-    std::vector<HistProbe> hp(npoints);
-    for (int k = 0; k < npoints; ++k) {
-        const int x = points[2 * k], y = points[2 * k + 1];
-        FS_REQUIRE(0 <= x && x < ctx->X && jo <= y && y < je, "probe outside this context's owned rows");
-        const int j = y - ctx->y0 + ctx->halo;
-        hp[k].u = (unsigned)(((long long)j * 2 + 0) * ctx->P + x);      // fs_device.h idx<2>
-        hp[k].w = (unsigned)(((long long)j * 2 + 1) * ctx->P + x);
-        hp[k].p = (unsigned)local(x, y);
-    }
-    std::vector<HistFace> hf(nfaces);
-    for (int k = 0; k < nfaces; ++k) {
-        const int x = faces[3 * k], y = faces[3 * k + 1], d = faces[3 * k + 2];
-        FS_REQUIRE(0 <= x && x < ctx->X && jo <= y && y < je, "face outside this context's owned rows");
-        FS_REQUIRE(0 <= d && d <= 3, "face direction must be 0 (+x), 1 (-x), 2 (+y) or 3 (-y)");
-        hf[k].p = (unsigned)local(x, y);
-        hf[k].dir = d;
-    }
-    FS_HIP(hipSetDevice(ctx->device));
-    fs_history *h = new fs_history();
-    h->ctx = ctx; h->np = npoints; h->nf = nfaces; h->cap = capacity; h->every = every;
-    h->nparts = nfaces > HIST_SPLIT ? (nfaces + HIST_FACES_PER_WG - 1) / HIST_FACES_PER_WG : 0;
-    const size_t ring = (size_t)capacity * (2 + 3 * (size_t)npoints) * sizeof(double);
-    hipError_t e = hipMalloc(&h->d_state, HIST_STATE * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc(&h->d_ring, ring);
-    if (e == hipSuccess && h->nparts) e = hipMalloc(&h->d_partial, 2 * (size_t)h->nparts * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&h->d_probes, std::max<size_t>(1, hp.size()) * sizeof(HistProbe));
-    if (e == hipSuccess) e = hipMalloc(&h->d_faces, std::max<size_t>(1, hf.size()) * sizeof(HistFace));
-    if (e == hipSuccess) e = hipMemsetAsync(h->d_state, 0, HIST_STATE * sizeof(long long), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(h->d_ring, 0, ring, ctx->stream);
-    if (e == hipSuccess && npoints) e = hipMemcpyAsync(h->d_probes, hp.data(), hp.size() * sizeof(HistProbe), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && nfaces) e = hipMemcpyAsync(h->d_faces, hf.data(), hf.size() * sizeof(HistFace), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { history_release(h); return hip_fail(e, "fs_history_create", __FILE__, __LINE__); }
-    ctx->histories.insert(h);
-    *out = h;
-    return FS_OK;
-}
-
-int fs_history_record(fs_ctx *ctx, fs_history *h, double dx, double limit, const fs_field *v, const fs_field *p)
-{
-    FS_REQUIRE(ctx && h, "null argument");
-    FS_REQUIRE(h->ctx == ctx && ctx->histories.count(h), "history from another context or freed");
-    FS_FIELD(v, 2); FS_FIELD(p, 1);
-    // everything the launch needs is in `h` and the fields: no allocation, copy or synchronisation here (the closure is captured / taped)
-    const HistProbe *pr = h->d_probes;
-    const HistFace *fc = h->d_faces;
-    const int np = h->np, nf = h->nf, every = h->every, cap = h->cap, threads = h->threads, nparts = h->nparts;
-    double *ring = h->d_ring, *partial = h->d_partial;
-    long long *state = h->d_state;
-    FS_DISPATCH(ctx, {
-        return launch(ctx, "history_record", [=] {
-            if (nparts)
-                FS_KLAUNCH((k_history_faces<T>), dim3(nparts), dim3(HIST_FACES_PER_WG), 0, ctx->stream, (const T *)p->d, fc, nf, dx, every, cap,
-                           (const long long *)state, partial);
-            FS_KLAUNCH((k_history_record<T>), dim3(1), dim3(threads), 0, ctx->stream, (const T *)v->d, (const T *)p->d, pr, np, fc, nf,
-                       (const double *)partial, nparts, dx, limit, every, cap, ring, state);
-        });
-    })
-}
-
-int fs_history_read(fs_ctx *ctx, fs_history *h, double *out, int max_records, int *n_records, long long *launches, int *dropped)
-{
-    FS_REQUIRE(ctx && h && n_records, "null argument");
-    FS_REQUIRE(h->ctx == ctx && ctx->histories.count(h), "history from another context or freed");
-    if (ctx->capturing || ctx->tape_rec) { set_error("history read during graph capture / tape recording"); return FS_ERR_STATE; }
-    FS_HIP(hipSetDevice(ctx->device));
-    long long st[HIST_STATE];
-    FS_HIP(hipMemcpyAsync(st, h->d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    *n_records = (int)st[1];
-    if (launches) *launches = st[0];
-    if (dropped) *dropped = (int)st[2];
-    if (!out) return FS_OK;
-    FS_REQUIRE(max_records >= st[1], "out holds fewer records than the ring");
-    if (st[1] > 0)
-        FS_HIP(hipMemcpyAsync(out, h->d_ring, (size_t)st[1] * (2 + 3 * (size_t)h->np) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(hipMemsetAsync(h->d_state + 1, 0, 2 * sizeof(long long), ctx->stream));       // written, dropped; the launch count runs on
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    return FS_OK;
-}
-
-int fs_history_free(fs_ctx *ctx, fs_history *h)
-{
-    if (!h) return FS_OK;
-    FS_REQUIRE(ctx && h->ctx == ctx && ctx->histories.count(h), "history from another context or freed");
-    ctx->histories.erase(h);
-    if (ctx->capturing) { ctx->deferred_hist.push_back(h); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
-    hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
-    history_release(h);
-    return FS_OK;
-}
-
-// ---- body surface loads (fs_loads.h) -----------------------------------------------------------------------------------------------------
-#define FS_LOADS_HANDLE(l) FS_REQUIRE((l)->ctx == ctx && ctx->loads.count(l), "loads from another context or freed")
-#define FS_LOADS_NO_CAPTURE(what) \
-    if (ctx->capturing || ctx->tape_rec) { set_error("loads " what " during graph capture / tape recording"); return FS_ERR_STATE; }
-
-int fs_loads_create(fs_ctx *ctx, int nfaces, const int *faces, const double *centre_xy, int capacity, long long every, long long start,
-                    fs_loads **out)
-{
-    FS_REQUIRE(ctx && out && faces && centre_xy, "null argument");
-    FS_REQUIRE(nfaces >= 1, "nfaces must be >= 1");
-    FS_REQUIRE(capacity >= 1 && every >= 1 && start >= 0, "capacity and every must be >= 1 and start >= 0");
-    FS_REQUIRE(std::isfinite(centre_xy[0]) && std::isfinite(centre_xy[1]), "the centre must be finite");
-    FS_LOADS_NO_CAPTURE("create")
-    // a face outside the owned rows would read a ghost row (stale between exchanges) or be counted twice across slabs
-    const int jo = ctx->y0, je = ctx->y0 + ctx->nyl;
-    const double cx = centre_xy[0], cy = centre_xy[1];
-    std::vector<LoadFace> lf(nfaces);
-    for (int k = 0; k < nfaces; ++k) {
-        const int x = faces[3 * k], y = faces[3 * k + 1], d = faces[3 * k + 2];
-        FS_REQUIRE(0 <= x && x < ctx->X && jo <= y && y < je, "face outside this context's owned rows");
-        FS_REQUIRE(0 <= d && d <= 3, "face direction must be 0 (+x), 1 (-x), 2 (+y) or 3 (-y)");
-        const long long j = y - ctx->y0 + ctx->halo;
-        lf[k].u = (unsigned)((j * 2 + 0) * ctx->P + x);      // fs_device.h idx<2>
-        lf[k].w = (unsigned)((j * 2 + 1) * ctx->P + x);
-        lf[k].p = (unsigned)(j * ctx->P + x);
-        lf[k].dir = d;
-        const double xm = d == 0 ? (double)x : d == 1 ? (double)x + 1.0 : (double)x + 0.5;      // the face midpoint, cell units
-        const double ym = d == 2 ? (double)y : d == 3 ? (double)y + 1.0 : (double)y + 0.5;
-        lf[k].rx = xm - cx;
-        lf[k].ry = ym - cy;
-    }
-    FS_HIP(hipSetDevice(ctx->device));
-    fs_loads *l = new fs_loads();
-    l->ctx = ctx; l->nf = nfaces; l->cap = capacity; l->every = every; l->start = start;
-    l->nparts = nfaces > LOADS_SPLIT ? (nfaces + LOADS_WG - 1) / LOADS_WG : 0;
-    const size_t ring = (size_t)capacity * LOADS_REC * sizeof(double), sums = (size_t)LOADS_SUMS * nfaces * sizeof(double);
-    hipError_t e = hipMalloc(&l->d_state, LOADS_STATE * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc(&l->d_ring, ring);
-    if (e == hipSuccess) e = hipMalloc(&l->d_sums, sums);
-    if (e == hipSuccess && l->nparts) e = hipMalloc(&l->d_partial, (size_t)LOADS_REC * l->nparts * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&l->d_faces, lf.size() * sizeof(LoadFace));
-    if (e == hipSuccess) e = hipMemsetAsync(l->d_state, 0, LOADS_STATE * sizeof(long long), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(l->d_ring, 0, ring, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(l->d_sums, 0, sums, ctx->stream);
-    if (e == hipSuccess && l->nparts) e = hipMemsetAsync(l->d_partial, 0, (size_t)LOADS_REC * l->nparts * sizeof(double), ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(l->d_faces, lf.data(), lf.size() * sizeof(LoadFace), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { loads_release(l); return hip_fail(e, "fs_loads_create", __FILE__, __LINE__); }
-    ctx->loads.insert(l);
-    *out = l;
-    return FS_OK;
-}
-
-int fs_loads_record(fs_ctx *ctx, fs_loads *l, double dx, double inv_re, double limit, const fs_field *v, const fs_field *p)
-{
-    FS_REQUIRE(ctx && l, "null argument");
-    FS_LOADS_HANDLE(l);
-    FS_FIELD(v, 2); FS_FIELD(p, 1);
-    // everything the launches need is in `l` and the fields: no allocation, copy or synchronisation here (the closure is captured / taped)
-    const LoadFace *fc = l->d_faces;
-    const int nf = l->nf, cap = l->cap, nparts = l->nparts;
-    const size_t stride = (size_t)l->nf;
-    const long long every = l->every, start = l->start;
-    double *sums = l->d_sums, *ring = l->d_ring, *partial = l->d_partial;
-    long long *state = l->d_state;
-    FS_DISPATCH(ctx, {
-        return launch(ctx, "loads_record", [=] {
-            if (nparts) {
-                FS_KLAUNCH((k_loads_faces<T>), dim3(nparts), dim3(LOADS_WG), 0, ctx->stream, (const T *)v->d, (const T *)p->d, fc, nf, stride, dx,
-                           inv_re, limit, start, every, (const long long *)state, sums, partial);
-                FS_KLAUNCH((k_loads_record), dim3(1), dim3(LOADS_WG), 0, ctx->stream, (const double *)partial, nparts, start, every, cap, ring, state);
-            } else {
-                FS_KLAUNCH((k_loads_one<T>), dim3(1), dim3(LOADS_WG), 0, ctx->stream, (const T *)v->d, (const T *)p->d, fc, nf, stride, dx, inv_re,
-                           limit, start, every, cap, sums, ring, state);
-            }
-        });
-    })
-}
-
-int fs_loads_read(fs_ctx *ctx, fs_loads *l, double *ring_out, int max_records, int *n_records, long long *launches, long long *samples,
-                  int *dropped)
-{
-    FS_REQUIRE(ctx && l && n_records, "null argument");
-    FS_LOADS_HANDLE(l);
-    FS_LOADS_NO_CAPTURE("read")
-    FS_HIP(hipSetDevice(ctx->device));
-    long long st[LOADS_STATE];
-    FS_HIP(hipMemcpyAsync(st, l->d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    *n_records = (int)st[2];
-    if (launches) *launches = st[0];
-    if (samples) *samples = st[1];
-    if (dropped) *dropped = (int)st[3];
-    if (!ring_out) return FS_OK;
-    FS_REQUIRE(max_records >= st[2], "ring_out holds fewer records than the ring");
-    if (st[2] > 0)
-        FS_HIP(hipMemcpyAsync(ring_out, l->d_ring, (size_t)st[2] * LOADS_REC * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(hipMemsetAsync(l->d_state + 2, 0, 2 * sizeof(long long), ctx->stream));       // written, dropped; launches and samples run on
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    return FS_OK;
-}
-
-int fs_loads_sums_read(fs_ctx *ctx, fs_loads *l, double *sums_out)
-{
-    FS_REQUIRE(ctx && l && sums_out, "null argument");
-    FS_LOADS_HANDLE(l);
-    FS_LOADS_NO_CAPTURE("sums_read")
-    FS_HIP(hipSetDevice(ctx->device));
-    FS_HIP(hipMemcpyAsync(sums_out, l->d_sums, (size_t)LOADS_SUMS * l->nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    return FS_OK;
-}
-
-int fs_loads_sums_write(fs_ctx *ctx, fs_loads *l, const double *sums_in, long long launches, long long samples)
-{
-    FS_REQUIRE(ctx && l && sums_in, "null argument");
-    FS_LOADS_HANDLE(l);
-    FS_REQUIRE(launches >= 0 && samples >= 0 && samples <= launches, "counters must satisfy 0 <= samples <= launches");
-    FS_LOADS_NO_CAPTURE("sums_write")
-    FS_HIP(hipSetDevice(ctx->device));
-    const long long st[2] = {launches, samples};
-    FS_HIP(hipMemcpyAsync(l->d_sums, sums_in, (size_t)LOADS_SUMS * l->nf * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipMemcpyAsync(l->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
-    return FS_OK;
-}
-
-int fs_loads_reset(fs_ctx *ctx, fs_loads *l)
-{
-    FS_REQUIRE(ctx && l, "null argument");
-    FS_LOADS_HANDLE(l);
-    FS_LOADS_NO_CAPTURE("reset")
-    FS_HIP(hipSetDevice(ctx->device));
-    FS_HIP(hipMemsetAsync(l->d_sums, 0, (size_t)LOADS_SUMS * l->nf * sizeof(double), ctx->stream));
-    FS_HIP(hipMemsetAsync(l->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
-    return FS_OK;
-}
-
-int fs_loads_free(fs_ctx *ctx, fs_loads *l)
-{
-    if (!l) return FS_OK;
-    FS_REQUIRE(ctx && l->ctx == ctx && ctx->loads.count(l), "loads from another context or freed");
-    ctx->loads.erase(l);
-    if (ctx->capturing) { ctx->deferred_loads.push_back(l); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
-    hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
-    loads_release(l);
-    return FS_OK;
-}
-
-// ---- time averages (fs_mean.h) ---------------------------------------------------------------------------------------------------------
-#define FS_MEAN_HANDLE(m) FS_REQUIRE((m)->ctx == ctx && ctx->means.count(m), "mean from another context or freed")
-#define FS_MEAN_NO_CAPTURE(what) \
-    if (ctx->capturing || ctx->tape_rec) { set_error("mean " what " during graph capture / tape recording"); return FS_ERR_STATE; }
-
-// workgroups of 256 lanes x `w` columns and `rpw` rows over the owned rows: rows per workgroup from `g0` up to MEAN_ROWS (fs_launch.h
-// diag_rows) - a non-sampling launch is a counter read per workgroup, so the grid stays in the thousands
-static int mean_width(const fs_ctx *ctx) { return ctx->X % 2 == 0 ? 2 : 1; }      // columns per lane: W of k_mean_accumulate / k_mean_finalize
-static dim3 mean_grid(const fs_ctx *ctx, int w, int g0, int *rpw)
-{
-    const int nx = (ctx->X + 256 * w - 1) / (256 * w), ny = ctx->nyl;
-    const int r = diag_rows(ctx, nx, ny, g0, MEAN_ROWS);
-    *rpw = r;
-    return dim3(nx, (ny + r - 1) / r);
-}
-
-// diagnostic: the rows per workgroup the next fs_flow_stats / fs_mean_accumulate / fs_mean_finalize launches of this context take
-int fs_diag_rows(fs_ctx *ctx, int *flow_stats_rows, int *mean_accumulate_rows, int *mean_finalize_rows)
-{
-    FS_REQUIRE(ctx && flow_stats_rows && mean_accumulate_rows && mean_finalize_rows, "null argument");
-    *flow_stats_rows = stats_rows(ctx);
-    mean_grid(ctx, mean_width(ctx), MEAN_G, mean_accumulate_rows);
-    mean_grid(ctx, mean_width(ctx), 1, mean_finalize_rows);
-    return FS_OK;
-}
-
-int fs_mean_create(fs_ctx *ctx, long long every, long long start, fs_mean **out)
-{
-    FS_REQUIRE(ctx && out, "null argument");
-    FS_REQUIRE(every >= 1 && start >= 0, "every must be >= 1 and start >= 0");
-    FS_MEAN_NO_CAPTURE("create")
-    FS_HIP(hipSetDevice(ctx->device));
-    fs_mean *m = new fs_mean();
-    m->ctx = ctx; m->every = every; m->start = start;
-    m->plane = (size_t)ctx->nyl * ctx->P + MEAN_PAD;
-    const size_t bytes = MEAN_PLANES * m->plane * sizeof(double);
-    hipError_t e = hipMalloc(&m->d_state, MEAN_STATE * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc(&m->d_sums, bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(m->d_state, 0, MEAN_STATE * sizeof(long long), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(m->d_sums, 0, bytes, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { mean_release(m); return hip_fail(e, "fs_mean_create", __FILE__, __LINE__); }
-    ctx->means.insert(m);
-    *out = m;
-    return FS_OK;
-}
-
-int fs_mean_accumulate(fs_ctx *ctx, fs_mean *m, double limit, const fs_field *v, const fs_field *p)
-{
-    FS_REQUIRE(ctx && m, "null argument");
-    FS_MEAN_HANDLE(m);
-    FS_FIELD(v, 2); FS_FIELD(p, 1);
-    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
-    // everything the launches need is in `m` and the fields: no allocation, copy or synchronisation here (the closure is captured / taped)
-    const int jb = ctx->halo, je = ctx->halo + ctx->nyl, w = mean_width(ctx);
-    int rpw;
-    const dim3 grid = mean_grid(ctx, w, MEAN_G, &rpw);
-    const long long every = m->every, start = m->start;
-    long long *state = m->d_state;
-    double *sums = m->d_sums;
-    const size_t plane = m->plane;
-    FS_DISPATCH(ctx, {
-        return launch(ctx, "mean_accumulate", [=] {
-            if (w == 2)
-                FS_KLAUNCH((k_mean_accumulate<T, 2>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, limit, start, every,
-                           (const long long *)state, (const T *)v->d, (const T *)p->d, sums, plane);
-            else
-                FS_KLAUNCH((k_mean_accumulate<T, 1>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, limit, start, every,
-                           (const long long *)state, (const T *)v->d, (const T *)p->d, sums, plane);
-            FS_KLAUNCH((k_mean_tick), dim3(1), dim3(64), 0, ctx->stream, start, every, state);
-        });
-    })
-}
-
-static int mean_counters(fs_ctx *ctx, fs_mean *m, long long *st)
-{
-    FS_HIP(hipSetDevice(ctx->device));
-    FS_HIP(hipMemcpyAsync(st, m->d_state, MEAN_STATE * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    return FS_OK;
-}
-
-int fs_mean_finalize(fs_ctx *ctx, fs_mean *m, fs_field *v_out, fs_field *p_out)
-{
-    FS_REQUIRE(ctx && m, "null argument");
-    FS_MEAN_HANDLE(m);
-    FS_FIELD(v_out, 2); FS_FIELD(p_out, 1);
-    FS_MEAN_NO_CAPTURE("finalize")
-    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
-    long long st[MEAN_STATE];
-    if (int rc = mean_counters(ctx, m, st)) return rc;
-    if (st[1] < 1) { set_error("mean finalize: no sample accumulated yet"); return FS_ERR_STATE; }
-    const int jb = ctx->halo, je = ctx->halo + ctx->nyl, w = mean_width(ctx);
-    int rpw;
-    const dim3 grid = mean_grid(ctx, w, 1, &rpw);
-    const long long *state = m->d_state;
-    const double *sums = m->d_sums;
-    const size_t plane = m->plane;
-    FS_DISPATCH(ctx, {
-        return launch(ctx, "mean_finalize", [=] {
-            if (w == 2)
-                FS_KLAUNCH((k_mean_finalize<T, 2>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, state, sums, plane, (T *)v_out->d,
-                           (T *)p_out->d, v_out->hot);
-            else
-                FS_KLAUNCH((k_mean_finalize<T, 1>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, state, sums, plane, (T *)v_out->d,
-                           (T *)p_out->d, v_out->hot);
-        });
-    })
-}
-
-int fs_mean_read(fs_ctx *ctx, fs_mean *m, double *sums_out, long long *launches, long long *samples)
-{
-    FS_REQUIRE(ctx && m, "null argument");
-    FS_MEAN_HANDLE(m);
-    FS_MEAN_NO_CAPTURE("read")
-    long long st[MEAN_STATE];
-    if (int rc = mean_counters(ctx, m, st)) return rc;
-    if (launches) *launches = st[0];
-    if (samples) *samples = st[1];
-    if (!sums_out) return FS_OK;
-    // per plane: nyl device rows of pitch P -> dense rows of X
-    for (int k = 0; k < MEAN_PLANES; ++k)
-        FS_HIP(hipMemcpy2DAsync(sums_out + (size_t)k * ctx->nyl * ctx->X, (size_t)ctx->X * sizeof(double), m->d_sums + k * m->plane,
-                                (size_t)ctx->P * sizeof(double), (size_t)ctx->X * sizeof(double), (size_t)ctx->nyl, hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    return FS_OK;
-}
-
-int fs_mean_write(fs_ctx *ctx, fs_mean *m, const double *sums_in, long long launches, long long samples)
-{
-    FS_REQUIRE(ctx && m && sums_in, "null argument");
-    FS_MEAN_HANDLE(m);
-    FS_REQUIRE(launches >= 0 && samples >= 0 && samples <= launches, "counters must satisfy 0 <= samples <= launches");
-    FS_MEAN_NO_CAPTURE("write")
-    FS_HIP(hipSetDevice(ctx->device));
-    const long long st[MEAN_STATE] = {launches, samples};
-    for (int k = 0; k < MEAN_PLANES; ++k)
-        FS_HIP(hipMemcpy2DAsync(m->d_sums + k * m->plane, (size_t)ctx->P * sizeof(double), sums_in + (size_t)k * ctx->nyl * ctx->X,
-                                (size_t)ctx->X * sizeof(double), (size_t)ctx->X * sizeof(double), (size_t)ctx->nyl, hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipMemcpyAsync(m->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
-    return FS_OK;
-}
-
-int fs_mean_reset(fs_ctx *ctx, fs_mean *m)
-{
-    FS_REQUIRE(ctx && m, "null argument");
-    FS_MEAN_HANDLE(m);
-    FS_MEAN_NO_CAPTURE("reset")
-    FS_HIP(hipSetDevice(ctx->device));
-    FS_HIP(hipMemsetAsync(m->d_sums, 0, MEAN_PLANES * m->plane * sizeof(double), ctx->stream));
-    FS_HIP(hipMemsetAsync(m->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
-    return FS_OK;
-}
-
-int fs_mean_free(fs_ctx *ctx, fs_mean *m)
-{
-    if (!m) return FS_OK;
-    FS_REQUIRE(ctx && m->ctx == ctx && ctx->means.count(m), "mean from another context or freed");
-    ctx->means.erase(m);
-    if (ctx->capturing) { ctx->deferred_mean.push_back(m); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
-    hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
-    mean_release(m);
     return FS_OK;
 }
 

@@ -398,6 +398,7 @@ __global__ __launch_bounds__(TRACER_WG) void k_tracer_fields(int X, int Y, Trace
 __global__ __launch_bounds__(TRACER_WG) void k_tracer_accumulate(int X, int Y, TracerDev t, long long start, long long every, long long *state,
                                                                  unsigned long long *__restrict__ occupancy, unsigned long long *__restrict__ age_sum)
 {
+    // (its own copy of the rule, fs_device.h samples_at: the advance has counted itself, and samples_at(n1 - 1, ...) compiles to other instructions)
     const long long n1 = t.count[0] - state[0];
     if (!(n1 > start && (n1 - start) % every == 0)) return;      // (the same in every lane of every workgroup)
     const int k = blockIdx.x * TRACER_WG + threadIdx.x;

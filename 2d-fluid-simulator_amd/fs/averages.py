@@ -5,19 +5,11 @@ The accumulation itself is a device launch per step (csrc/fs_mean.h, include/fs_
 FluidSimulator.start_averaging / averages / reset_averages / stop_averaging."""
 import numpy as np
 
+from .riders import Rider, is_sampling_launch, samples_after      # noqa: F401 (the sampling rule: re-exported)
+
 FLUID, WALL = 0, 1
 # plane order of fs_mean_read / fs_mean_write
 SUMS = ("S_u", "S_w", "S_p", "S_uu", "S_ww", "S_uw", "S_pp")
-
-
-def is_sampling_launch(n, every, start):
-    """Whether accumulation launch n (counted from 0) samples: n + 1 > start and (n + 1 - start) % every == 0."""
-    return n + 1 > start and (n + 1 - start) % every == 0
-
-
-def samples_after(launches, every, start):
-    """Samples taken by the first `launches` launches."""
-    return max(0, (int(launches) - int(start)) // int(every))
 
 
 def derive_averages(sums, samples, mask=None):
@@ -66,7 +58,7 @@ def recirculation_length(mean_u, mask, body_box, dx):
     return float((x - x1) * dx)
 
 
-class Averager:
+class Averager(Rider):
     """One time average of a FluidSimulator (start_averaging): the device accumulator and its parameters."""
 
     def __init__(self, dev, mean, every, start_step):
@@ -75,3 +67,18 @@ class Averager:
     @property
     def token(self):
         return ("mean", self.mean.serial)
+
+    def launch(self, sim):
+        v, p = sim._solver.get_fields()[:2]
+        self.dev.mean_accumulate(self.mean, v, p)
+
+    def free(self):
+        self.dev.mean_free(self.mean)
+
+    def checkpoint(self):
+        sums, launches, samples = self.dev.mean_read(self.mean)
+        return {"mean.sums": sums, "mean.launches": np.array(launches), "mean.samples": np.array(samples),
+                "mean.every": np.array(self.every), "mean.start": np.array(self.start_step)}
+
+    def restore(self, z):
+        self.dev.mean_write(self.mean, z["mean.sums"], int(z["mean.launches"]), int(z["mean.samples"]))

@@ -89,47 +89,43 @@ class FluidSimulator:
         self._tracker = None       # fs.loads.Tracker while track_body() is on
         self._last_tracker = None  # ... and after stop_body(): what body_loads() / body_surface() still return
 
-    def _update(self):
-        """One solver step, then the history record if a recorder is attached, the accumulation of the time averages if an averager is,
-        the body tracker's launches if one is and the advance of the tracer particles if a set is: what step(), the periods
-        capture_period() captures and the slab periods tape_period() logs all run (so a graph or tape holds these launches exactly when
-        _signature() says so)."""
-        self._solver.update()
-        rec = self._recorder
-        if rec is not None:
-            if rec.room() <= 0 and not getattr(self._dev, "capturing", False):
-                rec.drain()          # (eager steps beyond the ring: run() drains between its chunks instead)
-            v, p = self._solver.get_fields()[:2]
-            self._dev.history_record(rec.hist, self._solver.dx, v, p)
-            rec.issued += 1
-        avg = self._averager
-        if avg is not None:
-            v, p = self._solver.get_fields()[:2]
-            self._dev.mean_accumulate(avg.mean, v, p)
-        bt = self._tracker
-        if bt is not None:
-            if bt.room() <= 0 and not getattr(self._dev, "capturing", False):
-                bt.drain()           # (eager steps beyond the ring: run() drains between its chunks instead)
-            v, p = self._solver.get_fields()[:2]
-            self._dev.loads_record(bt.loads, self._solver.dx, 1.0 / self._solver.re, v, p)
-            bt.issued += 1
-        tr = self._tracers
-        if tr is not None:
-            self._dev.tracer_advance(tr.set, self._solver.dt / self._solver.dx, self._solver.get_fields()[0])
-            tr.issued += 1
-            if tr.accumulation is not None:
-                self._dev.tracer_accum_add(tr.set)      # (behind the advance: gated on the device from the set's launch counter)
+    def _riders(self):
+        """The attached riders (fs.riders.Rider) in their fixed order - history, averages, loads, tracers: the order of their launches behind
+        the solver step and of their tokens in _signature()."""
+        return [r for r in (self._recorder, self._averager, self._tracker, self._tracers) if r is not None]
 
-    def _sort_if_due(self):
-        """The scheduled device sort of the tracer particles (seed_tracers(sort_every=K)): after every K-th step, between launch sequences -
-        never inside a capture."""
-        tr = self._tracers
-        if tr is not None and tr.due() and not getattr(self._dev, "capturing", False):
-            tr.sort()
+    def _capturing(self):
+        return getattr(self._dev, "capturing", False)
+
+    def _not_capturing(self, name):
+        if getattr(self._dev, "capturing", False):
+            raise RuntimeError(f"{name} during a graph capture")
+
+    @staticmethod
+    def _cadence(every, start_step=0):
+        every, start_step = int(every), int(start_step)
+        if every < 1:
+            raise ValueError("every must be >= 1")
+        if start_step < 0:
+            raise ValueError("start_step must be >= 0")
+        return every, start_step
+
+    def _update(self):
+        """One solver step, then the launches of every attached rider: what step(), the periods capture_period() captures and the slab
+        periods tape_period() logs all run (so a graph or tape holds these launches exactly when _signature() says so)."""
+        self._solver.update()
+        for r in self._riders():
+            r.launch(self)
+
+    def _between_chunks(self):
+        """What the riders do between launch sequences - never inside a capture (the scheduled sort of the tracer particles)."""
+        if not self._capturing():
+            for r in self._riders():
+                r.between_chunks()
 
     def step(self):
         self._update()
-        self._sort_if_due()
+        self._between_chunks()
         self._eager_seen = True        # (captures call the solver directly: see capture_period)
         self._pending_after_step = self._limit_pending()
         self._since_hot_check += 1
@@ -141,7 +137,7 @@ class FluidSimulator:
         up) the pass runs on every step, and as its own full-grid launch it is three times faster than inside a boundary launch at res 4096:
         looked at between launch sequences - at the start of run() / capture_period() and every 256 eager steps (one 12-byte download)."""
         dev = self._dev
-        if getattr(dev, "capturing", False):
+        if self._capturing():
             return            # (a user capture of step() in progress: the look is a download - it waits for the next eager step)
         self._since_hot_check = 0
         if not getattr(dev, "limit_deferral", False):
@@ -176,16 +172,8 @@ class FluidSimulator:
                     sig.append((f.serial, f.user_data, f.static_id, f.pending_limit, f.pending_clamp, f.bc_parity))      # (pending_limit: a deferred limit_field, runtime.DeviceBase.limit_field)
         for spare in (getattr(s, "_v_spare", None), getattr(s, "_dye_spare", None)) + tuple(getattr(s.pressure_updater, "_spare", None) or ()):
             sig.append((spare.serial, spare.static_id, spare.bc_parity) if spare is not None else 0)
-        if self._recorder is not None:
-            sig.append(self._recorder.token)        # (graphs / tapes with the record launch in them are never replayed without it, or vice versa)
-        if self._averager is not None:
-            sig.append(self._averager.token)        # (likewise the accumulation launch of the time averages)
-        if self._tracker is not None:
-            sig.append(self._tracker.token)         # (and the launches of the body tracker)
-        if self._tracers is not None:
-            sig.append(self._tracers.token)         # (and the advance of the tracer particles)
-            if self._tracers.accumulation is not None:
-                sig.append(self._tracers.accumulation.token)      # (and the accumulation launch behind it)
+        for r in self._riders():
+            sig.extend(r.tokens())      # (graphs / tapes with a rider's launches in them are never replayed without it, or vice versa)
         return tuple(sig)
 
     _LONG_STEPS = 16     # steps per long-form graph (capture_period)
@@ -204,33 +192,25 @@ class FluidSimulator:
         rings - the smaller room of the two - and whichever is full is drained between them: no record is ever dropped.  With a sort
         schedule for the tracer particles (seed_tracers(sort_every=K)) it is also cut at every K-th step since seed_tracers, where the
         particles are sorted between two chunks; the two cuts compose."""
-        tr = self._tracers
-        rings = [r for r in (self._recorder, self._tracker) if r is not None]      # (each with a device ring: room() / drain())
-        cut = tr is not None and tr.sort_every > 0
-        if not rings and not cut:
+        riders = self._riders()
+        rings = [r for r in riders if r.room() is not None]      # (each with a device ring: room() / drain())
+        cutters = [r for r in riders if r.next_cut() is not None]
+        if not rings and not cutters:
             return self._run_chunk(nsteps, graph)
         while nsteps > 0:
-            m = nsteps
             full = [r for r in rings if r.room() <= 0]
             if full:
                 for r in full:
                     r.drain()
                 continue
-            for r in rings:
-                m = min(m, r.room())
-            if cut:
-                m = min(m, tr.to_next_sort())
-            self._run_chunk(m, graph, reuse=cut)       # (its eager steps sort when they land on the K-th step themselves)
+            m = min([nsteps] + [r.room() for r in rings] + [r.next_cut() for r in cutters])
+            self._run_chunk(m, graph, reuse=bool(cutters))       # (its eager steps sort when they land on the K-th step themselves)
             nsteps -= m
-            self._sort_if_due()
+            self._between_chunks()
 
     def _replayed(self, steps):
-        if self._recorder is not None:
-            self._recorder.issued += steps
-        if self._tracers is not None:
-            self._tracers.issued += steps
-        if self._tracker is not None:
-            self._tracker.issued += steps
+        for r in self._riders():
+            r.replayed(steps)
 
     def _run_chunk(self, nsteps, graph, reuse=False):
         """reuse (the chunks a sort schedule cuts): a chunk that starts in a phase of the buffer rotation no cached graph belongs to takes
@@ -382,11 +362,8 @@ class FluidSimulator:
         start_step + k.  Changes no field and no trajectory; a recorder already attached is stopped first.  history() returns the records.
         Not allowed during a graph capture."""
         dev, s = self._dev, self._solver
-        if getattr(dev, "capturing", False):
-            raise RuntimeError("record_history during a graph capture")
-        every = int(every)
-        if every < 1:
-            raise ValueError("every must be >= 1")
+        self._not_capturing("record_history")
+        every, _ = self._cadence(every)
         mask = s._bc.mask
         pts = check_probes(mask, probes)
         if body_box is not None:
@@ -400,7 +377,7 @@ class FluidSimulator:
             capacity = max(64, (16 << 20) // (8 * (2 + 3 * len(pts))))
         if int(capacity) < 1:
             raise ValueError("capacity must be >= 1")
-        self.stop_history()
+        self._make_way("_recorder")
         hist = dev.history_create(pts, faces, int(capacity), every)
         self._recorder = Recorder(dev, hist, pts, body_box, every, start_step, s.dt)
         self._last_recorder = None
@@ -418,18 +395,37 @@ class FluidSimulator:
     def stop_history(self):
         """Drain and detach the recorder: the cached graphs and tapes that hold its launch are freed, then its device ring.  history() still
         returns what it recorded until the next record_history()."""
-        rec = self._recorder
-        if rec is None:
+        self._detach(self, "_recorder", "stop_history")
+
+    def _make_way(self, attr, refusal=None):
+        """An attach call that finds a rider of its kind attached: its replaces_attached says whether it is stopped or the call refused."""
+        r = getattr(self, attr)
+        if r is not None:
+            if not r.replaces_attached:
+                raise RuntimeError(refusal)
+            self._detach(self, attr, None)
+
+    def _detach(self, owner, attr, name):
+        """The stop_* methods: drain the rider owner.<attr>, free the cached graphs and tapes that hold its launches, then its device objects.
+        Its class says whether this may happen inside a graph capture (stop_in_capture: no graph can be freed there - theirs stay cached,
+        never matched again - and the device memory is released when the capture ends) and whether it stays as _last<attr> (keeps_last)."""
+        r = getattr(owner, attr)
+        if r is None:
             return
-        dev = self._dev
-        if getattr(dev, "capturing", False):
-            raise RuntimeError("stop_history during a graph capture")
+        capturing = self._capturing()
+        if capturing and not r.stop_in_capture:
+            raise RuntimeError(f"{name} during a graph capture")
         try:
-            rec.drain()
+            r.drain()
+            r.close()
         finally:
-            self._drop_cached(rec.token)
-            dev.history_free(rec.hist)
-            self._recorder, self._last_recorder = None, rec
+            if not capturing:
+                for tok in r.tokens():
+                    self._drop_cached(tok)
+            r.free()
+            setattr(owner, attr, None)
+            if r.keeps_last:
+                setattr(owner, "_last" + attr, r)
 
     def _drop_cached(self, tok):
         """Free the cached graphs and tapes whose signature holds `tok` (they contain a launch on a device object about to be freed)."""
@@ -470,15 +466,9 @@ class FluidSimulator:
         trajectory.  body_loads() returns the series, body_surface() the distributions.  Raises while a tracker is attached already; not
         allowed during a graph capture."""
         dev, s = self._dev, self._solver
-        if getattr(dev, "capturing", False):
-            raise RuntimeError("track_body during a graph capture")
-        if self._tracker is not None:
-            raise RuntimeError("a body tracker is attached already: stop_body() first")
-        every, start_step = int(every), int(start_step)
-        if every < 1:
-            raise ValueError("every must be >= 1")
-        if start_step < 0:
-            raise ValueError("start_step must be >= 0")
+        self._not_capturing("track_body")
+        self._make_way("_tracker", "a body tracker is attached already: stop_body() first")
+        every, start_step = self._cadence(every, start_step)
         capacity = 65536 if capacity is None else int(capacity)
         if capacity < 1:
             raise ValueError("capacity must be >= 1")
@@ -492,8 +482,7 @@ class FluidSimulator:
         if bt is None:
             raise RuntimeError("no body tracker: call track_body() first")
         if bt is self._tracker:
-            if getattr(self._dev, "capturing", False):
-                raise RuntimeError("body_loads / body_surface during a graph capture")
+            self._not_capturing("body_loads / body_surface")
             bt.drain()
         return bt
 
@@ -514,8 +503,7 @@ class FluidSimulator:
         """Per-face sums and sample count back to zero; the step count (the phase of `every` / `start_step`) and the series run on."""
         if self._tracker is None:
             raise RuntimeError("no body tracker: call track_body() first")
-        if getattr(self._dev, "capturing", False):
-            raise RuntimeError("reset_body_surface during a graph capture")
+        self._not_capturing("reset_body_surface")
         self._tracker.drain()
         self._dev.loads_reset(self._tracker.loads)
         self._tracker.samples = 0
@@ -523,19 +511,7 @@ class FluidSimulator:
     def stop_body(self):
         """Drain and detach the body tracker: the cached graphs and tapes that hold its launches are freed, then its device memory.
         body_loads() and body_surface() still return what it gathered until the next track_body()."""
-        bt = self._tracker
-        if bt is None:
-            return
-        dev = self._dev
-        if getattr(dev, "capturing", False):
-            raise RuntimeError("stop_body during a graph capture")
-        try:
-            bt.drain()
-            bt.close()
-        finally:
-            self._drop_cached(bt.token)
-            dev.loads_free(bt.loads)
-            self._tracker, self._last_tracker = None, bt
+        self._detach(self, "_tracker", "stop_body")
 
     def body_snapshot(self, body_box, center=None):
         """The loads of the fields as they are now: the keys of body_loads() without step / time as floats, plus "faces", "x", "y", "nx",
@@ -543,8 +519,7 @@ class FluidSimulator:
         graph and no attached tracker, and leaves a deferred limit_field deferred (the kernel limits the values it reads).  Not allowed
         during a graph capture."""
         dev, s = self._dev, self._solver
-        if getattr(dev, "capturing", False):
-            raise RuntimeError("body_snapshot during a graph capture")
+        self._not_capturing("body_snapshot")
         body_box, faces, centre = self._body_faces(body_box, center)
         v, p = s.get_fields()[:2]
         lo = dev.loads_create(faces, centre, 1, 1, 0)
@@ -574,15 +549,9 @@ class FluidSimulator:
         Changes no field and no trajectory.  averages() returns the result.  Raises while an average is attached already; not allowed during
         a graph capture."""
         dev = self._dev
-        if getattr(dev, "capturing", False):
-            raise RuntimeError("start_averaging during a graph capture")
-        if self._averager is not None:
-            raise RuntimeError("an average is attached already: stop_averaging() first (or reset_averages())")
-        every, start_step = int(every), int(start_step)
-        if every < 1:
-            raise ValueError("every must be >= 1")
-        if start_step < 0:
-            raise ValueError("start_step must be >= 0")
+        self._not_capturing("start_averaging")
+        self._make_way("_averager", "an average is attached already: stop_averaging() first (or reset_averages())")
+        every, start_step = self._cadence(every, start_step)
         self._averager = Averager(dev, dev.mean_create(every, start_step), every, start_step)
 
     def _avg(self):
@@ -615,7 +584,7 @@ class FluidSimulator:
         from .runtime import Field
         avg = self._avg()
         dev = self._dev
-        if getattr(dev, "capturing", False):
+        if self._capturing():
             raise FsError("mean_fields / mean_flow_stats during a graph capture: they allocate and download")
         v, p = Field(dev, 2), Field(dev, 1)      # (not dev.alloc: scratch fields stay out of the ghost-row bookkeeping state of the tapes)
         dev.mean_finalize(avg.mean, v, p)
@@ -635,13 +604,7 @@ class FluidSimulator:
     def stop_averaging(self):
         """Detach the average and free its device memory; the cached graphs and tapes that hold its launch are freed first.  Nothing is kept
         on the host: call averages() before.  Inside a graph capture the device memory is released when the capture ends."""
-        avg = self._averager
-        if avg is None:
-            return
-        if not getattr(self._dev, "capturing", False):      # (inside a capture no graph can be freed: theirs stay cached, never matched again)
-            self._drop_cached(avg.token)
-        self._dev.mean_free(avg.mean)
-        self._averager = None
+        self._detach(self, "_averager", "stop_averaging")
 
     # -- tracer particles (new): pathlines and streaklines advanced on the device ------------------------------------------------------
     def seed_tracers(self, seeds, respawn=True, max_age=0, sort_every=0, tau=None, gravity=(0.0, 0.0), deposits=False):
@@ -674,10 +637,9 @@ class FluidSimulator:
         cell with deposits.  gravity or deposits without tau raise ValueError.  tracers() gains "u", "w" and "tau"."""
         from ._lib import FsError
         dev, s = self._dev, self._solver
-        if getattr(dev, "capturing", False):
-            raise RuntimeError("seed_tracers during a graph capture")
-        if self._tracers is not None:
-            raise RuntimeError("a tracer set is attached already: stop_tracers() first")
+        # (through the class: the tests check the refusal on slabs with an object that is no FluidSimulator)
+        FluidSimulator._not_capturing(self, "seed_tracers")
+        FluidSimulator._make_way(self, "_tracers", "a tracer set is attached already: stop_tracers() first")
         if dev.nranks > 1:
             raise FsError("tracer particles need a single-GPU context: on slabs they would have to migrate between ranks (not implemented)")
         max_age, sort_every = int(max_age), int(sort_every)
@@ -724,8 +686,7 @@ class FluidSimulator:
     def sort_tracers(self):
         """Sort the particle slots by cell on the device now (DeviceBase.tracer_sort): what seed_tracers(sort_every=K) does every K steps.
         Nothing observable changes, and the cached graphs stay valid.  Not allowed during a graph capture."""
-        if getattr(self._dev, "capturing", False):
-            raise RuntimeError("sort_tracers during a graph capture")
+        self._not_capturing("sort_tracers")
         self._trc().sort()
 
     def tracer_fields(self):
@@ -733,8 +694,7 @@ class FluidSimulator:
         int64 (X, Y), the sum of their ages in steps (fs.tracers.residence_map(count, age_sum, dt) is the residence-time map); "steps":
         steps since seed_tracers()}.  Exact and repeatable (integer atomics); 12 bytes per cell on the device for the call and in the
         download.  Not allowed during a graph capture."""
-        if getattr(self._dev, "capturing", False):
-            raise RuntimeError("tracer_fields during a graph capture")
+        self._not_capturing("tracer_fields")
         tr = self._trc()
         count, age_sum = tr.dev.tracer_fields(tr.set)
         return {"count": count, "age_sum": age_sum, "steps": tr.dev.tracer_read_steps(tr.set)}
@@ -750,8 +710,7 @@ class FluidSimulator:
     def tracer_deposits(self):
         """Wall hits per wall cell since seed_tracers(tau=..., deposits=True): int32 (X, Y), exact and repeatable (integer atomics).  A
         particle that hits a wall is counted in the wall cell it would have entered, whether it respawns or not."""
-        if getattr(self._dev, "capturing", False):
-            raise RuntimeError("tracer_deposits during a graph capture")
+        self._not_capturing("tracer_deposits")
         tr = self._trc()
         if not tr.deposits:
             raise RuntimeError("the tracer set records no deposits: seed_tracers(tau=..., deposits=True)")
@@ -765,17 +724,12 @@ class FluidSimulator:
         Passive and inertial sets alike.  tracer_accumulation() returns the result.  Raises without a tracer set, while an accumulation is
         attached already and during a graph capture."""
         dev = self._dev
-        if getattr(dev, "capturing", False):
-            raise RuntimeError("accumulate_tracers during a graph capture")
+        self._not_capturing("accumulate_tracers")
         tr = self._trc()
         if tr.accumulation is not None:
             raise RuntimeError("an accumulation is attached already: stop_tracer_accumulation() first (or reset_tracer_accumulation())")
-        every, start_step = int(every), int(start_step)
-        if every < 1:
-            raise ValueError("every must be >= 1")
-        if start_step < 0:
-            raise ValueError("start_step must be >= 0")
-        tr.accumulation = TracerAccumulation(dev.tracer_accum_create(tr.set, every, start_step), every, start_step)
+        every, start_step = self._cadence(every, start_step)
+        tr.accumulation = TracerAccumulation(dev.tracer_accum_create(tr.set, every, start_step), every, start_step, dev=dev)
 
     def _tacc(self):
         tr = self._trc()
@@ -788,8 +742,7 @@ class FluidSimulator:
         summed over the sampled steps; "age_sum": int64 (X, Y), the sum of their ages (fs.tracers.residence_map(occupancy, age_sum, dt):
         the mean residence time, fs.tracers.concentration(occupancy, samples): the mean particles per cell); "samples": sampled steps;
         "steps": steps since accumulate_tracers()}.  Not allowed during a graph capture."""
-        if getattr(self._dev, "capturing", False):
-            raise RuntimeError("tracer_accumulation during a graph capture")
+        self._not_capturing("tracer_accumulation")
         tr = self._tacc()
         occ, age, launches, samples = tr.dev.tracer_accum_read(tr.set)
         return {"occupancy": occ, "age_sum": age, "samples": samples, "steps": launches}
@@ -802,26 +755,14 @@ class FluidSimulator:
     def stop_tracer_accumulation(self):
         """Detach the accumulation and free its device memory; the cached graphs that hold its launch are freed first.  Nothing is kept
         on the host: call tracer_accumulation() before.  Inside a graph capture the device memory is released when the capture ends."""
-        tr = self._tracers
-        if tr is None or tr.accumulation is None:
-            return
-        if not getattr(self._dev, "capturing", False):      # (inside a capture no graph can be freed: theirs stay cached, never matched again)
-            self._drop_cached(tr.accumulation.token)
-        self._dev.tracer_accum_free(tr.set)
-        tr.accumulation = None
+        if self._tracers is not None:
+            self._detach(self._tracers, "accumulation", "stop_tracer_accumulation")
 
     def stop_tracers(self):
         """Detach the tracer set (and its accumulation) and free its device memory; the cached graphs that hold its launch are freed
         first.  Nothing is kept on the host: call tracers() before.  Inside a graph capture the device memory is released when the capture
         ends."""
-        tr = self._tracers
-        if tr is None:
-            return
-        self.stop_tracer_accumulation()
-        if not getattr(self._dev, "capturing", False):      # (inside a capture no graph can be freed: theirs stay cached, never matched again)
-            self._drop_cached(tr.token)
-        self._dev.tracer_free(tr.set)
-        self._tracers = None
+        self._detach(self, "_tracers", "stop_tracers")
 
     # -- visualisation (fs/fluid_simulator.py:22-58): device kernels; like the reference these return the image FIELD ----
     def get_norm_field(self):

@@ -4,6 +4,8 @@ The recording itself is a device launch per step (csrc/fs_history.h, include/fs_
 FluidSimulator.record_history / history / stop_history."""
 import numpy as np
 
+from .riders import Rider, ring_room
+
 FLUID, WALL = 0, 1
 # direction wall -> fluid of a face: (di, dj) of the fluid cell seen from the wall cell, in the order of the `dir` codes of fs_history_create
 DIRS = ((1, 0), (-1, 0), (0, 1), (0, -1))
@@ -70,9 +72,10 @@ def dominant_frequency(signal, dt):
     return int(np.argmax(spec)) / (n * float(dt))
 
 
-class Recorder:
+class Recorder(Rider):
     """One history of a FluidSimulator (record_history): the device ring, the records drained from it so far, and how many record launches
     have been issued - from which the simulator knows how many steps it may run before the ring is full (room)."""
+    stop_in_capture, keeps_last, replaces_attached = False, True, True
 
     def __init__(self, dev, hist, probes, box, every, start_step, dt):
         self.dev, self.hist, self.probes, self.box = dev, hist, probes, box
@@ -87,7 +90,16 @@ class Recorder:
 
     def room(self):
         """Steps that may run before the next one would find the ring full: the ring holds issued // every - drained records."""
-        return (self.hist.capacity + self.drained + 1) * self.every - 1 - self.issued
+        return ring_room(self.issued, self.every, 0, self.hist.capacity, self.drained)
+
+    def launch(self, sim):
+        self._make_room()
+        v, p = sim._solver.get_fields()[:2]
+        self.dev.history_record(self.hist, sim._solver.dx, v, p)
+        self.issued += 1
+
+    def free(self):
+        self.dev.history_free(self.hist)
 
     def drain(self):
         forces, values, launches, dropped = self.dev.history_read(self.hist)

@@ -6,6 +6,7 @@ FluidSimulator.track_body / body_loads / body_surface / stop_body."""
 import numpy as np
 
 from .history import DIRS, WALL
+from .riders import Rider, ring_room, samples_after
 
 RECORD = ("pressure_x", "pressure_y", "viscous_x", "viscous_y", "moment_pressure", "moment_viscous")      # a device record, in order
 SUMS = ("p", "pp", "tau", "tautau")                                                                         # the per-face planes, in order
@@ -61,9 +62,10 @@ def surface_statistics(sums, samples):
     return pm, np.sqrt(np.maximum(sums[1] / samples - pm * pm, 0.0)), tm, np.sqrt(np.maximum(sums[3] / samples - tm * tm, 0.0))
 
 
-class Tracker:
+class Tracker(Rider):
     """One body tracker of a FluidSimulator (track_body): the device object, the records drained from its ring so far, and how many
     launches have been issued - from which the simulator knows how many steps it may run before the ring is full (room)."""
+    stop_in_capture, keeps_last = False, True
 
     def __init__(self, dev, loads, faces, box, centre, every, start_step, dt):
         self.dev, self.loads, self.faces, self.box, self.centre = dev, loads, np.asarray(faces, np.int32).reshape(-1, 3), box, centre
@@ -81,14 +83,21 @@ class Tracker:
 
     def _sampled(self, launches):
         """Samples among the first `launches` launches."""
-        return max(0, launches - self.start_step) // self.every
+        return samples_after(launches, self.every, self.start_step)
 
     def room(self):
         """Steps that may run before the next sampling one would find the ring full."""
-        held = self._sampled(self.issued) - self._sampled(self.base) - self.drained
-        free = self.loads.capacity - held
-        nxt = self.start_step + (self._sampled(self.issued) + free + 1) * self.every      # the launch count whose sample would not fit
-        return nxt - 1 - self.issued
+        return ring_room(self.issued, self.every, self.start_step, self.loads.capacity, self._sampled(self.base) + self.drained)
+
+    def launch(self, sim):
+        self._make_room()
+        s = sim._solver
+        v, p = s.get_fields()[:2]
+        self.dev.loads_record(self.loads, s.dx, 1.0 / s.re, v, p)
+        self.issued += 1
+
+    def free(self):
+        self.dev.loads_free(self.loads)
 
     def drain(self):
         rec, launches, samples, dropped = self.dev.loads_read(self.loads)
@@ -100,9 +109,17 @@ class Tracker:
             raise RuntimeError(f"{dropped} body-load record(s) were dropped: the ring of {self.loads.capacity} records filled up "
                                "(launches replayed outside FluidSimulator.run / step)")
 
-    def restore(self, sums, launches, samples):
+    def checkpoint(self):
+        self.drain()
+        return {"loads.sums": self.sums(), "loads.launches": np.array(self.issued), "loads.samples": np.array(self.samples),
+                "loads.box": np.array(self.box), "loads.center": np.array(self.centre, np.float64), "loads.every": np.array(self.every),
+                "loads.start": np.array(self.start_step)}
+
+    def restore(self, sums, launches=None, samples=None):
         """Continue where a checkpoint stopped: its (4, F) sums and both counters go to the device; the records of this ring are numbered
-        on from `launches`."""
+        on from `launches`.  restore(z): the three from the mapping checkpoint() wrote."""
+        if launches is None:
+            sums, launches, samples = sums["loads.sums"], int(sums["loads.launches"]), int(sums["loads.samples"])
         self.dev.loads_sums(self.loads, write=sums, launches=launches, samples=samples)
         self.issued = self.base = int(launches)
         self.samples = int(samples)

@@ -1,0 +1,715 @@
+"""Device side of what rides the step and of the diagnostics (new; the reference has none): flow statistics, the per-step history, the
+body surface loads, the time averages and the tracer particles.  Two mixins: RideOps is the backend-agnostic host logic fs.runtime.DeviceBase
+inherits (slab partition, combination over ranks, argument checks, the op log of a logged period), NativeRideOps the `_p_*` primitives
+fs.runtime.Device binds to libfs_hip.so; the stand-in devices of the CPU tests override those.  fs.runtime re-exports every name here."""
+import ctypes
+import itertools
+
+import numpy as np
+
+from . import _lib
+
+_serials = itertools.count(1)      # identities for life of fields and device objects (id() is recycled)
+
+
+class _Handle:
+    """A device object of a rider: `_h`, the library's handle (None once freed), and `serial`, its name in signatures and op keys."""
+
+    def __init__(self, h):
+        self._h, self.serial = h, next(_serials)
+
+
+class TracerSet(_Handle):
+    """A device tracer set (DeviceBase.tracer_create): handle, particle count, respawn, max_age."""
+
+    def __init__(self, h, n, respawn, max_age):
+        super().__init__(h)
+        self.n, self.respawn, self.max_age = n, respawn, max_age
+        self.inertial, self.deposits, self.gravity, self.tau, self.alpha = False, False, (0.0, 0.0), None, None      # (tracer_create_inertial)
+        self.accum = None          # TracerAccum while tracer_accum_create's planes are attached
+
+
+class TracerAccum(_Handle):
+    """The accumulated-occupancy planes of a tracer set (DeviceBase.tracer_accum_create): every, start and an identity of its own."""
+
+    def __init__(self, tr, every, start):
+        super().__init__(None)      # (no handle of its own: the planes hang on the set's)
+        self.set, self.every, self.start = tr, every, start
+
+
+class Mean(_Handle):
+    """Device accumulators of a time average (DeviceBase.mean_create): handle, every, start."""
+
+    def __init__(self, h, every, start):
+        super().__init__(h)
+        self.every, self.start = every, start
+
+
+class Loads(_Handle):
+    """A device body tracker (DeviceBase.loads_create): handle (None on a slab that owns no face), the global face count, which faces
+    this rank owns, capacity, every, start."""
+
+    def __init__(self, h, nfaces, mine, capacity, every, start):
+        super().__init__(h)
+        self.nfaces, self.mine, self.capacity, self.every, self.start = nfaces, np.asarray(mine, np.int64), capacity, every, start
+
+
+class History(_Handle):
+    """A device history ring (DeviceBase.history_create): handle, the global probe count, which of them this rank owns, capacity, every."""
+
+    def __init__(self, h, nprobes, mine, capacity, every):
+        super().__init__(h)
+        self.nprobes, self.mine, self.capacity, self.every = nprobes, np.asarray(mine, np.int64), capacity, every
+
+
+class RideOps:
+    """flow_stats and the history_* / loads_* / mean_* / tracer_* calls of DeviceBase."""
+
+    # (The tracer calls reach these through the class - RideOps._host_only(self, ...) - as they always reached _tracer_host_call: the CPU
+    #  tests check their refusals on objects that are no devices.)
+    def _host_only(self, message):
+        """Refuse during a graph capture what allocates, downloads or synchronises: FsError(message)."""
+        if getattr(self, "capturing", False):
+            raise _lib.FsError(message)
+
+    def _single_gpu_only(self):
+        if self.nranks > 1:
+            raise _lib.FsError("tracer particles need a single-GPU context: on slabs they would have to migrate between ranks (not implemented)")
+
+    def _tracer_host_call(self, what):
+        RideOps._host_only(self, f"{what} during a graph capture")
+        RideOps._single_gpu_only(self)
+
+    def _ride(self, name, args=None):
+        """A rider's launch behind the step.  Not a _run: no flush, no exchange, no ghost row, writes no field - in a logged period a kernel
+        op of its own.  args=None: a placeholder that launches nothing and keeps the period's shape."""
+        if self._oplog is not None:
+            self._oplog.append(("k", name, args or (), ()))
+        if args is not None:
+            self._p_kernel(name, *args)
+
+    @staticmethod
+    def _limit_of(v):
+        """The limit a deferred limit_field of v still owes, for the kernels that apply it to the values they read; 0: none."""
+        return float(v.pending_limit) if v.pending_limit is not None else 0.0
+
+    @staticmethod
+    def _check_counters(launches, samples):
+        launches, samples = int(launches), int(samples)
+        if not 0 <= samples <= launches:
+            raise ValueError("counters must satisfy 0 <= samples <= launches")
+        return launches, samples
+
+    @staticmethod
+    def _check_cadence(every, start, capacity=None):
+        every, start = int(every), int(start)
+        if capacity is not None and (every < 1 or start < 0 or int(capacity) < 1):
+            raise ValueError("every and capacity must be >= 1 and start >= 0")
+        if every < 1 or start < 0:
+            raise ValueError("every must be >= 1 and start >= 0")
+        return every, start
+
+    def _adopt(self, handle, obj):
+        """Register a device object's handle under its serial (its name in the op keys of a logged period) -> obj."""
+        if handle is not None:
+            self._handle_serial[id(handle)] = obj.serial
+        return obj
+
+    def _release(self, obj, free):
+        if obj._h is not None:
+            self._handle_serial.pop(id(obj._h), None)
+            free(obj._h)
+            obj._h = None
+
+    # slots of fs_flow_stats (include/fs_hip.h), in ABI order; those of _STAT_MAX combine by maximum, the others by sum
+    STAT_SLOTS = ("fluid_cells", "sum_s2", "sum_om2", "sum_dv2", "max_s2", "max_a", "max_abs_dv", "nonfinite", "force_x", "force_y")
+    _STAT_MAX = (4, 5, 6)
+
+    def flow_stats(self, dx, v, p, box=None):
+        """{slot: value} of fs_flow_stats over the GLOBAL grid (include/fs_hip.h): kinetic-energy, enstrophy and divergence sums, maxima,
+        the non-finite count and the pressure force on the wall cells of `box` = (x0, y0, x1, y1) in global cells (half-open; None: no force).
+        Across slabs the sums add and the maxima take the maximum; a NaN maximum on any rank makes the global one NaN.  Alters no field.
+        A limit_field v still owes (limit_field) stays deferred while the buffer's flag is down - the pass would change no cell, and the
+        solver's buffers keep the state their captured graphs expect; with the flag up it is launched first, as a download would.  Not
+        allowed during a graph capture (FsError; the library refuses as well)."""
+        self._host_only("flow_stats during a graph capture: the statistics are a download (sample between captures / replays)")
+        # Skipping the owed pass relies on the flag being conservative - up whenever a stored cell may have x*x + y*y > 99 (csrc/fs_device.h,
+        # "hot" flag: raised by every kernel that stores such a velocity, by uploads and unpacked ghost rows).  A deferred pass has
+        # limit * limit > 99.01 (limit_field), and fs_limit_field exits on the same flag words fs_field_hot reads: with the flag down the
+        # pass changes no cell.  Whoever changes the flag's rules must keep this true or flush unconditionally here.
+        if v.pending_limit is not None and self.field_hot(v):
+            self.flush_limit(v)
+        if self.nranks > 1:
+            stale = [f for f in (v, p) if f.valid < 1]
+            if stale:
+                self.exchange_many(stale)
+        if box is not None:
+            box = tuple(int(b) for b in box)
+            if len(box) != 4:
+                raise ValueError("box must be (x0, y0, x1, y1)")
+        s = [float(x) for x in self._p_flow_stats(dx, v._h, p._h, box)]
+        if self.nranks > 1:
+            mx = [s[k] for k in self._STAT_MAX]
+            sums = [k for k in range(len(s)) if k not in self._STAT_MAX]
+            tot = self._p_allreduce([s[k] for k in sums] + [1.0 if m != m else 0.0 for m in mx])     # (+ per maximum: ranks that hold NaN)
+            for k, x in zip(sums, tot):
+                s[k] = x
+            top = self._p_max_over_ranks([0.0 if m != m else m for m in mx])      # (a plain maximum would drop NaN: it is carried by the sum)
+            for n, (k, x) in enumerate(zip(self._STAT_MAX, top)):
+                s[k] = float("nan") if tot[len(sums) + n] > 0 else float(x)
+        return dict(zip(self.STAT_SLOTS, s))
+
+    # ---- per-step history (include/fs_hip.h fs_history_*): probe values and body faces gathered by one launch per step ------------------
+    def history_create(self, points, faces, capacity, every):
+        """A device ring of `capacity` records for FluidSimulator.record_history: points (P, 2) global probe cells, faces (n, 3) global
+        (x, y, dir) of fs.history.body_faces.  A slab keeps the probes and faces whose cell lies in its owned rows: the record reads no ghost
+        row, needs no exchange and sits in a tape as an ordinary kernel op.  Not allowed during a graph capture."""
+        from .history import owned
+        self._host_only("history_create during a graph capture")
+        points = np.asarray(points, np.int32).reshape(-1, 2)
+        faces = np.asarray(faces, np.int32).reshape(-1, 3)
+        mine = owned(points, self.y0, self.nyl)
+        h = self._p_history_create(np.ascontiguousarray(points[mine]), np.ascontiguousarray(faces[owned(faces, self.y0, self.nyl)]),
+                                   int(capacity), int(every))
+        return self._adopt(h, History(h, len(points), mine, int(capacity), int(every)))
+
+    def history_record(self, hist, dx, v, p):
+        """Append the record of the current v and p (every `every`-th call).  A limit_field v still owes stays deferred: the kernel limits
+        the probe values as the pass would store them.  Not a _run: no flush, no exchange, no ghost row - on slabs a kernel op of its own
+        in the logged period (writes no field)."""
+        self._ride("history_record", (hist._h, float(dx), self._limit_of(v), v._h, p._h))
+
+    def history_read(self, hist):
+        """Empty the ring -> (forces (n, 2), probes (n, P, 3): u, w, p; launches so far, records dropped).  Across slabs the forces add
+        and each probe comes from the rank that owns it (the others contribute -0.0, which leaves every value's bits alone).  Collective on
+        slab runs; not allowed during a graph capture."""
+        self._host_only("history_read during a graph capture: the ring is read between captures / replays")
+        rec, launches, dropped = self._p_history_read(hist._h, len(hist.mine), hist.capacity)
+        n = rec.shape[0]
+        if self.nranks > 1:
+            if not self._p_same_over_ranks([n, launches]):
+                raise RuntimeError("history_read: the ranks hold different numbers of records")
+            full = np.full((n + 1, 2 + 3 * hist.nprobes), -0.0)        # (+ one row: the ranks' dropped counts)
+            full[:n, :2] = rec[:, :2]
+            cols = (2 + 3 * np.repeat(hist.mine, 3) + np.tile(np.arange(3), len(hist.mine))).astype(np.int64)
+            full[:n, cols] = rec[:, 2:]
+            full[n, 0] = float(dropped)
+            tot = self._p_allreduce_array(full.ravel()).reshape(full.shape)
+            dropped, rec = int(tot[n, 0]), tot[:n]
+        return rec[:, :2].copy(), rec[:, 2:].reshape(n, hist.nprobes, 3).copy(), int(launches), int(dropped)
+
+    def history_free(self, hist):
+        self._release(hist, self._p_history_free)
+
+    # ---- body surface loads (include/fs_hip.h fs_loads_*): force, moment and per-face pressure / shear sums, one launch sequence per step -----
+    LOADS_REC = 6       # Fpx, Fpy, Fvx, Fvy, Mp, Mv
+    LOADS_SUMS = 4      # S_p, S_pp, S_t, S_tt per face
+
+    def loads_create(self, faces, centre, capacity, every=1, start=0):
+        """A device body tracker for FluidSimulator.track_body: faces (F, 3) global (x, y, dir) of fs.history.body_faces, F >= 1, centre
+        (cx, cy) in cell units, a ring of `capacity` records.  Launch n (from 0) of loads_record samples when n + 1 > start and
+        (n + 1 - start) % every == 0.  A slab keeps the faces whose fluid cell lies in its owned rows: the launch reads no ghost row, needs
+        no exchange and sits in a tape as an ordinary kernel op.  Not allowed during a graph capture."""
+        from .history import owned
+        self._host_only("loads_create during a graph capture")
+        faces = np.asarray(faces, np.int32).reshape(-1, 3)
+        centre = np.asarray(centre, np.float64).ravel()
+        capacity = int(capacity)
+        if len(faces) < 1:
+            raise ValueError("a body tracker needs at least one face")
+        if centre.shape != (2,) or not np.all(np.isfinite(centre)):
+            raise ValueError("centre must be two finite numbers (cx, cy)")
+        every, start = self._check_cadence(every, start, capacity)
+        mine = owned(faces, self.y0, self.nyl)
+        # (a slab whose rows touch no face of the body still needs a handle: the counters advance on every rank)
+        h = self._p_loads_create(np.ascontiguousarray(faces[mine]), centre, capacity, every, start) if len(mine) else None
+        return self._adopt(h, Loads(h, len(faces), mine, capacity, every, start))
+
+    def loads_record(self, lo, dx, inv_re, v, p):
+        """One launch sequence of the tracker on the current v and p; whether it samples is decided on the device.  A limit_field v still
+        owes stays deferred: the kernel limits the values as the pass would store them.  Not a _run: no flush, no exchange, no ghost row - on
+        slabs a kernel op of its own in the logged period (writes no field)."""
+        if lo._h is None:
+            # this slab owns no face of the body: nothing to launch, but the logged period keeps the shape it has on the other ranks
+            # (tape_period compiles a tape only when all ranks' tapes have the same length)
+            return self._ride("loads_idle")
+        self._ride("loads_record", (lo._h, float(dx), float(inv_re), self._limit_of(v), v._h, p._h))
+
+    def loads_read(self, lo):
+        """Empty the ring -> (records (n, 6): Fpx, Fpy, Fvx, Fvy, Mp, Mv; launches, samples, records dropped).  Across slabs the records
+        add, and the ranks that hold faces must agree on the counters (a slab without a face of the body holds none).  Collective on slab
+        runs; not allowed during a graph capture."""
+        self._host_only("loads_read during a graph capture: the ring is read between captures / replays")
+        if lo._h is not None:
+            rec, launches, samples, dropped = self._p_loads_read(lo._h, lo.capacity)
+        else:
+            rec, launches, samples, dropped = np.zeros((0, self.LOADS_REC)), 0, 0, 0
+        n = rec.shape[0]
+        if self.nranks > 1:
+            top = [int(x) for x in self._p_max_over_ranks([n, launches, samples])]
+            odd = lo._h is not None and top != [n, launches, samples]
+            n, launches, samples = top
+            full = np.full((n + 1, self.LOADS_REC), -0.0)        # (+ one row: the ranks' dropped counts, and who disagrees)
+            if lo._h is not None and not odd:
+                full[:n] = rec
+            full[n, 0], full[n, 1] = float(dropped), float(odd)
+            tot = self._p_allreduce_array(full.ravel()).reshape(full.shape)
+            if tot[n, 1] > 0:
+                raise RuntimeError("loads_read: the ranks hold different launch / sample / record counts")
+            dropped, rec = int(tot[n, 0]), tot[:n]
+        return rec.copy(), int(launches), int(samples), int(dropped)
+
+    def loads_sums(self, lo, write=None, launches=None, samples=None):
+        """-> the per-face sums, float64 (4, F): S_p, S_pp, S_t, S_tt in the order of the GLOBAL face list.  On slabs every face comes from
+        the rank that owns it (the others contribute -0.0, which leaves every value's bits alone; collective).  write=(4, F) array with
+        launches, samples: the inverse (resume) - each slab keeps its own faces.  Not allowed during a graph capture."""
+        self._host_only("loads_sums during a graph capture")
+        if write is not None:
+            write = np.asarray(write, np.float64)
+            if write.shape != (self.LOADS_SUMS, lo.nfaces):
+                raise ValueError(f"expected sums of shape {(self.LOADS_SUMS, lo.nfaces)}, got {write.shape}")
+            launches, samples = self._check_counters(launches, samples)
+            if lo._h is not None:
+                self._p_loads_sums_write(lo._h, np.ascontiguousarray(write[:, lo.mine]), launches, samples)
+            return None
+        full = np.full((self.LOADS_SUMS, lo.nfaces), -0.0) if self.nranks > 1 else np.zeros((self.LOADS_SUMS, lo.nfaces))
+        if lo._h is not None:
+            full[:, lo.mine] = self._p_loads_sums_read(lo._h, len(lo.mine))
+        if self.nranks > 1:
+            full = self._p_allreduce_array(full.ravel()).reshape(full.shape)
+        return full
+
+    def loads_reset(self, lo):
+        """Sums and sample count to zero; the launch count runs on.  Not allowed during a graph capture."""
+        self._host_only("loads_reset during a graph capture")
+        if lo._h is not None:
+            self._p_loads_reset(lo._h)
+
+    def loads_free(self, lo):
+        self._release(lo, self._p_loads_free)
+
+    # ---- time averages (include/fs_hip.h fs_mean_*): seven planes of double sums over the owned rows, fed by one launch per step -----------
+    MEAN_PLANES = 7     # S_u, S_w, S_p, S_uu, S_ww, S_uw, S_pp (fs.averages.SUMS)
+
+    def mean_create(self, every=1, start=0):
+        """Device accumulators for FluidSimulator.start_averaging: 56 bytes per owned cell, zeroed.  Launch n (from 0) of mean_accumulate
+        samples when n + 1 > start and (n + 1 - start) % every == 0.  Not allowed during a graph capture."""
+        self._host_only("mean_create during a graph capture")
+        every, start = self._check_cadence(every, start)
+        h = self._p_mean_create(every, start)
+        return self._adopt(h, Mean(h, every, start))
+
+    def mean_accumulate(self, mean, v, p):
+        """Add the current v and p to the sums when this launch is a sampling one; the counters advance on the device.  A limit_field v
+        still owes stays deferred: the kernel limits the values as the pass would store them.  Not a _run: no flush, no exchange, no ghost
+        row - on slabs a kernel op of its own in the logged period (writes no field)."""
+        self._ride("mean_accumulate", (mean._h, self._limit_of(v), v._h, p._h))
+
+    def mean_read(self, mean, local=False):
+        """-> (sums float64 (7, X, Y) in the order of fs.averages.SUMS, launches, samples).  On slabs the ranks' owned rows are assembled
+        like Field.to_numpy (allgather; local=True: this slab's rows only) and all ranks must report the same counters.  Collective on
+        slab runs; not allowed during a graph capture."""
+        self._host_only("mean_read during a graph capture: the sums are a download (read between captures / replays)")
+        mine, launches, samples = self._p_mean_read(mean._h)
+        launches, samples = int(launches), int(samples)
+        if self.nranks > 1 and not self._p_same_over_ranks([launches, samples]):
+            raise RuntimeError("mean_read: the ranks hold different launch / sample counts")
+        if local or self.nranks == 1:
+            return mine, launches, samples
+        if self.allgather is None:
+            raise RuntimeError("mean_read() on a slab needs runtime.init(allgather=...) or local=True")
+        return np.concatenate(self.allgather(mine), axis=2), launches, samples
+
+    def mean_write(self, mean, sums, launches, samples):
+        """Restore what mean_read returned (resume): sums is the GLOBAL (7, X, Y) array, each slab keeps its owned rows."""
+        self._host_only("mean_write during a graph capture")
+        sums = np.asarray(sums, np.float64)
+        if sums.shape != (self.MEAN_PLANES, self.nx, self.ny):
+            raise ValueError(f"expected sums of shape {(self.MEAN_PLANES, self.nx, self.ny)}, got {sums.shape}")
+        launches, samples = self._check_counters(launches, samples)
+        self._p_mean_write(mean._h, np.ascontiguousarray(sums[:, :, self.y0:self.y0 + self.nyl]), launches, samples)
+
+    def mean_reset(self, mean):
+        """Sums and sample count to zero; the launch count runs on.  Not allowed during a graph capture."""
+        self._host_only("mean_reset during a graph capture")
+        self._p_mean_reset(mean._h)
+
+    def mean_finalize(self, mean, v_out, p_out):
+        """The means as fields: S_u / n, S_w / n into the 2-channel v_out, S_p / n into the 1-channel p_out (n = samples, > 0), wall cells
+        0, in the fields' precision.  Owned rows only: on slabs the targets' ghost rows are stale afterwards (valid = 0), and whatever reads
+        them exchanges first.  Not allowed during a graph capture."""
+        self._host_only("mean_finalize during a graph capture")
+        for f in (v_out, p_out):
+            f.pending_limit = f.pending_clamp = None      # (every owned cell is overwritten)
+        self._p_mean_finalize(mean._h, v_out._h, p_out._h)
+        for f in (v_out, p_out):
+            f.valid = 0 if self.nranks > 1 else self.halo
+            f.user_data = True
+            f.static_id = next(_serials)
+
+    def mean_free(self, mean):
+        self._release(mean, self._p_mean_free)
+
+    # ---- tracer particles (include/fs_hip.h fs_tracer_*): N particles in double cell coordinates, advanced by one launch per step -------
+    def tracer_create(self, seeds, respawn=True, max_age=0):
+        """A device tracer set for FluidSimulator.seed_tracers: seeds float64 (N, 2) in cell units, N >= 1, inside the domain (whether
+        the cells are fluid is fs.tracers.check_seeds' business).  52 bytes per particle (+ 36 and 4 per sort bin once tracer_sort has
+        run).  Single-context grids only (FsError on a slab); not allowed during a graph capture."""
+        RideOps._tracer_host_call(self, "tracer_create")
+        seeds = np.ascontiguousarray(seeds, np.float64)
+        if seeds.ndim != 2 or seeds.shape[1] != 2 or len(seeds) < 1:
+            raise ValueError(f"seeds must have shape (N, 2) with N >= 1, got {seeds.shape}")
+        max_age = int(max_age)
+        if max_age < 0:
+            raise ValueError("max_age must be >= 0")
+        h = self._p_tracer_create(seeds, bool(respawn), max_age)
+        return self._adopt(h, TracerSet(h, len(seeds), bool(respawn), max_age))
+
+    def tracer_advance(self, tr, h, v):
+        """One midpoint step h = dt / dx of every alive particle in the velocity field v; the launch counter advances on the device.  A
+        limit_field v still owes stays deferred: the kernel limits the corner values as the pass would store them.  Not a _run: no flush,
+        no exchange (writes no field)."""
+        self._ride("tracer_advance", (tr._h, float(h), self._limit_of(v), v._h))
+
+    def tracer_read(self, tr, raw=False):
+        """-> {"x", "y": float64 (N,), "age", "status", "respawns": int32 (N,), "seeds": float64 (N, 2), "steps": launches so far}: one
+        download, in SEED order (entry k belongs to seed k) whatever tracer_sort has done on the device.  raw=True: x, y, age, status
+        and respawns in the device's SLOT order instead, plus "id": int32 (N,), the seed index of the particle in each slot (the seeds
+        stay in seed order: the seed of slot k is seeds[id[k]]).  Not allowed during a graph capture."""
+        self._host_only("tracer_read during a graph capture: the state is a download (read between captures / replays)")
+        pos, ints, launches = self._p_tracer_read(tr._h, tr.n)
+        out = {"x": pos[0].copy(), "y": pos[1].copy(), "age": ints[0].copy(), "status": ints[1].copy(), "respawns": ints[2].copy(),
+               "seeds": np.ascontiguousarray(pos[2:4].T), "steps": int(launches)}
+        if raw:
+            ids = self._p_tracer_order(tr._h, tr.n)
+            for k in ("x", "y", "age", "status", "respawns"):
+                out[k] = out[k][ids]
+            out["id"] = ids
+        return out
+
+    def tracer_read_steps(self, tr):
+        """Launches of the advance so far (the "steps" of tracer_read) without the particle download."""
+        self._host_only("tracer_read during a graph capture: the state is a download (read between captures / replays)")
+        return int(self._p_tracer_read(tr._h, 0)[2])
+
+    def tracer_sort(self, tr):
+        """Reorder the particle slots on the device by cell (fs.tracers.sort_key: rows of bins SORT_BIN_CELLS cells wide; dead and
+        outside particles last) so that the advance gathers from neighbouring cache lines.  Changes nothing tracer_read() or any other
+        call shows, and no device address: graphs that hold the advance stay valid.  A handful of launches outside any graph (profiled
+        as tracer_sort_*); not allowed during a graph capture."""
+        RideOps._tracer_host_call(self, "tracer_sort")
+        self._p_tracer_sort(tr._h)
+
+    def tracer_order(self, tr):
+        """-> int32 (N,): the seed index of the particle in each device slot (arange(N) until the first tracer_sort)."""
+        RideOps._tracer_host_call(self, "tracer_order")
+        return self._p_tracer_order(tr._h, tr.n)
+
+    def tracer_fields(self, tr):
+        """-> (count int32 (X, Y), age_sum int64 (X, Y)): per cell, the number of alive particles inside it and the sum of their ages.
+        One launch with integer atomics (exact, repeatable) + the download; 12 bytes per cell of device memory during the call."""
+        RideOps._tracer_host_call(self, "tracer_fields")
+        return self._p_tracer_fields(tr._h)
+
+    def tracer_write(self, tr, state):
+        """Restore what tracer_read returned (checkpoints): the same keys, arrays of the set's N."""
+        self._host_only("tracer_write during a graph capture")
+        n = tr.n
+        seeds = np.asarray(state["seeds"], np.float64)
+        if seeds.shape != (n, 2):
+            raise ValueError(f"expected seeds of shape {(n, 2)}, got {seeds.shape}")
+        pos = np.empty((4, n), np.float64)
+        ints = np.empty((3, n), np.int32)
+        for row, key in ((0, "x"), (1, "y")):
+            a = np.asarray(state[key], np.float64)
+            if a.shape != (n,):
+                raise ValueError(f"expected {key} of shape {(n,)}, got {a.shape}")
+            pos[row] = a
+        pos[2], pos[3] = seeds[:, 0], seeds[:, 1]
+        for row, key in enumerate(("age", "status", "respawns")):
+            a = np.asarray(state[key])
+            if a.shape != (n,):
+                raise ValueError(f"expected {key} of shape {(n,)}, got {a.shape}")
+            ints[row] = a
+        if (ints[0] < 0).any() or (ints[2] < 0).any() or (ints[1] < 0).any() or (ints[1] > 3).any() or int(state["steps"]) < 0:
+            raise ValueError("tracer state: age, respawns and steps must be >= 0 and status in 0 .. 3")
+        self._p_tracer_write(tr._h, pos, ints, int(state["steps"]))
+
+    def tracer_draw(self, tr, rgb, color=(1.0, 1.0, 1.0)):
+        """Store `color` into pixel (floor x, floor y) of the 3-channel field rgb for every alive particle."""
+        r, g, b = (float(c) for c in color)
+        self._p_kernel("tracer_draw", tr._h, r, g, b, rgb._h)
+
+    # ---- inertial tracer sets, deposits, accumulated occupancy (include/fs_hip.h fs_tracer_create_inertial ... fs_tracer_accum_*) ---------
+    def tracer_create_inertial(self, seeds, alpha, tau, gravity=(0.0, 0.0), respawn=True, max_age=0, deposits=False):
+        """A device set of inertial particles for FluidSimulator.seed_tracers(tau=...): as tracer_create, plus alpha (N,) in (0, 1] (the
+        response of one step, fs.tracers.response(tau, dt)), tau (N,) finite and >= 0 in the solver's time units, gravity (gx, gy) in
+        velocity per time; deposits: the set owns an int32 plane that counts the wall hits per wall cell.  84 bytes per particle (+ 68 and
+        4 per sort bin once tracer_sort has run) and 4 per cell with deposits."""
+        RideOps._tracer_host_call(self, "tracer_create_inertial")
+        seeds = np.ascontiguousarray(seeds, np.float64)
+        if seeds.ndim != 2 or seeds.shape[1] != 2 or len(seeds) < 1:
+            raise ValueError(f"seeds must have shape (N, 2) with N >= 1, got {seeds.shape}")
+        n = len(seeds)
+        alpha, tau = np.ascontiguousarray(alpha, np.float64), np.ascontiguousarray(tau, np.float64)
+        if alpha.shape != (n,) or tau.shape != (n,):
+            raise ValueError(f"alpha and tau must have shape {(n,)}, got {alpha.shape} and {tau.shape}")
+        if not ((alpha > 0.0) & (alpha <= 1.0)).all():
+            raise ValueError("alpha must lie in (0, 1]")
+        if not (np.isfinite(tau) & (tau >= 0.0)).all():
+            raise ValueError("tau must be finite and >= 0")
+        gravity = tuple(float(g) for g in gravity)
+        if len(gravity) != 2 or not all(np.isfinite(g) for g in gravity):
+            raise ValueError("gravity must be two finite numbers (gx, gy)")
+        max_age = int(max_age)
+        if max_age < 0:
+            raise ValueError("max_age must be >= 0")
+        h = self._p_tracer_create_inertial(seeds, alpha, tau, gravity, bool(respawn), max_age, bool(deposits))
+        tr = TracerSet(h, n, bool(respawn), max_age)
+        tr.inertial, tr.deposits, tr.gravity, tr.tau, tr.alpha = True, bool(deposits), gravity, tau.copy(), alpha.copy()
+        return self._adopt(h, tr)
+
+    def tracer_read_vel(self, tr):
+        """-> (pu, pw) float64 (N,): the particle velocities of an inertial set in SEED order (one download)."""
+        RideOps._tracer_host_call(self, "tracer_read_vel")
+        if not getattr(tr, "inertial", False):
+            raise ValueError("not an inertial tracer set")
+        vel = self._p_tracer_read_vel(tr._h, tr.n)
+        return vel[0].copy(), vel[1].copy()
+
+    def tracer_write_vel(self, tr, pu, pw):
+        """Restore what tracer_read_vel returned (checkpoints; after tracer_write)."""
+        RideOps._tracer_host_call(self, "tracer_write_vel")
+        if not getattr(tr, "inertial", False):
+            raise ValueError("not an inertial tracer set")
+        vel = np.empty((2, tr.n), np.float64)
+        for row, (key, a) in enumerate((("u", pu), ("w", pw))):
+            a = np.asarray(a, np.float64)
+            if a.shape != (tr.n,):
+                raise ValueError(f"expected {key} of shape {(tr.n,)}, got {a.shape}")
+            vel[row] = a
+        self._p_tracer_write_vel(tr._h, vel)
+
+    def tracer_deposits(self, tr):
+        """-> int32 (X, Y): wall hits per wall cell since creation (a set created with deposits=True)."""
+        RideOps._tracer_host_call(self, "tracer_deposits")
+        if not getattr(tr, "deposits", False):
+            raise ValueError("the tracer set records no deposits (deposits=True)")
+        return self._p_tracer_deposits(tr._h)
+
+    def tracer_deposits_write(self, tr, plane):
+        """Restore what tracer_deposits returned (checkpoints)."""
+        RideOps._tracer_host_call(self, "tracer_deposits_write")
+        if not getattr(tr, "deposits", False):
+            raise ValueError("the tracer set records no deposits (deposits=True)")
+        plane = np.asarray(plane)
+        if plane.shape != (self.nx, self.ny) or (plane < 0).any():
+            raise ValueError(f"expected deposits >= 0 of shape {(self.nx, self.ny)}, got {plane.shape}")
+        self._p_tracer_deposits_write(tr._h, plane.astype(np.int32))
+
+    def tracer_accum_create(self, tr, every=1, start=0):
+        """Attach the accumulated-occupancy planes to a set (passive or inertial): 16 bytes per cell, zeroed.  With n advances since this
+        call before a step's, tracer_accum_add samples behind that step's advance when n + 1 > start and (n + 1 - start) % every == 0.
+        -> TracerAccum (one per set)."""
+        RideOps._tracer_host_call(self, "tracer_accum_create")
+        every, start = RideOps._check_cadence(every, start)
+        if getattr(tr, "accum", None) is not None:
+            raise RuntimeError("the tracer set has an accumulator already")
+        self._p_tracer_accum("create", tr._h, every, start)
+        tr.accum = TracerAccum(tr, every, start)
+        return tr.accum
+
+    def tracer_accum_add(self, tr):
+        """The accumulation launch behind tracer_advance (gated on the device; part of captured steps).  Not a _run: writes no field."""
+        self._ride("tracer_accum_add", (tr._h,))
+
+    def tracer_accum_read(self, tr):
+        """-> (occupancy int64 (X, Y), age_sum int64 (X, Y), launches, samples)."""
+        RideOps._tracer_host_call(self, "tracer_accum_read")
+        return self._p_tracer_accum_read(tr._h)
+
+    def tracer_accum_write(self, tr, occupancy, age_sum, launches, samples):
+        """Restore what tracer_accum_read returned (checkpoints; after tracer_write, which sets the launch count the phase hangs on)."""
+        RideOps._tracer_host_call(self, "tracer_accum_write")
+        occupancy, age_sum = np.asarray(occupancy), np.asarray(age_sum)
+        for name, a in (("occupancy", occupancy), ("age_sum", age_sum)):
+            if a.shape != (self.nx, self.ny) or (a < 0).any():
+                raise ValueError(f"expected {name} >= 0 of shape {(self.nx, self.ny)}, got {a.shape}")
+        launches, samples = RideOps._check_counters(launches, samples)
+        self._p_tracer_accum_write(tr._h, occupancy.astype(np.int64), age_sum.astype(np.int64), launches, samples)
+
+    def tracer_accum_reset(self, tr):
+        """Planes and sample count to zero; the phase of every / start runs on."""
+        RideOps._tracer_host_call(self, "tracer_accum_reset")
+        self._p_tracer_accum("reset", tr._h)
+
+    def tracer_accum_free(self, tr):
+        """Detach the accumulator (inside a capture the device memory is released when the capture ends)."""
+        if getattr(tr, "accum", None) is not None and tr._h is not None:
+            self._p_tracer_accum("free", tr._h)
+        tr.accum = None
+
+    def tracer_free(self, tr):
+        if tr._h is not None:
+            self._release(tr, self._p_tracer_free)       # (the library releases an attached accumulator with the set)
+            tr.accum = None
+
+
+class NativeRideOps:
+    """The primitives of RideOps on libfs_hip.so (self._ctx: the library's context)."""
+
+    def _p_flow_stats(self, dx, vh, ph, box):
+        out = (ctypes.c_double * len(self.STAT_SLOTS))()
+        b = None if box is None else (ctypes.c_int * 4)(*box)
+        _lib.call("fs_flow_stats", self._ctx, dx, vh, ph, b, out)
+        return list(out)
+
+    def _p_history_create(self, points, faces, capacity, every):
+        h = ctypes.c_void_p()
+        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if a.size else None
+        _lib.call("fs_history_create", self._ctx, len(points), ip(points), len(faces), ip(faces), capacity, every, ctypes.byref(h))
+        return h
+
+    def _p_history_read(self, h, nlocal, capacity):
+        out = np.empty((capacity, 2 + 3 * nlocal), np.float64)
+        n, launches, dropped = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_int()
+        _lib.call("fs_history_read", self._ctx, h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), capacity, ctypes.byref(n),
+                  ctypes.byref(launches), ctypes.byref(dropped))
+        return out[:n.value], launches.value, dropped.value
+
+    def _p_history_free(self, h):
+        if self._ctx is not None:
+            _lib.call("fs_history_free", self._ctx, h)
+
+    def _p_loads_create(self, faces, centre, capacity, every, start):
+        h = ctypes.c_void_p()
+        c = (ctypes.c_double * 2)(float(centre[0]), float(centre[1]))
+        _lib.call("fs_loads_create", self._ctx, len(faces), faces.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if faces.size else None, c,
+                  capacity, every, start, ctypes.byref(h))
+        return h
+
+    def _p_loads_read(self, h, capacity):
+        out = np.empty((capacity, self.LOADS_REC), np.float64)
+        n, launches, samples, dropped = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_int()
+        _lib.call("fs_loads_read", self._ctx, h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), capacity, ctypes.byref(n),
+                  ctypes.byref(launches), ctypes.byref(samples), ctypes.byref(dropped))
+        return out[:n.value], launches.value, samples.value, dropped.value
+
+    def _p_loads_sums_read(self, h, nlocal):
+        out = np.empty((self.LOADS_SUMS, nlocal), np.float64)
+        _lib.call("fs_loads_sums_read", self._ctx, h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        return out
+
+    def _p_loads_sums_write(self, h, sums, launches, samples):
+        a = np.ascontiguousarray(sums, np.float64)
+        _lib.call("fs_loads_sums_write", self._ctx, h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), launches, samples)
+
+    def _p_loads_reset(self, h):
+        _lib.call("fs_loads_reset", self._ctx, h)
+
+    def _p_loads_free(self, h):
+        if self._ctx is not None:
+            _lib.call("fs_loads_free", self._ctx, h)
+
+    def _p_mean_create(self, every, start):
+        h = ctypes.c_void_p()
+        _lib.call("fs_mean_create", self._ctx, every, start, ctypes.byref(h))
+        return h
+
+    def _p_mean_read(self, h):
+        out = np.empty((self.MEAN_PLANES, self.nyl, self.nx), np.float64)       # (the library's layout: x contiguous)
+        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
+        _lib.call("fs_mean_read", self._ctx, h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(launches), ctypes.byref(samples))
+        return out.transpose(0, 2, 1), launches.value, samples.value
+
+    def _p_mean_write(self, h, sums, launches, samples):
+        a = np.ascontiguousarray(sums.transpose(0, 2, 1), np.float64)
+        _lib.call("fs_mean_write", self._ctx, h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), launches, samples)
+
+    def _p_mean_reset(self, h):
+        _lib.call("fs_mean_reset", self._ctx, h)
+
+    def _p_mean_finalize(self, h, vh, ph):
+        _lib.call("fs_mean_finalize", self._ctx, h, vh, ph)
+
+    def _p_mean_free(self, h):
+        if self._ctx is not None:
+            _lib.call("fs_mean_free", self._ctx, h)
+
+    def _p_tracer_create(self, seeds, respawn, max_age):
+        h = ctypes.c_void_p()
+        _lib.call("fs_tracer_create", self._ctx, len(seeds), seeds.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(respawn), max_age,
+                  ctypes.byref(h))
+        return h
+
+    def _p_tracer_read(self, h, n):
+        launches = ctypes.c_longlong()
+        if n == 0:      # the launch counter alone
+            _lib.call("fs_tracer_read", self._ctx, h, None, None, ctypes.byref(launches))
+            return None, None, launches.value
+        pos, ints = np.empty((4, n), np.float64), np.empty((3, n), np.int32)
+        _lib.call("fs_tracer_read", self._ctx, h, pos.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                  ints.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.byref(launches))
+        return pos, ints, launches.value
+
+    def _p_tracer_write(self, h, pos, ints, launches):
+        _lib.call("fs_tracer_write", self._ctx, h, pos.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                  ints.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), launches)
+
+    def _p_tracer_sort(self, h):
+        _lib.call("fs_tracer_sort", self._ctx, h)
+
+    def _p_tracer_order(self, h, n):
+        ids = np.empty(n, np.int32)
+        _lib.call("fs_tracer_order", self._ctx, h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+        return ids
+
+    def _p_tracer_fields(self, h):
+        count, age = np.empty((self.ny, self.nx), np.int32), np.empty((self.ny, self.nx), np.int64)       # (the library's layout: x contiguous)
+        _lib.call("fs_tracer_fields", self._ctx, h, count.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                  age.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)))
+        return np.ascontiguousarray(count.T), np.ascontiguousarray(age.T)
+
+    def _p_tracer_free(self, h):
+        if self._ctx is not None:
+            _lib.call("fs_tracer_free", self._ctx, h)
+
+    def _p_tracer_create_inertial(self, seeds, alpha, tau, gravity, respawn, max_age, deposits):
+        h = ctypes.c_void_p()
+        dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        _lib.call("fs_tracer_create_inertial", self._ctx, len(seeds), dp(seeds), dp(alpha), dp(tau), gravity[0], gravity[1], int(respawn), max_age,
+                  int(deposits), ctypes.byref(h))
+        return h
+
+    def _p_tracer_read_vel(self, h, n):
+        vel = np.empty((2, n), np.float64)
+        _lib.call("fs_tracer_read_vel", self._ctx, h, vel.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        return vel
+
+    def _p_tracer_write_vel(self, h, vel):
+        _lib.call("fs_tracer_write_vel", self._ctx, h, vel.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+
+    def _p_tracer_deposits(self, h):
+        plane = np.empty((self.ny, self.nx), np.int32)       # (the library's layout: x contiguous)
+        _lib.call("fs_tracer_deposits", self._ctx, h, plane.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+        return np.ascontiguousarray(plane.T)
+
+    def _p_tracer_deposits_write(self, h, plane):
+        a = np.ascontiguousarray(plane.T, np.int32)
+        _lib.call("fs_tracer_deposits_write", self._ctx, h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+
+    def _p_tracer_accum(self, what, h, *args):
+        if self._ctx is not None:
+            _lib.call("fs_tracer_accum_" + what, self._ctx, h, *args)
+
+    def _p_tracer_accum_read(self, h):
+        occ, age = np.empty((self.ny, self.nx), np.int64), np.empty((self.ny, self.nx), np.int64)
+        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
+        lp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))
+        _lib.call("fs_tracer_accum_read", self._ctx, h, lp(occ), lp(age), ctypes.byref(launches), ctypes.byref(samples))
+        return np.ascontiguousarray(occ.T), np.ascontiguousarray(age.T), launches.value, samples.value
+
+    def _p_tracer_accum_write(self, h, occupancy, age_sum, launches, samples):
+        occ, age = np.ascontiguousarray(occupancy.T, np.int64), np.ascontiguousarray(age_sum.T, np.int64)
+        lp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))
+        _lib.call("fs_tracer_accum_write", self._ctx, h, lp(occ), lp(age), launches, samples)

@@ -6,6 +6,8 @@ tracers / draw_tracers / stop_tracers.  Positions are float64 in CELL units: cel
 sits at (i + 0.5, j + 0.5)."""
 import numpy as np
 
+from .riders import Rider
+
 FLUID, WALL, INFLOW, OUTFLOW = 0, 1, 2, 3
 # status of a particle (fs_tracer_read): alive, or the fate that ended it when the set does not respawn
 FATE_ALIVE, FATE_LEFT, FATE_WALL, FATE_EXPIRED = 0, 1, 2, 3
@@ -166,18 +168,29 @@ def concentration(occupancy, samples):
     return np.asarray(occupancy).astype(np.float64) / np.float64(samples)
 
 
-class TracerAccumulation:
-    """The accumulated occupancy of a FluidSimulator's tracer set (accumulate_tracers): the device accumulator and its parameters."""
+class TracerAccumulation(Rider):
+    """The accumulated occupancy of a FluidSimulator's tracer set (accumulate_tracers): the device accumulator and its parameters.  It
+    rides inside its Tracers, which issues its launch behind the advance and writes its part of a checkpoint."""
 
-    def __init__(self, accum, every, start_step):
-        self.accum, self.every, self.start_step = accum, int(every), int(start_step)
+    def __init__(self, accum, every, start_step, dev=None):
+        self.accum, self.every, self.start_step, self.dev = accum, int(every), int(start_step), dev
+        self.set = getattr(accum, "set", None)        # (the device set the planes are attached to)
 
     @property
     def token(self):
         return ("tracer_accum", self.accum.serial)
 
+    def free(self):
+        self.dev.tracer_accum_free(self.set)
 
-class Tracers:
+    def restore(self, z):
+        """(After Tracers.restore, which sets the launch count the phase hangs on.)  A checkpoint without an accumulation: nothing."""
+        if "tracer.accum.occupancy" in z:
+            self.dev.tracer_accum_write(self.set, z["tracer.accum.occupancy"], z["tracer.accum.age_sum"], int(z["tracer.accum.steps"]),
+                                        int(z["tracer.accum.samples"]))
+
+
+class Tracers(Rider):
     """One tracer set of a FluidSimulator (seed_tracers): the device set and its parameters; `issued`: advances issued since seed_tracers
     (what sort_every counts), `sorts`: device sorts so far."""
 
@@ -203,3 +216,53 @@ class Tracers:
     @property
     def token(self):
         return ("tracer", self.set.serial)
+
+    def tokens(self):
+        return (self.token,) if self.accumulation is None else (self.token, self.accumulation.token)
+
+    def launch(self, sim):
+        self.dev.tracer_advance(self.set, sim._solver.dt / sim._solver.dx, sim._solver.get_fields()[0])
+        self.issued += 1
+        if self.accumulation is not None:
+            self.dev.tracer_accum_add(self.set)      # (behind the advance: gated on the device from the set's launch counter)
+
+    def next_cut(self):
+        return self.to_next_sort()
+
+    def between_chunks(self):
+        """The scheduled device sort (seed_tracers(sort_every=K)): after every K-th step."""
+        if self.due():
+            self.sort()
+
+    def free(self):
+        if self.accumulation is not None:
+            self.accumulation.free()
+            self.accumulation = None
+        self.dev.tracer_free(self.set)
+
+    def checkpoint(self):
+        """A passive set: the keys of tracer_read and respawn, max_age - the format it always had; an inertial set adds u, w, tau, gravity
+        and, when it has them, the deposit plane; an attached accumulation adds its planes, counters and parameters."""
+        arrays = {f"tracer.{k}": np.asarray(a) for k, a in self.dev.tracer_read(self.set).items()}
+        arrays.update({"tracer.respawn": np.array(self.respawn), "tracer.max_age": np.array(self.max_age)})
+        if self.tau is not None:
+            u, w = self.dev.tracer_read_vel(self.set)
+            arrays.update({"tracer.u": u, "tracer.w": w, "tracer.tau": np.asarray(self.tau, np.float64),
+                           "tracer.gravity": np.array(self.gravity, np.float64)})
+            if self.deposits:
+                arrays["tracer.deposits"] = self.dev.tracer_deposits(self.set)
+        acc = self.accumulation
+        if acc is not None:
+            occ, age, launches, samples = self.dev.tracer_accum_read(self.set)
+            arrays.update({"tracer.accum.occupancy": occ, "tracer.accum.age_sum": age, "tracer.accum.steps": np.array(launches),
+                           "tracer.accum.samples": np.array(samples), "tracer.accum.every": np.array(acc.every),
+                           "tracer.accum.start": np.array(acc.start_step)})
+        return arrays
+
+    def restore(self, z):
+        """The state of the set itself, in seed order.  An accumulation is attached and restored after this (TracerAccumulation.restore)."""
+        self.dev.tracer_write(self.set, {k: z[f"tracer.{k}"] for k in KEYS})
+        if self.tau is not None:
+            self.dev.tracer_write_vel(self.set, z["tracer.u"], z["tracer.w"])
+            if self.deposits:
+                self.dev.tracer_deposits_write(self.set, z["tracer.deposits"])

@@ -145,8 +145,7 @@ def load_mean(sim, path):
     z = np.load(_npz_path(path))
     if "mean.sums" not in z.files:
         return False
-    avg = sim._averager
-    avg.dev.mean_write(avg.mean, z["mean.sums"], int(z["mean.launches"]), int(z["mean.samples"]))
+    sim._averager.restore(z)
     return True
 
 
@@ -163,7 +162,7 @@ def load_loads(sim, path):
     z = np.load(_npz_path(path))
     if "loads.sums" not in z.files:
         return False
-    sim._tracker.restore(z["loads.sums"], int(z["loads.launches"]), int(z["loads.samples"]))
+    sim._tracker.restore(z)
     return True
 
 
@@ -196,7 +195,6 @@ def load_tracers(sim, path, sort_every=0, accumulate=None):
     run that wrote it sorted its particles, and whether this one will (sort_every), makes no difference.  An inertial set comes back with
     its response times, gravity, particle velocities and deposit plane; accumulate = (every, start): the accumulation is attached and, when
     the checkpoint holds one, continued."""
-    from fs.tracers import KEYS
     z = np.load(_npz_path(path))
     if "tracer.x" not in z.files:
         return False
@@ -204,37 +202,16 @@ def load_tracers(sim, path, sort_every=0, accumulate=None):
     if "tracer.tau" in z.files:
         inertial = {"tau": z["tracer.tau"], "gravity": tuple(float(g) for g in z["tracer.gravity"]), "deposits": "tracer.deposits" in z.files}
     sim.seed_tracers(z["tracer.seeds"], respawn=bool(z["tracer.respawn"]), max_age=int(z["tracer.max_age"]), sort_every=sort_every, **inertial)
-    tr = sim._tracers
-    tr.dev.tracer_write(tr.set, {k: z[f"tracer.{k}"] for k in KEYS})
-    if inertial:
-        tr.dev.tracer_write_vel(tr.set, z["tracer.u"], z["tracer.w"])
-        if inertial["deposits"]:
-            tr.dev.tracer_deposits_write(tr.set, z["tracer.deposits"])
+    sim._tracers.restore(z)
     if accumulate is not None:
         sim.accumulate_tracers(every=accumulate[0], start_step=accumulate[1])
-        if "tracer.accum.occupancy" in z.files:
-            tr.dev.tracer_accum_write(tr.set, z["tracer.accum.occupancy"], z["tracer.accum.age_sum"], int(z["tracer.accum.steps"]),
-                                      int(z["tracer.accum.samples"]))
+        sim._tracers.accumulation.restore(z)        # (nothing when the checkpoint holds none: a fresh accumulation)
     return True
 
 
 def tracer_state_arrays(tr):
-    """The checkpoint's arrays for a tracer set (fs.tracers.Tracers).  A passive set: the keys of tracer_read and respawn, max_age - the
-    format it always had; an inertial set adds u, w, tau, gravity and, when it has them, the deposit plane; an attached accumulation adds
-    its planes, counters and parameters."""
-    arrays = {f"tracer.{k}": np.asarray(a) for k, a in tr.dev.tracer_read(tr.set).items()}
-    arrays.update({"tracer.respawn": np.array(tr.respawn), "tracer.max_age": np.array(tr.max_age)})
-    if tr.tau is not None:
-        u, w = tr.dev.tracer_read_vel(tr.set)
-        arrays.update({"tracer.u": u, "tracer.w": w, "tracer.tau": np.asarray(tr.tau, np.float64), "tracer.gravity": np.array(tr.gravity, np.float64)})
-        if tr.deposits:
-            arrays["tracer.deposits"] = tr.dev.tracer_deposits(tr.set)
-    acc = tr.accumulation
-    if acc is not None:
-        occ, age, launches, samples = tr.dev.tracer_accum_read(tr.set)
-        arrays.update({"tracer.accum.occupancy": occ, "tracer.accum.age_sum": age, "tracer.accum.steps": np.array(launches),
-                       "tracer.accum.samples": np.array(samples), "tracer.accum.every": np.array(acc.every), "tracer.accum.start": np.array(acc.start_step)})
-    return arrays
+    """The checkpoint's arrays for a tracer set (fs.tracers.Tracers.checkpoint)."""
+    return tr.checkpoint()
 
 
 def tracer_seeds(mask, n_random, rng_seed, lines):
@@ -255,20 +232,8 @@ def tracer_seeds(mask, n_random, rng_seed, lines):
 def save_state(sim, path, step):
     s = sim._solver
     arrays = {"step": np.array(step)}
-    tr = getattr(sim, "_tracers", None)
-    if tr is not None:
-        arrays.update(tracer_state_arrays(tr))
-    avg = getattr(sim, "_averager", None)
-    if avg is not None:
-        sums, launches, samples = avg.dev.mean_read(avg.mean)
-        arrays.update({"mean.sums": sums, "mean.launches": np.array(launches), "mean.samples": np.array(samples),
-                       "mean.every": np.array(avg.every), "mean.start": np.array(avg.start_step)})
-    bt = getattr(sim, "_tracker", None)
-    if bt is not None:
-        bt.drain()
-        arrays.update({"loads.sums": bt.sums(), "loads.launches": np.array(bt.issued), "loads.samples": np.array(bt.samples),
-                       "loads.box": np.array(bt.box), "loads.center": np.array(bt.centre, np.float64), "loads.every": np.array(bt.every),
-                       "loads.start": np.array(bt.start_step)})
+    for rider in sim._riders():
+        arrays.update(rider.checkpoint())       # (a history recorder has nothing to resume: its records are written as they come)
     for name in _STATE:
         if hasattr(s, name):
             arrays[f"{name}.current"] = getattr(s, name).current.to_numpy()

@@ -1,0 +1,152 @@
+"""The riders of the step together (history recorder, time averages, body tracker) on the NumPy stand-in device of tests/loads_standin.py:
+each gathers, attached beside the others, exactly what it gathers alone; their launches and signature tokens keep one order; a checkpoint
+holds the same keys and resumes bit for bit; and the stop_* methods keep their differences during a graph capture."""
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+from conftest import REPO
+
+FNAME = "traj_bc3_upwind_vc0.npz"
+CHUNKS = (5, 30, 7)
+RIDERS = ("history", "mean", "loads")
+# what main.save_state writes for this scene with an averager and a tracker attached
+CHECKPOINT_KEYS = {"step", "v.current", "v.next", "p.current", "p.next",
+                   "mean.sums", "mean.launches", "mean.samples", "mean.every", "mean.start",
+                   "loads.sums", "loads.launches", "loads.samples", "loads.box", "loads.center", "loads.every", "loads.start"}
+
+
+@pytest.fixture(scope="module")
+def standin():
+    import fs
+    from loads_standin import device_cls
+    saved = fs.runtime.config()
+    fs.runtime.init(dtype="f32", device_cls=device_cls())
+    yield
+    fs.runtime.init(**{k: saved[k] for k in ("gpu", "rank", "nranks", "halo", "bcast", "allgather", "device_cls")},
+                    dtype="f64" if saved["dtype"] == np.float64 else "f32")
+
+
+def _cli():
+    spec = importlib.util.spec_from_file_location("fs_cli_main_riders", os.path.join(REPO, "2d-fluid-simulator_amd", "main.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _attach(sim, cfg, which):
+    from fs.boundary_condition import default_body_box
+    box = default_body_box(cfg["bc"], cfg["res"])
+    if "history" in which:
+        fluid = np.argwhere(np.asarray(sim._solver._bc.mask) == 0)
+        probes = [tuple(fluid[len(fluid) // 3]), tuple(fluid[2 * len(fluid) // 3])]
+        sim.record_history(probes, box, every=1, capacity=20)
+    if "mean" in which:
+        sim.start_averaging(every=3, start_step=4)
+    if "loads" in which:
+        sim.track_body(box, every=2, capacity=10)
+
+
+def _sim(which):
+    from loads_standin import make_sim
+    sim, cfg = make_sim(FNAME)
+    _attach(sim, cfg, which)
+    return sim, cfg
+
+
+@pytest.fixture(scope="module")
+def combined(standin):
+    """All three riders attached, after run(5); run(30); run(7).  Shared: the tests below read it and leave it as it is."""
+    sim, cfg = _sim(RIDERS)
+    for n in CHUNKS:
+        sim.run(n)
+    return sim, cfg
+
+
+def _same(a, b, what):
+    assert a.keys() == b.keys(), what
+    for k in a:
+        assert np.array_equal(a[k], b[k]), f"{what}[{k}]"
+
+
+def test_riders_together_equal_riders_alone(combined):
+    sim, _ = combined
+    alone = {}
+    for name in RIDERS:
+        alone[name], _ = _sim((name,))
+        for n in CHUNKS:
+            alone[name].run(n)
+    h = sim.history()
+    assert h["step"].tolist() == list(range(1, 43)) and np.abs(h["u"]).max() > 0.0
+    _same(h, alone["history"].history(), "history")
+    a = sim.averages()
+    assert a["samples"] == (42 - 4) // 3
+    _same(a, alone["mean"].averages(), "averages")
+    b = sim.body_loads()
+    assert b["step"].tolist() == list(range(2, 43, 2)) and np.abs(b["pressure_x"]).max() > 0.0
+    _same(b, alone["loads"].body_loads(), "body_loads")
+    assert np.array_equal(sim.body_surface()["sums"], alone["loads"].body_surface()["sums"])
+
+
+def test_launch_order_and_token_order(standin):
+    sim, _ = _sim(RIDERS)
+    dev = sim._dev
+    dev._oplog = []
+    try:
+        sim.step()
+        names = [op[1] for op in dev._oplog if op[0] == "k"]
+    finally:
+        dev._oplog = None
+    assert names[-3:] == ["history_record", "mean_accumulate", "loads_record"]
+    assert len(names) > 3 and not set(names[:-3]) & {"history_record", "mean_accumulate", "loads_record"}
+    tail = sim._signature()[-3:]
+    assert [t[0] for t in tail] == list(RIDERS)
+    assert tail == (("history", sim._recorder.hist.serial), ("mean", sim._averager.mean.serial), ("loads", sim._tracker.loads.serial))
+
+
+def test_checkpoint_keys_and_resume(combined, tmp_path):
+    cli = _cli()
+    sim, cfg = combined
+    ck = str(tmp_path / "ck.npz")
+    cli.save_state(sim, ck, 42)
+    assert set(np.load(ck).files) == CHECKPOINT_KEYS
+    assert cli.saved_mean(ck) == (3, 4) and cli.saved_loads(ck)[2:] == (2, 0)
+    ref, _ = _sim(RIDERS)          # the uninterrupted run: the same 42 steps, then 12 more
+    for n in CHUNKS:
+        ref.run(n)
+    new, _ = _sim(("mean", "loads"))
+    assert cli.load_state(new, ck) == 42
+    assert cli.load_mean(new, ck) and cli.load_loads(new, ck)
+    ref.run(12)
+    new.run(12)
+    _same(new.averages(), ref.averages(), "averages")
+    got, exp = new.body_loads(), ref.body_loads()
+    assert got["step"].tolist() == list(range(44, 55, 2))
+    for k in exp:
+        assert np.array_equal(got[k], exp[k][-6:]), k
+    gs, es = new.body_surface(), ref.body_surface()
+    assert gs["samples"] == es["samples"] == 27 and np.array_equal(gs["sums"], es["sums"])
+    plain = str(tmp_path / "plain.npz")
+    cli.save_state(_sim(())[0], plain, 0)
+    assert not cli.load_mean(new, plain) and not cli.load_loads(new, plain)
+
+
+def test_stop_methods_during_a_capture(standin):
+    sim, _ = _sim(RIDERS)
+    sim.run(3)
+    dev = sim._dev
+    dev.capturing = True
+    try:
+        with pytest.raises(RuntimeError):
+            sim.stop_history()
+        with pytest.raises(RuntimeError):
+            sim.stop_body()
+        assert sim._recorder is not None and sim._tracker is not None
+        sim.stop_averaging()
+        assert sim._averager is None
+    finally:
+        dev.capturing = False
+    sim.stop_history()
+    sim.stop_body()
+    assert sim.history()["step"].tolist() == [1, 2, 3] and sim.body_loads()["step"].tolist() == [2]
