@@ -123,138 +123,25 @@ static int prof_drain(fs_ctx *c)
     return FS_OK;
 }
 
-// Compact list of the workgroups of a dense XCD-band launch that have anything to do (Grid::tiles), built once per geometry from the
-// host-side activity maps of the scene.  lanes = cells per lane (4: wave columns of 248 cells, 2: of 120), rt = rows per tile.
-// cls: 0 = every workgroup with work; 1 / 2 = those whose tiles see nothing but fluid within `reach` rows and the halo lanes ("plain":
-// no mask loads, no boundary views - their own kernel and register budget) / the others
-// `lanes` names the wave geometry: 4 = quads, 62 owner lanes (248 cells, 4 halo cells per side); 2 = pairs, 60 owner lanes (120 cells, 4 halo
-// cells); 3 = pairs, 62 owner lanes (124 cells, 2 halo cells)
-const fs_ctx::TileList *tile_list(fs_ctx *c, int lanes, int rt, bool stacked, int group, int nbx, int nby, int cls, int reach, int wgw, int jb, int je, int parent_rt)
+// The launch list of `spec` on the device (fs_tiles.h: what a list holds; fs_launch.h ov_grid: who asks), built at first use and kept until the
+// next mask.  nullptr: the launch stays dense - no maps for this scene, a spec a list cannot express, nothing to skip and no hint to give, or
+// no way to build one now.
+const fs_ctx::TileList *tile_list(fs_ctx *c, TileSpec spec)
 {
-    if (c->h_act4.empty() || nbx > 0xfff || nby > 0xffff || lanes > 4 || c->rows > 0xffff) return nullptr;      // (entry: class hints << 28 | by << 12 | bx)
-    if (je < 0) je = c->rows;
-    if (parent_rt == rt) parent_rt = 0;
-    if (parent_rt && (wgw != 1 || parent_rt % rt != 0 || parent_rt > 64)) return nullptr;
-    if (cls == 3 && !(rt == 8 && parent_rt == 16 && wgw == 1 && lanes == 2)) return nullptr;      // (a coarser plain tiling is defined for one-wave workgroups)
-    const fs_ctx::TileKey key{{lanes, rt, stacked ? 1 : 0, group, cls, reach, wgw, parent_rt, jb, je}};      // (slab launches cover varying row ranges: one list per range)
+    if (c->act.quad.empty() || !tile_spec_ok(spec, c->rows)) return nullptr;
+    const fs_ctx::TileKey key = spec.key();
     auto it = c->tile_lists.find(key);
     if (it != c->tile_lists.end()) return it->second.d ? &it->second : nullptr;
     // (building one allocates and synchronises the stream: not inside a capture or a tape recording - the dense grid then; and slab launches over ever new
     //  row ranges stop at 512 lists.  Both cases are counted: fs_tile_list_stats - a run whose warm-up covered its period reports none)
     if (c->capturing || c->tape_rec || c->tile_lists.size() >= 512) { ++c->tile_list_misses; return nullptr; }
-    const std::vector<uint8_t> &act = lanes == 4 ? c->h_act4 : (lanes == 2 ? c->h_act2 : c->h_act2w);
-    const int ow = geo_owners(lanes), waves = (c->X / geo_cells(lanes) + ow - 1) / ow, Y = c->rows;       // (activity maps are indexed by LOCAL row)
-    std::vector<uint32_t> per[8];
-    bool any_hint = false;
-    // no non-fluid cell (bit 1 of the activity byte: halo lanes included) in wave columns [wx0, wx1) within `reach` rows of rows [p0, p1) - and
-    // the whole box inside the domain: a wave column at the domain's first / last column clamps its halo lanes onto the edge cells, a row
-    // range that leaves the slab has rows nobody classified (the reference's scenes keep walls there; an uploaded mask need not)
-    auto plain_box = [&](int wx0, int wx1, int p0, int p1) -> bool {
-        if (wx0 <= 0 || wx1 >= waves || p0 - reach < 0 || p1 + reach > Y) return false;
-        for (int wx = wx0; wx < wx1; ++wx)
-            for (int j = p0 - reach; j < p1 + reach; ++j)
-                if (act[(size_t)wx * Y + j] & 2) return false;
-        return true;
-    };
-    const int groups = (nby + group - 1) / group;
-    // inside a group the workgroups are listed column by column: vertically adjacent workgroups, which re-read each other's halo rows, are
-    // neighbours in dispatch order (bc5 res 4096: K3+K4 333 -> 319 us, the red-black pair 195 -> 191 against row by row)
-    constexpr bool col_major = true;
-    for (int xcd = 0; xcd < 8; ++xcd)
-        for (int lg = 0; lg * 8 + xcd < groups; ++lg)
-            for (int o = 0; o < group * nbx; ++o) {
-                const int ly = col_major ? o % group : o / nbx, bx = col_major ? o / group : o % nbx;
-                const int by = (lg * 8 + xcd) * group + ly;
-                if (by >= nby) continue;
-                {
-                    // wave columns / rows of this workgroup (4 waves: side by side, or stacked = 4 tile rows of one column)
-                    const int wx0 = stacked ? bx : bx * wgw, wx1 = std::min(waves, stacked ? bx + 1 : bx * wgw + wgw);
-                    const int j0 = jb + (stacked ? by * wgw : by) * rt, j1 = std::min(je, jb + (stacked ? by * wgw + wgw : by + 1) * rt);
-                    bool any = false;
-                    for (int wx = wx0; wx < wx1 && !any; ++wx)
-                        for (int j = j0; j < j1; ++j)
-                            if (act[(size_t)wx * Y + j] & 1) { any = true; break; }
-                    if (cls == 3) {
-                        // mixed list of the one-launch red-black pair (fs_rbpair.h k_rbsor_pair_all): units of rt = 8 rows; an all-fluid parent tile of
-                        // parent_rt = 16 rows is ONE entry at its lower unit (hint bit 0), any other unit with work an entry with the per-4-row-tile
-                        // "fluid in its own rows" bits (1, 2)
-                        const int p0 = jb + (j0 - jb) / parent_rt * parent_rt, p1 = std::min(je, p0 + parent_rt);
-                        if (p1 - p0 == parent_rt && plain_box(wx0, wx1, p0, p1)) {
-                            if (j0 == p0) per[xcd].push_back((1u << 28) | ((uint32_t)by << 12) | (uint32_t)bx);
-                        } else if (any) {
-                            uint32_t h = 0u;
-                            for (int s = 0; s < 2; ++s)
-                                for (int j = j0 + 4 * s; j < std::min(j1, j0 + 4 * s + 4); ++j)
-                                    if (act[(size_t)bx * Y + j] & 4) { h |= 2u << s; break; }
-                            per[xcd].push_back((h << 28) | ((uint32_t)by << 12) | (uint32_t)bx);
-                        }
-                        any_hint = true;
-                        continue;
-                    }
-                    if (any && cls) {
-                        // plain: no non-fluid cell (bit 1 of the activity byte; halo lanes included) within `reach` rows of the tile - or, for the
-                        // boundary list of a launch whose plain part runs on tiles of parent_rt rows, of the parent tile this tile lies in
-                        // A tile (or parent tile) the row range cuts short is never plain: the plain kernels may store every row of their tile
-                        // (the stacked red-black pair does - ADVICE r5: rows past row_end of a slab range), the kernels with masks guard `je`.
-                        int p0 = j0, p1 = j1, full_rows = (stacked ? wgw : 1) * rt;
-                        if (parent_rt) { p0 = jb + (j0 - jb) / parent_rt * parent_rt; p1 = std::min(je, p0 + parent_rt); full_rows = parent_rt; }
-                        any = (p1 - p0 == full_rows && plain_box(wx0, wx1, p0, p1)) == (cls == 1);
-                    }
-                    uint32_t hints = 0u;
-                    if (any && !cls && reach > 0 && wgw <= 4) {
-                        // per-wave hint for a kernel that holds both paths (unsplit launches): wave w is plain - no non-fluid cell within `reach` rows
-                        // of ITS tile, halo lanes included - and may skip its mask loads and the classification (band_coords cls)
-                        for (int w = 0; w < wgw; ++w) {
-                            const int wx = stacked ? bx : bx * wgw + w;
-                            const int t0 = jb + (stacked ? by * wgw + w : by) * rt, t1 = std::min(je, t0 + rt);
-                            if (wx >= waves || t0 >= je) continue;
-                            const bool plain = plain_box(wx, wx + 1, t0, t1);
-                            if (plain) hints |= 1u << w;
-                        }
-                        any_hint = any_hint || hints != 0u;
-                    }
-                    if (any && cls == 2 && wgw == 1) {
-                        // boundary list of a multi-part launch (one-wave workgroups): bit 1 of the hint = "a fluid cell in the tile's own rows, halo lanes
-                        // included" - the general kernels then request their window without waiting for the masks that would tell them so
-                        for (int j = j0; j < j1; ++j)
-                            if (act[(size_t)bx * Y + j] & 4) { hints |= 2u; break; }
-                    }
-                    if (any) per[xcd].push_back((hints << 28) | ((uint32_t)by << 12) | (uint32_t)bx);
-                }
-            }
-    if ((!cls || cls == 3) && any_hint && wgw == 1) {
-        // one launch over both kinds of tile (fs_cip_step): the tiles that take the longer, masked body go FIRST in each XCD's list - the all-fluid tiles fill in
-        // behind them and the launch does not end on the slow ones (round 6: 281.5-282.7 -> 279.1-280.7 us; the other way round 283.6-284.6)
-        for (auto &v : per) std::stable_partition(v.begin(), v.end(), [](uint32_t e) { return ((e >> 28) & 1u) == 0u; });
-    }
-    size_t K = 0, total = 0;
-    for (auto &v : per) total += v.size();
-    if (total >= 64) {
-        // The geometry deals a class of tiles unevenly (bc5 res 4096: the boundary tiles of the red-black pair 1003 .. 1365 per XCD) and a compact
-        // launch lasts as long as its fullest XCD.  An entry names its tile, so any XCD may run it: the surplus of an XCD - the END of its list, whole
-        // runs of vertically adjacent tiles - goes to the end of the emptiest lists.  Those tiles read their halo rows through another L2; they are
-        // a few per cent of the list.
-        const size_t target = (total + 7) / 8;
-        for (int d = 0; d < 8; ++d)
-            while (per[d].size() > target) {
-                int r = 0;
-                for (int x = 1; x < 8; ++x) if (per[x].size() < per[r].size()) r = x;
-                if (per[r].size() >= target) break;
-                const size_t n = std::min(per[d].size() - target, target - per[r].size());
-                per[r].insert(per[r].end(), per[d].end() - n, per[d].end());
-                per[d].resize(per[d].size() - n);
-            }
-    }
-    for (auto &v : per) K = std::max(K, v.size());
+    const TileWords h = build_tile_list(spec, c->act.of(spec.lanes).data(), c->X, c->rows);
     fs_ctx::TileList tl;
-    if (K > 0 && (cls || any_hint || total < (size_t)nbx * nby)) {        // (nothing to skip, no hint to give: the dense grid needs no list)
-        std::vector<uint32_t> h(K * 8, 0xffffffffu);
-        for (int xcd = 0; xcd < 8; ++xcd)
-            for (size_t k = 0; k < per[xcd].size(); ++k) h[k * 8 + xcd] = per[xcd][k];
-        if (hipMalloc(&tl.d, h.size() * sizeof(uint32_t)) == hipSuccess &&
-            hipMemcpyAsync(tl.d, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) == hipSuccess &&
+    if (h.needed) {
+        if (hipMalloc(&tl.d, h.words.size() * sizeof(uint32_t)) == hipSuccess &&
+            hipMemcpyAsync(tl.d, h.words.data(), h.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) == hipSuccess &&
             hipStreamSynchronize(c->stream) == hipSuccess)
-            { tl.per_xcd = (int)K; tl.count = (int)total; }
+            { tl.per_xcd = h.per_xcd; tl.count = h.count; }
         else { if (tl.d) hipFree(tl.d); tl.d = nullptr; }
     }
     auto &slot = c->tile_lists[key] = tl;
@@ -606,7 +493,7 @@ extern "C" {
 int fs_abi_version(void) { return FS_ABI_VERSION; }
 const char *fs_last_error(void) { return g_err.c_str(); }
 
-// Launch lists of this context (fs_core.hip tile_list): how many were built so far (each costs one hipMalloc + a stream synchronisation at the first
+// Launch lists of this context (tile_list above): how many were built so far (each costs one hipMalloc + a stream synchronisation at the first
 // launch of its geometry / row range), and how many launches wanted one they could not build - inside a hipGraph capture or a tape recording, or beyond the
 // cap of 512 - and ran (or were recorded) as dense grids instead.  bench.py samples this around its timed region: 0 built, 0 misses.
 int fs_tile_list_stats(const fs_ctx *ctx, int *built, int *misses)
@@ -792,37 +679,14 @@ int fs_upload_mask(fs_ctx *ctx, const uint8_t *mask_xy)
     FS_HIP(hipMemsetAsync(ctx->d_bcmap, 0, (size_t)ctx->rows * ctx->Pm, ctx->stream));
     FS_HIP(hipMemsetAsync(ctx->d_lazyflags, 63, (size_t)std::max(ctx->nwx, 1) * ctx->rows, ctx->stream));
     rc = upload_global(ctx, ctx->d_bcmap, 1, 1, ctx->h_bcmap.data(), ctx->Pm);
-    // activity of the scene per (wave column, row) for the compact launches: a cell is "deep wall" when it is a wall cell that no
-    // boundary kernel writes - workgroups made of such cells only have nothing to do in any kernel
     // captured graphs and recorded tapes hold the device pointers of the lists (and the launch geometry of the old scene): a new mask
     // invalidates them - a later fs_graph_launch / fs_tape_replay of such an id is an error, not a read through a dangling pointer
     for (auto &gexec : ctx->graphs) if (gexec) { hipGraphExecDestroy(gexec); gexec = nullptr; }
     for (auto &tp : ctx->tapes) if (tp) { delete tp; tp = nullptr; }
     tile_lists_free(ctx);
-    ctx->h_act4.clear(); ctx->h_act2.clear(); ctx->h_act2w.clear();
-    if (ctx->X % 2 == 0 && ctx->tile_list_mask && ctx->rows <= 0xffff) {
-        // indexed by LOCAL row (a slab: its ghost rows included; rows outside the domain are deep wall)
-        const int X = ctx->X, Y = ctx->Y, R = ctx->rows, g0 = ctx->y0 - ctx->halo;
-        struct Geo { std::vector<uint8_t> *act; int w, halo; } geos[3] = {{&ctx->h_act4, 248, 4}, {&ctx->h_act2, 120, 4}, {&ctx->h_act2w, 124, 2}};
-        for (const Geo &ge : geos) {
-            const int w = ge.w, n = (X + w - 1) / w;
-            ge.act->assign((size_t)n * R, 0);
-            for (int i = 0; i < X; ++i) {
-                const uint8_t *m = mask_xy + (size_t)i * Y, *b = ctx->h_bcmap.data() + (size_t)i * Y;
-                uint8_t *a = ge.act->data() + (size_t)(i / w) * R;
-                // the neighbouring wave column whose halo lanes cover column i, if any
-                const int r = i % w;
-                uint8_t *h = r < ge.halo && i / w > 0 ? a - R : (r >= w - ge.halo && i / w + 1 < n ? a + R : nullptr);
-                for (int lr = 0; lr < R; ++lr) {
-                    const int j = g0 + lr;
-                    if (j < 0 || j >= Y) { a[lr] |= 2; if (h) h[lr] |= 2; continue; }
-                    const uint8_t nf = m[j] != 0 ? 2 : 4;            // bit 1: a cell that is not fluid, bit 2: a fluid cell - both with the halo lanes of the neighbouring column
-                    a[lr] |= (uint8_t)((m[j] != 1) | (b[j] != 0)) | nf;
-                    if (h) h[lr] |= nf;
-                }
-            }
-        }
-    }
+    ctx->act.clear();      // the scene's activity maps for the compact launches (fs_tiles.h; local rows: a slab's ghost rows included)
+    if (ctx->X % 2 == 0 && ctx->tile_list_mask && ctx->rows <= TILE_MAX_ROWS)
+        ctx->act = activity_maps(mask_xy, ctx->h_bcmap.data(), ctx->X, ctx->Y, ctx->rows, ctx->y0 - ctx->halo);
     std::vector<uint8_t>().swap(ctx->h_bcmap);
     if (rc) return rc;
     if (ctx->X % 4 == 0) {      // per-tile flags of the lazy pressure BC

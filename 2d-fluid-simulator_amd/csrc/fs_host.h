@@ -14,7 +14,7 @@
 #include "../../include/fs_hip.h"
 #include "fs_device.h"
 #include "fs_kernels.h"
-#include "fs_march.h"
+#include "fs_march.h"      // (with fs_tiles.h: the launch lists' host side)
 #include "fs_rbpair.h"
 #include "fs_jquad.h"
 #include "fs_k34n.h"
@@ -148,14 +148,13 @@ struct fs_ctx {
     bool limit_gate = true;    // env FS_LIMIT_GATE=0: limit_field always reads the whole field (A/B; the results are the same)
     int stack_mask = 0;       // kernel families (XCD_* bits) launched with stacked workgroups (fs_create)
 
-    // compact launches (fs_device.h Grid::tiles): per-cell activity of the scene on the host (bit 0: some cell of wave column wx - 248
-    // cells - in row j is not deep wall, bit 1: the same for the 120-cell wave columns of the 2-cell-lane kernels), and the lists built from
-    // it per launch geometry (key: lane width, rows per tile, stacked, group size)
+    // compact launches (fs_device.h Grid::tiles): the scene's activity per (wave column, local row) on the host, and the lists built from it per launch
+    // geometry at first use (fs_tiles.h: the maps, the list specification, the builder; fs_core.hip tile_list: upload and cache)
     int tile_list_mask = 1 | 2 | 4 | 8 | 32;              // env FS_TILE_LIST: kernel families (XCD_* bits) launched compactly.  Measured at bc5 res 4096:
                                              // K3+K4 363 -> 346 us, red-black pair 215 -> 192, vorticity confinement (2-cell lanes) 97 -> 95, K2 (2-cell lanes) 105 -> 102, the plain Jacobi sweeps 87.2 -> 85.8 (reading v) / 75.5 -> 74.1 (source pair)
-    std::vector<uint8_t> h_act4, h_act2, h_act2w;     // [wave column][local row]
+    fs::ActivityMaps act;         // empty: no lists for this scene (odd width, FS_TILE_LIST=0, more rows than an entry holds)
     struct TileList { uint32_t *d = nullptr; int per_xcd = 0; int count = 0; };      // count: listed workgroups (without the padding)
-    using TileKey = std::array<int, 10>;     // lanes, rows per tile, stacked, group, class, reach, waves per workgroup, parent tile rows, row range
+    using TileKey = decltype(fs::TileSpec().key());
     std::map<TileKey, TileList> tile_lists;
 
     fs::Grid grid() const
@@ -247,7 +246,7 @@ void history_release(fs_history *h);      // fs_diag.hip
 void mean_release(fs_mean *m);            // fs_diag.hip
 void loads_release(fs_loads *l);          // fs_diag.hip
 
-// HIP-event pair around a span of stream work that is not one kernel launch (fs_api.hip; the ghost-row exchange chain of fs_comm.hip)
+// HIP-event pair around a span of stream work that is not one kernel launch (fs_core.hip; the ghost-row exchange chain of fs_comm.hip)
 ProfRec prof_span_begin(fs_ctx *c, const char *name, hipStream_t stream);
 void prof_span_end(fs_ctx *c, const ProfRec &rec, hipStream_t stream);
 

@@ -12,7 +12,7 @@
 // recomputed by whoever reads them, wall cells without one hold the same value in both buffers - the host checks that (Field.static_id:
 // equal unless somebody uploaded into one of them) and otherwise keeps the two-sweep passes, which tell the two buffers' histories apart.
 //
-// Validity (host-checked per mask, fs_api.hip build_bc_ops -> jq_ok): no recipe reads a source on the far side of its target as seen
+// Validity (host-checked per mask, fs_core.hip build_bc_ops -> jq_ok): no recipe reads a source on the far side of its target as seen
 // from a cell whose raw value is live (a fluid cell, or the source of some recipe) - then the plain stencil's footprint suffices, as in
 // fs_rbpair.h; and the first / last domain row hold no not-wall cell.
 #pragma once
@@ -140,7 +140,7 @@ __device__ __forceinline__ void jacobi_ov2_tile(const Grid &g, const Konst<float
     }
 }
 
-// the list's per-wave hint (fs_core.hip tile_list, reach 1): nothing but fluid in and around the wave's tile - no mask loads, whole-lane stores
+// the list's per-wave hint (fs_tiles.h entry_all, reach 1): nothing but fluid in and around the wave's tile - no mask loads, whole-lane stores
 template <int RT, int DM>
 __global__ __launch_bounds__(256) void k_jacobi_ov2(Grid g, Konst<float> k, int nbx, int nby, int jb, int je, float *pn, const float *pc, const float *vc)
 {
@@ -170,8 +170,8 @@ __global__ __launch_bounds__(256) void k_jacobi_ov2(Grid g, Konst<float> k, int 
     jacobi_ov2_tile<RT, DM, false>(g, k, lm, i0, j0, je, nw, pn, pc, vc);
 }
 
-// PATH 2: classify the tile here (mask loads); 3: the host listed this workgroup as plain - nothing but fluid within reach (fs_api.hip
-// tile_list): the plain path without looking, as its own kernel with its own (small) register budget
+// PATH 2: classify the tile here (mask loads); 3: the host listed this workgroup as plain - nothing but fluid within reach (fs_tiles.h
+// plain_box): the plain path without looking, as its own kernel with its own (small) register budget
 template <int N, int RT, int PATH, typename T>
 __global__ __launch_bounds__(256) void k_jacobi_quad(Grid g, int nbx, int nby, int jb, int je, const uint8_t *bcmap, T *pn, const T *pc, const T *src)
 {

@@ -19,7 +19,7 @@
 // confinement of this one) before anything looks at it.  The tiles that are NOT all fluid take the same route with the masks (k234_bnd_phase1 / 2
 // below), and ONE launch covers both kinds (k_cip_step_all: the list entry's hint picks the body; fs_transport.hip fs_cip_step).  Until late in
 // round 5 the other tiles ran the general K3 + K4 kernel of fs_k34n.h behind a K2 launch over their rows.
-// Plain tile: every cell within 2 rows and within the halo lanes is fluid and inside the domain (fs_core.hip tile_list) - K2's own reads
+// Plain tile: every cell within 2 rows and within the halo lanes is fluid and inside the domain (fs_tiles.h plain_box) - K2's own reads
 // one cell further out take whatever the buffers hold there, as the reference's K2 does.
 #pragma once
 #include <type_traits>

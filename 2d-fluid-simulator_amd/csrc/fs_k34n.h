@@ -17,7 +17,7 @@
 // Every row is loaded CLAMPED (sample() clamps coordinates, fs/differentiation.py:4-9) and a register slot that stands for a row outside
 // the domain takes the K3 result of the edge row it clamps onto, so one launch covers every row.  One channel per wave: the C passes over
 // a tile are adjacent in dispatch order on the SAME XCD and share their input rows through that XCD's L2.
-// PLAIN: the host listed this workgroup as seeing nothing but fluid within its reach (fs_api.hip tile_list, compact launch): no mask
+// PLAIN: the host listed this workgroup as seeing nothing but fluid within its reach (fs_tiles.h plain_box, compact launch): no mask
 // loads, constant selectors, unconditional stores - as its own kernel.  CLAMP: clamp_field(dye, 0, 1) (fs/solver.py:46-49) folded into
 // the store of the advected value.
 //
@@ -86,7 +86,7 @@ __device__ __forceinline__ void cip_grad_advect_n_body(const Grid &g, const Kons
     if (!PLAIN && !__any(any_fl)) {
         // no fluid cell in this wave's tile: every output is a carried value (out = fc, old gradients on inflow / outflow cells) - and only
         // cells that SOME kernel writes can differ between fc and out: not-wall cells and, for the velocity, the targets of the velocity
-        // boundary kernel (bit 7 of the recipe byte, fs_api.hip build_bc_ops).  Deep wall rows move nothing (a third of scene 5); `full`:
+        // boundary kernel (bit 7 of the recipe byte, fs_core.hip build_bc_ops).  Deep wall rows move nothing (a third of scene 5); `full`:
         // after an upload the two buffers may differ anywhere - carry every cell once (fs/solver.py, Field.static_id).
 #pragma unroll
         for (int t = 0; t < RT; ++t) {
@@ -355,7 +355,7 @@ __device__ __forceinline__ void cip_grad_advect_pk_body(const Grid &g, const Kon
     unsigned cls = 0u;
     if (!tile_coords_nz<N, C, HL>(g, nbx, nby, jb, je, RT, wx, ty, cg, PLAIN ? nullptr : &cls)) return;
     // boundary list of a multi-part launch (one-wave workgroups): bit 1 of the entry's hint = the host saw a fluid cell in the tile's own rows
-    // (fs_core.hip tile_list) - the window is then requested WITH the masks instead of behind the test that needs them
+    // (fs_tiles.h entry_split) - the window is then requested WITH the masks instead of behind the test that needs them
     const bool bnd_fluid = !PLAIN && !full && (blockDim.x >> 6) == 1 && (cls & 2u) != 0u;
     const LaneMapN<N> lm_in = lane_map_n<N, HL>(g, wx);
     const LaneMapN<N> lm = PLAIN ? LaneMapN<N>{lm_in.i0, lm_in.owner, false, false} : lm_in;
@@ -569,7 +569,7 @@ __global__ __launch_bounds__(256) void k_cip_nonadv_n(Grid g, Konst<T> k, int nb
 // A lane computes w for RT+2 rows of its cells from RT+4 rows of v, takes the x-neighbours of |w| from the adjacent lanes (DPP) and
 // writes RT rows of vn; w / |w| never touch HBM unless STORE_W.  One halo lane per side (the pass reaches 2 cells in x).
 // ------------------------------------------------------------------------------------------------
-// PLAIN: the launch list says this wave sees nothing but fluid within reach (per-wave hint, fs_core.hip tile_list): no mask loads before the
+// PLAIN: the launch list says this wave sees nothing but fluid within reach (per-wave hint, fs_tiles.h entry_all): no mask loads before the
 // window is requested, constant selectors, no lane at the domain's first / last column (round 5: the mask round trip in front of the loads was
 // what the literal Jacobi sweep lost 8 % to)
 template <int N, int RT, int DM, bool STORE_W, bool PLAIN, typename T>

@@ -78,59 +78,87 @@ static inline int whole_grid(const fs_ctx *c, int jb, int je) { return c->halo =
 
 static inline dim3 cells_grid(const fs_ctx *c, int jb, int je) { return dim3((c->X + 255) / 256, je - jb, 1); }
 
-// overlapped-wave tile kernels: nbx blocks of 4 waves x 62 quads across, nby tile rows, XCD-band 1-D launch
-struct OvGrid { int nbx, nby; dim3 grid; Grid g; int threads = 256; };    // threads: 64 x waves per workgroup
+// overlapped-wave tile kernels: nbx blocks of `threads / 64` waves across, nby tile rows, XCD-band 1-D launch
+struct OvGrid {
+    int nbx, nby; dim3 grid; Grid g; int threads = 256;      // threads: 64 x waves per workgroup
+    const fs_ctx::TileList *list = nullptr;                  // the launch list behind g.tiles (until the next mask), or null: a dense launch
+};
 enum { XCD_RBSOR = 1, XCD_VORT = 2, XCD_ADVECT = 4, XCD_NONADV = 8, XCD_GRAD = 16, XCD_JACOBI = 32 };
-// Compact list of the workgroups of a dense XCD-band launch that have anything to do (Grid::tiles), built once per geometry from the
-// host-side activity maps of the scene.  lanes = cells per lane (4: wave columns of 248 cells, 2: of 120), rt = rows per tile.
-// cls: 0 = every workgroup with work; 1 / 2 = those whose tiles see nothing but fluid within `reach` rows and the halo lanes ("plain":
-// no mask loads, no boundary views - their own kernel and register budget) / the others
-// `lanes` names the wave geometry: 4 = quads, 62 owner lanes (248 cells, 4 halo cells per side); 2 = pairs, 60 owner lanes (120 cells, 4 halo
-// cells); 3 = pairs, 62 owner lanes (124 cells, 2 halo cells)
-static inline int geo_cells(int lanes) { return lanes == 4 ? 4 : 2; }
-static inline int geo_owners(int lanes) { return lanes == 2 ? 60 : 62; }
-const fs_ctx::TileList *tile_list(fs_ctx *c, int lanes, int rt, bool stacked, int group, int nbx, int nby, int cls = 0, int reach = 0, int wgw = 4, int jb = 0, int je = -1, int parent_rt = 0);      // fs_core.hip
 
-// XCD-band launch geometry of a tile kernel family (fs_march.h band_coords); `lanes`: cells per lane.  When the launch covers the whole
-// single-GPU grid, the workgroups without anything to do are left out (compact list, Grid::tiles).
-static inline OvGrid ov_grid_lanes(fs_ctx *c, int jb, int je, int rt, int zgroups, int family, int lanes, bool allow_list = true, int cls = 0, int reach = 0, int wgw = 4, int parent_rt = 0,
-                                   bool slab_classes = false)      // slab_classes: plain / boundary lists (cls 1 / 2) for a row range of a slab too (fs_cip_step)
+// A tile kernel's launch, said in words at the call site: tiles(family, lanes) and what differs from a dense-or-skipping launch of 4-wave
+// workgroups on 1-row tiles.  The *_within(reach) forms pick which tiles the launch list holds and which hints its entries carry (fs_tiles.h).
+struct TileLaunch {
+    int family, lanes;            // XCD_* bit of the kernel family; wave geometry (fs_tiles.h LANES_*)
+    int rt = 1, zgroups = 1, wgw = 4;
+    bool compact = true;
+    int cls = TILES_ALL, reach = 0, parent_rt = 0;
+    bool slab_classes = false;
+
+    TileLaunch rows(int n) const { TileLaunch l = *this; l.rt = n; return l; }                          // rows per tile
+    TileLaunch channel_groups(int n) const { TileLaunch l = *this; l.zgroups = n; return l; }           // passes over the same tile, adjacent in dispatch order
+    TileLaunch waves(int n) const { TileLaunch l = *this; l.wgw = n; return l; }                        // waves per workgroup
+    TileLaunch dense_if(bool dense) const { TileLaunch l = *this; l.compact = !dense; return l; }       // no list: every workgroup of the grid
+    // every workgroup with work; bit w of an entry: wave w sees nothing but fluid within `reach` rows of its tile and its halo lanes ("plain")
+    TileLaunch hints_within(int reach_) const { TileLaunch l = *this; l.cls = TILES_ALL; l.reach = reach_; return l; }
+    // the two parts of a split launch: the plain tiles, the others
+    TileLaunch plain_within(int reach_) const { TileLaunch l = *this; l.cls = TILES_PLAIN; l.reach = reach_; return l; }
+    TileLaunch boundary_within(int reach_) const { TileLaunch l = *this; l.cls = TILES_BOUNDARY; l.reach = reach_; return l; }
+    // the one-launch red-black pair: 8-row units, a plain parent tile as one entry
+    TileLaunch mixed_within(int reach_) const { TileLaunch l = *this; l.cls = TILES_MIXED; l.reach = reach_; return l; }
+    TileLaunch parent_rows(int n) const { TileLaunch l = *this; l.parent_rt = n; return l; }            // plain is decided per parent tile of n rows
+    // plain / boundary / mixed lists for a row range of a slab too (fs_cip_step, the one-launch pair); without it a slab's ranges get TILES_ALL lists only
+    TileLaunch classes_on_slabs(bool on) const { TileLaunch l = *this; l.slab_classes = on; return l; }
+};
+static inline TileLaunch tiles(int family, int lanes) { return TileLaunch{family, lanes}; }
+
+// Round 6: the hinted single-launch kernels of the pressure families run as ONE-wave workgroups - a list entry is then one tile, and the entries whose tile
+// takes the masked body stand first in every XCD's list (fs_tiles.h masked_first), the all-fluid tiles fill in behind them: the four-sweep Jacobi pass at bc2 res
+// 1600 30.2 -> 23.9 us (configs[1] 2 057 -> 2 472 steps/s), the finishing pass 24.2 -> 21.2, the small grids' red-black pair 12.7 -> 12.0 (res 400) / 12.3 ->
+// 11.6 (configs[0]: 59.6 -> 62.0 k steps/s), the graded literal sweep 73.6 -> 72.1 (three A/B rounds).  Vorticity confinement and K2' measured no gain
+// (85.5 against 84.9; 155.4 against 154.8) and keep their 4-wave workgroups (column-by-column locality).
+static inline TileLaunch one_wave_where_hinted(const fs_ctx *c, TileLaunch l)
 {
+    if (c->dtype == 0 && (l.family & (XCD_RBSOR | XCD_JACOBI)) && l.wgw == 4 && l.cls == TILES_ALL && l.reach > 0 && l.compact) l.wgw = 1;      // (f32: the f64 bodies were not measured)
+    return l;
+}
+// from the launch to the list it takes its work from: the workgroup shape and the dense grid's extents over rows [jb, je)
+static inline TileSpec list_spec(const fs_ctx *c, const TileLaunch &l, int jb, int je)
+{
+    TileSpec s;
+    s.lanes = l.lanes; s.rt = l.rt; s.wgw = l.wgw; s.cls = l.cls; s.reach = l.reach; s.parent_rt = l.parent_rt; s.jb = jb; s.je = je;
+    const int waves = geo_waves(c->X, l.lanes), tile_rows = (je - jb + l.rt - 1) / l.rt;
+    s.stacked = (c->stack_mask & l.family) != 0 && l.wgw > 1;    // the waves of a workgroup: tile rows of one wave column
+    s.nbx = s.stacked ? waves : (waves + l.wgw - 1) / l.wgw;
+    s.nby = s.stacked ? (tile_rows + l.wgw - 1) / l.wgw : tile_rows;
+    // Groups of 8 tile rows per XCD measured best for every family (2 / 4 / 16 / 32 / per-family sizes: rounds 2 - 4)
+    constexpr int xg = 8;
+    s.group = s.stacked ? std::max(1, xg / l.wgw) : xg;     // the same number of field rows per XCD group
+    return s;
+}
+const fs_ctx::TileList *tile_list(fs_ctx *c, TileSpec spec);      // fs_core.hip
+
+// XCD-band launch geometry of a tile kernel family (fs_march.h band_coords).  When the launch covers the whole single-GPU grid - or a row range
+// of a slab - the workgroups without anything to do are left out (compact list, Grid::tiles).
+static inline OvGrid ov_grid(fs_ctx *c, int jb, int je, const TileLaunch &asked)
+{
+    const TileLaunch l = one_wave_where_hinted(c, asked);
+    const TileSpec s = list_spec(c, l, jb, je);
     OvGrid o;
     o.g = c->grid();
-    // Round 6: the hinted single-launch kernels of the pressure families run as ONE-wave workgroups - a list entry is then one tile, and the entries whose tile
-    // takes the masked body stand first in every XCD's list (fs_core.hip tile_list), the all-fluid tiles fill in behind them: the four-sweep Jacobi pass at bc2 res
-    // 1600 30.2 -> 23.9 us (configs[1] 2 057 -> 2 472 steps/s), the finishing pass 24.2 -> 21.2, the small grids' red-black pair 12.7 -> 12.0 (res 400) / 12.3 ->
-    // 11.6 (configs[0]: 59.6 -> 62.0 k steps/s), the graded literal sweep 73.6 -> 72.1 (three A/B rounds).  Vorticity confinement and K2' measured no gain
-    // (85.5 against 84.9; 155.4 against 154.8) and keep their 4-wave workgroups (column-by-column locality).
-    if (c->dtype == 0 && (family & (XCD_RBSOR | XCD_JACOBI)) && wgw == 4 && cls == 0 && reach > 0 && allow_list) wgw = 1;      // (f32: the f64 bodies were not measured)
-    const int ow = geo_owners(lanes);
-    const int nu = c->X / geo_cells(lanes), waves = (nu + ow - 1) / ow, tiles = (je - jb + rt - 1) / rt;
-    const bool stacked = (c->stack_mask & family) != 0 && wgw > 1;    // the 4 waves of a workgroup: 4 tile rows of one wave column
-    o.threads = 64 * wgw;
-    o.nbx = stacked ? waves : (waves + wgw - 1) / wgw;
-    o.nby = stacked ? (tiles + wgw - 1) / wgw : tiles;
-    {
-        // (8 * block columns, rows per XCD group * channel groups, groups per XCD): decoded without a division (fs_march.h band_coords).  Groups of
-        // 8 tile rows per XCD measured best for every family (2 / 4 / 16 / 32 / per-family sizes: rounds 2 - 4)
-        constexpr int xg = 8;
-        const int group = stacked ? std::max(1, xg / wgw) : xg;     // the same number of field rows per XCD group
-        const int groups = (o.nby + group - 1) / group;
-        const fs_ctx::TileList *tl = allow_list && (c->tile_list_mask & family) && ((jb == 0 && je == c->rows) || (c->halo != 0 && (cls == 0 || slab_classes)))
-                                         ? tile_list(c, lanes, rt, stacked, group, o.nbx, o.nby, cls, reach, wgw, jb, je, parent_rt) : nullptr;
-        const bool inner = zgroups > 1 && tl;
-        if (tl) { o.grid = dim3(8 * tl->per_xcd * zgroups, 1, 1); o.g.tiles = tl->d; }
-        else o.grid = dim3(8 * o.nbx, group * zgroups, (groups + 7) / 8);
-        o.nby |= (group - 1) << 24;
-        if (inner) o.nby |= FS_CG_INNER;
-    }
-    if (stacked) o.nby |= FS_STACKED;
+    o.threads = 64 * l.wgw;
+    o.nbx = s.nbx;
+    o.nby = s.nby;
+    const bool listed = l.compact && (c->tile_list_mask & l.family) && ((jb == 0 && je == c->rows) || (c->halo != 0 && (l.cls == TILES_ALL || l.slab_classes)));
+    o.list = listed ? tile_list(c, s) : nullptr;
+    // dense: (8 * block columns, rows per XCD group * channel groups, groups per XCD), decoded without a division (fs_march.h band_coords)
+    const int groups = (o.nby + s.group - 1) / s.group;
+    if (o.list) { o.grid = dim3(8 * o.list->per_xcd * l.zgroups, 1, 1); o.g.tiles = o.list->d; }
+    else o.grid = dim3(8 * o.nbx, s.group * l.zgroups, (groups + 7) / 8);
+    o.nby |= (s.group - 1) << 24;
+    if (l.zgroups > 1 && o.list) o.nby |= FS_CG_INNER;
+    if (s.stacked) o.nby |= FS_STACKED;
     return o;
 }
-static inline OvGrid ov_grid(fs_ctx *c, int jb, int je, int rt, int zgroups, int family, bool allow_list = true)
-{ return ov_grid_lanes(c, jb, je, rt, zgroups, family, 4, allow_list); }
-template <int N>
-static OvGrid ov_grid_n(fs_ctx *c, int jb, int je, int rt) { return ov_grid_lanes(c, jb, je, rt, 1, XCD_RBSOR, N); }
 
 // Division-mode dispatch (fs_device.h DM_*): CALL(DM) is expanded for the modes a kernel family distinguishes.  f32 fields divide by their
 // loop-invariant divisors through the f64 multiplication (modes 4 / 5; divisors that admit a tie: IEEE division, modes 0 / 1); power-of-two dx-derived

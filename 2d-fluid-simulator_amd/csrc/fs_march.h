@@ -17,6 +17,7 @@
 #pragma once
 #include "fs_device.h"
 #include "fs_kernels.h"
+#include "fs_tiles.h"
 
 namespace fs {
 
@@ -86,7 +87,7 @@ __device__ __forceinline__ bool lane_needed(unsigned active) { return (active | 
 __device__ __forceinline__ uint32_t mask_quad(const Grid &g, int i0, int j)
 { return load_row_quad<uint32_t, uint8_t>(g.mask + (size_t)j * g.Pm, i0); }
 
-// recipe bytes of the boundary kernels, one per cell (fs_api.hip build_bc_ops): bits 0-6 the pressure recipe (k_jacobi_lazy below),
+// recipe bytes of the boundary kernels, one per cell (fs_core.hip build_bc_ops): bits 0-6 the pressure recipe (k_jacobi_lazy below),
 // bit 7: the cell is a target of the velocity boundary kernel.  Rows are clamped into the domain.
 __device__ __forceinline__ uint32_t bcmap_quad(const Grid &g, const uint8_t *bcmap, int i0, int row)
 { return load_row_quad<uint32_t, uint8_t>(bcmap + (size_t)clampy(g, row) * g.Pm, i0); }
@@ -157,7 +158,7 @@ struct LaneMap {
 // instructions of a one-row K2 tile on them).
 constexpr int FS_CG_INNER = 1 << 22;
 // cls (optional): bits 28 .. 31 of a compact list's entry - bit w: the host found wave w of this workgroup to be PLAIN, nothing but fluid within the
-// kernel's reach (fs_api.hip tile_list, lists built with a hint reach; round 4): a kernel that holds both paths takes the plain one
+// kernel's reach (fs_tiles.h entry_all, lists built with a hint reach; round 4): a kernel that holds both paths takes the plain one
 // without loading a mask byte.  0 where the launch is dense or the list carries no hints.
 template <int ZG = 1>
 __device__ __forceinline__ bool band_coords(const Grid &g, int nbx, int nby_packed, int &bx, int &by, int &cg, int zoff = 0, unsigned *cls = nullptr)
@@ -169,11 +170,11 @@ __device__ __forceinline__ bool band_coords(const Grid &g, int nbx, int nby_pack
         const int t = (int)blockIdx.x >> 3, xcd = (int)blockIdx.x & 7;
         const int k = ZG == 1 ? t : t / ZG;
         cg = ZG == 1 ? 0 : t - k * ZG;
-        const uint32_t e = g.tiles[k * 8 + xcd];
-        bx = (int)(e & 0xfffu);
-        by = (int)((e >> 12) & 0xffffu);
-        if (cls) *cls = e >> 28;
-        return e != 0xffffffffu;
+        const uint32_t e = g.tiles[k * 8 + xcd];      // (fs_tiles.h: the entry format)
+        bx = tile_entry_bx(e);
+        by = tile_entry_by(e);
+        if (cls) *cls = tile_entry_hints(e);
+        return e != TILE_PAD;
     }
     const int nby = nby_packed & 0x3fffff, FS_XCD_GROUP = (nby_packed >> 24) + 1;   // group size rides in the top byte, bit 23 = stacked, bit 22 = channel groups innermost
     const int xcd = blockIdx.x & 7;
@@ -501,7 +502,7 @@ __global__ __launch_bounds__(256) void k_jacobi_ov(Grid g, Konst<T> k, int nbx, 
 // whether any not-wall cell of the tile has a target among its 4 neighbours - only those tiles load the two extra rows of p and the
 // three rows of bcmap, every other tile is the plain source-pair sweep.  The host runs n - 2 lazy sweeps and then the last two with
 // the real K7, which leaves both physical p buffers exactly as the reference's n x (K7, sweep, swap) does (fs/pressure_updater.py).
-// Host-checked preconditions (fs_api.hip lazy_ok): every source is a not-wall cell (an inflow cell whose right neighbour is a wall
+// Host-checked preconditions (fs_core.hip lazy_ok): every source is a not-wall cell (an inflow cell whose right neighbour is a wall
 // would read that buffer's history), and rows 0 / Y-1 hold no not-wall cell (no clamped y neighbour of a computed cell).
 // bcmap byte: bit 0 target, bits 1-2 kind (0 copy, 1 mean, 2 zero), bits 3-4 direction of source 1, bits 5-6 of source 2
 // (0 = i-1, 1 = i+1, 2 = j-1, 3 = j+1).
@@ -609,7 +610,7 @@ __device__ __forceinline__ Q4<T> bc_row_h(const LaneMap &lm, const Q4<T> &c, uin
 
 // One row of the buffer as K7 would leave it, from RAW rows: m / c / n = rows j-1 / j / j+1, code = recipe bytes of row j.  Each cell's
 // boundary value is evaluated ONCE here and the stencil then runs on the finished rows (evaluating it per stencil neighbour costs 5x the
-// selects).  At the domain's first / last column sample() clamps onto the cell itself - no recipe points outside (fs_api.hip build_bc_ops).
+// selects).  At the domain's first / last column sample() clamps onto the cell itself - no recipe points outside (fs_core.hip build_bc_ops).
 // Must be called by the whole wave (cross-lane shifts).
 template <typename T>
 __device__ __forceinline__ Q4<T> bc_row(const LaneMap &lm, const Q4<T> &m, const Q4<T> &c, const Q4<T> &n, uint32_t code)

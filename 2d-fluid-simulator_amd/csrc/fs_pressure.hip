@@ -24,7 +24,7 @@ static int launch_jacobi(fs_ctx *ctx, const char *name, const Konst<T> &k, int j
         // the literal f32 sweep on packed lanes of 2 cells, 4-row tiles, per-wave plain hints in the launch list (fs_jquad.h k_jacobi_ov2; round 5:
         // 74.5-75.6 against 81.6 us for the quad form below - 8-row tiles 86, 2-row tiles 84, without the hints 79-80)
         if (ctx->use_pairs) {
-            const OvGrid og = ov_grid_lanes(ctx, jb, je, 4, 1, XCD_JACOBI, 3, true, 0, 1);      // (reach 1: the hints)
+            const OvGrid og = ov_grid(ctx, jb, je, tiles(XCD_JACOBI, LANES_PAIR_WIDE).rows(4).hints_within(1));
             const int dm = dm_const(ctx, k);
 #define FS_JAC2(DM) FS_KLAUNCH((k_jacobi_ov2<4, DM>), og.grid, dim3(og.threads), 0, ctx->stream, og.g, k, og.nbx, og.nby, jb, je, pn, pc, vs)
             return launch(ctx, name, [=] { FS_DMC(dm, FS_JAC2); });
@@ -33,7 +33,7 @@ static int launch_jacobi(fs_ctx *ctx, const char *name, const Konst<T> &k, int j
     // overlapped-wave register tiles of quads: the source-pair form streams best with 1-row tiles at 8 waves/SIMD (76 vs 79 us), the v-reading form (f64)
     // with 4-row tiles (round 4: 84.7 against 85.9-86.4 us; the tile heights 2 and 3 of rounds 2 - 4 went with their switch in round 6)
     constexpr int RT = SRC ? 1 : 4;
-    const OvGrid og = ov_grid(ctx, jb, je, RT, 1, XCD_JACOBI);
+    const OvGrid og = ov_grid(ctx, jb, je, tiles(XCD_JACOBI, LANES_QUAD).rows(RT));
     const int dm = SRC ? 0 : dm_const(ctx, k);           // the source-pair form divides nothing
 #define FS_JAC(DM) FS_KLAUNCH((k_jacobi_ov<SRC, RT, DM, T>), og.grid, dim3(256), 0, ctx->stream, og.g, k, og.nbx, og.nby, jb, je, pn, pc, vs)
     return launch(ctx, name, [=] { FS_DMC(dm, FS_JAC); });
@@ -97,7 +97,7 @@ int fs_jacobi_sweep_lazy(fs_ctx *ctx, fs_field *pn, const fs_field *pc, const fs
     FS_REQUIRE(pn != pc, "Jacobi needs two distinct pressure fields");
     FS_ROWS();
     if (!(ctx->lazy_ok && ctx->use_march)) { set_error("this mask does not admit the lazy pressure boundary condition (fs_lazy_bc_ok)"); return FS_ERR_UNSUPPORTED; }
-    const OvGrid og = ov_grid(ctx, row_begin, row_end, 1, 1, XCD_JACOBI);
+    const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_JACOBI, LANES_QUAD).rows(1));
     FS_DISPATCH(ctx, {
         return launch(ctx, "jacobi_sweep_lazy", [=] {
             FS_KLAUNCH((k_jacobi_lazy<T>), og.grid, dim3(256), 0, ctx->stream, og.g, og.nbx, og.nby, row_begin, row_end,
@@ -117,7 +117,7 @@ int fs_jacobi_pair_lazy(fs_ctx *ctx, fs_field *pn, const fs_field *pc, const fs_
     FS_ROWS();
     if (!(ctx->lazy_ok && ctx->use_march)) { set_error("this mask does not admit the lazy pressure boundary condition (fs_lazy_bc_ok)"); return FS_ERR_UNSUPPORTED; }
     const int rt = (mode & 2) ? 2 : 3;      // rows per tile: 3 is within 2 % of the best of 2 / 3 / 4 from res 1024 to 4096 (the third tile path at 3 rows: 97 VGPRs, one wave per SIMD less)
-    const OvGrid og = ov_grid(ctx, row_begin, row_end, rt, 1, XCD_JACOBI, false);      // (dense: its general rows ride in leading z slices)
+    const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_JACOBI, LANES_QUAD).rows(rt).dense_if(true));      // (dense: its general rows ride in leading z slices)
     FS_DISPATCH(ctx, {
         return launch(ctx, "jacobi_pair_lazy", [=] {
             switch (mode) {
@@ -162,7 +162,7 @@ int fs_rbsor_iteration(fs_ctx *ctx, double dt, double dx, double omega, fs_field
     }
     // lanes of 2 cells, 4-row tiles (fs_k34n.h k_rbsor_iter_n): 119 -> 115 us at bc5 res 4096 against the 3-row quad tiles it replaces, f64 (bc3 res
     // 4096) 318 -> 289; 2 / 6 rows: 129 / 115
-    const OvGrid og = ov_grid_lanes(ctx, row_begin, row_end, 4, 1, XCD_RBSOR, 3, false);
+    const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_RBSOR, LANES_PAIR_WIDE).rows(4).dense_if(true));
     FS_DISPATCH(ctx, {
         auto k = make_konst<T>(ctx, dt, dx, 1.0, 0.0, omega);
 #define FS_RBN4(DM) FS_KLAUNCH((k_rbsor_iter_n<2, 4, DM, T>), og.grid, dim3(256), 0, ctx->stream, og.g, k, og.nbx, og.nby, row_begin, row_end, \
@@ -191,10 +191,10 @@ int fs_jacobi_quad_lazy(fs_ctx *ctx, fs_field *pn, const fs_field *pc, const fs_
     constexpr int rt = 4;
 #define FS_JQ(RT, PATH) FS_KLAUNCH((k_jacobi_quad<2, RT, PATH, T>), og.grid, dim3(og.threads), 0, ctx->stream, og.g, og.nbx, og.nby, row_begin, row_end, \
                                (const uint8_t *)ctx->d_bcmap, (T *)pn->d, (const T *)pc->d, (const T *)src->d)
-    // ONE launch of one-wave workgroups whose list entry says which body the tile takes, masked tiles first (round 6; fs_launch.h ov_grid_lanes: the hinted
+    // ONE launch of one-wave workgroups whose list entry says which body the tile takes, masked tiles first (round 6; fs_launch.h one_wave_where_hinted: the hinted
     // launches of the pressure families) - bc5 res 4096 122.5 -> 108.7 us per pass against rounds 4 - 5's two compact launches over the all-fluid and the other
     // workgroups (81.4 + 49.8; 137.5 dense), bc2 res 1600 30.2 -> 23.9 against the 4-wave workgroups with per-wave hints
-    const OvGrid og = ov_grid_lanes(ctx, row_begin, row_end, rt, 1, XCD_RBSOR, 2, true, 0, 4);      // (reach 4: the hints)
+    const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_RBSOR, LANES_PAIR).rows(rt).hints_within(4));
     return launch(ctx, "jacobi_quad_lazy", [=] {
         FS_JQ(4, 2);
     });
@@ -210,7 +210,7 @@ int fs_jacobi_finish(fs_ctx *ctx, fs_field *pc_out, fs_field *pn, const fs_field
     FS_ROWS();
     if (!(ctx->jq_ok && ctx->use_march && ctx->dtype == 0)) { set_error("this mask / precision does not admit the multi-sweep Jacobi passes (fs_jacobi_quad_ok)"); return FS_ERR_UNSUPPORTED; }
     using T = float;
-    const OvGrid og = ov_grid_lanes(ctx, row_begin, row_end, 4, 1, XCD_RBSOR, 2, true, 0, 2);      // (per-wave plain hints: two sweeps reach 2 rows)
+    const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_RBSOR, LANES_PAIR).rows(4).hints_within(2));      // (two sweeps reach 2 rows)
     return launch(ctx, "jacobi_finish", [=] {
         FS_KLAUNCH((k_jacobi_finish<2, 4, T>), og.grid, dim3(og.threads), 0, ctx->stream, og.g, og.nbx, og.nby, row_begin, row_end,
                            (const uint8_t *)ctx->d_bcmap, (T *)pc_out->d, (T *)pn->d, (const T *)pc->d, (const T *)src->d);
@@ -251,15 +251,15 @@ int fs_rbsor_pair(fs_ctx *ctx, double dt, double dx, double omega, fs_field *pc_
         if (!full && (ctx->rbpair_split == 2 || (ctx->rbpair_split == 1 && (size_t)ctx->X * ctx->Y >= ((size_t)1 << 23)))) {
             // (round 6: ONE launch of one-wave workgroups over both kinds of tile, as the f32 pass has it, loses here - 514-527 against 424 us at bc3 res 4096:
             //  the double2 bodies hold 220-256 VGPRs, and the masked one then sets the occupancy of the all-fluid tiles too)
-            const OvGrid og = ov_grid_lanes(ctx, row_begin, row_end, 4, 1, XCD_RBSOR, 2, true, 1, 4, 1);
-            const OvGrid ogb = ov_grid_lanes(ctx, row_begin, row_end, 2, 1, XCD_RBSOR, 2, true, 2, 4, 1, 4);
+            const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_RBSOR, LANES_PAIR).rows(4).waves(1).plain_within(4));
+            const OvGrid ogb = ov_grid(ctx, row_begin, row_end, tiles(XCD_RBSOR, LANES_PAIR).rows(2).waves(1).boundary_within(4).parent_rows(4));
             if (og.g.tiles && ogb.g.tiles) {
                 int rc = launch(ctx, "rbsor_pair", [=] { FS_RBPD(4, 3, false); });
                 if (rc) return rc;
                 { const OvGrid og = ogb; return launch(ctx, "rbsor_pair_bnd", [=] { FS_RBPD(2, 2, false); }); }
             }
         }
-        const OvGrid og = ov_grid_lanes(ctx, row_begin, row_end, 2, 1, XCD_RBSOR, 2, !full, 0, 4);
+        const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_RBSOR, LANES_PAIR).rows(2).dense_if(full).hints_within(4));
         return launch(ctx, "rbsor_pair", [=] { if (full) FS_RBPD(2, 2, true); else FS_RBPD(2, 2, false); });
     }
     using T = float;
@@ -281,7 +281,7 @@ int fs_rbsor_pair(fs_ctx *ctx, double dt, double dx, double omega, fs_field *pc_
     // 23.0 -> 19.0, res 800 20.0 -> 16.7; res 512 14.5 -> 14.9 and res 400 12.6 -> 14.0 (the 2-row tiles of small grids stay there).  Round 5's two
     // launches over the two kinds of tile (k_rbsor_pair_stack, then the masked kernel: from 8 M cells) went with it.
     if (!full && (ctx->rbpair_split == 2 || (ctx->rbpair_split == 1 && (size_t)ctx->X * ctx->Y >= ((size_t)1 << 20)))) {
-        const OvGrid og = ov_grid_lanes(ctx, row_begin, row_end, 8, 1, XCD_RBSOR, 2, true, 3, 4, 1, 16, ctx->halo != 0);
+        const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_RBSOR, LANES_PAIR).rows(8).waves(1).mixed_within(4).parent_rows(16).classes_on_slabs(ctx->halo != 0));
         if (og.g.tiles) {
 #define FS_RBA_K(PAR, DM) FS_KLAUNCH((k_rbsor_pair_all<2, PAR, DM, T>), og.grid, dim3(128), 0, ctx->stream, og.g, k, og.nbx, og.nby, row_begin, row_end, \
                                (const uint8_t *)ctx->d_bcmap, (T *)pc_out->d, (T *)pn_out->d, (const T *)pc->d, (const T *)pn->d, (const T *)vc->d)
@@ -290,7 +290,7 @@ int fs_rbsor_pair(fs_ctx *ctx, double dt, double dx, double omega, fs_field *pc_
         }
     }
     // (one launch: the list's entries carry a per-wave "plain" hint - a wave that sees nothing but fluid within 4 rows skips its mask loads)
-    const OvGrid og = ov_grid_lanes(ctx, row_begin, row_end, rt, 1, XCD_RBSOR, 2, !full, 0, 4);
+    const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_RBSOR, LANES_PAIR).rows(rt).dense_if(full).hints_within(4));
     return launch(ctx, "rbsor_pair", [=] {
         if (full) FS_RBP_PAR(4, 0, 2, true);
         else if (rt == 2) FS_RBP_DM(2, 2);
@@ -323,7 +323,7 @@ int fs_poisson_source(fs_ctx *ctx, double dt, double dx, fs_field *src, const fs
     FS_DISPATCH(ctx, {
         auto k = make_konst<T>(ctx, dt, dx, 1.0);
         if (ctx->use_pairs) {
-            const OvGrid og = ov_grid_lanes(ctx, row_begin, row_end, 4, 1, XCD_JACOBI, 3);      // (deep-wall workgroups skipped: nobody reads the source there)
+            const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_JACOBI, LANES_PAIR_WIDE).rows(4));      // (deep-wall workgroups skipped: nobody reads the source there)
 #define FS_PSN(DM) FS_KLAUNCH((k_poisson_source_n<2, 4, DM, T>), og.grid, dim3(og.threads), 0, ctx->stream, og.g, k, og.nbx, og.nby, row_begin, row_end, (T *)src->d, (const T *)vc->d)
             return launch(ctx, "poisson_source", [=] { FS_DMC(dm_const(ctx, k), FS_PSN); });
         }

@@ -25,7 +25,7 @@
 // value in all four buffers (zero, or - after an upload - whatever one FULL pass carries over), so only fluid cells and K7 targets
 // are stored.
 //
-// Validity of the shrinking-window argument (host-checked per mask, fs_api.hip build_bc_ops -> rb_pair_ok): a recipe never reads a
+// Validity of the shrinking-window argument (host-checked per mask, fs_core.hip build_bc_ops -> rb_pair_ok): a recipe never reads a
 // source that lies on the far side of its target as seen from a fluid reader (a wall one cell thick between two fluid regions) -
 // then whoever reads a boundary value finds the recipe's sources inside its own radius-1 neighbourhood, and the plain stencil's
 // footprint suffices; and the first / last domain row hold no fluid cell (no clamped y neighbour of a relaxed cell).  All of the
@@ -477,7 +477,7 @@ __device__ __forceinline__ void rbsor_pair_wave_at(const Grid &g, const Konst<T>
     const LaneMapN<N> lm = lane_map_n<N>(g, wx);
     const int i0 = lm.i0, j0 = jb + ty * RT;
     unsigned fl[W];
-    // plain: the host listed this workgroup (PATH 3) / this wave (hint) as seeing nothing but fluid within reach (fs_api.hip tile_list) - or the
+    // plain: the host listed this workgroup (PATH 3) / this wave (hint) as seeing nothing but fluid within reach (fs_tiles.h plain_box) - or the
     // masks say so.  ONE instance of each path in the kernel.
     bool plain = PATH == 3 || hint;
     if (!plain && bnd_fluid) {
@@ -528,7 +528,7 @@ __device__ __forceinline__ void rbsor_pair_wave(const Grid &g, const Konst<T> &k
 // waves 3.07 rounds of long-lived waves at 3 per SIMD.  Measured (round 6): the stacked plain part does not care about its occupancy - 113.9 /
 // 113.5 / 112.9 us at 5 / 3 / 2.5 waves per SIMD (dynamic LDS holding it down) - so both bodies fit ONE kernel at the boundary body's register
 // budget, and the boundary tiles, listed first, fill in while the all-fluid ones stream (what k_cip_step_all did for fs_cip_step).
-// The list (fs_core.hip tile_list, class 3) is over units of 8 rows: an all-fluid 16-row parent tile is ONE entry at its lower unit (hint bit 0) and
+// The list (fs_tiles.h entry_mixed, TILES_MIXED) is over units of 8 rows: an all-fluid 16-row parent tile is ONE entry at its lower unit (hint bit 0) and
 // runs the two stacked waves; a unit of any other parent is an entry whose two waves take its two 4-row tiles with the masked body (hint bits
 // 1 / 2: fluid in the rows of tile 0 / 1 - the window is then requested with the masks, not behind them).
 template <int N, int PAR0, int DM, typename T>

@@ -24,7 +24,7 @@ static int launch_k34(fs_ctx *ctx, const char *name, const char *name_bnd, doubl
     const int N = ctx->X % 4 != 0 || C == 3 ? 2 : (cells >= ((size_t)1 << 23) || cells < ((size_t)1 << 21) ? 2 : 4);
     // (below 1 M cells: 1-row tiles for the dye's three channels - a launch is one wave's chain there, fs_ctx::small_tiles; res 400: 17.6 against
     //  17.1 k steps/s with the dye; the velocity's pass stays on 2 rows: 29.0 against 28.1 k)
-    const int RT = N == 4 ? 2 : (cells >= ((size_t)1 << 23) ? 4 : (small_tiles(ctx) && !full && C == 3 ? 1 : 2)), geo = N == 2 ? 3 : 4;
+    const int RT = N == 4 ? 2 : (cells >= ((size_t)1 << 23) ? 4 : (small_tiles(ctx) && !full && C == 3 ? 1 : 2)), geo = N == 2 ? LANES_PAIR_WIDE : LANES_QUAD;
 #define FS_K34(NN, R, DM, PL) FS_KLAUNCH((k_cip_grad_advect_n<C, NN, R, DM, PL, CLAMP, T>), og.grid, dim3(og.threads), 0, ctx->stream, og.g, k, og.nbx, og.nby, jb, je, \
         (T *)f_out->d, (T *)gx_out->d, (T *)gy_out->d, (const T *)fn->d, (const T *)fc->d, (const T *)gxc->d, (const T *)gyc->d, v ? (const T *)v->d : (const T *)nullptr, \
         f_out->hot, (const uint8_t *)ctx->d_bcmap, full)
@@ -39,8 +39,8 @@ static int launch_k34(fs_ctx *ctx, const char *name, const char *name_bnd, doubl
     // Compact launch in two parts on large single-GPU grids (as fs_rbsor_pair): the workgroups that see nothing but fluid within
     // reach run without mask loads, selects and conditional stores (PLAIN), the others the general tile
     if (!full && RT != 1 && (ctx->rbpair_split == 2 || (ctx->rbpair_split == 1 && (size_t)ctx->X * ctx->Y >= ((size_t)1 << 23)))) {
-        const OvGrid og = ov_grid_lanes(ctx, jb, je, RT, C, XCD_ADVECT, geo, true, 1, 2, 1);
-        const OvGrid ogb = ov_grid_lanes(ctx, jb, je, RT, C, XCD_ADVECT, geo, true, 2, 2, 1);
+        const OvGrid og = ov_grid(ctx, jb, je, tiles(XCD_ADVECT, geo).rows(RT).channel_groups(C).waves(1).plain_within(2));
+        const OvGrid ogb = ov_grid(ctx, jb, je, tiles(XCD_ADVECT, geo).rows(RT).channel_groups(C).waves(1).boundary_within(2));
         if (og.g.tiles && ogb.g.tiles) {
             int rc = launch(ctx, name, [=] { FS_K34_ANY(P); });
             if (rc) return rc;
@@ -49,7 +49,7 @@ static int launch_k34(fs_ctx *ctx, const char *name, const char *name_bnd, doubl
     }
     // (the carrying pass visits every tile.  The per-wave plain hint of fs_rbsor_pair was tried here too: 78.8-79.2 against 77.4-78.8 us at bc2 res 1600 -
     //  the kernel then holds four tile bodies instead of two)
-    const OvGrid og = ov_grid_lanes(ctx, jb, je, RT, C, XCD_ADVECT, geo, !full);
+    const OvGrid og = ov_grid(ctx, jb, je, tiles(XCD_ADVECT, geo).rows(RT).channel_groups(C).dense_if(full));
     return launch(ctx, name, [=] { if (N == 2 && RT == 1) FS_DMX(dm, FS_K34_21); else FS_K34_ANY(); });
 }
 
@@ -70,7 +70,7 @@ int fs_mac_update(fs_ctx *ctx, int scheme, double dt, double dx, double re, fs_f
             // form it replaces; f64: 424 -> 306 with 2-row tiles), 2 rows on small grids (more workgroups) and for f64 (registers)
             // (round 6, packed body: 6-row tiles 144.7-151.1 against 154.2 us, 8-row tiles 157.8-158.9 (111 VGPRs = 4 waves): left at 4)
             const int rt = sizeof(T) == 4 && (size_t)ctx->X * ctx->Y >= ((size_t)1 << 20) ? 4 : 2;
-            const OvGrid og = ov_grid_lanes(ctx, row_begin, row_end, rt, 1, XCD_NONADV, 3, true, 0, 2);      // (reach: per-wave plain hints in the list)
+            const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_NONADV, LANES_PAIR_WIDE).rows(rt).hints_within(2));
             return launch(ctx, scheme == FS_UPWIND ? "mac_update_upwind" : "mac_update_kk", [=] {
 #define FS_K2MN(SS, RR, PP) FS_KLAUNCH((k_mac_update_n<SS, 2, RR, PP, T>), og.grid, dim3(og.threads), 0, ctx->stream, og.g, k, og.nbx, og.nby, row_begin, row_end, \
             (T *)vn->d, (const T *)vc->d, (const T *)pc->d, vn->hot)
@@ -130,7 +130,7 @@ int fs_cip_nonadv(fs_ctx *ctx, double dt, double dx, double re, fs_field *fn, co
             // it replaces (2 rows: 112, 8 rows: 106-110)
             // (small grids - fewer waves than SIMDs, a launch takes as long as one wave's chain: 2-row tiles, fs_ctx::small_tiles)
             const bool small = small_tiles(ctx);
-            const OvGrid og = ov_grid_lanes(ctx, row_begin, row_end, small ? 2 : 4, 1, XCD_NONADV, 3, true, 0, 1);      // (reach 1: per-wave plain hints)
+            const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_NONADV, LANES_PAIR_WIDE).rows(small ? 2 : 4).hints_within(1));
             const int clear3 = whole_grid(ctx, row_begin, row_end);      // (fs_device.h "hot" word [3])
             return launch(ctx, "cip_nonadv", [=] {
 #define FS_K2N4(DM) FS_KLAUNCH((k_cip_nonadv_n<2, 4, DM, T>), og.grid, dim3(og.threads), 0, ctx->stream, og.g, k, og.nbx, og.nby, row_begin, row_end, (T *)fn->d, (const T *)fc->d, (const T *)pc->d, fn->hot, clear3)
@@ -154,7 +154,7 @@ int fs_cip_nonadv_dye(fs_ctx *ctx, double dt, double dx, double re, fs_field *dn
         if (ctx->use_pairs) {
             // lanes of 2 cells, 4-row tiles (fs_k34n.h k_cip_nonadv_dye_n), compact launch: 141 -> 122-130 us at bc5 res 4096 against the one-row quad form
             const bool small = small_tiles(ctx);       // (2-row tiles, see fs_cip_nonadv)
-            const OvGrid og = ov_grid_lanes(ctx, row_begin, row_end, small ? 2 : 4, 1, XCD_NONADV, 3, true, 0, 1);
+            const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_NONADV, LANES_PAIR_WIDE).rows(small ? 2 : 4).hints_within(1));
             return launch(ctx, "cip_nonadv_dye", [=] {
 #define FS_K12N(DM) FS_KLAUNCH((k_cip_nonadv_dye_n<2, 4, DM, T>), og.grid, dim3(og.threads), 0, ctx->stream, og.g, k, og.nbx, og.nby, row_begin, row_end, (T *)dn->d, (const T *)dc->d)
 #define FS_K12N2(DM) FS_KLAUNCH((k_cip_nonadv_dye_n<2, 2, DM, T>), og.grid, dim3(og.threads), 0, ctx->stream, og.g, k, og.nbx, og.nby, row_begin, row_end, (T *)dn->d, (const T *)dc->d)
@@ -179,7 +179,7 @@ int fs_cip_nonadv_grad(fs_ctx *ctx, double dx, fs_field *fxn, fs_field *fyn, con
     FS_DISPATCH(ctx, {
         auto k = make_konst<T>(ctx, 1.0, dx, 1.0);
         if (ctx->use_march) {
-            const OvGrid og = ov_grid(ctx, row_begin, row_end, 1, C == 2 ? 1 : 3, XCD_GRAD);
+            const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_GRAD, LANES_QUAD).rows(1).channel_groups(C == 2 ? 1 : 3));
             return launch(ctx, C == 2 ? "cip_nonadv_grad" : "cip_nonadv_grad_c3", [=] {
 #define FS_K3Q_V(DM) FS_K3Q(2, 2, DM)
 #define FS_K3Q_D(DM) FS_K3Q(3, 1, DM)
@@ -211,7 +211,7 @@ int fs_cip_advect(fs_ctx *ctx, double dt, double dx, fs_field *fn, fs_field *fxn
     FS_DISPATCH(ctx, {
         auto k = make_konst<T>(ctx, dt, dx, 1.0);
         const bool self = (v == fc);
-        const OvGrid og = ov_grid(ctx, row_begin, row_end, 1, (C == 2 && !self) ? 2 : 1, XCD_ADVECT);   // C == 3: one pass over the channels
+        const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_ADVECT, LANES_QUAD).rows(1).channel_groups((C == 2 && !self) ? 2 : 1));   // C == 3: one pass over the channels
         const dim3 qgrid = og.grid;
         return launch(ctx, C == 2 ? "cip_advect" : "cip_advect_c3", [=] {
             if (ctx->use_march) {
@@ -236,7 +236,7 @@ int fs_cip_advect_dye_clamped(fs_ctx *ctx, double dt, double dx, fs_field *fn, f
     FS_REQUIRE(fn != fc && fxn != fxc && fyn != fyc, "outputs must not alias inputs");
     FS_REQUIRE(ctx->use_march, "needs X % 4 == 0 (use fs_cip_advect + fs_clamp_field)");
     FS_ROWS();
-    const OvGrid og = ov_grid(ctx, row_begin, row_end, 1, 1, XCD_ADVECT);
+    const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_ADVECT, LANES_QUAD).rows(1));
     FS_DISPATCH(ctx, {
         auto k = make_konst<T>(ctx, dt, dx, 1.0);
         return launch(ctx, "cip_advect_c3_clamped", [=] {
@@ -281,7 +281,7 @@ static bool cip_step_multi_part(const fs_ctx *ctx)
     // 1200 10.35 -> 11.0 k, res 1600 6 150 -> 6 700).  As two launches the form paid from 2.6 M cells; with K2 as a third launch over the boundary tiles' rows and
     // the general K3 + K4 kernel there (the round's first form) from 8 M.
     const bool big = ctx->rbpair_split == 2 || ctx->rbpair_split == 1;
-    return ctx->mask_set && ctx->fuse_k2 != 0 && big && ctx->dtype == 0 && ctx->use_pairs && !ctx->h_act2.empty() && (ctx->tile_list_mask & XCD_ADVECT);
+    return ctx->mask_set && ctx->fuse_k2 != 0 && big && ctx->dtype == 0 && ctx->use_pairs && !ctx->act.pair.empty() && (ctx->tile_list_mask & XCD_ADVECT);
 }
 int fs_cip_step_ok(const fs_ctx *ctx, int *ok)
 {
@@ -299,13 +299,10 @@ int fs_cip_step_tiles(fs_ctx *ctx, int *plain, int *boundary, int *band, int *ti
     *plain = *boundary = *band = 0; *tile_rows = 4; *tile_cells = 120;
     if (!cip_step_multi_part(ctx) || ctx->capturing || ctx->tape_rec) return FS_OK;
     if (ctx->fuse_k2 >= 2 && small_tiles(ctx)) *tile_rows = 2;
-    const OvGrid ogp = ov_grid_lanes(ctx, 0, ctx->rows, *tile_rows, 1, XCD_ADVECT, 2, true, 1, 2, 1);
-    const OvGrid ogb = ov_grid_lanes(ctx, 0, ctx->rows, *tile_rows, 1, XCD_ADVECT, 2, true, 2, 2, 1);
-    for (const auto &kv : ctx->tile_lists) {
-        if (!kv.second.d) continue;
-        if (kv.second.d == ogp.g.tiles) *plain = kv.second.count;
-        if (kv.second.d == ogb.g.tiles) *boundary = kv.second.count;
-    }
+    const TileLaunch step_tiles = tiles(XCD_ADVECT, LANES_PAIR).rows(*tile_rows).waves(1);
+    const OvGrid ogp = ov_grid(ctx, 0, ctx->rows, step_tiles.plain_within(2)), ogb = ov_grid(ctx, 0, ctx->rows, step_tiles.boundary_within(2));
+    if (ogp.list) *plain = ogp.list->count;
+    if (ogb.list) *boundary = ogb.list->count;
     return FS_OK;
 }
 
@@ -336,26 +333,26 @@ int fs_cip_step(fs_ctx *ctx, double dt, double dx, double re, fs_field *v_out, f
     if (cip_step_multi_part(ctx) && !full && rows_ok && (slab || (row_begin == 0 && row_end == ctx->rows))) {
         auto k = make_konst<T>(ctx, dt, dx, re);
         const int dm = dm_all(ctx, k);
-#define FS_K234(KERNEL, DM) FS_KLAUNCH((KERNEL<RT, DM>), og.grid, dim3(128), 0, ctx->stream, og.g, k, og.nbx, og.nby, row_begin, row_end, \
+        const TileLaunch step_tiles = tiles(XCD_ADVECT, LANES_PAIR).waves(1);      // (one entry per tile, two component waves each)
+#define FS_K234(KERNEL, R, DM) FS_KLAUNCH((KERNEL<R, DM>), og.grid, dim3(128), 0, ctx->stream, og.g, k, og.nbx, og.nby, row_begin, row_end, \
         (T *)v_out->d, (T *)gx_out->d, (T *)gy_out->d, (T *)fn->d, (const T *)fc->d, (const T *)pc->d, (const T *)gxc->d, (const T *)gyc->d, v_out->hot, fn->hot)
-#define FS_K234A(DM) FS_K234(k_cip_step_all, DM)
-#define FS_K234P(DM) FS_K234(k_cip_step_plain, DM)
-#define FS_K234B(DM) FS_K234(k_cip_step_bnd, DM)
+#define FS_K234A(DM) FS_K234(k_cip_step_all, RT, DM)
+#define FS_K234A2(DM) FS_K234(k_cip_step_all, 2, DM)
+#define FS_K234P(DM) FS_K234(k_cip_step_plain, RT, DM)
+#define FS_K234B(DM) FS_K234(k_cip_step_bnd, RT, DM)
         if (ctx->fuse_k2 >= 2) {
             // one launch over both kinds of tile: the class 0 list, whose entries carry the per-tile "all fluid within reach" hint
             // (grids below FS_SMALL_CELLS: 2-row tiles - a launch there lasts as long as one wave's chain, fs_launch.h small_tiles)
             if (small_tiles(ctx)) {
-                const OvGrid oga = ov_grid_lanes(ctx, row_begin, row_end, 2, 1, XCD_ADVECT, 2, true, 0, 2, 1, 0, slab);
-#define FS_K234A2(DM) FS_KLAUNCH((k_cip_step_all<2, DM>), og.grid, dim3(128), 0, ctx->stream, og.g, k, og.nbx, og.nby, row_begin, row_end, \
-        (T *)v_out->d, (T *)gx_out->d, (T *)gy_out->d, (T *)fn->d, (const T *)fc->d, (const T *)pc->d, (const T *)gxc->d, (const T *)gyc->d, v_out->hot, fn->hot)
+                const OvGrid oga = ov_grid(ctx, row_begin, row_end, step_tiles.rows(2).hints_within(2));
                 if (oga.g.tiles) return launch(ctx, "cip_step", [=] { const OvGrid og = oga; FS_DMA(dm, FS_K234A2); });
             }
-            const OvGrid oga = ov_grid_lanes(ctx, row_begin, row_end, RT, 1, XCD_ADVECT, 2, true, 0, 2, 1, 0, slab);
+            const OvGrid oga = ov_grid(ctx, row_begin, row_end, step_tiles.rows(RT).hints_within(2));
             if (oga.g.tiles) return launch(ctx, "cip_step", [=] { const OvGrid og = oga; FS_DMA(dm, FS_K234A); });
         }
-        // two launches: the all-fluid tiles, the others (one entry per tile, two waves each)
-        const OvGrid ogp = ov_grid_lanes(ctx, row_begin, row_end, RT, 1, XCD_ADVECT, 2, true, 1, 2, 1, 0, slab);
-        const OvGrid ogb = ov_grid_lanes(ctx, row_begin, row_end, RT, 1, XCD_ADVECT, 2, true, 2, 2, 1, 0, slab);
+        // two launches: the all-fluid tiles, the others
+        const OvGrid ogp = ov_grid(ctx, row_begin, row_end, step_tiles.rows(RT).plain_within(2).classes_on_slabs(slab));
+        const OvGrid ogb = ov_grid(ctx, row_begin, row_end, step_tiles.rows(RT).boundary_within(2).classes_on_slabs(slab));
         if (ogp.g.tiles && ogb.g.tiles) {
             int rc = launch(ctx, "cip_step", [=] { const OvGrid og = ogp; FS_DMA(dm, FS_K234P); });
             if (rc) return rc;
@@ -404,28 +401,27 @@ int fs_cip_step_dye(fs_ctx *ctx, double dt, double dx, double re, fs_field *d_ou
         auto k = make_konst<T>(ctx, dt, dx, re);
         const int dm = dm_all(ctx, k);
         // k_cip_dye<RT, DM, CLAMP, KIND> over a list: KIND 1 - the all-fluid tiles, 2 - the others, 0 - both (class 0 list with the per-tile hint)
-#define FS_KD(DM, CL, KIND) FS_KLAUNCH((k_cip_dye<RT, DM, CL, KIND>), og.grid, dim3(64), 0, ctx->stream, og.g, k, og.nbx, og.nby, row_begin, row_end, \
+        const TileLaunch step_tiles = tiles(XCD_ADVECT, LANES_PAIR).waves(1).channel_groups(3);
+#define FS_KD(R, DM, CL, KIND) FS_KLAUNCH((k_cip_dye<R, DM, CL, KIND>), og.grid, dim3(64), 0, ctx->stream, og.g, k, og.nbx, og.nby, row_begin, row_end, \
         (T *)d_out->d, (T *)gx_out->d, (T *)gy_out->d, (T *)fn->d, (const T *)fc->d, (const T *)gxc->d, (const T *)gyc->d, (const T *)v->d)
-#define FS_KD_C0(DM) FS_KD(DM, true, 0)
-#define FS_KD_N0(DM) FS_KD(DM, false, 0)
-#define FS_KD_C1(DM) FS_KD(DM, true, 1)
-#define FS_KD_N1(DM) FS_KD(DM, false, 1)
-#define FS_KD_C2(DM) FS_KD(DM, true, 2)
-#define FS_KD_N2(DM) FS_KD(DM, false, 2)
+#define FS_KD_C0(DM) FS_KD(RT, DM, true, 0)
+#define FS_KD_N0(DM) FS_KD(RT, DM, false, 0)
+#define FS_KD_C1(DM) FS_KD(RT, DM, true, 1)
+#define FS_KD_N1(DM) FS_KD(RT, DM, false, 1)
+#define FS_KD_C2(DM) FS_KD(RT, DM, true, 2)
+#define FS_KD_N2(DM) FS_KD(RT, DM, false, 2)
+#define FS_KD2_C(DM) FS_KD(2, DM, true, 0)
+#define FS_KD2_N(DM) FS_KD(2, DM, false, 0)
         if (ctx->fuse_k2 >= 2) {
             if (small_tiles(ctx)) {      // (2-row tiles, as fs_cip_step)
-                const OvGrid oga = ov_grid_lanes(ctx, row_begin, row_end, 2, 3, XCD_ADVECT, 2, true, 0, 2, 1, 0, slab);
-#define FS_KD2(DM, CL) FS_KLAUNCH((k_cip_dye<2, DM, CL, 0>), og.grid, dim3(64), 0, ctx->stream, og.g, k, og.nbx, og.nby, row_begin, row_end, \
-        (T *)d_out->d, (T *)gx_out->d, (T *)gy_out->d, (T *)fn->d, (const T *)fc->d, (const T *)gxc->d, (const T *)gyc->d, (const T *)v->d)
-#define FS_KD2_C(DM) FS_KD2(DM, true)
-#define FS_KD2_N(DM) FS_KD2(DM, false)
+                const OvGrid oga = ov_grid(ctx, row_begin, row_end, step_tiles.rows(2).hints_within(2));
                 if (oga.g.tiles) return launch(ctx, "cip_step_dye", [=] { const OvGrid og = oga; if (clamp01) FS_DMA(dm, FS_KD2_C); else FS_DMA(dm, FS_KD2_N); });
             }
-            const OvGrid oga = ov_grid_lanes(ctx, row_begin, row_end, RT, 3, XCD_ADVECT, 2, true, 0, 2, 1, 0, slab);
+            const OvGrid oga = ov_grid(ctx, row_begin, row_end, step_tiles.rows(RT).hints_within(2));
             if (oga.g.tiles) return launch(ctx, "cip_step_dye", [=] { const OvGrid og = oga; if (clamp01) FS_DMA(dm, FS_KD_C0); else FS_DMA(dm, FS_KD_N0); });
         }
-        const OvGrid ogp = ov_grid_lanes(ctx, row_begin, row_end, RT, 3, XCD_ADVECT, 2, true, 1, 2, 1, 0, slab);
-        const OvGrid ogb = ov_grid_lanes(ctx, row_begin, row_end, RT, 3, XCD_ADVECT, 2, true, 2, 2, 1, 0, slab);
+        const OvGrid ogp = ov_grid(ctx, row_begin, row_end, step_tiles.rows(RT).plain_within(2).classes_on_slabs(slab));
+        const OvGrid ogb = ov_grid(ctx, row_begin, row_end, step_tiles.rows(RT).boundary_within(2).classes_on_slabs(slab));
         if (ogp.g.tiles && ogb.g.tiles) {
             int rc = launch(ctx, "cip_step_dye", [=] { const OvGrid og = ogp; if (clamp01) FS_DMA(dm, FS_KD_C1); else FS_DMA(dm, FS_KD_N1); });
             if (rc) return rc;
@@ -479,7 +475,7 @@ int fs_vort_confine(fs_ctx *ctx, double dt, double dx, double weight, fs_field *
     // lanes of 2 cells (fs_k34n.h k_vort_n), 4-row tiles, compact launch: 100 -> 95 us at bc5 res 4096 against the quad form it replaces (6 / 8 rows:
     // 102 / 103; f64 at bc3 res 4096: 251 -> 224)
     const bool small = small_tiles(ctx) && !vort;      // (small grids: 2-row tiles, see fs_cip_nonadv)
-    const OvGrid og = ov_grid_lanes(ctx, row_begin, row_end, small ? 2 : 4, 1, XCD_VORT, 3, true, 0, 2);      // (reach 2: per-wave plain hints in the list)
+    const OvGrid og = ov_grid(ctx, row_begin, row_end, tiles(XCD_VORT, LANES_PAIR_WIDE).rows(small ? 2 : 4).hints_within(2));
     FS_DISPATCH(ctx, {
         auto k = make_konst<T>(ctx, dt, dx, 1.0, weight);
         const int dm = dm_dx(ctx, k);
