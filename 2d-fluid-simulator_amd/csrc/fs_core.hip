@@ -580,6 +580,8 @@ int fs_destroy(fs_ctx *ctx)
     ctx->histories.clear();
     for (fs_mean *m : ctx->means) mean_release(m);
     ctx->means.clear();
+    for (fs_modes *m : ctx->modes) modes_release(m);
+    ctx->modes.clear();
     for (fs_loads *l : ctx->loads) loads_release(l);
     ctx->loads.clear();
     for (fs_tracer *t : ctx->tracers) tracer_release(t);

@@ -1,13 +1,17 @@
 // fs_diag.hip - C-ABI entry points of what reads the flow without changing it: the flow diagnostics (fs_stats.h), the per-step history ring
-// (fs_history.h), the body surface loads (fs_loads.h) and the time averages (fs_mean.h), with the release functions of their objects.
+// (fs_history.h), the body surface loads (fs_loads.h), the time averages (fs_mean.h) and the harmonic modes (fs_modes.h), with the release
+// functions of their objects.
 #include "fs_launch.h"
 #include "fs_stats.h"
 #include "fs_mean.h"
+#include "fs_modes.h"
 #include "fs_loads.h"
 
 static_assert(fs::STATS_N == FS_FLOW_NSTAT, "fs_stats.h and include/fs_hip.h disagree on the slots");
 static_assert(fs::LOADS_REC == FS_LOADS_NREC && fs::LOADS_SUMS == FS_LOADS_NSUM, "fs_loads.h and include/fs_hip.h disagree on the record / the sums");
 static_assert(fs::MEAN_PLANES == FS_MEAN_NPLANE, "fs_mean.h and include/fs_hip.h disagree on the planes");
+static_assert(fs::MODES_MAX_FREQ == FS_MODES_MAX_FREQ && fs::modes_scalars(FS_MODES_MAX_FREQ) == FS_MODES_NSCALAR(FS_MODES_MAX_FREQ),
+              "fs_modes.h and include/fs_hip.h disagree on the frequencies / the scalars");
 
 namespace fs {
 void history_release(fs_history *h)
@@ -32,6 +36,13 @@ void mean_release(fs_mean *m)
 {
     if (m->d_sums) hipFree(m->d_sums);
     if (m->d_state) hipFree(m->d_state);
+    delete m;
+}
+void modes_release(fs_modes *m)
+{
+    if (m->d_sums) hipFree(m->d_sums);
+    if (m->d_state) hipFree(m->d_state);
+    if (m->d_scal) hipFree(m->d_scal);
     delete m;
 }
 }  // namespace fs
@@ -497,6 +508,186 @@ int fs_mean_free(fs_ctx *ctx, fs_mean *m)
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
     mean_release(m);
+    return FS_OK;
+}
+
+// ---- harmonic flow modes (fs_modes.h) ----------------------------------------------------------------------------------------------------
+#define FS_MODES_HANDLE(m) FS_REQUIRE((m)->ctx == ctx && ctx->modes.count(m), "modes from another context or freed")
+#define FS_MODES_NO_CAPTURE(what) \
+    if (ctx->capturing || ctx->tape_rec) { set_error("modes " what " during graph capture / tape recording"); return FS_ERR_STATE; }
+
+// as mean_grid: rows per workgroup from `g0` up to `rmax` (fs_launch.h diag_rows)
+static dim3 modes_grid(const fs_ctx *ctx, int w, int g0, int rmax, int *rpw)
+{
+    const int nx = (ctx->X + 256 * w - 1) / (256 * w), ny = ctx->nyl;
+    const int r = diag_rows(ctx, nx, ny, g0, rmax);
+    *rpw = r;
+    return dim3(nx, (ny + r - 1) / r);
+}
+
+int fs_modes_rows(fs_ctx *ctx, int nfreq, int *accumulate_rows, int *combine_rows)
+{
+    FS_REQUIRE(ctx && accumulate_rows && combine_rows, "null argument");
+    FS_REQUIRE(nfreq >= 1 && nfreq <= MODES_MAX_FREQ, "nfreq must be 1 .. FS_MODES_MAX_FREQ");
+    modes_grid(ctx, mean_width(ctx), modes_group(nfreq), modes_rows(nfreq), accumulate_rows);
+    modes_grid(ctx, mean_width(ctx), 1, MEAN_ROWS, combine_rows);
+    return FS_OK;
+}
+
+// the scalars of a fresh or reset object: every phasor (1, 0), the Gram matrix zero
+static void modes_fresh_scalars(int nfreq, double *sc)
+{
+    for (int k = 0; k < modes_scalars(nfreq); ++k) sc[k] = 0.0;
+    for (int k = 0; k < nfreq; ++k) sc[2 * k] = 1.0;
+}
+
+int fs_modes_create(fs_ctx *ctx, int nfreq, const double *cos_sin, long long every, long long start, fs_modes **out)
+{
+    FS_REQUIRE(ctx && cos_sin && out, "null argument");
+    FS_REQUIRE(nfreq >= 1 && nfreq <= MODES_MAX_FREQ, "nfreq must be 1 .. FS_MODES_MAX_FREQ");
+    FS_REQUIRE(every >= 1 && start >= 0, "every must be >= 1 and start >= 0");
+    FS_MODES_NO_CAPTURE("create")
+    FS_HIP(hipSetDevice(ctx->device));
+    fs_modes *m = new fs_modes();
+    m->ctx = ctx; m->nfreq = nfreq; m->every = every; m->start = start;
+    for (int k = 0; k < nfreq; ++k) { m->cd[k] = cos_sin[2 * k]; m->sd[k] = cos_sin[2 * k + 1]; }
+    m->plane = (size_t)ctx->nyl * ctx->P + MEAN_PAD;
+    const size_t bytes = 3 * (size_t)modes_basis(nfreq) * m->plane * sizeof(double);
+    double sc[modes_scalars(MODES_MAX_FREQ)];
+    modes_fresh_scalars(nfreq, sc);
+    hipError_t e = hipMalloc(&m->d_state, MODES_STATE * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc(&m->d_scal, modes_scalars(nfreq) * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&m->d_sums, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(m->d_state, 0, MODES_STATE * sizeof(long long), ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(m->d_scal, sc, modes_scalars(nfreq) * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(m->d_sums, 0, bytes, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { modes_release(m); return hip_fail(e, "fs_modes_create", __FILE__, __LINE__); }
+    ctx->modes.insert(m);
+    *out = m;
+    return FS_OK;
+}
+
+int fs_modes_accumulate(fs_ctx *ctx, fs_modes *m, double limit, const fs_field *v, const fs_field *p)
+{
+    FS_REQUIRE(ctx && m, "null argument");
+    FS_MODES_HANDLE(m);
+    FS_FIELD(v, 2); FS_FIELD(p, 1);
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    // everything the launches need is in `m` and the fields: no allocation, copy or synchronisation here (the closure is captured / taped)
+    const int jb = ctx->halo, je = ctx->halo + ctx->nyl, w = mean_width(ctx), nfreq = m->nfreq;
+    int rpw;
+    const dim3 grid = modes_grid(ctx, w, modes_group(nfreq), modes_rows(nfreq), &rpw);
+    const long long every = m->every, start = m->start;
+    long long *state = m->d_state;
+    double *scal = m->d_scal, *sums = m->d_sums;
+    const size_t plane = m->plane;
+    ModesRot rot;
+    for (int k = 0; k < MODES_MAX_FREQ; ++k) { rot.cd[k] = m->cd[k]; rot.sd[k] = m->sd[k]; }
+#define FS_MODES_ACC(W_, K_)                                                                                                                   \
+    FS_KLAUNCH((k_modes_accumulate<T, W_, K_>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, limit, start, every,                \
+               (const long long *)state, (const double *)scal, (const T *)v->d, (const T *)p->d, sums, plane)
+#define FS_MODES_ACC_W(W_)                                                                                                                     \
+    switch (nfreq) { case 1: FS_MODES_ACC(W_, 1); break; case 2: FS_MODES_ACC(W_, 2); break; case 3: FS_MODES_ACC(W_, 3); break;              \
+                     default: FS_MODES_ACC(W_, 4); break; }
+    FS_DISPATCH(ctx, {
+        return launch(ctx, "modes_accumulate", [=] {
+            if (w == 2) { FS_MODES_ACC_W(2) } else { FS_MODES_ACC_W(1) }
+            FS_KLAUNCH((k_modes_tick), dim3(1), dim3(64), 0, ctx->stream, nfreq, rot, start, every, state, scal);
+        });
+    })
+#undef FS_MODES_ACC_W
+#undef FS_MODES_ACC
+}
+
+int fs_modes_combine(fs_ctx *ctx, fs_modes *m, const double *weights, fs_field *v_out, fs_field *p_out)
+{
+    FS_REQUIRE(ctx && m && weights, "null argument");
+    FS_MODES_HANDLE(m);
+    FS_FIELD(v_out, 2); FS_FIELD(p_out, 1);
+    FS_MODES_NO_CAPTURE("combine")
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    const int jb = ctx->halo, je = ctx->halo + ctx->nyl, w = mean_width(ctx), B = modes_basis(m->nfreq);
+    int rpw;
+    const dim3 grid = modes_grid(ctx, w, 1, MEAN_ROWS, &rpw);
+    ModesWeights wgt;
+    for (int k = 0; k < 3 * MODES_MAX_B; ++k) wgt.w[k] = k < 3 * B ? weights[k] : 0.0;
+    const double *sums = m->d_sums;
+    const size_t plane = m->plane;
+    FS_DISPATCH(ctx, {
+        return launch(ctx, "modes_combine", [=] {
+            if (w == 2)
+                FS_KLAUNCH((k_modes_combine<T, 2>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, B, wgt, sums, plane, (T *)v_out->d,
+                           (T *)p_out->d, v_out->hot);
+            else
+                FS_KLAUNCH((k_modes_combine<T, 1>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, B, wgt, sums, plane, (T *)v_out->d,
+                           (T *)p_out->d, v_out->hot);
+        });
+    })
+}
+
+int fs_modes_read(fs_ctx *ctx, fs_modes *m, double *sums_out, double *scalars_out, long long *launches, long long *samples)
+{
+    FS_REQUIRE(ctx && m, "null argument");
+    FS_MODES_HANDLE(m);
+    FS_MODES_NO_CAPTURE("read")
+    FS_HIP(hipSetDevice(ctx->device));
+    long long st[MODES_STATE];
+    FS_HIP(hipMemcpyAsync(st, m->d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+    if (scalars_out)
+        FS_HIP(hipMemcpyAsync(scalars_out, m->d_scal, modes_scalars(m->nfreq) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    // per plane: nyl device rows of pitch P -> dense rows of X
+    if (sums_out)
+        for (int k = 0; k < 3 * modes_basis(m->nfreq); ++k)
+            FS_HIP(hipMemcpy2DAsync(sums_out + (size_t)k * ctx->nyl * ctx->X, (size_t)ctx->X * sizeof(double), m->d_sums + k * m->plane,
+                                    (size_t)ctx->P * sizeof(double), (size_t)ctx->X * sizeof(double), (size_t)ctx->nyl, hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    if (launches) *launches = st[0];
+    if (samples) *samples = st[1];
+    return FS_OK;
+}
+
+int fs_modes_write(fs_ctx *ctx, fs_modes *m, const double *sums_in, const double *scalars_in, long long launches, long long samples)
+{
+    FS_REQUIRE(ctx && m && sums_in && scalars_in, "null argument");
+    FS_MODES_HANDLE(m);
+    FS_REQUIRE(launches >= 0 && samples >= 0 && samples <= launches, "counters must satisfy 0 <= samples <= launches");
+    FS_MODES_NO_CAPTURE("write")
+    FS_HIP(hipSetDevice(ctx->device));
+    const long long st[MODES_STATE] = {launches, samples};
+    for (int k = 0; k < 3 * modes_basis(m->nfreq); ++k)
+        FS_HIP(hipMemcpy2DAsync(m->d_sums + k * m->plane, (size_t)ctx->P * sizeof(double), sums_in + (size_t)k * ctx->nyl * ctx->X,
+                                (size_t)ctx->X * sizeof(double), (size_t)ctx->X * sizeof(double), (size_t)ctx->nyl, hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipMemcpyAsync(m->d_scal, scalars_in, modes_scalars(m->nfreq) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipMemcpyAsync(m->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));      // (the sources are the caller's / this frame's memory)
+    return FS_OK;
+}
+
+int fs_modes_reset(fs_ctx *ctx, fs_modes *m)
+{
+    FS_REQUIRE(ctx && m, "null argument");
+    FS_MODES_HANDLE(m);
+    FS_MODES_NO_CAPTURE("reset")
+    FS_HIP(hipSetDevice(ctx->device));
+    double sc[modes_scalars(MODES_MAX_FREQ)];
+    modes_fresh_scalars(m->nfreq, sc);
+    FS_HIP(hipMemsetAsync(m->d_sums, 0, 3 * (size_t)modes_basis(m->nfreq) * m->plane * sizeof(double), ctx->stream));
+    FS_HIP(hipMemsetAsync(m->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
+    FS_HIP(hipMemcpyAsync(m->d_scal, sc, modes_scalars(m->nfreq) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));      // (the source is this frame's memory)
+    return FS_OK;
+}
+
+int fs_modes_free(fs_ctx *ctx, fs_modes *m)
+{
+    if (!m) return FS_OK;
+    FS_REQUIRE(ctx && m->ctx == ctx && ctx->modes.count(m), "modes from another context or freed");
+    ctx->modes.erase(m);
+    if (ctx->capturing) { ctx->deferred_release.push_back([m] { modes_release(m); }); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
+    modes_release(m);
     return FS_OK;
 }
 

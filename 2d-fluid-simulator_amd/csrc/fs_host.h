@@ -130,6 +130,7 @@ struct fs_ctx {
     std::set<fs_field *> fields;  // live fields, released with the context
     std::set<fs_history *> histories;        // live history rings (fs_history_create), released with the context
     std::set<fs_mean *> means;               // live time averages (fs_mean_create), released with the context
+    std::set<fs_modes *> modes;              // live harmonic-mode accumulators (fs_modes_create), released with the context
     std::set<fs_loads *> loads;              // live body trackers (fs_loads_create), released with the context
     std::set<fs_tracer *> tracers;           // live tracer sets (fs_tracer_create), released with the context
     // a *_free during a hipGraph capture (neither a synchronisation nor hipFree is legal there: either invalidates the capture) leaves its
@@ -200,6 +201,18 @@ struct fs_mean {
     long long *d_state = nullptr;   // [MEAN_STATE]
 };
 
+// harmonic flow modes (fs_modes_*, fs_modes.h): the Fourier-sum planes over this context's owned rows, the device counters and scalars
+struct fs_modes {
+    fs_ctx *ctx = nullptr;
+    int nfreq = 1;
+    long long every = 1, start = 0;
+    double cd[4] = {1, 1, 1, 1}, sd[4] = {0, 0, 0, 0};      // cos / sin of the phase step per sample of each frequency (MODES_MAX_FREQ)
+    size_t plane = 0;               // doubles from one plane to the next: nyl * P + MEAN_PAD
+    double *d_sums = nullptr;       // [3 (1 + 2 nfreq)][plane]
+    long long *d_state = nullptr;   // [MODES_STATE]
+    double *d_scal = nullptr;       // [2 nfreq] phasors, then the upper triangle of the Gram matrix
+};
+
 namespace fs { struct LoadFace; }      // fs_loads.h (included by fs_diag.hip alone)
 // body surface loads (fs_loads_*, fs_loads.h): the face list of this context's owned rows, the per-face sums, the ring and the device counters
 struct fs_loads {
@@ -245,6 +258,7 @@ namespace fs {
 void history_release(fs_history *h);      // fs_diag.hip
 void mean_release(fs_mean *m);            // fs_diag.hip
 void loads_release(fs_loads *l);          // fs_diag.hip
+void modes_release(fs_modes *m);          // fs_diag.hip
 
 // HIP-event pair around a span of stream work that is not one kernel launch (fs_core.hip; the ghost-row exchange chain of fs_comm.hip)
 ProfRec prof_span_begin(fs_ctx *c, const char *name, hipStream_t stream);

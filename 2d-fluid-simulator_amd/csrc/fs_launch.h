@@ -1,6 +1,6 @@
 // fs_launch.h - host-side launch plumbing shared by the translation units behind the C-ABI (fs_core.hip: contexts, fields, scene upload,
 // boundary kernels, graphs / tapes / profiling; fs_transport.hip: K2 - K6, K10 - K13; fs_pressure.hip: K7 - K8, the Poisson residual;
-// fs_diag.hip: flow diagnostics, history, body loads, time averages):
+// fs_diag.hip: flow diagnostics, history, body loads, time averages, harmonic modes):
 // the launch wrapper (profiling events, tape recording), XCD-band launch geometry with compact tile lists, division-mode dispatch,
 // argument checks.
 #pragma once
@@ -64,7 +64,7 @@ inline int launch(fs_ctx *c, const char *name, F &&f)
 // tiles of half the height halve that chain (round 4, tools/r4_chain.py; env FS_SMALL_CELLS=0: the big grids' tile heights everywhere)
 static inline bool small_tiles(const fs_ctx *c) { return (size_t)c->X * c->Y < c->small_cells; }
 
-// Rows per workgroup of the diagnostics' kernels (k_flow_stats, k_mean_accumulate, k_mean_finalize: `nx` workgroups across, `ny` owned rows):
+// Rows per workgroup of the diagnostics' kernels (k_flow_stats, k_mean_accumulate, k_mean_finalize, k_modes_accumulate, k_modes_combine: `nx` workgroups across, `ny` owned rows):
 // doubled from `r0` while the grid keeps >= diag_wgs workgroups (2048: 8 per CU; env FS_DIAG_WGS), at most `rmax`
 static inline int diag_rows(const fs_ctx *c, int nx, int ny, int r0, int rmax)
 {

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FS_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libfs_hip.so")     # FS_LIB: A/B builds (tools/)
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _lib = None
 
@@ -97,6 +97,14 @@ _PROTOS = {
     "fs_mean_reset": [_c_vp, _c_vp],
     "fs_mean_free": [_c_vp, _c_vp],
     "fs_diag_rows": [_c_vp] + [_P(_c_int)] * 3,
+    "fs_modes_create": [_c_vp, _c_int, _P(_c_dbl), ctypes.c_longlong, ctypes.c_longlong, _P(_c_vp)],
+    "fs_modes_accumulate": [_c_vp, _c_vp, _c_dbl, _c_vp, _c_vp],
+    "fs_modes_combine": [_c_vp, _c_vp, _P(_c_dbl), _c_vp, _c_vp],
+    "fs_modes_read": [_c_vp, _c_vp, _P(_c_dbl), _P(_c_dbl), _P(ctypes.c_longlong), _P(ctypes.c_longlong)],
+    "fs_modes_write": [_c_vp, _c_vp, _P(_c_dbl), _P(_c_dbl), ctypes.c_longlong, ctypes.c_longlong],
+    "fs_modes_reset": [_c_vp, _c_vp],
+    "fs_modes_free": [_c_vp, _c_vp],
+    "fs_modes_rows": [_c_vp, _c_int, _P(_c_int), _P(_c_int)],
     "fs_tracer_create": [_c_vp, _c_int, _P(_c_dbl), _c_int, _c_int, _P(_c_vp)],
     "fs_tracer_advance": [_c_vp, _c_vp, _c_dbl, _c_dbl, _c_vp],
     "fs_tracer_read": [_c_vp, _c_vp, _P(_c_dbl), _P(_c_int), _P(ctypes.c_longlong)],

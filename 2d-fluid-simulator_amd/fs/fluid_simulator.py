@@ -14,6 +14,7 @@ from .averages import Averager, derive_averages
 from .boundary_condition import get_boundary_condition
 from .history import Recorder, body_faces, check_probes
 from .loads import Tracker, body_centroid, face_geometry
+from .modes import Modes, fit as fit_modes, gram_matrix, phasor_steps, reconstruct_weights
 from .pressure_updater import JacobiPressureUpdater, RedBlackSorPressureUpdater
 from .solver import CipMacSolver, DyeCipMacSolver, DyeMacSolver, MacSolver
 from .tracers import TracerAccumulation, Tracers, check_seeds, response
@@ -85,14 +86,15 @@ class FluidSimulator:
         self._recorder = None      # fs.history.Recorder while record_history() is on
         self._last_recorder = None  # ... and after stop_history(): what history() still returns
         self._averager = None      # fs.averages.Averager while start_averaging() is on
+        self._moder = None         # fs.modes.Modes while start_modes() is on
         self._tracers = None       # fs.tracers.Tracers while seed_tracers() is on
         self._tracker = None       # fs.loads.Tracker while track_body() is on
         self._last_tracker = None  # ... and after stop_body(): what body_loads() / body_surface() still return
 
     def _riders(self):
-        """The attached riders (fs.riders.Rider) in their fixed order - history, averages, loads, tracers: the order of their launches behind
-        the solver step and of their tokens in _signature()."""
-        return [r for r in (self._recorder, self._averager, self._tracker, self._tracers) if r is not None]
+        """The attached riders (fs.riders.Rider) in their fixed order - history, averages, modes, loads, tracers: the order of their launches
+        behind the solver step and of their tokens in _signature()."""
+        return [r for r in (self._recorder, self._averager, self._moder, self._tracker, self._tracers) if r is not None]
 
     def _capturing(self):
         return getattr(self._dev, "capturing", False)
@@ -605,6 +607,84 @@ class FluidSimulator:
         """Detach the average and free its device memory; the cached graphs and tapes that hold its launch are freed first.  Nothing is kept
         on the host: call averages() before.  Inside a graph capture the device memory is released when the capture ends."""
         self._detach(self, "_averager", "stop_averaging")
+
+    # -- harmonic flow modes (new): Fourier sums of u, w, p at chosen frequencies accumulated on the device ---------------------------------
+    def start_modes(self, frequencies, every=1, start_step=0):
+        """From the next step on, accumulate the harmonic content of u, w and p at `frequencies` (1 to 4 distinct positive values, in 1 /
+        simulated time - history() and fs.history.dominant_frequency give the shedding frequency) in every not-wall cell: after every step k
+        (counted from here) with k > start_step and (k - start_step) % every == 0 the fields, multiplied by 1 and by the cosine and sine of
+        each frequency's phase, are added to double sums on the device (fs.modes; csrc/fs_modes.h).  The launch is part of the step: it is
+        captured into the replayed graphs and recorded into slab tapes, and run() is not cut into chunks by it.  Costs 24 (1 + 2K) bytes
+        per cell of device memory (72 for one frequency, 216 for four), and a sampling step moves 16 (3 + 6K) bytes per cell for the sums:
+        choose `every` accordingly - ValueError when a frequency reaches the Nyquist limit f every dt >= 0.5.  Changes no field and no
+        trajectory.  modes() returns the fit, mode_fields() the phase-averaged flow as fields.  Raises while modes are attached already;
+        not allowed during a graph capture."""
+        dev, s = self._dev, self._solver
+        self._not_capturing("start_modes")
+        self._make_way("_moder", "modes are attached already: stop_modes() first (or reset_modes())")
+        every, start_step = self._cadence(every, start_step)
+        cd, sd = phasor_steps(frequencies, every, s.dt)
+        freqs = np.atleast_1d(np.asarray(frequencies, np.float64))
+        self._moder = Modes(dev, dev.modes_create(np.stack([cd, sd], axis=1), every, start_step), freqs, every, start_step)
+
+    def _modes(self):
+        if self._moder is None:
+            raise RuntimeError("no modes: call start_modes() first")
+        return self._moder
+
+    def modes(self, local=False):
+        """The fit so far (a download of 24 (1 + 2K) bytes per cell): {"frequencies", "samples": int, "steps": int (steps since start_modes),
+        "u", "w", "p": {"mean": (X, Y), "cos", "sin", "amplitude", "phase": (K, X, Y)} (fs.modes.fit: the signal at a cell is mean +
+        sum_k amplitude[k] cos(theta_k - phase[k]), theta_k = 2 pi f_k (t - time of the first sample); wall cells 0), "sums": the raw planes
+        (3 (1 + 2K), X, Y), "gram": the Gram matrix of the applied basis, "mask"}.  On slabs the global arrays are assembled on every rank
+        (collective); local=True: this rank's owned rows only.  Raises while there are fewer samples than the 1 + 2K unknowns."""
+        mo = self._modes()
+        dev = self._dev
+        sums, scalars, launches, samples = dev.modes_read(mo.modes, local=local)
+        K = len(mo.frequencies)
+        if samples < 1 + 2 * K:
+            raise RuntimeError(f"{samples} samples yet, {1 + 2 * K} needed ({launches} steps since start_modes(every={mo.every}, "
+                               f"start_step={mo.start_step}))")
+        mask = np.asarray(self._solver._bc.mask)
+        if local:
+            mask = mask[:, dev.y0:dev.y0 + dev.nyl]
+        out = {"frequencies": mo.frequencies.copy(), "samples": samples, "steps": launches}
+        out.update(fit_modes(sums, scalars, K, mask))
+        out["sums"], out["gram"], out["mask"] = sums, gram_matrix(scalars, K), mask.copy()
+        return out
+
+    def mode_fields(self, phase=None, frequency=0):
+        """The phase-averaged flow as device fields (v: 2 channels, p: 1 channel; wall cells 0): the fitted mean plus the component of
+        frequency number `frequency` at `phase` (radians; 0 is the phase of the first sample); phase=None: the fitted mean alone.  For
+        everything that takes fields - the visualisation kernels, to_numpy, DeviceBase.flow_stats - as mean_fields().  One device pass over
+        the planes (fs_modes_combine), no download of them.  New fields on every call; the caller owns them."""
+        from ._lib import FsError
+        from .runtime import Field
+        mo = self._modes()
+        dev = self._dev
+        if self._capturing():
+            raise FsError("mode_fields during a graph capture: it allocates and downloads")
+        K = len(mo.frequencies)
+        frequency = int(frequency)
+        if not 0 <= frequency < K:
+            raise ValueError(f"frequency must be an index in 0 .. {K - 1}")
+        _, scalars, launches, samples = dev.modes_read_scalars(mo.modes)
+        if samples < 1 + 2 * K:
+            raise RuntimeError(f"{samples} samples yet, {1 + 2 * K} needed ({launches} steps since start_modes)")
+        phases = None if phase is None else [float(phase) if k == frequency else None for k in range(K)]
+        w = reconstruct_weights(scalars, K, phases)
+        v, p = Field(dev, 2), Field(dev, 1)      # (not dev.alloc: scratch fields stay out of the ghost-row bookkeeping state of the tapes)
+        dev.modes_combine(mo.modes, np.tile(w, (3, 1)), v, p)
+        return v, p
+
+    def reset_modes(self):
+        """Sums, Gram matrix and sample count back to zero, the phase back to 0; the step count and the phase of `every` / `start_step` run on."""
+        self._dev.modes_reset(self._modes().modes)
+
+    def stop_modes(self):
+        """Detach the modes and free their device memory; the cached graphs and tapes that hold their launch are freed first.  Nothing is
+        kept on the host: call modes() before.  Inside a graph capture the device memory is released when the capture ends."""
+        self._detach(self, "_moder", "stop_modes")
 
     # -- tracer particles (new): pathlines and streaklines advanced on the device ------------------------------------------------------
     def seed_tracers(self, seeds, respawn=True, max_age=0, sort_every=0, tau=None, gravity=(0.0, 0.0), deposits=False):

@@ -1,5 +1,5 @@
 """Device side of what rides the step and of the diagnostics (new; the reference has none): flow statistics, the per-step history, the
-body surface loads, the time averages and the tracer particles.  Two mixins: RideOps is the backend-agnostic host logic fs.runtime.DeviceBase
+body surface loads, the time averages, the harmonic modes and the tracer particles.  Two mixins: RideOps is the backend-agnostic host logic fs.runtime.DeviceBase
 inherits (slab partition, combination over ranks, argument checks, the op log of a logged period), NativeRideOps the `_p_*` primitives
 fs.runtime.Device binds to libfs_hip.so; the stand-in devices of the CPU tests override those.  fs.runtime re-exports every name here."""
 import ctypes
@@ -45,6 +45,14 @@ class Mean(_Handle):
         self.every, self.start = every, start
 
 
+class Modes(_Handle):
+    """Device accumulators of the harmonic modes (DeviceBase.modes_create): handle, number of frequencies, every, start."""
+
+    def __init__(self, h, nfreq, every, start):
+        super().__init__(h)
+        self.nfreq, self.every, self.start = nfreq, every, start
+
+
 class Loads(_Handle):
     """A device body tracker (DeviceBase.loads_create): handle (None on a slab that owns no face), the global face count, which faces
     this rank owns, capacity, every, start."""
@@ -63,7 +71,7 @@ class History(_Handle):
 
 
 class RideOps:
-    """flow_stats and the history_* / loads_* / mean_* / tracer_* calls of DeviceBase."""
+    """flow_stats and the history_* / loads_* / mean_* / modes_* / tracer_* calls of DeviceBase."""
 
     # (The tracer calls reach these through the class - RideOps._host_only(self, ...) - as they always reached _tracer_host_call: the CPU
     #  tests check their refusals on objects that are no devices.)
@@ -350,6 +358,102 @@ class RideOps:
     def mean_free(self, mean):
         self._release(mean, self._p_mean_free)
 
+    # ---- harmonic flow modes (include/fs_hip.h fs_modes_*): 3 (1 + 2K) planes of Fourier sums over the owned rows, one launch per step ----
+    MODES_MAX_FREQ = 4
+
+    @staticmethod
+    def modes_planes(nfreq):
+        """Planes of an accumulator of nfreq frequencies: 3 B, B = 1 + 2 nfreq."""
+        return 3 * (1 + 2 * int(nfreq))
+
+    @staticmethod
+    def modes_scalars(nfreq):
+        """Scalars of an accumulator: the 2 nfreq phasor entries, then the B (B + 1) / 2 entries of the Gram matrix's upper triangle."""
+        b = 1 + 2 * int(nfreq)
+        return 2 * int(nfreq) + b * (b + 1) // 2
+
+    def modes_create(self, cos_sin, every=1, start=0):
+        """Device accumulators for FluidSimulator.start_modes: cos_sin float64 (K, 2), the cosine and sine of each frequency's phase step per
+        sample (fs.modes.phasor_steps), 1 <= K <= MODES_MAX_FREQ; 24 (1 + 2K) bytes per owned cell, zeroed, every phasor (1, 0).  Launch n
+        (from 0) of modes_accumulate samples when n + 1 > start and (n + 1 - start) % every == 0.  Not allowed during a graph capture."""
+        self._host_only("modes_create during a graph capture")
+        cos_sin = np.ascontiguousarray(cos_sin, np.float64)
+        if cos_sin.ndim != 2 or cos_sin.shape[1] != 2 or not 1 <= len(cos_sin) <= self.MODES_MAX_FREQ:
+            raise ValueError(f"cos_sin must have shape (K, 2) with 1 <= K <= {self.MODES_MAX_FREQ}, got {cos_sin.shape}")
+        if not np.all(np.isfinite(cos_sin)):
+            raise ValueError("cos_sin must be finite")
+        every, start = self._check_cadence(every, start)
+        h = self._p_modes_create(cos_sin, every, start)
+        return self._adopt(h, Modes(h, len(cos_sin), every, start))
+
+    def modes_accumulate(self, modes, v, p):
+        """Add the current v and p, weighted by the basis of the current phasors, to the planes when this launch is a sampling one; Gram
+        matrix, counters and phasors advance on the device.  A limit_field v still owes stays deferred: the kernel limits the values as the
+        pass would store them.  Not a _run: no flush, no exchange, no ghost row - on slabs a kernel op of its own in the logged period
+        (writes no field)."""
+        self._ride("modes_accumulate", (modes._h, self._limit_of(v), v._h, p._h))
+
+    def modes_read_scalars(self, modes):
+        """-> (None, scalars, launches, samples): modes_read without the download of the planes."""
+        return self.modes_read(modes, local=True, with_sums=False)
+
+    def modes_read(self, modes, local=False, with_sums=True):
+        """-> (sums float64 (3 B, X, Y): plane a B + j of field a in (u, w, p) and basis entry j of [1, c_1, s_1, ...]; scalars float64
+        (modes_scalars,): phasors, Gram triangle; launches, samples).  On slabs the ranks' owned rows are assembled like Field.to_numpy
+        (allgather; local=True: this slab's rows only) and all ranks must hold the same counters and scalars (RuntimeError otherwise).
+        Collective on slab runs; not allowed during a graph capture."""
+        self._host_only("modes_read during a graph capture: the sums are a download (read between captures / replays)")
+        mine, scalars, launches, samples = self._p_modes_read(modes._h, modes.nfreq, with_sums)
+        launches, samples = int(launches), int(samples)
+        # (the scalars are compared by their bits, as 32-bit halves: the collective carries integers below 2^40)
+        if self.nranks > 1 and not self._p_same_over_ranks([launches, samples] + [int(x) for x in np.ascontiguousarray(scalars).view(np.uint32)]):
+            raise RuntimeError("modes_read: the ranks hold different counters, phasors or Gram matrices")
+        if local or self.nranks == 1:
+            return mine, scalars, launches, samples
+        if self.allgather is None:
+            raise RuntimeError("modes_read() on a slab needs runtime.init(allgather=...) or local=True")
+        return np.concatenate(self.allgather(mine), axis=2), scalars, launches, samples
+
+    def modes_write(self, modes, sums, scalars, launches, samples):
+        """Restore what modes_read returned (resume): sums is the GLOBAL (3 B, X, Y) array, each slab keeps its owned rows."""
+        self._host_only("modes_write during a graph capture")
+        sums, scalars = np.asarray(sums, np.float64), np.ascontiguousarray(scalars, np.float64)
+        shape = (self.modes_planes(modes.nfreq), self.nx, self.ny)
+        if sums.shape != shape:
+            raise ValueError(f"expected sums of shape {shape}, got {sums.shape}")
+        if scalars.shape != (self.modes_scalars(modes.nfreq),):
+            raise ValueError(f"expected {self.modes_scalars(modes.nfreq)} scalars, got shape {scalars.shape}")
+        launches, samples = self._check_counters(launches, samples)
+        self._p_modes_write(modes._h, np.ascontiguousarray(sums[:, :, self.y0:self.y0 + self.nyl]), scalars, launches, samples)
+
+    def modes_reset(self, modes):
+        """Planes, Gram matrix and sample count to zero, the phasors to (1, 0); the launch count runs on.  Not allowed during a graph capture."""
+        self._host_only("modes_reset during a graph capture")
+        self._p_modes_reset(modes._h)
+
+    def modes_combine(self, modes, weights, v_out, p_out):
+        """The planes reduced to fields: sum_j weights[a, j] * plane[a B + j] (in double, j ascending) for a = u, w into the 2-channel v_out
+        and a = p into the 1-channel p_out, wall cells 0, in the fields' precision; weights float64 (3, B).  Owned rows only: on slabs the
+        targets' ghost rows are stale afterwards (valid = 0).  Not allowed during a graph capture."""
+        self._host_only("modes_combine during a graph capture")
+        weights = np.ascontiguousarray(weights, np.float64)
+        if weights.shape != (3, 1 + 2 * modes.nfreq):
+            raise ValueError(f"expected weights of shape {(3, 1 + 2 * modes.nfreq)}, got {weights.shape}")
+        for f in (v_out, p_out):
+            f.pending_limit = f.pending_clamp = None      # (every owned cell is overwritten)
+        self._p_modes_combine(modes._h, weights, v_out._h, p_out._h)
+        for f in (v_out, p_out):
+            f.valid = 0 if self.nranks > 1 else self.halo
+            f.user_data = True
+            f.static_id = next(_serials)
+
+    def modes_rows(self, nfreq):
+        """{"accumulate", "combine"}: the rows per workgroup the next launches take on this context (fs_modes_rows; FS_DIAG_WGS moves them)."""
+        return dict(zip(("accumulate", "combine"), self._p_modes_rows(int(nfreq))))
+
+    def modes_free(self, modes):
+        self._release(modes, self._p_modes_free)
+
     # ---- tracer particles (include/fs_hip.h fs_tracer_*): N particles in double cell coordinates, advanced by one launch per step -------
     def tracer_create(self, seeds, respawn=True, max_age=0):
         """A device tracer set for FluidSimulator.seed_tracers: seeds float64 (N, 2) in cell units, N >= 1, inside the domain (whether
@@ -635,6 +739,39 @@ class NativeRideOps:
     def _p_mean_free(self, h):
         if self._ctx is not None:
             _lib.call("fs_mean_free", self._ctx, h)
+
+    def _p_modes_create(self, cos_sin, every, start):
+        h = ctypes.c_void_p()
+        _lib.call("fs_modes_create", self._ctx, len(cos_sin), cos_sin.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), every, start, ctypes.byref(h))
+        return h
+
+    def _p_modes_read(self, h, nfreq, with_sums=True):
+        out = np.empty((self.modes_planes(nfreq) if with_sums else 0, self.nyl, self.nx), np.float64)       # (the library's layout: x contiguous)
+        scalars = np.empty(self.modes_scalars(nfreq), np.float64)
+        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
+        dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        _lib.call("fs_modes_read", self._ctx, h, dp(out) if with_sums else None, dp(scalars), ctypes.byref(launches), ctypes.byref(samples))
+        return (out.transpose(0, 2, 1) if with_sums else None), scalars, launches.value, samples.value
+
+    def _p_modes_write(self, h, sums, scalars, launches, samples):
+        a = np.ascontiguousarray(sums.transpose(0, 2, 1), np.float64)
+        dp = lambda x: x.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        _lib.call("fs_modes_write", self._ctx, h, dp(a), dp(scalars), launches, samples)
+
+    def _p_modes_reset(self, h):
+        _lib.call("fs_modes_reset", self._ctx, h)
+
+    def _p_modes_combine(self, h, weights, vh, ph):
+        _lib.call("fs_modes_combine", self._ctx, h, weights.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), vh, ph)
+
+    def _p_modes_rows(self, nfreq):
+        a, c = ctypes.c_int(), ctypes.c_int()
+        _lib.call("fs_modes_rows", self._ctx, nfreq, ctypes.byref(a), ctypes.byref(c))
+        return a.value, c.value
+
+    def _p_modes_free(self, h):
+        if self._ctx is not None:
+            _lib.call("fs_modes_free", self._ctx, h)
 
     def _p_tracer_create(self, seeds, respawn, max_age):
         h = ctypes.c_void_p()

@@ -12,6 +12,9 @@ The reference opens a GGUI window and steps forever; here the loop runs `--steps
     GPU, written to `--history-file` (.npz) at the end of the run.
   * average u, w, p and their second moments over time on the GPU (`--mean-every`, `--mean-start`), written to `--mean-file` (.npz) at
     the end of the run; the sums travel with `--save-state` / `--load-state`, so an average continues over restarts.
+  * accumulate the harmonic content of u, w, p at given frequencies on the GPU (`--modes-freq f[,f2,...]`, `--modes-every`, `--modes-start`):
+    mean, amplitude and phase per cell written to `--modes-file` (.npz) at the end of the run, the phase-averaged cycle of the first frequency
+    as `--modes-frames N` images; the sums travel with `--save-state` / `--load-state`.
   * follow tracer particles on the GPU (`--tracers N`, `--tracer-line x0,y0,x1,y1,n`): pathlines (`--tracer-once`) or streaklines, written
     to `--tracer-file` (.npz) at the end of the run and every `--tracer-dump-every` steps, drawn into the `-vis` frames; the particle state
     travels with `--save-state` / `--load-state`.  `--tracer-sort-every K` sorts the particles by cell on the GPU every K steps (large sets
@@ -85,6 +88,16 @@ def build_parser():
     p.add_argument("--mean-file", type=str, default=None,
                    help=".npz of the averages: samples, steps, u, w, p, uu, ww, uw, p_rms, tke, mask, dt, dx, every, start "
                         "(default: <out>/mean.npz)")
+    p.add_argument("--modes-freq", type=str, default=None, metavar="F[,F2,...]",
+                   help="accumulate the harmonic content of u, w, p at these 1 to 4 frequencies (1 / simulated time) on the GPU "
+                        "(FluidSimulator.start_modes); each must stay below the Nyquist limit f * N * dt < 0.5 of --modes-every N")
+    p.add_argument("--modes-every", type=int, default=None, help="sample the modes after every N-th step (default 1)")
+    p.add_argument("--modes-start", type=int, default=None, help="steps of the run (restarts included) to leave out before the first sample (default 0)")
+    p.add_argument("--modes-file", type=str, default=None,
+                   help=".npz of the modes: frequencies, mean_u / _w / _p, amplitude_u / _w / _p, phase_u / _w / _p, samples, steps, mask, dt, "
+                        "dx, every, start (default: <out>/modes.npz)")
+    p.add_argument("--modes-frames", type=int, default=0,
+                   help="write N -vis images modes_phase_<i>.png of the phase-averaged flow over one period of the first frequency")
     p.add_argument("--tracers", type=int, default=0,
                    help="follow N tracer particles seeded at random in fluid cells (FluidSimulator.seed_tracers; 0: none unless --tracer-line)")
     p.add_argument("--tracer-seed", type=int, default=None, help="seed of the random generator behind --tracers (default 0)")
@@ -146,6 +159,23 @@ def load_mean(sim, path):
     if "mean.sums" not in z.files:
         return False
     sim._averager.restore(z)
+    return True
+
+
+def saved_modes(path):
+    """(frequencies, every, start) of the harmonic modes a checkpoint holds, or None."""
+    z = np.load(_npz_path(path))
+    if "modes.sums" not in z.files:
+        return None
+    return (tuple(float(f) for f in z["modes.frequencies"]), int(z["modes.every"]), int(z["modes.start"]))
+
+
+def load_modes(sim, path):
+    """Restore the planes, scalars and counters of the checkpoint's modes into the attached ones -> whether the checkpoint held any."""
+    z = np.load(_npz_path(path))
+    if "modes.sums" not in z.files:
+        return False
+    sim._moder.restore(z)
     return True
 
 
@@ -261,8 +291,20 @@ def load_state(sim, path):
 
 def mean_frame(sim, vis):
     """The -vis 0 / 1 / 2 image of the mean flow (FluidSimulator.mean_fields), downloaded as an (X, Y, 3) array."""
+    return fields_frame(sim, vis, *sim.mean_fields())
+
+
+def modes_file_arrays(modes):
+    """The arrays of --modes-file from FluidSimulator.modes()."""
+    out = {"frequencies": modes["frequencies"], "samples": np.array(modes["samples"]), "steps": np.array(modes["steps"]), "mask": modes["mask"]}
+    for name in ("u", "w", "p"):
+        out[f"mean_{name}"], out[f"amplitude_{name}"], out[f"phase_{name}"] = modes[name]["mean"], modes[name]["amplitude"], modes[name]["phase"]
+    return out
+
+
+def fields_frame(sim, vis, v, p):
+    """The -vis 0 / 1 / 2 image of the flow in the fields v, p, downloaded as an (X, Y, 3) array."""
     dev = sim._dev
-    v, p = sim.mean_fields()
     if vis == 0:
         dev.vis_norm(sim.rgb_buf, v, p)
     elif vis == 1:
@@ -410,6 +452,28 @@ def main(argv=None):
             print(f"--load-state {args.load_state}: its time average was taken with --mean-every {held[0]} --mean-start {held[1]}, "
                   f"not {args.mean_every} / {args.mean_start}; continue with those or average without the checkpoint's sums", file=sys.stderr)
             sys.exit(2)
+    modes_freqs = None
+    if args.modes_freq is None:
+        if args.modes_every is not None or args.modes_start is not None or args.modes_file or args.modes_frames:
+            parser.error("--modes-every, --modes-start, --modes-file and --modes-frames need --modes-freq F")
+    else:
+        from fs.modes import phasor_steps
+        modes_freqs = _tracer_floats(parser, "--modes-freq", args.modes_freq)
+        modes_every, modes_start = (1 if args.modes_every is None else args.modes_every), args.modes_start or 0
+        if modes_every < 1 or modes_start < 0 or args.modes_frames < 0:
+            parser.error("--modes-every must be >= 1, --modes-start and --modes-frames >= 0")
+        if args.modes_frames and args.visualization == 3:
+            parser.error("--modes-frames: -vis 3 is the dye, which has no modes (use -vis 0, 1 or 2)")
+        try:
+            phasor_steps(modes_freqs, modes_every, dt)
+        except ValueError as e:
+            parser.error(f"--modes-freq {args.modes_freq}: {e}")
+        if args.load_state:
+            held = saved_modes(args.load_state)
+            if held is not None and held != (tuple(modes_freqs), modes_every, modes_start):
+                print(f"--load-state {args.load_state}: its modes were taken with --modes-freq {','.join(repr(f) for f in held[0])} --modes-every "
+                      f"{held[1]} --modes-start {held[2]}; continue with those or accumulate without the checkpoint's sums", file=sys.stderr)
+                sys.exit(2)
     tracing = args.tracers > 0 or bool(args.tracer_line)
     if args.tracers < 0 or args.tracer_dump_every < 0 or (args.tracer_max_age is not None and args.tracer_max_age < 0) or args.tracer_sort_every < 0:
         parser.error("--tracers, --tracer-max-age, --tracer-dump-every and --tracer-sort-every must be >= 0")
@@ -503,6 +567,30 @@ def main(argv=None):
             out.mkdir(exist_ok=True)
             save_png(mean_frame(sim, args.visualization), out / "mean_vis.png")
 
+    modes_file = None
+    if modes_freqs is not None:
+        modes_file = Path(args.modes_file) if args.modes_file else out / "modes.npz"
+        sim.start_modes(modes_freqs, every=modes_every, start_step=modes_start)
+        if args.load_state and load_modes(sim, args.load_state):
+            print(f"modes: continuing the checkpoint's ({sim._dev.modes_read_scalars(sim._moder.modes)[3]} samples so far)")
+
+    def write_modes():
+        if modes_file is None:
+            return
+        try:
+            modes = sim.modes()
+        except RuntimeError as e:
+            print(f"modes: {e}; no file written", file=sys.stderr)
+            return
+        modes_file.parent.mkdir(parents=True, exist_ok=True)
+        np.savez(str(modes_file), dt=np.array(dt), dx=np.array(dx), every=np.array(modes_every), start=np.array(modes_start),
+                 **modes_file_arrays(modes))
+        if args.modes_frames:
+            out.mkdir(exist_ok=True)
+            for i in range(args.modes_frames):
+                v, p = sim.mode_fields(2.0 * np.pi * i / args.modes_frames, 0)
+                save_png(fields_frame(sim, args.visualization, v, p), out / f"modes_phase_{i}.png")
+
     loads_file = None
     if args.loads_every > 0:
         loads_file = Path(args.loads_file) if args.loads_file else out / "loads.npz"
@@ -587,6 +675,7 @@ def main(argv=None):
             print(f"step {step}: non-finite values (NaN / Inf) in v or p; stopping (--stop-on-nonfinite)", file=sys.stderr)
             write_history()
             write_mean()
+            write_modes()
             write_loads()
             if tracer_file is not None:
                 write_tracers(tracer_file, fields_file, step)
@@ -629,6 +718,7 @@ def main(argv=None):
         stats.close()
     write_history()
     write_mean()
+    write_modes()
     write_loads()
     if tracer_file is not None:
         write_tracers(tracer_file, fields_file, step0 + args.steps)

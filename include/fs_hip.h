@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 17
+#define FS_ABI_VERSION 18
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -365,6 +365,41 @@ int fs_mean_free(fs_ctx *ctx, fs_mean *m);
  * (4 - 32, 4 - 8 and 1 - 8: more on larger grids; env FS_DIAG_WGS, read by fs_create, moves the grid size at which they grow).  Launches
  * nothing: allowed during graph capture / tape recording. */
 int fs_diag_rows(fs_ctx *ctx, int *flow_stats_rows, int *mean_accumulate_rows, int *mean_finalize_rows);
+
+/* Harmonic flow modes (new, ABI 18): per-cell Fourier sums of u, w and p at nfreq frequencies, accumulated on the device by a launch that can
+ * be captured in a hipGraph and recorded in a tape (csrc/fs_modes.h).  With B = 1 + 2 nfreq and the basis b = [1, c_1, s_1, ..., c_K, s_K]:
+ * 3 B planes of double over this context's OWNED rows - plane a * B + j holds the sum over the samples of x_a * b_j, a in (u, w, p) - which
+ * is 24 B bytes per cell; two device counters (launches, samples); and FS_MODES_NSCALAR(nfreq) scalars of double: the phasors c_1, s_1, ...,
+ * c_K, s_K, then the upper triangle (i <= j, row major) of the Gram matrix G[i][j] = sum over the samples of b_i * b_j.
+ * create:     1 <= nfreq <= FS_MODES_MAX_FREQ; cos_sin holds cd_1, sd_1, ..., cd_K, sd_K, the cosine and sine of the phase step per sample
+ *             2 pi f_k every dt, computed by the caller (the device evaluates no sin / cos); every >= 1, start >= 0.  Planes, Gram matrix and
+ *             counters zero, every phasor (1, 0).  An allocation that does not fit returns FS_ERR_HIP.
+ * accumulate: launch n (from 0) samples by the rule of fs_mean_accumulate.  A sampling launch adds, on every not-wall cell of the owned rows,
+ *             x to plane a B and x * b_j to plane a B + j (j > 0), x the stored value promoted to double, the product rounded before the sum;
+ *             limit > 0: u, w are limited as a deferred limit_field(limit) would store them.  Behind it on the stream, a sampling launch
+ *             adds b_i * b_j to the Gram matrix, adds 1 to samples and rotates the phasors, c' = c cd - s sd, s' = s cd + c sd, in this order;
+ *             every launch adds 1 to launches.  Deterministic: an IEEE double loop over the sampled fields reproduces every number bit for bit.
+ *             Wall cells keep their sums.  Reads no ghost row, changes no field.
+ * combine:    v_out[a] = (T) sum_j weights[a B + j] * plane[a B + j] (j = 0 .. B - 1 in this order from 0.0, in double, product then sum) for
+ *             a = u, w into the 2-channel v_out and a = p into the 1-channel p_out on the not-wall cells of the owned rows, 0 on wall cells;
+ *             weights: 3 B doubles.  Ghost rows of the targets are not written.
+ * read:       synchronises; sums_out (NULL: skipped) receives [3 B][ny_local][X] doubles, x contiguous; scalars_out (NULL: skipped) the
+ *             FS_MODES_NSCALAR(nfreq) scalars.  write: the inverse (resume), 0 <= samples <= launches.
+ * reset:      planes, Gram matrix and the sample count to zero, the phasors to (1, 0); the launch count runs on.
+ * free:       as fs_mean_free (during a capture the release is deferred to its end).
+ * rows:       diagnostic - the rows per workgroup the accumulate (nfreq frequencies) and combine launches of this context take (fs_diag_rows).
+ * create, combine, read, write and reset return FS_ERR_STATE during graph capture / tape recording.                                     */
+#define FS_MODES_MAX_FREQ 4
+#define FS_MODES_NSCALAR(nfreq) (2 * (nfreq) + (1 + 2 * (nfreq)) * (2 + 2 * (nfreq)) / 2)
+typedef struct fs_modes fs_modes;
+int fs_modes_create(fs_ctx *ctx, int nfreq, const double *cos_sin, long long every, long long start, fs_modes **out);
+int fs_modes_accumulate(fs_ctx *ctx, fs_modes *m, double limit, const fs_field *v, const fs_field *p);
+int fs_modes_combine(fs_ctx *ctx, fs_modes *m, const double *weights, fs_field *v_out, fs_field *p_out);
+int fs_modes_read(fs_ctx *ctx, fs_modes *m, double *sums_out, double *scalars_out, long long *launches, long long *samples);
+int fs_modes_write(fs_ctx *ctx, fs_modes *m, const double *sums_in, const double *scalars_in, long long launches, long long samples);
+int fs_modes_reset(fs_ctx *ctx, fs_modes *m);
+int fs_modes_free(fs_ctx *ctx, fs_modes *m);
+int fs_modes_rows(fs_ctx *ctx, int nfreq, int *accumulate_rows, int *combine_rows);
 
 /* Tracer particles (new): n passive particles advanced on the device by one launch per step that can be captured in a hipGraph
  * (csrc/fs_tracer.h).  Positions are doubles in CELL units: cell (i, j) covers [i, i + 1) x [j, j + 1), its stored value sits at
