@@ -17,6 +17,11 @@ namespace fs {
 
 static thread_local std::string g_err;
 void set_error(const std::string &msg) { g_err = msg; }
+int no_variant(const char *name)
+{
+    set_error(std::string(name) + ": no kernel variant for these arguments");
+    return FS_ERR_UNSUPPORTED;
+}
 int hip_fail(hipError_t e, const char *what, const char *file, int line)
 {
     char buf[512];
@@ -638,9 +643,9 @@ static int upload_window(fs_ctx *ctx, void *dev, int C, size_t esize, const void
     FS_HIP(hipMemcpyAsync(ctx->d_stage, host, bytes, hipMemcpyHostToDevice, ctx->stream));
     const int Q = nrows * C;
     dim3 grid((ctx->X + 63) / 64, (Q + 63) / 64);
-    if (esize == 1) FS_KLAUNCH(k_to_device<uint8_t>, grid, dim3(256), 0, ctx->stream, (const uint8_t *)ctx->d_stage, (uint8_t *)dev, ctx->X, Q, pitch, row_begin * C);
-    else if (esize == 4) FS_KLAUNCH(k_to_device<float>, grid, dim3(256), 0, ctx->stream, (const float *)ctx->d_stage, (float *)dev, ctx->X, Q, pitch, row_begin * C);
-    else FS_KLAUNCH(k_to_device<double>, grid, dim3(256), 0, ctx->stream, (const double *)ctx->d_stage, (double *)dev, ctx->X, Q, pitch, row_begin * C);
+    if (esize == 1) klaunch(k_to_device<uint8_t>, grid, dim3(256), ctx->stream, (const uint8_t *)ctx->d_stage, (uint8_t *)dev, ctx->X, Q, pitch, row_begin * C);
+    else if (esize == 4) klaunch(k_to_device<float>, grid, dim3(256), ctx->stream, (const float *)ctx->d_stage, (float *)dev, ctx->X, Q, pitch, row_begin * C);
+    else klaunch(k_to_device<double>, grid, dim3(256), ctx->stream, (const double *)ctx->d_stage, (double *)dev, ctx->X, Q, pitch, row_begin * C);
     FS_HIP(hipGetLastError());
     FS_HIP(hipStreamSynchronize(ctx->stream));
     return FS_OK;
@@ -692,14 +697,14 @@ int fs_upload_mask(fs_ctx *ctx, const uint8_t *mask_xy)
     std::vector<uint8_t>().swap(ctx->h_bcmap);
     if (rc) return rc;
     if (ctx->X % 4 == 0) {      // per-tile flags of the lazy pressure BC
-        FS_KLAUNCH(k_lazy_flags, dim3((ctx->nwx * ctx->rows + 3) / 4), dim3(256), 0, ctx->stream, ctx->grid(), ctx->nwx, ctx->d_bcmap, ctx->d_lazyflags);
+        klaunch(k_lazy_flags, dim3((ctx->nwx * ctx->rows + 3) / 4), dim3(256), ctx->stream, ctx->grid(), ctx->nwx, ctx->d_bcmap, ctx->d_lazyflags);
         FS_HIP(hipGetLastError());
         // the rows the two-sweep kernel hands to its general path: list + count (read back once per mask)
         const size_t cap = (size_t)ctx->nwx * ctx->rows;
         if (!ctx->d_pairlist) FS_HIP(hipMalloc(&ctx->d_pairlist, (2 * cap + 2) * sizeof(uint32_t)));
         unsigned *d_count = (unsigned *)(ctx->d_pairlist + 2 * cap);
         FS_HIP(hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned), ctx->stream));
-        FS_KLAUNCH(k_pair_list, dim3((ctx->nwx * ctx->rows + 3) / 4), dim3(256), 0, ctx->stream, ctx->grid(), ctx->nwx, (uint8_t *)ctx->d_lazyflags,
+        klaunch(k_pair_list, dim3((ctx->nwx * ctx->rows + 3) / 4), dim3(256), ctx->stream, ctx->grid(), ctx->nwx, (uint8_t *)ctx->d_lazyflags,
                            ctx->d_pairlist, ctx->d_pairlist + cap, d_count);
         FS_HIP(hipGetLastError());
         unsigned n[2] = {0, 0};
@@ -783,12 +788,12 @@ int fs_field_fill(fs_field *f, double value)
     fs_ctx *ctx = f->ctx;
     const size_t n = f->bytes / ctx->esize;
     const unsigned hot = 2.0 * value * value > 0.999 * (double)FS_HOT_SQ ? 1u : 0u;      // every channel takes `value` (the margin: x * x + y * y is evaluated in the field type on the device)
-    FS_DISPATCH(ctx, {
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         return launch(ctx, "fill", [=] {
-            FS_KLAUNCH(k_fill<T>, dim3(2048), dim3(256), 0, ctx->stream, (T *)f->d, n, (T)value);
-            FS_KLAUNCH(k_fill<unsigned>, dim3(1), dim3(64), 0, ctx->stream, f->hot, (size_t)4, hot);
+            klaunch(k_fill<T>, dim3(2048), dim3(256), ctx->stream, (T *)f->d, n, (T)value);
+            klaunch(k_fill<unsigned>, dim3(1), dim3(64), ctx->stream, f->hot, (size_t)4, hot);
         });
-    })
+    });
 }
 
 int fs_field_upload(fs_field *f, const void *host_xrc, int row_begin, int nrows)
@@ -798,9 +803,10 @@ int fs_field_upload(fs_field *f, const void *host_xrc, int row_begin, int nrows)
     FS_HIP(hipSetDevice(ctx->device));
     int rc = upload_window(ctx, f->d, f->C, ctx->esize, host_xrc, row_begin, nrows, ctx->P);
     if (rc || f->C != 2 || nrows == 0) return rc;
-    FS_DISPATCH(ctx, {      // what came in may exceed the speed the limit_field gate assumes: look at it (fs_device.h "hot" flag)
-        FS_KLAUNCH(k_scan_hot<T>, cells_grid(ctx, row_begin, row_begin + nrows), dim3(256), 0, ctx->stream, ctx->grid(), row_begin, (const T *)f->d, f->hot);
-    })
+    by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;      // what came in may exceed the speed the limit_field gate assumes: look at it (fs_device.h "hot" flag)
+        klaunch_cells(k_scan_hot<T>, ctx, row_begin, row_begin + nrows, (const T *)f->d, f->hot);
+        return FS_OK;
+    });
     FS_HIP(hipGetLastError());
     return FS_OK;
 }
@@ -818,9 +824,10 @@ int fs_field_download(const fs_field *f, void *host_xrc, int row_begin, int nrow
     if (rc) return rc;
     const int Q = nrows * f->C;
     dim3 grid((ctx->X + 63) / 64, (Q + 63) / 64);
-    FS_DISPATCH(ctx, {
-        FS_KLAUNCH(k_to_host<T>, grid, dim3(256), 0, ctx->stream, (T *)ctx->d_stage, (const T *)f->d, ctx->X, Q, ctx->P, row_begin * f->C);
-    })
+    by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
+        klaunch(k_to_host<T>, grid, dim3(256), ctx->stream, (T *)ctx->d_stage, (const T *)f->d, ctx->X, Q, ctx->P, row_begin * f->C);
+        return FS_OK;
+    });
     FS_HIP(hipGetLastError());
     FS_HIP(hipMemcpyAsync(host_xrc, ctx->d_stage, bytes, hipMemcpyDeviceToHost, ctx->stream));
     FS_HIP(hipStreamSynchronize(ctx->stream));
@@ -852,7 +859,7 @@ int fs_field_copy(fs_field *dst, const fs_field *src)
 {
     FS_REQUIRE(dst && src && dst->ctx == src->ctx && dst->C == src->C, "copy needs two fields of one context and shape");
     FS_HIP(hipMemcpyAsync(dst->d, src->d, src->bytes, hipMemcpyDeviceToDevice, dst->ctx->stream));
-    FS_KLAUNCH(k_hot_fold, dim3(1), dim3(64), 0, dst->ctx->stream, dst->hot, (const unsigned *)src->hot);      // (one word: the copy starts a new parity sequence)
+    klaunch(k_hot_fold, dim3(1), dim3(64), dst->ctx->stream, dst->hot, (const unsigned *)src->hot);      // (one word: the copy starts a new parity sequence)
     FS_HIP(hipGetLastError());
     return FS_OK;
 }
@@ -883,12 +890,12 @@ int fs_velocity_bc(fs_ctx *ctx, fs_field *v, int row_begin, int row_end)
     if (!ctx->d_bc_const) { set_error("bc_const not uploaded"); return FS_ERR_STATE; }
     int rc = bc_guard(ctx); if (rc) return rc;
     if (ctx->ops_vel.lanes() == 0) return FS_OK;
-    FS_DISPATCH(ctx, {
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         return launch(ctx, "velocity_bc", [=] {
-            FS_KLAUNCH(k_velocity_bc<T>, dim3((ctx->ops_vel.lanes() + 255) / 256), dim3(256), 0, ctx->stream,
+            klaunch(k_velocity_bc<T>, dim3((ctx->ops_vel.lanes() + 255) / 256), dim3(256), ctx->stream,
                                ctx->grid(), ctx->ops_vel.view(), row_begin, row_end, (T *)v->d, (const T *)ctx->d_bc_const, v->hot);
         });
-    })
+    });
 }
 
 // limit_field(v, limit) of the step before + the velocity boundary kernel of this step in one launch (fs_march.h k_velocity_bc_limit):
@@ -915,14 +922,14 @@ int fs_velocity_bc_limit(fs_ctx *ctx, double limit, fs_field *v, int parity, int
     int ok = 0;
     fs_velocity_bc_limit_ok(ctx, &ok);
     if (!ok || !((float)limit * (float)limit > FS_HOT_GATE_SQ)) { set_error("fs_velocity_bc_limit is not available for this context / limit (fs_velocity_bc_limit_ok)"); return FS_ERR_UNSUPPORTED; }
-    FS_DISPATCH(ctx, {
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         return launch(ctx, "velocity_bc", [=] {
             // (at least one workgroup per row of the limit pass, up to 64 (the barrier costs ~40 ns per workgroup): with the flag up - a run that has once exceeded a speed of 8 keeps it
             //  up - the pass is shared by the launch's workgroups; the extra ones find no op and cost nothing while the flag is down)
-            FS_KLAUNCH(k_velocity_bc_limit<T>, dim3(std::max((ctx->ops_vel.lanes() + 255) / 256, std::min(64, limit_end - limit_begin))), dim3(256), 0, ctx->stream,
+            klaunch(k_velocity_bc_limit<T>, dim3(std::max((ctx->ops_vel.lanes() + 255) / 256, std::min(64, limit_end - limit_begin))), dim3(256), ctx->stream,
                                ctx->grid(), ctx->ops_vel.view(), row_begin, row_end, limit_begin, limit_end, (T)limit, (T *)v->d, (const T *)ctx->d_bc_const, v->hot, ctx->d_sync, parity);
         });
-    })
+    });
 }
 
 int fs_pressure_bc(fs_ctx *ctx, fs_field *p, int row_begin, int row_end)
@@ -932,12 +939,12 @@ int fs_pressure_bc(fs_ctx *ctx, fs_field *p, int row_begin, int row_end)
     FS_ROWS();
     int rc = bc_guard(ctx); if (rc) return rc;
     if (ctx->ops_prs.lanes() == 0) return FS_OK;
-    FS_DISPATCH(ctx, {
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         return launch(ctx, "pressure_bc", [=] {
-            FS_KLAUNCH(k_pressure_bc<T>, dim3((ctx->ops_prs.lanes() + 255) / 256), dim3(256), 0, ctx->stream,
+            klaunch(k_pressure_bc<T>, dim3((ctx->ops_prs.lanes() + 255) / 256), dim3(256), ctx->stream,
                                ctx->grid(), ctx->ops_prs.view(), row_begin, row_end, (T *)p->d);
         });
-    })
+    });
 }
 
 int fs_dye_bc(fs_ctx *ctx, fs_field *dye, int row_begin, int row_end)
@@ -947,12 +954,12 @@ int fs_dye_bc(fs_ctx *ctx, fs_field *dye, int row_begin, int row_end)
     FS_ROWS();
     if (!ctx->d_bc_dye) { set_error("bc_dye not uploaded"); return FS_ERR_STATE; }
     if (ctx->ops_dye.lanes() == 0) return FS_OK;
-    FS_DISPATCH(ctx, {
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         return launch(ctx, "dye_bc", [=] {
-            FS_KLAUNCH(k_dye_bc<T>, dim3((ctx->ops_dye.lanes() + 255) / 256), dim3(256), 0, ctx->stream,
+            klaunch(k_dye_bc<T>, dim3((ctx->ops_dye.lanes() + 255) / 256), dim3(256), ctx->stream,
                                ctx->grid(), ctx->ops_dye.view(), row_begin, row_end, (T *)dye->d, (const T *)ctx->d_bc_dye);
         });
-    })
+    });
 }
 
 int fs_dye_bc_limit_ok(const fs_ctx *ctx, int *ok)
@@ -972,13 +979,13 @@ int fs_dye_bc_limit(fs_ctx *ctx, double limit, fs_field *v, fs_field *dye, int l
     int ok = 0;
     fs_dye_bc_limit_ok(ctx, &ok);
     if (!ok || !((float)limit * (float)limit > FS_HOT_GATE_SQ)) { set_error("fs_dye_bc_limit is not available for this context / limit (fs_dye_bc_limit_ok)"); return FS_ERR_UNSUPPORTED; }
-    FS_DISPATCH(ctx, {
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         return launch(ctx, "dye_bc", [=] {
-            FS_KLAUNCH(k_dye_bc_limit<T>, dim3(std::max((ctx->ops_dye.lanes() + 255) / 256, std::min(64, limit_end - limit_begin))), dim3(256), 0, ctx->stream,
+            klaunch(k_dye_bc_limit<T>, dim3(std::max((ctx->ops_dye.lanes() + 255) / 256, std::min(64, limit_end - limit_begin))), dim3(256), ctx->stream,
                                ctx->grid(), ctx->ops_dye.view(), row_begin, row_end, limit_begin, limit_end, (T)limit, (T *)v->d, v->hot, ctx->d_sync,
                                (T *)dye->d, (const T *)ctx->d_bc_dye);
         });
-    })
+    });
 }
 
 
@@ -994,7 +1001,7 @@ int fs_selftest_f64div(fs_ctx *ctx, double divisor, int *mismatches)
     FS_HIP(hipMalloc(&flag, sizeof(unsigned)));
     hipError_t e = hipMemsetAsync(flag, 0, sizeof(unsigned), ctx->stream);
     if (e == hipSuccess) {
-        FS_KLAUNCH(k_verify_f64div, dim3(1u << 15, 10 + 2), dim3(256), 0, ctx->stream, d, 1.0 / (double)d, tie_free((double)d) ? 0 : 1, flag);   // the form the library uses for this divisor
+        klaunch(k_verify_f64div, dim3(1u << 15, 10 + 2), dim3(256), ctx->stream, d, 1.0 / (double)d, tie_free((double)d) ? 0 : 1, flag);   // the form the library uses for this divisor
         e = hipMemcpyAsync(&h, flag, sizeof h, hipMemcpyDeviceToHost, ctx->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -1089,8 +1096,8 @@ static int box_valu_rate(fs_ctx *ctx, double budget_ms, double *ginstr_per_simd,
     for (int pass = 0; pass < 2 && e == hipSuccess; ++pass) {
         (void)hipEventRecord(e0, ctx->stream);
         for (int r = 0; r < reps; ++r) {
-            if (packed) FS_KLAUNCH(k_box_valu_pk, dim3(cus * 4), dim3(256), 0, ctx->stream, sink, 1.0000001f, 1e-9f, iters);
-            else FS_KLAUNCH(k_box_valu, dim3(cus * 4), dim3(256), 0, ctx->stream, sink, 1.0000001f, 1e-9f, iters);
+            if (packed) klaunch(k_box_valu_pk, dim3(cus * 4), dim3(256), ctx->stream, sink, 1.0000001f, 1e-9f, iters);
+            else klaunch(k_box_valu, dim3(cus * 4), dim3(256), ctx->stream, sink, 1.0000001f, 1e-9f, iters);
         }
         (void)hipEventRecord(e1, ctx->stream);
         e = hipEventSynchronize(e1);
@@ -1148,7 +1155,7 @@ int fs_box_mixed_rate(fs_ctx *ctx, size_t bytes, double budget_ms, double *GBps)
     int reps = 1;
     for (int pass = 0; pass < 2 && e == hipSuccess; ++pass) {
         (void)hipEventRecord(e0, ctx->stream);
-        for (int r = 0; r < reps; ++r) FS_KLAUNCH(k_box_mixed, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, ctx->stream, a, b, n, 1.0000001f, 1e-9f);
+        for (int r = 0; r < reps; ++r) klaunch(k_box_mixed, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), ctx->stream, a, b, n, 1.0000001f, 1e-9f);
         (void)hipEventRecord(e1, ctx->stream);
         e = hipEventSynchronize(e1);
         float ms = 0.f;
@@ -1190,8 +1197,8 @@ int fs_box_rates(fs_ctx *ctx, size_t bytes, double budget_ms, double *read_GBps,
         for (int pass = 0; pass < 2 && e == hipSuccess; ++pass) {
             (void)hipEventRecord(e0, ctx->stream);
             for (int r = 0; r < reps; ++r) {
-                if (copy) FS_KLAUNCH(k_box_copy, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, ctx->stream, a, b, n);
-                else FS_KLAUNCH(k_box_read, dim3(2048), dim3(256), 0, ctx->stream, a, sink, n);
+                if (copy) klaunch(k_box_copy, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), ctx->stream, a, b, n);
+                else klaunch(k_box_read, dim3(2048), dim3(256), ctx->stream, a, sink, n);
             }
             (void)hipEventRecord(e1, ctx->stream);
             e = hipEventSynchronize(e1);
@@ -1220,18 +1227,18 @@ int fs_limit_field(fs_ctx *ctx, double limit, fs_field *v, int row_begin, int ro
     FS_REQUIRE(ctx, "ctx is null");
     FS_FIELD(v, 2);
     FS_ROWS();
-    FS_DISPATCH(ctx, {
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         if (ctx->use_pairs) {      // (any even width: the quads stop at the row's width)
             // gated by the buffer's "hot" flag (fs_device.h): while no writer has stored a speed above 9.95 the pass has nothing to do
             const int gated = (T)limit * (T)limit > (T)FS_HOT_GATE_SQ && ctx->limit_gate ? 1 : 0;
             const int lanes = std::min(row_end - row_begin, 256);
             return launch(ctx, "limit_field", [=] {
-                FS_KLAUNCH((k_limit_quad<T>), dim3(((ctx->X + 3) / 4 + 255) / 256, lanes), dim3(256), 0, ctx->stream,
+                klaunch(k_limit_quad<T>, dim3(((ctx->X + 3) / 4 + 255) / 256, lanes), dim3(256), ctx->stream,
                                    ctx->grid(), row_begin, row_end, (T)limit, (T *)v->d, v->hot, gated);
             });
         }
-        FS_LAUNCH_CELLS("limit_field", (k_limit<T>), ctx->grid(), row_begin, (T)limit, (T *)v->d)
-    })
+        return launch_cells(ctx, "limit_field", k_limit<T>, row_begin, row_end, (T)limit, (T *)v->d);
+    });
 }
 
 int fs_clamp_field(fs_ctx *ctx, double low, double high, fs_field *f, int row_begin, int row_end)
@@ -1240,28 +1247,24 @@ int fs_clamp_field(fs_ctx *ctx, double low, double high, fs_field *f, int row_be
     FS_REQUIRE(f->ctx == ctx, "field from another context");
     FS_ROWS();
     const int C = f->C;
-    FS_DISPATCH(ctx, {
-        if (C == 1) { FS_LAUNCH_CELLS("clamp_field_c1", (k_clamp<1, T>), ctx->grid(), row_begin, (T)low, (T)high, (T *)f->d) }
-        else if (C == 2) { FS_LAUNCH_CELLS("clamp_field_c2", (k_clamp<2, T>), ctx->grid(), row_begin, (T)low, (T)high, (T *)f->d) }
-        else { FS_LAUNCH_CELLS("clamp_field", (k_clamp<3, T>), ctx->grid(), row_begin, (T)low, (T)high, (T *)f->d) }
-    })
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
+        if (C == 1) return launch_cells(ctx, "clamp_field_c1", k_clamp<1, T>, row_begin, row_end, (T)low, (T)high, (T *)f->d);
+        if (C == 2) return launch_cells(ctx, "clamp_field_c2", k_clamp<2, T>, row_begin, row_end, (T)low, (T)high, (T *)f->d);
+        return launch_cells(ctx, "clamp_field", k_clamp<3, T>, row_begin, row_end, (T)low, (T)high, (T *)f->d);
+    });
 }
 
 // ---- visualisation (GUI side of the reference; device kernels so that a frame costs one pass + one download) ------------
 static int visualize(fs_ctx *ctx, int mode, double dx, fs_field *rgb, const fs_field *a, const fs_field *b, int row_begin, int row_end)
 {
     static const char *names[4] = {"vis_norm", "vis_pressure", "vis_vorticity", "vis_dye"};
-    FS_DISPATCH(ctx, {
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         auto k = make_konst<T>(ctx, 1.0, dx, 1.0);
         const T *pa = (const T *)a->d, *pb = b ? (const T *)b->d : nullptr;
         return launch(ctx, names[mode], [=] {
-            const dim3 grid = cells_grid(ctx, row_begin, row_end);
-            if (mode == 0) FS_KLAUNCH((k_visualize<0, T>), grid, dim3(256), 0, ctx->stream, ctx->grid(), k, row_begin, (T *)rgb->d, pa, pb);
-            else if (mode == 1) FS_KLAUNCH((k_visualize<1, T>), grid, dim3(256), 0, ctx->stream, ctx->grid(), k, row_begin, (T *)rgb->d, pa, pb);
-            else if (mode == 2) FS_KLAUNCH((k_visualize<2, T>), grid, dim3(256), 0, ctx->stream, ctx->grid(), k, row_begin, (T *)rgb->d, pa, pb);
-            else FS_KLAUNCH((k_visualize<3, T>), grid, dim3(256), 0, ctx->stream, ctx->grid(), k, row_begin, (T *)rgb->d, pa, pb);
+            return pick<0, 1, 2, 3>(mode, [&](auto MODE) { klaunch_cells(k_visualize<MODE, T>, ctx, row_begin, row_end, k, (T *)rgb->d, pa, pb); });
         });
-    })
+    });
 }
 
 int fs_vis_norm(fs_ctx *ctx, fs_field *rgb, const fs_field *v, const fs_field *p, int row_begin, int row_end)
@@ -1360,23 +1363,23 @@ int fs_tracer_advance(fs_ctx *ctx, fs_tracer *t, double h, double limit, const f
     if (t->inertial) {
         const size_t n = (size_t)t->n;
         const TracerInertial q{t->d_vel, t->d_vel + n, t->d_vel + 2 * n, t->d_vel + 3 * n, t->gx, t->gy, t->d_dep};
-        FS_DISPATCH(ctx, {
+        return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
             return launch(ctx, "tracer_advance_inertial", [=] {
                 if (limit > 0.0)
-                    FS_KLAUNCH((k_tracer_advance_inertial<T, true>), grid, dim3(TRACER_WG), 0, ctx->stream, ctx->grid(), Y, h, limit, respawn, max_age, td, q, (const T *)v->d);
+                    klaunch(k_tracer_advance_inertial<T, true>, grid, dim3(TRACER_WG), ctx->stream, ctx->grid(), Y, h, limit, respawn, max_age, td, q, (const T *)v->d);
                 else
-                    FS_KLAUNCH((k_tracer_advance_inertial<T, false>), grid, dim3(TRACER_WG), 0, ctx->stream, ctx->grid(), Y, h, limit, respawn, max_age, td, q, (const T *)v->d);
+                    klaunch(k_tracer_advance_inertial<T, false>, grid, dim3(TRACER_WG), ctx->stream, ctx->grid(), Y, h, limit, respawn, max_age, td, q, (const T *)v->d);
             });
-        })
+        });
     }
-    FS_DISPATCH(ctx, {
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         return launch(ctx, "tracer_advance", [=] {
             if (limit > 0.0)
-                FS_KLAUNCH((k_tracer_advance<T, true>), grid, dim3(TRACER_WG), 0, ctx->stream, ctx->grid(), Y, h, limit, respawn, max_age, td, (const T *)v->d);
+                klaunch(k_tracer_advance<T, true>, grid, dim3(TRACER_WG), ctx->stream, ctx->grid(), Y, h, limit, respawn, max_age, td, (const T *)v->d);
             else
-                FS_KLAUNCH((k_tracer_advance<T, false>), grid, dim3(TRACER_WG), 0, ctx->stream, ctx->grid(), Y, h, limit, respawn, max_age, td, (const T *)v->d);
+                klaunch(k_tracer_advance<T, false>, grid, dim3(TRACER_WG), ctx->stream, ctx->grid(), Y, h, limit, respawn, max_age, td, (const T *)v->d);
         });
-    })
+    });
 }
 
 // id (slot -> seed index) on the host, synchronised; FS_ERR_STATE when an entry lies outside 0 .. n - 1
@@ -1510,25 +1513,25 @@ int fs_tracer_sort(fs_ctx *ctx, fs_tracer *t)
     hipStream_t st = ctx->stream;
     FS_HIP(hipMemsetAsync(bins, 0, (size_t)nbins * sizeof(int), st));      // (a failed zeroing must not pass for a sort)
     rc = launch(ctx, "tracer_sort_count", [=] {
-        FS_KLAUNCH(k_tracer_sort_count, grid, wg, 0, st, X, Y, NB, td, key, bins);
+        klaunch(k_tracer_sort_count, grid, wg, st, X, Y, NB, td, key, bins);
     });
     if (rc) return rc;
     rc = launch(ctx, "tracer_sort_scan", [=] {
-        FS_KLAUNCH(k_tracer_scan_blocks, dim3(nblocks), wg, 0, st, nbins, bins, sums);
-        FS_KLAUNCH(k_tracer_scan_sums, dim3(1), wg, 0, st, nblocks, sums);
-        FS_KLAUNCH(k_tracer_scan_add, dim3((nbins + TRACER_WG - 1) / TRACER_WG), wg, 0, st, nbins, bins, (const int *)sums);
+        klaunch(k_tracer_scan_blocks, dim3(nblocks), wg, st, nbins, bins, sums);
+        klaunch(k_tracer_scan_sums, dim3(1), wg, st, nblocks, sums);
+        klaunch(k_tracer_scan_add, dim3((nbins + TRACER_WG - 1) / TRACER_WG), wg, st, nbins, bins, (const int *)sums);
     });
     if (rc) return rc;
     double *vel = t->d_vel, *sv = t->d_svel;
     const bool carry = t->inertial;
     rc = launch(ctx, "tracer_sort_scatter", [=] {
-        if (carry) FS_KLAUNCH(k_tracer_sort_scatter_inertial, grid, wg, 0, st, td, (const int *)key, bins, sx, sy, si, (const double *)vel, sv);
-        else FS_KLAUNCH(k_tracer_sort_scatter, grid, wg, 0, st, td, (const int *)key, bins, sx, sy, si);
+        if (carry) klaunch(k_tracer_sort_scatter_inertial, grid, wg, st, td, (const int *)key, bins, sx, sy, si, (const double *)vel, sv);
+        else klaunch(k_tracer_sort_scatter, grid, wg, st, td, (const int *)key, bins, sx, sy, si);
     });
     if (rc) return rc;
     rc = launch(ctx, "tracer_sort_copy", [=] {
-        if (carry) FS_KLAUNCH(k_tracer_sort_copy_inertial, grid, wg, 0, st, td, (const double *)sx, (const double *)sy, (const int *)si, vel, (const double *)sv);
-        else FS_KLAUNCH(k_tracer_sort_copy, grid, wg, 0, st, td, (const double *)sx, (const double *)sy, (const int *)si);
+        if (carry) klaunch(k_tracer_sort_copy_inertial, grid, wg, st, td, (const double *)sx, (const double *)sy, (const int *)si, vel, (const double *)sv);
+        else klaunch(k_tracer_sort_copy, grid, wg, st, td, (const double *)sx, (const double *)sy, (const int *)si);
     });
     if (rc) return rc;
     t->permuted = true;
@@ -1564,7 +1567,7 @@ int fs_tracer_fields(fs_ctx *ctx, fs_tracer *t, int *count, long long *age_sum)
     const hipError_t ez = hipMemsetAsync(d_age, 0, cells * (sizeof(unsigned long long) + sizeof(int)), st);
     if (ez != hipSuccess) { hipFree(d_age); return hip_fail(ez, "fs_tracer_fields (zeroing)", __FILE__, __LINE__); }
     int rc = launch(ctx, "tracer_fields", [=] {
-        FS_KLAUNCH(k_tracer_fields, grid, dim3(TRACER_WG), 0, st, X, Y, td, d_cnt, d_age);
+        klaunch(k_tracer_fields, grid, dim3(TRACER_WG), st, X, Y, td, d_cnt, d_age);
     });
     hipError_t e = hipSuccess;
     if (rc == FS_OK) {
@@ -1587,11 +1590,11 @@ int fs_tracer_draw(fs_ctx *ctx, fs_tracer *t, double r, double g, double b, fs_f
     const TracerDev td = tracer_dev(t);
     const dim3 grid((t->n + TRACER_WG - 1) / TRACER_WG);
     const int Y = ctx->Y;
-    FS_DISPATCH(ctx, {
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         return launch(ctx, "tracer_draw", [=] {
-            FS_KLAUNCH((k_tracer_draw<T>), grid, dim3(TRACER_WG), 0, ctx->stream, ctx->grid(), Y, td, (T)r, (T)g, (T)b, (T *)rgb->d);
+            klaunch(k_tracer_draw<T>, grid, dim3(TRACER_WG), ctx->stream, ctx->grid(), Y, td, (T)r, (T)g, (T)b, (T *)rgb->d);
         });
-    })
+    });
 }
 
 // ---- inertial sets ------------------------------------------------------------------------------------------
@@ -1735,7 +1738,7 @@ int fs_tracer_accum_add(fs_ctx *ctx, fs_tracer *t)
     long long *state = t->d_acc_state;
     unsigned long long *occ = t->d_acc, *age = t->d_acc + (size_t)X * Y;
     return launch(ctx, "tracer_accumulate", [=] {
-        FS_KLAUNCH(k_tracer_accumulate, grid, dim3(TRACER_WG), 0, ctx->stream, X, Y, td, start, every, state, occ, age);
+        klaunch(k_tracer_accumulate, grid, dim3(TRACER_WG), ctx->stream, X, Y, td, start, every, state, occ, age);
     });
 }
 

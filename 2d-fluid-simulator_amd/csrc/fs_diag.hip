@@ -77,14 +77,13 @@ int fs_flow_stats(fs_ctx *ctx, double dx, const fs_field *v, const fs_field *p, 
         ctx->stats_cap = nblocks + 1;
     }
     double *partial = ctx->d_stats, *total = ctx->d_stats + nblocks * STATS_N;
-    int rc;
-    FS_DISPATCH(ctx, {
-        rc = launch(ctx, "flow_stats", [=] {
-            FS_KLAUNCH((k_flow_stats<T>), grid, dim3(256), 0, ctx->stream, ctx->grid(), row_begin, row_end, rpw, dx, b[0], b[1], b[2], b[3],
+    const int rc = by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
+        return launch(ctx, "flow_stats", [=] {
+            klaunch(k_flow_stats<T>, grid, dim3(256), ctx->stream, ctx->grid(), row_begin, row_end, rpw, dx, b[0], b[1], b[2], b[3],
                        (const T *)v->d, (const T *)p->d, partial);
-            FS_KLAUNCH((k_flow_stats_final), dim3(1), dim3(256), 0, ctx->stream, (const double *)partial, (int)nblocks, total);
+            klaunch(k_flow_stats_final, dim3(1), dim3(256), ctx->stream, (const double *)partial, (int)nblocks, total);
         });
-    })
+    });
     if (rc) return rc;
     FS_HIP(hipMemcpyAsync(out, total, STATS_N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     FS_HIP(hipStreamSynchronize(ctx->stream));
@@ -150,15 +149,15 @@ int fs_history_record(fs_ctx *ctx, fs_history *h, double dx, double limit, const
     const int np = h->np, nf = h->nf, every = h->every, cap = h->cap, threads = h->threads, nparts = h->nparts;
     double *ring = h->d_ring, *partial = h->d_partial;
     long long *state = h->d_state;
-    FS_DISPATCH(ctx, {
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         return launch(ctx, "history_record", [=] {
             if (nparts)
-                FS_KLAUNCH((k_history_faces<T>), dim3(nparts), dim3(HIST_FACES_PER_WG), 0, ctx->stream, (const T *)p->d, fc, nf, dx, every, cap,
+                klaunch(k_history_faces<T>, dim3(nparts), dim3(HIST_FACES_PER_WG), ctx->stream, (const T *)p->d, fc, nf, dx, every, cap,
                            (const long long *)state, partial);
-            FS_KLAUNCH((k_history_record<T>), dim3(1), dim3(threads), 0, ctx->stream, (const T *)v->d, (const T *)p->d, pr, np, fc, nf,
+            klaunch(k_history_record<T>, dim3(1), dim3(threads), ctx->stream, (const T *)v->d, (const T *)p->d, pr, np, fc, nf,
                        (const double *)partial, nparts, dx, limit, every, cap, ring, state);
         });
-    })
+    });
 }
 
 int fs_history_read(fs_ctx *ctx, fs_history *h, double *out, int max_records, int *n_records, long long *launches, int *dropped)
@@ -259,18 +258,18 @@ int fs_loads_record(fs_ctx *ctx, fs_loads *l, double dx, double inv_re, double l
     const long long every = l->every, start = l->start;
     double *sums = l->d_sums, *ring = l->d_ring, *partial = l->d_partial;
     long long *state = l->d_state;
-    FS_DISPATCH(ctx, {
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         return launch(ctx, "loads_record", [=] {
             if (nparts) {
-                FS_KLAUNCH((k_loads_faces<T>), dim3(nparts), dim3(LOADS_WG), 0, ctx->stream, (const T *)v->d, (const T *)p->d, fc, nf, stride, dx,
+                klaunch(k_loads_faces<T>, dim3(nparts), dim3(LOADS_WG), ctx->stream, (const T *)v->d, (const T *)p->d, fc, nf, stride, dx,
                            inv_re, limit, start, every, (const long long *)state, sums, partial);
-                FS_KLAUNCH((k_loads_record), dim3(1), dim3(LOADS_WG), 0, ctx->stream, (const double *)partial, nparts, start, every, cap, ring, state);
+                klaunch(k_loads_record, dim3(1), dim3(LOADS_WG), ctx->stream, (const double *)partial, nparts, start, every, cap, ring, state);
             } else {
-                FS_KLAUNCH((k_loads_one<T>), dim3(1), dim3(LOADS_WG), 0, ctx->stream, (const T *)v->d, (const T *)p->d, fc, nf, stride, dx, inv_re,
+                klaunch(k_loads_one<T>, dim3(1), dim3(LOADS_WG), ctx->stream, (const T *)v->d, (const T *)p->d, fc, nf, stride, dx, inv_re,
                            limit, start, every, cap, sums, ring, state);
             }
         });
-    })
+    });
 }
 
 int fs_loads_read(fs_ctx *ctx, fs_loads *l, double *ring_out, int max_records, int *n_records, long long *launches, long long *samples,
@@ -405,17 +404,16 @@ int fs_mean_accumulate(fs_ctx *ctx, fs_mean *m, double limit, const fs_field *v,
     long long *state = m->d_state;
     double *sums = m->d_sums;
     const size_t plane = m->plane;
-    FS_DISPATCH(ctx, {
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         return launch(ctx, "mean_accumulate", [=] {
-            if (w == 2)
-                FS_KLAUNCH((k_mean_accumulate<T, 2>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, limit, start, every,
-                           (const long long *)state, (const T *)v->d, (const T *)p->d, sums, plane);
-            else
-                FS_KLAUNCH((k_mean_accumulate<T, 1>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, limit, start, every,
-                           (const long long *)state, (const T *)v->d, (const T *)p->d, sums, plane);
-            FS_KLAUNCH((k_mean_tick), dim3(1), dim3(64), 0, ctx->stream, start, every, state);
+            const bool found = pick<1, 2>(w, [&](auto W) {
+                klaunch(k_mean_accumulate<T, W>, grid, dim3(256), ctx->stream, ctx->grid(), jb, je, rpw, limit, start, every, (const long long *)state, (const T *)v->d,
+                        (const T *)p->d, sums, plane);
+            });
+            klaunch(k_mean_tick, dim3(1), dim3(64), ctx->stream, start, every, state);
+            return found;
         });
-    })
+    });
 }
 
 static int mean_counters(fs_ctx *ctx, fs_mean *m, long long *st)
@@ -442,16 +440,13 @@ int fs_mean_finalize(fs_ctx *ctx, fs_mean *m, fs_field *v_out, fs_field *p_out)
     const long long *state = m->d_state;
     const double *sums = m->d_sums;
     const size_t plane = m->plane;
-    FS_DISPATCH(ctx, {
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         return launch(ctx, "mean_finalize", [=] {
-            if (w == 2)
-                FS_KLAUNCH((k_mean_finalize<T, 2>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, state, sums, plane, (T *)v_out->d,
-                           (T *)p_out->d, v_out->hot);
-            else
-                FS_KLAUNCH((k_mean_finalize<T, 1>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, state, sums, plane, (T *)v_out->d,
-                           (T *)p_out->d, v_out->hot);
+            return pick<1, 2>(w, [&](auto W) {
+                klaunch(k_mean_finalize<T, W>, grid, dim3(256), ctx->stream, ctx->grid(), jb, je, rpw, state, sums, plane, (T *)v_out->d, (T *)p_out->d, v_out->hot);
+            });
         });
-    })
+    });
 }
 
 int fs_mean_read(fs_ctx *ctx, fs_mean *m, double *sums_out, long long *launches, long long *samples)
@@ -584,20 +579,16 @@ int fs_modes_accumulate(fs_ctx *ctx, fs_modes *m, double limit, const fs_field *
     const size_t plane = m->plane;
     ModesRot rot;
     for (int k = 0; k < MODES_MAX_FREQ; ++k) { rot.cd[k] = m->cd[k]; rot.sd[k] = m->sd[k]; }
-#define FS_MODES_ACC(W_, K_)                                                                                                                   \
-    FS_KLAUNCH((k_modes_accumulate<T, W_, K_>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, limit, start, every,                \
-               (const long long *)state, (const double *)scal, (const T *)v->d, (const T *)p->d, sums, plane)
-#define FS_MODES_ACC_W(W_)                                                                                                                     \
-    switch (nfreq) { case 1: FS_MODES_ACC(W_, 1); break; case 2: FS_MODES_ACC(W_, 2); break; case 3: FS_MODES_ACC(W_, 3); break;              \
-                     default: FS_MODES_ACC(W_, 4); break; }
-    FS_DISPATCH(ctx, {
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         return launch(ctx, "modes_accumulate", [=] {
-            if (w == 2) { FS_MODES_ACC_W(2) } else { FS_MODES_ACC_W(1) }
-            FS_KLAUNCH((k_modes_tick), dim3(1), dim3(64), 0, ctx->stream, nfreq, rot, start, every, state, scal);
+            const bool found = pick<1, 2>(w, [&](auto W) { return pick<1, 2, 3, 4>(nfreq, [&](auto NFREQ) {
+                klaunch(k_modes_accumulate<T, W, NFREQ>, grid, dim3(256), ctx->stream, ctx->grid(), jb, je, rpw, limit, start, every, (const long long *)state,
+                        (const double *)scal, (const T *)v->d, (const T *)p->d, sums, plane);
+            }); });
+            klaunch(k_modes_tick, dim3(1), dim3(64), ctx->stream, nfreq, rot, start, every, state, scal);
+            return found;
         });
-    })
-#undef FS_MODES_ACC_W
-#undef FS_MODES_ACC
+    });
 }
 
 int fs_modes_combine(fs_ctx *ctx, fs_modes *m, const double *weights, fs_field *v_out, fs_field *p_out)
@@ -614,16 +605,13 @@ int fs_modes_combine(fs_ctx *ctx, fs_modes *m, const double *weights, fs_field *
     for (int k = 0; k < 3 * MODES_MAX_B; ++k) wgt.w[k] = k < 3 * B ? weights[k] : 0.0;
     const double *sums = m->d_sums;
     const size_t plane = m->plane;
-    FS_DISPATCH(ctx, {
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         return launch(ctx, "modes_combine", [=] {
-            if (w == 2)
-                FS_KLAUNCH((k_modes_combine<T, 2>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, B, wgt, sums, plane, (T *)v_out->d,
-                           (T *)p_out->d, v_out->hot);
-            else
-                FS_KLAUNCH((k_modes_combine<T, 1>), grid, dim3(256), 0, ctx->stream, ctx->grid(), jb, je, rpw, B, wgt, sums, plane, (T *)v_out->d,
-                           (T *)p_out->d, v_out->hot);
+            return pick<1, 2>(w, [&](auto W) {
+                klaunch(k_modes_combine<T, W>, grid, dim3(256), ctx->stream, ctx->grid(), jb, je, rpw, B, wgt, sums, plane, (T *)v_out->d, (T *)p_out->d, v_out->hot);
+            });
         });
-    })
+    });
 }
 
 int fs_modes_read(fs_ctx *ctx, fs_modes *m, double *sums_out, double *scalars_out, long long *launches, long long *samples)

@@ -49,15 +49,16 @@ struct BcOpsDev {
 };
 
 // Which __global__ functions a profiled launch name stands for (fs_prof_kernels: bench.py quotes the demangled symbols instead of string
-// literals).  Every kernel launch of the library is written FS_KLAUNCH(kernel, grid, block, lds, stream, args...): the host stub's address
+// literals).  Every kernel launch of the library is written klaunch(kernel, grid, block, stream, args...): the host stub's address
 // is noted per thread, and fs::launch() (fs_launch.h) files the notes of the callable it just ran under the launch's profile name.
 struct KernelNotes { const void *fn[4]; int n; };
 extern thread_local KernelNotes kernel_notes;      // fs_core.hip
-#define FS_KLAUNCH(kern, grid, block, lds, stream, ...)                                                        \
-    do {                                                                                                       \
-        if (fs::kernel_notes.n < 4) fs::kernel_notes.fn[fs::kernel_notes.n++] = (const void *)(kern);           \
-        hipLaunchKernelGGLInternal((kern), (grid), (block), (lds), (stream), __VA_ARGS__);                     \
-    } while (0)
+template <typename... P, typename... A>
+inline void klaunch(void (*kern)(P...), dim3 grid, dim3 block, hipStream_t stream, A... args)
+{
+    if (kernel_notes.n < 4) kernel_notes.fn[kernel_notes.n++] = (const void *)kern;
+    kern<<<grid, block, 0, stream>>>(args...);
+}
 
 struct ProfRec {
     int name_id;

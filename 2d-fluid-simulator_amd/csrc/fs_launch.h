@@ -1,8 +1,17 @@
 // fs_launch.h - host-side launch plumbing shared by the translation units behind the C-ABI (fs_core.hip: contexts, fields, scene upload,
 // boundary kernels, graphs / tapes / profiling; fs_transport.hip: K2 - K6, K10 - K13; fs_pressure.hip: K7 - K8, the Poisson residual;
 // fs_diag.hip: flow diagnostics, history, body loads, time averages, harmonic modes):
-// the launch wrapper (profiling events, tape recording), XCD-band launch geometry with compact tile lists, division-mode dispatch,
+// the launch wrapper (profiling events, tape recording), XCD-band launch geometry with compact tile lists, the typed kernel dispatch,
 // argument checks.
+//
+// A launch site reads:   return launch(ctx, "name", [=] { return with_dm_all<T>(dm, [&](auto DM) { klaunch(k_foo<2, 4, DM, T>, og, ctx->stream, k, jb, je, ...); }); });
+//   launch()           runs the callable (captures BY VALUE) under the profile name, records it on an open tape, turns "no variant" into an error;
+//   pick / pick_bool / with_dm_* (fs_pick.h)   make a run-time value a template argument, for the values listed there and no others;
+//   klaunch()          notes the kernel for fs_prof_kernels and launches it - with explicit grid and block (fs_host.h), from an OvGrid (a tile
+//                      kernel: grid, threads, Grid, nbx, nby come from the object), or one cell per lane over a row range (klaunch_cells);
+//   by_dtype()         runs a callable with T = float or double, by the context's dtype.
+// How to add a kernel variant: add its value to the list of the pick<...> at the launch site (a new rows-per-tile: pick<2, 4, 8>(rt, ...)) or one
+// more branch where the variant exists for some combinations only.  Nothing else names the instantiation.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -11,11 +20,21 @@
 #include <type_traits>
 
 #include "fs_host.h"
+#include "fs_pick.h"
 
 namespace fs {
 
 hipEvent_t prof_event(fs_ctx *c);      // fs_core.hip
 
+
+// f(): true unless it returns the false of a pick (fs_pick.h) that found no kernel for its value
+template <typename F>
+inline bool launched(const F &f)
+{
+    if constexpr (std::is_void<decltype(f())>::value) { f(); return true; }
+    else return f();
+}
+int no_variant(const char *name);      // fs_core.hip: sets the error text, returns FS_ERR_UNSUPPORTED
 
 // Every kernel launch of the library goes through here.  The callable captures its arguments BY VALUE: while a tape is being
 // recorded (fs_tape_begin) a copy is kept and re-issued by fs_tape_replay without going back through the caller.
@@ -23,8 +42,8 @@ template <typename F>
 inline int launch(fs_ctx *c, const char *name, F &&f)
 {
     if (c->tape_rec) {
-        c->tape_rec->ops.emplace_back([f]() -> int {
-            f();
+        c->tape_rec->ops.emplace_back([f, name]() -> int {
+            if (!launched(f)) return no_variant(name);
             hipError_t e = hipGetLastError();
             return e == hipSuccess ? FS_OK : hip_fail(e, "tape replay", __FILE__, __LINE__);
         });
@@ -47,7 +66,7 @@ inline int launch(fs_ctx *c, const char *name, F &&f)
         (void)hipEventRecord(rec.start, c->stream);
     }
     kernel_notes.n = 0;
-    f();
+    const bool found = launched(f);
     if (prof) {
         (void)hipEventRecord(rec.stop, c->stream);
         c->prof_recs.push_back(rec);
@@ -57,7 +76,7 @@ inline int launch(fs_ctx *c, const char *name, F &&f)
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, name, __FILE__, __LINE__);
-    return FS_OK;
+    return found ? FS_OK : no_variant(name);
 }
 
 // Grids below 2 M cells have few waves per SIMD: a launch takes as long as ONE wave's chain of loads, stages and stores, and
@@ -78,11 +97,44 @@ static inline int whole_grid(const fs_ctx *c, int jb, int je) { return c->halo =
 
 static inline dim3 cells_grid(const fs_ctx *c, int jb, int je) { return dim3((c->X + 255) / 256, je - jb, 1); }
 
+// plain and boundary workgroups as two compact launches (fs_ctx::rbpair_split): always, or from `threshold` cells on
+static inline bool split_launch(const fs_ctx *c, size_t cells, size_t threshold) { return c->rbpair_split == 2 || (c->rbpair_split == 1 && cells >= threshold); }
+
+// one-cell-per-lane kernels over rows [jb, je): k_foo(Grid, Konst<T>, jb, ...) and k_foo(Grid, jb, ...)
+template <typename K, typename... P, typename... A>
+inline void klaunch_cells(void (*kern)(Grid, Konst<K>, int, P...), const fs_ctx *c, int jb, int je, const Konst<K> &k, A... args)
+{
+    klaunch(kern, cells_grid(c, jb, je), dim3(256), c->stream, c->grid(), k, jb, args...);
+}
+template <typename... P, typename... A>
+inline void klaunch_cells(void (*kern)(Grid, int, P...), const fs_ctx *c, int jb, int je, A... args)
+{
+    klaunch(kern, cells_grid(c, jb, je), dim3(256), c->stream, c->grid(), jb, args...);
+}
+// ... as a launch of their own
+template <typename Kern, typename... A>
+inline int launch_cells(fs_ctx *c, const char *name, Kern kern, int jb, int je, A... args)
+{
+    return launch(c, name, [=] { klaunch_cells(kern, c, jb, je, args...); });
+}
+
 // overlapped-wave tile kernels: nbx blocks of `threads / 64` waves across, nby tile rows, XCD-band 1-D launch
 struct OvGrid {
     int nbx, nby; dim3 grid; Grid g; int threads = 256;      // threads: 64 x waves per workgroup
     const fs_ctx::TileList *list = nullptr;                  // the launch list behind g.tiles (until the next mask), or null: a dense launch
+    OvGrid with_threads(int n) const { OvGrid o = *this; o.threads = n; return o; }      // (kernels whose list entry is a tile of several component waves)
 };
+// tile kernels take their geometry from the OvGrid handed in: k_foo(Grid, Konst<T>, nbx, nby, ...) and k_foo(Grid, nbx, nby, ...)
+template <typename K, typename... P, typename... A>
+inline void klaunch(void (*kern)(Grid, Konst<K>, int, int, P...), const OvGrid &og, hipStream_t stream, const Konst<K> &k, A... args)
+{
+    klaunch(kern, og.grid, dim3(og.threads), stream, og.g, k, og.nbx, og.nby, args...);
+}
+template <typename... P, typename... A>
+inline void klaunch(void (*kern)(Grid, int, int, P...), const OvGrid &og, hipStream_t stream, A... args)
+{
+    klaunch(kern, og.grid, dim3(og.threads), stream, og.g, og.nbx, og.nby, args...);
+}
 enum { XCD_RBSOR = 1, XCD_VORT = 2, XCD_ADVECT = 4, XCD_NONADV = 8, XCD_GRAD = 16, XCD_JACOBI = 32 };
 
 // A tile kernel's launch, said in words at the call site: tiles(family, lanes) and what differs from a dense-or-skipping launch of 4-wave
@@ -160,17 +212,6 @@ static inline OvGrid ov_grid(fs_ctx *c, int jb, int je, const TileLaunch &asked)
     return o;
 }
 
-// Division-mode dispatch (fs_device.h DM_*): CALL(DM) is expanded for the modes a kernel family distinguishes.  f32 fields divide by their
-// loop-invariant divisors through the f64 multiplication (modes 4 / 5; divisors that admit a tie: IEEE division, modes 0 / 1); power-of-two dx-derived
-// divisors by exact multiplication (bit 0).
-#define FS_F32_ONLY(dm, bits, CALL, MODE) if constexpr (std::is_same<T, float>::value) { if (((dm) & 7) == (bits)) { CALL(MODE); break; } }
-#define FS_DMC(dm, CALL)      /* modes 0 / 4 : no dx-derived divisor                */ \
-    do { FS_F32_ONLY(dm, 4, CALL, 4) CALL(0); } while (0)
-#define FS_DMX(dm, CALL)      /* modes 0 / 1 / 4 : dx-derived divisors only         */ \
-    do { if ((dm) & 1) { CALL(1); break; } FS_F32_ONLY(dm, 4, CALL, 4) CALL(0); } while (0)
-#define FS_DMA(dm, CALL)      /* modes 0 / 1 / 4 / 5 : both kinds                   */ \
-    do { FS_F32_ONLY(dm, 5, CALL, 5) FS_F32_ONLY(dm, 4, CALL, 4) if ((dm) & 1) { CALL(1); break; } CALL(0); } while (0)
-
 int check_rows(const fs_ctx *c, int jb, int je);                               // fs_core.hip
 int check_field(const fs_ctx *c, const fs_field *f, int C, const char *what);
 int ensure_stage(fs_ctx *c, size_t bytes);
@@ -188,14 +229,9 @@ int ensure_stage(fs_ctx *c, size_t bytes);
         if (row_begin == row_end) return FS_OK;                    \
     } while (0)
 
-// dispatch on ctx dtype: BODY sees `T`
-#define FS_DISPATCH(ctx, ...)                                      \
-    if ((ctx)->dtype == 0) { using T = float; __VA_ARGS__ }        \
-    else { using T = double; __VA_ARGS__ }
-
-#define FS_LAUNCH_CELLS(name, kern, ...)                                                                   \
-    return launch(ctx, name, [=] {                                                                         \
-        FS_KLAUNCH(kern, cells_grid(ctx, row_begin, row_end), dim3(256), 0, ctx->stream, __VA_ARGS__); \
-    });
+// dispatch on ctx dtype: f(Type<float>{}) or f(Type<double>{}), whose int it returns (`using T = typename decltype(tag)::type;`)
+template <typename T> struct Type { using type = T; };
+template <typename F>
+inline int by_dtype(const fs_ctx *c, F &&f) { return c->dtype == 0 ? f(Type<float>{}) : f(Type<double>{}); }
 
 }  // namespace fs
