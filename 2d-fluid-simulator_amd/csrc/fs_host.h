@@ -132,6 +132,7 @@ struct fs_ctx {
     std::set<fs_history *> histories;        // live history rings (fs_history_create), released with the context
     std::set<fs_mean *> means;               // live time averages (fs_mean_create), released with the context
     std::set<fs_modes *> modes;              // live harmonic-mode accumulators (fs_modes_create), released with the context
+    std::set<fs_mg *> mgs;                   // live multigrid hierarchies (fs_mg_create), released with the context
     std::set<fs_loads *> loads;              // live body trackers (fs_loads_create), released with the context
     std::set<fs_tracer *> tracers;           // live tracer sets (fs_tracer_create), released with the context
     // a *_free during a hipGraph capture (neither a synchronisation nor hipFree is legal there: either invalidates the capture) leaves its
@@ -260,6 +261,7 @@ void history_release(fs_history *h);      // fs_diag.hip
 void mean_release(fs_mean *m);            // fs_diag.hip
 void loads_release(fs_loads *l);          // fs_diag.hip
 void modes_release(fs_modes *m);          // fs_diag.hip
+void mg_release(fs_mg *m);                // fs_multigrid.hip
 
 // HIP-event pair around a span of stream work that is not one kernel launch (fs_core.hip; the ghost-row exchange chain of fs_comm.hip)
 ProfRec prof_span_begin(fs_ctx *c, const char *name, hipStream_t stream);

@@ -10,6 +10,6 @@ from .boundary_condition import (BoundaryCondition, DyeBoundaryCondition,  # noq
                                  get_boundary_condition)
 from .double_buffer import DoubleBuffer  # noqa: F401
 from .fluid_simulator import DyeFluidSimulator, FluidSimulator  # noqa: F401
-from .pressure_updater import JacobiPressureUpdater, RedBlackSorPressureUpdater  # noqa: F401
+from .pressure_updater import JacobiPressureUpdater, MultigridPressureUpdater, RedBlackSorPressureUpdater  # noqa: F401
 from .solver import CipMacSolver, DyeCipMacSolver, DyeMacSolver, MacSolver  # noqa: F401
 from .vorticity_confinement import VorticityConfinement  # noqa: F401

@@ -3,7 +3,7 @@
 `create()` composes boundary condition + vorticity confinement + red-black SOR(omega 1.3, 2 iterations)
 + solver exactly like the reference (fs/fluid_simulator.py:60-108, 129-176); `step()` is the hot path.
 `pressure_updater=` is an extension (the reference hard-codes RB-SOR): ("jacobi", n_iter) or
-("rbsor", omega, n_iter) or a ready PressureUpdater factory.
+("rbsor", omega, n_iter) or ("multigrid", n_cycles[, omega]) or a ready PressureUpdater factory.
 """
 import math
 
@@ -15,7 +15,7 @@ from .boundary_condition import get_boundary_condition
 from .history import Recorder, body_faces, check_probes
 from .loads import Tracker, body_centroid, face_geometry
 from .modes import Modes, fit as fit_modes, gram_matrix, phasor_steps, reconstruct_weights
-from .pressure_updater import JacobiPressureUpdater, RedBlackSorPressureUpdater
+from .pressure_updater import JacobiPressureUpdater, MultigridPressureUpdater, RedBlackSorPressureUpdater
 from .solver import CipMacSolver, DyeCipMacSolver, DyeMacSolver, MacSolver
 from .tracers import TracerAccumulation, Tracers, check_seeds, response
 from .vorticity_confinement import VorticityConfinement
@@ -33,6 +33,8 @@ def _make_updater(spec, bc, dt, dx):
         return RedBlackSorPressureUpdater(bc, dt, dx, relaxation_factor=float(spec[1]), n_iter=int(spec[2]))
     if kind == "jacobi":
         return JacobiPressureUpdater(bc, dt, dx, int(spec[1]))
+    if kind == "multigrid":       # ("multigrid", n_cycles[, omega])
+        return MultigridPressureUpdater(bc, dt, dx, relaxation_factor=float(spec[2]) if len(spec) > 2 else 1.3, n_cycles=int(spec[1]))
     raise ValueError(f"Unknown pressure updater: {spec!r}")
 
 
@@ -340,6 +342,14 @@ class FluidSimulator:
         return {"v": fields[0].to_numpy(), "p": fields[1].to_numpy()}
 
     # -- diagnostics (new; the reference's user watches the window instead) ----------------------------------------------
+    def pressure_residual(self):
+        """rms over the not-wall cells of predict_p(p) - p for the fields get_fields() returns (include/fs_hip.h fs_poisson_residual): how far
+        the pressure is from solving its own equation.  A download: not inside a graph capture."""
+        self._not_capturing("pressure_residual")
+        v, p = self._solver.get_fields()[:2]
+        s, n = self._dev.poisson_residual(self._solver.dt, self._solver.dx, p, v)
+        return math.sqrt(s / n) if n > 0 else 0.0
+
     def flow_stats(self, body_box=None):
         """Scalar diagnostics of the fields get_fields() returns, computed on the GPU in one pass (include/fs_hip.h fs_flow_stats):
           kinetic_energy = 0.5 dx^2 sum_F (u^2 + w^2)     enstrophy = 0.5 dx^2 sum_F omega^2 (central differences)

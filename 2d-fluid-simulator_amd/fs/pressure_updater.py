@@ -177,3 +177,58 @@ class RedBlackSorPressureUpdater(PressureUpdater):
 
     def _update_pressures_even(self, pn, pc, vc):
         self._half(0, pn, pc, vc)
+
+
+class MultigridPressureUpdater(PressureUpdater):
+    """W-cycle multigrid around the reference's red-black SOR (new; the reference has no converging pressure solve).  Per cycle:
+    `pre` red-black iterations (the class above, unchanged - pair pass and buffer rotation included), the pressure boundary kernel on
+    p.current, then one call that restricts the fluid-cell residual 4 (predict_p - p) to the mask-aware coarse hierarchy of
+    fs/multigrid.py, runs W(1, R1) there (two coarse visits per level: V-cycles diverge with these piecewise-constant transfers) and adds
+    the prolonged correction to the fluid cells of p.current AND p.next (csrc/fs_mg.h; include/fs_hip.h fs_mg_cycle), the boundary kernel
+    on p.next, and `post` red-black iterations.  Both buffers take the correction because the reference's iteration is a two-buffer method:
+    its even half sweep blends with the value p.next held, so a correction p.next lacks comes back as (1 - omega) x itself.
+    FS_MG_TAIL=<cells>: the levels from the first one of at most that many cells down run in one workgroup (default: whatever fits its
+    LDS; 0: one launch per half sweep everywhere) - the same bits for every value.  Single GPU; nothing to checkpoint."""
+
+    def __init__(self, boundary_condition, dt, dx, relaxation_factor=1.3, n_cycles=1, pre=2, post=2, coarse_sweeps=2, coarsest_sweeps=64):
+        super().__init__(boundary_condition, dt, dx)
+        if self._dev.nranks > 1:
+            raise NotImplementedError("the multigrid pressure updater runs on a single GPU (no slabs)")
+        from .multigrid import build_hierarchy
+        self._n_cycles, self._pre, self._post = int(n_cycles), int(pre), int(post)
+        if min(self._n_cycles, self._pre, self._post, int(coarse_sweeps), int(coarsest_sweeps)) < 0:
+            raise ValueError("cycle, iteration and sweep counts must be >= 0")
+        self._relaxation_factor = relaxation_factor
+        levels = build_hierarchy(boundary_condition.mask, self._dev.dtype)      # (ValueError: odd extents, no coarse level)
+        tail = int(os.environ.get("FS_MG_TAIL", "-1"))
+        self._mg = self._dev.mg_create(levels, tail, int(coarse_sweeps), int(coarsest_sweeps))
+        self.levels = [lv[0].shape for lv in levels]
+        # one inner updater serves both smoothing legs (its iteration count is set per leg): one pair of rotating spare buffers
+        self._inner = RedBlackSorPressureUpdater(boundary_condition, dt, dx, relaxation_factor, max(self._pre, self._post, 1))
+
+    @property
+    def _spare(self):
+        """The inner updater's rotating buffers (FluidSimulator._signature)."""
+        return self._inner._spare
+
+    def info(self):
+        """{"levels", "tail_level" (0: no one-workgroup kernel), "launches" of the last correction}."""
+        return self._dev.mg_info(self._mg)
+
+    def _smooth(self, n, p, v_current):
+        self._inner._n_iter = n
+        self._inner.update(p, v_current)
+
+    def update(self, p, v_current):
+        for _ in range(self._n_cycles):
+            self._smooth(self._pre, p, v_current)
+            self._bc.set_pressure_boundary_condition(p.current)
+            self._dev.mg_cycle(self._mg, self.dt, self.dx, p.current, p.next, v_current)
+            self._bc.set_pressure_boundary_condition(p.next)
+            self._smooth(self._post, p, v_current)
+
+    def __del__(self):
+        try:
+            self._dev.mg_free(self._mg)
+        except Exception:
+            pass

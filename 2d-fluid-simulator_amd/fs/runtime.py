@@ -1000,6 +1000,31 @@ class Device(NativeRideOps, DeviceBase):
         _lib.call("fs_poisson_residual", self._ctx, dt, dx, ph, vh, ctypes.byref(s), ctypes.byref(n))
         return s.value, n.value
 
+    # -- multigrid pressure correction (include/fs_hip.h fs_mg_*; csrc/fs_mg.h) --------------------------------
+    def mg_create(self, levels, tail_cells, coarse_sweeps, coarsest_sweeps):
+        """levels: [(cx, cy, diag), ...] as (nx, ny) arrays of the field dtype (fs/multigrid.py) -> handle."""
+        dims = (ctypes.c_int * (2 * len(levels)))(*[n for lv in levels for n in lv[0].shape])
+        flat = [np.ascontiguousarray(np.concatenate([np.asarray(lv[k], self.dtype).T.ravel() for lv in levels])) for k in range(3)]
+        h = ctypes.c_void_p()
+        _lib.call("fs_mg_create", self._ctx, len(levels), dims, *[a.ctypes.data_as(ctypes.c_void_p) for a in flat],
+                  int(tail_cells), int(coarse_sweeps), int(coarsest_sweeps), ctypes.byref(h))
+        return h
+
+    def mg_cycle(self, h, dt, dx, pc, pn, vc):
+        """One W-cycle correction of pc and pn from the residual of pc (pc: boundary kernel applied)."""
+        for f in (pc, pn, vc):
+            self.flush_limit(f)
+        _lib.call("fs_mg_cycle", self._ctx, h, dt, dx, pc._h, pn._h, vc._h)
+
+    def mg_info(self, h):
+        v = [ctypes.c_int() for _ in range(3)]
+        _lib.call("fs_mg_info", self._ctx, h, *[ctypes.byref(x) for x in v])
+        return dict(zip(("levels", "tail_level", "launches"), (x.value for x in v)))
+
+    def mg_free(self, h):
+        if self._ctx is not None and h:
+            self._lib.fs_mg_free(self._ctx, h)
+
     def _p_allreduce_array(self, a):
         a = np.ascontiguousarray(a, np.float64).copy()
         _lib.call("fs_allreduce_sum", self._ctx, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), a.size)

@@ -70,6 +70,10 @@ def build_parser():
     p.add_argument("--stats-every", type=int, default=0,
                    help="sample the flow diagnostics (FluidSimulator.flow_stats) at the first step and every N steps into --stats-file")
     p.add_argument("--stats-file", type=str, default=None, help="CSV of the samples: step,time,<keys> (default: <out>/stats.csv)")
+    p.add_argument("--pressure", type=str, choices=["rbsor", "multigrid"], default=None,
+                   help="pressure updater: rbsor - the reference's red-black SOR(1.3, 2), the default; multigrid - W-cycles around it "
+                        "(fs.pressure_updater.MultigridPressureUpdater).  Given, --stats-every also writes a p_residual column")
+    p.add_argument("--mg-cycles", type=int, default=None, help="W-cycles per step of --pressure multigrid (default 1)")
     p.add_argument("--body", type=str, default=None,
                    help="x0,y0,x1,y1 (global cells, half-open): add the pressure force on the wall cells in this box to the samples "
                         "and the history; 'auto': the scene's obstacle (scenes 1, 3, 5, 6; fs.boundary_condition.default_body_box)")
@@ -339,8 +343,9 @@ def frame(sim, vis):
 class StatsWriter:
     """--stats-every: one CSV row per sample (step, simulated time, the keys of FluidSimulator.flow_stats; floats at full precision)."""
 
-    def __init__(self, sim, path, dt, box, stop_on_nonfinite):
+    def __init__(self, sim, path, dt, box, stop_on_nonfinite, p_residual=False):
         self.sim, self.dt, self.box, self.stop = sim, dt, box, stop_on_nonfinite
+        self.p_residual = p_residual      # --pressure given: one more column, FluidSimulator.pressure_residual
         path.parent.mkdir(parents=True, exist_ok=True)
         self.fh = open(path, "w")
         self.keys = None
@@ -348,6 +353,8 @@ class StatsWriter:
     def sample(self, step):
         """Write one row -> the number of non-finite cells found."""
         d = self.sim.flow_stats(self.box)
+        if self.p_residual:
+            d["p_residual"] = self.sim.pressure_residual()
         if self.keys is None:
             self.keys = list(d)
             self.fh.write(",".join(["step", "time"] + self.keys) + "\n")
@@ -426,6 +433,10 @@ def main(argv=None):
             parser.error(f"-bc 6: {e}")
     if (args.stop_on_nonfinite or args.stats_file) and args.stats_every <= 0:
         parser.error("--stats-file and --stop-on-nonfinite need --stats-every N")
+    if args.mg_cycles is not None and (args.pressure != "multigrid" or args.mg_cycles < 1):
+        parser.error("--mg-cycles N needs --pressure multigrid and N >= 1")
+    if args.pressure == "multigrid" and res % 2:
+        parser.error("--pressure multigrid needs an even -res (no coarse level otherwise)")
     if args.body is not None and args.stats_every <= 0 and args.history_every <= 0 and args.loads_every <= 0:
         parser.error("--body needs --stats-every N, --history-every N or --loads-every N")
     if args.loads_every < 0 or args.loads_start < 0:
@@ -529,7 +540,8 @@ def main(argv=None):
           f"Scheme: {args.advection_scheme}\nVorticity confinement: {vor_eps}")
     fs.runtime.init(gpu=args.gpu, dtype="f64" if args.f64 else "f32")
     cls = DyeFluidSimulator if enable_dye else FluidSimulator
-    sim = cls.create(args.boundary_condition, res, dt, dx, args.reynolds_num, vor_eps, args.advection_scheme)
+    updater = ("multigrid", args.mg_cycles or 1) if args.pressure == "multigrid" else None      # (None: the reference's red-black SOR(1.3, 2))
+    sim = cls.create(args.boundary_condition, res, dt, dx, args.reynolds_num, vor_eps, args.advection_scheme, pressure_updater=updater)
     out = Path(args.out)
     step0 = load_state(sim, args.load_state) if args.load_state else 0
     dev = sim._solver._bc.device
@@ -667,7 +679,8 @@ def main(argv=None):
 
     stats = None
     if args.stats_every > 0:
-        stats = StatsWriter(sim, Path(args.stats_file) if args.stats_file else out / "stats.csv", dt, box, args.stop_on_nonfinite)
+        stats = StatsWriter(sim, Path(args.stats_file) if args.stats_file else out / "stats.csv", dt, box, args.stop_on_nonfinite,
+                            p_residual=args.pressure is not None)
 
     def sample(step):
         if stats.sample(step) > 0 and stats.stop:

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 18
+#define FS_ABI_VERSION 19
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -400,6 +400,26 @@ int fs_modes_write(fs_ctx *ctx, fs_modes *m, const double *sums_in, const double
 int fs_modes_reset(fs_ctx *ctx, fs_modes *m);
 int fs_modes_free(fs_ctx *ctx, fs_modes *m);
 int fs_modes_rows(fs_ctx *ctx, int nfreq, int *accumulate_rows, int *combine_rows);
+
+/* Multigrid pressure correction (new, ABI 19): one W-cycle (two coarse visits per level) on a mask-aware hierarchy of coarse levels, for the
+ * third pressure updater (fs/pressure_updater.py MultigridPressureUpdater; kernels and operation order: csrc/fs_mg.h).  Single-GPU contexts.
+ * create:  levels 1 .. nlevels with dims = nx_1, ny_1, nx_2, ny_2, ... - level 1 half the grid, every level half the one above; cx, cy, diag:
+ *          the levels' coefficients in the context's dtype, level after level, each [ny][nx] with x contiguous (host memory; built by
+ *          fs/multigrid.py - diag 0 marks an inactive cell).  tail_cells: the levels from the first one of at most that many cells down run
+ *          in ONE workgroup that holds them in LDS (< 0: from the first level that fits the LDS of a workgroup; 0: no such kernel) - the
+ *          bits are the same for every value.  coarse_sweeps / coarsest_sweeps: red-black sweeps around every coarse visit / on the last level.
+ * cycle:   pc must hold a pressure the boundary kernel has been applied to.  R1 <- restriction of 4 (predict_p(pc, vc) - pc) over fluid
+ *          cells; E1 <- W(1, R1); pc[fluid] += E1[i >> 1, j >> 1] and pn[fluid] += the same (both buffers of the red-black pair are iterates
+ *          of the same equation).  Every launch goes on the context's stream: capturable, no synchronisation, no allocation, no atomics,
+ *          and no kernel waits for another workgroup.
+ * info:    levels; the first level the one-workgroup kernel holds (0: none); the kernel launches of the last cycle.
+ * free:    as fs_mean_free (during a capture the release is deferred to its end).  create returns FS_ERR_STATE during graph capture.       */
+typedef struct fs_mg fs_mg;
+int fs_mg_create(fs_ctx *ctx, int nlevels, const int *dims, const void *cx, const void *cy, const void *diag, long long tail_cells,
+                 int coarse_sweeps, int coarsest_sweeps, fs_mg **out);
+int fs_mg_cycle(fs_ctx *ctx, fs_mg *m, double dt, double dx, fs_field *pc, fs_field *pn, const fs_field *vc);
+int fs_mg_info(fs_ctx *ctx, fs_mg *m, int *levels, int *tail_level, int *launches);
+int fs_mg_free(fs_ctx *ctx, fs_mg *m);
 
 /* Tracer particles (new): n passive particles advanced on the device by one launch per step that can be captured in a hipGraph
  * (csrc/fs_tracer.h).  Positions are doubles in CELL units: cell (i, j) covers [i, i + 1) x [j, j + 1), its stored value sits at
