@@ -152,7 +152,7 @@ int fs_mg_create(fs_ctx *ctx, int nlevels, const int *dims, const void *cx, cons
 int fs_mg_cycle(fs_ctx *ctx, fs_mg *m, double dt, double dx, fs_field *pc, fs_field *pn, const fs_field *vc)
 {
     FS_REQUIRE(ctx && m, "null argument");
-    FS_REQUIRE(m->ctx == ctx && ctx->mgs.count(m), "multigrid hierarchy from another context or freed");
+    FS_REQUIRE(ctx->mgs.count(m), "multigrid hierarchy from another context or freed");      // (the set lookup never reads the handle)
     FS_FIELD(pc, 1); FS_FIELD(pn, 1); FS_FIELD(vc, 2);
     FS_REQUIRE(pc != pn, "the correction needs the two distinct pressure buffers of the red-black pair");
     if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
@@ -176,7 +176,7 @@ int fs_mg_cycle(fs_ctx *ctx, fs_mg *m, double dt, double dx, fs_field *pc, fs_fi
 int fs_mg_info(fs_ctx *ctx, fs_mg *m, int *levels, int *tail_level, int *launches)
 {
     FS_REQUIRE(ctx && m && levels && tail_level && launches, "null argument");
-    FS_REQUIRE(m->ctx == ctx && ctx->mgs.count(m), "multigrid hierarchy from another context or freed");
+    FS_REQUIRE(ctx->mgs.count(m), "multigrid hierarchy from another context or freed");      // (the set lookup never reads the handle)
     *levels = m->n;
     *tail_level = m->tail < 0 ? 0 : m->tail + 1;
     *launches = m->launches;
@@ -186,7 +186,7 @@ int fs_mg_info(fs_ctx *ctx, fs_mg *m, int *levels, int *tail_level, int *launche
 int fs_mg_free(fs_ctx *ctx, fs_mg *m)
 {
     if (!m) return FS_OK;
-    FS_REQUIRE(ctx && m->ctx == ctx && ctx->mgs.count(m), "multigrid hierarchy from another context or freed");
+    FS_REQUIRE(ctx && ctx->mgs.count(m), "multigrid hierarchy from another context or freed");
     ctx->mgs.erase(m);
     if (ctx->capturing) { ctx->deferred_release.push_back([m] { mg_release(m); }); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
     FS_HIP(hipStreamSynchronize(ctx->stream));

@@ -118,3 +118,157 @@ def test_box_probes_give_plausible_rates_and_refuse_nonsense(dev):
         dev.box_valu_rate(0.0)
     with pytest.raises(FsError):
         dev.box_mixed_rate(64 << 20, -1.0)
+
+
+# ---- the multigrid entry points (include/fs_hip.h fs_mg_*) ---------------------------------------------------------------------------------
+MG_DT, MG_DX = 0.05 / 32, 1.0 / 32
+
+
+@pytest.fixture()
+def mg(hip_lib):
+    """A 32 x 16 context with a random mask -> (bc, a function that runs one valid multigrid update on it and compares it with the restatement)."""
+    import fs
+    import multigrid_ref as M
+    from fs.boundary_condition import BoundaryCondition
+    from fs.double_buffer import DoubleBuffer
+    from oracle import oracle as O
+    from test_gpu_random_masks import _random_scene
+    fs.runtime.init(gpu=0, dtype="f32")
+    rng = np.random.default_rng(3216)
+    const, mask, _ = _random_scene(rng, 32, 16, 0.15, 0.03)
+    pc, pn = (rng.uniform(-1, 1, (32, 16)).astype(np.float32) for _ in range(2))
+    v = rng.uniform(-1, 1, (32, 16, 2)).astype(np.float32)
+    exp = O.Buf2(pc.shape, 1, pc.dtype)
+    exp.current[...], exp.next[...] = pc, pn
+    M.MultigridRef(O.OracleBC(const, mask, None, np.float32), MG_DT, MG_DX).update(exp, v.copy())
+    assert np.isfinite(exp.current).all() and not np.array_equal(exp.current, pc)
+    bc = BoundaryCondition(const, mask)
+    p, vf = DoubleBuffer((32, 16), 1, bc.device), bc.device.alloc(2)
+
+    def still_usable():
+        pu = fs.MultigridPressureUpdater(bc, MG_DT, MG_DX)
+        p.current.from_numpy(pc); p.next.from_numpy(pn); vf.from_numpy(v)
+        pu.update(p, vf)
+        assert np.array_equal(p.current.to_numpy(), exp.current) and np.array_equal(p.next.to_numpy(), exp.next), "the context no longer computes the restatement's update"
+        bc.device.mg_free(pu._mg)
+        pu._mg = None
+
+    yield bc, still_usable
+    bc.device.close()
+
+
+def test_mg_cycle_misuse(mg, hip_lib):
+    """One pressure buffer given twice, a hierarchy used on another context, a hierarchy used after fs_mg_free (a stale handle is only ever
+    looked up in the context's set of live hierarchies, never read)."""
+    import fs
+    from fs._lib import FsError
+    from fs.boundary_condition import BoundaryCondition
+    bc, still_usable = mg
+    dev = bc.device
+    pu = fs.MultigridPressureUpdater(bc, MG_DT, MG_DX)
+    p, q, v = dev.alloc(1), dev.alloc(1), dev.alloc(2)
+    with pytest.raises(FsError, match="distinct pressure buffers"):
+        dev.mg_cycle(pu._mg, MG_DT, MG_DX, p, p, v)
+    still_usable()
+    with pytest.raises(FsError, match="channel count"):
+        dev.mg_cycle(pu._mg, MG_DT, MG_DX, p, v, v)
+    still_usable()
+    other = BoundaryCondition(np.zeros((32, 16, 2), np.float32), np.zeros((32, 16), np.uint8)).device
+    try:
+        with pytest.raises(FsError, match="another context or freed"):
+            other.mg_cycle(pu._mg, MG_DT, MG_DX, other.alloc(1), other.alloc(1), other.alloc(2))
+        with pytest.raises(FsError, match="another context or freed"):
+            other.mg_info(pu._mg)
+        assert hip_lib.fs_mg_free(other._ctx, pu._mg) == -1 and b"another context or freed" in hip_lib.fs_last_error()
+    finally:
+        other.close()
+    assert dev.mg_info(pu._mg)["levels"] == 4              # the refused free on the other context left it alive here
+    still_usable()
+    stale, pu._mg = pu._mg, None                           # (the updater's finaliser must not free it a second time)
+    dev.mg_free(stale)
+    with pytest.raises(FsError, match="another context or freed"):
+        dev.mg_cycle(stale, MG_DT, MG_DX, p, q, v)
+    with pytest.raises(FsError, match="another context or freed"):
+        dev.mg_info(stale)
+    assert hip_lib.fs_mg_free(dev._ctx, stale) == -1 and b"another context or freed" in hip_lib.fs_last_error()
+    assert hip_lib.fs_mg_free(dev._ctx, None) == 0         # a null handle: nothing to free
+    still_usable()
+
+
+def test_mg_create_refuses_bad_hierarchies(mg, hip_lib):
+    from fs import _lib
+    from fs._lib import FsError
+    from fs.multigrid import build_hierarchy
+    bc, still_usable = mg
+    dev = bc.device
+    good = build_hierarchy(bc.mask, np.float32)
+    assert [lv[0].shape for lv in good] == [(16, 8), (8, 4), (4, 2), (2, 1)]
+
+    def level(nx, ny):
+        return tuple(np.ones((nx, ny), np.float32) for _ in range(3))
+
+    one = np.ones(1, np.float32).ctypes.data_as(ctypes.c_void_p)
+    with pytest.raises(FsError, match="nlevels"):          # (Device.mg_create cannot flatten an empty list: the entry point itself)
+        _lib.call("fs_mg_create", dev._ctx, 0, (ctypes.c_int * 2)(16, 8), one, one, one, -1, 2, 64, ctypes.byref(ctypes.c_void_p()))
+    still_usable()
+    for levels, tail, sweeps, msg in (([level(1, 1)] * 25, -1, (2, 64), "nlevels"),
+                                      (good, -1, (-1, 64), "sweep counts"),
+                                      (good, -1, (2, -1), "sweep counts"),
+                                      (good[1:], -1, (2, 64), "level 1 must be half the grid"),
+                                      ([good[0], level(4, 4)], -1, (2, 64), "half the level above"),
+                                      ([good[0], good[1], level(4, 1)], 0, (2, 64), "half the level above")):
+        with pytest.raises(FsError, match=msg):
+            dev.mg_create(levels, tail, *sweeps)
+        still_usable()
+
+
+def test_mg_create_inside_a_capture_is_a_state_error(mg):
+    from fs._lib import FsError
+    from fs.multigrid import build_hierarchy
+    bc, still_usable = mg
+    dev = bc.device
+    good = build_hierarchy(bc.mask, np.float32)
+    p = dev.alloc(1)
+    seen = []
+
+    def body():
+        dev.pressure_bc(p)
+        with pytest.raises(FsError, match="status -3: multigrid create during graph capture") as e:
+            dev.mg_create(good, -1, 2, 64)
+        seen.append(e)
+        dev.pressure_bc(p)
+
+    gid = dev.capture(body)                                # the refusal left the capture intact
+    assert seen
+    dev.replay(gid)
+    dev.free_graph(gid)
+    still_usable()
+
+
+def test_mg_constructor_refuses_an_odd_grid(hip_lib):
+    import fs
+    from fs.boundary_condition import BoundaryCondition
+    from fs.double_buffer import DoubleBuffer
+    from oracle import oracle as O
+    fs.runtime.init(gpu=0, dtype="f32")
+    rng = np.random.default_rng(3316)
+    mask = (rng.random((33, 16)) < 0.15).astype(np.uint8)
+    const = np.zeros((33, 16, 2), np.float32)
+    bc = BoundaryCondition(const, mask)
+    try:
+        with pytest.raises(ValueError, match="even grid extents"):
+            fs.MultigridPressureUpdater(bc, MG_DT, MG_DX)
+        with pytest.raises(ValueError, match=">= 0"):
+            fs.MultigridPressureUpdater(bc, MG_DT, MG_DX, coarse_sweeps=-1)
+        # no multigrid on this grid; the context still runs the red-black updater as the oracle does
+        pc = rng.uniform(-1, 1, (33, 16)).astype(np.float32)
+        v = rng.uniform(-1, 1, (33, 16, 2)).astype(np.float32)
+        exp = O.Buf2(pc.shape, 1, pc.dtype)
+        exp.current[...] = pc
+        O.OracleRedBlackSor(O.OracleBC(const, mask, None, np.float32), MG_DT, MG_DX, 1.3, 2).update(exp, v.copy())
+        p, vf = DoubleBuffer((33, 16), 1, bc.device), bc.device.alloc(2)
+        p.current.from_numpy(pc); vf.from_numpy(v)
+        fs.RedBlackSorPressureUpdater(bc, MG_DT, MG_DX, 1.3, 2).update(p, vf)
+        assert np.array_equal(p.current.to_numpy(), exp.current)
+    finally:
+        bc.device.close()

@@ -10,6 +10,7 @@ import functools
 import numpy as np
 import pytest
 
+import multigrid_cases as C
 import multigrid_ref as M
 from oracle import oracle as O
 
@@ -96,6 +97,30 @@ def test_coefficients_are_dyadic_and_the_product_builds_the_same(scene):
                 s = a * 2.0 ** k
                 assert np.array_equal(s, np.round(s))
                 assert b.dtype == np.float32 and np.array_equal(a, b.astype(np.float64))
+
+
+@pytest.mark.parametrize("wall_p", C.DENSITIES)
+@pytest.mark.parametrize("grid", list(C.SHAPES), ids=lambda g: f"{g[0]}x{g[1]}")
+def test_random_masks_through_the_host_hierarchy(grid, wall_p):
+    """What tests/test_gpu_multigrid_shapes.py rests on: on random masks (fluid on the domain edge, one-cell walls, inflow and outflow anywhere;
+    wide, tall, one-level and 1 x 1-coarsest grids) the product's mask rules equal the K7 probe, its hierarchy equals the restatement's array
+    for array in both dtypes, and one restatement update from uniform(-1, 1) fields is finite."""
+    from fs.multigrid import build_hierarchy, never_written
+    const, mask = C.scene(*grid, wall_p)
+    for dtype in ("float32", "float64"):
+        bc = O.OracleBC(const, mask, None, np.dtype(dtype))
+        assert np.array_equal(never_written(mask), M.probe_never_written(bc))
+        mg = M.MultigridRef(bc, C.DT, C.DX)
+        mine = build_hierarchy(mask, np.dtype(dtype))
+        assert [lv.shape for lv in mg.levels] == C.SHAPES[grid] == [lv[0].shape for lv in mine]
+        for lv, (cx, cy, diag) in zip(mg.levels, mine):
+            for a, b in ((lv.cx, cx), (lv.cy, cy), (lv.diag, diag)):
+                assert a.dtype == b.dtype == np.dtype(dtype) and np.array_equal(a, b)
+        pc, pn, v = C.fields(*grid, wall_p, dtype)
+        p = _buf(pc, pn)
+        mg.update(p, v.copy())
+        assert np.isfinite(p.current).all() and np.isfinite(p.next).all()
+        assert not np.array_equal(p.current, pc)
 
 
 @pytest.mark.parametrize("scene,faces", [(1, 0), (2, 4), (4, 4), (5, 0)])
