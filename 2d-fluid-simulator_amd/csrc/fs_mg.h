@@ -127,6 +127,33 @@ __global__ __launch_bounds__(256) void k_mg_prolong(MgLevel<T> f, const T *Ec, i
     if (f.diag[c] > (T)0) f.E[c] = f.E[c] + Ec[(j >> 1) * nxc + (i >> 1)];
 }
 
+// ---- the last level solved exactly (fs_mg_set_direct) ---------------------------------------------------------------------------------------
+// E[active] = M R[active] with the dense inverse M of the level's operator on its n active cells (fs/multigrid.py direct_solve; rows padded with
+// zeros to `stride` = 64 ceil(n / 64) elements).  One wave per row, MG_DIRECT_ROWS rows per workgroup; every workgroup stages the compact
+// right-hand side r in LDS once (at most 4096 elements: 32 KB in f64).  Lane l walks the columns 64 k + l - coalesced rows of M, conflict-free
+// reads of r - and the 64 partial sums meet in a halving tree.  The order is the specification (tests/multigrid_direct_ref.py):
+//     r[j] = R[cells[j]] for j < n, 0 for n <= j < stride                          (the padded columns take part: 0 * 0)
+//     a_l = 0;  for k = 0 .. stride / 64 - 1:  a_l = a_l + M[i][64 k + l] * r[64 k + l]
+//     for s = 32, 16, 8, 4, 2, 1:  a_l = a_l + a_{l + s} for l < s;    E[cells[i]] = a_0
+// Inactive cells keep the 0 the kernel that wrote R stored in E.
+constexpr int MG_DIRECT_MAX = 4096;      // active cells of a level with an exact solve
+constexpr int MG_DIRECT_ROWS = 4;        // rows (waves) per workgroup
+
+template <typename T>
+__global__ __launch_bounds__(64 * MG_DIRECT_ROWS) void k_mg_direct(const T *M, const int *cells, const T *R, T *E, int n, int stride)
+{
+    __shared__ T r[MG_DIRECT_MAX];
+    for (int j = threadIdx.x; j < stride; j += 64 * MG_DIRECT_ROWS) r[j] = j < n ? R[cells[j]] : (T)0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, i = blockIdx.x * MG_DIRECT_ROWS + (threadIdx.x >> 6);
+    if (i >= n) return;                  // (whole waves leave: the shuffles below see all 64 lanes)
+    const T *row = M + (size_t)i * stride;
+    T a = (T)0;
+    for (int c = lane; c < stride; c += 64) a = a + row[c] * r[c];
+    for (int s = 32; s >= 1; s >>= 1) a = a + __shfl_down(a, s);      // (lanes >= s add what nothing reads)
+    if (lane == 0) E[cells[i]] = a;
+}
+
 // ---- the tail: every level from `first` down in the LDS of one workgroup ----------------------------------------------------------------------
 // The levels of a W-cycle below a few thousand cells are chains of tiny dependent launches (level k is visited 2^(k-1) times per cycle).  One
 // workgroup loads their coefficients and the first level's R into LDS, runs W(first, R) with an explicit visit stack - `done` holds, per level,

@@ -15,12 +15,17 @@ struct fs_mg {
     size_t tail_bytes = 0;
     int coarse_sweeps = 2, coarsest_sweeps = 64;
     int launches = 0;                            // kernel launches of one fs_mg_cycle (counted while it runs)
+    // an exact solve attached to the LAST level (fs_mg_set_direct): E[active] = M R[active] instead of coarsest_sweeps sweeps
+    bool direct = false;
+    int direct_n = 0, direct_stride = 0;         // active cells; elements per row of M (64 ceil(n / 64))
+    int *d_cells = nullptr;                      // their indices J * nx + I in the level, ascending
+    void *d_M = nullptr;                         // [n][stride] in the field dtype
 };
 
 namespace fs {
 void mg_release(fs_mg *m)
 {
-    for (void *p : {m->d_E, m->d_R, m->d_cx, m->d_cy, m->d_diag})
+    for (void *p : {m->d_E, m->d_R, m->d_cx, m->d_cy, m->d_diag, (void *)m->d_cells, m->d_M})
         if (p) hipFree(p);
     delete m;
 }
@@ -71,12 +76,27 @@ static int mg_tail_launch(fs_ctx *ctx, fs_mg *m)
     });
 }
 
+// the last level's exact solve: one launch (none when the level has no active cell: its E stays 0)
+template <typename T>
+static int mg_direct_launch(fs_ctx *ctx, fs_mg *m)
+{
+    if (m->direct_n == 0) return FS_OK;
+    const MgLevel<T> l = mg_level<T>(m, m->n - 1);
+    const T *M = (const T *)m->d_M;
+    const int *cells = m->d_cells;
+    const int n = m->direct_n, stride = m->direct_stride;
+    ++m->launches;
+    return launch(ctx, "mg_direct", [=] {
+        klaunch(k_mg_direct<T>, dim3((n + MG_DIRECT_ROWS - 1) / MG_DIRECT_ROWS), dim3(64 * MG_DIRECT_ROWS), ctx->stream, M, cells, (const T *)l.R, l.E, n, stride);
+    });
+}
+
 // W(k, R_k): E_k is zero on entry (the kernel that wrote R_k zeroed it)
 template <typename T>
 static int mg_w(fs_ctx *ctx, fs_mg *m, int k)
 {
     if (k == m->tail) return mg_tail_launch<T>(ctx, m);
-    if (k == m->n - 1) return mg_sweeps<T>(ctx, m, k, m->coarsest_sweeps);
+    if (k == m->n - 1) return m->direct ? mg_direct_launch<T>(ctx, m) : mg_sweeps<T>(ctx, m, k, m->coarsest_sweeps);
     int rc = mg_sweeps<T>(ctx, m, k, m->coarse_sweeps);
     if (rc) return rc;
     const MgLevel<T> f = mg_level<T>(m, k), c = mg_level<T>(m, k + 1);
@@ -146,6 +166,47 @@ int fs_mg_create(fs_ctx *ctx, int nlevels, const int *dims, const void *cx, cons
     if (e != hipSuccess) { mg_release(m); return hip_fail(e, "fs_mg_create", __FILE__, __LINE__); }
     ctx->mgs.insert(m);
     *out = m;
+    return FS_OK;
+}
+
+int fs_mg_set_direct(fs_ctx *ctx, fs_mg *m, int n, const int *cells, const void *M, long long row_stride)
+{
+    FS_REQUIRE(ctx && m && cells && M, "null argument");
+    FS_REQUIRE(ctx->mgs.count(m), "multigrid hierarchy from another context or freed");      // (the set lookup never reads the handle)
+    FS_REQUIRE(n >= 0 && n <= MG_DIRECT_MAX, "a direct solve holds 0 .. 4096 active cells");
+    FS_REQUIRE(row_stride == 64ll * ((n + 63) / 64), "row_stride must be 64 * ceil(n / 64)");
+    const long long level_cells = (long long)m->nx[m->n - 1] * m->ny[m->n - 1];
+    for (int j = 0; j < n; ++j)
+        FS_REQUIRE(cells[j] >= 0 && cells[j] < level_cells && (j == 0 || cells[j] > cells[j - 1]), "cells must be strictly ascending indices of the last level");
+    if (m->tail >= 0) { set_error("a direct solve needs a hierarchy without a tail kernel (tail_cells = 0)"); return FS_ERR_STATE; }
+    if (m->direct) { set_error("this hierarchy already has a direct solve"); return FS_ERR_STATE; }
+    if (ctx->capturing || ctx->tape_rec) { set_error("multigrid set_direct during graph capture / tape recording"); return FS_ERR_STATE; }
+    FS_HIP(hipSetDevice(ctx->device));
+    int *d_cells = nullptr;
+    void *d_M = nullptr;
+    if (n > 0) {
+        const size_t mbytes = (size_t)n * (size_t)row_stride * ctx->esize;
+        hipError_t e = hipMalloc(&d_cells, (size_t)n * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc(&d_M, mbytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_cells, cells, (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_M, M, mbytes, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            if (d_cells) hipFree(d_cells);
+            if (d_M) hipFree(d_M);
+            return hip_fail(e, "fs_mg_set_direct", __FILE__, __LINE__);
+        }
+    }
+    m->direct = true; m->direct_n = n; m->direct_stride = (int)row_stride; m->d_cells = d_cells; m->d_M = d_M;
+    return FS_OK;
+}
+
+int fs_mg_direct_info(fs_ctx *ctx, fs_mg *m, int *direct_level, int *direct_cells)
+{
+    FS_REQUIRE(ctx && m && direct_level && direct_cells, "null argument");
+    FS_REQUIRE(ctx->mgs.count(m), "multigrid hierarchy from another context or freed");      // (the set lookup never reads the handle)
+    *direct_level = m->direct ? m->n : 0;
+    *direct_cells = m->direct_n;
     return FS_OK;
 }
 

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FS_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libfs_hip.so")     # FS_LIB: A/B builds (tools/)
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _lib = None
 
@@ -108,6 +108,8 @@ _PROTOS = {
     "fs_mg_create": [_c_vp, _c_int, _P(_c_int), _c_vp, _c_vp, _c_vp, ctypes.c_longlong, _c_int, _c_int, _P(_c_vp)],
     "fs_mg_cycle": [_c_vp, _c_vp, _c_dbl, _c_dbl, _c_vp, _c_vp, _c_vp],
     "fs_mg_info": [_c_vp, _c_vp, _P(_c_int), _P(_c_int), _P(_c_int)],
+    "fs_mg_set_direct": [_c_vp, _c_vp, _c_int, _P(_c_int), _c_vp, ctypes.c_longlong],
+    "fs_mg_direct_info": [_c_vp, _c_vp, _P(_c_int), _P(_c_int)],
     "fs_mg_free": [_c_vp, _c_vp],
     "fs_tracer_create": [_c_vp, _c_int, _P(_c_dbl), _c_int, _c_int, _P(_c_vp)],
     "fs_tracer_advance": [_c_vp, _c_vp, _c_dbl, _c_dbl, _c_vp],

@@ -3,7 +3,8 @@
 `create()` composes boundary condition + vorticity confinement + red-black SOR(omega 1.3, 2 iterations)
 + solver exactly like the reference (fs/fluid_simulator.py:60-108, 129-176); `step()` is the hot path.
 `pressure_updater=` is an extension (the reference hard-codes RB-SOR): ("jacobi", n_iter) or
-("rbsor", omega, n_iter) or ("multigrid", n_cycles[, omega]) or a ready PressureUpdater factory.
+("rbsor", omega, n_iter) or ("multigrid", n_cycles[, omega][, {keyword arguments of MultigridPressureUpdater}]) or a ready
+PressureUpdater factory.
 """
 import math
 
@@ -33,8 +34,10 @@ def _make_updater(spec, bc, dt, dx):
         return RedBlackSorPressureUpdater(bc, dt, dx, relaxation_factor=float(spec[1]), n_iter=int(spec[2]))
     if kind == "jacobi":
         return JacobiPressureUpdater(bc, dt, dx, int(spec[1]))
-    if kind == "multigrid":       # ("multigrid", n_cycles[, omega])
-        return MultigridPressureUpdater(bc, dt, dx, relaxation_factor=float(spec[2]) if len(spec) > 2 else 1.3, n_cycles=int(spec[1]))
+    if kind == "multigrid":       # ("multigrid", n_cycles[, omega][, {keyword arguments}])
+        kw = dict(spec[-1]) if isinstance(spec[-1], dict) else {}
+        rest = spec[:-1] if isinstance(spec[-1], dict) else spec
+        return MultigridPressureUpdater(bc, dt, dx, relaxation_factor=float(rest[2]) if len(rest) > 2 else 1.3, n_cycles=int(rest[1]), **kw)
     raise ValueError(f"Unknown pressure updater: {spec!r}")
 
 

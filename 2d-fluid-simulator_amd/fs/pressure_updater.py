@@ -188,20 +188,37 @@ class MultigridPressureUpdater(PressureUpdater):
     on p.next, and `post` red-black iterations.  Both buffers take the correction because the reference's iteration is a two-buffer method:
     its even half sweep blends with the value p.next held, so a correction p.next lacks comes back as (1 - omega) x itself.
     FS_MG_TAIL=<cells>: the levels from the first one of at most that many cells down run in one workgroup (default: whatever fits its
-    LDS; 0: one launch per half sweep everywhere) - the same bits for every value.  Single GPU; nothing to checkpoint."""
+    LDS; 0: one launch per half sweep everywhere) - the same bits for every value.  Single GPU; nothing to checkpoint.
+    coarsest="sweeps" (the default) relaxes the last level - where an extent turns odd - with `coarsest_sweeps` sweeps, which does not solve a
+    last level of more than a few dozen cells (res 100, 200, 400 end on 50 x 25).  coarsest="direct" cuts the hierarchy at the first level
+    of at most `direct_cells` cells (the last level if none is that small; ValueError beyond 4096 active cells) and solves it exactly: the
+    inverse of its operator is built once on the host (fs/multigrid.py direct_solve, float64, rounded to the field dtype) and applied with
+    one launch per visit.  Then FS_MG_TAIL is not read (no one-workgroup kernel) and `coarsest_sweeps` is ignored."""
 
-    def __init__(self, boundary_condition, dt, dx, relaxation_factor=1.3, n_cycles=1, pre=2, post=2, coarse_sweeps=2, coarsest_sweeps=64):
+    def __init__(self, boundary_condition, dt, dx, relaxation_factor=1.3, n_cycles=1, pre=2, post=2, coarse_sweeps=2, coarsest_sweeps=64,
+                 coarsest="sweeps", direct_cells=2048):
         super().__init__(boundary_condition, dt, dx)
         if self._dev.nranks > 1:
             raise NotImplementedError("the multigrid pressure updater runs on a single GPU (no slabs)")
-        from .multigrid import build_hierarchy
+        from .multigrid import build_hierarchy, direct_level, direct_solve
         self._n_cycles, self._pre, self._post = int(n_cycles), int(pre), int(post)
         if min(self._n_cycles, self._pre, self._post, int(coarse_sweeps), int(coarsest_sweeps)) < 0:
             raise ValueError("cycle, iteration and sweep counts must be >= 0")
+        if coarsest not in ("sweeps", "direct"):
+            raise ValueError(f"coarsest must be 'sweeps' or 'direct', got {coarsest!r}")
+        if int(direct_cells) < 1:
+            raise ValueError("direct_cells must be >= 1")
         self._relaxation_factor = relaxation_factor
         levels = build_hierarchy(boundary_condition.mask, self._dev.dtype)      # (ValueError: odd extents, no coarse level)
-        tail = int(os.environ.get("FS_MG_TAIL", "-1"))
-        self._mg = self._dev.mg_create(levels, tail, int(coarse_sweeps), int(coarsest_sweeps))
+        self._direct = None
+        if coarsest == "direct":
+            k = direct_level([lv[0].shape for lv in levels], int(direct_cells), [int((lv[2] > 0).sum()) for lv in levels])
+            levels = levels[:k]
+            self._mg = self._dev.mg_create(levels, 0, int(coarse_sweeps), int(coarsest_sweeps))
+            self._direct = self._dev.mg_set_direct(self._mg, *direct_solve(*levels[-1]))
+        else:
+            tail = int(os.environ.get("FS_MG_TAIL", "-1"))
+            self._mg = self._dev.mg_create(levels, tail, int(coarse_sweeps), int(coarsest_sweeps))
         self.levels = [lv[0].shape for lv in levels]
         # one inner updater serves both smoothing legs (its iteration count is set per leg): one pair of rotating spare buffers
         self._inner = RedBlackSorPressureUpdater(boundary_condition, dt, dx, relaxation_factor, max(self._pre, self._post, 1))
@@ -212,8 +229,16 @@ class MultigridPressureUpdater(PressureUpdater):
         return self._inner._spare
 
     def info(self):
-        """{"levels", "tail_level" (0: no one-workgroup kernel), "launches" of the last correction}."""
+        """{"levels", "tail_level" (0: no one-workgroup kernel), "launches" of the last correction, "direct_level" (0: the last level is
+        relaxed), "direct_cells" (the active cells of the level that is solved exactly)}."""
         return self._dev.mg_info(self._mg)
+
+    def direct_matrix(self):
+        """(cells, M) of coarsest="direct" exactly as uploaded: the active cells' indices J * nx + I in the last level (int32, ascending) and
+        the inverse in the field dtype, padding stripped."""
+        if self._direct is None:
+            raise ValueError("direct_matrix() needs coarsest='direct'")
+        return self._direct
 
     def _smooth(self, n, p, v_current):
         self._inner._n_iter = n

@@ -1016,10 +1016,23 @@ class Device(NativeRideOps, DeviceBase):
             self.flush_limit(f)
         _lib.call("fs_mg_cycle", self._ctx, h, dt, dx, pc._h, pn._h, vc._h)
 
+    def mg_set_direct(self, h, cells, M):
+        """Attach the exact solve of the hierarchy's last level: cells (n, ascending J * nx + I), M (n, n) -> (cells, M) as uploaded (int32;
+        the field dtype, padding stripped)."""
+        cells = np.ascontiguousarray(cells, np.int32)
+        n = cells.size
+        stride = 64 * ((n + 63) // 64)
+        padded = np.zeros((max(n, 1), max(stride, 1)), self.dtype)      # (never an empty buffer: the entry point refuses null pointers)
+        padded[:n, :n] = M
+        c = cells if n else np.zeros(1, np.int32)
+        _lib.call("fs_mg_set_direct", self._ctx, h, n, c.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), padded.ctypes.data_as(ctypes.c_void_p), stride)
+        return cells, np.ascontiguousarray(padded[:n, :n])
+
     def mg_info(self, h):
-        v = [ctypes.c_int() for _ in range(3)]
-        _lib.call("fs_mg_info", self._ctx, h, *[ctypes.byref(x) for x in v])
-        return dict(zip(("levels", "tail_level", "launches"), (x.value for x in v)))
+        v = [ctypes.c_int() for _ in range(5)]
+        _lib.call("fs_mg_info", self._ctx, h, *[ctypes.byref(x) for x in v[:3]])
+        _lib.call("fs_mg_direct_info", self._ctx, h, *[ctypes.byref(x) for x in v[3:]])
+        return dict(zip(("levels", "tail_level", "launches", "direct_level", "direct_cells"), (x.value for x in v)))
 
     def mg_free(self, h):
         if self._ctx is not None and h:

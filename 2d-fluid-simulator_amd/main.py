@@ -74,6 +74,10 @@ def build_parser():
                    help="pressure updater: rbsor - the reference's red-black SOR(1.3, 2), the default; multigrid - W-cycles around it "
                         "(fs.pressure_updater.MultigridPressureUpdater).  Given, --stats-every also writes a p_residual column")
     p.add_argument("--mg-cycles", type=int, default=None, help="W-cycles per step of --pressure multigrid (default 1)")
+    p.add_argument("--mg-coarsest", type=str, choices=["sweeps", "direct"], default=None,
+                   help="last level of --pressure multigrid: sweeps - 64 red-black sweeps where an extent turns odd, the default; direct - the "
+                        "hierarchy is cut at a level of at most --mg-direct-cells cells and that level is solved exactly (converges at any even -res)")
+    p.add_argument("--mg-direct-cells", type=int, default=None, help="cells of the level --mg-coarsest direct solves exactly (default 2048)")
     p.add_argument("--body", type=str, default=None,
                    help="x0,y0,x1,y1 (global cells, half-open): add the pressure force on the wall cells in this box to the samples "
                         "and the history; 'auto': the scene's obstacle (scenes 1, 3, 5, 6; fs.boundary_condition.default_body_box)")
@@ -435,6 +439,10 @@ def main(argv=None):
         parser.error("--stats-file and --stop-on-nonfinite need --stats-every N")
     if args.mg_cycles is not None and (args.pressure != "multigrid" or args.mg_cycles < 1):
         parser.error("--mg-cycles N needs --pressure multigrid and N >= 1")
+    if args.mg_coarsest is not None and args.pressure != "multigrid":
+        parser.error("--mg-coarsest needs --pressure multigrid")
+    if args.mg_direct_cells is not None and (args.pressure != "multigrid" or args.mg_direct_cells < 1):
+        parser.error("--mg-direct-cells N needs --pressure multigrid and N >= 1")
     if args.pressure == "multigrid" and res % 2:
         parser.error("--pressure multigrid needs an even -res (no coarse level otherwise)")
     if args.body is not None and args.stats_every <= 0 and args.history_every <= 0 and args.loads_every <= 0:
@@ -540,7 +548,10 @@ def main(argv=None):
           f"Scheme: {args.advection_scheme}\nVorticity confinement: {vor_eps}")
     fs.runtime.init(gpu=args.gpu, dtype="f64" if args.f64 else "f32")
     cls = DyeFluidSimulator if enable_dye else FluidSimulator
-    updater = ("multigrid", args.mg_cycles or 1) if args.pressure == "multigrid" else None      # (None: the reference's red-black SOR(1.3, 2))
+    updater = None      # (the reference's red-black SOR(1.3, 2))
+    if args.pressure == "multigrid":
+        mg_kw = {k: v for k, v in (("coarsest", args.mg_coarsest), ("direct_cells", args.mg_direct_cells)) if v is not None}
+        updater = ("multigrid", args.mg_cycles or 1) + ((mg_kw,) if mg_kw else ())
     sim = cls.create(args.boundary_condition, res, dt, dx, args.reynolds_num, vor_eps, args.advection_scheme, pressure_updater=updater)
     out = Path(args.out)
     step0 = load_state(sim, args.load_state) if args.load_state else 0

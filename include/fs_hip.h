@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 19
+#define FS_ABI_VERSION 20
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -413,12 +413,23 @@ int fs_modes_rows(fs_ctx *ctx, int nfreq, int *accumulate_rows, int *combine_row
  *          of the same equation).  Every launch goes on the context's stream: capturable, no synchronisation, no allocation, no atomics,
  *          and no kernel waits for another workgroup.
  * info:    levels; the first level the one-workgroup kernel holds (0: none); the kernel launches of the last cycle.
- * free:    as fs_mean_free (during a capture the release is deferred to its end).  create returns FS_ERR_STATE during graph capture.       */
+ * free:    as fs_mean_free (during a capture the release is deferred to its end).  create returns FS_ERR_STATE during graph capture.
+ * set_direct (ABI 20): attaches an exact solve to the hierarchy's LAST level: from then on a cycle computes that level's E = M R on its n
+ *          active cells with ONE launch (k_mg_direct, csrc/fs_mg.h: the operation order is written there; none when n == 0) instead of
+ *          coarsest_sweeps sweeps.  cells: the n active cells' indices J * nx + I in the level, strictly ascending; M: the inverse of the
+ *          level's operator on them (fs/multigrid.py direct_solve), [n][row_stride] in the context's dtype, row-major, every row padded with
+ *          zeros to row_stride = 64 * ceil(n / 64) elements.  Both arrays are copied to the device; fs_mg_free releases them.  FS_ERR_ARG
+ *          for a null argument, n < 0 or n > 4096, another stride, cells that are not strictly ascending or lie outside the level;
+ *          FS_ERR_STATE for a hierarchy with a one-workgroup tail (create it with tail_cells = 0), for a second call on the same handle and
+ *          during graph capture / tape recording.  A refused call changes nothing.
+ * direct_info: the level with an exact solve (nlevels; 0: none) and its active cells.                                                        */
 typedef struct fs_mg fs_mg;
 int fs_mg_create(fs_ctx *ctx, int nlevels, const int *dims, const void *cx, const void *cy, const void *diag, long long tail_cells,
                  int coarse_sweeps, int coarsest_sweeps, fs_mg **out);
 int fs_mg_cycle(fs_ctx *ctx, fs_mg *m, double dt, double dx, fs_field *pc, fs_field *pn, const fs_field *vc);
 int fs_mg_info(fs_ctx *ctx, fs_mg *m, int *levels, int *tail_level, int *launches);
+int fs_mg_set_direct(fs_ctx *ctx, fs_mg *m, int n, const int *cells, const void *M, long long row_stride);
+int fs_mg_direct_info(fs_ctx *ctx, fs_mg *m, int *direct_level, int *direct_cells);
 int fs_mg_free(fs_ctx *ctx, fs_mg *m);
 
 /* Tracer particles (new): n passive particles advanced on the device by one launch per step that can be captured in a hipGraph
