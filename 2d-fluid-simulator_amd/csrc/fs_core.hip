@@ -587,6 +587,8 @@ int fs_destroy(fs_ctx *ctx)
     ctx->means.clear();
     for (fs_modes *m : ctx->modes) modes_release(m);
     ctx->modes.clear();
+    for (fs_pod *p : ctx->pods) pod_release(p);
+    ctx->pods.clear();
     for (fs_mg *m : ctx->mgs) mg_release(m);
     ctx->mgs.clear();
     for (fs_loads *l : ctx->loads) loads_release(l);

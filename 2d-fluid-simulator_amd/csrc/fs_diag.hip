@@ -1,10 +1,11 @@
 // fs_diag.hip - C-ABI entry points of what reads the flow without changing it: the flow diagnostics (fs_stats.h), the per-step history ring
-// (fs_history.h), the body surface loads (fs_loads.h), the time averages (fs_mean.h) and the harmonic modes (fs_modes.h), with the release
-// functions of their objects.
+// (fs_history.h), the body surface loads (fs_loads.h), the time averages (fs_mean.h), the harmonic modes (fs_modes.h) and the snapshot POD
+// (fs_pod.h), with the release functions of their objects.
 #include "fs_launch.h"
 #include "fs_stats.h"
 #include "fs_mean.h"
 #include "fs_modes.h"
+#include "fs_pod.h"
 #include "fs_loads.h"
 
 static_assert(fs::STATS_N == FS_FLOW_NSTAT, "fs_stats.h and include/fs_hip.h disagree on the slots");
@@ -12,6 +13,8 @@ static_assert(fs::LOADS_REC == FS_LOADS_NREC && fs::LOADS_SUMS == FS_LOADS_NSUM,
 static_assert(fs::MEAN_PLANES == FS_MEAN_NPLANE, "fs_mean.h and include/fs_hip.h disagree on the planes");
 static_assert(fs::MODES_MAX_FREQ == FS_MODES_MAX_FREQ && fs::modes_scalars(FS_MODES_MAX_FREQ) == FS_MODES_NSCALAR(FS_MODES_MAX_FREQ),
               "fs_modes.h and include/fs_hip.h disagree on the frequencies / the scalars");
+
+static_assert(fs::POD_MAX == FS_POD_MAX, "fs_pod.h and include/fs_hip.h disagree on the slots");
 
 namespace fs {
 void history_release(fs_history *h)
@@ -44,6 +47,13 @@ void modes_release(fs_modes *m)
     if (m->d_state) hipFree(m->d_state);
     if (m->d_scal) hipFree(m->d_scal);
     delete m;
+}
+void pod_release(fs_pod *p)
+{
+    if (p->d_slots) hipFree(p->d_slots);
+    if (p->d_state) hipFree(p->d_state);
+    if (p->d_gram) hipFree(p->d_gram);
+    delete p;
 }
 }  // namespace fs
 
@@ -676,6 +686,206 @@ int fs_modes_free(fs_ctx *ctx, fs_modes *m)
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
     modes_release(m);
+    return FS_OK;
+}
+
+// ---- snapshot POD (fs_pod.h) ---------------------------------------------------------------------------------------------------------------
+#define FS_POD_HANDLE(p) FS_REQUIRE((p)->ctx == ctx && ctx->pods.count(p), "pod from another context or freed")
+#define FS_POD_NO_CAPTURE(what) \
+    if (ctx->capturing || ctx->tape_rec) { set_error("pod " what " during graph capture / tape recording"); return FS_ERR_STATE; }
+
+static size_t pod_slot_bytes(const fs_ctx *ctx, const fs_pod *p) { return 3 * p->plane * ctx->esize; }
+
+int fs_pod_create(fs_ctx *ctx, int M, long long every, long long start, fs_pod **out)
+{
+    FS_REQUIRE(ctx && out, "null argument");
+    FS_REQUIRE(M >= 2 && M <= POD_MAX, "M must be 2 .. FS_POD_MAX");
+    FS_REQUIRE(every >= 1 && start >= 0, "every must be >= 1 and start >= 0");
+    FS_POD_NO_CAPTURE("create")
+    if (ctx->halo != 0 || ctx->nyl != ctx->Y) {
+        set_error("snapshot POD needs a single-GPU context: on a slab the Gram matrix needs a rank-ordered reduction (not implemented)");
+        return FS_ERR_UNSUPPORTED;
+    }
+    FS_HIP(hipSetDevice(ctx->device));
+    fs_pod *p = new fs_pod();
+    p->ctx = ctx; p->M = M; p->every = every; p->start = start;
+    p->plane = (size_t)ctx->nyl * ctx->P + MEAN_PAD;
+    const size_t bytes = (size_t)M * pod_slot_bytes(ctx, p);
+    hipError_t e = hipMalloc(&p->d_state, POD_STATE * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc(&p->d_slots, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(p->d_state, 0, POD_STATE * sizeof(long long), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(p->d_slots, 0, bytes, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { pod_release(p); return hip_fail(e, "fs_pod_create", __FILE__, __LINE__); }
+    ctx->pods.insert(p);
+    *out = p;
+    return FS_OK;
+}
+
+int fs_pod_launch(fs_ctx *ctx, fs_pod *pod, double limit, const fs_field *v, const fs_field *p)
+{
+    FS_REQUIRE(ctx && pod, "null argument");
+    FS_POD_HANDLE(pod);
+    FS_FIELD(v, 2); FS_FIELD(p, 1);
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    // everything the launches need is in `pod` and the fields: no allocation, copy or synchronisation here (the closure is captured / taped)
+    const int jb = ctx->halo, je = ctx->halo + ctx->nyl, w = mean_width(ctx), M = pod->M;
+    int rpw;
+    const dim3 grid = mean_grid(ctx, w, MEAN_G, &rpw);
+    const long long every = pod->every, start = pod->start;
+    long long *state = pod->d_state;
+    void *slots = pod->d_slots;
+    const size_t plane = pod->plane;
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
+        return launch(ctx, "pod_capture", [=] {
+            const bool found = pick<1, 2>(w, [&](auto W) {
+                klaunch(k_pod_capture<T, W>, grid, dim3(256), ctx->stream, ctx->grid(), jb, je, rpw, limit, start, every, M, (const long long *)state,
+                        (const T *)v->d, (const T *)p->d, (T *)slots, plane);
+            });
+            klaunch(k_pod_tick, dim3(1), dim3(64), ctx->stream, start, every, state);
+            return found;
+        });
+    });
+}
+
+static int pod_counters(fs_ctx *ctx, fs_pod *pod, long long *st)
+{
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemcpyAsync(st, pod->d_state, POD_STATE * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_pod_read(fs_ctx *ctx, fs_pod *pod, long long *launches, long long *samples)
+{
+    FS_REQUIRE(ctx && pod, "null argument");
+    FS_POD_HANDLE(pod);
+    FS_POD_NO_CAPTURE("read")
+    long long st[POD_STATE];
+    if (int rc = pod_counters(ctx, pod, st)) return rc;
+    if (launches) *launches = st[0];
+    if (samples) *samples = st[1];
+    return FS_OK;
+}
+
+int fs_pod_gram(fs_ctx *ctx, fs_pod *pod, double *out, int max_n, int *n_out, long long *launches, long long *samples)
+{
+    FS_REQUIRE(ctx && pod && n_out, "null argument");
+    FS_POD_HANDLE(pod);
+    FS_POD_NO_CAPTURE("gram")
+    long long st[POD_STATE];
+    if (int rc = pod_counters(ctx, pod, st)) return rc;
+    const int n = (int)std::min<long long>(st[1], pod->M);
+    if (out) FS_REQUIRE(max_n >= n, "out holds fewer rows than there are resident samples");
+    *n_out = n;
+    if (launches) *launches = st[0];
+    if (samples) *samples = st[1];
+    if (!out || n == 0) return FS_OK;
+    // the geometry of csrc/fs_pod.h: nt tiles of POD_T slots, the diagonal tiles and the pairs ta < tb over blockIdx.z, 256 columns and rpw rows
+    const int nt = (n + POD_T - 1) / POD_T, noff = nt * (nt - 1) / 2;
+    const int nx = (ctx->X + 255) / 256, ny = ctx->nyl;
+    const int rpw = diag_rows(ctx, nx, ny, POD_GRAM_G, POD_GRAM_ROWS);
+    const int nby = (ny + rpw - 1) / rpw;
+    const size_t nblocks = (size_t)nx * nby;
+    const size_t need = (size_t)(nt + noff) * POD_TT * nblocks + (size_t)n * n;
+    if (need > pod->gram_cap) {
+        if (pod->d_gram) { FS_HIP(hipFree(pod->d_gram)); pod->d_gram = nullptr; pod->gram_cap = 0; }      // (the stream is idle: pod_counters)
+        FS_HIP(hipMalloc(&pod->d_gram, need * sizeof(double)));
+        pod->gram_cap = need;
+    }
+    double *partial = pod->d_gram, *total = pod->d_gram + (size_t)(nt + noff) * POD_TT * nblocks;
+    const int X = ctx->X, P = ctx->P, jb = ctx->halo, je = ctx->halo + ctx->nyl;
+    const void *slots = pod->d_slots;
+    const size_t plane = pod->plane;
+    const int rc = by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
+        return launch(ctx, "pod_gram", [=] {
+            klaunch(k_pod_gram<T, true>, dim3(nx, nby, nt), dim3(256), ctx->stream, X, P, jb, je, rpw, n, nt, 0, (const T *)slots, plane, partial);
+            if (noff)
+                klaunch(k_pod_gram<T, false>, dim3(nx, nby, noff), dim3(256), ctx->stream, X, P, jb, je, rpw, n, nt, nt, (const T *)slots, plane, partial);
+            klaunch(k_pod_gram_final, dim3((nt + noff) * POD_TT), dim3(256), ctx->stream, (const double *)partial, (int)nblocks, n, nt, total);
+        });
+    });
+    if (rc) return rc;
+    FS_HIP(hipMemcpyAsync(out, total, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_pod_combine(fs_ctx *ctx, fs_pod *pod, const double *weights, fs_field *v_out, fs_field *p_out)
+{
+    FS_REQUIRE(ctx && pod && weights, "null argument");
+    FS_POD_HANDLE(pod);
+    FS_FIELD(v_out, 2); FS_FIELD(p_out, 1);
+    FS_POD_NO_CAPTURE("combine")
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    const int jb = ctx->halo, je = ctx->halo + ctx->nyl, w = mean_width(ctx), M = pod->M;
+    int rpw;
+    const dim3 grid = mean_grid(ctx, w, 1, &rpw);
+    PodWeights wgt;
+    for (int k = 0; k < POD_MAX; ++k) wgt.w[k] = k < M ? weights[k] : 0.0;
+    const void *slots = pod->d_slots;
+    const size_t plane = pod->plane;
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
+        return launch(ctx, "pod_combine", [=] {
+            return pick<1, 2>(w, [&](auto W) {
+                klaunch(k_pod_combine<T, W>, grid, dim3(256), ctx->stream, ctx->grid(), jb, je, rpw, M, wgt, (const T *)slots, plane, (T *)v_out->d, (T *)p_out->d, v_out->hot);
+            });
+        });
+    });
+}
+
+// per plane: nyl device rows of pitch P <-> dense rows of X, in the field type
+int fs_pod_get(fs_ctx *ctx, fs_pod *pod, void *slots_out)
+{
+    FS_REQUIRE(ctx && pod && slots_out, "null argument");
+    FS_POD_HANDLE(pod);
+    FS_POD_NO_CAPTURE("get")
+    FS_HIP(hipSetDevice(ctx->device));
+    const size_t es = ctx->esize, dense = (size_t)ctx->nyl * ctx->X * es;
+    for (int k = 0; k < 3 * pod->M; ++k)
+        FS_HIP(hipMemcpy2DAsync((char *)slots_out + k * dense, (size_t)ctx->X * es, (const char *)pod->d_slots + k * pod->plane * es, (size_t)ctx->P * es,
+                                (size_t)ctx->X * es, (size_t)ctx->nyl, hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_pod_set(fs_ctx *ctx, fs_pod *pod, const void *slots_in, long long launches, long long samples)
+{
+    FS_REQUIRE(ctx && pod && slots_in, "null argument");
+    FS_POD_HANDLE(pod);
+    FS_REQUIRE(launches >= 0 && samples >= 0 && samples <= launches, "counters must satisfy 0 <= samples <= launches");
+    FS_POD_NO_CAPTURE("set")
+    FS_HIP(hipSetDevice(ctx->device));
+    const long long st[POD_STATE] = {launches, samples};
+    const size_t es = ctx->esize, dense = (size_t)ctx->nyl * ctx->X * es;
+    for (int k = 0; k < 3 * pod->M; ++k)
+        FS_HIP(hipMemcpy2DAsync((char *)pod->d_slots + k * pod->plane * es, (size_t)ctx->P * es, (const char *)slots_in + k * dense, (size_t)ctx->X * es,
+                                (size_t)ctx->X * es, (size_t)ctx->nyl, hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipMemcpyAsync(pod->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
+    return FS_OK;
+}
+
+int fs_pod_reset(fs_ctx *ctx, fs_pod *pod)
+{
+    FS_REQUIRE(ctx && pod, "null argument");
+    FS_POD_HANDLE(pod);
+    FS_POD_NO_CAPTURE("reset")
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemsetAsync(pod->d_slots, 0, (size_t)pod->M * pod_slot_bytes(ctx, pod), ctx->stream));
+    FS_HIP(hipMemsetAsync(pod->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
+    return FS_OK;
+}
+
+int fs_pod_free(fs_ctx *ctx, fs_pod *pod)
+{
+    if (!pod) return FS_OK;
+    FS_REQUIRE(ctx && pod->ctx == ctx && ctx->pods.count(pod), "pod from another context or freed");
+    ctx->pods.erase(pod);
+    if (ctx->capturing) { ctx->deferred_release.push_back([pod] { pod_release(pod); }); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
+    pod_release(pod);
     return FS_OK;
 }
 

@@ -132,6 +132,7 @@ struct fs_ctx {
     std::set<fs_history *> histories;        // live history rings (fs_history_create), released with the context
     std::set<fs_mean *> means;               // live time averages (fs_mean_create), released with the context
     std::set<fs_modes *> modes;              // live harmonic-mode accumulators (fs_modes_create), released with the context
+    std::set<fs_pod *> pods;                 // live snapshot sets (fs_pod_create), released with the context
     std::set<fs_mg *> mgs;                   // live multigrid hierarchies (fs_mg_create), released with the context
     std::set<fs_loads *> loads;              // live body trackers (fs_loads_create), released with the context
     std::set<fs_tracer *> tracers;           // live tracer sets (fs_tracer_create), released with the context
@@ -215,6 +216,18 @@ struct fs_modes {
     double *d_scal = nullptr;       // [2 nfreq] phasors, then the upper triangle of the Gram matrix
 };
 
+// snapshot POD (fs_pod_*, fs_pod.h): the ring of resident snapshots over this context's owned rows, the device counters, the Gram scratch
+struct fs_pod {
+    fs_ctx *ctx = nullptr;
+    int M = 2;
+    long long every = 1, start = 0;
+    size_t plane = 0;               // elements of the field type from one plane to the next: nyl * P + MEAN_PAD
+    void *d_slots = nullptr;        // [M][3][plane] of the field type: u, w, p
+    long long *d_state = nullptr;   // [POD_STATE]
+    double *d_gram = nullptr;       // fs_pod_gram: the workgroups' partial sums, then the n x n matrix (allocated at the first call)
+    size_t gram_cap = 0;            // doubles
+};
+
 namespace fs { struct LoadFace; }      // fs_loads.h (included by fs_diag.hip alone)
 // body surface loads (fs_loads_*, fs_loads.h): the face list of this context's owned rows, the per-face sums, the ring and the device counters
 struct fs_loads {
@@ -261,6 +274,7 @@ void history_release(fs_history *h);      // fs_diag.hip
 void mean_release(fs_mean *m);            // fs_diag.hip
 void loads_release(fs_loads *l);          // fs_diag.hip
 void modes_release(fs_modes *m);          // fs_diag.hip
+void pod_release(fs_pod *p);              // fs_diag.hip
 void mg_release(fs_mg *m);                // fs_multigrid.hip
 
 // HIP-event pair around a span of stream work that is not one kernel launch (fs_core.hip; the ghost-row exchange chain of fs_comm.hip)

@@ -16,6 +16,7 @@ from .boundary_condition import get_boundary_condition
 from .history import Recorder, body_faces, check_probes
 from .loads import Tracker, body_centroid, face_geometry
 from .modes import Modes, fit as fit_modes, gram_matrix, phasor_steps, reconstruct_weights
+from .pod import Pod
 from .pressure_updater import JacobiPressureUpdater, MultigridPressureUpdater, RedBlackSorPressureUpdater
 from .solver import CipMacSolver, DyeCipMacSolver, DyeMacSolver, MacSolver
 from .tracers import TracerAccumulation, Tracers, check_seeds, response
@@ -92,14 +93,15 @@ class FluidSimulator:
         self._last_recorder = None  # ... and after stop_history(): what history() still returns
         self._averager = None      # fs.averages.Averager while start_averaging() is on
         self._moder = None         # fs.modes.Modes while start_modes() is on
+        self._podr = None          # fs.pod.Pod while start_pod() is on
         self._tracers = None       # fs.tracers.Tracers while seed_tracers() is on
         self._tracker = None       # fs.loads.Tracker while track_body() is on
         self._last_tracker = None  # ... and after stop_body(): what body_loads() / body_surface() still return
 
     def _riders(self):
-        """The attached riders (fs.riders.Rider) in their fixed order - history, averages, modes, loads, tracers: the order of their launches
-        behind the solver step and of their tokens in _signature()."""
-        return [r for r in (self._recorder, self._averager, self._moder, self._tracker, self._tracers) if r is not None]
+        """The attached riders (fs.riders.Rider) in their fixed order - history, averages, modes, pod, loads, tracers: the order of their
+        launches behind the solver step and of their tokens in _signature()."""
+        return [r for r in (self._recorder, self._averager, self._moder, self._podr, self._tracker, self._tracers) if r is not None]
 
     def _capturing(self):
         return getattr(self._dev, "capturing", False)
@@ -698,6 +700,93 @@ class FluidSimulator:
         """Detach the modes and free their device memory; the cached graphs and tapes that hold their launch are freed first.  Nothing is
         kept on the host: call modes() before.  Inside a graph capture the device memory is released when the capture ends."""
         self._detach(self, "_moder", "stop_modes")
+
+    # -- snapshot POD (new): the last M sampled fields resident on the device, their Gram matrix reduced there ------------------------------
+    def start_pod(self, snapshots, every=1, start_step=0):
+        """From the next step on, keep the last `snapshots` = M (2 .. 64) sampled flow fields resident on the device: after every step k
+        (counted from here) with k > start_step and (k - start_step) % every == 0 the fields u, w, p are copied into slot number
+        (samples % M) of a ring (csrc/fs_pod.h; wall cells 0).  The launch is part of the step: it is captured into the replayed graphs,
+        decides on the device whether it samples, and run() is not cut into chunks by it.  Costs 12 M bytes per cell of device memory in f32,
+        24 M in f64 (res 4096: 403 MB per snapshot).  Changes no field and no trajectory.  pod() returns the proper orthogonal decomposition
+        of the resident snapshots - energies, temporal coefficients, mode weights - from their M x M Gram matrix, which is reduced on the
+        device; pod_fields() the modes as fields.  Raises while a POD is attached already and during a graph capture; single-GPU contexts
+        only (FsError on slabs: the Gram matrix would need a rank-ordered reduction)."""
+        dev = self._dev
+        self._not_capturing("start_pod")
+        self._make_way("_podr", "a POD is attached already: stop_pod() first (or reset_pod())")
+        every, start_step = self._cadence(every, start_step)
+        self._podr = Pod(dev, dev.pod_create(snapshots, every, start_step), every, start_step)
+
+    def _pod(self):
+        if self._podr is None:
+            raise RuntimeError("no POD: call start_pod() first")
+        return self._podr
+
+    def pod(self, n_modes=None, subtract_mean=True):
+        """The proper orthogonal decomposition of the n resident snapshots (fs.pod.decompose; the download is the n x n Gram matrix alone):
+        {"gram": (n, n) raw, chronological; "energies": eigenvalues descending, (r,) with r the numerical rank; "fraction": energies / their
+        sum; "coefficients": (n, k), a_j(m) = sqrt(lambda_j) V[m, j], chronological, k = min(n_modes, r) (n_modes=None: r); "weights":
+        (k, n) in SLOT order - mode j is sum_m weights[j, m] * slot m (what pod_fields(j) evaluates); "sample_steps": the step of every
+        resident sample, chronological; "samples", "steps": samples and steps since start_pod / reset_pod}.  subtract_mean: decompose the
+        fluctuations about the mean of the resident snapshots (the usual POD of a wake) instead of the raw snapshots.  Raises while fewer
+        than 2 samples are resident; not allowed during a graph capture."""
+        a = self._pod().analyse(subtract_mean)
+        k = len(a["energies"]) if n_modes is None else max(0, min(int(n_modes), len(a["energies"])))
+        w = np.zeros((k, len(a["slots"])))
+        w[:, a["slots"]] = a["weights"][:k]
+        return {"gram": a["gram"].copy(), "energies": a["energies"].copy(), "fraction": a["fraction"].copy(),
+                "coefficients": a["coefficients"][:, :k].copy(), "weights": w, "sample_steps": a["sample_steps"].copy(),
+                "samples": a["samples"], "steps": a["steps"]}
+
+    def _pod_combine(self, chronological):
+        from ._lib import FsError
+        from .runtime import Field
+        po = self._pod()
+        dev = self._dev
+        if self._capturing():
+            raise FsError("pod_fields / pod_snapshot during a graph capture: they allocate and download")
+        w = po.slot_weights(chronological)
+        v, p = Field(dev, 2), Field(dev, 1)      # (not dev.alloc: scratch fields stay out of the ghost-row bookkeeping state of the tapes)
+        dev.pod_combine(po.pod, w, v, p)
+        return v, p
+
+    def pod_fields(self, k=None, subtract_mean=True):
+        """POD mode k (0: the most energetic) as device fields (v: 2 channels, p: 1 channel; wall cells 0): the combination of the resident
+        snapshots with pod()["weights"][k] - p is the extended mode, the same combination of the pressure planes.  k=None: the mean of the
+        resident snapshots.  One device pass over the slots (fs_pod_combine), no download of them.  For everything that takes fields - the
+        visualisation kernels, to_numpy, DeviceBase.flow_stats - as mean_fields().  New fields on every call; the caller owns them."""
+        a = self._pod().analyse(subtract_mean)
+        n = len(a["slots"])
+        if k is None:
+            return self._pod_combine(np.full(n, 1.0 / n))
+        k = int(k)
+        if not 0 <= k < len(a["energies"]):
+            raise ValueError(f"mode must be an index in 0 .. {len(a['energies']) - 1} (the numerical rank of the {n} snapshots)")
+        return self._pod_combine(a["weights"][k])
+
+    def pod_snapshot(self, m):
+        """Resident sample m (0: the oldest; negative: from the newest) as device fields (v, p): a unit weight through fs_pod_combine."""
+        po = self._pod()
+        if self._capturing():
+            from ._lib import FsError
+            raise FsError("pod_fields / pod_snapshot during a graph capture: they allocate and download")
+        _, samples = self._dev.pod_read(po.pod)
+        n = min(samples, po.pod.slots)
+        m = int(m)
+        if not -n <= m < n:
+            raise IndexError(f"sample {m}: {n} samples are resident")
+        w = np.zeros(n)
+        w[m] = 1.0
+        return self._pod_combine(w)
+
+    def reset_pod(self):
+        """Slots and sample count back to zero; the step count and the phase of `every` / `start_step` run on."""
+        self._pod().reset()
+
+    def stop_pod(self):
+        """Detach the POD and free its device memory; the cached graphs that hold its launch are freed first.  Nothing is kept on the host:
+        call pod() before.  Inside a graph capture the device memory is released when the capture ends."""
+        self._detach(self, "_podr", "stop_pod")
 
     # -- tracer particles (new): pathlines and streaklines advanced on the device ------------------------------------------------------
     def seed_tracers(self, seeds, respawn=True, max_age=0, sort_every=0, tau=None, gravity=(0.0, 0.0), deposits=False):

@@ -1,6 +1,6 @@
 """Device side of what rides the step and of the diagnostics (new; the reference has none): flow statistics, the per-step history, the
-body surface loads, the time averages, the harmonic modes and the tracer particles.  Two mixins: RideOps is the backend-agnostic host logic fs.runtime.DeviceBase
-inherits (slab partition, combination over ranks, argument checks, the op log of a logged period), NativeRideOps the `_p_*` primitives
+body surface loads, the time averages, the harmonic modes, the snapshot POD and the tracer particles.  Two mixins: RideOps is the
+backend-agnostic host logic fs.runtime.DeviceBase inherits (slab partition, combination over ranks, argument checks, the op log of a logged period), NativeRideOps the `_p_*` primitives
 fs.runtime.Device binds to libfs_hip.so; the stand-in devices of the CPU tests override those.  fs.runtime re-exports every name here."""
 import ctypes
 import itertools
@@ -53,6 +53,14 @@ class Modes(_Handle):
         self.nfreq, self.every, self.start = nfreq, every, start
 
 
+class Pod(_Handle):
+    """Device snapshots of the POD (DeviceBase.pod_create): handle, number of slots, every, start."""
+
+    def __init__(self, h, slots, every, start):
+        super().__init__(h)
+        self.slots, self.every, self.start = slots, every, start
+
+
 class Loads(_Handle):
     """A device body tracker (DeviceBase.loads_create): handle (None on a slab that owns no face), the global face count, which faces
     this rank owns, capacity, every, start."""
@@ -71,7 +79,7 @@ class History(_Handle):
 
 
 class RideOps:
-    """flow_stats and the history_* / loads_* / mean_* / modes_* / tracer_* calls of DeviceBase."""
+    """flow_stats and the history_* / loads_* / mean_* / modes_* / pod_* / tracer_* calls of DeviceBase."""
 
     # (The tracer calls reach these through the class - RideOps._host_only(self, ...) - as they always reached _tracer_host_call: the CPU
     #  tests check their refusals on objects that are no devices.)
@@ -454,6 +462,83 @@ class RideOps:
     def modes_free(self, modes):
         self._release(modes, self._p_modes_free)
 
+    # ---- snapshot POD (include/fs_hip.h fs_pod_*): a ring of M resident snapshots of u, w, p, one launch per step; Gram matrix on the device ----
+    POD_MAX = 64
+
+    def pod_create(self, slots, every=1, start=0):
+        """Device snapshots for FluidSimulator.start_pod: a ring of `slots` = M snapshots (2 <= M <= POD_MAX) of u, w, p in the fields'
+        precision - 12 M bytes per cell in f32, 24 M in f64 - zeroed.  Launch n (from 0) of pod_launch samples when n + 1 > start and
+        (n + 1 - start) % every == 0.  Single-context grids only (FsError on a slab: the Gram matrix would need a rank-ordered reduction of
+        per-rank matrices); not allowed during a graph capture."""
+        RideOps._host_only(self, "pod_create during a graph capture")      # (through the class, as the tracer calls: the tests ask objects that are no devices)
+        if self.nranks > 1:
+            raise _lib.FsError("snapshot POD needs a single-GPU context: on slabs the Gram matrix needs a rank-ordered reduction (not implemented)")
+        slots = int(slots)
+        if not 2 <= slots <= self.POD_MAX:
+            raise ValueError(f"snapshots must be 2 .. {self.POD_MAX}, got {slots}")
+        every, start = self._check_cadence(every, start)
+        h = self._p_pod_create(slots, every, start)
+        return self._adopt(h, Pod(h, slots, every, start))
+
+    def pod_launch(self, pod, v, p):
+        """Store the current v and p into slot samples % M when this launch is a sampling one; the counters advance on the device.  A
+        limit_field v still owes stays deferred: the kernel limits the values as the pass would store them.  Not a _run: no flush, no
+        exchange, no ghost row (writes no field)."""
+        self._ride("pod_launch", (pod._h, self._limit_of(v), v._h, p._h))
+
+    def pod_read(self, pod):
+        """-> (launches, samples).  Not allowed during a graph capture."""
+        self._host_only("pod_read during a graph capture: the counters are a download (read between captures / replays)")
+        launches, samples = self._p_pod_read(pod._h)
+        return int(launches), int(samples)
+
+    def pod_gram(self, pod):
+        """-> (G float64 (n, n) in SLOT order, launches, samples): the Gram matrix of the n = min(samples, M) resident snapshots,
+        G[a][b] = sum over the cells of u_a u_b + w_a w_b in double, reduced on the device in a fixed order (csrc/fs_pod.h): only n * n
+        doubles are downloaded.  Not allowed during a graph capture."""
+        self._host_only("pod_gram during a graph capture: the matrix is a download (read between captures / replays)")
+        G, launches, samples = self._p_pod_gram(pod._h, pod.slots)
+        return G, int(launches), int(samples)
+
+    def pod_combine(self, pod, weights, v_out, p_out):
+        """The slots reduced to fields: sum_m weights[m] * slot_m (in double, m ascending) of u, w into the 2-channel v_out and of p into
+        the 1-channel p_out, wall cells 0, in the fields' precision; weights float64 (M,).  Not allowed during a graph capture."""
+        self._host_only("pod_combine during a graph capture")
+        weights = np.ascontiguousarray(weights, np.float64)
+        if weights.shape != (pod.slots,):
+            raise ValueError(f"expected weights of shape {(pod.slots,)}, got {weights.shape}")
+        for f in (v_out, p_out):
+            f.pending_limit = f.pending_clamp = None      # (every owned cell is overwritten)
+        self._p_pod_combine(pod._h, weights, v_out._h, p_out._h)
+        for f in (v_out, p_out):
+            f.valid = 0 if self.nranks > 1 else self.halo
+            f.user_data = True
+            f.static_id = next(_serials)
+
+    def pod_get(self, pod):
+        """-> (slots (M, 3, X, Y) in the fields' dtype: u, w, p of every slot; launches, samples) - the whole ring, for checkpoints."""
+        self._host_only("pod_get during a graph capture")
+        launches, samples = self.pod_read(pod)
+        return self._p_pod_get(pod._h, pod.slots), launches, samples
+
+    def pod_set(self, pod, slots, launches, samples):
+        """Restore what pod_get returned (resume)."""
+        self._host_only("pod_set during a graph capture")
+        slots = np.asarray(slots)
+        shape = (pod.slots, 3, self.nx, self.ny)
+        if slots.shape != shape:
+            raise ValueError(f"expected slots of shape {shape}, got {slots.shape}")
+        launches, samples = self._check_counters(launches, samples)
+        self._p_pod_set(pod._h, slots.astype(self.dtype, copy=False), launches, samples)
+
+    def pod_reset(self, pod):
+        """Slots and sample count to zero; the launch count runs on.  Not allowed during a graph capture."""
+        self._host_only("pod_reset during a graph capture")
+        self._p_pod_reset(pod._h)
+
+    def pod_free(self, pod):
+        self._release(pod, self._p_pod_free)
+
     # ---- tracer particles (include/fs_hip.h fs_tracer_*): N particles in double cell coordinates, advanced by one launch per step -------
     def tracer_create(self, seeds, respawn=True, max_age=0):
         """A device tracer set for FluidSimulator.seed_tracers: seeds float64 (N, 2) in cell units, N >= 1, inside the domain (whether
@@ -772,6 +857,42 @@ class NativeRideOps:
     def _p_modes_free(self, h):
         if self._ctx is not None:
             _lib.call("fs_modes_free", self._ctx, h)
+
+    def _p_pod_create(self, slots, every, start):
+        h = ctypes.c_void_p()
+        _lib.call("fs_pod_create", self._ctx, slots, every, start, ctypes.byref(h))
+        return h
+
+    def _p_pod_read(self, h):
+        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
+        _lib.call("fs_pod_read", self._ctx, h, ctypes.byref(launches), ctypes.byref(samples))
+        return launches.value, samples.value
+
+    def _p_pod_gram(self, h, slots):
+        out = np.empty((slots, slots), np.float64)
+        n, launches, samples = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_longlong()
+        _lib.call("fs_pod_gram", self._ctx, h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), slots, ctypes.byref(n), ctypes.byref(launches),
+                  ctypes.byref(samples))
+        return out.ravel()[:n.value * n.value].reshape(n.value, n.value).copy(), launches.value, samples.value
+
+    def _p_pod_combine(self, h, weights, vh, ph):
+        _lib.call("fs_pod_combine", self._ctx, h, weights.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), vh, ph)
+
+    def _p_pod_get(self, h, slots):
+        out = np.empty((slots, 3, self.nyl, self.nx), self.dtype)       # (the library's layout: x contiguous)
+        _lib.call("fs_pod_get", self._ctx, h, out.ctypes.data_as(ctypes.c_void_p))
+        return np.ascontiguousarray(out.transpose(0, 1, 3, 2))
+
+    def _p_pod_set(self, h, slots, launches, samples):
+        a = np.ascontiguousarray(slots.transpose(0, 1, 3, 2), self.dtype)
+        _lib.call("fs_pod_set", self._ctx, h, a.ctypes.data_as(ctypes.c_void_p), launches, samples)
+
+    def _p_pod_reset(self, h):
+        _lib.call("fs_pod_reset", self._ctx, h)
+
+    def _p_pod_free(self, h):
+        if self._ctx is not None:
+            _lib.call("fs_pod_free", self._ctx, h)
 
     def _p_tracer_create(self, seeds, respawn, max_age):
         h = ctypes.c_void_p()

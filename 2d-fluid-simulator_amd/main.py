@@ -15,6 +15,10 @@ The reference opens a GGUI window and steps forever; here the loop runs `--steps
   * accumulate the harmonic content of u, w, p at given frequencies on the GPU (`--modes-freq f[,f2,...]`, `--modes-every`, `--modes-start`):
     mean, amplitude and phase per cell written to `--modes-file` (.npz) at the end of the run, the phase-averaged cycle of the first frequency
     as `--modes-frames N` images; the sums travel with `--save-state` / `--load-state`.
+  * proper orthogonal decomposition of the flow by the method of snapshots (`--pod-snapshots M`, `--pod-every`, `--pod-start`, `--pod-modes K`):
+    the last M sampled fields stay on the GPU, their Gram matrix is reduced there; energies, temporal coefficients and the first K modes are
+    written to `--pod-file` (.npz) at the end of the run, with -vis (or --frame-every) the modes as `pod_mode_<k>.png`; the snapshots travel with
+    `--save-state` / `--load-state`.
   * follow tracer particles on the GPU (`--tracers N`, `--tracer-line x0,y0,x1,y1,n`): pathlines (`--tracer-once`) or streaklines, written
     to `--tracer-file` (.npz) at the end of the run and every `--tracer-dump-every` steps, drawn into the `-vis` frames; the particle state
     travels with `--save-state` / `--load-state`.  `--tracer-sort-every K` sorts the particles by cell on the GPU every K steps (large sets
@@ -106,6 +110,16 @@ def build_parser():
                         "dx, every, start (default: <out>/modes.npz)")
     p.add_argument("--modes-frames", type=int, default=0,
                    help="write N -vis images modes_phase_<i>.png of the phase-averaged flow over one period of the first frequency")
+    p.add_argument("--pod-snapshots", type=int, default=0, metavar="M",
+                   help="keep the last M (2 .. 64) sampled flow fields on the GPU and decompose them into POD modes at the end of the run "
+                        "(FluidSimulator.start_pod; 0: off); 12 M bytes per cell in f32")
+    p.add_argument("--pod-every", type=int, default=None, help="take a snapshot after every N-th step (default 1)")
+    p.add_argument("--pod-start", type=int, default=None, help="steps of the run (restarts included) to leave out before the first snapshot (default 0)")
+    p.add_argument("--pod-modes", type=int, default=None, metavar="K", help="modes written to --pod-file as fields (default 4)")
+    p.add_argument("--pod-file", type=str, default=None,
+                   help=".npz of the POD: energies, fraction, coefficients, gram, sample_steps, samples, steps, u, w, p (the first K modes, "
+                        "(K, X, Y) each), mean_u / _w / _p, mask, dt, dx, every, start (default: <out>/pod.npz); "
+                        "with -vis 0 / 1 / 2 given, or --frame-every, also the images pod_mode_<k>.png")
     p.add_argument("--tracers", type=int, default=0,
                    help="follow N tracer particles seeded at random in fluid cells (FluidSimulator.seed_tracers; 0: none unless --tracer-line)")
     p.add_argument("--tracer-seed", type=int, default=None, help="seed of the random generator behind --tracers (default 0)")
@@ -185,6 +199,41 @@ def load_modes(sim, path):
         return False
     sim._moder.restore(z)
     return True
+
+
+def saved_pod(path):
+    """(snapshots, every, start) of the POD a checkpoint holds, or None."""
+    z = np.load(_npz_path(path))
+    if "pod.slots" not in z.files:
+        return None
+    return (int(z["pod.snapshots"]), int(z["pod.every"]), int(z["pod.start"]))
+
+
+def load_pod(sim, path):
+    """Restore the snapshots and counters of the checkpoint's POD into the attached one -> whether the checkpoint held any."""
+    z = np.load(_npz_path(path))
+    if "pod.slots" not in z.files:
+        return False
+    sim._podr.restore(z)
+    return True
+
+
+def pod_file_arrays(sim, n_modes):
+    """The arrays of --pod-file: FluidSimulator.pod() and the first n_modes modes, downloaded from pod_fields()."""
+    pod = sim.pod(n_modes)
+    out = {k: np.asarray(pod[k]) for k in ("energies", "fraction", "coefficients", "gram", "sample_steps", "samples", "steps")}
+    u, w, q = [], [], []
+    for k in range(pod["coefficients"].shape[1]):
+        v, p = sim.pod_fields(k)
+        a = v.to_numpy()
+        u.append(a[..., 0]); w.append(a[..., 1]); q.append(p.to_numpy())
+    shape = (0,) + np.asarray(sim._solver._bc.mask).shape
+    out["u"], out["w"], out["p"] = (np.stack(x) if x else np.zeros(shape) for x in (u, w, q))
+    v, p = sim.pod_fields(None)
+    a = v.to_numpy()
+    out["mean_u"], out["mean_w"], out["mean_p"] = a[..., 0], a[..., 1], p.to_numpy()
+    out["mask"] = np.asarray(sim._solver._bc.mask).copy()
+    return out
 
 
 def saved_loads(path):
@@ -420,6 +469,7 @@ def _probe(parser, spec):
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
+    vis_given = any(a in ("-vis", "--visualization") or a.startswith("--visualization=") for a in (sys.argv[1:] if argv is None else argv))
     if args.cpu:
         print("note: -cpu ignored; this build runs on the GPU only", file=sys.stderr)
     res = args.resolution
@@ -492,6 +542,21 @@ def main(argv=None):
             if held is not None and held != (tuple(modes_freqs), modes_every, modes_start):
                 print(f"--load-state {args.load_state}: its modes were taken with --modes-freq {','.join(repr(f) for f in held[0])} --modes-every "
                       f"{held[1]} --modes-start {held[2]}; continue with those or accumulate without the checkpoint's sums", file=sys.stderr)
+                sys.exit(2)
+    pod_every, pod_start, pod_modes = (1 if args.pod_every is None else args.pod_every), args.pod_start or 0, (4 if args.pod_modes is None else args.pod_modes)
+    if args.pod_snapshots == 0:
+        if args.pod_every is not None or args.pod_start is not None or args.pod_modes is not None or args.pod_file:
+            parser.error("--pod-every, --pod-start, --pod-modes and --pod-file need --pod-snapshots M")
+    else:
+        if not 2 <= args.pod_snapshots <= 64:
+            parser.error("--pod-snapshots must be 2 .. 64")
+        if pod_every < 1 or pod_start < 0 or pod_modes < 0:
+            parser.error("--pod-every must be >= 1, --pod-start and --pod-modes >= 0")
+        if args.load_state:
+            held = saved_pod(args.load_state)
+            if held is not None and held != (args.pod_snapshots, pod_every, pod_start):
+                print(f"--load-state {args.load_state}: its POD snapshots were taken with --pod-snapshots {held[0]} --pod-every {held[1]} --pod-start "
+                      f"{held[2]}; continue with those or sample without the checkpoint's snapshots", file=sys.stderr)
                 sys.exit(2)
     tracing = args.tracers > 0 or bool(args.tracer_line)
     if args.tracers < 0 or args.tracer_dump_every < 0 or (args.tracer_max_age is not None and args.tracer_max_age < 0) or args.tracer_sort_every < 0:
@@ -614,6 +679,28 @@ def main(argv=None):
                 v, p = sim.mode_fields(2.0 * np.pi * i / args.modes_frames, 0)
                 save_png(fields_frame(sim, args.visualization, v, p), out / f"modes_phase_{i}.png")
 
+    pod_file = None
+    if args.pod_snapshots:
+        pod_file = Path(args.pod_file) if args.pod_file else out / "pod.npz"
+        sim.start_pod(args.pod_snapshots, every=pod_every, start_step=pod_start)
+        if args.load_state and load_pod(sim, args.load_state):
+            print(f"POD: continuing the checkpoint's ({sim._dev.pod_read(sim._podr.pod)[1]} samples so far)")
+
+    def write_pod():
+        if pod_file is None:
+            return
+        try:
+            arrays = pod_file_arrays(sim, pod_modes)
+        except (RuntimeError, ValueError) as e:
+            print(f"POD: {e}; no file written", file=sys.stderr)
+            return
+        pod_file.parent.mkdir(parents=True, exist_ok=True)
+        np.savez(str(pod_file), dt=np.array(dt), dx=np.array(dx), every=np.array(pod_every), start=np.array(pod_start), **arrays)
+        if (vis_given or args.frame_every) and args.visualization != 3:      # (-vis 3 is the dye: it has no modes)
+            out.mkdir(exist_ok=True)
+            for k in range(arrays["coefficients"].shape[1]):
+                save_png(fields_frame(sim, args.visualization, *sim.pod_fields(k)), out / f"pod_mode_{k}.png")
+
     loads_file = None
     if args.loads_every > 0:
         loads_file = Path(args.loads_file) if args.loads_file else out / "loads.npz"
@@ -700,6 +787,7 @@ def main(argv=None):
             write_history()
             write_mean()
             write_modes()
+            write_pod()
             write_loads()
             if tracer_file is not None:
                 write_tracers(tracer_file, fields_file, step)
@@ -743,6 +831,7 @@ def main(argv=None):
     write_history()
     write_mean()
     write_modes()
+    write_pod()
     write_loads()
     if tracer_file is not None:
         write_tracers(tracer_file, fields_file, step0 + args.steps)

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 20
+#define FS_ABI_VERSION 21
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -400,6 +400,39 @@ int fs_modes_write(fs_ctx *ctx, fs_modes *m, const double *sums_in, const double
 int fs_modes_reset(fs_ctx *ctx, fs_modes *m);
 int fs_modes_free(fs_ctx *ctx, fs_modes *m);
 int fs_modes_rows(fs_ctx *ctx, int nfreq, int *accumulate_rows, int *combine_rows);
+
+/* Snapshot POD (new, ABI 21): the last M sampled flow fields kept resident on the device by a launch that can be captured in a hipGraph, their
+ * M x M Gram matrix reduced on the device, and linear combinations of them as fields (csrc/fs_pod.h).  State: M slots of three planes (u, w, p)
+ * of the context's dtype over the owned rows - 12 bytes per cell and slot in f32, 24 in f64 - and two device counters (launches, samples).
+ * Single-GPU contexts: create returns FS_ERR_UNSUPPORTED on a slab context (the Gram matrix would need a rank-ordered reduction).
+ * create:  2 <= M <= FS_POD_MAX, every >= 1, start >= 0; slots and counters zero.  An allocation that does not fit returns FS_ERR_HIP and
+ *          leaves nothing behind.
+ * launch:  launch n (from 0) samples by the rule of fs_mean_accumulate, into slot samples % M (a ring: the object holds the last
+ *          min(samples, M) samples): u, w, p as stored on the not-wall cells (limit > 0: u, w limited as a deferred limit_field(limit) would
+ *          store them), +0 on the wall cells.  The counters advance on the device behind the launch.  Reads no ghost row, changes no field.
+ * gram:    synchronises.  n = min(samples, M) goes to *n_out; with out != NULL (max_n >= n) out receives the dense n x n matrix in SLOT order,
+ *          G[a][b] = sum over the cells of (double)u_a * (double)u_b + (double)w_a * (double)w_b, every product and sum rounded on its own, in
+ *          the fixed order csrc/fs_pod.h states (two deterministic stages, no atomics): two calls return the same bits, and G is exactly
+ *          symmetric.  n == 0: nothing is launched.
+ * combine: v_out, p_out = (T) sum_m weights[m] * slot_m, m = 0 .. M - 1 in this order from 0.0, in double, product then sum, for u, w into the
+ *          2-channel v_out and p into the 1-channel p_out; 0 on wall cells; weights: M doubles.  Ghost rows of the targets are not written.
+ * read:    synchronises; the counters.
+ * get:     synchronises; slots_out receives [M][3][Y][X] values of the context's dtype, x contiguous.  set: the inverse (resume),
+ *          0 <= samples <= launches.
+ * reset:   slots and the sample count to zero; the launch count (and with it the phase of `every` / `start`) runs on.
+ * free:    as fs_mean_free (during a capture the release is deferred to its end).
+ * create, gram, combine, read, get, set and reset return FS_ERR_STATE during graph capture / tape recording.                            */
+#define FS_POD_MAX 64
+typedef struct fs_pod fs_pod;
+int fs_pod_create(fs_ctx *ctx, int M, long long every, long long start, fs_pod **out);
+int fs_pod_launch(fs_ctx *ctx, fs_pod *pod, double limit, const fs_field *v, const fs_field *p);
+int fs_pod_gram(fs_ctx *ctx, fs_pod *pod, double *out, int max_n, int *n_out, long long *launches, long long *samples);
+int fs_pod_combine(fs_ctx *ctx, fs_pod *pod, const double *weights, fs_field *v_out, fs_field *p_out);
+int fs_pod_read(fs_ctx *ctx, fs_pod *pod, long long *launches, long long *samples);
+int fs_pod_get(fs_ctx *ctx, fs_pod *pod, void *slots_out);
+int fs_pod_set(fs_ctx *ctx, fs_pod *pod, const void *slots_in, long long launches, long long samples);
+int fs_pod_reset(fs_ctx *ctx, fs_pod *pod);
+int fs_pod_free(fs_ctx *ctx, fs_pod *pod);
 
 /* Multigrid pressure correction (new, ABI 19): one W-cycle (two coarse visits per level) on a mask-aware hierarchy of coarse levels, for the
  * third pressure updater (fs/pressure_updater.py MultigridPressureUpdater; kernels and operation order: csrc/fs_mg.h).  Single-GPU contexts.
