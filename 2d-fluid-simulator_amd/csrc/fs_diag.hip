@@ -1,11 +1,12 @@
 // fs_diag.hip - C-ABI entry points of what reads the flow without changing it: the flow diagnostics (fs_stats.h), the per-step history ring
-// (fs_history.h), the body surface loads (fs_loads.h), the time averages (fs_mean.h), the harmonic modes (fs_modes.h) and the snapshot POD
-// (fs_pod.h), with the release functions of their objects.
+// (fs_history.h), the body surface loads (fs_loads.h), the time averages (fs_mean.h), the harmonic modes (fs_modes.h), the snapshot POD
+// (fs_pod.h) and the flow maps through its snapshots (fs_lcs.h), with the release functions of their objects.
 #include "fs_launch.h"
 #include "fs_stats.h"
 #include "fs_mean.h"
 #include "fs_modes.h"
 #include "fs_pod.h"
+#include "fs_lcs.h"
 #include "fs_loads.h"
 
 static_assert(fs::STATS_N == FS_FLOW_NSTAT, "fs_stats.h and include/fs_hip.h disagree on the slots");
@@ -15,6 +16,7 @@ static_assert(fs::MODES_MAX_FREQ == FS_MODES_MAX_FREQ && fs::modes_scalars(FS_MO
               "fs_modes.h and include/fs_hip.h disagree on the frequencies / the scalars");
 
 static_assert(fs::POD_MAX == FS_POD_MAX, "fs_pod.h and include/fs_hip.h disagree on the slots");
+static_assert(fs::FM_LEFT == FS_TRACER_LEFT && fs::FM_WALL == FS_TRACER_WALL && fs::FM_UNSEEDED == FS_FLOWMAP_UNSEEDED && fs::FM_MAX_SUBSTEPS == FS_FLOWMAP_MAX_SUBSTEPS, "fs_lcs.h and include/fs_hip.h disagree");
 
 namespace fs {
 void history_release(fs_history *h)
@@ -54,6 +56,12 @@ void pod_release(fs_pod *p)
     if (p->d_state) hipFree(p->d_state);
     if (p->d_gram) hipFree(p->d_gram);
     delete p;
+}
+void flowmap_release(fs_flowmap *f)
+{
+    if (f->d_pos) hipFree(f->d_pos);
+    if (f->d_status) hipFree(f->d_status);
+    delete f;
 }
 }  // namespace fs
 
@@ -886,6 +894,121 @@ int fs_pod_free(fs_ctx *ctx, fs_pod *pod)
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
     pod_release(pod);
+    return FS_OK;
+}
+
+// ---- flow maps through the resident snapshots (fs_lcs.h) ----------------------------------------------------------------------------------
+#define FS_FLOWMAP_HANDLE(f) FS_REQUIRE((f)->ctx == ctx && ctx->flowmaps.count(f), "flow map from another context or freed")
+#define FS_FLOWMAP_NO_CAPTURE(what) \
+    if (ctx->capturing || ctx->tape_rec) { set_error("flow map " what " during graph capture / tape recording"); return FS_ERR_STATE; }
+
+static FlowMapDev flowmap_dev(const fs_flowmap *f)
+{
+    const size_t n = (size_t)f->nx * f->ny;
+    return FlowMapDev{f->nx, f->ny, f->box[0], f->box[1], f->r, f->d_pos, f->d_pos + n, f->d_status, f->d_pos + 2 * n};
+}
+static dim3 flowmap_grid(const fs_flowmap *f) { return dim3((unsigned)(((size_t)f->nx * f->ny + FM_WG - 1) / FM_WG)); }
+
+static int flowmap_seed(fs_ctx *ctx, fs_flowmap *fm)
+{
+    const FlowMapDev fd = flowmap_dev(fm);
+    const dim3 grid = flowmap_grid(fm);
+    return launch(ctx, "flowmap_seed", [=] { klaunch(k_flowmap_seed, grid, dim3(FM_WG), ctx->stream, ctx->grid(), fd); });
+}
+
+int fs_flowmap_create(fs_ctx *ctx, const int *box, int refine, fs_flowmap **out)
+{
+    FS_REQUIRE(ctx && box && out, "null argument");
+    FS_REQUIRE(0 <= box[0] && box[0] < box[2] && box[2] <= ctx->X && 0 <= box[1] && box[1] < box[3] && box[3] <= ctx->Y,
+               "flow-map box must satisfy 0 <= x0 < x1 <= X and 0 <= y0 < y1 <= Y");
+    FS_REQUIRE(refine == 1 || refine == 2 || refine == 4 || refine == 8, "refine must be 1, 2, 4 or 8");
+    const long long nx = (long long)refine * (box[2] - box[0]), ny = (long long)refine * (box[3] - box[1]);
+    FS_REQUIRE(nx * ny <= (1LL << 30), "flow map of more than 2^30 nodes");
+    FS_FLOWMAP_NO_CAPTURE("create")
+    if (ctx->comm || ctx->halo != 0 || ctx->y0 != 0 || ctx->nyl != ctx->Y) {
+        set_error("flow maps need a single-GPU context: on a slab the particles would have to migrate between ranks (not implemented)");
+        return FS_ERR_UNSUPPORTED;
+    }
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    FS_HIP(hipSetDevice(ctx->device));
+    fs_flowmap *f = new fs_flowmap();
+    f->ctx = ctx; f->r = refine; f->nx = (int)nx; f->ny = (int)ny;
+    for (int k = 0; k < 4; ++k) f->box[k] = box[k];
+    const size_t n = (size_t)(nx * ny);
+    hipError_t e = hipMalloc(&f->d_pos, 3 * n * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&f->d_status, n * sizeof(int));
+    if (e != hipSuccess) { flowmap_release(f); return hip_fail(e, "fs_flowmap_create", __FILE__, __LINE__); }
+    if (int rc = flowmap_seed(ctx, f)) { hipStreamSynchronize(ctx->stream); flowmap_release(f); return rc; }
+    ctx->flowmaps.insert(f);
+    *out = f;
+    return FS_OK;
+}
+
+int fs_flowmap_advance(fs_ctx *ctx, fs_flowmap *fm, const fs_pod *pod, int slot_from, int slot_to, double h, int substeps)
+{
+    FS_REQUIRE(ctx && fm && pod, "null argument");
+    FS_FLOWMAP_HANDLE(fm);
+    FS_REQUIRE(pod->ctx == ctx && ctx->pods.count(const_cast<fs_pod *>(pod)), "pod from another context or freed");
+    FS_REQUIRE(0 <= slot_from && slot_from < pod->M && 0 <= slot_to && slot_to < pod->M, "slot outside 0 .. M - 1");
+    FS_REQUIRE(slot_from != slot_to, "slot_from and slot_to must differ");
+    FS_REQUIRE(substeps >= 1 && substeps <= FM_MAX_SUBSTEPS, "substeps must be 1 .. FS_FLOWMAP_MAX_SUBSTEPS");
+    FS_REQUIRE(std::isfinite(h) && h != 0.0, "h must be finite and not 0");
+    FS_FLOWMAP_NO_CAPTURE("advance")
+    const FlowMapDev fd = flowmap_dev(fm);
+    const dim3 grid = flowmap_grid(fm);
+    const int Y = ctx->Y;
+    const size_t plane = pod->plane;
+    const void *slots = pod->d_slots;
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
+        const T *from = (const T *)slots + (size_t)slot_from * 3 * plane, *to = (const T *)slots + (size_t)slot_to * 3 * plane;
+        return launch(ctx, "flowmap_advance", [=] {
+            klaunch(k_flowmap_advance<T>, grid, dim3(FM_WG), ctx->stream, ctx->grid(), Y, h, substeps, fd, from, to, plane);
+        });
+    });
+}
+
+int fs_flowmap_cauchy_green(fs_ctx *ctx, fs_flowmap *fm)
+{
+    FS_REQUIRE(ctx && fm, "null argument");
+    FS_FLOWMAP_HANDLE(fm);
+    FS_FLOWMAP_NO_CAPTURE("cauchy_green")
+    const FlowMapDev fd = flowmap_dev(fm);
+    const dim3 grid = flowmap_grid(fm);
+    return launch(ctx, "flowmap_cauchy_green", [=] { klaunch(k_flowmap_cauchy_green, grid, dim3(FM_WG), ctx->stream, fd); });
+}
+
+int fs_flowmap_get(fs_ctx *ctx, fs_flowmap *fm, double *x, double *y, int *status, double *lam)
+{
+    FS_REQUIRE(ctx && fm, "null argument");
+    FS_FLOWMAP_HANDLE(fm);
+    FS_FLOWMAP_NO_CAPTURE("get")
+    FS_HIP(hipSetDevice(ctx->device));
+    const size_t n = (size_t)fm->nx * fm->ny;
+    double *const dst[3] = {x, y, lam};
+    for (int k = 0; k < 3; ++k)
+        if (dst[k]) FS_HIP(hipMemcpyAsync(dst[k], fm->d_pos + k * n, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (status) FS_HIP(hipMemcpyAsync(status, fm->d_status, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_flowmap_reset(fs_ctx *ctx, fs_flowmap *fm)
+{
+    FS_REQUIRE(ctx && fm, "null argument");
+    FS_FLOWMAP_HANDLE(fm);
+    FS_FLOWMAP_NO_CAPTURE("reset")
+    return flowmap_seed(ctx, fm);
+}
+
+int fs_flowmap_free(fs_ctx *ctx, fs_flowmap *fm)
+{
+    if (!fm) return FS_OK;
+    FS_REQUIRE(ctx && fm->ctx == ctx && ctx->flowmaps.count(fm), "flow map from another context or freed");
+    FS_FLOWMAP_NO_CAPTURE("free")
+    ctx->flowmaps.erase(fm);
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
+    flowmap_release(fm);
     return FS_OK;
 }
 

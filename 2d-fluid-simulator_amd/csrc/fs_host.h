@@ -133,6 +133,7 @@ struct fs_ctx {
     std::set<fs_mean *> means;               // live time averages (fs_mean_create), released with the context
     std::set<fs_modes *> modes;              // live harmonic-mode accumulators (fs_modes_create), released with the context
     std::set<fs_pod *> pods;                 // live snapshot sets (fs_pod_create), released with the context
+    std::set<fs_flowmap *> flowmaps;         // live flow-map lattices (fs_flowmap_create), released with the context
     std::set<fs_mg *> mgs;                   // live multigrid hierarchies (fs_mg_create), released with the context
     std::set<fs_loads *> loads;              // live body trackers (fs_loads_create), released with the context
     std::set<fs_tracer *> tracers;           // live tracer sets (fs_tracer_create), released with the context
@@ -228,6 +229,15 @@ struct fs_pod {
     size_t gram_cap = 0;            // doubles
 };
 
+// flow map through the resident snapshots (fs_flowmap_*, fs_lcs.h): the lattice of nodes over a cell box
+struct fs_flowmap {
+    fs_ctx *ctx = nullptr;
+    int box[4] = {0, 0, 0, 0};      // x0, y0, x1, y1 (cells)
+    int r = 1, nx = 0, ny = 0;      // nodes per cell and direction; the lattice
+    double *d_pos = nullptr;        // [3][ny][nx]: x, y, lam
+    int *d_status = nullptr;        // [ny][nx]
+};
+
 namespace fs { struct LoadFace; }      // fs_loads.h (included by fs_diag.hip alone)
 // body surface loads (fs_loads_*, fs_loads.h): the face list of this context's owned rows, the per-face sums, the ring and the device counters
 struct fs_loads {
@@ -275,6 +285,7 @@ void mean_release(fs_mean *m);            // fs_diag.hip
 void loads_release(fs_loads *l);          // fs_diag.hip
 void modes_release(fs_modes *m);          // fs_diag.hip
 void pod_release(fs_pod *p);              // fs_diag.hip
+void flowmap_release(fs_flowmap *f);      // fs_diag.hip
 void mg_release(fs_mg *m);                // fs_multigrid.hip
 
 // HIP-event pair around a span of stream work that is not one kernel launch (fs_core.hip; the ghost-row exchange chain of fs_comm.hip)

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FS_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libfs_hip.so")     # FS_LIB: A/B builds (tools/)
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _lib = None
 
@@ -114,6 +114,12 @@ _PROTOS = {
     "fs_pod_set": [_c_vp, _c_vp, _c_vp, ctypes.c_longlong, ctypes.c_longlong],
     "fs_pod_reset": [_c_vp, _c_vp],
     "fs_pod_free": [_c_vp, _c_vp],
+    "fs_flowmap_create": [_c_vp, _P(_c_int), _c_int, _P(_c_vp)],
+    "fs_flowmap_advance": [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_int],
+    "fs_flowmap_cauchy_green": [_c_vp, _c_vp],
+    "fs_flowmap_get": [_c_vp, _c_vp, _P(_c_dbl), _P(_c_dbl), _P(_c_int), _P(_c_dbl)],
+    "fs_flowmap_reset": [_c_vp, _c_vp],
+    "fs_flowmap_free": [_c_vp, _c_vp],
     "fs_mg_create": [_c_vp, _c_int, _P(_c_int), _c_vp, _c_vp, _c_vp, ctypes.c_longlong, _c_int, _c_int, _P(_c_vp)],
     "fs_mg_cycle": [_c_vp, _c_vp, _c_dbl, _c_dbl, _c_vp, _c_vp, _c_vp],
     "fs_mg_info": [_c_vp, _c_vp, _P(_c_int), _P(_c_int), _P(_c_int)],

@@ -788,6 +788,63 @@ class FluidSimulator:
         call pod() before.  Inside a graph capture the device memory is released when the capture ends."""
         self._detach(self, "_podr", "stop_pod")
 
+    # -- flow maps and FTLE fields (new): a lattice of particles carried through the POD's resident snapshots on the device --------------
+    def flow_map(self, direction="backward", refine=1, box=None, substeps=1, first=None, last=None):
+        """The flow map over the resident snapshots of the attached POD (start_pod), integrated on the device (csrc/fs_lcs.h): refine x
+        refine particles per cell of the cell box (x0, y0, x1, y1) (None: the whole domain; refine in 1, 2, 4, 8) are carried from resident
+        sample `first` to `last` ("forward") or from `last` back to `first` ("backward") - indices into the resident samples, 0 the oldest,
+        negative from the newest, None the oldest / newest - with `substeps` (1 .. 16) midpoint steps per interval in the velocity
+        interpolated bilinearly in space and linearly in time between consecutive snapshots.  One launch per interval, one pass for the
+        Cauchy-Green tensor, one download of the lattice; no field is downloaded.  -> {"x", "y": float64 (nx, ny), the final positions in
+        cell units; "x0", "y0": the start positions; "status": int32, 0 arrived, 1 left the domain (forward: through an outflow cell too;
+        backward: into an inflow cell too), 2 ran into a wall cell, 4 started in one (never moved) - a node with status 1 or 2 kept its
+        last valid position; "lam": the largest eigenvalue of the Cauchy-Green tensor (NaN on status-4 nodes); "ftle": log(lam) / (2 span)
+        (fs.lcs.ftle); "span": (window samples - 1) * every * dt; "sample_steps": the steps of the window's samples; "direction", "refine",
+        "box"}.  Backward-time FTLE ridges are the attracting structures (where dye collects), forward-time ridges the repelling ones.
+        The ring holds 0 in wall cells, so the no-slip point is the wall cell's centre; the time resolution is the snapshot cadence.
+        Raises RuntimeError without a POD or with fewer than 2 resident samples; not allowed during a graph capture; single-GPU contexts."""
+        from . import lcs
+        from ._lib import FsError
+        from .pod import sample_steps
+        po = self._pod()
+        dev = self._dev
+        if self._capturing():
+            raise FsError("flow_map / ftle / ftle_fields during a graph capture: they allocate and download")
+        box, refine, substeps = lcs.check_lattice(box, refine, substeps, (dev.nx, dev.ny))
+        _, samples = dev.pod_read(po.pod)
+        pairs = lcs.intervals(samples, po.pod.slots, first, last, direction)
+        i0, i1 = lcs.window(samples, po.pod.slots, first, last)
+        h = lcs.step_size(po.every, self._solver.dt, self._solver.dx, substeps, direction)
+        fm = dev.flowmap_create(box, refine)
+        try:
+            for a, b in pairs:
+                dev.flowmap_advance(fm, po.pod, a, b, h, substeps)
+            dev.flowmap_cauchy_green(fm)
+            x, y, status, lam = dev.flowmap_get(fm)
+        finally:
+            dev.flowmap_free(fm)
+        span = (i1 - i0) * po.every * float(self._solver.dt)
+        x0, y0 = lcs.start_positions(box, refine)
+        return {"x": x, "y": y, "x0": x0, "y0": y0, "status": status, "lam": lam, "ftle": lcs.ftle(lam, span), "span": span,
+                "sample_steps": sample_steps(samples, po.pod.slots, po.every, po.start_step, po.base)[i0:i1 + 1],
+                "direction": direction, "refine": refine, "box": box}
+
+    def ftle(self, direction="backward", refine=1, box=None, substeps=1, first=None, last=None):
+        """The finite-time Lyapunov exponent field of flow_map() alone: float64 (nx, ny)."""
+        return self.flow_map(direction, refine, box, substeps, first, last)["ftle"]
+
+    def ftle_fields(self, direction="backward", substeps=1, first=None, last=None):
+        """flow_map() over the whole domain at refine=1 as device fields (v, p), as pod_fields() returns them - for fields_frame and the
+        pressure renderer: p holds the FTLE in the fields' precision (non-finite values as 0), v the displacement (x - x0, y - y0).  New
+        fields on every call; the caller owns them.  Not a hot path: the lattice is downloaded and the two fields are uploaded."""
+        from .runtime import Field
+        m = self.flow_map(direction, 1, None, substeps, first, last)
+        dev = self._dev
+        v, p = Field(dev, 2), Field(dev, 1)      # (not dev.alloc: scratch fields stay out of the ghost-row bookkeeping state of the tapes)
+        v.from_numpy(np.stack([m["x"] - m["x0"], m["y"] - m["y0"]], axis=-1).astype(dev.dtype))
+        p.from_numpy(np.where(np.isfinite(m["ftle"]), m["ftle"], 0.0).astype(dev.dtype))
+        return v, p
+
     # -- tracer particles (new): pathlines and streaklines advanced on the device ------------------------------------------------------
     def seed_tracers(self, seeds, respawn=True, max_age=0, sort_every=0, tau=None, gravity=(0.0, 0.0), deposits=False):
         """From the next step on, N passive particles ride the step: seeds float64 (N, 2) in CELL units (cell (i, j) covers [i, i + 1) x

@@ -1,5 +1,5 @@
 """Device side of what rides the step and of the diagnostics (new; the reference has none): flow statistics, the per-step history, the
-body surface loads, the time averages, the harmonic modes, the snapshot POD and the tracer particles.  Two mixins: RideOps is the
+body surface loads, the time averages, the harmonic modes, the snapshot POD, the flow maps through its snapshots and the tracer particles.  Two mixins: RideOps is the
 backend-agnostic host logic fs.runtime.DeviceBase inherits (slab partition, combination over ranks, argument checks, the op log of a logged period), NativeRideOps the `_p_*` primitives
 fs.runtime.Device binds to libfs_hip.so; the stand-in devices of the CPU tests override those.  fs.runtime re-exports every name here."""
 import ctypes
@@ -61,6 +61,15 @@ class Pod(_Handle):
         self.slots, self.every, self.start = slots, every, start
 
 
+class FlowMap(_Handle):
+    """A device lattice of flow-map nodes (DeviceBase.flowmap_create): handle, cell box, refine, and the lattice (nx, ny)."""
+
+    def __init__(self, h, box, refine):
+        super().__init__(h)
+        self.box, self.refine = tuple(box), refine
+        self.shape = (refine * (box[2] - box[0]), refine * (box[3] - box[1]))
+
+
 class Loads(_Handle):
     """A device body tracker (DeviceBase.loads_create): handle (None on a slab that owns no face), the global face count, which faces
     this rank owns, capacity, every, start."""
@@ -79,7 +88,7 @@ class History(_Handle):
 
 
 class RideOps:
-    """flow_stats and the history_* / loads_* / mean_* / modes_* / pod_* / tracer_* calls of DeviceBase."""
+    """flow_stats and the history_* / loads_* / mean_* / modes_* / pod_* / flowmap_* / tracer_* calls of DeviceBase."""
 
     # (The tracer calls reach these through the class - RideOps._host_only(self, ...) - as they always reached _tracer_host_call: the CPU
     #  tests check their refusals on objects that are no devices.)
@@ -539,6 +548,51 @@ class RideOps:
     def pod_free(self, pod):
         self._release(pod, self._p_pod_free)
 
+    # ---- flow maps (include/fs_hip.h fs_flowmap_*): a lattice of particles carried through the resident snapshots of a POD; csrc/fs_lcs.h ----
+    def flowmap_create(self, box=None, refine=1):
+        """A device lattice for FluidSimulator.flow_map: refine x refine nodes per cell of the cell box (x0, y0, x1, y1) (None: the whole
+        domain), seeded at (x0 + (a + 0.5) / refine, y0 + (b + 0.5) / refine); nodes that start in a wall cell are UNSEEDED.  28 bytes per
+        node.  Single-context grids only (FsError on a slab); not allowed during a graph capture."""
+        from .lcs import check_lattice
+        RideOps._host_only(self, "flowmap_create during a graph capture")
+        if self.nranks > 1:
+            raise _lib.FsError("flow maps need a single-GPU context: on slabs the particles would have to migrate between ranks (not implemented)")
+        box, refine, _ = check_lattice(box, refine, 1, (self.nx, self.ny))
+        h = self._p_flowmap_create(box, refine)
+        return self._adopt(h, FlowMap(h, box, refine))
+
+    def flowmap_advance(self, fm, pod, slot_from, slot_to, h, substeps=1):
+        """Every alive node across one interval of the ring, from slot_from to slot_to, in `substeps` midpoint steps of signed size h (cell
+        units) in the velocity interpolated linearly in time between the two slots.  One launch; reads the ring, writes the lattice."""
+        self._host_only("flowmap_advance during a graph capture")
+        slot_from, slot_to, substeps, h = int(slot_from), int(slot_to), int(substeps), float(h)
+        if not (0 <= slot_from < pod.slots and 0 <= slot_to < pod.slots) or slot_from == slot_to:
+            raise ValueError(f"slots must be two different ones of 0 .. {pod.slots - 1}, got {slot_from} and {slot_to}")
+        if not 1 <= substeps <= 16:
+            raise ValueError(f"substeps must be 1 .. 16, got {substeps}")
+        if not np.isfinite(h) or h == 0.0:
+            raise ValueError(f"h must be finite and not 0, got {h}")
+        self._p_flowmap_advance(fm._h, pod._h, slot_from, slot_to, h, substeps)
+
+    def flowmap_cauchy_green(self, fm):
+        """lam of every node: the largest eigenvalue of the Cauchy-Green tensor of the map, from the positions of the lattice neighbours."""
+        self._host_only("flowmap_cauchy_green during a graph capture")
+        self._p_flowmap_cauchy_green(fm._h)
+
+    def flowmap_get(self, fm):
+        """-> (x, y float64 (nx, ny); status int32 (nx, ny): 0 alive, 1 LEFT, 2 WALL, 4 UNSEEDED; lam float64 (nx, ny))."""
+        self._host_only("flowmap_get during a graph capture")
+        return self._p_flowmap_get(fm._h, fm.shape)
+
+    def flowmap_reset(self, fm):
+        """Seed again: the state after flowmap_create."""
+        self._host_only("flowmap_reset during a graph capture")
+        self._p_flowmap_reset(fm._h)
+
+    def flowmap_free(self, fm):
+        self._host_only("flowmap_free during a graph capture")
+        self._release(fm, self._p_flowmap_free)
+
     # ---- tracer particles (include/fs_hip.h fs_tracer_*): N particles in double cell coordinates, advanced by one launch per step -------
     def tracer_create(self, seeds, respawn=True, max_age=0):
         """A device tracer set for FluidSimulator.seed_tracers: seeds float64 (N, 2) in cell units, N >= 1, inside the domain (whether
@@ -893,6 +947,32 @@ class NativeRideOps:
     def _p_pod_free(self, h):
         if self._ctx is not None:
             _lib.call("fs_pod_free", self._ctx, h)
+
+    def _p_flowmap_create(self, box, refine):
+        h = ctypes.c_void_p()
+        _lib.call("fs_flowmap_create", self._ctx, (ctypes.c_int * 4)(*box), refine, ctypes.byref(h))
+        return h
+
+    def _p_flowmap_advance(self, h, pod_h, slot_from, slot_to, step, substeps):
+        _lib.call("fs_flowmap_advance", self._ctx, h, pod_h, slot_from, slot_to, step, substeps)
+
+    def _p_flowmap_cauchy_green(self, h):
+        _lib.call("fs_flowmap_cauchy_green", self._ctx, h)
+
+    def _p_flowmap_get(self, h, shape):
+        nx, ny = shape
+        x, y, lam = (np.empty((ny, nx), np.float64) for _ in range(3))       # (the library's layout: a contiguous)
+        status = np.empty((ny, nx), np.int32)
+        dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        _lib.call("fs_flowmap_get", self._ctx, h, dp(x), dp(y), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), dp(lam))
+        return tuple(np.ascontiguousarray(a.T) for a in (x, y, status, lam))
+
+    def _p_flowmap_reset(self, h):
+        _lib.call("fs_flowmap_reset", self._ctx, h)
+
+    def _p_flowmap_free(self, h):
+        if self._ctx is not None:
+            _lib.call("fs_flowmap_free", self._ctx, h)
 
     def _p_tracer_create(self, seeds, respawn, max_age):
         h = ctypes.c_void_p()

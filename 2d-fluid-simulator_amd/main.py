@@ -19,6 +19,9 @@ The reference opens a GGUI window and steps forever; here the loop runs `--steps
     the last M sampled fields stay on the GPU, their Gram matrix is reduced there; energies, temporal coefficients and the first K modes are
     written to `--pod-file` (.npz) at the end of the run, with -vis (or --frame-every) the modes as `pod_mode_<k>.png`; the snapshots travel with
     `--save-state` / `--load-state`.
+  * finite-time Lyapunov exponent fields from those resident snapshots (`--ftle forward|backward|both`, `--ftle-refine R`, `--ftle-substeps S`;
+    needs `--pod-snapshots`): a lattice of particles is carried through the snapshots on the GPU, forwards or backwards in time; FTLE, final
+    positions and statuses are written to `--ftle-file` (.npz) at the end of the run, with -vis (or --frame-every) also `ftle_<direction>.png`.
   * follow tracer particles on the GPU (`--tracers N`, `--tracer-line x0,y0,x1,y1,n`): pathlines (`--tracer-once`) or streaklines, written
     to `--tracer-file` (.npz) at the end of the run and every `--tracer-dump-every` steps, drawn into the `-vis` frames; the particle state
     travels with `--save-state` / `--load-state`.  `--tracer-sort-every K` sorts the particles by cell on the GPU every K steps (large sets
@@ -120,6 +123,16 @@ def build_parser():
                    help=".npz of the POD: energies, fraction, coefficients, gram, sample_steps, samples, steps, u, w, p (the first K modes, "
                         "(K, X, Y) each), mean_u / _w / _p, mask, dt, dx, every, start (default: <out>/pod.npz); "
                         "with -vis 0 / 1 / 2 given, or --frame-every, also the images pod_mode_<k>.png")
+    p.add_argument("--ftle", choices=("forward", "backward", "both"), default=None,
+                   help="at the end of the run, carry a lattice of particles through the resident POD snapshots on the GPU (needs --pod-snapshots) and "
+                        "write the finite-time Lyapunov exponent field (FluidSimulator.flow_map): backward marks the attracting structures - dye "
+                        "streaks -, forward the repelling ones")
+    p.add_argument("--ftle-refine", type=int, default=None, metavar="R", help="lattice nodes per cell and direction: 1, 2, 4 or 8 (default 1)")
+    p.add_argument("--ftle-substeps", type=int, default=None, metavar="S", help="midpoint steps per snapshot interval, 1 .. 16 (default 1)")
+    p.add_argument("--ftle-file", type=str, default=None,
+                   help=".npz of the flow maps: ftle_<direction>, status_<direction>, x_<direction>, y_<direction> ((R X, R Y) each), span, "
+                        "sample_steps, refine (default: <out>/ftle.npz); with -vis 0 / 1 / 2 given, or --frame-every, also the images "
+                        "ftle_<direction>.png")
     p.add_argument("--tracers", type=int, default=0,
                    help="follow N tracer particles seeded at random in fluid cells (FluidSimulator.seed_tracers; 0: none unless --tracer-line)")
     p.add_argument("--tracer-seed", type=int, default=None, help="seed of the random generator behind --tracers (default 0)")
@@ -558,6 +571,15 @@ def main(argv=None):
                 print(f"--load-state {args.load_state}: its POD snapshots were taken with --pod-snapshots {held[0]} --pod-every {held[1]} --pod-start "
                       f"{held[2]}; continue with those or sample without the checkpoint's snapshots", file=sys.stderr)
                 sys.exit(2)
+    ftle_refine, ftle_substeps = (1 if args.ftle_refine is None else args.ftle_refine), (1 if args.ftle_substeps is None else args.ftle_substeps)
+    if args.ftle is None:
+        if args.ftle_refine is not None or args.ftle_substeps is not None or args.ftle_file:
+            parser.error("--ftle-refine, --ftle-substeps and --ftle-file need --ftle forward|backward|both")
+    else:
+        if args.pod_snapshots == 0:
+            parser.error("--ftle needs --pod-snapshots M: the flow map is integrated through the resident snapshots")
+        if ftle_refine not in (1, 2, 4, 8) or not 1 <= ftle_substeps <= 16:
+            parser.error("--ftle-refine must be 1, 2, 4 or 8 and --ftle-substeps 1 .. 16")
     tracing = args.tracers > 0 or bool(args.tracer_line)
     if args.tracers < 0 or args.tracer_dump_every < 0 or (args.tracer_max_age is not None and args.tracer_max_age < 0) or args.tracer_sort_every < 0:
         parser.error("--tracers, --tracer-max-age, --tracer-dump-every and --tracer-sort-every must be >= 0")
@@ -701,6 +723,26 @@ def main(argv=None):
             for k in range(arrays["coefficients"].shape[1]):
                 save_png(fields_frame(sim, args.visualization, *sim.pod_fields(k)), out / f"pod_mode_{k}.png")
 
+    def write_ftle():
+        if args.ftle is None:
+            return
+        arrays = {}
+        try:
+            for direction in ("forward", "backward") if args.ftle == "both" else (args.ftle,):
+                m = sim.flow_map(direction, refine=ftle_refine, substeps=ftle_substeps)
+                arrays.update({f"ftle_{direction}": m["ftle"], f"status_{direction}": m["status"], f"x_{direction}": m["x"], f"y_{direction}": m["y"],
+                               "span": np.array(m["span"]), "sample_steps": m["sample_steps"], "refine": np.array(m["refine"])})
+        except RuntimeError as e:
+            print(f"FTLE: {e}; no file written", file=sys.stderr)
+            return
+        ftle_file = Path(args.ftle_file) if args.ftle_file else out / "ftle.npz"
+        ftle_file.parent.mkdir(parents=True, exist_ok=True)
+        np.savez(str(ftle_file), **arrays)
+        if vis_given or args.frame_every:
+            out.mkdir(exist_ok=True)
+            for direction in ("forward", "backward") if args.ftle == "both" else (args.ftle,):
+                save_png(fields_frame(sim, 1, *sim.ftle_fields(direction, substeps=ftle_substeps)), out / f"ftle_{direction}.png")      # (the pressure renderer)
+
     loads_file = None
     if args.loads_every > 0:
         loads_file = Path(args.loads_file) if args.loads_file else out / "loads.npz"
@@ -788,6 +830,7 @@ def main(argv=None):
             write_mean()
             write_modes()
             write_pod()
+            write_ftle()
             write_loads()
             if tracer_file is not None:
                 write_tracers(tracer_file, fields_file, step)
@@ -832,6 +875,7 @@ def main(argv=None):
     write_mean()
     write_modes()
     write_pod()
+    write_ftle()
     write_loads()
     if tracer_file is not None:
         write_tracers(tracer_file, fields_file, step0 + args.steps)

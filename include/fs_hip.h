@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 21
+#define FS_ABI_VERSION 22
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -433,6 +433,36 @@ int fs_pod_get(fs_ctx *ctx, fs_pod *pod, void *slots_out);
 int fs_pod_set(fs_ctx *ctx, fs_pod *pod, const void *slots_in, long long launches, long long samples);
 int fs_pod_reset(fs_ctx *ctx, fs_pod *pod);
 int fs_pod_free(fs_ctx *ctx, fs_pod *pod);
+
+/* Flow maps through the resident snapshots (new, ABI 22): a lattice of particles carried through the ring of a snapshot POD, forwards or
+ * backwards in time, and the largest eigenvalue lam of the Cauchy-Green tensor of the map - FTLE = log(lam) / (2 |T|) is the host's (fs/lcs.py).
+ * Kernels, operation order and the bit-for-bit specification: csrc/fs_lcs.h.  Only reads the ring and the mask; never part of a captured step.
+ * Single-GPU contexts: create returns FS_ERR_UNSUPPORTED on a slab context, as fs_pod_create.
+ * create:  box = {x0, y0, x1, y1} in cells, 0 <= x0 < x1 <= X, 0 <= y0 < y1 <= Y; refine r in {1, 2, 4, 8}: nx = r (x1 - x0) by ny = r (y1 - y0)
+ *          nodes, at most 2^30; node (a, b) starts at (x0 + (a + 0.5) / r, y0 + (b + 0.5) / r), status 0 (alive) or FS_FLOWMAP_UNSEEDED where the
+ *          start cell is a wall cell; lam NaN.  28 bytes per node.  Needs the mask.
+ * advance: every alive node across one interval of the ring, from slot_from to slot_to (0 .. M - 1, different), in `substeps` (1 ..
+ *          FS_FLOWMAP_MAX_SUBSTEPS) midpoint steps of signed size h (finite, not 0; cell units: +- every dt / (dx substeps)) in the velocity
+ *          interpolated bilinearly in space and linearly in time between the two slots.  A node that leaves the domain, or enters an outflow cell
+ *          (h > 0) or an inflow cell (h < 0), gets status FS_TRACER_LEFT, one that enters a wall cell FS_TRACER_WALL; it keeps its last valid
+ *          position and is never moved again.  One launch; no synchronisation.
+ * cauchy_green: lam of every node from the positions of its lattice neighbours (central differences, one-sided beside the lattice's edge and
+ *          beside UNSEEDED nodes; NaN where a direction has neither neighbour, and on UNSEEDED nodes).  One launch; no synchronisation.
+ * get:     synchronises; x, y, lam receive [ny][nx] doubles and status [ny][nx] ints (a contiguous); each may be NULL.
+ * reset:   seeds again (the state after create).
+ * free:    as fs_mean_free.
+ * Every call returns FS_ERR_STATE during graph capture / tape recording, and FS_ERR_ARG - without touching anything - for a null argument
+ * (get's outputs apart), a box outside the grid or empty, another refine, too many nodes, a slot outside 0 .. M - 1, equal slots, substeps
+ * outside 1 .. FS_FLOWMAP_MAX_SUBSTEPS, a non-finite or zero h.                                                                          */
+#define FS_FLOWMAP_UNSEEDED 4
+#define FS_FLOWMAP_MAX_SUBSTEPS 16
+typedef struct fs_flowmap fs_flowmap;
+int fs_flowmap_create(fs_ctx *ctx, const int *box, int refine, fs_flowmap **out);
+int fs_flowmap_advance(fs_ctx *ctx, fs_flowmap *fm, const fs_pod *pod, int slot_from, int slot_to, double h, int substeps);
+int fs_flowmap_cauchy_green(fs_ctx *ctx, fs_flowmap *fm);
+int fs_flowmap_get(fs_ctx *ctx, fs_flowmap *fm, double *x, double *y, int *status, double *lam);
+int fs_flowmap_reset(fs_ctx *ctx, fs_flowmap *fm);
+int fs_flowmap_free(fs_ctx *ctx, fs_flowmap *fm);
 
 /* Multigrid pressure correction (new, ABI 19): one W-cycle (two coarse visits per level) on a mask-aware hierarchy of coarse levels, for the
  * third pressure updater (fs/pressure_updater.py MultigridPressureUpdater; kernels and operation order: csrc/fs_mg.h).  Single-GPU contexts.
