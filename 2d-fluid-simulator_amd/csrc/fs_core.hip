@@ -589,6 +589,8 @@ int fs_destroy(fs_ctx *ctx)
     ctx->modes.clear();
     for (fs_pod *p : ctx->pods) pod_release(p);
     ctx->pods.clear();
+    for (fs_vortex *x : ctx->vortices) vortex_release(x);
+    ctx->vortices.clear();
     for (fs_flowmap *f : ctx->flowmaps) flowmap_release(f);
     ctx->flowmaps.clear();
     for (fs_mg *m : ctx->mgs) mg_release(m);

@@ -1,6 +1,7 @@
 // fs_diag.hip - C-ABI entry points of what reads the flow without changing it: the flow diagnostics (fs_stats.h), the per-step history ring
 // (fs_history.h), the body surface loads (fs_loads.h), the time averages (fs_mean.h), the harmonic modes (fs_modes.h), the snapshot POD
-// (fs_pod.h) and the flow maps through its snapshots (fs_lcs.h), with the release functions of their objects.
+// (fs_pod.h), the flow maps through its snapshots (fs_lcs.h) and the vortex identification (fs_vortex.h), with the release functions of their
+// objects.
 #include "fs_launch.h"
 #include "fs_stats.h"
 #include "fs_mean.h"
@@ -8,6 +9,7 @@
 #include "fs_pod.h"
 #include "fs_lcs.h"
 #include "fs_loads.h"
+#include "fs_vortex.h"
 
 static_assert(fs::STATS_N == FS_FLOW_NSTAT, "fs_stats.h and include/fs_hip.h disagree on the slots");
 static_assert(fs::LOADS_REC == FS_LOADS_NREC && fs::LOADS_SUMS == FS_LOADS_NSUM, "fs_loads.h and include/fs_hip.h disagree on the record / the sums");
@@ -17,6 +19,9 @@ static_assert(fs::MODES_MAX_FREQ == FS_MODES_MAX_FREQ && fs::modes_scalars(FS_MO
 
 static_assert(fs::POD_MAX == FS_POD_MAX, "fs_pod.h and include/fs_hip.h disagree on the slots");
 static_assert(fs::FM_LEFT == FS_TRACER_LEFT && fs::FM_WALL == FS_TRACER_WALL && fs::FM_UNSEEDED == FS_FLOWMAP_UNSEEDED && fs::FM_MAX_SUBSTEPS == FS_FLOWMAP_MAX_SUBSTEPS, "fs_lcs.h and include/fs_hip.h disagree");
+
+static_assert(fs::VX_NACC == FS_VORTEX_NACC && fs::VX_REC == FS_VORTEX_NREC && fs::VX_HEAD == FS_VORTEX_NHEAD && fs::VX_MAX_VORTICES == FS_VORTEX_MAX_VORTICES,
+              "fs_vortex.h and include/fs_hip.h disagree");
 
 namespace fs {
 void history_release(fs_history *h)
@@ -56,6 +61,18 @@ void pod_release(fs_pod *p)
     if (p->d_state) hipFree(p->d_state);
     if (p->d_gram) hipFree(p->d_gram);
     delete p;
+}
+void vortex_release(fs_vortex *x)
+{
+    if (x->d_flags) hipFree(x->d_flags);
+    if (x->d_labels) hipFree(x->d_labels);
+    if (x->d_ids) hipFree(x->d_ids);
+    if (x->d_counts) hipFree(x->d_counts);
+    if (x->d_table) hipFree(x->d_table);
+    if (x->d_tmp) hipFree(x->d_tmp);
+    if (x->d_ring) hipFree(x->d_ring);
+    if (x->d_state) hipFree(x->d_state);
+    delete x;
 }
 void flowmap_release(fs_flowmap *f)
 {
@@ -894,6 +911,236 @@ int fs_pod_free(fs_ctx *ctx, fs_pod *pod)
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
     pod_release(pod);
+    return FS_OK;
+}
+
+// ---- vortex identification (fs_vortex.h) ----------------------------------------------------------------------------------------------------
+#define FS_VORTEX_HANDLE(x) FS_REQUIRE((x)->ctx == ctx && ctx->vortices.count(x), "vortex tracker from another context or freed")
+#define FS_VORTEX_NO_CAPTURE(what) \
+    if (ctx->capturing || ctx->tape_rec) { set_error("vortex " what " during graph capture / tape recording"); return FS_ERR_STATE; }
+#define FS_VORTEX_SINGLE_GPU() \
+    if (ctx->halo != 0 || ctx->nyl != ctx->Y) { \
+        set_error("vortex identification needs a single-GPU context: on a slab the components would have to be united across ranks (not implemented)"); \
+        return FS_ERR_UNSUPPORTED; \
+    }
+
+// the three launches that turn a flag plane into labels (fs_vortex.h b); counts: the roots per block of the compression, or nullptr
+static int vortex_label_launches(fs_ctx *ctx, VxWhen when, const uint8_t *flags, int *labels, int *counts)
+{
+    const int X = ctx->X, Y = ctx->Y, n = X * Y;
+    const int ntx = (X + VX_TX - 1) / VX_TX, nty = (Y + VX_TY - 1) / VX_TY;
+    const long long pairs = (long long)(ntx - 1) * Y + (long long)(nty - 1) * X;
+    int rc = launch(ctx, "vortex_local", [=] { klaunch(k_vortex_local, dim3(ntx, nty), dim3(256), ctx->stream, X, Y, when, flags, labels); });
+    if (rc) return rc;
+    rc = launch(ctx, "vortex_seam", [=] {
+        klaunch(k_vortex_seam, dim3((unsigned)std::max<long long>(1, (pairs + 255) / 256)), dim3(256), ctx->stream, X, Y, when, flags, labels);
+    });
+    if (rc) return rc;
+    return launch(ctx, "vortex_compress", [=] {
+        klaunch(k_vortex_compress, dim3((n + VX_BLOCK - 1) / VX_BLOCK), dim3(256), ctx->stream, n, when, labels, counts);
+    });
+}
+
+static dim3 vortex_flags_grid(const fs_ctx *ctx, int *rpw)
+{
+    const int nx = (ctx->X + 255) / 256;
+    *rpw = diag_rows(ctx, nx, ctx->Y, VX_G, VX_ROWS);
+    return dim3(nx, (ctx->Y + *rpw - 1) / *rpw);
+}
+
+int fs_vortex_create(fs_ctx *ctx, int criterion, double threshold, double scale, long long every, long long start, int min_area, int max_vortices,
+                     int max_components, int capacity, fs_vortex **out)
+{
+    FS_REQUIRE(ctx && out, "null argument");
+    FS_REQUIRE(criterion >= 0 && criterion <= 2, "criterion must be 0 (q), 1 (swirl) or 2 (vorticity)");
+    FS_REQUIRE(std::isfinite(threshold), "threshold must be finite");
+    FS_REQUIRE(std::isfinite(scale) && scale > 0.0, "scale must be finite and positive");
+    FS_REQUIRE(every >= 1 && start >= 0, "every must be >= 1 and start >= 0");
+    FS_REQUIRE(min_area >= 1, "min_area must be >= 1");
+    FS_REQUIRE(max_vortices >= 1 && max_vortices <= VX_MAX_VORTICES, "max_vortices must be 1 .. FS_VORTEX_MAX_VORTICES");
+    FS_REQUIRE(max_components >= 1 && max_components <= (1 << 24), "max_components must be 1 .. 2^24");
+    FS_REQUIRE(capacity >= 1, "capacity must be >= 1");
+    FS_VORTEX_NO_CAPTURE("create")
+    FS_VORTEX_SINGLE_GPU()
+    FS_HIP(hipSetDevice(ctx->device));
+    fs_vortex *x = new fs_vortex();
+    x->ctx = ctx; x->criterion = criterion; x->threshold = threshold; x->scale = scale; x->every = every; x->start = start;
+    x->min_area = min_area; x->maxv = max_vortices; x->maxc = max_components; x->cap = capacity;
+    x->cells = ctx->X * ctx->Y;
+    x->nblocks = (x->cells + VX_BLOCK - 1) / VX_BLOCK;
+    x->words = VX_HEAD + VX_REC * max_vortices;
+    const size_t n = (size_t)x->cells, table = (size_t)VX_NACC * max_components * sizeof(long long);
+    hipError_t e = hipMalloc(&x->d_state, VX_STATE * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc(&x->d_tmp, VX_TMP * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc(&x->d_flags, n);
+    if (e == hipSuccess) e = hipMalloc(&x->d_labels, n * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&x->d_ids, n * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&x->d_counts, (size_t)x->nblocks * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&x->d_table, table);
+    if (e == hipSuccess) e = hipMalloc(&x->d_ring, (size_t)capacity * x->words * sizeof(long long));
+    if (e == hipSuccess) e = hipMemsetAsync(x->d_state, 0, VX_STATE * sizeof(long long), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(x->d_tmp, 0, VX_TMP * sizeof(long long), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(x->d_flags, 0, n, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(x->d_labels, 0xff, n * sizeof(int), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(x->d_ids, 0, n * sizeof(int), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(x->d_table, 0, table, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(x->d_ring, 0, (size_t)capacity * x->words * sizeof(long long), ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { vortex_release(x); return hip_fail(e, "fs_vortex_create", __FILE__, __LINE__); }
+    ctx->vortices.insert(x);
+    *out = x;
+    return FS_OK;
+}
+
+int fs_vortex_launch(fs_ctx *ctx, fs_vortex *vx, double limit, double dx, const fs_field *v)
+{
+    FS_REQUIRE(ctx && vx, "null argument");
+    FS_VORTEX_HANDLE(vx);
+    FS_FIELD(v, 2);
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    // everything the launches need is in `vx` and the field: no allocation, copy or synchronisation here (the closure is captured / taped)
+    const fs_vortex x = *vx;
+    const VxWhen when{x.d_state, x.start, x.every, x.cap};
+    int rpw;
+    const dim3 fgrid = vortex_flags_grid(ctx, &rpw);
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
+        int rc = launch(ctx, "vortex_flags", [=] {
+            klaunch(k_vortex_flags<T, false>, fgrid, dim3(256), ctx->stream, ctx->grid(), ctx->Y, rpw, when, x.criterion, x.threshold, dx, limit,
+                    (const T *)v->d, x.d_flags, (double *)nullptr, x.d_table, x.maxc, x.d_tmp);
+        });
+        if (rc) return rc;
+        rc = vortex_label_launches(ctx, when, x.d_flags, x.d_labels, x.d_counts);
+        if (rc) return rc;
+        rc = launch(ctx, "vortex_scan", [=] { klaunch(k_vortex_scan, dim3(1), dim3(256), ctx->stream, x.nblocks, when, x.d_counts, x.d_tmp); });
+        if (rc) return rc;
+        rc = launch(ctx, "vortex_ids", [=] {
+            klaunch(k_vortex_ids, dim3(x.nblocks), dim3(256), ctx->stream, x.cells, when, x.maxc, (const int *)x.d_labels, (const int *)x.d_counts, x.d_ids,
+                    x.d_table);
+        });
+        if (rc) return rc;
+        rc = launch(ctx, "vortex_reduce", [=] {
+            klaunch(k_vortex_reduce<T>, dim3((x.cells + 255) / 256), dim3(256), ctx->stream, ctx->grid(), x.cells, when, dx, limit, x.scale, x.maxc,
+                    (const T *)v->d, (const uint8_t *)x.d_flags, (const int *)x.d_labels, (const int *)x.d_ids, x.d_table, x.d_tmp);
+        });
+        if (rc) return rc;
+        rc = launch(ctx, "vortex_records", [=] {
+            klaunch(k_vortex_records, dim3(1), dim3(1024), ctx->stream, when, x.maxc, x.min_area, x.maxv, x.words, (const uint8_t *)x.d_flags,
+                    (const long long *)x.d_table, (const long long *)x.d_tmp, x.d_ring);
+        });
+        if (rc) return rc;
+        return launch(ctx, "vortex_tick", [=] { klaunch(k_vortex_tick, dim3(1), dim3(64), ctx->stream, x.start, x.every, x.cap, x.d_state); });
+    });
+}
+
+int fs_vortex_read(fs_ctx *ctx, fs_vortex *vx, long long *out, int max_samples, int *n_out, long long *launches, long long *lost)
+{
+    FS_REQUIRE(ctx && vx && n_out, "null argument");
+    FS_VORTEX_HANDLE(vx);
+    FS_VORTEX_NO_CAPTURE("read")
+    FS_HIP(hipSetDevice(ctx->device));
+    long long st[VX_STATE];
+    FS_HIP(hipMemcpyAsync(st, vx->d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    const int n = (int)st[1];
+    FS_REQUIRE(n == 0 || (out && max_samples >= n), "out holds fewer samples than the ring");
+    if (n) FS_HIP(hipMemcpyAsync(out, vx->d_ring, (size_t)n * vx->words * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipMemsetAsync(vx->d_state + 1, 0, 2 * sizeof(long long), ctx->stream));      // the ring is empty again, nothing lost since
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    *n_out = n;
+    if (launches) *launches = st[0];
+    if (lost) *lost = st[2];
+    return FS_OK;
+}
+
+int fs_vortex_get_labels(fs_ctx *ctx, fs_vortex *vx, unsigned char *flags, int *labels)
+{
+    FS_REQUIRE(ctx && vx, "null argument");
+    FS_VORTEX_HANDLE(vx);
+    FS_VORTEX_NO_CAPTURE("get_labels")
+    FS_HIP(hipSetDevice(ctx->device));
+    if (flags) FS_HIP(hipMemcpyAsync(flags, vx->d_flags, (size_t)vx->cells, hipMemcpyDeviceToHost, ctx->stream));
+    if (labels) FS_HIP(hipMemcpyAsync(labels, vx->d_labels, (size_t)vx->cells * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_vortex_set(fs_ctx *ctx, fs_vortex *vx, long long launches)
+{
+    FS_REQUIRE(ctx && vx, "null argument");
+    FS_VORTEX_HANDLE(vx);
+    FS_REQUIRE(launches >= 0, "launches must be >= 0");
+    FS_VORTEX_NO_CAPTURE("set")
+    FS_HIP(hipSetDevice(ctx->device));
+    const long long st[VX_STATE] = {launches, 0, 0, 0};
+    FS_HIP(hipMemcpyAsync(vx->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));      // (the source is this frame's memory)
+    return FS_OK;
+}
+
+int fs_vortex_label(fs_ctx *ctx, const unsigned char *flags, int *labels)
+{
+    FS_REQUIRE(ctx && flags && labels, "null argument");
+    FS_VORTEX_NO_CAPTURE("label")
+    FS_VORTEX_SINGLE_GPU()
+    FS_HIP(hipSetDevice(ctx->device));
+    const size_t n = (size_t)ctx->X * ctx->Y;
+    uint8_t *d_flags = nullptr;
+    int *d_labels = nullptr;
+    hipError_t e = hipMalloc(&d_flags, n);
+    if (e == hipSuccess) e = hipMalloc(&d_labels, n * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpyAsync(d_flags, flags, n, hipMemcpyHostToDevice, ctx->stream);
+    int rc = FS_OK;
+    if (e == hipSuccess) {
+        const VxWhen always{nullptr, 0, 1, 0};
+        rc = vortex_label_launches(ctx, always, d_flags, d_labels, nullptr);
+    }
+    if (e == hipSuccess && rc == FS_OK) e = hipMemcpyAsync(labels, d_labels, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (d_flags) hipFree(d_flags);
+    if (d_labels) hipFree(d_labels);
+    if (rc) return rc;
+    if (e == hipSuccess) e = es;
+    return e == hipSuccess ? FS_OK : hip_fail(e, "fs_vortex_label", __FILE__, __LINE__);
+}
+
+int fs_vortex_criterion(fs_ctx *ctx, int which, double limit, double dx, const fs_field *v, double *out)
+{
+    FS_REQUIRE(ctx && out, "null argument");
+    FS_REQUIRE(which >= 0 && which <= 2, "criterion must be 0 (q), 1 (swirl) or 2 (vorticity)");
+    FS_FIELD(v, 2);
+    FS_VORTEX_NO_CAPTURE("criterion")
+    FS_VORTEX_SINGLE_GPU()
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    FS_HIP(hipSetDevice(ctx->device));
+    const size_t n = (size_t)ctx->X * ctx->Y;
+    double *d_crit = nullptr;
+    FS_HIP(hipMalloc(&d_crit, n * sizeof(double)));
+    const VxWhen always{nullptr, 0, 1, 0};
+    int rpw;
+    const dim3 fgrid = vortex_flags_grid(ctx, &rpw);
+    const int rc = by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
+        return launch(ctx, "vortex_criterion", [=] {
+            klaunch(k_vortex_flags<T, true>, fgrid, dim3(256), ctx->stream, ctx->grid(), ctx->Y, rpw, always, which, 0.0, dx, limit, (const T *)v->d,
+                    (uint8_t *)nullptr, d_crit, (long long *)nullptr, 0, (long long *)nullptr);
+        });
+    });
+    hipError_t e = rc ? hipSuccess : hipMemcpyAsync(out, d_crit, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    hipFree(d_crit);
+    if (rc) return rc;
+    if (e == hipSuccess) e = es;
+    return e == hipSuccess ? FS_OK : hip_fail(e, "fs_vortex_criterion", __FILE__, __LINE__);
+}
+
+int fs_vortex_free(fs_ctx *ctx, fs_vortex *vx)
+{
+    if (!vx) return FS_OK;
+    FS_REQUIRE(ctx && vx->ctx == ctx && ctx->vortices.count(vx), "vortex tracker from another context or freed");
+    ctx->vortices.erase(vx);
+    if (ctx->capturing) { ctx->deferred_release.push_back([vx] { vortex_release(vx); }); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
+    vortex_release(vx);
     return FS_OK;
 }
 

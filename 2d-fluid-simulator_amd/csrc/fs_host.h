@@ -133,6 +133,7 @@ struct fs_ctx {
     std::set<fs_mean *> means;               // live time averages (fs_mean_create), released with the context
     std::set<fs_modes *> modes;              // live harmonic-mode accumulators (fs_modes_create), released with the context
     std::set<fs_pod *> pods;                 // live snapshot sets (fs_pod_create), released with the context
+    std::set<fs_vortex *> vortices;          // live vortex trackers (fs_vortex_create), released with the context
     std::set<fs_flowmap *> flowmaps;         // live flow-map lattices (fs_flowmap_create), released with the context
     std::set<fs_mg *> mgs;                   // live multigrid hierarchies (fs_mg_create), released with the context
     std::set<fs_loads *> loads;              // live body trackers (fs_loads_create), released with the context
@@ -238,6 +239,23 @@ struct fs_flowmap {
     int *d_status = nullptr;        // [ny][nx]
 };
 
+// vortex identification (fs_vortex_*, fs_vortex.h): the flag, label and id planes of the whole grid, the accumulator table, the ring of samples
+struct fs_vortex {
+    fs_ctx *ctx = nullptr;
+    int criterion = 0, min_area = 4, maxv = 64, maxc = 65536, cap = 1;
+    double threshold = 0.0, scale = 1.0;    // scale: 2^(30 - e), what turns om into the integer q
+    long long every = 1, start = 0;
+    int cells = 0, nblocks = 0, words = 0;  // X * Y; workgroups of the compression / id passes; long long words per sample
+    uint8_t *d_flags = nullptr;     // [Y][X]
+    int *d_labels = nullptr;        // [Y][X]
+    int *d_ids = nullptr;           // [Y][X]: the dense id of every root
+    int *d_counts = nullptr;        // [nblocks]: roots per block, then their exclusive offsets
+    long long *d_table = nullptr;   // [VX_NACC][maxc]
+    long long *d_tmp = nullptr;     // [VX_TMP]
+    long long *d_ring = nullptr;    // [cap][words]
+    long long *d_state = nullptr;   // [VX_STATE]
+};
+
 namespace fs { struct LoadFace; }      // fs_loads.h (included by fs_diag.hip alone)
 // body surface loads (fs_loads_*, fs_loads.h): the face list of this context's owned rows, the per-face sums, the ring and the device counters
 struct fs_loads {
@@ -286,6 +304,7 @@ void loads_release(fs_loads *l);          // fs_diag.hip
 void modes_release(fs_modes *m);          // fs_diag.hip
 void pod_release(fs_pod *p);              // fs_diag.hip
 void flowmap_release(fs_flowmap *f);      // fs_diag.hip
+void vortex_release(fs_vortex *x);        // fs_diag.hip
 void mg_release(fs_mg *m);                // fs_multigrid.hip
 
 // HIP-event pair around a span of stream work that is not one kernel launch (fs_core.hip; the ghost-row exchange chain of fs_comm.hip)

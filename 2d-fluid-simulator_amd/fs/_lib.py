@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FS_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libfs_hip.so")     # FS_LIB: A/B builds (tools/)
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 _lib = None
 
@@ -114,6 +114,14 @@ _PROTOS = {
     "fs_pod_set": [_c_vp, _c_vp, _c_vp, ctypes.c_longlong, ctypes.c_longlong],
     "fs_pod_reset": [_c_vp, _c_vp],
     "fs_pod_free": [_c_vp, _c_vp],
+    "fs_vortex_create": [_c_vp, _c_int, _c_dbl, _c_dbl, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int, _P(_c_vp)],
+    "fs_vortex_launch": [_c_vp, _c_vp, _c_dbl, _c_dbl, _c_vp],
+    "fs_vortex_read": [_c_vp, _c_vp, _P(ctypes.c_longlong), _c_int, _P(_c_int), _P(ctypes.c_longlong), _P(ctypes.c_longlong)],
+    "fs_vortex_get_labels": [_c_vp, _c_vp, _P(ctypes.c_ubyte), _P(_c_int)],
+    "fs_vortex_set": [_c_vp, _c_vp, ctypes.c_longlong],
+    "fs_vortex_label": [_c_vp, _P(ctypes.c_ubyte), _P(_c_int)],
+    "fs_vortex_criterion": [_c_vp, _c_int, _c_dbl, _c_dbl, _c_vp, _P(_c_dbl)],
+    "fs_vortex_free": [_c_vp, _c_vp],
     "fs_flowmap_create": [_c_vp, _P(_c_int), _c_int, _P(_c_vp)],
     "fs_flowmap_advance": [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_int],
     "fs_flowmap_cauchy_green": [_c_vp, _c_vp],

@@ -17,6 +17,7 @@ from .history import Recorder, body_faces, check_probes
 from .loads import Tracker, body_centroid, face_geometry
 from .modes import Modes, fit as fit_modes, gram_matrix, phasor_steps, reconstruct_weights
 from .pod import Pod
+from .vortices import VELOCITY_LIMIT, Vortices, assemble, omega_exponent
 from .pressure_updater import JacobiPressureUpdater, MultigridPressureUpdater, RedBlackSorPressureUpdater
 from .solver import CipMacSolver, DyeCipMacSolver, DyeMacSolver, MacSolver
 from .tracers import TracerAccumulation, Tracers, check_seeds, response
@@ -97,11 +98,14 @@ class FluidSimulator:
         self._tracers = None       # fs.tracers.Tracers while seed_tracers() is on
         self._tracker = None       # fs.loads.Tracker while track_body() is on
         self._last_tracker = None  # ... and after stop_body(): what body_loads() / body_surface() still return
+        self._vortexr = None       # fs.vortices.Vortices while track_vortices() is on
+        self._last_vortexr = None  # ... and after stop_vortices(): what vortices() / vortex_labels() still return
+        self._found_planes = None  # the planes of the last find_vortices()
 
     def _riders(self):
-        """The attached riders (fs.riders.Rider) in their fixed order - history, averages, modes, pod, loads, tracers: the order of their
-        launches behind the solver step and of their tokens in _signature()."""
-        return [r for r in (self._recorder, self._averager, self._moder, self._podr, self._tracker, self._tracers) if r is not None]
+        """The attached riders (fs.riders.Rider) in their fixed order - history, averages, modes, pod, loads, tracers, vortices: the order of
+        their launches behind the solver step and of their tokens in _signature()."""
+        return [r for r in (self._recorder, self._averager, self._moder, self._podr, self._tracker, self._tracers, self._vortexr) if r is not None]
 
     def _capturing(self):
         return getattr(self._dev, "capturing", False)
@@ -787,6 +791,108 @@ class FluidSimulator:
         """Detach the POD and free its device memory; the cached graphs that hold its launch are freed first.  Nothing is kept on the host:
         call pod() before.  Inside a graph capture the device memory is released when the capture ends."""
         self._detach(self, "_podr", "stop_pod")
+
+    # -- vortex identification (new): criterion, labelled components and per-vortex records, on the device ----------------------------------
+    def _vortex_create(self, threshold, criterion, every, start_step, min_area, max_vortices, max_components, omega_max, capacity):
+        s = self._solver
+        if threshold is None:
+            raise ValueError("threshold must be given (1 / time^2): see track_vortices")
+        if omega_max is None:
+            omega_max = 2.0 * VELOCITY_LIMIT / s.dx
+        if capacity is None:
+            capacity = max(16, (16 << 20) // (8 * (8 + 16 * int(max_vortices))))
+        return self._dev.vortex_create(criterion, threshold, omega_exponent(omega_max), every, start_step, min_area, max_vortices, max_components,
+                                       int(capacity))
+
+    def track_vortices(self, threshold, criterion="q", every=1, start_step=0, min_area=4, max_vortices=64, max_components=65536, omega_max=None,
+                       capacity=None):
+        """From the next step on, identify the vortices after every step k (counted from here, k = 1, 2, ...) with k > start_step and
+        (k - start_step) % every == 0, on the device (csrc/fs_vortex.h): a cell is part of a vortex when it is fluid and its criterion c
+        exceeds `threshold`; the 4-connected cells of equal rotation sense form a component; every component of at least `min_area` cells
+        becomes a record - the first `max_vortices` (at most 1024) in order of their label, the smallest j * X + i of the component - in a
+        device ring of `capacity` samples (default: 16 MB of them) that run() drains between chunks.
+
+        criterion, in 1 / time^2 with the central differences of flow_stats: "q" - Q = -(ux^2 + wy^2) / 2 - uy wx, positive where rotation
+        outweighs strain; "swirl" - lambda_ci^2 = (ux wy - uy wx) - (ux + wy)^2 / 4, positive where the velocity gradient has complex
+        eigenvalues; "vorticity" - om^2.  threshold has no default: with U the free-stream speed and L the size of the body, gradients in
+        the wake are of order U / L, so start from a fraction of (U / L)^2 - 0.1 (U / L)^2 for "q" and "swirl" keeps the cores and drops the
+        shear layers, for "vorticity" take 1 (U / L)^2 - and look at vortex_criterion() to refine it.  A threshold of 0 flags half the domain.
+
+        The records hold integer sums (vorticity in units of 2^(e - 30), e = ceil(log2(omega_max)); omega_max defaults to 2 * 10 / dx, the
+        bound of a limited velocity field; cells beyond it are clamped and counted in `clipped`): they do not depend on the order of the
+        device's atomics, and a resumed run continues them exactly.  At most `max_components` components are reduced per sample (those of
+        smallest label; the cells of the others are counted in `dropped_cells`).  The launches go behind every other rider's, are captured
+        into the replayed graphs, and change no field and no trajectory.  9 bytes per cell of device memory.  Raises while a tracker is
+        attached already and during a graph capture; single-GPU contexts.  Out of scope: slabs, 8-connectivity, three dimensions."""
+        self._not_capturing("track_vortices")
+        self._make_way("_vortexr", "a vortex tracker is attached already: stop_vortices() first")
+        every, start_step = self._cadence(every, start_step)
+        s = self._solver
+        vx = self._vortex_create(threshold, criterion, every, start_step, min_area, max_vortices, max_components, omega_max, capacity)
+        self._vortexr = Vortices(self._dev, vx, every, start_step, s.dt, s.dx)
+        self._last_vortexr = None
+
+    def vortices(self):
+        """Every sample since track_vortices().  Per sample: "step", "time" (step * dt), "components" (roots found), "passed" (those of at
+        least min_area cells), "count" (records written), "clipped", "dropped_cells".  Per record, flat over the samples in (sample, label)
+        order: "sample" (index into the per-sample arrays), "label", "sign" (+1: counter-clockwise), "area" (cells), "circulation", "x", "y"
+        (|om|-weighted centroid, cell units: the centre of cell i is i + 0.5), "xg", "yg" (geometric centroid), "peak_omega", "peak_cell",
+        "bbox" (xmin, ymin, xmax, ymax, inclusive).  "raw": the integers of every record (fs.vortices.RECORD), "exponent": e.
+        fs.vortices.convert documents the order of every conversion.  Drains the device ring (a download)."""
+        r = self._vortexr or self._last_vortexr
+        if r is None:
+            raise RuntimeError("no vortex tracker: call track_vortices() first")
+        if r is self._vortexr:
+            self._not_capturing("vortices")
+            r.drain()
+        return r.data()
+
+    def stop_vortices(self):
+        """Drain and detach the vortex tracker: the cached graphs that hold its launches are freed, then its device memory.  vortices() and
+        vortex_labels() still return what it gathered until the next track_vortices()."""
+        if self._vortexr is not None:
+            self._found_planes = None
+        self._detach(self, "_vortexr", "stop_vortices")
+
+    def find_vortices(self, threshold, criterion="q", min_area=4, max_vortices=64, max_components=65536, omega_max=None):
+        """The vortices of the fields as they are now: what vortices() returns, with one sample whose "step" and "time" are 0 (the call
+        counts no steps).  One temporary tracker, one eager launch sequence, a read and a free: changes no field,
+        no graph and no attached tracker, and leaves a deferred limit_field deferred.  vortex_labels() returns its planes until the next
+        call.  Not allowed during a graph capture."""
+        dev, s = self._dev, self._solver
+        self._not_capturing("find_vortices")
+        vx = self._vortex_create(threshold, criterion, 1, 0, min_area, max_vortices, max_components, omega_max, 1)
+        try:
+            saved, dev._oplog = getattr(dev, "_oplog", None), None      # (never part of a logged period)
+            try:
+                dev.vortex_launch(vx, s.dx, s.get_fields()[0])
+            finally:
+                dev._oplog = saved
+            words, _, _ = dev.vortex_read(vx)
+            self._found_planes = dev.vortex_labels(vx)
+        finally:
+            dev.vortex_free(vx)
+        return assemble(words, vx.max_vortices, vx.exponent, s.dx, dev.nx, np.zeros(len(words), np.int64), s.dt)
+
+    def vortex_labels(self):
+        """{"flags": uint8 (X, Y) - 1: om >= 0, 2: om < 0, 0: no vortex; "labels": int32 (X, Y) - the smallest j * X + i of the cell's
+        component, -1 without a flag} of the attached tracker's last sample; without one, of the last find_vortices() or stopped tracker,
+        whichever is the more recent."""
+        self._not_capturing("vortex_labels")
+        if self._vortexr is not None:
+            return self._vortexr.planes()
+        if self._found_planes is not None:
+            return self._found_planes
+        if self._last_vortexr is None:
+            raise RuntimeError("no labels: call track_vortices() or find_vortices() first")
+        return self._last_vortexr.planes()
+
+    def vortex_criterion(self, criterion="q"):
+        """The criterion field of the current velocity, float64 (X, Y), 0 on cells that are not fluid: what track_vortices compares with its
+        threshold.  Not allowed during a graph capture."""
+        self._not_capturing("vortex_criterion")
+        s = self._solver
+        return self._dev.vortex_criterion(criterion, s.dx, s.get_fields()[0])
 
     # -- flow maps and FTLE fields (new): a lattice of particles carried through the POD's resident snapshots on the device --------------
     def flow_map(self, direction="backward", refine=1, box=None, substeps=1, first=None, last=None):

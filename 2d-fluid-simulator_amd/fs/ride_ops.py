@@ -61,6 +61,15 @@ class Pod(_Handle):
         self.slots, self.every, self.start = slots, every, start
 
 
+class Vortex(_Handle):
+    """A device vortex tracker (DeviceBase.vortex_create): handle and the parameters of its samples."""
+
+    def __init__(self, h, criterion, threshold, exponent, every, start, min_area, max_vortices, max_components, capacity):
+        super().__init__(h)
+        self.criterion, self.threshold, self.exponent, self.every, self.start = criterion, threshold, exponent, every, start
+        self.min_area, self.max_vortices, self.max_components, self.capacity = min_area, max_vortices, max_components, capacity
+
+
 class FlowMap(_Handle):
     """A device lattice of flow-map nodes (DeviceBase.flowmap_create): handle, cell box, refine, and the lattice (nx, ny)."""
 
@@ -548,6 +557,81 @@ class RideOps:
     def pod_free(self, pod):
         self._release(pod, self._p_pod_free)
 
+    # ---- vortex identification (include/fs_hip.h fs_vortex_*): criterion, labelled components and integer records; csrc/fs_vortex.h ----
+    VORTEX_CRITERIA = ("q", "swirl", "vorticity")
+    VORTEX_MAX = 1024
+
+    def _vortex_host_call(self, what):
+        RideOps._host_only(self, f"{what} during a graph capture")
+        if self.nranks > 1:
+            raise _lib.FsError("vortex identification needs a single-GPU context: on slabs the components would have to be united across ranks (not implemented)")
+
+    def _vortex_criterion(self, criterion):
+        if criterion not in self.VORTEX_CRITERIA:
+            raise ValueError(f"criterion must be one of {self.VORTEX_CRITERIA}, got {criterion!r}")
+        return self.VORTEX_CRITERIA.index(criterion)
+
+    def vortex_create(self, criterion, threshold, exponent, every=1, start=0, min_area=4, max_vortices=64, max_components=65536, capacity=256):
+        """A device vortex tracker for FluidSimulator.track_vortices: flag, label and id planes of the grid (9 bytes per cell), a table of
+        120 bytes per component and a ring of `capacity` samples of 8 + 16 max_vortices int64 words.  threshold: finite, in 1 / time^2;
+        exponent e: q = llrint(ldexp(om, 30 - e)).  Launch n (from 0) of vortex_launch samples when n + 1 > start and (n + 1 - start) %
+        every == 0.  Single-context grids only; not allowed during a graph capture."""
+        RideOps._vortex_host_call(self, "vortex_create")      # (through the class, as the tracer calls: the tests ask objects that are no devices)
+        which = self._vortex_criterion(criterion)
+        if threshold is None or not np.isfinite(float(threshold)):
+            raise ValueError(f"threshold must be a finite number (1 / time^2), got {threshold!r}")
+        every, start = self._check_cadence(every, start, capacity)
+        min_area, max_vortices, max_components, exponent = int(min_area), int(max_vortices), int(max_components), int(exponent)
+        if not 1 <= max_vortices <= self.VORTEX_MAX:
+            raise ValueError(f"max_vortices must be 1 .. {self.VORTEX_MAX}, got {max_vortices}")
+        if min_area < 1 or not 1 <= max_components <= 1 << 24:
+            raise ValueError("min_area must be >= 1 and max_components 1 .. 2^24")
+        if not -900 <= exponent <= 900:
+            raise ValueError(f"exponent {exponent} out of range")
+        h = self._p_vortex_create(which, float(threshold), exponent, every, start, min_area, max_vortices, max_components, int(capacity))
+        return self._adopt(h, Vortex(h, criterion, float(threshold), exponent, every, start, min_area, max_vortices, max_components, int(capacity)))
+
+    def vortex_launch(self, vx, dx, v):
+        """The launches of one step: when this launch samples, flag, label and reduce the components of v and append a sample to the ring;
+        the counters advance on the device.  A limit_field v still owes stays deferred: the kernels limit the values they read.  Not a
+        _run: no flush, no exchange, no ghost row (writes no field)."""
+        self._ride("vortex_launch", (vx._h, self._limit_of(v), float(dx), v._h))
+
+    def vortex_read(self, vx):
+        """Drain the ring -> (int64 (n, 8 + 16 max_vortices) samples, launches, samples lost to a full ring since the last read)."""
+        self._host_only("vortex_read during a graph capture: the ring is a download (read between captures / replays)")
+        return self._p_vortex_read(vx._h, vx.capacity, 8 + 16 * vx.max_vortices)
+
+    def vortex_labels(self, vx):
+        """-> {"flags": uint8 (X, Y), "labels": int32 (X, Y)} of the last sampling launch: 1 / 2 / 0, and the smallest j * X + i of the cell's
+        component (-1 without a flag)."""
+        self._host_only("vortex_labels during a graph capture")
+        flags, labels = self._p_vortex_get_labels(vx._h)
+        return {"flags": flags, "labels": labels}
+
+    def vortex_set(self, vx, launches):
+        """The launch count of a resumed run; the ring is emptied."""
+        self._host_only("vortex_set during a graph capture")
+        if int(launches) < 0:
+            raise ValueError("launches must be >= 0")
+        self._p_vortex_set(vx._h, int(launches))
+
+    def vortex_label(self, flags):
+        """The labels of a flag plane uint8 (X, Y): cells with equal non-zero bytes join over their 4 neighbours -> int32 (X, Y)."""
+        self._vortex_host_call("vortex_label")
+        flags = np.asarray(flags)
+        if flags.shape != (self.nx, self.ny) or flags.dtype != np.uint8:
+            raise ValueError(f"expected uint8 flags of shape {(self.nx, self.ny)}, got {flags.dtype} {flags.shape}")
+        return self._p_vortex_label(flags)
+
+    def vortex_criterion(self, criterion, dx, v):
+        """The criterion field of v -> float64 (X, Y), 0 on cells that are not fluid (csrc/fs_vortex.h a)."""
+        self._vortex_host_call("vortex_criterion")
+        return self._p_vortex_criterion(self._vortex_criterion(criterion), self._limit_of(v), float(dx), v._h)
+
+    def vortex_free(self, vx):
+        self._release(vx, self._p_vortex_free)
+
     # ---- flow maps (include/fs_hip.h fs_flowmap_*): a lattice of particles carried through the resident snapshots of a POD; csrc/fs_lcs.h ----
     def flowmap_create(self, box=None, refine=1):
         """A device lattice for FluidSimulator.flow_map: refine x refine nodes per cell of the cell box (x0, y0, x1, y1) (None: the whole
@@ -947,6 +1031,43 @@ class NativeRideOps:
     def _p_pod_free(self, h):
         if self._ctx is not None:
             _lib.call("fs_pod_free", self._ctx, h)
+
+    def _p_vortex_create(self, which, threshold, exponent, every, start, min_area, max_vortices, max_components, capacity):
+        h = ctypes.c_void_p()
+        _lib.call("fs_vortex_create", self._ctx, which, threshold, float(np.ldexp(1.0, 30 - exponent)), every, start, min_area, max_vortices,
+                  max_components, capacity, ctypes.byref(h))
+        return h
+
+    def _p_vortex_read(self, h, capacity, words):
+        out = np.empty((capacity, words), np.int64)
+        n, launches, lost = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_longlong()
+        _lib.call("fs_vortex_read", self._ctx, h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), capacity, ctypes.byref(n),
+                  ctypes.byref(launches), ctypes.byref(lost))
+        return out[:n.value].copy(), launches.value, lost.value
+
+    def _p_vortex_get_labels(self, h):
+        flags, labels = np.empty((self.ny, self.nx), np.uint8), np.empty((self.ny, self.nx), np.int32)      # (the library's layout: x contiguous)
+        _lib.call("fs_vortex_get_labels", self._ctx, h, flags.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)),
+                  labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+        return np.ascontiguousarray(flags.T), np.ascontiguousarray(labels.T)
+
+    def _p_vortex_set(self, h, launches):
+        _lib.call("fs_vortex_set", self._ctx, h, launches)
+
+    def _p_vortex_label(self, flags):
+        f = np.ascontiguousarray(flags.T)
+        labels = np.empty((self.ny, self.nx), np.int32)
+        _lib.call("fs_vortex_label", self._ctx, f.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)), labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+        return np.ascontiguousarray(labels.T)
+
+    def _p_vortex_criterion(self, which, limit, dx, vh):
+        out = np.empty((self.ny, self.nx), np.float64)
+        _lib.call("fs_vortex_criterion", self._ctx, which, limit, dx, vh, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        return np.ascontiguousarray(out.T)
+
+    def _p_vortex_free(self, h):
+        if self._ctx is not None:
+            _lib.call("fs_vortex_free", self._ctx, h)
 
     def _p_flowmap_create(self, box, refine):
         h = ctypes.c_void_p()

@@ -29,6 +29,9 @@ The reference opens a GGUI window and steps forever; here the loop runs `--steps
   * give the particles inertia (`--tracer-tau T[,T2,...]`: response times that cycle over the particles as size classes, `--tracer-gravity
     gx,gy`), count where they hit the walls (`--tracer-deposits`) and accumulate the per-cell occupancy over the run on the GPU
     (`--tracer-accumulate-every K`, `--tracer-accumulate-start S`); all of it travels with `--save-state` / `--load-state`.
+  * identify and track the vortices (`--vortices-every N --vortex-threshold T`, `--vortex-criterion`, `--vortex-min-area`, `--vortex-max`):
+    criterion, connected components and per-vortex integer records on the GPU (csrc/fs_vortex.h), written with the track id of every
+    record to `--vortices-file` (.npz) at the end of the run; the samples travel with `--save-state` / `--load-state`
   * track the complete load on a body (`--body` with `--loads-every N`): pressure and viscous force, their moments about `--loads-center`,
     and the mean / rms pressure and wall shear of every face of the surface, gathered on the GPU and written to `--loads-file` (.npz) at
     the end of the run, with Cd, Cl, Cm, Cp and Cf when `--loads-ref U,L` gives the reference speed and length; the per-face sums and
@@ -163,6 +166,16 @@ def build_parser():
                    help="accumulate the per-cell particle count and age sum on the GPU after every K-th step (FluidSimulator.accumulate_tracers); "
                         "written as occupancy, accumulated_age_sum, samples with --tracer-fields (default 0: off)")
     p.add_argument("--tracer-accumulate-start", type=int, default=None, help="steps to skip before --tracer-accumulate-every samples (default 0)")
+    p.add_argument("--vortices-every", type=int, default=0, metavar="N",
+                   help="identify the vortices after every N-th step on the GPU (FluidSimulator.track_vortices; 0: off); needs --vortex-threshold")
+    p.add_argument("--vortex-threshold", type=float, default=None, metavar="T",
+                   help="a cell belongs to a vortex where the criterion exceeds T (1 / time^2): a fraction of (U / L)^2 of the scene")
+    p.add_argument("--vortex-criterion", choices=("q", "swirl", "vorticity"), default="q", help="the criterion field (default: q)")
+    p.add_argument("--vortex-min-area", type=int, default=4, metavar="A", help="components of fewer cells are not recorded (default 4)")
+    p.add_argument("--vortex-max", type=int, default=64, metavar="M", help="most records per sample, those of smallest label (default 64, at most 1024)")
+    p.add_argument("--vortex-link", type=float, default=4.0, metavar="D", help="reach of the tracking between two samples, cells (default 4)")
+    p.add_argument("--vortices-file", type=str, default=None,
+                   help=".npz of the vortices: the arrays of FluidSimulator.vortices and the track id of every record (default: <out>/vortices.npz)")
     p.add_argument("--loads-every", type=int, default=0,
                    help="track the loads on the --body after every N-th step on the GPU (FluidSimulator.track_body): pressure + viscous "
                         "force, moments, per-face pressure and wall shear statistics (0: off)")
@@ -255,6 +268,19 @@ def saved_loads(path):
     if "loads.sums" not in z.files:
         return None
     return (tuple(int(b) for b in z["loads.box"]), tuple(float(c) for c in z["loads.center"]), int(z["loads.every"]), int(z["loads.start"]))
+
+
+def saved_vortices(path):
+    """(criterion, threshold, every, min_area, max_vortices) of the vortex tracker a checkpoint holds, or None."""
+    z = np.load(_npz_path(path))
+    if "vortex.words" not in z.files:
+        return None
+    return (str(z["vortex.criterion"]), float(z["vortex.threshold"]), int(z["vortex.every"]), int(z["vortex.min_area"]), int(z["vortex.max_vortices"]))
+
+
+def _lib_error():
+    from fs._lib import FsError
+    return (FsError, ValueError)
 
 
 def load_loads(sim, path):
@@ -510,6 +536,14 @@ def main(argv=None):
         parser.error("--pressure multigrid needs an even -res (no coarse level otherwise)")
     if args.body is not None and args.stats_every <= 0 and args.history_every <= 0 and args.loads_every <= 0:
         parser.error("--body needs --stats-every N, --history-every N or --loads-every N")
+    if args.vortices_every < 0:
+        parser.error("--vortices-every must be >= 0")
+    if args.vortices_every > 0 and (args.vortex_threshold is None or not np.isfinite(args.vortex_threshold)):
+        parser.error("--vortices-every needs a finite --vortex-threshold T (1 / time^2)")
+    if args.vortices_every > 0 and not (1 <= args.vortex_max <= 1024 and args.vortex_min_area >= 1 and args.vortex_link >= 0.0):
+        parser.error("--vortex-max must be 1 .. 1024, --vortex-min-area >= 1 and --vortex-link >= 0")
+    if (args.vortex_threshold is not None or args.vortices_file) and args.vortices_every <= 0:
+        parser.error("--vortex-threshold and --vortices-file need --vortices-every N")
     if args.loads_every < 0 or args.loads_start < 0:
         parser.error("--loads-every and --loads-start must be >= 0")
     if (args.loads_start or args.loads_center or args.loads_ref or args.loads_file) and args.loads_every <= 0:
@@ -777,6 +811,42 @@ def main(argv=None):
         np.savez(str(loads_file), center=np.array(sim._tracker.centre), box=np.array(sim._tracker.box), re=np.array(args.reynolds_num),
                  dx=np.array(dx), dt=np.array(dt), every=np.array(args.loads_every), start=np.array(args.loads_start), **loads, **surf, **more)
 
+    vortices_file = None
+    if args.vortices_every > 0:
+        vortices_file = Path(args.vortices_file) if args.vortices_file else out / "vortices.npz"
+        try:
+            sim.track_vortices(args.vortex_threshold, criterion=args.vortex_criterion, every=args.vortices_every, min_area=args.vortex_min_area,
+                               max_vortices=args.vortex_max)
+        except _lib_error() as e:
+            print(f"--vortices-every: {e}", file=sys.stderr)
+            dev.close()
+            sys.exit(2)
+        if args.load_state:
+            held = saved_vortices(args.load_state)
+            vx = sim._vortexr.vx
+            mine = (vx.criterion, vx.threshold, vx.every, vx.min_area, vx.max_vortices)
+            if held is not None and held != mine:
+                print(f"--load-state {args.load_state}: its vortices were tracked with --vortex-criterion {held[0]} --vortex-threshold {held[1]!r} "
+                      f"--vortices-every {held[2]} --vortex-min-area {held[3]} --vortex-max {held[4]}; continue with those or track without the "
+                      "checkpoint's samples", file=sys.stderr)
+                dev.close()
+                sys.exit(2)
+            if held is not None:
+                sim._vortexr.restore(np.load(_npz_path(args.load_state)))
+                print(f"vortices: continuing the checkpoint's ({len(sim._vortexr._words[0]) if sim._vortexr._words else 0} samples so far)")
+
+    def write_vortices():
+        if vortices_file is None:
+            return
+        from fs.vortices import link
+        data = sim.vortices()
+        raw = data.pop("raw")
+        tracks = link(data, args.vortex_link)
+        vortices_file.parent.mkdir(parents=True, exist_ok=True)
+        np.savez(str(vortices_file), track=tracks, dx=np.array(dx), dt=np.array(dt), every=np.array(args.vortices_every),
+                 threshold=np.array(args.vortex_threshold), criterion=np.array(args.vortex_criterion), **{f"raw_{k}": a for k, a in raw.items()},
+                 **data)
+
     tracer_file = None
     if tracing:
         tracer_file = Path(args.tracer_file) if args.tracer_file else out / "tracers.npz"
@@ -832,6 +902,7 @@ def main(argv=None):
             write_pod()
             write_ftle()
             write_loads()
+            write_vortices()
             if tracer_file is not None:
                 write_tracers(tracer_file, fields_file, step)
             dev.close()
@@ -877,6 +948,7 @@ def main(argv=None):
     write_pod()
     write_ftle()
     write_loads()
+    write_vortices()
     if tracer_file is not None:
         write_tracers(tracer_file, fields_file, step0 + args.steps)
     dev.close()

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 22
+#define FS_ABI_VERSION 23
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -463,6 +463,42 @@ int fs_flowmap_cauchy_green(fs_ctx *ctx, fs_flowmap *fm);
 int fs_flowmap_get(fs_ctx *ctx, fs_flowmap *fm, double *x, double *y, int *status, double *lam);
 int fs_flowmap_reset(fs_ctx *ctx, fs_flowmap *fm);
 int fs_flowmap_free(fs_ctx *ctx, fs_flowmap *fm);
+
+/* Vortex identification (new, ABI 23): a criterion field of the velocity gradient, its 4-connected components of equal rotation sense labelled
+ * on the device in a fixed number of launches, and one record of INTEGER sums per component appended to a ring of samples (kernels, operation
+ * order, accumulator layout and bounds: csrc/fs_vortex.h).  Planes are [Y][X] with x contiguous; a label is the smallest j * X + i of the
+ * component, -1 on a cell without a flag.  Single-GPU contexts: create, label and criterion return FS_ERR_UNSUPPORTED on a slab context.
+ * create:  criterion 0 "q", 1 "swirl", 2 "vorticity"; threshold finite, in 1 / time^2; scale = 2^(30 - e) > 0 with e = ceil(log2(omega_max)):
+ *          q = llrint(om * scale) clamped to +-2^30; every >= 1, start >= 0 (the sampling rule of fs_mean_create); min_area >= 1;
+ *          1 <= max_vortices <= FS_VORTEX_MAX_VORTICES; max_components >= 1; capacity >= 1 samples of FS_VORTEX_NHEAD + FS_VORTEX_NREC *
+ *          max_vortices long long words.  9 bytes per cell, 8 FS_VORTEX_NACC max_components for the table, and the ring.
+ * launch:  nine launches behind the step, nothing else (no allocation, copy or synchronisation: capturable); all of them return at once
+ *          unless this launch samples and the ring has room.  limit > 0: v still owes limit_field(limit).  A sampling launch that finds the
+ *          ring full counts as lost.
+ * read:    synchronises; copies the n samples of the ring (at most max_samples, else FS_ERR_ARG) to `out`, empties the ring, and returns the
+ *          launch count and the samples lost since the last read.  Sample: {launch index (from 0), components, passed, count, clipped,
+ *          dropped cells, 0, 0}, then `count` records {label, area, sum q, sum |q|, sum (2i+1), sum (2j+1), sum |q|(2i+1) low 32 bits / the
+ *          rest, the same for |q|(2j+1), min i, max i, min j, max j, peak, flag of the root}; the words behind them are undefined.
+ * get_labels: the flag and label planes of the last sampling launch (zeros / undefined before the first); either may be NULL.
+ * set:     the launch count (resume; the ring is empty).
+ * label:   the labels of a caller's flag plane (host memory, any non-zero byte is a flag; cells join when their bytes are equal).
+ * criterion: the criterion field as doubles, 0 on cells that are not fluid.  Needs the mask.
+ * free:    as fs_mean_free (during a capture the release is deferred to its end).
+ * Everything but launch and free returns FS_ERR_STATE during graph capture / tape recording.                                             */
+#define FS_VORTEX_NACC 15
+#define FS_VORTEX_NREC 16
+#define FS_VORTEX_NHEAD 8
+#define FS_VORTEX_MAX_VORTICES 1024
+typedef struct fs_vortex fs_vortex;
+int fs_vortex_create(fs_ctx *ctx, int criterion, double threshold, double scale, long long every, long long start, int min_area, int max_vortices,
+                     int max_components, int capacity, fs_vortex **out);
+int fs_vortex_launch(fs_ctx *ctx, fs_vortex *vx, double limit, double dx, const fs_field *v);
+int fs_vortex_read(fs_ctx *ctx, fs_vortex *vx, long long *out, int max_samples, int *n_out, long long *launches, long long *lost);
+int fs_vortex_get_labels(fs_ctx *ctx, fs_vortex *vx, unsigned char *flags, int *labels);
+int fs_vortex_set(fs_ctx *ctx, fs_vortex *vx, long long launches);
+int fs_vortex_label(fs_ctx *ctx, const unsigned char *flags, int *labels);
+int fs_vortex_criterion(fs_ctx *ctx, int which, double limit, double dx, const fs_field *v, double *out);
+int fs_vortex_free(fs_ctx *ctx, fs_vortex *vx);
 
 /* Multigrid pressure correction (new, ABI 19): one W-cycle (two coarse visits per level) on a mask-aware hierarchy of coarse levels, for the
  * third pressure updater (fs/pressure_updater.py MultigridPressureUpdater; kernels and operation order: csrc/fs_mg.h).  Single-GPU contexts.
