@@ -7,11 +7,13 @@ against the float64 sum over the downloaded snapshots below, at and past the 8-s
 The grids are the smallest at which the kernels can go wrong: scene 1 at res 20; a random mask at (37, 12) - odd X, the one-column path;
 (1030, 8) - beyond two 256 x 2 column blocks with a partial last one; (102, 13) with FS_DIAG_WGS=1 - 8 rows per workgroup of the capture, so
 the second workgroup ends in a partial row group, and the Gram kernel's 64 rows in one workgroup (on the others both take 4 rows per
-workgroup: 2 to 5 workgroups down the grid).
+workgroup: 2 to 5 workgroups down the grid).  The Gram matrix alone also on (1030, 262), 269,860 cells, with uploaded snapshots: at the default
+floor 4 rows per workgroup, 5 x 66 = 330 workgroups with a last one of 2 rows, so that k_pod_gram_final folds a second, partial round of
+partials (nblocks > 256); with FS_DIAG_WGS=85 16 rows per workgroup, 17 workgroups down the grid, the last of 6 rows.
 
 Gram tolerance (set by the issue that introduced the feature): |G[a][b] - G_numpy[a][b]| <= 1e-12 sqrt(G[a][a] G[b][b]) - the tolerance
 tests/flow_stats_ref.py gives the same kind of reduction: column chains of at most a few hundred terms followed by trees, and the sum of |t|
-is at most sqrt(G_aa G_bb)."""
+is at most sqrt(G_aa G_bb).  (On the tall grid the column chains are 4 or 16 terms: the same argument.)"""
 import ctypes
 import functools
 import os
@@ -224,6 +226,55 @@ def test_gram_against_numpy_around_the_tile(grid, dtype, hip_lib, monkeypatch):
                 assert np.array_equal(G, again), "two calls return different bits"
         slots = dev.pod_get(pod)[0]
         assert np.array_equal(slots[:, :2], np.array(ups)), "the slots differ from the masked uploads"
+        dev.pod_free(pod)
+    finally:
+        dev.close()
+
+
+# ---- the Gram matrix on the tall grid: a second round of k_pod_gram_final, several workgroups of 16 rows with a short last one ---------------
+TALL = (1030, 262, 0.15)
+TALL_N = (7, 9, 17)      # one tile; two tiles; three tiles with all three off-diagonal pairs
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+@pytest.mark.parametrize("rows", [4, 16])
+def test_gram_on_the_tall_grid(rows, dtype, hip_lib, monkeypatch):
+    """rows = 4 (the default floor of 2048 workgroups): 5 x 66 = 330 workgroups, the last of 2 rows - k_pod_gram_final's lanes 0 .. 73 fold
+    a second partial, the others one.  rows = 16 (FS_DIAG_WGS = 85): 5 x 17 workgroups, the last of 6 rows."""
+    from fs.runtime import Device
+    from helpers import diag_floor
+    from multigrid_cases import scene
+    X, Y, wall_p = TALL
+    if rows == 4:
+        monkeypatch.delenv("FS_DIAG_WGS", raising=False)
+    else:
+        monkeypatch.setenv("FS_DIAG_WGS", str(diag_floor(-(-X // 256), Y, 4, rows)))
+    mask = np.array(scene(X, Y, wall_p)[1])
+    dt_ = np.float32 if dtype == "f32" else np.float64
+    rng = np.random.default_rng(X * 1000 + Y)
+    dev = Device(X, Y, dtype)
+    try:
+        # the Gram kernel's rows: diag_rows (csrc/fs_launch.h) with nx = ceil(X / 256), ny = Y, from 4 up to 64; flow_stats is the same rule
+        # with the same inputs from 4 up to 32, and both stop at 4 or 16 here
+        assert dev.diag_rows()["flow_stats"] == rows, "the Gram kernel does not take the rows this case is about"
+        assert (-(-X // 256) * -(-Y // rows) > 256) == (rows == 4)
+        dev.upload_scene(mask, np.zeros((X, Y, 2), dt_))
+        v, p = dev.alloc(2), dev.alloc(1)
+        pod = dev.pod_create(max(TALL_N))
+        wall = mask == 1
+        p.from_numpy(np.zeros((X, Y), dt_))
+        ups = []
+        for n in range(1, max(TALL_N) + 1):
+            va = (rng.standard_normal((X, Y, 2)) * (0.1 + 3.0 * rng.random())).astype(dt_)
+            v.from_numpy(va)
+            dev.pod_launch(pod, v, p)
+            ups.append(np.stack([np.where(wall, 0, va[..., 0]), np.where(wall, 0, va[..., 1])]))
+            if n in TALL_N:
+                G, launches, samples = dev.pod_gram(pod)
+                assert (launches, samples) == (n, n) and G.dtype == np.float64
+                _assert_gram(G, gram_ref(np.array(ups)), f"tall, {rows} rows, {dtype}")
+                again = dev.pod_gram(pod)[0]
+                assert np.array_equal(G, again), "two calls return different bits"
         dev.pod_free(pod)
     finally:
         dev.close()

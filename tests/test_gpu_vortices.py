@@ -9,7 +9,9 @@ Grids, by the geometry of the kernels (tiles of 32 x 8 cells in k_vortex_local, 
 per workgroup in the compression and id passes): scene 1 at res 20 (40 x 20); (37, 12) - odd X, a partial second tile each way; (1030, 8) -
 past four 256-column blocks and 32 tiles with a partial last one, one tile row, a 9th block of the id pass; (300, 70) - more than one tile and
 more than one block each way, neither extent a multiple of the tile, 21 blocks of the id pass; (102, 13) with FS_DIAG_WGS=1 - the flag pass
-takes all 13 rows in one workgroup: three full row groups and a partial one (on the others it takes 4 rows per workgroup)."""
+takes all 13 rows in one workgroup: three full row groups and a partial one (on the others it takes 4 rows per workgroup).  The forms the
+kernels take only on large grids - several blocks per lane of the scans, wrapped counter slots, sums near their bounds, 16 rows per
+workgroup of the flag pass, the full ring - are in tests/test_gpu_vortices_large.py on (1030, 262)."""
 import ctypes
 import functools
 import os
