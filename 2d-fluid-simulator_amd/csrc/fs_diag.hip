@@ -1,7 +1,7 @@
 // fs_diag.hip - C-ABI entry points of what reads the flow without changing it: the flow diagnostics (fs_stats.h), the per-step history ring
 // (fs_history.h), the body surface loads (fs_loads.h), the time averages (fs_mean.h), the harmonic modes (fs_modes.h), the snapshot POD
-// (fs_pod.h), the flow maps through its snapshots (fs_lcs.h) and the vortex identification (fs_vortex.h), with the release functions of their
-// objects.
+// (fs_pod.h), the flow maps through its snapshots (fs_lcs.h) and the vortex identification (fs_vortex.h).  Their objects live in the context's
+// registry (fs_host.h: FS_OBJECT, FS_HANDLE, FS_NO_CAPTURE, object_free).
 #include "fs_launch.h"
 #include "fs_stats.h"
 #include "fs_mean.h"
@@ -23,66 +23,28 @@ static_assert(fs::FM_LEFT == FS_TRACER_LEFT && fs::FM_WALL == FS_TRACER_WALL && 
 static_assert(fs::VX_NACC == FS_VORTEX_NACC && fs::VX_REC == FS_VORTEX_NREC && fs::VX_HEAD == FS_VORTEX_NHEAD && fs::VX_MAX_VORTICES == FS_VORTEX_MAX_VORTICES,
               "fs_vortex.h and include/fs_hip.h disagree");
 
-namespace fs {
-void history_release(fs_history *h)
-{
-    if (h->d_probes) hipFree(h->d_probes);
-    if (h->d_faces) hipFree(h->d_faces);
-    if (h->d_ring) hipFree(h->d_ring);
-    if (h->d_state) hipFree(h->d_state);
-    if (h->d_partial) hipFree(h->d_partial);
-    delete h;
-}
-void loads_release(fs_loads *l)
-{
-    if (l->d_faces) hipFree(l->d_faces);
-    if (l->d_sums) hipFree(l->d_sums);
-    if (l->d_ring) hipFree(l->d_ring);
-    if (l->d_state) hipFree(l->d_state);
-    if (l->d_partial) hipFree(l->d_partial);
-    delete l;
-}
-void mean_release(fs_mean *m)
-{
-    if (m->d_sums) hipFree(m->d_sums);
-    if (m->d_state) hipFree(m->d_state);
-    delete m;
-}
-void modes_release(fs_modes *m)
-{
-    if (m->d_sums) hipFree(m->d_sums);
-    if (m->d_state) hipFree(m->d_state);
-    if (m->d_scal) hipFree(m->d_scal);
-    delete m;
-}
-void pod_release(fs_pod *p)
-{
-    if (p->d_slots) hipFree(p->d_slots);
-    if (p->d_state) hipFree(p->d_state);
-    if (p->d_gram) hipFree(p->d_gram);
-    delete p;
-}
-void vortex_release(fs_vortex *x)
-{
-    if (x->d_flags) hipFree(x->d_flags);
-    if (x->d_labels) hipFree(x->d_labels);
-    if (x->d_ids) hipFree(x->d_ids);
-    if (x->d_counts) hipFree(x->d_counts);
-    if (x->d_table) hipFree(x->d_table);
-    if (x->d_tmp) hipFree(x->d_tmp);
-    if (x->d_ring) hipFree(x->d_ring);
-    if (x->d_state) hipFree(x->d_state);
-    delete x;
-}
-void flowmap_release(fs_flowmap *f)
-{
-    if (f->d_pos) hipFree(f->d_pos);
-    if (f->d_status) hipFree(f->d_status);
-    delete f;
-}
-}  // namespace fs
+FS_OBJECT(fs_history, OBJ_HISTORY, "history", "history from another context or freed");
+FS_OBJECT(fs_loads, OBJ_LOADS, "loads", "loads from another context or freed");
+FS_OBJECT(fs_mean, OBJ_MEAN, "mean", "mean from another context or freed");
+FS_OBJECT(fs_modes, OBJ_MODES, "modes", "modes from another context or freed");
+FS_OBJECT(fs_pod, OBJ_POD, "pod", "pod from another context or freed");
+FS_OBJECT(fs_vortex, OBJ_VORTEX, "vortex", "vortex tracker from another context or freed");
+FS_OBJECT(fs_flowmap, OBJ_FLOWMAP, "flow map", "flow map from another context or freed");
 
 using namespace fs;
+
+// `planes` planes of nyl rows, elements of `es` bytes: device rows of pitch P (planes `plane` elements apart) <-> dense host rows of X.  Queued on the
+// stream; the caller synchronises
+static int copy_planes(fs_ctx *ctx, int planes, size_t es, void *dev, size_t plane, void *host, hipMemcpyKind kind)
+{
+    const size_t dense = (size_t)ctx->nyl * ctx->X * es, wp = (size_t)ctx->P * es, wx = (size_t)ctx->X * es, ny = (size_t)ctx->nyl;
+    for (int k = 0; k < planes; ++k) {
+        char *d = (char *)dev + k * plane * es, *h = (char *)host + k * dense;
+        if (kind == hipMemcpyDeviceToHost) FS_HIP(hipMemcpy2DAsync(h, wx, d, wp, wx, ny, kind, ctx->stream));
+        else FS_HIP(hipMemcpy2DAsync(d, wp, h, wx, wx, ny, kind, ctx->stream));
+    }
+    return FS_OK;
+}
 
 extern "C" {
 
@@ -131,7 +93,7 @@ int fs_history_create(fs_ctx *ctx, int npoints, const int *points, int nfaces, c
     FS_REQUIRE(npoints >= 0 && nfaces >= 0 && (points || npoints == 0) && (faces || nfaces == 0), "bad point / face list");
     FS_REQUIRE(capacity >= 1 && every >= 1, "capacity and every must be >= 1");
     FS_REQUIRE((2 + 3 * (long long)npoints) * capacity < (1LL << 40), "ring too large");
-    if (ctx->capturing || ctx->tape_rec) { set_error("history create during graph capture / tape recording"); return FS_ERR_STATE; }
+    FS_NO_CAPTURE(fs_history, "create");
     // a probe / face outside the owned rows would read a ghost row (stale between exchanges) or count a face twice across slabs
     const int jo = ctx->y0, je = ctx->y0 + ctx->nyl;
     auto local = [&](int x, int y) -> long long { return (long long)(y - ctx->y0 + ctx->halo) * ctx->P + x; };      // row-major element of (x, y)
@@ -153,30 +115,29 @@ int fs_history_create(fs_ctx *ctx, int npoints, const int *points, int nfaces, c
         hf[k].dir = d;
     }
     FS_HIP(hipSetDevice(ctx->device));
-    fs_history *h = new fs_history();
-    h->ctx = ctx; h->np = npoints; h->nf = nfaces; h->cap = capacity; h->every = every;
+    auto h = std::make_unique<fs_history>();
+    h->np = npoints; h->nf = nfaces; h->cap = capacity; h->every = every;
     h->nparts = nfaces > HIST_SPLIT ? (nfaces + HIST_FACES_PER_WG - 1) / HIST_FACES_PER_WG : 0;
     const size_t ring = (size_t)capacity * (2 + 3 * (size_t)npoints) * sizeof(double);
-    hipError_t e = hipMalloc(&h->d_state, HIST_STATE * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc(&h->d_ring, ring);
-    if (e == hipSuccess && h->nparts) e = hipMalloc(&h->d_partial, 2 * (size_t)h->nparts * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&h->d_probes, std::max<size_t>(1, hp.size()) * sizeof(HistProbe));
-    if (e == hipSuccess) e = hipMalloc(&h->d_faces, std::max<size_t>(1, hf.size()) * sizeof(HistFace));
+    hipError_t e = h->d_state.alloc(HIST_STATE * sizeof(long long));
+    if (e == hipSuccess) e = h->d_ring.alloc(ring);
+    if (e == hipSuccess && h->nparts) e = h->d_partial.alloc(2 * (size_t)h->nparts * sizeof(double));
+    if (e == hipSuccess) e = h->d_probes.alloc(std::max<size_t>(1, hp.size()) * sizeof(HistProbe));
+    if (e == hipSuccess) e = h->d_faces.alloc(std::max<size_t>(1, hf.size()) * sizeof(HistFace));
     if (e == hipSuccess) e = hipMemsetAsync(h->d_state, 0, HIST_STATE * sizeof(long long), ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(h->d_ring, 0, ring, ctx->stream);
     if (e == hipSuccess && npoints) e = hipMemcpyAsync(h->d_probes, hp.data(), hp.size() * sizeof(HistProbe), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess && nfaces) e = hipMemcpyAsync(h->d_faces, hf.data(), hf.size() * sizeof(HistFace), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { history_release(h); return hip_fail(e, "fs_history_create", __FILE__, __LINE__); }
-    ctx->histories.insert(h);
-    *out = h;
+    if (e != hipSuccess) return hip_fail(e, "fs_history_create", __FILE__, __LINE__);
+    *out = adopt(ctx, std::move(h));
     return FS_OK;
 }
 
 int fs_history_record(fs_ctx *ctx, fs_history *h, double dx, double limit, const fs_field *v, const fs_field *p)
 {
     FS_REQUIRE(ctx && h, "null argument");
-    FS_REQUIRE(h->ctx == ctx && ctx->histories.count(h), "history from another context or freed");
+    FS_HANDLE(h);
     FS_FIELD(v, 2); FS_FIELD(p, 1);
     // everything the launch needs is in `h` and the fields: no allocation, copy or synchronisation here (the closure is captured / taped)
     const HistProbe *pr = h->d_probes;
@@ -198,12 +159,10 @@ int fs_history_record(fs_ctx *ctx, fs_history *h, double dx, double limit, const
 int fs_history_read(fs_ctx *ctx, fs_history *h, double *out, int max_records, int *n_records, long long *launches, int *dropped)
 {
     FS_REQUIRE(ctx && h && n_records, "null argument");
-    FS_REQUIRE(h->ctx == ctx && ctx->histories.count(h), "history from another context or freed");
-    if (ctx->capturing || ctx->tape_rec) { set_error("history read during graph capture / tape recording"); return FS_ERR_STATE; }
-    FS_HIP(hipSetDevice(ctx->device));
+    FS_HANDLE(h);
+    FS_NO_CAPTURE(fs_history, "read");
     long long st[HIST_STATE];
-    FS_HIP(hipMemcpyAsync(st, h->d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));
+    if (int rc = read_counters(ctx, h->d_state, st)) return rc;
     *n_records = (int)st[1];
     if (launches) *launches = st[0];
     if (dropped) *dropped = (int)st[2];
@@ -216,22 +175,9 @@ int fs_history_read(fs_ctx *ctx, fs_history *h, double *out, int max_records, in
     return FS_OK;
 }
 
-int fs_history_free(fs_ctx *ctx, fs_history *h)
-{
-    if (!h) return FS_OK;
-    FS_REQUIRE(ctx && h->ctx == ctx && ctx->histories.count(h), "history from another context or freed");
-    ctx->histories.erase(h);
-    if (ctx->capturing) { ctx->deferred_release.push_back([h] { history_release(h); }); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
-    hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
-    history_release(h);
-    return FS_OK;
-}
+int fs_history_free(fs_ctx *ctx, fs_history *h) { return object_free(ctx, h); }
 
 // ---- body surface loads (fs_loads.h) -----------------------------------------------------------------------------------------------------
-#define FS_LOADS_HANDLE(l) FS_REQUIRE((l)->ctx == ctx && ctx->loads.count(l), "loads from another context or freed")
-#define FS_LOADS_NO_CAPTURE(what) \
-    if (ctx->capturing || ctx->tape_rec) { set_error("loads " what " during graph capture / tape recording"); return FS_ERR_STATE; }
 
 int fs_loads_create(fs_ctx *ctx, int nfaces, const int *faces, const double *centre_xy, int capacity, long long every, long long start,
                     fs_loads **out)
@@ -240,7 +186,7 @@ int fs_loads_create(fs_ctx *ctx, int nfaces, const int *faces, const double *cen
     FS_REQUIRE(nfaces >= 1, "nfaces must be >= 1");
     FS_REQUIRE(capacity >= 1 && every >= 1 && start >= 0, "capacity and every must be >= 1 and start >= 0");
     FS_REQUIRE(std::isfinite(centre_xy[0]) && std::isfinite(centre_xy[1]), "the centre must be finite");
-    FS_LOADS_NO_CAPTURE("create")
+    FS_NO_CAPTURE(fs_loads, "create");
     // a face outside the owned rows would read a ghost row (stale between exchanges) or be counted twice across slabs
     const int jo = ctx->y0, je = ctx->y0 + ctx->nyl;
     const double cx = centre_xy[0], cy = centre_xy[1];
@@ -260,31 +206,30 @@ int fs_loads_create(fs_ctx *ctx, int nfaces, const int *faces, const double *cen
         lf[k].ry = ym - cy;
     }
     FS_HIP(hipSetDevice(ctx->device));
-    fs_loads *l = new fs_loads();
-    l->ctx = ctx; l->nf = nfaces; l->cap = capacity; l->every = every; l->start = start;
+    auto l = std::make_unique<fs_loads>();
+    l->nf = nfaces; l->cap = capacity; l->every = every; l->start = start;
     l->nparts = nfaces > LOADS_SPLIT ? (nfaces + LOADS_WG - 1) / LOADS_WG : 0;
     const size_t ring = (size_t)capacity * LOADS_REC * sizeof(double), sums = (size_t)LOADS_SUMS * nfaces * sizeof(double);
-    hipError_t e = hipMalloc(&l->d_state, LOADS_STATE * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc(&l->d_ring, ring);
-    if (e == hipSuccess) e = hipMalloc(&l->d_sums, sums);
-    if (e == hipSuccess && l->nparts) e = hipMalloc(&l->d_partial, (size_t)LOADS_REC * l->nparts * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&l->d_faces, lf.size() * sizeof(LoadFace));
+    hipError_t e = l->d_state.alloc(LOADS_STATE * sizeof(long long));
+    if (e == hipSuccess) e = l->d_ring.alloc(ring);
+    if (e == hipSuccess) e = l->d_sums.alloc(sums);
+    if (e == hipSuccess && l->nparts) e = l->d_partial.alloc((size_t)LOADS_REC * l->nparts * sizeof(double));
+    if (e == hipSuccess) e = l->d_faces.alloc(lf.size() * sizeof(LoadFace));
     if (e == hipSuccess) e = hipMemsetAsync(l->d_state, 0, LOADS_STATE * sizeof(long long), ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(l->d_ring, 0, ring, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(l->d_sums, 0, sums, ctx->stream);
     if (e == hipSuccess && l->nparts) e = hipMemsetAsync(l->d_partial, 0, (size_t)LOADS_REC * l->nparts * sizeof(double), ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(l->d_faces, lf.data(), lf.size() * sizeof(LoadFace), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { loads_release(l); return hip_fail(e, "fs_loads_create", __FILE__, __LINE__); }
-    ctx->loads.insert(l);
-    *out = l;
+    if (e != hipSuccess) return hip_fail(e, "fs_loads_create", __FILE__, __LINE__);
+    *out = adopt(ctx, std::move(l));
     return FS_OK;
 }
 
 int fs_loads_record(fs_ctx *ctx, fs_loads *l, double dx, double inv_re, double limit, const fs_field *v, const fs_field *p)
 {
     FS_REQUIRE(ctx && l, "null argument");
-    FS_LOADS_HANDLE(l);
+    FS_HANDLE(l);
     FS_FIELD(v, 2); FS_FIELD(p, 1);
     // everything the launches need is in `l` and the fields: no allocation, copy or synchronisation here (the closure is captured / taped)
     const LoadFace *fc = l->d_faces;
@@ -311,12 +256,10 @@ int fs_loads_read(fs_ctx *ctx, fs_loads *l, double *ring_out, int max_records, i
                   int *dropped)
 {
     FS_REQUIRE(ctx && l && n_records, "null argument");
-    FS_LOADS_HANDLE(l);
-    FS_LOADS_NO_CAPTURE("read")
-    FS_HIP(hipSetDevice(ctx->device));
+    FS_HANDLE(l);
+    FS_NO_CAPTURE(fs_loads, "read");
     long long st[LOADS_STATE];
-    FS_HIP(hipMemcpyAsync(st, l->d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));
+    if (int rc = read_counters(ctx, l->d_state, st)) return rc;
     *n_records = (int)st[2];
     if (launches) *launches = st[0];
     if (samples) *samples = st[1];
@@ -333,8 +276,8 @@ int fs_loads_read(fs_ctx *ctx, fs_loads *l, double *ring_out, int max_records, i
 int fs_loads_sums_read(fs_ctx *ctx, fs_loads *l, double *sums_out)
 {
     FS_REQUIRE(ctx && l && sums_out, "null argument");
-    FS_LOADS_HANDLE(l);
-    FS_LOADS_NO_CAPTURE("sums_read")
+    FS_HANDLE(l);
+    FS_NO_CAPTURE(fs_loads, "sums_read");
     FS_HIP(hipSetDevice(ctx->device));
     FS_HIP(hipMemcpyAsync(sums_out, l->d_sums, (size_t)LOADS_SUMS * l->nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     FS_HIP(hipStreamSynchronize(ctx->stream));
@@ -344,9 +287,9 @@ int fs_loads_sums_read(fs_ctx *ctx, fs_loads *l, double *sums_out)
 int fs_loads_sums_write(fs_ctx *ctx, fs_loads *l, const double *sums_in, long long launches, long long samples)
 {
     FS_REQUIRE(ctx && l && sums_in, "null argument");
-    FS_LOADS_HANDLE(l);
-    FS_REQUIRE(launches >= 0 && samples >= 0 && samples <= launches, "counters must satisfy 0 <= samples <= launches");
-    FS_LOADS_NO_CAPTURE("sums_write")
+    FS_HANDLE(l);
+    FS_COUNTERS(launches, samples);
+    FS_NO_CAPTURE(fs_loads, "sums_write");
     FS_HIP(hipSetDevice(ctx->device));
     const long long st[2] = {launches, samples};
     FS_HIP(hipMemcpyAsync(l->d_sums, sums_in, (size_t)LOADS_SUMS * l->nf * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -358,30 +301,17 @@ int fs_loads_sums_write(fs_ctx *ctx, fs_loads *l, const double *sums_in, long lo
 int fs_loads_reset(fs_ctx *ctx, fs_loads *l)
 {
     FS_REQUIRE(ctx && l, "null argument");
-    FS_LOADS_HANDLE(l);
-    FS_LOADS_NO_CAPTURE("reset")
+    FS_HANDLE(l);
+    FS_NO_CAPTURE(fs_loads, "reset");
     FS_HIP(hipSetDevice(ctx->device));
     FS_HIP(hipMemsetAsync(l->d_sums, 0, (size_t)LOADS_SUMS * l->nf * sizeof(double), ctx->stream));
     FS_HIP(hipMemsetAsync(l->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
     return FS_OK;
 }
 
-int fs_loads_free(fs_ctx *ctx, fs_loads *l)
-{
-    if (!l) return FS_OK;
-    FS_REQUIRE(ctx && l->ctx == ctx && ctx->loads.count(l), "loads from another context or freed");
-    ctx->loads.erase(l);
-    if (ctx->capturing) { ctx->deferred_release.push_back([l] { loads_release(l); }); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
-    hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
-    loads_release(l);
-    return FS_OK;
-}
+int fs_loads_free(fs_ctx *ctx, fs_loads *l) { return object_free(ctx, l); }
 
 // ---- time averages (fs_mean.h) ---------------------------------------------------------------------------------------------------------
-#define FS_MEAN_HANDLE(m) FS_REQUIRE((m)->ctx == ctx && ctx->means.count(m), "mean from another context or freed")
-#define FS_MEAN_NO_CAPTURE(what) \
-    if (ctx->capturing || ctx->tape_rec) { set_error("mean " what " during graph capture / tape recording"); return FS_ERR_STATE; }
 
 // workgroups of 256 lanes x `w` columns and `rpw` rows over the owned rows: rows per workgroup from `g0` up to MEAN_ROWS (fs_launch.h
 // diag_rows) - a non-sampling launch is a counter read per workgroup, so the grid stays in the thousands
@@ -407,28 +337,27 @@ int fs_diag_rows(fs_ctx *ctx, int *flow_stats_rows, int *mean_accumulate_rows, i
 int fs_mean_create(fs_ctx *ctx, long long every, long long start, fs_mean **out)
 {
     FS_REQUIRE(ctx && out, "null argument");
-    FS_REQUIRE(every >= 1 && start >= 0, "every must be >= 1 and start >= 0");
-    FS_MEAN_NO_CAPTURE("create")
+    FS_EVERY_START(every, start);
+    FS_NO_CAPTURE(fs_mean, "create");
     FS_HIP(hipSetDevice(ctx->device));
-    fs_mean *m = new fs_mean();
-    m->ctx = ctx; m->every = every; m->start = start;
+    auto m = std::make_unique<fs_mean>();
+    m->every = every; m->start = start;
     m->plane = (size_t)ctx->nyl * ctx->P + MEAN_PAD;
     const size_t bytes = MEAN_PLANES * m->plane * sizeof(double);
-    hipError_t e = hipMalloc(&m->d_state, MEAN_STATE * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc(&m->d_sums, bytes);
+    hipError_t e = m->d_state.alloc(MEAN_STATE * sizeof(long long));
+    if (e == hipSuccess) e = m->d_sums.alloc(bytes);
     if (e == hipSuccess) e = hipMemsetAsync(m->d_state, 0, MEAN_STATE * sizeof(long long), ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(m->d_sums, 0, bytes, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { mean_release(m); return hip_fail(e, "fs_mean_create", __FILE__, __LINE__); }
-    ctx->means.insert(m);
-    *out = m;
+    if (e != hipSuccess) return hip_fail(e, "fs_mean_create", __FILE__, __LINE__);
+    *out = adopt(ctx, std::move(m));
     return FS_OK;
 }
 
 int fs_mean_accumulate(fs_ctx *ctx, fs_mean *m, double limit, const fs_field *v, const fs_field *p)
 {
     FS_REQUIRE(ctx && m, "null argument");
-    FS_MEAN_HANDLE(m);
+    FS_HANDLE(m);
     FS_FIELD(v, 2); FS_FIELD(p, 1);
     if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
     // everything the launches need is in `m` and the fields: no allocation, copy or synchronisation here (the closure is captured / taped)
@@ -451,23 +380,15 @@ int fs_mean_accumulate(fs_ctx *ctx, fs_mean *m, double limit, const fs_field *v,
     });
 }
 
-static int mean_counters(fs_ctx *ctx, fs_mean *m, long long *st)
-{
-    FS_HIP(hipSetDevice(ctx->device));
-    FS_HIP(hipMemcpyAsync(st, m->d_state, MEAN_STATE * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    return FS_OK;
-}
-
 int fs_mean_finalize(fs_ctx *ctx, fs_mean *m, fs_field *v_out, fs_field *p_out)
 {
     FS_REQUIRE(ctx && m, "null argument");
-    FS_MEAN_HANDLE(m);
+    FS_HANDLE(m);
     FS_FIELD(v_out, 2); FS_FIELD(p_out, 1);
-    FS_MEAN_NO_CAPTURE("finalize")
+    FS_NO_CAPTURE(fs_mean, "finalize");
     if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
     long long st[MEAN_STATE];
-    if (int rc = mean_counters(ctx, m, st)) return rc;
+    if (int rc = read_counters(ctx, m->d_state, st)) return rc;
     if (st[1] < 1) { set_error("mean finalize: no sample accumulated yet"); return FS_ERR_STATE; }
     const int jb = ctx->halo, je = ctx->halo + ctx->nyl, w = mean_width(ctx);
     int rpw;
@@ -487,17 +408,14 @@ int fs_mean_finalize(fs_ctx *ctx, fs_mean *m, fs_field *v_out, fs_field *p_out)
 int fs_mean_read(fs_ctx *ctx, fs_mean *m, double *sums_out, long long *launches, long long *samples)
 {
     FS_REQUIRE(ctx && m, "null argument");
-    FS_MEAN_HANDLE(m);
-    FS_MEAN_NO_CAPTURE("read")
+    FS_HANDLE(m);
+    FS_NO_CAPTURE(fs_mean, "read");
     long long st[MEAN_STATE];
-    if (int rc = mean_counters(ctx, m, st)) return rc;
+    if (int rc = read_counters(ctx, m->d_state, st)) return rc;
     if (launches) *launches = st[0];
     if (samples) *samples = st[1];
     if (!sums_out) return FS_OK;
-    // per plane: nyl device rows of pitch P -> dense rows of X
-    for (int k = 0; k < MEAN_PLANES; ++k)
-        FS_HIP(hipMemcpy2DAsync(sums_out + (size_t)k * ctx->nyl * ctx->X, (size_t)ctx->X * sizeof(double), m->d_sums + k * m->plane,
-                                (size_t)ctx->P * sizeof(double), (size_t)ctx->X * sizeof(double), (size_t)ctx->nyl, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = copy_planes(ctx, MEAN_PLANES, sizeof(double), m->d_sums, m->plane, sums_out, hipMemcpyDeviceToHost)) return rc;
     FS_HIP(hipStreamSynchronize(ctx->stream));
     return FS_OK;
 }
@@ -505,14 +423,12 @@ int fs_mean_read(fs_ctx *ctx, fs_mean *m, double *sums_out, long long *launches,
 int fs_mean_write(fs_ctx *ctx, fs_mean *m, const double *sums_in, long long launches, long long samples)
 {
     FS_REQUIRE(ctx && m && sums_in, "null argument");
-    FS_MEAN_HANDLE(m);
-    FS_REQUIRE(launches >= 0 && samples >= 0 && samples <= launches, "counters must satisfy 0 <= samples <= launches");
-    FS_MEAN_NO_CAPTURE("write")
+    FS_HANDLE(m);
+    FS_COUNTERS(launches, samples);
+    FS_NO_CAPTURE(fs_mean, "write");
     FS_HIP(hipSetDevice(ctx->device));
     const long long st[MEAN_STATE] = {launches, samples};
-    for (int k = 0; k < MEAN_PLANES; ++k)
-        FS_HIP(hipMemcpy2DAsync(m->d_sums + k * m->plane, (size_t)ctx->P * sizeof(double), sums_in + (size_t)k * ctx->nyl * ctx->X,
-                                (size_t)ctx->X * sizeof(double), (size_t)ctx->X * sizeof(double), (size_t)ctx->nyl, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = copy_planes(ctx, MEAN_PLANES, sizeof(double), m->d_sums, m->plane, const_cast<double *>(sums_in), hipMemcpyHostToDevice)) return rc;
     FS_HIP(hipMemcpyAsync(m->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
     FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
     return FS_OK;
@@ -521,30 +437,17 @@ int fs_mean_write(fs_ctx *ctx, fs_mean *m, const double *sums_in, long long laun
 int fs_mean_reset(fs_ctx *ctx, fs_mean *m)
 {
     FS_REQUIRE(ctx && m, "null argument");
-    FS_MEAN_HANDLE(m);
-    FS_MEAN_NO_CAPTURE("reset")
+    FS_HANDLE(m);
+    FS_NO_CAPTURE(fs_mean, "reset");
     FS_HIP(hipSetDevice(ctx->device));
     FS_HIP(hipMemsetAsync(m->d_sums, 0, MEAN_PLANES * m->plane * sizeof(double), ctx->stream));
     FS_HIP(hipMemsetAsync(m->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
     return FS_OK;
 }
 
-int fs_mean_free(fs_ctx *ctx, fs_mean *m)
-{
-    if (!m) return FS_OK;
-    FS_REQUIRE(ctx && m->ctx == ctx && ctx->means.count(m), "mean from another context or freed");
-    ctx->means.erase(m);
-    if (ctx->capturing) { ctx->deferred_release.push_back([m] { mean_release(m); }); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
-    hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
-    mean_release(m);
-    return FS_OK;
-}
+int fs_mean_free(fs_ctx *ctx, fs_mean *m) { return object_free(ctx, m); }
 
 // ---- harmonic flow modes (fs_modes.h) ----------------------------------------------------------------------------------------------------
-#define FS_MODES_HANDLE(m) FS_REQUIRE((m)->ctx == ctx && ctx->modes.count(m), "modes from another context or freed")
-#define FS_MODES_NO_CAPTURE(what) \
-    if (ctx->capturing || ctx->tape_rec) { set_error("modes " what " during graph capture / tape recording"); return FS_ERR_STATE; }
 
 // as mean_grid: rows per workgroup from `g0` up to `rmax` (fs_launch.h diag_rows)
 static dim3 modes_grid(const fs_ctx *ctx, int w, int g0, int rmax, int *rpw)
@@ -575,33 +478,32 @@ int fs_modes_create(fs_ctx *ctx, int nfreq, const double *cos_sin, long long eve
 {
     FS_REQUIRE(ctx && cos_sin && out, "null argument");
     FS_REQUIRE(nfreq >= 1 && nfreq <= MODES_MAX_FREQ, "nfreq must be 1 .. FS_MODES_MAX_FREQ");
-    FS_REQUIRE(every >= 1 && start >= 0, "every must be >= 1 and start >= 0");
-    FS_MODES_NO_CAPTURE("create")
+    FS_EVERY_START(every, start);
+    FS_NO_CAPTURE(fs_modes, "create");
     FS_HIP(hipSetDevice(ctx->device));
-    fs_modes *m = new fs_modes();
-    m->ctx = ctx; m->nfreq = nfreq; m->every = every; m->start = start;
+    auto m = std::make_unique<fs_modes>();
+    m->nfreq = nfreq; m->every = every; m->start = start;
     for (int k = 0; k < nfreq; ++k) { m->cd[k] = cos_sin[2 * k]; m->sd[k] = cos_sin[2 * k + 1]; }
     m->plane = (size_t)ctx->nyl * ctx->P + MEAN_PAD;
     const size_t bytes = 3 * (size_t)modes_basis(nfreq) * m->plane * sizeof(double);
     double sc[modes_scalars(MODES_MAX_FREQ)];
     modes_fresh_scalars(nfreq, sc);
-    hipError_t e = hipMalloc(&m->d_state, MODES_STATE * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc(&m->d_scal, modes_scalars(nfreq) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&m->d_sums, bytes);
+    hipError_t e = m->d_state.alloc(MODES_STATE * sizeof(long long));
+    if (e == hipSuccess) e = m->d_scal.alloc(modes_scalars(nfreq) * sizeof(double));
+    if (e == hipSuccess) e = m->d_sums.alloc(bytes);
     if (e == hipSuccess) e = hipMemsetAsync(m->d_state, 0, MODES_STATE * sizeof(long long), ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(m->d_scal, sc, modes_scalars(nfreq) * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(m->d_sums, 0, bytes, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { modes_release(m); return hip_fail(e, "fs_modes_create", __FILE__, __LINE__); }
-    ctx->modes.insert(m);
-    *out = m;
+    if (e != hipSuccess) return hip_fail(e, "fs_modes_create", __FILE__, __LINE__);
+    *out = adopt(ctx, std::move(m));
     return FS_OK;
 }
 
 int fs_modes_accumulate(fs_ctx *ctx, fs_modes *m, double limit, const fs_field *v, const fs_field *p)
 {
     FS_REQUIRE(ctx && m, "null argument");
-    FS_MODES_HANDLE(m);
+    FS_HANDLE(m);
     FS_FIELD(v, 2); FS_FIELD(p, 1);
     if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
     // everything the launches need is in `m` and the fields: no allocation, copy or synchronisation here (the closure is captured / taped)
@@ -629,9 +531,9 @@ int fs_modes_accumulate(fs_ctx *ctx, fs_modes *m, double limit, const fs_field *
 int fs_modes_combine(fs_ctx *ctx, fs_modes *m, const double *weights, fs_field *v_out, fs_field *p_out)
 {
     FS_REQUIRE(ctx && m && weights, "null argument");
-    FS_MODES_HANDLE(m);
+    FS_HANDLE(m);
     FS_FIELD(v_out, 2); FS_FIELD(p_out, 1);
-    FS_MODES_NO_CAPTURE("combine")
+    FS_NO_CAPTURE(fs_modes, "combine");
     if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
     const int jb = ctx->halo, je = ctx->halo + ctx->nyl, w = mean_width(ctx), B = modes_basis(m->nfreq);
     int rpw;
@@ -652,18 +554,15 @@ int fs_modes_combine(fs_ctx *ctx, fs_modes *m, const double *weights, fs_field *
 int fs_modes_read(fs_ctx *ctx, fs_modes *m, double *sums_out, double *scalars_out, long long *launches, long long *samples)
 {
     FS_REQUIRE(ctx && m, "null argument");
-    FS_MODES_HANDLE(m);
-    FS_MODES_NO_CAPTURE("read")
+    FS_HANDLE(m);
+    FS_NO_CAPTURE(fs_modes, "read");
     FS_HIP(hipSetDevice(ctx->device));
     long long st[MODES_STATE];
     FS_HIP(hipMemcpyAsync(st, m->d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
     if (scalars_out)
         FS_HIP(hipMemcpyAsync(scalars_out, m->d_scal, modes_scalars(m->nfreq) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    // per plane: nyl device rows of pitch P -> dense rows of X
     if (sums_out)
-        for (int k = 0; k < 3 * modes_basis(m->nfreq); ++k)
-            FS_HIP(hipMemcpy2DAsync(sums_out + (size_t)k * ctx->nyl * ctx->X, (size_t)ctx->X * sizeof(double), m->d_sums + k * m->plane,
-                                    (size_t)ctx->P * sizeof(double), (size_t)ctx->X * sizeof(double), (size_t)ctx->nyl, hipMemcpyDeviceToHost, ctx->stream));
+        if (int rc = copy_planes(ctx, 3 * modes_basis(m->nfreq), sizeof(double), m->d_sums, m->plane, sums_out, hipMemcpyDeviceToHost)) return rc;
     FS_HIP(hipStreamSynchronize(ctx->stream));
     if (launches) *launches = st[0];
     if (samples) *samples = st[1];
@@ -673,14 +572,12 @@ int fs_modes_read(fs_ctx *ctx, fs_modes *m, double *sums_out, double *scalars_ou
 int fs_modes_write(fs_ctx *ctx, fs_modes *m, const double *sums_in, const double *scalars_in, long long launches, long long samples)
 {
     FS_REQUIRE(ctx && m && sums_in && scalars_in, "null argument");
-    FS_MODES_HANDLE(m);
-    FS_REQUIRE(launches >= 0 && samples >= 0 && samples <= launches, "counters must satisfy 0 <= samples <= launches");
-    FS_MODES_NO_CAPTURE("write")
+    FS_HANDLE(m);
+    FS_COUNTERS(launches, samples);
+    FS_NO_CAPTURE(fs_modes, "write");
     FS_HIP(hipSetDevice(ctx->device));
     const long long st[MODES_STATE] = {launches, samples};
-    for (int k = 0; k < 3 * modes_basis(m->nfreq); ++k)
-        FS_HIP(hipMemcpy2DAsync(m->d_sums + k * m->plane, (size_t)ctx->P * sizeof(double), sums_in + (size_t)k * ctx->nyl * ctx->X,
-                                (size_t)ctx->X * sizeof(double), (size_t)ctx->X * sizeof(double), (size_t)ctx->nyl, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = copy_planes(ctx, 3 * modes_basis(m->nfreq), sizeof(double), m->d_sums, m->plane, const_cast<double *>(sums_in), hipMemcpyHostToDevice)) return rc;
     FS_HIP(hipMemcpyAsync(m->d_scal, scalars_in, modes_scalars(m->nfreq) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     FS_HIP(hipMemcpyAsync(m->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
     FS_HIP(hipStreamSynchronize(ctx->stream));      // (the sources are the caller's / this frame's memory)
@@ -690,8 +587,8 @@ int fs_modes_write(fs_ctx *ctx, fs_modes *m, const double *sums_in, const double
 int fs_modes_reset(fs_ctx *ctx, fs_modes *m)
 {
     FS_REQUIRE(ctx && m, "null argument");
-    FS_MODES_HANDLE(m);
-    FS_MODES_NO_CAPTURE("reset")
+    FS_HANDLE(m);
+    FS_NO_CAPTURE(fs_modes, "reset");
     FS_HIP(hipSetDevice(ctx->device));
     double sc[modes_scalars(MODES_MAX_FREQ)];
     modes_fresh_scalars(m->nfreq, sc);
@@ -702,22 +599,9 @@ int fs_modes_reset(fs_ctx *ctx, fs_modes *m)
     return FS_OK;
 }
 
-int fs_modes_free(fs_ctx *ctx, fs_modes *m)
-{
-    if (!m) return FS_OK;
-    FS_REQUIRE(ctx && m->ctx == ctx && ctx->modes.count(m), "modes from another context or freed");
-    ctx->modes.erase(m);
-    if (ctx->capturing) { ctx->deferred_release.push_back([m] { modes_release(m); }); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
-    hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
-    modes_release(m);
-    return FS_OK;
-}
+int fs_modes_free(fs_ctx *ctx, fs_modes *m) { return object_free(ctx, m); }
 
 // ---- snapshot POD (fs_pod.h) ---------------------------------------------------------------------------------------------------------------
-#define FS_POD_HANDLE(p) FS_REQUIRE((p)->ctx == ctx && ctx->pods.count(p), "pod from another context or freed")
-#define FS_POD_NO_CAPTURE(what) \
-    if (ctx->capturing || ctx->tape_rec) { set_error("pod " what " during graph capture / tape recording"); return FS_ERR_STATE; }
 
 static size_t pod_slot_bytes(const fs_ctx *ctx, const fs_pod *p) { return 3 * p->plane * ctx->esize; }
 
@@ -725,32 +609,31 @@ int fs_pod_create(fs_ctx *ctx, int M, long long every, long long start, fs_pod *
 {
     FS_REQUIRE(ctx && out, "null argument");
     FS_REQUIRE(M >= 2 && M <= POD_MAX, "M must be 2 .. FS_POD_MAX");
-    FS_REQUIRE(every >= 1 && start >= 0, "every must be >= 1 and start >= 0");
-    FS_POD_NO_CAPTURE("create")
+    FS_EVERY_START(every, start);
+    FS_NO_CAPTURE(fs_pod, "create");
     if (ctx->halo != 0 || ctx->nyl != ctx->Y) {
         set_error("snapshot POD needs a single-GPU context: on a slab the Gram matrix needs a rank-ordered reduction (not implemented)");
         return FS_ERR_UNSUPPORTED;
     }
     FS_HIP(hipSetDevice(ctx->device));
-    fs_pod *p = new fs_pod();
-    p->ctx = ctx; p->M = M; p->every = every; p->start = start;
+    auto p = std::make_unique<fs_pod>();
+    p->M = M; p->every = every; p->start = start;
     p->plane = (size_t)ctx->nyl * ctx->P + MEAN_PAD;
-    const size_t bytes = (size_t)M * pod_slot_bytes(ctx, p);
-    hipError_t e = hipMalloc(&p->d_state, POD_STATE * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc(&p->d_slots, bytes);
+    const size_t bytes = (size_t)M * pod_slot_bytes(ctx, p.get());
+    hipError_t e = p->d_state.alloc(POD_STATE * sizeof(long long));
+    if (e == hipSuccess) e = p->d_slots.alloc(bytes);
     if (e == hipSuccess) e = hipMemsetAsync(p->d_state, 0, POD_STATE * sizeof(long long), ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(p->d_slots, 0, bytes, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { pod_release(p); return hip_fail(e, "fs_pod_create", __FILE__, __LINE__); }
-    ctx->pods.insert(p);
-    *out = p;
+    if (e != hipSuccess) return hip_fail(e, "fs_pod_create", __FILE__, __LINE__);
+    *out = adopt(ctx, std::move(p));
     return FS_OK;
 }
 
 int fs_pod_launch(fs_ctx *ctx, fs_pod *pod, double limit, const fs_field *v, const fs_field *p)
 {
     FS_REQUIRE(ctx && pod, "null argument");
-    FS_POD_HANDLE(pod);
+    FS_HANDLE(pod);
     FS_FIELD(v, 2); FS_FIELD(p, 1);
     if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
     // everything the launches need is in `pod` and the fields: no allocation, copy or synchronisation here (the closure is captured / taped)
@@ -773,21 +656,13 @@ int fs_pod_launch(fs_ctx *ctx, fs_pod *pod, double limit, const fs_field *v, con
     });
 }
 
-static int pod_counters(fs_ctx *ctx, fs_pod *pod, long long *st)
-{
-    FS_HIP(hipSetDevice(ctx->device));
-    FS_HIP(hipMemcpyAsync(st, pod->d_state, POD_STATE * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    return FS_OK;
-}
-
 int fs_pod_read(fs_ctx *ctx, fs_pod *pod, long long *launches, long long *samples)
 {
     FS_REQUIRE(ctx && pod, "null argument");
-    FS_POD_HANDLE(pod);
-    FS_POD_NO_CAPTURE("read")
+    FS_HANDLE(pod);
+    FS_NO_CAPTURE(fs_pod, "read");
     long long st[POD_STATE];
-    if (int rc = pod_counters(ctx, pod, st)) return rc;
+    if (int rc = read_counters(ctx, pod->d_state, st)) return rc;
     if (launches) *launches = st[0];
     if (samples) *samples = st[1];
     return FS_OK;
@@ -796,10 +671,10 @@ int fs_pod_read(fs_ctx *ctx, fs_pod *pod, long long *launches, long long *sample
 int fs_pod_gram(fs_ctx *ctx, fs_pod *pod, double *out, int max_n, int *n_out, long long *launches, long long *samples)
 {
     FS_REQUIRE(ctx && pod && n_out, "null argument");
-    FS_POD_HANDLE(pod);
-    FS_POD_NO_CAPTURE("gram")
+    FS_HANDLE(pod);
+    FS_NO_CAPTURE(fs_pod, "gram");
     long long st[POD_STATE];
-    if (int rc = pod_counters(ctx, pod, st)) return rc;
+    if (int rc = read_counters(ctx, pod->d_state, st)) return rc;
     const int n = (int)std::min<long long>(st[1], pod->M);
     if (out) FS_REQUIRE(max_n >= n, "out holds fewer rows than there are resident samples");
     *n_out = n;
@@ -814,8 +689,8 @@ int fs_pod_gram(fs_ctx *ctx, fs_pod *pod, double *out, int max_n, int *n_out, lo
     const size_t nblocks = (size_t)nx * nby;
     const size_t need = (size_t)(nt + noff) * POD_TT * nblocks + (size_t)n * n;
     if (need > pod->gram_cap) {
-        if (pod->d_gram) { FS_HIP(hipFree(pod->d_gram)); pod->d_gram = nullptr; pod->gram_cap = 0; }      // (the stream is idle: pod_counters)
-        FS_HIP(hipMalloc(&pod->d_gram, need * sizeof(double)));
+        pod->gram_cap = 0;
+        FS_HIP(pod->d_gram.alloc(need * sizeof(double)));      // (frees the smaller one first; the stream is idle: read_counters)
         pod->gram_cap = need;
     }
     double *partial = pod->d_gram, *total = pod->d_gram + (size_t)(nt + noff) * POD_TT * nblocks;
@@ -839,9 +714,9 @@ int fs_pod_gram(fs_ctx *ctx, fs_pod *pod, double *out, int max_n, int *n_out, lo
 int fs_pod_combine(fs_ctx *ctx, fs_pod *pod, const double *weights, fs_field *v_out, fs_field *p_out)
 {
     FS_REQUIRE(ctx && pod && weights, "null argument");
-    FS_POD_HANDLE(pod);
+    FS_HANDLE(pod);
     FS_FIELD(v_out, 2); FS_FIELD(p_out, 1);
-    FS_POD_NO_CAPTURE("combine")
+    FS_NO_CAPTURE(fs_pod, "combine");
     if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
     const int jb = ctx->halo, je = ctx->halo + ctx->nyl, w = mean_width(ctx), M = pod->M;
     int rpw;
@@ -859,17 +734,13 @@ int fs_pod_combine(fs_ctx *ctx, fs_pod *pod, const double *weights, fs_field *v_
     });
 }
 
-// per plane: nyl device rows of pitch P <-> dense rows of X, in the field type
 int fs_pod_get(fs_ctx *ctx, fs_pod *pod, void *slots_out)
 {
     FS_REQUIRE(ctx && pod && slots_out, "null argument");
-    FS_POD_HANDLE(pod);
-    FS_POD_NO_CAPTURE("get")
+    FS_HANDLE(pod);
+    FS_NO_CAPTURE(fs_pod, "get");
     FS_HIP(hipSetDevice(ctx->device));
-    const size_t es = ctx->esize, dense = (size_t)ctx->nyl * ctx->X * es;
-    for (int k = 0; k < 3 * pod->M; ++k)
-        FS_HIP(hipMemcpy2DAsync((char *)slots_out + k * dense, (size_t)ctx->X * es, (const char *)pod->d_slots + k * pod->plane * es, (size_t)ctx->P * es,
-                                (size_t)ctx->X * es, (size_t)ctx->nyl, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = copy_planes(ctx, 3 * pod->M, ctx->esize, pod->d_slots, pod->plane, slots_out, hipMemcpyDeviceToHost)) return rc;
     FS_HIP(hipStreamSynchronize(ctx->stream));
     return FS_OK;
 }
@@ -877,15 +748,12 @@ int fs_pod_get(fs_ctx *ctx, fs_pod *pod, void *slots_out)
 int fs_pod_set(fs_ctx *ctx, fs_pod *pod, const void *slots_in, long long launches, long long samples)
 {
     FS_REQUIRE(ctx && pod && slots_in, "null argument");
-    FS_POD_HANDLE(pod);
-    FS_REQUIRE(launches >= 0 && samples >= 0 && samples <= launches, "counters must satisfy 0 <= samples <= launches");
-    FS_POD_NO_CAPTURE("set")
+    FS_HANDLE(pod);
+    FS_COUNTERS(launches, samples);
+    FS_NO_CAPTURE(fs_pod, "set");
     FS_HIP(hipSetDevice(ctx->device));
     const long long st[POD_STATE] = {launches, samples};
-    const size_t es = ctx->esize, dense = (size_t)ctx->nyl * ctx->X * es;
-    for (int k = 0; k < 3 * pod->M; ++k)
-        FS_HIP(hipMemcpy2DAsync((char *)pod->d_slots + k * pod->plane * es, (size_t)ctx->P * es, (const char *)slots_in + k * dense, (size_t)ctx->X * es,
-                                (size_t)ctx->X * es, (size_t)ctx->nyl, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = copy_planes(ctx, 3 * pod->M, ctx->esize, pod->d_slots, pod->plane, const_cast<void *>(slots_in), hipMemcpyHostToDevice)) return rc;
     FS_HIP(hipMemcpyAsync(pod->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
     FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
     return FS_OK;
@@ -894,30 +762,17 @@ int fs_pod_set(fs_ctx *ctx, fs_pod *pod, const void *slots_in, long long launche
 int fs_pod_reset(fs_ctx *ctx, fs_pod *pod)
 {
     FS_REQUIRE(ctx && pod, "null argument");
-    FS_POD_HANDLE(pod);
-    FS_POD_NO_CAPTURE("reset")
+    FS_HANDLE(pod);
+    FS_NO_CAPTURE(fs_pod, "reset");
     FS_HIP(hipSetDevice(ctx->device));
     FS_HIP(hipMemsetAsync(pod->d_slots, 0, (size_t)pod->M * pod_slot_bytes(ctx, pod), ctx->stream));
     FS_HIP(hipMemsetAsync(pod->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
     return FS_OK;
 }
 
-int fs_pod_free(fs_ctx *ctx, fs_pod *pod)
-{
-    if (!pod) return FS_OK;
-    FS_REQUIRE(ctx && pod->ctx == ctx && ctx->pods.count(pod), "pod from another context or freed");
-    ctx->pods.erase(pod);
-    if (ctx->capturing) { ctx->deferred_release.push_back([pod] { pod_release(pod); }); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
-    hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
-    pod_release(pod);
-    return FS_OK;
-}
+int fs_pod_free(fs_ctx *ctx, fs_pod *pod) { return object_free(ctx, pod); }
 
 // ---- vortex identification (fs_vortex.h) ----------------------------------------------------------------------------------------------------
-#define FS_VORTEX_HANDLE(x) FS_REQUIRE((x)->ctx == ctx && ctx->vortices.count(x), "vortex tracker from another context or freed")
-#define FS_VORTEX_NO_CAPTURE(what) \
-    if (ctx->capturing || ctx->tape_rec) { set_error("vortex " what " during graph capture / tape recording"); return FS_ERR_STATE; }
 #define FS_VORTEX_SINGLE_GPU() \
     if (ctx->halo != 0 || ctx->nyl != ctx->Y) { \
         set_error("vortex identification needs a single-GPU context: on a slab the components would have to be united across ranks (not implemented)"); \
@@ -955,29 +810,29 @@ int fs_vortex_create(fs_ctx *ctx, int criterion, double threshold, double scale,
     FS_REQUIRE(criterion >= 0 && criterion <= 2, "criterion must be 0 (q), 1 (swirl) or 2 (vorticity)");
     FS_REQUIRE(std::isfinite(threshold), "threshold must be finite");
     FS_REQUIRE(std::isfinite(scale) && scale > 0.0, "scale must be finite and positive");
-    FS_REQUIRE(every >= 1 && start >= 0, "every must be >= 1 and start >= 0");
+    FS_EVERY_START(every, start);
     FS_REQUIRE(min_area >= 1, "min_area must be >= 1");
     FS_REQUIRE(max_vortices >= 1 && max_vortices <= VX_MAX_VORTICES, "max_vortices must be 1 .. FS_VORTEX_MAX_VORTICES");
     FS_REQUIRE(max_components >= 1 && max_components <= (1 << 24), "max_components must be 1 .. 2^24");
     FS_REQUIRE(capacity >= 1, "capacity must be >= 1");
-    FS_VORTEX_NO_CAPTURE("create")
+    FS_NO_CAPTURE(fs_vortex, "create");
     FS_VORTEX_SINGLE_GPU()
     FS_HIP(hipSetDevice(ctx->device));
-    fs_vortex *x = new fs_vortex();
-    x->ctx = ctx; x->criterion = criterion; x->threshold = threshold; x->scale = scale; x->every = every; x->start = start;
+    auto x = std::make_unique<fs_vortex>();
+    x->criterion = criterion; x->threshold = threshold; x->scale = scale; x->every = every; x->start = start;
     x->min_area = min_area; x->maxv = max_vortices; x->maxc = max_components; x->cap = capacity;
     x->cells = ctx->X * ctx->Y;
     x->nblocks = (x->cells + VX_BLOCK - 1) / VX_BLOCK;
     x->words = VX_HEAD + VX_REC * max_vortices;
     const size_t n = (size_t)x->cells, table = (size_t)VX_NACC * max_components * sizeof(long long);
-    hipError_t e = hipMalloc(&x->d_state, VX_STATE * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc(&x->d_tmp, VX_TMP * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc(&x->d_flags, n);
-    if (e == hipSuccess) e = hipMalloc(&x->d_labels, n * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&x->d_ids, n * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&x->d_counts, (size_t)x->nblocks * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&x->d_table, table);
-    if (e == hipSuccess) e = hipMalloc(&x->d_ring, (size_t)capacity * x->words * sizeof(long long));
+    hipError_t e = x->d_state.alloc(VX_STATE * sizeof(long long));
+    if (e == hipSuccess) e = x->d_tmp.alloc(VX_TMP * sizeof(long long));
+    if (e == hipSuccess) e = x->d_flags.alloc(n);
+    if (e == hipSuccess) e = x->d_labels.alloc(n * sizeof(int));
+    if (e == hipSuccess) e = x->d_ids.alloc(n * sizeof(int));
+    if (e == hipSuccess) e = x->d_counts.alloc((size_t)x->nblocks * sizeof(int));
+    if (e == hipSuccess) e = x->d_table.alloc(table);
+    if (e == hipSuccess) e = x->d_ring.alloc((size_t)capacity * x->words * sizeof(long long));
     if (e == hipSuccess) e = hipMemsetAsync(x->d_state, 0, VX_STATE * sizeof(long long), ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(x->d_tmp, 0, VX_TMP * sizeof(long long), ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(x->d_flags, 0, n, ctx->stream);
@@ -986,61 +841,63 @@ int fs_vortex_create(fs_ctx *ctx, int criterion, double threshold, double scale,
     if (e == hipSuccess) e = hipMemsetAsync(x->d_table, 0, table, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(x->d_ring, 0, (size_t)capacity * x->words * sizeof(long long), ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { vortex_release(x); return hip_fail(e, "fs_vortex_create", __FILE__, __LINE__); }
-    ctx->vortices.insert(x);
-    *out = x;
+    if (e != hipSuccess) return hip_fail(e, "fs_vortex_create", __FILE__, __LINE__);
+    *out = adopt(ctx, std::move(x));
     return FS_OK;
 }
 
 int fs_vortex_launch(fs_ctx *ctx, fs_vortex *vx, double limit, double dx, const fs_field *v)
 {
     FS_REQUIRE(ctx && vx, "null argument");
-    FS_VORTEX_HANDLE(vx);
+    FS_HANDLE(vx);
     FS_FIELD(v, 2);
     if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
     // everything the launches need is in `vx` and the field: no allocation, copy or synchronisation here (the closure is captured / taped)
-    const fs_vortex x = *vx;
-    const VxWhen when{x.d_state, x.start, x.every, x.cap};
+    const int criterion = vx->criterion, min_area = vx->min_area, maxv = vx->maxv, maxc = vx->maxc, cap = vx->cap, cells = vx->cells, nblocks = vx->nblocks, words = vx->words;
+    const double threshold = vx->threshold, scale = vx->scale;
+    const long long every = vx->every, start = vx->start;
+    uint8_t *flags = vx->d_flags;
+    int *labels = vx->d_labels, *ids = vx->d_ids, *counts = vx->d_counts;
+    long long *table = vx->d_table, *tmp = vx->d_tmp, *ring = vx->d_ring, *state = vx->d_state;
+    const VxWhen when{state, start, every, cap};
     int rpw;
     const dim3 fgrid = vortex_flags_grid(ctx, &rpw);
     return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
         int rc = launch(ctx, "vortex_flags", [=] {
-            klaunch(k_vortex_flags<T, false>, fgrid, dim3(256), ctx->stream, ctx->grid(), ctx->Y, rpw, when, x.criterion, x.threshold, dx, limit,
-                    (const T *)v->d, x.d_flags, (double *)nullptr, x.d_table, x.maxc, x.d_tmp);
+            klaunch(k_vortex_flags<T, false>, fgrid, dim3(256), ctx->stream, ctx->grid(), ctx->Y, rpw, when, criterion, threshold, dx, limit,
+                    (const T *)v->d, flags, (double *)nullptr, table, maxc, tmp);
         });
         if (rc) return rc;
-        rc = vortex_label_launches(ctx, when, x.d_flags, x.d_labels, x.d_counts);
+        rc = vortex_label_launches(ctx, when, flags, labels, counts);
         if (rc) return rc;
-        rc = launch(ctx, "vortex_scan", [=] { klaunch(k_vortex_scan, dim3(1), dim3(256), ctx->stream, x.nblocks, when, x.d_counts, x.d_tmp); });
+        rc = launch(ctx, "vortex_scan", [=] { klaunch(k_vortex_scan, dim3(1), dim3(256), ctx->stream, nblocks, when, counts, tmp); });
         if (rc) return rc;
         rc = launch(ctx, "vortex_ids", [=] {
-            klaunch(k_vortex_ids, dim3(x.nblocks), dim3(256), ctx->stream, x.cells, when, x.maxc, (const int *)x.d_labels, (const int *)x.d_counts, x.d_ids,
-                    x.d_table);
+            klaunch(k_vortex_ids, dim3(nblocks), dim3(256), ctx->stream, cells, when, maxc, (const int *)labels, (const int *)counts, ids,
+                    table);
         });
         if (rc) return rc;
         rc = launch(ctx, "vortex_reduce", [=] {
-            klaunch(k_vortex_reduce<T>, dim3((x.cells + 255) / 256), dim3(256), ctx->stream, ctx->grid(), x.cells, when, dx, limit, x.scale, x.maxc,
-                    (const T *)v->d, (const uint8_t *)x.d_flags, (const int *)x.d_labels, (const int *)x.d_ids, x.d_table, x.d_tmp);
+            klaunch(k_vortex_reduce<T>, dim3((cells + 255) / 256), dim3(256), ctx->stream, ctx->grid(), cells, when, dx, limit, scale, maxc,
+                    (const T *)v->d, (const uint8_t *)flags, (const int *)labels, (const int *)ids, table, tmp);
         });
         if (rc) return rc;
         rc = launch(ctx, "vortex_records", [=] {
-            klaunch(k_vortex_records, dim3(1), dim3(1024), ctx->stream, when, x.maxc, x.min_area, x.maxv, x.words, (const uint8_t *)x.d_flags,
-                    (const long long *)x.d_table, (const long long *)x.d_tmp, x.d_ring);
+            klaunch(k_vortex_records, dim3(1), dim3(1024), ctx->stream, when, maxc, min_area, maxv, words, (const uint8_t *)flags,
+                    (const long long *)table, (const long long *)tmp, ring);
         });
         if (rc) return rc;
-        return launch(ctx, "vortex_tick", [=] { klaunch(k_vortex_tick, dim3(1), dim3(64), ctx->stream, x.start, x.every, x.cap, x.d_state); });
+        return launch(ctx, "vortex_tick", [=] { klaunch(k_vortex_tick, dim3(1), dim3(64), ctx->stream, start, every, cap, state); });
     });
 }
 
 int fs_vortex_read(fs_ctx *ctx, fs_vortex *vx, long long *out, int max_samples, int *n_out, long long *launches, long long *lost)
 {
     FS_REQUIRE(ctx && vx && n_out, "null argument");
-    FS_VORTEX_HANDLE(vx);
-    FS_VORTEX_NO_CAPTURE("read")
-    FS_HIP(hipSetDevice(ctx->device));
+    FS_HANDLE(vx);
+    FS_NO_CAPTURE(fs_vortex, "read");
     long long st[VX_STATE];
-    FS_HIP(hipMemcpyAsync(st, vx->d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));
+    if (int rc = read_counters(ctx, vx->d_state, st)) return rc;
     const int n = (int)st[1];
     FS_REQUIRE(n == 0 || (out && max_samples >= n), "out holds fewer samples than the ring");
     if (n) FS_HIP(hipMemcpyAsync(out, vx->d_ring, (size_t)n * vx->words * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
@@ -1055,8 +912,8 @@ int fs_vortex_read(fs_ctx *ctx, fs_vortex *vx, long long *out, int max_samples, 
 int fs_vortex_get_labels(fs_ctx *ctx, fs_vortex *vx, unsigned char *flags, int *labels)
 {
     FS_REQUIRE(ctx && vx, "null argument");
-    FS_VORTEX_HANDLE(vx);
-    FS_VORTEX_NO_CAPTURE("get_labels")
+    FS_HANDLE(vx);
+    FS_NO_CAPTURE(fs_vortex, "get_labels");
     FS_HIP(hipSetDevice(ctx->device));
     if (flags) FS_HIP(hipMemcpyAsync(flags, vx->d_flags, (size_t)vx->cells, hipMemcpyDeviceToHost, ctx->stream));
     if (labels) FS_HIP(hipMemcpyAsync(labels, vx->d_labels, (size_t)vx->cells * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -1067,9 +924,9 @@ int fs_vortex_get_labels(fs_ctx *ctx, fs_vortex *vx, unsigned char *flags, int *
 int fs_vortex_set(fs_ctx *ctx, fs_vortex *vx, long long launches)
 {
     FS_REQUIRE(ctx && vx, "null argument");
-    FS_VORTEX_HANDLE(vx);
+    FS_HANDLE(vx);
     FS_REQUIRE(launches >= 0, "launches must be >= 0");
-    FS_VORTEX_NO_CAPTURE("set")
+    FS_NO_CAPTURE(fs_vortex, "set");
     FS_HIP(hipSetDevice(ctx->device));
     const long long st[VX_STATE] = {launches, 0, 0, 0};
     FS_HIP(hipMemcpyAsync(vx->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
@@ -1080,7 +937,7 @@ int fs_vortex_set(fs_ctx *ctx, fs_vortex *vx, long long launches)
 int fs_vortex_label(fs_ctx *ctx, const unsigned char *flags, int *labels)
 {
     FS_REQUIRE(ctx && flags && labels, "null argument");
-    FS_VORTEX_NO_CAPTURE("label")
+    FS_NO_CAPTURE(fs_vortex, "label");
     FS_VORTEX_SINGLE_GPU()
     FS_HIP(hipSetDevice(ctx->device));
     const size_t n = (size_t)ctx->X * ctx->Y;
@@ -1108,7 +965,7 @@ int fs_vortex_criterion(fs_ctx *ctx, int which, double limit, double dx, const f
     FS_REQUIRE(ctx && out, "null argument");
     FS_REQUIRE(which >= 0 && which <= 2, "criterion must be 0 (q), 1 (swirl) or 2 (vorticity)");
     FS_FIELD(v, 2);
-    FS_VORTEX_NO_CAPTURE("criterion")
+    FS_NO_CAPTURE(fs_vortex, "criterion");
     FS_VORTEX_SINGLE_GPU()
     if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
     FS_HIP(hipSetDevice(ctx->device));
@@ -1132,22 +989,9 @@ int fs_vortex_criterion(fs_ctx *ctx, int which, double limit, double dx, const f
     return e == hipSuccess ? FS_OK : hip_fail(e, "fs_vortex_criterion", __FILE__, __LINE__);
 }
 
-int fs_vortex_free(fs_ctx *ctx, fs_vortex *vx)
-{
-    if (!vx) return FS_OK;
-    FS_REQUIRE(ctx && vx->ctx == ctx && ctx->vortices.count(vx), "vortex tracker from another context or freed");
-    ctx->vortices.erase(vx);
-    if (ctx->capturing) { ctx->deferred_release.push_back([vx] { vortex_release(vx); }); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
-    hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
-    vortex_release(vx);
-    return FS_OK;
-}
+int fs_vortex_free(fs_ctx *ctx, fs_vortex *vx) { return object_free(ctx, vx); }
 
 // ---- flow maps through the resident snapshots (fs_lcs.h) ----------------------------------------------------------------------------------
-#define FS_FLOWMAP_HANDLE(f) FS_REQUIRE((f)->ctx == ctx && ctx->flowmaps.count(f), "flow map from another context or freed")
-#define FS_FLOWMAP_NO_CAPTURE(what) \
-    if (ctx->capturing || ctx->tape_rec) { set_error("flow map " what " during graph capture / tape recording"); return FS_ERR_STATE; }
 
 static FlowMapDev flowmap_dev(const fs_flowmap *f)
 {
@@ -1171,36 +1015,35 @@ int fs_flowmap_create(fs_ctx *ctx, const int *box, int refine, fs_flowmap **out)
     FS_REQUIRE(refine == 1 || refine == 2 || refine == 4 || refine == 8, "refine must be 1, 2, 4 or 8");
     const long long nx = (long long)refine * (box[2] - box[0]), ny = (long long)refine * (box[3] - box[1]);
     FS_REQUIRE(nx * ny <= (1LL << 30), "flow map of more than 2^30 nodes");
-    FS_FLOWMAP_NO_CAPTURE("create")
+    FS_NO_CAPTURE(fs_flowmap, "create");
     if (ctx->comm || ctx->halo != 0 || ctx->y0 != 0 || ctx->nyl != ctx->Y) {
         set_error("flow maps need a single-GPU context: on a slab the particles would have to migrate between ranks (not implemented)");
         return FS_ERR_UNSUPPORTED;
     }
     if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
     FS_HIP(hipSetDevice(ctx->device));
-    fs_flowmap *f = new fs_flowmap();
-    f->ctx = ctx; f->r = refine; f->nx = (int)nx; f->ny = (int)ny;
+    auto f = std::make_unique<fs_flowmap>();
+    f->r = refine; f->nx = (int)nx; f->ny = (int)ny;
     for (int k = 0; k < 4; ++k) f->box[k] = box[k];
     const size_t n = (size_t)(nx * ny);
-    hipError_t e = hipMalloc(&f->d_pos, 3 * n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&f->d_status, n * sizeof(int));
-    if (e != hipSuccess) { flowmap_release(f); return hip_fail(e, "fs_flowmap_create", __FILE__, __LINE__); }
-    if (int rc = flowmap_seed(ctx, f)) { hipStreamSynchronize(ctx->stream); flowmap_release(f); return rc; }
-    ctx->flowmaps.insert(f);
-    *out = f;
+    hipError_t e = f->d_pos.alloc(3 * n * sizeof(double));
+    if (e == hipSuccess) e = f->d_status.alloc(n * sizeof(int));
+    if (e != hipSuccess) return hip_fail(e, "fs_flowmap_create", __FILE__, __LINE__);
+    if (int rc = flowmap_seed(ctx, f.get())) { hipStreamSynchronize(ctx->stream); return rc; }
+    *out = adopt(ctx, std::move(f));
     return FS_OK;
 }
 
 int fs_flowmap_advance(fs_ctx *ctx, fs_flowmap *fm, const fs_pod *pod, int slot_from, int slot_to, double h, int substeps)
 {
     FS_REQUIRE(ctx && fm && pod, "null argument");
-    FS_FLOWMAP_HANDLE(fm);
-    FS_REQUIRE(pod->ctx == ctx && ctx->pods.count(const_cast<fs_pod *>(pod)), "pod from another context or freed");
+    FS_HANDLE(fm);
+    FS_HANDLE(pod);
     FS_REQUIRE(0 <= slot_from && slot_from < pod->M && 0 <= slot_to && slot_to < pod->M, "slot outside 0 .. M - 1");
     FS_REQUIRE(slot_from != slot_to, "slot_from and slot_to must differ");
     FS_REQUIRE(substeps >= 1 && substeps <= FM_MAX_SUBSTEPS, "substeps must be 1 .. FS_FLOWMAP_MAX_SUBSTEPS");
     FS_REQUIRE(std::isfinite(h) && h != 0.0, "h must be finite and not 0");
-    FS_FLOWMAP_NO_CAPTURE("advance")
+    FS_NO_CAPTURE(fs_flowmap, "advance");
     const FlowMapDev fd = flowmap_dev(fm);
     const dim3 grid = flowmap_grid(fm);
     const int Y = ctx->Y;
@@ -1217,8 +1060,8 @@ int fs_flowmap_advance(fs_ctx *ctx, fs_flowmap *fm, const fs_pod *pod, int slot_
 int fs_flowmap_cauchy_green(fs_ctx *ctx, fs_flowmap *fm)
 {
     FS_REQUIRE(ctx && fm, "null argument");
-    FS_FLOWMAP_HANDLE(fm);
-    FS_FLOWMAP_NO_CAPTURE("cauchy_green")
+    FS_HANDLE(fm);
+    FS_NO_CAPTURE(fs_flowmap, "cauchy_green");
     const FlowMapDev fd = flowmap_dev(fm);
     const dim3 grid = flowmap_grid(fm);
     return launch(ctx, "flowmap_cauchy_green", [=] { klaunch(k_flowmap_cauchy_green, grid, dim3(FM_WG), ctx->stream, fd); });
@@ -1227,8 +1070,8 @@ int fs_flowmap_cauchy_green(fs_ctx *ctx, fs_flowmap *fm)
 int fs_flowmap_get(fs_ctx *ctx, fs_flowmap *fm, double *x, double *y, int *status, double *lam)
 {
     FS_REQUIRE(ctx && fm, "null argument");
-    FS_FLOWMAP_HANDLE(fm);
-    FS_FLOWMAP_NO_CAPTURE("get")
+    FS_HANDLE(fm);
+    FS_NO_CAPTURE(fs_flowmap, "get");
     FS_HIP(hipSetDevice(ctx->device));
     const size_t n = (size_t)fm->nx * fm->ny;
     double *const dst[3] = {x, y, lam};
@@ -1242,21 +1085,17 @@ int fs_flowmap_get(fs_ctx *ctx, fs_flowmap *fm, double *x, double *y, int *statu
 int fs_flowmap_reset(fs_ctx *ctx, fs_flowmap *fm)
 {
     FS_REQUIRE(ctx && fm, "null argument");
-    FS_FLOWMAP_HANDLE(fm);
-    FS_FLOWMAP_NO_CAPTURE("reset")
+    FS_HANDLE(fm);
+    FS_NO_CAPTURE(fs_flowmap, "reset");
     return flowmap_seed(ctx, fm);
 }
 
 int fs_flowmap_free(fs_ctx *ctx, fs_flowmap *fm)
 {
     if (!fm) return FS_OK;
-    FS_REQUIRE(ctx && fm->ctx == ctx && ctx->flowmaps.count(fm), "flow map from another context or freed");
-    FS_FLOWMAP_NO_CAPTURE("free")
-    ctx->flowmaps.erase(fm);
-    hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
-    flowmap_release(fm);
-    return FS_OK;
+    FS_HANDLE(fm);
+    FS_NO_CAPTURE(fs_flowmap, "free");      // (the one free that a capture refuses instead of deferring)
+    return object_free(ctx, fm);
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include <map>
 #include <set>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/fs_hip.h"
@@ -19,6 +20,7 @@
 #include "fs_jquad.h"
 #include "fs_k34n.h"
 #include "fs_history.h"
+#include "fs_objects.h"
 
 namespace fs {
 
@@ -38,6 +40,31 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
             return FS_ERR_ARG;                 \
         }                                      \
     } while (0)
+
+// Owner of one hipMalloc'd buffer: move-only, freed with whatever holds it.  It converts to the raw pointer, so kernel arguments, pointer
+// arithmetic and the copies read as before; an untyped buffer also casts to the element type of the field, `(T *)d_slots`, like a void *.
+template <typename T>
+class DevBuf {
+    T *p = nullptr;
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.release()) {}
+    DevBuf &operator=(DevBuf &&o) noexcept { reset(o.release()); return *this; }
+    ~DevBuf() { reset(); }
+    void reset(T *q = nullptr) { if (p) hipFree(p); p = q; }
+    T *release() { T *q = p; p = nullptr; return q; }      // hands the buffer out: the caller frees it
+    hipError_t alloc(size_t bytes)                         // (what it held is freed first)
+    {
+        reset();
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
+    T *get() const { return p; }
+    operator T *() const { return p; }
+    template <typename U, typename V = T, typename = std::enable_if_t<std::is_void<V>::value>>
+    explicit operator U *() const { return (U *)p; }
+};
 
 struct BcOpsDev {
     int nsimple = 0, npair = 0, ncomp = 0, nops = 0;
@@ -129,23 +156,7 @@ struct fs_ctx {
     // comm
     fs::Comm *comm = nullptr;
     std::set<fs_field *> fields;  // live fields, released with the context
-    std::set<fs_history *> histories;        // live history rings (fs_history_create), released with the context
-    std::set<fs_mean *> means;               // live time averages (fs_mean_create), released with the context
-    std::set<fs_modes *> modes;              // live harmonic-mode accumulators (fs_modes_create), released with the context
-    std::set<fs_pod *> pods;                 // live snapshot sets (fs_pod_create), released with the context
-    std::set<fs_vortex *> vortices;          // live vortex trackers (fs_vortex_create), released with the context
-    std::set<fs_flowmap *> flowmaps;         // live flow-map lattices (fs_flowmap_create), released with the context
-    std::set<fs_mg *> mgs;                   // live multigrid hierarchies (fs_mg_create), released with the context
-    std::set<fs_loads *> loads;              // live body trackers (fs_loads_create), released with the context
-    std::set<fs_tracer *> tracers;           // live tracer sets (fs_tracer_create), released with the context
-    // a *_free during a hipGraph capture (neither a synchronisation nor hipFree is legal there: either invalidates the capture) leaves its
-    // release here; fs_graph_end and fs_destroy run the list in the order of the calls
-    std::vector<std::function<void()>> deferred_release;
-    void release_deferred()
-    {
-        for (auto &release : deferred_release) release();
-        deferred_release.clear();
-    }
+    fs::Objects objects;          // every other live object (fs::ObjKind), released with the context; the releases a capture defers (fs_objects.h)
     // tuning knobs (env FS_MARCH=0: one-cell-per-lane kernels only)
     bool use_march = true;
     bool use_pairs = true;     // lanes of 2 cells: even widths (every `res`); use_march: the quad kernels, X % 4 == 0
@@ -177,135 +188,173 @@ struct fs_ctx {
     }
 };
 
+// d and hot stay raw pointers: every launch site of every unit hands them to a kernel by value.  The field owns both and frees them when deleted.
 struct fs_field {
     fs_ctx *ctx = nullptr;
     int C = 1;
     void *d = nullptr;
     size_t bytes = 0;
     unsigned *hot = nullptr;   // device words: [0] "may hold a speed above 9.95" (fs_device.h; meaningful for 2-channel fields), [1], [2] the same, raised by the op list of a k_velocity_bc_limit launch of parity 0 / 1
+    fs_field() = default;
+    fs_field(const fs_field &) = delete;
+    ~fs_field() { if (d) hipFree(d); if (hot) hipFree(hot); }
 };
 
 // per-step history ring (fs_history_*, fs_history.h): probe and face lists of this context's owned rows, the ring and its device counters
 struct fs_history {
-    fs_ctx *ctx = nullptr;
     int np = 0, nf = 0, cap = 0, every = 1, threads = 256;
     int nparts = 0;                 // workgroups of the split face sum (HIST_SPLIT; 0: the record launch sums the faces)
-    double *d_partial = nullptr;    // [nparts][2]
-    fs::HistProbe *d_probes = nullptr;
-    fs::HistFace *d_faces = nullptr;
-    double *d_ring = nullptr;       // [cap][2 + 3 np]
-    long long *d_state = nullptr;   // [HIST_STATE]
+    fs::DevBuf<double> d_partial;    // [nparts][2]
+    fs::DevBuf<fs::HistProbe> d_probes;
+    fs::DevBuf<fs::HistFace> d_faces;
+    fs::DevBuf<double> d_ring;       // [cap][2 + 3 np]
+    fs::DevBuf<long long> d_state;   // [HIST_STATE]
 };
 
 // time averages (fs_mean_*, fs_mean.h): the accumulator planes over this context's owned rows and the device counters
 struct fs_mean {
-    fs_ctx *ctx = nullptr;
     long long every = 1, start = 0;
     size_t plane = 0;               // doubles from one plane to the next: nyl * P + MEAN_PAD
-    double *d_sums = nullptr;       // [MEAN_PLANES][plane]
-    long long *d_state = nullptr;   // [MEAN_STATE]
+    fs::DevBuf<double> d_sums;       // [MEAN_PLANES][plane]
+    fs::DevBuf<long long> d_state;   // [MEAN_STATE]
 };
 
 // harmonic flow modes (fs_modes_*, fs_modes.h): the Fourier-sum planes over this context's owned rows, the device counters and scalars
 struct fs_modes {
-    fs_ctx *ctx = nullptr;
     int nfreq = 1;
     long long every = 1, start = 0;
     double cd[4] = {1, 1, 1, 1}, sd[4] = {0, 0, 0, 0};      // cos / sin of the phase step per sample of each frequency (MODES_MAX_FREQ)
     size_t plane = 0;               // doubles from one plane to the next: nyl * P + MEAN_PAD
-    double *d_sums = nullptr;       // [3 (1 + 2 nfreq)][plane]
-    long long *d_state = nullptr;   // [MODES_STATE]
-    double *d_scal = nullptr;       // [2 nfreq] phasors, then the upper triangle of the Gram matrix
+    fs::DevBuf<double> d_sums;       // [3 (1 + 2 nfreq)][plane]
+    fs::DevBuf<long long> d_state;   // [MODES_STATE]
+    fs::DevBuf<double> d_scal;       // [2 nfreq] phasors, then the upper triangle of the Gram matrix
 };
 
 // snapshot POD (fs_pod_*, fs_pod.h): the ring of resident snapshots over this context's owned rows, the device counters, the Gram scratch
 struct fs_pod {
-    fs_ctx *ctx = nullptr;
     int M = 2;
     long long every = 1, start = 0;
     size_t plane = 0;               // elements of the field type from one plane to the next: nyl * P + MEAN_PAD
-    void *d_slots = nullptr;        // [M][3][plane] of the field type: u, w, p
-    long long *d_state = nullptr;   // [POD_STATE]
-    double *d_gram = nullptr;       // fs_pod_gram: the workgroups' partial sums, then the n x n matrix (allocated at the first call)
+    fs::DevBuf<void> d_slots;        // [M][3][plane] of the field type: u, w, p
+    fs::DevBuf<long long> d_state;   // [POD_STATE]
+    fs::DevBuf<double> d_gram;       // fs_pod_gram: the workgroups' partial sums, then the n x n matrix (allocated at the first call)
     size_t gram_cap = 0;            // doubles
 };
 
 // flow map through the resident snapshots (fs_flowmap_*, fs_lcs.h): the lattice of nodes over a cell box
 struct fs_flowmap {
-    fs_ctx *ctx = nullptr;
     int box[4] = {0, 0, 0, 0};      // x0, y0, x1, y1 (cells)
     int r = 1, nx = 0, ny = 0;      // nodes per cell and direction; the lattice
-    double *d_pos = nullptr;        // [3][ny][nx]: x, y, lam
-    int *d_status = nullptr;        // [ny][nx]
+    fs::DevBuf<double> d_pos;        // [3][ny][nx]: x, y, lam
+    fs::DevBuf<int> d_status;        // [ny][nx]
 };
 
 // vortex identification (fs_vortex_*, fs_vortex.h): the flag, label and id planes of the whole grid, the accumulator table, the ring of samples
 struct fs_vortex {
-    fs_ctx *ctx = nullptr;
     int criterion = 0, min_area = 4, maxv = 64, maxc = 65536, cap = 1;
     double threshold = 0.0, scale = 1.0;    // scale: 2^(30 - e), what turns om into the integer q
     long long every = 1, start = 0;
     int cells = 0, nblocks = 0, words = 0;  // X * Y; workgroups of the compression / id passes; long long words per sample
-    uint8_t *d_flags = nullptr;     // [Y][X]
-    int *d_labels = nullptr;        // [Y][X]
-    int *d_ids = nullptr;           // [Y][X]: the dense id of every root
-    int *d_counts = nullptr;        // [nblocks]: roots per block, then their exclusive offsets
-    long long *d_table = nullptr;   // [VX_NACC][maxc]
-    long long *d_tmp = nullptr;     // [VX_TMP]
-    long long *d_ring = nullptr;    // [cap][words]
-    long long *d_state = nullptr;   // [VX_STATE]
+    fs::DevBuf<uint8_t> d_flags;     // [Y][X]
+    fs::DevBuf<int> d_labels;        // [Y][X]
+    fs::DevBuf<int> d_ids;           // [Y][X]: the dense id of every root
+    fs::DevBuf<int> d_counts;        // [nblocks]: roots per block, then their exclusive offsets
+    fs::DevBuf<long long> d_table;   // [VX_NACC][maxc]
+    fs::DevBuf<long long> d_tmp;     // [VX_TMP]
+    fs::DevBuf<long long> d_ring;    // [cap][words]
+    fs::DevBuf<long long> d_state;   // [VX_STATE]
 };
 
 namespace fs { struct LoadFace; }      // fs_loads.h (included by fs_diag.hip alone)
 // body surface loads (fs_loads_*, fs_loads.h): the face list of this context's owned rows, the per-face sums, the ring and the device counters
 struct fs_loads {
-    fs_ctx *ctx = nullptr;
     int nf = 0, cap = 0;
     long long every = 1, start = 0;
     int nparts = 0;                 // workgroups of the split form (LOADS_SPLIT; 0: one workgroup does the whole launch)
-    double *d_partial = nullptr;    // [nparts][LOADS_REC]
-    fs::LoadFace *d_faces = nullptr;
-    double *d_sums = nullptr;       // [LOADS_SUMS][nf]
-    double *d_ring = nullptr;       // [cap][LOADS_REC]
-    long long *d_state = nullptr;   // [LOADS_STATE]
+    fs::DevBuf<double> d_partial;    // [nparts][LOADS_REC]
+    fs::DevBuf<fs::LoadFace> d_faces;
+    fs::DevBuf<double> d_sums;       // [LOADS_SUMS][nf]
+    fs::DevBuf<double> d_ring;       // [cap][LOADS_REC]
+    fs::DevBuf<long long> d_state;   // [LOADS_STATE]
 };
 
 // tracer particles (fs_tracer_*, fs_tracer.h): the particle arrays and the launch counter
 struct fs_tracer {
-    fs_ctx *ctx = nullptr;
     int n = 0, respawn = 1, max_age = 0;
-    double *d_pos = nullptr;        // [4][n]: x, y, x_seed, y_seed
-    int *d_int = nullptr;           // [4][n]: age, status, respawns, id (slot -> seed index)
-    long long *d_count = nullptr;   // launches since creation
+    fs::DevBuf<double> d_pos;        // [4][n]: x, y, x_seed, y_seed
+    fs::DevBuf<int> d_int;           // [4][n]: age, status, respawns, id (slot -> seed index)
+    fs::DevBuf<long long> d_count;   // launches since creation
     // fs_tracer_sort (allocated at the first sort, freed with the set)
     bool permuted = false;          // a sort has run since creation / the last write: id may differ from the identity
-    double *d_spos = nullptr;       // [2][n]: x, y in the new order
-    int *d_sint = nullptr;          // [5][n]: age, status, respawns, id in the new order; the key of every slot
-    int *d_bins = nullptr;          // [nbins] counts / cursors, then [nblocks] totals of the scan's tiles
+    fs::DevBuf<double> d_spos;       // [2][n]: x, y in the new order
+    fs::DevBuf<int> d_sint;          // [5][n]: age, status, respawns, id in the new order; the key of every slot
+    fs::DevBuf<int> d_bins;          // [nbins] counts / cursors, then [nblocks] totals of the scan's tiles
     int nbins = 0, nblocks = 0;
     // inertial sets (fs_tracer_create_inertial)
     bool inertial = false;
     double gx = 0.0, gy = 0.0;
-    double *d_vel = nullptr;        // [4][n]: pu, pw, alpha, tau (slot order)
-    double *d_svel = nullptr;       // [4][n]: the same in the new order (with the sort's scratch)
+    fs::DevBuf<double> d_vel;        // [4][n]: pu, pw, alpha, tau (slot order)
+    fs::DevBuf<double> d_svel;       // [4][n]: the same in the new order (with the sort's scratch)
     std::vector<double> h_resp;     // [2][n]: alpha, tau in SEED order (fs_tracer_write puts the slots back into seed order)
-    int *d_dep = nullptr;           // [Y][X] deposit counts, or nullptr (deposits off)
+    fs::DevBuf<int> d_dep;           // [Y][X] deposit counts, or nullptr (deposits off)
     // accumulated occupancy (fs_tracer_accum_*): one per set
-    unsigned long long *d_acc = nullptr;      // [2][Y][X]: occupancy, age_sum
-    long long *d_acc_state = nullptr;         // [0] base: the launch count when attached, [1] samples
+    fs::DevBuf<unsigned long long> d_acc;      // [2][Y][X]: occupancy, age_sum
+    fs::DevBuf<long long> d_acc_state;         // [0] base: the launch count when attached, [1] samples
     long long acc_every = 1, acc_start = 0;
 };
 
 namespace fs {
 
-void history_release(fs_history *h);      // fs_diag.hip
-void mean_release(fs_mean *m);            // fs_diag.hip
-void loads_release(fs_loads *l);          // fs_diag.hip
-void modes_release(fs_modes *m);          // fs_diag.hip
-void pod_release(fs_pod *p);              // fs_diag.hip
-void flowmap_release(fs_flowmap *f);      // fs_diag.hip
-void vortex_release(fs_vortex *x);        // fs_diag.hip
-void mg_release(fs_mg *m);                // fs_multigrid.hip
+// ---- the objects behind the other handles: one registry (fs_ctx::objects, fs_objects.h), one guard, one no-capture check, one free -------------
+enum ObjKind { OBJ_HISTORY, OBJ_LOADS, OBJ_MEAN, OBJ_MODES, OBJ_POD, OBJ_VORTEX, OBJ_FLOWMAP, OBJ_TRACER, OBJ_MG };
+// kind, noun and stale-handle text of an object type: FS_OBJECT(type, kind, noun, text), once, in the unit that implements the type
+template <typename T> struct ObjInfo;
+#define FS_OBJECT(T, KIND, NOUN, STALE) \
+    template <> struct fs::ObjInfo<T> { static constexpr int kind = fs::KIND; static constexpr const char *noun = NOUN, *stale = STALE; }
+
+// a create hands its finished object to the context's registry and its caller the handle
+template <typename T>
+inline T *adopt(fs_ctx *ctx, std::unique_ptr<T> obj) { return ctx->objects.adopt(std::move(obj), ObjInfo<T>::kind); }
+// the guard of every entry point that takes a handle (const ones too): a registry lookup that never reads through `h`; only after it may `h` be used
+template <typename T>
+inline bool handle_ok(const fs_ctx *ctx, const T *h)
+{
+    if (ctx && ctx->objects.holds(h, ObjInfo<T>::kind)) return true;
+    set_error(ObjInfo<T>::stale);
+    return false;
+}
+#define FS_HANDLE(h) do { if (!fs::handle_ok(ctx, h)) return FS_ERR_ARG; } while (0)
+// what allocates, copies or synchronises has no place in a capture or on a tape
+#define FS_NO_CAPTURE(T, what)                                                                                                        \
+    do {                                                                                                                              \
+        if (ctx->capturing || ctx->tape_rec) {                                                                                        \
+            fs::set_error(std::string(fs::ObjInfo<T>::noun) + " " what " during graph capture / tape recording");                     \
+            return FS_ERR_STATE;                                                                                                      \
+        }                                                                                                                             \
+    } while (0)
+// every fs_*_free: null is fine; a live handle leaves the registry and is deleted once the stream is idle - or, inside a capture, when it ends
+template <typename T>
+inline int object_free(fs_ctx *ctx, T *h)
+{
+    if (!h) return FS_OK;
+    FS_HANDLE(h);
+    ctx->objects.free(h, ObjInfo<T>::kind, ctx->capturing, [ctx] { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); });
+    return FS_OK;
+}
+
+// the small repeats of the riders' entry points
+#define FS_EVERY_START(every, start) FS_REQUIRE((every) >= 1 && (start) >= 0, "every must be >= 1 and start >= 0")
+#define FS_COUNTERS(launches, samples) \
+    FS_REQUIRE((launches) >= 0 && (samples) >= 0 && (samples) <= (launches), "counters must satisfy 0 <= samples <= launches")
+// an object's device counters on the host, synchronised
+template <int N>
+inline int read_counters(fs_ctx *ctx, const long long *d_state, long long (&st)[N])
+{
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemcpyAsync(st, d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
 
 // HIP-event pair around a span of stream work that is not one kernel launch (fs_core.hip; the ghost-row exchange chain of fs_comm.hip)
 ProfRec prof_span_begin(fs_ctx *c, const char *name, hipStream_t stream);

@@ -58,7 +58,7 @@ struct FlowMapDev {
     double *lam;
 };
 
-// (fs_tracer.h tracer_inside: that header defines kernels of fs_core.hip and is included there alone)
+// (fs_tracer.h tracer_inside: that header defines kernels of fs_tracers.hip and is included there alone)
 __device__ __forceinline__ bool flowmap_inside(double x, double y, double X, double Y) { return x >= 0.0 && x < X && y >= 0.0 && y < Y; }
 
 __global__ __launch_bounds__(FM_WG) void k_flowmap_seed(Grid g, FlowMapDev f)

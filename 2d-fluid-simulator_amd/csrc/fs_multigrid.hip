@@ -5,12 +5,11 @@
 
 // the hierarchy of one updater (fs_mg_create): five concatenated arrays over the cells of levels 1 .. n, level after level
 struct fs_mg {
-    fs_ctx *ctx = nullptr;
     int n = 0;                                   // levels 1 .. n (index 0 .. n - 1 below)
     int nx[fs::MG_MAX_LEVELS], ny[fs::MG_MAX_LEVELS];
     size_t off[fs::MG_MAX_LEVELS];               // first cell of the level
     size_t cells = 0;
-    void *d_E = nullptr, *d_R = nullptr, *d_cx = nullptr, *d_cy = nullptr, *d_diag = nullptr;
+    fs::DevBuf<void> d_E, d_R, d_cx, d_cy, d_diag;
     int tail = -1;                               // index of the first level the tail kernel holds in LDS (-1: none)
     size_t tail_bytes = 0;
     int coarse_sweeps = 2, coarsest_sweeps = 64;
@@ -18,18 +17,11 @@ struct fs_mg {
     // an exact solve attached to the LAST level (fs_mg_set_direct): E[active] = M R[active] instead of coarsest_sweeps sweeps
     bool direct = false;
     int direct_n = 0, direct_stride = 0;         // active cells; elements per row of M (64 ceil(n / 64))
-    int *d_cells = nullptr;                      // their indices J * nx + I in the level, ascending
-    void *d_M = nullptr;                         // [n][stride] in the field dtype
+    fs::DevBuf<int> d_cells;                     // their indices J * nx + I in the level, ascending
+    fs::DevBuf<void> d_M;                        // [n][stride] in the field dtype
 };
 
-namespace fs {
-void mg_release(fs_mg *m)
-{
-    for (void *p : {m->d_E, m->d_R, m->d_cx, m->d_cy, m->d_diag, (void *)m->d_cells, m->d_M})
-        if (p) hipFree(p);
-    delete m;
-}
-}  // namespace fs
+FS_OBJECT(fs_mg, OBJ_MG, "multigrid", "multigrid hierarchy from another context or freed");
 
 using namespace fs;
 
@@ -126,10 +118,11 @@ int fs_mg_create(fs_ctx *ctx, int nlevels, const int *dims, const void *cx, cons
     FS_REQUIRE(dims[0] * 2 == ctx->X && dims[1] * 2 == ctx->Y, "level 1 must be half the grid in both directions");
     for (int k = 1; k < nlevels; ++k)
         FS_REQUIRE(dims[2 * k] * 2 == dims[2 * k - 2] && dims[2 * k + 1] * 2 == dims[2 * k - 1] && dims[2 * k] >= 1 && dims[2 * k + 1] >= 1, "every level must be half the level above it");
-    if (ctx->capturing || ctx->tape_rec) { set_error("multigrid create during graph capture / tape recording"); return FS_ERR_STATE; }
+    FS_NO_CAPTURE(fs_mg, "create");
     FS_HIP(hipSetDevice(ctx->device));
-    fs_mg *m = new fs_mg();
-    m->ctx = ctx; m->n = nlevels; m->coarse_sweeps = coarse_sweeps; m->coarsest_sweeps = coarsest_sweeps;
+    auto mg = std::make_unique<fs_mg>();
+    fs_mg *m = mg.get();
+    m->n = nlevels; m->coarse_sweeps = coarse_sweeps; m->coarsest_sweeps = coarsest_sweeps;
     for (int k = 0; k < nlevels; ++k) {
         m->nx[k] = dims[2 * k]; m->ny[k] = dims[2 * k + 1];
         m->off[k] = m->cells;
@@ -149,30 +142,29 @@ int fs_mg_create(fs_ctx *ctx, int nlevels, const int *dims, const void *cx, cons
     if (m->tail >= 0 && m->tail_bytes > 48 * 1024) {
         e = ctx->dtype == 0 ? hipFuncSetAttribute((const void *)k_mg_tail<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->tail_bytes)
                             : hipFuncSetAttribute((const void *)k_mg_tail<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->tail_bytes);
-        if (e != hipSuccess) { mg_release(m); return hip_fail(e, "fs_mg_create: hipFuncSetAttribute", __FILE__, __LINE__); }
+        if (e != hipSuccess) return hip_fail(e, "fs_mg_create: hipFuncSetAttribute", __FILE__, __LINE__);
     }
     const size_t bytes = m->cells * ctx->esize;
-    e = hipMalloc(&m->d_E, bytes);
-    if (e == hipSuccess) e = hipMalloc(&m->d_R, bytes);
-    if (e == hipSuccess) e = hipMalloc(&m->d_cx, bytes);
-    if (e == hipSuccess) e = hipMalloc(&m->d_cy, bytes);
-    if (e == hipSuccess) e = hipMalloc(&m->d_diag, bytes);
+    e = m->d_E.alloc(bytes);
+    if (e == hipSuccess) e = m->d_R.alloc(bytes);
+    if (e == hipSuccess) e = m->d_cx.alloc(bytes);
+    if (e == hipSuccess) e = m->d_cy.alloc(bytes);
+    if (e == hipSuccess) e = m->d_diag.alloc(bytes);
     if (e == hipSuccess) e = hipMemsetAsync(m->d_E, 0, bytes, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(m->d_R, 0, bytes, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(m->d_cx, cx, bytes, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(m->d_cy, cy, bytes, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(m->d_diag, diag, bytes, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { mg_release(m); return hip_fail(e, "fs_mg_create", __FILE__, __LINE__); }
-    ctx->mgs.insert(m);
-    *out = m;
+    if (e != hipSuccess) return hip_fail(e, "fs_mg_create", __FILE__, __LINE__);
+    *out = adopt(ctx, std::move(mg));
     return FS_OK;
 }
 
 int fs_mg_set_direct(fs_ctx *ctx, fs_mg *m, int n, const int *cells, const void *M, long long row_stride)
 {
     FS_REQUIRE(ctx && m && cells && M, "null argument");
-    FS_REQUIRE(ctx->mgs.count(m), "multigrid hierarchy from another context or freed");      // (the set lookup never reads the handle)
+    FS_HANDLE(m);
     FS_REQUIRE(n >= 0 && n <= MG_DIRECT_MAX, "a direct solve holds 0 .. 4096 active cells");
     FS_REQUIRE(row_stride == 64ll * ((n + 63) / 64), "row_stride must be 64 * ceil(n / 64)");
     const long long level_cells = (long long)m->nx[m->n - 1] * m->ny[m->n - 1];
@@ -180,31 +172,27 @@ int fs_mg_set_direct(fs_ctx *ctx, fs_mg *m, int n, const int *cells, const void 
         FS_REQUIRE(cells[j] >= 0 && cells[j] < level_cells && (j == 0 || cells[j] > cells[j - 1]), "cells must be strictly ascending indices of the last level");
     if (m->tail >= 0) { set_error("a direct solve needs a hierarchy without a tail kernel (tail_cells = 0)"); return FS_ERR_STATE; }
     if (m->direct) { set_error("this hierarchy already has a direct solve"); return FS_ERR_STATE; }
-    if (ctx->capturing || ctx->tape_rec) { set_error("multigrid set_direct during graph capture / tape recording"); return FS_ERR_STATE; }
+    FS_NO_CAPTURE(fs_mg, "set_direct");
     FS_HIP(hipSetDevice(ctx->device));
-    int *d_cells = nullptr;
-    void *d_M = nullptr;
+    DevBuf<int> d_cells;      // (the hierarchy takes the two over only when both are filled)
+    DevBuf<void> d_M;
     if (n > 0) {
         const size_t mbytes = (size_t)n * (size_t)row_stride * ctx->esize;
-        hipError_t e = hipMalloc(&d_cells, (size_t)n * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc(&d_M, mbytes);
+        hipError_t e = d_cells.alloc((size_t)n * sizeof(int));
+        if (e == hipSuccess) e = d_M.alloc(mbytes);
         if (e == hipSuccess) e = hipMemcpyAsync(d_cells, cells, (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(d_M, M, mbytes, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            if (d_cells) hipFree(d_cells);
-            if (d_M) hipFree(d_M);
-            return hip_fail(e, "fs_mg_set_direct", __FILE__, __LINE__);
-        }
+        if (e != hipSuccess) return hip_fail(e, "fs_mg_set_direct", __FILE__, __LINE__);
     }
-    m->direct = true; m->direct_n = n; m->direct_stride = (int)row_stride; m->d_cells = d_cells; m->d_M = d_M;
+    m->direct = true; m->direct_n = n; m->direct_stride = (int)row_stride; m->d_cells = std::move(d_cells); m->d_M = std::move(d_M);
     return FS_OK;
 }
 
 int fs_mg_direct_info(fs_ctx *ctx, fs_mg *m, int *direct_level, int *direct_cells)
 {
     FS_REQUIRE(ctx && m && direct_level && direct_cells, "null argument");
-    FS_REQUIRE(ctx->mgs.count(m), "multigrid hierarchy from another context or freed");      // (the set lookup never reads the handle)
+    FS_HANDLE(m);
     *direct_level = m->direct ? m->n : 0;
     *direct_cells = m->direct_n;
     return FS_OK;
@@ -213,7 +201,7 @@ int fs_mg_direct_info(fs_ctx *ctx, fs_mg *m, int *direct_level, int *direct_cell
 int fs_mg_cycle(fs_ctx *ctx, fs_mg *m, double dt, double dx, fs_field *pc, fs_field *pn, const fs_field *vc)
 {
     FS_REQUIRE(ctx && m, "null argument");
-    FS_REQUIRE(ctx->mgs.count(m), "multigrid hierarchy from another context or freed");      // (the set lookup never reads the handle)
+    FS_HANDLE(m);
     FS_FIELD(pc, 1); FS_FIELD(pn, 1); FS_FIELD(vc, 2);
     FS_REQUIRE(pc != pn, "the correction needs the two distinct pressure buffers of the red-black pair");
     if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
@@ -237,22 +225,13 @@ int fs_mg_cycle(fs_ctx *ctx, fs_mg *m, double dt, double dx, fs_field *pc, fs_fi
 int fs_mg_info(fs_ctx *ctx, fs_mg *m, int *levels, int *tail_level, int *launches)
 {
     FS_REQUIRE(ctx && m && levels && tail_level && launches, "null argument");
-    FS_REQUIRE(ctx->mgs.count(m), "multigrid hierarchy from another context or freed");      // (the set lookup never reads the handle)
+    FS_HANDLE(m);
     *levels = m->n;
     *tail_level = m->tail < 0 ? 0 : m->tail + 1;
     *launches = m->launches;
     return FS_OK;
 }
 
-int fs_mg_free(fs_ctx *ctx, fs_mg *m)
-{
-    if (!m) return FS_OK;
-    FS_REQUIRE(ctx && ctx->mgs.count(m), "multigrid hierarchy from another context or freed");
-    ctx->mgs.erase(m);
-    if (ctx->capturing) { ctx->deferred_release.push_back([m] { mg_release(m); }); return FS_OK; }      // (no synchronisation / hipFree inside a capture)
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    mg_release(m);
-    return FS_OK;
-}
+int fs_mg_free(fs_ctx *ctx, fs_mg *m) { return object_free(ctx, m); }
 
 }  // extern "C"

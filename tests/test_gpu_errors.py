@@ -272,3 +272,143 @@ def test_mg_constructor_refuses_an_odd_grid(hip_lib):
         assert np.array_equal(p.current.to_numpy(), exp.current)
     finally:
         bc.device.close()
+
+
+# ---- the nine kinds of device object behind one registry, one handle check and one free (csrc/fs_objects.h, fs_host.h) -------------------------
+# Straight through the C-ABI: the Python layer nulls a handle it has released (RideOps._release), so a stale one never gets past it.
+_LL = ctypes.c_longlong
+
+
+def _handle(L, name, ctx, *args):
+    h = ctypes.c_void_p()
+    assert getattr(L, name)(ctx, *args, ctypes.byref(h)) == 0, L.fs_last_error()
+    return h
+
+
+def _mg_create(L, ctx):
+    ones = np.ones(16 * 8, np.float32).ctypes.data_as(ctypes.c_void_p)      # one level, half of 32 x 16
+    return _handle(L, "fs_mg_create", ctx, 1, (ctypes.c_int * 2)(16, 8), ones, ones, ones, 0, 2, 4)
+
+
+# kind -> (create(L, ctx) -> handle, the cheapest use(L, ctx, handle) -> status, the free's name, the text of a refused handle)
+KINDS = {
+    "history": (lambda L, c: _handle(L, "fs_history_create", c, 1, (ctypes.c_int * 2)(5, 5), 0, None, 4, 1),
+                lambda L, c, h: L.fs_history_read(c, h, None, 0, ctypes.byref(ctypes.c_int()), None, None),
+                "fs_history_free", b"history from another context or freed"),
+    "loads": (lambda L, c: _handle(L, "fs_loads_create", c, 1, (ctypes.c_int * 3)(5, 5, 0), (ctypes.c_double * 2)(4.0, 4.0), 4, 1, 0),
+              lambda L, c, h: L.fs_loads_reset(c, h), "fs_loads_free", b"loads from another context or freed"),
+    "mean": (lambda L, c: _handle(L, "fs_mean_create", c, 1, 0),
+             lambda L, c, h: L.fs_mean_reset(c, h), "fs_mean_free", b"mean from another context or freed"),
+    "modes": (lambda L, c: _handle(L, "fs_modes_create", c, 1, (ctypes.c_double * 2)(1.0, 0.0), 1, 0),
+              lambda L, c, h: L.fs_modes_reset(c, h), "fs_modes_free", b"modes from another context or freed"),
+    "pod": (lambda L, c: _handle(L, "fs_pod_create", c, 2, 1, 0),
+            lambda L, c, h: L.fs_pod_reset(c, h), "fs_pod_free", b"pod from another context or freed"),
+    "vortex": (lambda L, c: _handle(L, "fs_vortex_create", c, 0, 0.0, 1.0, 1, 0, 1, 4, 16, 2),
+               lambda L, c, h: L.fs_vortex_read(c, h, None, 0, ctypes.byref(ctypes.c_int()), None, None),
+               "fs_vortex_free", b"vortex tracker from another context or freed"),
+    "flowmap": (lambda L, c: _handle(L, "fs_flowmap_create", c, (ctypes.c_int * 4)(4, 4, 12, 12), 1),
+                lambda L, c, h: L.fs_flowmap_reset(c, h), "fs_flowmap_free", b"flow map from another context or freed"),
+    "tracer": (lambda L, c: _handle(L, "fs_tracer_create", c, 1, (ctypes.c_double * 2)(8.0, 8.0), 1, 0),
+               lambda L, c, h: L.fs_tracer_order(c, h, (ctypes.c_int * 1)()), "fs_tracer_free", b"tracer set from another context or freed"),
+    "mg": (_mg_create, lambda L, c, h: L.fs_mg_info(c, h, *(ctypes.byref(ctypes.c_int()) for _ in range(3))),
+           "fs_mg_free", b"multigrid hierarchy from another context or freed"),
+}
+
+
+def _refused(L, status, text):
+    return status == -1 and L.fs_last_error() == text
+
+
+@pytest.mark.parametrize("kind", sorted(KINDS))
+def test_object_handle_of_another_context_or_freed(dev, hip_lib, kind):
+    """Per kind: a handle of context A used or freed through context B, and used or freed again after its free, is refused with the kind's text
+    (FS_ERR_ARG) - by a lookup that never reads through the handle; the refusals leave the object usable on A; a null free is fine."""
+    from fs import _lib
+    L, a = hip_lib, dev._ctx
+    create, use, free_name, text = KINDS[kind]
+    free = getattr(L, free_name)
+    b = ctypes.c_void_p()
+    _lib.call("fs_create", ctypes.byref(b), 0, 32, 16, 0, 0, 16, 0)
+    try:
+        h = create(L, a)
+        assert use(L, a, h) == 0
+        assert _refused(L, use(L, b, h), text)
+        assert _refused(L, free(b, h), text)
+        assert use(L, a, h) == 0                                # the refused free on B left it alive on A
+        assert free(a, h) == 0
+        assert _refused(L, use(L, a, h), text)                  # stale from here on
+        assert _refused(L, free(a, h), text)
+        assert _refused(L, use(L, b, h), text)
+        assert free(a, None) == 0 and free(b, None) == 0        # a null handle: nothing to free
+    finally:
+        assert L.fs_destroy(b) == 0
+
+
+@pytest.mark.parametrize("given, expected", [("mean", "modes"), ("pod", "mean"), ("tracer", "vortex"), ("modes", "pod"), ("mg", "history")])
+def test_object_handle_of_another_kind(dev, hip_lib, given, expected):
+    """A LIVE handle of one kind where another is expected: refused with the expected kind's text, and still what it was afterwards."""
+    L, a = hip_lib, dev._ctx
+    create, use, free_name, _ = KINDS[given]
+    _, use_as, free_as, text = KINDS[expected]
+    h = create(L, a)
+    assert _refused(L, use_as(L, a, h), text)
+    assert _refused(L, getattr(L, free_as)(a, h), text)
+    assert use(L, a, h) == 0
+    assert getattr(L, free_name)(a, h) == 0
+
+
+@pytest.mark.parametrize("kind", sorted(KINDS))
+def test_object_free_inside_a_capture(dev, hip_lib, kind):
+    """Per kind: *_free inside a hipGraph capture returns 0 and defers the release to the capture's end - the capture stays valid and the graph
+    replays - and the handle is stale from the call on.  fs_flowmap_free is the one free that refuses a capture instead (FS_ERR_STATE, as
+    tests/test_gpu_lcs.py asserts since the flow maps exist): there the capture stays valid too and the flow map stays live."""
+    L, a = hip_lib, dev._ctx
+    create, use, free_name, text = KINDS[kind]
+    free = getattr(L, free_name)
+    h, p = create(L, a), dev.alloc(1)
+    seen = []
+
+    def body():
+        dev.pressure_bc(p)
+        seen.append(free(a, h))
+        seen.append(L.fs_last_error())
+        dev.pressure_bc(p)
+
+    gid = dev.capture(body)                                     # (fs_graph_end fails on an invalidated capture)
+    dev.replay(gid)
+    dev.free_graph(gid)
+    if kind == "flowmap":
+        assert seen == [-3, b"flow map free during graph capture / tape recording"]
+        assert use(L, a, h) == 0 and free(a, h) == 0
+    else:
+        assert seen[0] == 0
+    assert _refused(L, use(L, a, h), text)
+    assert _refused(L, free(a, h), text)
+    dev.pressure_bc(p)
+    assert np.isfinite(p.to_numpy()).all()
+
+
+def test_destroy_with_a_live_object_of_every_kind(hip_lib):
+    """fs_destroy releases whatever the registry still holds - one live object of each kind here, and one freed before - and returns 0; a context
+    created afterwards runs a launch."""
+    import fs
+    from fs.boundary_condition import BoundaryCondition
+    fs.runtime.init(gpu=0, dtype="f32")
+    L = hip_lib
+    mask = np.zeros((32, 16), np.uint8); mask[:, :2] = 1; mask[:, -2:] = 1
+    victim = BoundaryCondition(np.zeros((32, 16, 2), np.float32), mask).device
+    ctx, victim._ctx = victim._ctx, None                        # (its close() and finaliser must not destroy the context a second time)
+    handles = {kind: KINDS[kind][0](L, ctx) for kind in sorted(KINDS)}
+    extra = KINDS["mean"][0](L, ctx)
+    assert L.fs_mean_free(ctx, extra) == 0
+    for kind, h in handles.items():
+        assert KINDS[kind][1](L, ctx, h) == 0, kind
+    assert L.fs_destroy(ctx) == 0
+    fresh = BoundaryCondition(np.zeros((32, 16, 2), np.float32), mask).device
+    try:
+        p = fresh.alloc(1)
+        p.from_numpy(np.ones((32, 16), np.float32))
+        fresh.pressure_bc(p)
+        assert np.isfinite(p.to_numpy()).all()
+    finally:
+        fresh.close()

@@ -8,7 +8,7 @@ mkdir -p "$(dirname "$0")/ab"
 make -C "$CS" -j8 >/dev/null
 /opt/rocm/bin/hipcc $EXTRA -O3 -fno-slp-vectorize -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -w -I/opt/rocm/include -c "$CS/$TU.hip" -o "/tmp/ab_${NAME}_$TU.o"
 OBJS=""
-for o in fs_core fs_transport fs_pressure fs_diag fs_comm; do
+for o in fs_core fs_transport fs_pressure fs_multigrid fs_diag fs_tracers fs_comm; do
     if [ "$o" = "$TU" ]; then OBJS="$OBJS /tmp/ab_${NAME}_$TU.o"; else OBJS="$OBJS $CS/$o.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$(dirname "$0")/ab/lib_$NAME.so" $OBJS -ldl

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Instruction mix of the gfx950 kernels: tools/isa_mix.py [name-substring ...]   (device-only -S of csrc/fs_transport.hip, fs_pressure.hip, fs_diag.hip, fs_core.hip)"""
+"""Instruction mix of the gfx950 kernels: tools/isa_mix.py [name-substring ...]   (device-only -S of csrc/fs_transport.hip, fs_pressure.hip, fs_diag.hip, fs_tracers.hip, fs_core.hip)"""
 import collections
 import os
 import re
@@ -12,7 +12,7 @@ CSRC = os.path.join(REPO, "2d-fluid-simulator_amd", "csrc")
 
 def main():
     lines = []
-    for tu in ("fs_transport", "fs_pressure", "fs_diag", "fs_core"):
+    for tu in ("fs_transport", "fs_pressure", "fs_diag", "fs_tracers", "fs_core"):
         asm = f"/tmp/{tu}_isa.s"
         subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-fno-slp-vectorize", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-w",
                         "-I/opt/rocm/include", "--cuda-device-only", "-S", os.path.join(CSRC, tu + ".hip"), "-o", asm], check=True)
