@@ -1,6 +1,6 @@
 // fs_diag.hip - C-ABI entry points of what reads the flow without changing it: the flow diagnostics (fs_stats.h), the per-step history ring
 // (fs_history.h), the body surface loads (fs_loads.h), the time averages (fs_mean.h), the harmonic modes (fs_modes.h), the snapshot POD
-// (fs_pod.h), the flow maps through its snapshots (fs_lcs.h) and the vortex identification (fs_vortex.h).  Their objects live in the context's
+// (fs_pod.h), the flow maps through its snapshots (fs_lcs.h), the vortex identification (fs_vortex.h) and the field distributions (fs_dist.h).  Their objects live in the context's
 // registry (fs_host.h: FS_OBJECT, FS_HANDLE, FS_NO_CAPTURE, object_free).
 #include "fs_launch.h"
 #include "fs_stats.h"
@@ -10,6 +10,7 @@
 #include "fs_lcs.h"
 #include "fs_loads.h"
 #include "fs_vortex.h"
+#include "fs_dist.h"
 
 static_assert(fs::STATS_N == FS_FLOW_NSTAT, "fs_stats.h and include/fs_hip.h disagree on the slots");
 static_assert(fs::LOADS_REC == FS_LOADS_NREC && fs::LOADS_SUMS == FS_LOADS_NSUM, "fs_loads.h and include/fs_hip.h disagree on the record / the sums");
@@ -23,12 +24,16 @@ static_assert(fs::FM_LEFT == FS_TRACER_LEFT && fs::FM_WALL == FS_TRACER_WALL && 
 static_assert(fs::VX_NACC == FS_VORTEX_NACC && fs::VX_REC == FS_VORTEX_NREC && fs::VX_HEAD == FS_VORTEX_NHEAD && fs::VX_MAX_VORTICES == FS_VORTEX_MAX_VORTICES,
               "fs_vortex.h and include/fs_hip.h disagree");
 
+static_assert(fs::DIST_MAX_BINS == FS_DIST_MAX_BINS && fs::DIST_MAX_CHANNELS == FS_DIST_MAX_CHANNELS && fs::DIST_MAX_RANKS == FS_DIST_MAX_RANKS && fs::DIST_TAILS == FS_DIST_NTAIL,
+              "fs_dist.h and include/fs_hip.h disagree");
+
 FS_OBJECT(fs_history, OBJ_HISTORY, "history", "history from another context or freed");
 FS_OBJECT(fs_loads, OBJ_LOADS, "loads", "loads from another context or freed");
 FS_OBJECT(fs_mean, OBJ_MEAN, "mean", "mean from another context or freed");
 FS_OBJECT(fs_modes, OBJ_MODES, "modes", "modes from another context or freed");
 FS_OBJECT(fs_pod, OBJ_POD, "pod", "pod from another context or freed");
 FS_OBJECT(fs_vortex, OBJ_VORTEX, "vortex", "vortex tracker from another context or freed");
+FS_OBJECT(fs_dist, OBJ_DIST, "distributions", "distributions from another context or freed");
 FS_OBJECT(fs_flowmap, OBJ_FLOWMAP, "flow map", "flow map from another context or freed");
 
 using namespace fs;
@@ -990,6 +995,224 @@ int fs_vortex_criterion(fs_ctx *ctx, int which, double limit, double dx, const f
 }
 
 int fs_vortex_free(fs_ctx *ctx, fs_vortex *vx) { return object_free(ctx, vx); }
+
+// ---- field distributions (fs_dist.h) ---------------------------------------------------------------------------------------------------------
+#define FS_DIST_SINGLE_GPU() \
+    if (ctx->halo != 0 || ctx->nyl != ctx->Y) { \
+        set_error("field distributions need a single-GPU context: on a slab the tables would have to be added across ranks (not implemented)"); \
+        return FS_ERR_UNSUPPORTED; \
+    }
+#define FS_DIST_BOX(box) \
+    FS_REQUIRE(0 <= (box)[0] && (box)[0] < (box)[2] && (box)[2] <= ctx->X && 0 <= (box)[1] && (box)[1] < (box)[3] && (box)[3] <= ctx->Y, \
+               "distribution box must satisfy 0 <= x0 < x1 <= X and 0 <= y0 < y1 <= Y")
+
+// the walk of a pass over `box`: the workgroups of the whole grid's tiling (256 columns, rows from diag_rows) that meet the box
+static DistWalk dist_walk_of(const fs_ctx *ctx, const int *box, int need, double dx, double limit, dim3 *grid)
+{
+    const int rpw = diag_rows(ctx, (ctx->X + 255) / 256, ctx->Y, DIST_G, DIST_ROWS);
+    const int bx0 = box[0] / 256, bx1 = (box[2] + 255) / 256, by0 = box[1] / rpw, by1 = (box[3] + rpw - 1) / rpw;
+    *grid = dim3(bx1 - bx0, by1 - by0);
+    return DistWalk{ctx->Y, rpw, bx0, by0, box[0], box[1], box[2], box[3], need, dx, limit};
+}
+
+int fs_dist_create(fs_ctx *ctx, int nchan, const fs_dist_spec *specs, long long every, long long start, fs_dist **out)
+{
+    FS_REQUIRE(ctx && specs && out, "null argument");
+    FS_REQUIRE(nchan >= 1 && nchan <= DIST_MAX_CHANNELS, "nchan must be 1 .. FS_DIST_MAX_CHANNELS");
+    FS_EVERY_START(every, start);
+    auto d = std::make_unique<fs_dist>();
+    d->nchan = nchan; d->every = every; d->start = start;
+    for (int c = 0; c < nchan; ++c) {
+        const fs_dist_spec &s = specs[c];
+        FS_REQUIRE(s.quantity >= 0 && s.quantity < DIST_NQ && s.quantity_b < DIST_NQ, "quantity must be 0 (u) .. 6 (swirl)");
+        FS_REQUIRE(s.bins >= 1 && s.bins <= DIST_MAX_BINS, "bins must be 1 .. FS_DIST_MAX_BINS");
+        FS_REQUIRE(std::isfinite(s.lo) && std::isfinite(s.hi) && s.lo < s.hi, "range must be finite with lo < hi");
+        d->inv[c] = (double)s.bins / (s.hi - s.lo);
+        FS_REQUIRE(std::isfinite(d->inv[c]) && d->inv[c] > 0.0, "range too narrow or too wide: bins / (hi - lo) must be finite and positive");
+        size_t words = (size_t)s.bins;
+        if (s.quantity_b >= 0) {
+            FS_REQUIRE(s.bins_b >= 1 && (long long)s.bins * s.bins_b <= DIST_MAX_BINS, "a joint table holds at most FS_DIST_MAX_BINS bins");
+            FS_REQUIRE(std::isfinite(s.lo_b) && std::isfinite(s.hi_b) && s.lo_b < s.hi_b, "range must be finite with lo < hi");
+            d->inv_b[c] = (double)s.bins_b / (s.hi_b - s.lo_b);
+            FS_REQUIRE(std::isfinite(d->inv_b[c]) && d->inv_b[c] > 0.0, "range too narrow or too wide: bins / (hi - lo) must be finite and positive");
+            words *= (size_t)s.bins_b;
+        }
+        FS_DIST_BOX(s.box);
+        d->spec[c] = s;
+        d->offset[c + 1] = d->offset[c] + words + DIST_TAILS;
+    }
+    FS_NO_CAPTURE(fs_dist, "create");
+    FS_DIST_SINGLE_GPU()
+    FS_HIP(hipSetDevice(ctx->device));
+    const size_t bytes = d->offset[nchan] * sizeof(long long);
+    hipError_t e = d->d_state.alloc(DIST_STATE * sizeof(long long));
+    if (e == hipSuccess) e = d->d_tables.alloc(bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(d->d_state, 0, DIST_STATE * sizeof(long long), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d->d_tables, 0, bytes, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "fs_dist_create", __FILE__, __LINE__);
+    *out = adopt(ctx, std::move(d));
+    return FS_OK;
+}
+
+int fs_dist_launch(fs_ctx *ctx, fs_dist *d, double limit, double dx, const fs_field *v, const fs_field *p)
+{
+    FS_REQUIRE(ctx && d, "null argument");
+    FS_HANDLE(d);
+    FS_FIELD(v, 2); FS_FIELD(p, 1);
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    // everything the launches need is in `d` and the fields: no allocation, copy or synchronisation here (the closure is captured / taped)
+    const long long every = d->every, start = d->start;
+    long long *state = d->d_state;
+    const DistWhen when{state, start, every};
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
+        for (int c = 0; c < d->nchan; ++c) {
+            const fs_dist_spec &s = d->spec[c];
+            const bool joint = s.quantity_b >= 0;
+            const DistChan ch{s.quantity, joint ? s.quantity_b : -1, s.bins, joint ? s.bins_b : 1, s.lo, s.hi, d->inv[c], s.lo_b, s.hi_b, d->inv_b[c]};
+            dim3 grid;
+            const DistWalk walk = dist_walk_of(ctx, s.box, dist_need(ch.qa) | dist_need(ch.qb), dx, limit, &grid);
+            long long *counts = d->d_tables + d->offset[c];
+            const int rc = launch(ctx, "dist_accumulate", [=] {
+                if (joint) klaunch(k_dist_accumulate<T, true>, grid, dim3(256), ctx->stream, ctx->grid(), walk, when, ch, (const T *)v->d, (const T *)p->d, counts);
+                else klaunch(k_dist_accumulate<T, false>, grid, dim3(256), ctx->stream, ctx->grid(), walk, when, ch, (const T *)v->d, (const T *)p->d, counts);
+            });
+            if (rc) return rc;
+        }
+        return launch(ctx, "dist_tick", [=] { klaunch(k_dist_tick, dim3(1), dim3(64), ctx->stream, start, every, state); });
+    });
+}
+
+int fs_dist_read(fs_ctx *ctx, fs_dist *d, int chan, long long *counts, long long *tails, long long *launches, long long *samples)
+{
+    FS_REQUIRE(ctx && d, "null argument");
+    FS_HANDLE(d);
+    FS_REQUIRE(chan >= 0 && chan < d->nchan, "channel outside 0 .. nchan - 1");
+    FS_NO_CAPTURE(fs_dist, "read");
+    long long st[DIST_STATE];
+    if (int rc = read_counters(ctx, d->d_state, st)) return rc;
+    const size_t bins = d->offset[chan + 1] - d->offset[chan] - DIST_TAILS;
+    if (counts) FS_HIP(hipMemcpyAsync(counts, d->d_tables + d->offset[chan], bins * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    if (tails) FS_HIP(hipMemcpyAsync(tails, d->d_tables + d->offset[chan] + bins, DIST_TAILS * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    if (launches) *launches = st[0];
+    if (samples) *samples = st[1];
+    return FS_OK;
+}
+
+int fs_dist_get(fs_ctx *ctx, fs_dist *d, long long *words_out)
+{
+    FS_REQUIRE(ctx && d && words_out, "null argument");
+    FS_HANDLE(d);
+    FS_NO_CAPTURE(fs_dist, "get");
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemcpyAsync(words_out, d->d_tables, d->offset[d->nchan] * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_dist_set(fs_ctx *ctx, fs_dist *d, const long long *words_in, long long launches, long long samples)
+{
+    FS_REQUIRE(ctx && d && words_in, "null argument");
+    FS_HANDLE(d);
+    FS_COUNTERS(launches, samples);
+    FS_NO_CAPTURE(fs_dist, "set");
+    FS_HIP(hipSetDevice(ctx->device));
+    const long long st[DIST_STATE] = {launches, samples};
+    FS_HIP(hipMemcpyAsync(d->d_tables, words_in, d->offset[d->nchan] * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipMemcpyAsync(d->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
+    return FS_OK;
+}
+
+int fs_dist_reset(fs_ctx *ctx, fs_dist *d)
+{
+    FS_REQUIRE(ctx && d, "null argument");
+    FS_HANDLE(d);
+    FS_NO_CAPTURE(fs_dist, "reset");
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemsetAsync(d->d_tables, 0, d->offset[d->nchan] * sizeof(long long), ctx->stream));
+    FS_HIP(hipMemsetAsync(d->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
+    return FS_OK;
+}
+
+int fs_dist_free(fs_ctx *ctx, fs_dist *d) { return object_free(ctx, d); }
+
+int fs_dist_select(fs_ctx *ctx, int quantity, const int *box, double limit, double dx, const fs_field *v, const fs_field *p,
+                   const long long *ranks, int nranks, double *values_out, long long *n_out, long long *nan_out)
+{
+    FS_REQUIRE(ctx && box && n_out && nan_out, "null argument");
+    FS_REQUIRE(quantity >= 0 && quantity < DIST_NQ, "quantity must be 0 (u) .. 6 (swirl)");
+    FS_REQUIRE(nranks >= 0 && nranks <= DIST_MAX_RANKS && (nranks == 0 || (ranks && values_out)), "nranks must be 0 .. FS_DIST_MAX_RANKS");
+    for (int r = 0; r < nranks; ++r) FS_REQUIRE(ranks[r] >= 0 && (r == 0 || ranks[r - 1] <= ranks[r]), "ranks must be >= 0 and ascending");
+    FS_DIST_BOX(box);
+    FS_FIELD(v, 2); FS_FIELD(p, 1);
+    FS_NO_CAPTURE(fs_dist, "select");
+    FS_DIST_SINGLE_GPU()
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    FS_HIP(hipSetDevice(ctx->device));
+    // the temporary objects of the call: the plane of the box's values, the digit tables of every prefix behind two counters
+    const size_t cells = (size_t)(box[2] - box[0]) * (box[3] - box[1]);
+    const size_t twords = 2 + (size_t)DIST_MAX_RANKS * DIST_DIGITS;
+    DevBuf<double> plane;
+    DevBuf<long long> tables;
+    if (nranks) FS_HIP(plane.alloc(cells * sizeof(double)));
+    FS_HIP(tables.alloc(twords * sizeof(long long)));
+    double *d_plane = plane;
+    long long *d_tot = tables, *d_tab = tables + 2;
+    dim3 grid;
+    const DistWalk walk = dist_walk_of(ctx, box, dist_need(quantity), dx, limit, &grid);
+    FS_HIP(hipMemsetAsync(d_tot, 0, 2 * sizeof(long long), ctx->stream));
+    int rc = by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
+        return launch(ctx, "dist_values", [=] {
+            klaunch(k_dist_values<T>, grid, dim3(256), ctx->stream, ctx->grid(), walk, quantity, (const T *)v->d, (const T *)p->d, d_plane, d_tot);
+        });
+    });
+    long long tot[2] = {0, 0};
+    hipError_t e = rc ? hipSuccess : hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, ctx->stream);
+    hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (rc) return rc;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return hip_fail(e, "fs_dist_select", __FILE__, __LINE__);
+    *n_out = tot[0];
+    *nan_out = tot[1];
+    if (nranks == 0) return FS_OK;
+    FS_REQUIRE(tot[0] > 0, "no selected cell holds a value that is not NaN: there is no order statistic");
+    FS_REQUIRE(ranks[nranks - 1] < tot[0], "rank must be below n, the number of selected cells whose value is not NaN");
+    // one launch per digit: a table per DISTINCT prefix (ranks that still agree share theirs), downloaded, and every rank's digit picked
+    unsigned long long prefix[DIST_MAX_RANKS];
+    long long rest[DIST_MAX_RANKS];
+    std::vector<long long> host((size_t)DIST_MAX_RANKS * DIST_DIGITS);
+    for (int r = 0; r < nranks; ++r) { prefix[r] = 0; rest[r] = ranks[r]; }
+    for (int pass = 0; pass < DIST_PASSES; ++pass) {
+        DistPrefixes pre;
+        int slot[DIST_MAX_RANKS], np = 0;
+        for (int r = 0; r < nranks; ++r) {      // ascending ranks: equal prefixes are neighbours
+            if (r > 0 && prefix[r] == prefix[r - 1]) { slot[r] = slot[r - 1]; continue; }
+            pre.p[np] = prefix[r];
+            slot[r] = np++;
+        }
+        for (int k = np; k < DIST_MAX_RANKS; ++k) pre.p[k] = 0;
+        const size_t bytes = (size_t)np * DIST_DIGITS * sizeof(long long);
+        FS_HIP(hipMemsetAsync(d_tab, 0, bytes, ctx->stream));
+        const dim3 dgrid((unsigned)((cells + DIST_VALUES_PER_WG - 1) / DIST_VALUES_PER_WG), np);
+        rc = launch(ctx, "dist_digits", [=] { klaunch(k_dist_digits, dgrid, dim3(256), ctx->stream, (const double *)d_plane, cells, pass, pre, d_tab); });
+        e = rc ? hipSuccess : hipMemcpyAsync(host.data(), d_tab, bytes, hipMemcpyDeviceToHost, ctx->stream);
+        es = hipStreamSynchronize(ctx->stream);
+        if (rc) return rc;
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) return hip_fail(e, "fs_dist_select", __FILE__, __LINE__);
+        for (int r = 0; r < nranks; ++r) {
+            long long within = 0;
+            const int digit = dist_pick(host.data() + (size_t)slot[r] * DIST_DIGITS, 1 << dist_width(pass), rest[r], &within);
+            if (digit < 0) { set_error("fs_dist_select: the digit counts do not hold the rank (internal)"); return FS_ERR_STATE; }
+            prefix[r] |= (unsigned long long)digit << dist_shift(pass);
+            rest[r] = within;
+        }
+    }
+    for (int r = 0; r < nranks; ++r) values_out[r] = dist_unkey(prefix[r]);
+    return FS_OK;
+}
 
 // ---- flow maps through the resident snapshots (fs_lcs.h) ----------------------------------------------------------------------------------
 

@@ -265,6 +265,17 @@ struct fs_vortex {
     fs::DevBuf<long long> d_state;   // [VX_STATE]
 };
 
+// field distributions (fs_dist_*, fs_dist.h): the tables of every channel - each its bins, then DIST_TAILS words - and the device counters
+struct fs_dist {
+    int nchan = 0;
+    long long every = 1, start = 0;
+    fs_dist_spec spec[4];           // as given to fs_dist_create (DIST_MAX_CHANNELS)
+    double inv[4] = {0, 0, 0, 0}, inv_b[4] = {0, 0, 0, 0};      // bins / (hi - lo) of both sides
+    size_t offset[5] = {0, 0, 0, 0, 0};      // the first word of every channel's table; [nchan]: all words
+    fs::DevBuf<long long> d_tables;  // [offset[nchan]]
+    fs::DevBuf<long long> d_state;   // [DIST_STATE]
+};
+
 namespace fs { struct LoadFace; }      // fs_loads.h (included by fs_diag.hip alone)
 // body surface loads (fs_loads_*, fs_loads.h): the face list of this context's owned rows, the per-face sums, the ring and the device counters
 struct fs_loads {
@@ -306,7 +317,7 @@ struct fs_tracer {
 namespace fs {
 
 // ---- the objects behind the other handles: one registry (fs_ctx::objects, fs_objects.h), one guard, one no-capture check, one free -------------
-enum ObjKind { OBJ_HISTORY, OBJ_LOADS, OBJ_MEAN, OBJ_MODES, OBJ_POD, OBJ_VORTEX, OBJ_FLOWMAP, OBJ_TRACER, OBJ_MG };
+enum ObjKind { OBJ_HISTORY, OBJ_LOADS, OBJ_MEAN, OBJ_MODES, OBJ_POD, OBJ_VORTEX, OBJ_FLOWMAP, OBJ_TRACER, OBJ_MG, OBJ_DIST };
 // kind, noun and stale-handle text of an object type: FS_OBJECT(type, kind, noun, text), once, in the unit that implements the type
 template <typename T> struct ObjInfo;
 #define FS_OBJECT(T, KIND, NOUN, STALE) \

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FS_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libfs_hip.so")     # FS_LIB: A/B builds (tools/)
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _lib = None
 
@@ -122,6 +122,15 @@ _PROTOS = {
     "fs_vortex_label": [_c_vp, _P(ctypes.c_ubyte), _P(_c_int)],
     "fs_vortex_criterion": [_c_vp, _c_int, _c_dbl, _c_dbl, _c_vp, _P(_c_dbl)],
     "fs_vortex_free": [_c_vp, _c_vp],
+    "fs_dist_create": [_c_vp, _c_int, _c_vp, ctypes.c_longlong, ctypes.c_longlong, _P(_c_vp)],
+    "fs_dist_launch": [_c_vp, _c_vp, _c_dbl, _c_dbl, _c_vp, _c_vp],
+    "fs_dist_read": [_c_vp, _c_vp, _c_int, _P(ctypes.c_longlong), _P(ctypes.c_longlong), _P(ctypes.c_longlong), _P(ctypes.c_longlong)],
+    "fs_dist_get": [_c_vp, _c_vp, _P(ctypes.c_longlong)],
+    "fs_dist_set": [_c_vp, _c_vp, _P(ctypes.c_longlong), ctypes.c_longlong, ctypes.c_longlong],
+    "fs_dist_reset": [_c_vp, _c_vp],
+    "fs_dist_free": [_c_vp, _c_vp],
+    "fs_dist_select": [_c_vp, _c_int, _P(_c_int), _c_dbl, _c_dbl, _c_vp, _c_vp, _P(ctypes.c_longlong), _c_int, _P(_c_dbl), _P(ctypes.c_longlong),
+                       _P(ctypes.c_longlong)],
     "fs_flowmap_create": [_c_vp, _P(_c_int), _c_int, _P(_c_vp)],
     "fs_flowmap_advance": [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_int],
     "fs_flowmap_cauchy_green": [_c_vp, _c_vp],

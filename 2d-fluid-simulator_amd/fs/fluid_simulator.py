@@ -17,6 +17,7 @@ from .history import Recorder, body_faces, check_probes
 from .loads import Tracker, body_centroid, face_geometry
 from .modes import Modes, fit as fit_modes, gram_matrix, phasor_steps, reconstruct_weights
 from .pod import Pod
+from . import dist as _dist
 from .vortices import VELOCITY_LIMIT, Vortices, assemble, omega_exponent
 from .pressure_updater import JacobiPressureUpdater, MultigridPressureUpdater, RedBlackSorPressureUpdater
 from .solver import CipMacSolver, DyeCipMacSolver, DyeMacSolver, MacSolver
@@ -95,6 +96,7 @@ class FluidSimulator:
         self._averager = None      # fs.averages.Averager while start_averaging() is on
         self._moder = None         # fs.modes.Modes while start_modes() is on
         self._podr = None          # fs.pod.Pod while start_pod() is on
+        self._distr = None         # fs.dist.Distributions while start_distributions() is on
         self._tracers = None       # fs.tracers.Tracers while seed_tracers() is on
         self._tracker = None       # fs.loads.Tracker while track_body() is on
         self._last_tracker = None  # ... and after stop_body(): what body_loads() / body_surface() still return
@@ -103,9 +105,10 @@ class FluidSimulator:
         self._found_planes = None  # the planes of the last find_vortices()
 
     def _riders(self):
-        """The attached riders (fs.riders.Rider) in their fixed order - history, averages, modes, pod, loads, tracers, vortices: the order of
-        their launches behind the solver step and of their tokens in _signature()."""
-        return [r for r in (self._recorder, self._averager, self._moder, self._podr, self._tracker, self._tracers, self._vortexr) if r is not None]
+        """The attached riders (fs.riders.Rider) in their fixed order - history, averages, modes, pod, distributions, loads, tracers, vortices:
+        the order of their launches behind the solver step and of their tokens in _signature()."""
+        return [r for r in (self._recorder, self._averager, self._moder, self._podr, self._distr, self._tracker, self._tracers, self._vortexr)
+                if r is not None]
 
     def _capturing(self):
         return getattr(self._dev, "capturing", False)
@@ -893,6 +896,110 @@ class FluidSimulator:
         self._not_capturing("vortex_criterion")
         s = self._solver
         return self._dev.vortex_criterion(criterion, s.dx, s.get_fields()[0])
+
+    # -- field distributions (new): histograms accumulated on the device, exact quantiles of the current fields ----------------------------------
+    def start_distributions(self, channels, every=1, start_step=0):
+        """From the next step on, accumulate histograms of the flow over the fluid cells on the device (csrc/fs_dist.h): after every step k
+        (counted from here) with k > start_step and (k - start_step) % every == 0 every channel's table of 64-bit counters takes one count
+        per selected cell.  channels: one dict or a list of 1 to 4, each {"quantity", "bins", "range"[, "box"][, "against": {"quantity",
+        "bins", "range"}]} - quantity one of "u", "w", "p", "speed", "vorticity", "q", "swirl" (the last three as vortex_criterion() and
+        flow_stats() difference them); bins 1 .. 4096 over range = (lo, hi), half-open, required: the bins do not move during a run; box =
+        (x0, y0, x1, y1) in global cells, half-open (default: the whole grid); against: a second quantity for a joint table of bins x bins
+        <= 4096.  The launches are part of the step: they are captured into the replayed graphs, decide on the device whether they sample,
+        and run() is not cut into chunks by them.  Counts are integers: identical between eager steps, replayed graphs and resumed runs.
+        8 bytes per bin of device memory.  Changes no field and no trajectory.  distributions() returns the tables.  Raises while
+        distributions are attached already and during a graph capture; single-GPU contexts only (FsError on slabs)."""
+        dev = self._dev
+        self._not_capturing("start_distributions")
+        self._make_way("_distr", "distributions are attached already: stop_distributions() first (or reset_distributions())")
+        every, start_step = self._cadence(every, start_step)
+        self._distr = _dist.Distributions(dev, dev.dist_create(channels, every, start_step), every, start_step)
+
+    def _dist(self):
+        if self._distr is None:
+            raise RuntimeError("no distributions: call start_distributions() first")
+        return self._distr
+
+    def distributions(self):
+        """The tables so far, one dict per channel: {"counts": int64 (B,) or (Ba, Bb), "below", "above" (joint: "outside"), "nan",
+        "edges" (joint: and "edges_b"), "samples", "sample_steps", "quantity" (joint: a pair), "box"}.  fs.dist.density / cdf / moments /
+        quantile_from_counts work on a 1-D dict.  A download of the tables; not allowed during a graph capture."""
+        self._not_capturing("distributions")
+        return self._dist().data()
+
+    def reset_distributions(self):
+        """Tables and sample count back to zero; the step count and the phase of `every` / `start_step` run on."""
+        self._not_capturing("reset_distributions")
+        self._dist().reset()
+
+    def stop_distributions(self):
+        """Detach the distributions and free their device memory; the cached graphs that hold their launches are freed first.  Nothing is
+        kept on the host: call distributions() before.  Inside a graph capture the device memory is released when the capture ends."""
+        self._detach(self, "_distr", "stop_distributions")
+
+    def histogram(self, quantity, bins, range=None, box=None, against=None):
+        """The histogram of the fields as they are now: the dict distributions() returns for one channel, with "samples" 1 and "sample_steps"
+        [0] (the call counts no steps).  One temporary object, one eager launch, a read and a free: changes no field, no graph and no
+        attached rider, and leaves a deferred limit_field deferred.  range=None (1-D only): the exact minimum and maximum of the values
+        (order_statistics ranks 0 and n - 1) give [min, nextafter(max, +inf)) - ValueError when either is infinite or no value is there.
+        Not allowed during a graph capture."""
+        dev, s = self._dev, self._solver
+        self._not_capturing("histogram")
+        if range is None:
+            if against is not None:
+                raise ValueError("range=None is for 1-D histograms: a joint table needs both ranges")
+            n = self.order_statistics(quantity, (), box)["n"]
+            if n == 0:
+                raise ValueError(f"no selected cell holds a value of {quantity!r}: there is no range to take")
+            lo, hi = self.order_statistics(quantity, (0, n - 1), box)["values"]
+            if not (math.isfinite(lo) and math.isfinite(hi)):
+                raise ValueError(f"the values of {quantity!r} reach ({lo}, {hi}): give a finite range")
+            range = (float(lo), math.nextafter(float(hi), math.inf))
+        spec = {"quantity": quantity, "bins": bins, "range": range, "box": box, "against": against}
+        d = dev.dist_create(spec, 1, 0)
+        try:
+            saved, dev._oplog = getattr(dev, "_oplog", None), None      # (never part of a logged period)
+            try:
+                v, p = s.get_fields()[:2]
+                dev.dist_launch(d, s.dx, v, p)
+            finally:
+                dev._oplog = saved
+            counts, tails, _, samples = dev.dist_read(d, 0)
+        finally:
+            dev.dist_free(d)
+        return _dist.result(dev, d.channels[0], counts, tails, samples, np.zeros(samples, np.int64))
+
+    def order_statistics(self, quantity, ranks, box=None):
+        """Exact order statistics of the fields as they are now: {"values": float64 (R,), the ranks[k]-th smallest (0-based, ascending, at
+        most 8 per call) of the values of `quantity` over the fluid cells of `box` that are not NaN - exactly what np.sort would put there;
+        "n": how many such values; "nan": selected cells whose value is NaN}.  A radix select on the device over a plane of 8 bytes per
+        cell of the box that lives for the call; no field is downloaded.  ValueError for a rank >= n.  Changes nothing, leaves a deferred
+        limit_field deferred.  Not allowed during a graph capture."""
+        self._not_capturing("order_statistics")
+        s = self._solver
+        v, p = s.get_fields()[:2]
+        values, n, nan = self._dev.dist_select(quantity, box, s.dx, v, p, ranks)
+        return {"values": values, "n": n, "nan": nan}
+
+    def quantile(self, quantity, q, box=None, method="linear"):
+        """Quantiles of `quantity` over the fluid cells of `box`, from exact order statistics: q a scalar or a sequence in [0, 1] -> float or
+        float64 array.  With pos = (n - 1) * q as a Python float, a and b the order statistics at floor(pos) and the next rank and g the
+        fractional part: method "lower" a, "higher" b, "nearest" the closer one, "linear" a + (b - a) * g - "lower" / "higher" are
+        np.quantile(values, q, method=...) exactly.  sim.quantile("q", 0.9) is the threshold track_vortices wants, without the download."""
+        if method not in _dist.METHODS:
+            raise ValueError(f"method must be one of {_dist.METHODS}, got {method!r}")
+        qs = [float(x) for x in np.atleast_1d(np.asarray(q, np.float64))]
+        n = self.order_statistics(quantity, (), box)["n"]
+        if n == 0:
+            raise ValueError(f"no selected cell holds a value of {quantity!r}: there is no quantile")
+        pairs = [_dist.rank_pair(n, x) for x in qs]
+        ranks = sorted({k for a, b, _ in pairs for k in (a, b)})
+        found = {}
+        for c in range(0, len(ranks), self._dev.DIST_MAX_RANKS):
+            chunk = ranks[c:c + self._dev.DIST_MAX_RANKS]
+            found.update(zip(chunk, self.order_statistics(quantity, chunk, box)["values"].tolist()))
+        out = np.array([_dist.interpolate(found[a], found[b], g, method) for a, b, g in pairs], np.float64)
+        return float(out[0]) if np.ndim(q) == 0 else out
 
     # -- flow maps and FTLE fields (new): a lattice of particles carried through the POD's resident snapshots on the device --------------
     def flow_map(self, direction="backward", refine=1, box=None, substeps=1, first=None, last=None):

@@ -1,9 +1,11 @@
 """Device side of what rides the step and of the diagnostics (new; the reference has none): flow statistics, the per-step history, the
-body surface loads, the time averages, the harmonic modes, the snapshot POD, the flow maps through its snapshots and the tracer particles.  Two mixins: RideOps is the
+body surface loads, the time averages, the harmonic modes, the snapshot POD, the flow maps through its snapshots, the field distributions and the tracer particles.  Two mixins: RideOps is the
 backend-agnostic host logic fs.runtime.DeviceBase inherits (slab partition, combination over ranks, argument checks, the op log of a logged period), NativeRideOps the `_p_*` primitives
 fs.runtime.Device binds to libfs_hip.so; the stand-in devices of the CPU tests override those.  fs.runtime re-exports every name here."""
+import collections
 import ctypes
 import itertools
+import math
 
 import numpy as np
 
@@ -70,6 +72,28 @@ class Vortex(_Handle):
         self.min_area, self.max_vortices, self.max_components, self.capacity = min_area, max_vortices, max_components, capacity
 
 
+class Dist(_Handle):
+    """Device tables of the field distributions (DeviceBase.dist_create): handle, the channels as dist_channel() returns them, every, start."""
+
+    def __init__(self, h, channels, every, start):
+        super().__init__(h)
+        self.channels, self.every, self.start = tuple(channels), every, start
+        self.words = sum(c.bins * max(1, c.bins_b) + RideOps.DIST_NTAIL for c in channels)      # (fs_dist_get / fs_dist_set)
+
+
+class DistChannel(collections.namedtuple("DistChannel", "quantity bins lo hi quantity_b bins_b lo_b hi_b box")):
+    """One table: quantity / quantity_b are indices into RideOps.DIST_QUANTITIES (quantity_b -1 and bins_b 0: a 1-D table), box x0, y0, x1, y1."""
+    __slots__ = ()
+
+    @property
+    def joint(self):
+        return self.quantity_b >= 0
+
+    @property
+    def shape(self):
+        return (self.bins, self.bins_b) if self.joint else (self.bins,)
+
+
 class FlowMap(_Handle):
     """A device lattice of flow-map nodes (DeviceBase.flowmap_create): handle, cell box, refine, and the lattice (nx, ny)."""
 
@@ -97,7 +121,7 @@ class History(_Handle):
 
 
 class RideOps:
-    """flow_stats and the history_* / loads_* / mean_* / modes_* / pod_* / flowmap_* / tracer_* calls of DeviceBase."""
+    """flow_stats and the history_* / loads_* / mean_* / modes_* / pod_* / flowmap_* / dist_* / tracer_* calls of DeviceBase."""
 
     # (The tracer calls reach these through the class - RideOps._host_only(self, ...) - as they always reached _tracer_host_call: the CPU
     #  tests check their refusals on objects that are no devices.)
@@ -632,6 +656,127 @@ class RideOps:
     def vortex_free(self, vx):
         self._release(vx, self._p_vortex_free)
 
+    # ---- field distributions (include/fs_hip.h fs_dist_*): histograms accumulated on the device, exact order statistics; csrc/fs_dist.h ----
+    DIST_QUANTITIES = ("u", "w", "p", "speed", "vorticity", "q", "swirl")
+    DIST_MAX_BINS, DIST_MAX_CHANNELS, DIST_MAX_RANKS, DIST_NTAIL = 4096, 4, 8, 4
+
+    def _dist_host_call(self, what):
+        RideOps._host_only(self, f"{what} during a graph capture")
+        if self.nranks > 1:
+            raise _lib.FsError("field distributions need a single-GPU context: on slabs the tables would have to be added across ranks (not implemented)")
+
+    def _dist_quantity(self, quantity):
+        if quantity not in RideOps.DIST_QUANTITIES:
+            raise ValueError(f"quantity must be one of {RideOps.DIST_QUANTITIES}, got {quantity!r}")
+        return RideOps.DIST_QUANTITIES.index(quantity)
+
+    def _dist_box(self, box):
+        if box is None:
+            return (0, 0, self.nx, self.ny)
+        box = tuple(int(b) for b in box)
+        if len(box) != 4 or not (0 <= box[0] < box[2] <= self.nx and 0 <= box[1] < box[3] <= self.ny):
+            raise ValueError(f"box must be (x0, y0, x1, y1) with 0 <= x0 < x1 <= {self.nx} and 0 <= y0 < y1 <= {self.ny}, got {box}")
+        return box
+
+    def _dist_side(self, spec):
+        q = RideOps._dist_quantity(self, spec.get("quantity"))
+        bins = int(spec.get("bins", 0))
+        if not 1 <= bins <= RideOps.DIST_MAX_BINS:
+            raise ValueError(f"bins must be 1 .. {RideOps.DIST_MAX_BINS}, got {bins}")
+        if spec.get("range") is None:
+            raise ValueError("range = (lo, hi) must be given: the bins of an accumulated table do not move")
+        lo, hi = (float(x) for x in spec["range"])
+        if not (math.isfinite(lo) and math.isfinite(hi)):
+            raise ValueError(f"range must be finite, got ({lo}, {hi})")
+        if not lo < hi:
+            raise ValueError(f"range must satisfy lo < hi, got ({lo}, {hi})")
+        inv = bins / (hi - lo) if math.isfinite(hi - lo) else 0.0
+        if not (math.isfinite(inv) and inv > 0.0):
+            raise ValueError(f"range ({lo}, {hi}) is too narrow or too wide: bins / (hi - lo) must be finite and positive")
+        return q, bins, lo, hi
+
+    def dist_channel(self, spec):
+        """{"quantity", "bins", "range"[, "box"][, "against": {"quantity", "bins", "range"}]} -> DistChannel, checked (ValueError)."""
+        if not isinstance(spec, dict):
+            raise ValueError(f"a channel is a dict with quantity, bins and range, got {spec!r}")
+        unknown = set(spec) - {"quantity", "bins", "range", "box", "against"}
+        if unknown:
+            raise ValueError(f"unknown channel keys {sorted(unknown)}")
+        a = RideOps._dist_side(self, spec)
+        b = (-1, 0, 0.0, 0.0)
+        if spec.get("against") is not None:
+            b = RideOps._dist_side(self, spec["against"])
+            if a[1] * b[1] > RideOps.DIST_MAX_BINS:
+                raise ValueError(f"a joint table holds at most {RideOps.DIST_MAX_BINS} bins, got {a[1]} x {b[1]}")
+        return DistChannel(*a, *b, RideOps._dist_box(self, spec.get("box")))
+
+    def dist_create(self, channels, every=1, start=0):
+        """Device tables for FluidSimulator.start_distributions / histogram: 1 .. DIST_MAX_CHANNELS channels (dicts, see dist_channel), 64-bit
+        counters, zeroed.  Launch n (from 0) of dist_launch samples when n + 1 > start and (n + 1 - start) % every == 0.  Single-context
+        grids only (FsError on a slab); not allowed during a graph capture."""
+        RideOps._dist_host_call(self, "dist_create")      # (through the class, as the tracer calls: the tests ask objects that are no devices)
+        channels = [channels] if isinstance(channels, dict) else list(channels)
+        if not 1 <= len(channels) <= RideOps.DIST_MAX_CHANNELS:
+            raise ValueError(f"1 .. {RideOps.DIST_MAX_CHANNELS} channels, got {len(channels)}")
+        chans = [RideOps.dist_channel(self, c) for c in channels]
+        every, start = RideOps._check_cadence(every, start)
+        h = self._p_dist_create(chans, every, start)
+        return self._adopt(h, Dist(h, chans, every, start))
+
+    def dist_launch(self, d, dx, v, p):
+        """The launches of one step: one pass per channel that adds the cells' bins to its table when this launch samples, then the tick
+        that advances the counters on the device.  A limit_field v still owes stays deferred: the kernel limits the values it reads.  Not
+        a _run: no flush, no exchange, no ghost row (writes no field)."""
+        self._ride("dist_launch", (d._h, self._limit_of(v), float(dx), v._h, p._h))
+
+    def dist_read(self, d, chan):
+        """-> (counts int64 of the channel's shape - (B,) or (Ba, Bb) -, tails int64 (4,): below, above, nan, 0 - joint: outside, 0, nan, 0 -,
+        launches, samples).  Not allowed during a graph capture."""
+        self._host_only("dist_read during a graph capture: the tables are a download (read between captures / replays)")
+        c = d.channels[chan]
+        counts, tails, launches, samples = self._p_dist_read(d._h, chan, c.bins * max(1, c.bins_b))
+        if c.joint:
+            counts = np.ascontiguousarray(counts.reshape(c.bins_b, c.bins).T)      # (bin bb * Ba + ba)
+        return counts, tails, int(launches), int(samples)
+
+    def dist_get(self, d):
+        """-> (every table and its tails as one int64 array, launches, samples), for checkpoints."""
+        self._host_only("dist_get during a graph capture")
+        _, _, launches, samples = self._p_dist_read(d._h, 0, 0)
+        return self._p_dist_get(d._h, d.words), int(launches), int(samples)
+
+    def dist_set(self, d, words, launches, samples):
+        """Restore what dist_get returned (resume)."""
+        self._host_only("dist_set during a graph capture")
+        words = np.ascontiguousarray(words, np.int64)
+        if words.shape != (d.words,):
+            raise ValueError(f"expected {d.words} table words, got {words.shape}")
+        launches, samples = self._check_counters(launches, samples)
+        self._p_dist_set(d._h, words, launches, samples)
+
+    def dist_reset(self, d):
+        """Tables and sample count to zero; the launch count runs on.  Not allowed during a graph capture."""
+        self._host_only("dist_reset during a graph capture")
+        self._p_dist_reset(d._h)
+
+    def dist_free(self, d):
+        self._release(d, self._p_dist_free)
+
+    def dist_select(self, quantity, box, dx, v, p, ranks):
+        """Exact order statistics of `quantity` over the fluid cells of `box` (None: the whole grid): -> (values float64 (R,), n, nan) with
+        values[k] the ranks[k]-th smallest (0-based, ascending, at most DIST_MAX_RANKS) of the n values that are not NaN, as a full sort
+        would place it; nan: selected cells whose value is NaN.  ranks=(): n and nan alone.  ValueError for a rank >= n (and for any rank
+        when n == 0).  8 bytes per cell of the box on the device for the duration of the call."""
+        RideOps._dist_host_call(self, "dist_select")
+        q = RideOps._dist_quantity(self, quantity)
+        box = RideOps._dist_box(self, box)
+        ranks = [int(r) for r in ranks]
+        if len(ranks) > RideOps.DIST_MAX_RANKS:
+            raise ValueError(f"at most {RideOps.DIST_MAX_RANKS} ranks per call, got {len(ranks)}")
+        if any(r < 0 for r in ranks) or any(a > b for a, b in zip(ranks, ranks[1:])):
+            raise ValueError(f"ranks must be >= 0 and ascending, got {ranks}")
+        return self._p_dist_select(q, box, self._limit_of(v), float(dx), v._h, p._h, ranks)
+
     # ---- flow maps (include/fs_hip.h fs_flowmap_*): a lattice of particles carried through the resident snapshots of a POD; csrc/fs_lcs.h ----
     def flowmap_create(self, box=None, refine=1):
         """A device lattice for FluidSimulator.flow_map: refine x refine nodes per cell of the cell box (x0, y0, x1, y1) (None: the whole
@@ -882,6 +1027,12 @@ class RideOps:
             tr.accum = None
 
 
+class _DistSpec(ctypes.Structure):
+    """fs_dist_spec of include/fs_hip.h."""
+    _fields_ = [("quantity", ctypes.c_int), ("bins", ctypes.c_int), ("quantity_b", ctypes.c_int), ("bins_b", ctypes.c_int), ("box", ctypes.c_int * 4),
+                ("lo", ctypes.c_double), ("hi", ctypes.c_double), ("lo_b", ctypes.c_double), ("hi_b", ctypes.c_double)]
+
+
 class NativeRideOps:
     """The primitives of RideOps on libfs_hip.so (self._ctx: the library's context)."""
 
@@ -1068,6 +1219,52 @@ class NativeRideOps:
     def _p_vortex_free(self, h):
         if self._ctx is not None:
             _lib.call("fs_vortex_free", self._ctx, h)
+
+    def _p_dist_create(self, chans, every, start):
+        h = ctypes.c_void_p()
+        specs = (_DistSpec * len(chans))()
+        for s, c in zip(specs, chans):
+            s.quantity, s.bins, s.quantity_b, s.bins_b = c.quantity, c.bins, c.quantity_b, c.bins_b
+            s.box[:] = c.box
+            s.lo, s.hi, s.lo_b, s.hi_b = c.lo, c.hi, c.lo_b, c.hi_b
+        _lib.call("fs_dist_create", self._ctx, len(chans), ctypes.cast(specs, ctypes.c_void_p), every, start, ctypes.byref(h))
+        return h
+
+    def _p_dist_read(self, h, chan, bins):
+        counts, tails = np.zeros(bins, np.int64), np.zeros(self.DIST_NTAIL, np.int64)
+        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
+        lp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))
+        _lib.call("fs_dist_read", self._ctx, h, chan, lp(counts) if bins else None, lp(tails) if bins else None, ctypes.byref(launches),
+                  ctypes.byref(samples))
+        return counts, tails, launches.value, samples.value
+
+    def _p_dist_get(self, h, words):
+        out = np.empty(words, np.int64)
+        _lib.call("fs_dist_get", self._ctx, h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)))
+        return out
+
+    def _p_dist_set(self, h, words, launches, samples):
+        _lib.call("fs_dist_set", self._ctx, h, words.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), launches, samples)
+
+    def _p_dist_reset(self, h):
+        _lib.call("fs_dist_reset", self._ctx, h)
+
+    def _p_dist_free(self, h):
+        if self._ctx is not None:
+            _lib.call("fs_dist_free", self._ctx, h)
+
+    def _p_dist_select(self, q, box, limit, dx, vh, ph, ranks):
+        r = (ctypes.c_longlong * max(1, len(ranks)))(*ranks)
+        out = np.empty(len(ranks), np.float64)
+        n, nan = ctypes.c_longlong(-1), ctypes.c_longlong(0)
+        try:
+            _lib.call("fs_dist_select", self._ctx, q, (ctypes.c_int * 4)(*box), limit, dx, vh, ph, r, len(ranks),
+                      out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(n), ctypes.byref(nan))
+        except _lib.FsError:
+            if ranks and 0 <= n.value <= ranks[-1]:      # (the library wrote n before it looked at the ranks)
+                raise ValueError(f"rank {ranks[-1]} >= n = {n.value}, the number of selected cells whose value is not NaN") from None
+            raise
+        return out, n.value, nan.value
 
     def _p_flowmap_create(self, box, refine):
         h = ctypes.c_void_p()

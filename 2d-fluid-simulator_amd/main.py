@@ -32,6 +32,9 @@ The reference opens a GGUI window and steps forever; here the loop runs `--steps
   * identify and track the vortices (`--vortices-every N --vortex-threshold T`, `--vortex-criterion`, `--vortex-min-area`, `--vortex-max`):
     criterion, connected components and per-vortex integer records on the GPU (csrc/fs_vortex.h), written with the track id of every
     record to `--vortices-file` (.npz) at the end of the run; the samples travel with `--save-state` / `--load-state`
+  * accumulate histograms of the flow over the fluid cells on the GPU (`--dist quantity:bins:lo:hi`, up to 4 times; `qa:ba:lo:hi,qb:bb:lo:hi`
+    for a joint table; `--dist-every`, `--dist-start`, `--dist-box x0,y0,x1,y1`): integer counts (csrc/fs_dist.h), written to `--dist-file`
+    (.npz) at the end of the run; the tables travel with `--save-state` / `--load-state`.
   * track the complete load on a body (`--body` with `--loads-every N`): pressure and viscous force, their moments about `--loads-center`,
     and the mean / rms pressure and wall shear of every face of the surface, gathered on the GPU and written to `--loads-file` (.npz) at
     the end of the run, with Cd, Cl, Cm, Cp and Cf when `--loads-ref U,L` gives the reference speed and length; the per-face sums and
@@ -126,6 +129,16 @@ def build_parser():
                    help=".npz of the POD: energies, fraction, coefficients, gram, sample_steps, samples, steps, u, w, p (the first K modes, "
                         "(K, X, Y) each), mean_u / _w / _p, mask, dt, dx, every, start (default: <out>/pod.npz); "
                         "with -vis 0 / 1 / 2 given, or --frame-every, also the images pod_mode_<k>.png")
+    p.add_argument("--dist", type=str, action="append", default=[], metavar="SPEC",
+                   help="accumulate a histogram over the fluid cells on the GPU (FluidSimulator.start_distributions): SPEC is quantity:bins:lo:hi "
+                        "with quantity one of u, w, p, speed, vorticity, q, swirl, bins 1 .. 4096 over [lo, hi); qa:ba:lo:hi,qb:bb:lo:hi is the "
+                        "joint table of two quantities (ba * bb <= 4096); may be repeated up to 4 times")
+    p.add_argument("--dist-every", type=int, default=None, help="sample after every N-th step (default 1)")
+    p.add_argument("--dist-start", type=int, default=None, help="steps of the run (restarts included) to leave out before the first sample (default 0)")
+    p.add_argument("--dist-box", type=str, default=None, metavar="X0,Y0,X1,Y1", help="cells of every --dist table, half-open (default: the whole grid)")
+    p.add_argument("--dist-file", type=str, default=None,
+                   help=".npz of the tables: per channel k c<k>.counts, c<k>.edges, c<k>.nan, c<k>.quantity, c<k>.box and c<k>.below / c<k>.above "
+                        "(a joint one: c<k>.outside, c<k>.edges_b), then samples, sample_steps, every, start, dt, dx (default: <out>/dist.npz)")
     p.add_argument("--ftle", choices=("forward", "backward", "both"), default=None,
                    help="at the end of the run, carry a lattice of particles through the resident POD snapshots on the GPU (needs --pod-snapshots) and "
                         "write the finite-time Lyapunov exponent field (FluidSimulator.flow_map): backward marks the attracting structures - dye "
@@ -276,6 +289,89 @@ def saved_vortices(path):
     if "vortex.words" not in z.files:
         return None
     return (str(z["vortex.criterion"]), float(z["vortex.threshold"]), int(z["vortex.every"]), int(z["vortex.min_area"]), int(z["vortex.max_vortices"]))
+
+
+def parse_dist(parser, specs, box, nx, ny):
+    """The --dist flags -> the channel dicts of FluidSimulator.start_distributions, checked against a grid of (nx, ny) cells."""
+    from fs.ride_ops import RideOps
+
+    class _Grid:
+        pass
+    grid = _Grid()
+    grid.nx, grid.ny = nx, ny
+    if len(specs) > RideOps.DIST_MAX_CHANNELS:
+        parser.error(f"--dist: at most {RideOps.DIST_MAX_CHANNELS} tables")
+    if box is not None:
+        try:
+            box = tuple(int(c) for c in box.split(","))
+            if len(box) != 4:
+                raise ValueError
+        except ValueError:
+            parser.error(f"--dist-box {box}: expected X0,Y0,X1,Y1")
+    chans = []
+    for spec in specs:
+        sides = []
+        for side in spec.split(","):
+            part = side.split(":")
+            try:
+                if len(part) != 4:
+                    raise ValueError
+                sides.append({"quantity": part[0], "bins": int(part[1]), "range": (float(part[2]), float(part[3]))})
+            except ValueError:
+                parser.error(f"--dist {spec}: expected quantity:bins:lo:hi, or two of them separated by a comma")
+        if len(sides) > 2:
+            parser.error(f"--dist {spec}: a joint table has two quantities")
+        chan = dict(sides[0], box=box)
+        if len(sides) == 2:
+            chan["against"] = sides[1]
+        try:
+            RideOps.dist_channel(grid, chan)
+        except ValueError as e:
+            parser.error(f"--dist {spec}: {e}")
+        chans.append(chan)
+    return chans, [RideOps.dist_channel(grid, c) for c in chans]
+
+
+def saved_dist(path):
+    """(channels array, every, start) of the distributions a checkpoint holds, or None."""
+    z = np.load(_npz_path(path))
+    if "dist.tables" not in z.files:
+        return None
+    return (np.asarray(z["dist.channels"], np.float64), int(z["dist.every"]), int(z["dist.start"]))
+
+
+def dist_flags(held):
+    """The flags that continue the distributions of a checkpoint (saved_dist), for the refusal's message."""
+    from fs.ride_ops import RideOps
+    names = RideOps.DIST_QUANTITIES
+    out = []
+    for row in held[0]:
+        side = f"{names[int(row[0])]}:{int(row[1])}:{float(row[2])!r}:{float(row[3])!r}"
+        if row[4] >= 0:
+            side += f",{names[int(row[4])]}:{int(row[5])}:{float(row[6])!r}:{float(row[7])!r}"
+        out.append(f"--dist {side}")
+    out.append("--dist-box " + ",".join(str(int(b)) for b in held[0][0][8:12]))
+    return " ".join(out) + f" --dist-every {held[1]} --dist-start {held[2]}"
+
+
+def load_dist(sim, path):
+    """Restore the tables and counters of the checkpoint's distributions into the attached ones -> whether the checkpoint held any."""
+    z = np.load(_npz_path(path))
+    if "dist.tables" not in z.files:
+        return False
+    sim._distr.restore(z)
+    return True
+
+
+def dist_file_arrays(sim):
+    """The arrays of --dist-file from FluidSimulator.distributions()."""
+    out = {}
+    for k, d in enumerate(sim.distributions()):
+        for name in ("counts", "edges", "edges_b", "below", "above", "outside", "nan", "quantity", "box"):
+            if name in d:
+                out[f"c{k}.{name}"] = np.asarray(d[name])
+        out["samples"], out["sample_steps"] = np.array(d["samples"]), d["sample_steps"]
+    return out
 
 
 def _lib_error():
@@ -605,6 +701,23 @@ def main(argv=None):
                 print(f"--load-state {args.load_state}: its POD snapshots were taken with --pod-snapshots {held[0]} --pod-every {held[1]} --pod-start "
                       f"{held[2]}; continue with those or sample without the checkpoint's snapshots", file=sys.stderr)
                 sys.exit(2)
+    dist_every, dist_start = (1 if args.dist_every is None else args.dist_every), args.dist_start or 0
+    dist_channels = None
+    if not args.dist:
+        if args.dist_every is not None or args.dist_start is not None or args.dist_box or args.dist_file:
+            parser.error("--dist-every, --dist-start, --dist-box and --dist-file need --dist SPEC")
+    else:
+        if dist_every < 1 or dist_start < 0:
+            parser.error("--dist-every must be >= 1 and --dist-start >= 0")
+        dist_channels, checked = parse_dist(parser, args.dist, args.dist_box, 2 * res, res)
+        if args.load_state:
+            held = saved_dist(args.load_state)
+            from fs.dist import channels_array
+            mine = channels_array(checked)
+            if held is not None and (held[0].shape != mine.shape or not np.array_equal(held[0], mine) or held[1:] != (dist_every, dist_start)):
+                print(f"--load-state {args.load_state}: its distributions were accumulated with {dist_flags(held)}; continue with those or "
+                      "accumulate without the checkpoint's tables", file=sys.stderr)
+                sys.exit(2)
     ftle_refine, ftle_substeps = (1 if args.ftle_refine is None else args.ftle_refine), (1 if args.ftle_substeps is None else args.ftle_substeps)
     if args.ftle is None:
         if args.ftle_refine is not None or args.ftle_substeps is not None or args.ftle_file:
@@ -757,6 +870,19 @@ def main(argv=None):
             for k in range(arrays["coefficients"].shape[1]):
                 save_png(fields_frame(sim, args.visualization, *sim.pod_fields(k)), out / f"pod_mode_{k}.png")
 
+    dist_file = None
+    if dist_channels:
+        dist_file = Path(args.dist_file) if args.dist_file else out / "dist.npz"
+        sim.start_distributions(dist_channels, every=dist_every, start_step=dist_start)
+        if args.load_state and load_dist(sim, args.load_state):
+            print(f"distributions: continuing the checkpoint's ({sim.distributions()[0]['samples']} samples so far)")
+
+    def write_dist():
+        if dist_file is None:
+            return
+        dist_file.parent.mkdir(parents=True, exist_ok=True)
+        np.savez(str(dist_file), dt=np.array(dt), dx=np.array(dx), every=np.array(dist_every), start=np.array(dist_start), **dist_file_arrays(sim))
+
     def write_ftle():
         if args.ftle is None:
             return
@@ -900,6 +1026,7 @@ def main(argv=None):
             write_mean()
             write_modes()
             write_pod()
+            write_dist()
             write_ftle()
             write_loads()
             write_vortices()
@@ -946,6 +1073,7 @@ def main(argv=None):
     write_mean()
     write_modes()
     write_pod()
+    write_dist()
     write_ftle()
     write_loads()
     write_vortices()

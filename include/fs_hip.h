@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 23
+#define FS_ABI_VERSION 24
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -499,6 +499,50 @@ int fs_vortex_set(fs_ctx *ctx, fs_vortex *vx, long long launches);
 int fs_vortex_label(fs_ctx *ctx, const unsigned char *flags, int *labels);
 int fs_vortex_criterion(fs_ctx *ctx, int which, double limit, double dx, const fs_field *v, double *out);
 int fs_vortex_free(fs_ctx *ctx, fs_vortex *vx);
+
+/* Field distributions (new, ABI 24): histograms and joint histograms of a quantity over the fluid cells, accumulated over a run by launches that
+ * can be captured in a hipGraph, and exact order statistics of the current fields (kernels, the value of a cell, the bin rule and the radix
+ * select: csrc/fs_dist.h).  Counts are 64-bit integers and an order statistic is one stored value: both are exact and do not depend on the
+ * order of any atomic.  Quantities: 0 "u", 1 "w", 2 "p", 3 "speed", 4 "vorticity", 5 "q", 6 "swirl", as doubles; the selection is the fluid
+ * cells (mask 0) of a half-open box x0, y0, x1, y1 of global cells (0 <= x0 < x1 <= X, 0 <= y0 < y1 <= Y, else FS_ERR_ARG).  NaN values are
+ * counted apart; +-Inf are values.  Single-GPU contexts: create and select return FS_ERR_UNSUPPORTED on a slab context.
+ * create:  1 <= nchan <= FS_DIST_MAX_CHANNELS tables.  spec: quantity over [lo, hi) in `bins` bins, 1 <= bins <= FS_DIST_MAX_BINS, lo < hi
+ *          finite with a finite positive bins / (hi - lo); quantity_b >= 0 makes the table joint with quantity_b over [lo_b, hi_b) in bins_b
+ *          bins, bins * bins_b <= FS_DIST_MAX_BINS, bin bb * bins + ba (quantity_b < 0: 1-D, the _b members are not read).  every >= 1,
+ *          start >= 0 (the sampling rule of fs_mean_create).  Tables and counters start at zero.
+ * launch:  one pass per channel and a one-lane tick, nothing else (no allocation, copy or synchronisation: capturable); the passes return
+ *          at once unless this launch samples.  limit > 0: v still owes limit_field(limit).  Needs the mask.
+ * read:    synchronises; counts: the bins (bins, or bins * bins_b) words of channel `chan`; tails: FS_DIST_NTAIL words {below, above, nan, 0}
+ *          - joint: {outside, 0, nan, 0}; either may be NULL.  Resets nothing.
+ * get / set: all tables, channel after channel, each its bins then its FS_DIST_NTAIL tail words, for checkpoints;
+ *          set also takes the counters, 0 <= samples <= launches.
+ * reset:   tables and sample count to zero; the launch count runs on.
+ * select:  the ranks[k]-th smallest (0-based; 0 <= nranks <= FS_DIST_MAX_RANKS, ascending, equal ones allowed) of the values of `quantity`
+ *          on the selection that are not NaN, by a radix select over their order-preserving keys -> values_out[k], exactly the double a full
+ *          sort would put there; *n: how many such values, *nan: selected cells whose value is NaN (both written before the ranks are
+ *          looked at).  n == 0 with nranks > 0, or a rank >= n: FS_ERR_ARG.  Extra device memory of 8 bytes per cell of the box for the
+ *          duration of the call (nranks == 0: none); synchronises.
+ * free:    as fs_mean_free (during a capture the release is deferred to its end).
+ * Everything but launch and free returns FS_ERR_STATE during graph capture / tape recording.                                             */
+#define FS_DIST_MAX_BINS 4096
+#define FS_DIST_MAX_CHANNELS 4
+#define FS_DIST_MAX_RANKS 8
+#define FS_DIST_NTAIL 4
+typedef struct fs_dist fs_dist;
+typedef struct fs_dist_spec {
+    int quantity, bins, quantity_b, bins_b;
+    int box[4];
+    double lo, hi, lo_b, hi_b;
+} fs_dist_spec;
+int fs_dist_create(fs_ctx *ctx, int nchan, const fs_dist_spec *specs, long long every, long long start, fs_dist **out);
+int fs_dist_launch(fs_ctx *ctx, fs_dist *d, double limit, double dx, const fs_field *v, const fs_field *p);
+int fs_dist_read(fs_ctx *ctx, fs_dist *d, int chan, long long *counts, long long *tails, long long *launches, long long *samples);
+int fs_dist_get(fs_ctx *ctx, fs_dist *d, long long *words_out);
+int fs_dist_set(fs_ctx *ctx, fs_dist *d, const long long *words_in, long long launches, long long samples);
+int fs_dist_reset(fs_ctx *ctx, fs_dist *d);
+int fs_dist_free(fs_ctx *ctx, fs_dist *d);
+int fs_dist_select(fs_ctx *ctx, int quantity, const int *box, double limit, double dx, const fs_field *v, const fs_field *p,
+                   const long long *ranks, int nranks, double *values_out, long long *n, long long *nan);
 
 /* Multigrid pressure correction (new, ABI 19): one W-cycle (two coarse visits per level) on a mask-aware hierarchy of coarse levels, for the
  * third pressure updater (fs/pressure_updater.py MultigridPressureUpdater; kernels and operation order: csrc/fs_mg.h).  Single-GPU contexts.

@@ -1,0 +1,142 @@
+"""CLI field distributions (2d-fluid-simulator_amd/main.py --dist / --dist-every / --dist-start / --dist-box / --dist-file, the tables in
+--save-state / --load-state)."""
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+from conftest import REPO
+
+RES = 20
+SPEED, JOINT = "speed:64:0:1.5", "u:16:-0.5:1.5,vorticity:32:-20:20"
+
+
+def _cli():
+    spec = importlib.util.spec_from_file_location("fs_cli_main_dist", os.path.join(REPO, "2d-fluid-simulator_amd", "main.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_flags_parse_and_refusals(tmp_path):
+    cli = _cli()
+    a = cli.build_parser().parse_args([])
+    assert (a.dist, a.dist_every, a.dist_start, a.dist_box, a.dist_file) == ([], None, None, None, None)
+    a = cli.build_parser().parse_args(["--dist", SPEED, "--dist", JOINT, "--dist-every", "5", "--dist-start", "100", "--dist-box", "1,2,3,4",
+                                       "--dist-file", "d.npz"])
+    assert (a.dist, a.dist_every, a.dist_start, a.dist_box, a.dist_file) == ([SPEED, JOINT], 5, 100, "1,2,3,4", "d.npz")
+    chans, checked = cli.parse_dist(cli.build_parser(), [SPEED, JOINT], "1,2,30,14", 2 * RES, RES)
+    assert chans[0] == {"quantity": "speed", "bins": 64, "range": (0.0, 1.5), "box": (1, 2, 30, 14)}
+    assert chans[1]["against"] == {"quantity": "vorticity", "bins": 32, "range": (-20.0, 20.0)} and chans[1]["quantity"] == "u"
+    assert checked[1].shape == (16, 32) and checked[0].box == (1, 2, 30, 14)
+    assert cli.parse_dist(cli.build_parser(), [SPEED], None, 2 * RES, RES)[1][0].box == (0, 0, 2 * RES, RES)
+    for argv in (["--dist-every", "4"],                            # without --dist
+                 ["--dist-start", "4"],
+                 ["--dist-box", "0,0,4,4"],
+                 ["--dist-file", str(tmp_path / "d.npz")],
+                 ["--dist", SPEED, "--dist-every", "0"],
+                 ["--dist", SPEED, "--dist-start", "-1"],
+                 ["--dist", "speed:64:0"],                         # the syntax
+                 ["--dist", "speed:x:0:1"],
+                 ["--dist", "speed:64:0:1,u:4:0:1,w:4:0:1"],
+                 ["--dist", "energy:64:0:1"],                      # the values
+                 ["--dist", "speed:0:0:1"],
+                 ["--dist", "speed:4097:0:1"],
+                 ["--dist", "speed:64:1:1"],
+                 ["--dist", "speed:64:0:inf"],
+                 ["--dist", "speed:64:nan:1"],
+                 ["--dist", "u:65:0:1,w:64:0:1"],                  # a joint table beyond 4096 bins
+                 ["--dist", SPEED, "--dist-box", "0,0,4"],
+                 ["--dist", SPEED, "--dist-box", "0,0,41,20"],     # beyond the grid of res 20
+                 ["--dist", SPEED, "--dist-box", "5,5,5,9"],       # empty
+                 ["--dist", SPEED, "--dist", SPEED, "--dist", SPEED, "--dist", SPEED, "--dist", SPEED]):
+        with pytest.raises(SystemExit) as e:
+            cli.main(argv + ["-res", str(RES), "--out", str(tmp_path)])
+        assert e.value.code == 2, argv
+
+
+def test_checkpoint_with_other_channels_is_refused(tmp_path, capsys):
+    """--load-state of a checkpoint whose tables were accumulated with other channels, every or start: message and exit status 2, before any
+    device work."""
+    from fs.dist import channels_array
+    cli = _cli()
+    _, checked = cli.parse_dist(cli.build_parser(), [SPEED, JOINT], None, 2 * RES, RES)
+    ck = tmp_path / "ck.npz"
+    np.savez(str(ck), step=np.array(10), **{"dist.tables": np.zeros(64 + 4 + 16 * 32 + 4, np.int64), "dist.launches": np.array(10),
+                                            "dist.samples": np.array(3), "dist.base": np.array(0), "dist.channels": channels_array(checked),
+                                            "dist.every": np.array(3), "dist.start": np.array(1)})
+    held = cli.saved_dist(str(ck))
+    assert held[1:] == (3, 1) and held[0].shape == (2, 12)
+    same = ["--dist", SPEED, "--dist", JOINT]
+    for argv in (same + ["--dist-every", "2", "--dist-start", "1"], same + ["--dist-every", "3"], ["--dist", SPEED, "--dist-every", "3", "--dist-start", "1"],
+                 ["--dist", JOINT, "--dist", SPEED, "--dist-every", "3", "--dist-start", "1"], same + ["--dist-every", "3", "--dist-start", "1", "--dist-box", "0,0,4,4"],
+                 ["--dist", "speed:64:0:1.25", "--dist", JOINT, "--dist-every", "3", "--dist-start", "1"]):
+        with pytest.raises(SystemExit) as e:
+            cli.main(argv + ["-res", str(RES), "--load-state", str(ck), "--out", str(tmp_path)])
+        assert e.value.code == 2
+        err = capsys.readouterr().err
+        assert "--dist speed:64:0.0:1.5 --dist u:16:-0.5:1.5,vorticity:32:-20.0:20.0 --dist-box 0,0,40,20 --dist-every 3 --dist-start 1" in err
+    plain = tmp_path / "plain.npz"
+    np.savez(str(plain), step=np.array(10))
+    assert cli.saved_dist(str(plain)) is None
+
+
+@pytest.mark.gpu
+def test_dist_file(tmp_path, hip_lib):
+    import fs
+    cli = _cli()
+    a = tmp_path / "a"
+    cli.main(["-res", str(RES), "--dist", SPEED, "--dist", JOINT, "--dist-every", "2", "--dist-box", "2,1,38,19", "--steps", "21", "--out", str(a),
+              "--graph"])
+    m = np.load(a / "dist.npz")
+    assert set(m.files) == {"c0.counts", "c0.edges", "c0.below", "c0.above", "c0.nan", "c0.quantity", "c0.box", "c1.counts", "c1.edges", "c1.edges_b",
+                            "c1.outside", "c1.nan", "c1.quantity", "c1.box", "samples", "sample_steps", "every", "start", "dt", "dx"}
+    assert int(m["samples"]) == 10 and m["sample_steps"].tolist() == list(range(2, 21, 2)) and (int(m["every"]), int(m["start"])) == (2, 0)
+    assert m["c0.counts"].shape == (64,) and m["c1.counts"].shape == (16, 32) and m["c0.counts"].dtype == np.int64
+    assert m["c0.box"].tolist() == [2, 1, 38, 19] and str(m["c0.quantity"]) == "speed" and m["c1.quantity"].tolist() == ["u", "vorticity"]
+    assert m["c0.counts"].sum() > 0 and len(m["c0.edges"]) == 65 and len(m["c1.edges_b"]) == 33
+    # the same run through the Python interface
+    fs.runtime.init(gpu=0)
+    sim = fs.DyeFluidSimulator.create(1, RES, 0.05 / RES, 1.0 / RES, 1e6, 5.0, "cip")
+    try:
+        box = (2, 1, 38, 19)
+        sim.start_distributions([{"quantity": "speed", "bins": 64, "range": (0, 1.5), "box": box},
+                                 {"quantity": "u", "bins": 16, "range": (-0.5, 1.5), "box": box,
+                                  "against": {"quantity": "vorticity", "bins": 32, "range": (-20, 20)}}], every=2)
+        sim.run(21, graph=True)
+        exp = sim.distributions()
+        assert np.array_equal(m["c0.counts"], exp[0]["counts"]) and np.array_equal(m["c1.counts"], exp[1]["counts"])
+        assert (int(m["c0.below"]), int(m["c0.above"]), int(m["c0.nan"]), int(m["c1.outside"])) == (exp[0]["below"], exp[0]["above"], exp[0]["nan"], exp[1]["outside"])
+        n = int((np.asarray(sim._solver._bc.mask)[2:38, 1:19] == 0).sum())
+        assert m["c0.counts"].sum() + int(m["c0.below"]) + int(m["c0.above"]) + int(m["c0.nan"]) == 10 * n
+    finally:
+        sim._solver._bc.device.close()
+    # eager steps: the same integers as the graph's
+    b = tmp_path / "b"
+    cli.main(["-res", str(RES), "--dist", SPEED, "--dist", JOINT, "--dist-every", "2", "--dist-box", "2,1,38,19", "--steps", "21", "--out", str(b),
+              "--dist-file", str(b / "named.npz")])
+    assert not (b / "dist.npz").exists() and np.array_equal(np.load(b / "named.npz")["c1.counts"], m["c1.counts"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("graph", [False, True])
+def test_resume_equals_the_uninterrupted_run(graph, tmp_path, hip_lib):
+    cli = _cli()
+    common = ["-res", str(RES), "--dist", SPEED, "--dist", JOINT, "--dist-every", "2", "--dist-start", "3"] + (["--graph"] if graph else [])
+    a, b = tmp_path / "a", tmp_path / "b"
+    cli.main(common + ["--steps", "27", "--out", str(a)])
+    m = np.load(a / "dist.npz")
+    assert int(m["samples"]) == 12 and m["sample_steps"].tolist() == list(range(5, 28, 2))
+    b.mkdir()
+    cli.main(common + ["--steps", "6", "--out", str(b), "--save-state", str(b / "ck.npz")])
+    ck = np.load(b / "ck.npz")
+    assert int(ck["dist.samples"]) == 1 and int(ck["dist.launches"]) == 6 and len(ck["dist.tables"]) == 64 + 4 + 16 * 32 + 4
+    cli.main(common + ["--steps", "21", "--out", str(b), "--load-state", str(b / "ck.npz")])
+    r = np.load(b / "dist.npz")
+    assert set(r.files) == set(m.files)
+    for k in r.files:
+        assert np.array_equal(r[k], m[k]), f"{k}: the resumed tables differ from the uninterrupted ones"
+    # a checkpoint without tables starts fresh
+    cli.main(["-res", str(RES), "--steps", "3", "--out", str(b), "--save-state", str(b / "plain.npz")])
+    cli.main(common + ["--steps", "14", "--out", str(b), "--load-state", str(b / "plain.npz")])
+    assert int(np.load(b / "dist.npz")["samples"]) == 5
