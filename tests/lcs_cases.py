@@ -42,6 +42,53 @@ def strain_rings(X=64, Y=32, M=5, a=0.1):
     return np.zeros((X, Y), np.uint8), slots
 
 
+# ---- boxed, refined lattices on a grid wider than one pitch unit ---------------------------------------------------------------------------
+LATTICE_DT, LATTICE_DX = 0.5, 0.1          # every = 1: a sub-step is 5 / S cells per unit velocity
+# (box, refine): 376 x 120 = 45,120 nodes, 177 workgroups of 256, the last of 64 lanes, the wall block inside the box;
+#                264 x 140 = 36,960 nodes, 145 workgroups, the last of 96 lanes, the box one column short of the outflow
+LATTICE_CASES = (((11, 5, 58, 20), 8), ((3, 2, 69, 37), 4))
+LATTICE_SUBSTEPS = (16, 5)
+LATTICE_RINGS = {"full": dict(samples=4, window={}), "wrapped": dict(samples=6, window=dict(first=1, last=-1))}
+
+
+def lattice_rings(dtype=np.float32, X=70, Y=40, M=4):
+    """A smooth, unsteady, sheared flow on a (70, 40) grid (row pitch 128: two 64-column units): walls in rows 0 and Y - 1 and a block at
+    i in [30, 36), j in [12, 20); column 0 inflow and column X - 1 outflow between the walls.  Snapshot m at the cell centres x = i + 0.5,
+    y = j + 0.5, a = 0.6 + 0.3 m:
+        u = a (1 + 0.4 sin(2 pi y / 40 + 0.7 m)) + 0.5 cos(2 pi x / 23) sin(2 pi y / 17)
+        w = 0.45 sin(2 pi x / 19 + 0.3 m) cos(2 pi y / 29)
+    cast to `dtype`, 0 on wall cells, p = 0.  Unlike lcs_ref.fate_rings nothing is piecewise constant: every bilinear weight and every
+    corner index matters.  -> (mask, slots (M, 3, X, Y))."""
+    mask = np.zeros((X, Y), np.uint8)
+    mask[0, 1:Y - 1] = 2
+    mask[X - 1, 1:Y - 1] = 3
+    mask[:, 0] = mask[:, Y - 1] = 1
+    mask[30:36, 12:20] = 1
+    x, y = np.meshgrid(np.arange(X) + 0.5, np.arange(Y) + 0.5, indexing="ij")
+    slots = np.zeros((M, 3, X, Y), dtype)
+    for m in range(M):
+        a = 0.6 + 0.3 * m
+        slots[m, 0] = a * (1.0 + 0.4 * np.sin(2.0 * np.pi * y / 40.0 + 0.7 * m)) + 0.5 * np.cos(2.0 * np.pi * x / 23.0) * np.sin(2.0 * np.pi * y / 17.0)
+        slots[m, 1] = 0.45 * np.sin(2.0 * np.pi * x / 19.0 + 0.3 * m) * np.cos(2.0 * np.pi * y / 29.0)
+    slots[:, :, mask == 1] = 0
+    return mask, slots
+
+
+def lattice_geometry(box, refine, wg=256):
+    """-> (nodes across, nodes down, workgroups of `wg` lanes, lanes of the last one)."""
+    nx, ny = refine * (box[2] - box[0]), refine * (box[3] - box[1])
+    groups = -(-nx * ny // wg)
+    return nx, ny, groups, nx * ny - (groups - 1) * wg
+
+
+def missing_neighbours(status, unseeded=4):
+    """Per side (lower a, upper a, lower b, upper b): the nodes whose lattice neighbour on that side is absent - outside the lattice or
+    UNSEEDED - which is where k_flowmap_cauchy_green takes a one-sided difference."""
+    there = np.asarray(status) != unseeded
+    pad = np.pad(there, 1, constant_values=False)
+    return ~pad[:-2, 1:-1], ~pad[2:, 1:-1], ~pad[1:-1, :-2], ~pad[1:-1, 2:]
+
+
 def strain_expectation(m, X, Y, a, h, N):
     """-> (interior nodes of the flow map m whose path and whose neighbours' paths stay a cell from the edge, the analytic lam = g^(2N)).
     One midpoint step of size h multiplies x - xc by 1 + q + q^2 / 2 and y - yc by 1 - q + q^2 / 2, q = a h: the larger factor is

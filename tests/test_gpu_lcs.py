@@ -5,7 +5,8 @@ stretching of a steady strain against its analytic value; the refusals and the l
 
 The grids are the smallest at which the kernels can go wrong: (33, 16) - 528 nodes at refine 1, 2112 at refine 2: more than one workgroup of
 256 and a partial last one, odd X; scene 1 at res 20 and a random mask at (37, 12) for the real ring; all-fluid (64, 16) and (64, 32) for the
-analytic cases.  Rings are installed with pod_set wherever the case needs no time stepping.
+analytic cases; and, for what only a larger lattice reaches (section 6), boxes with an offset at refine 4 and 8 on a (70, 40) grid - 45,120 and
+36,960 nodes.  Rings are installed with pod_set wherever the case needs no time stepping.
 
 Bounds (set by the issue that introduced the feature): equality everywhere but the strain case, whose lam = g^(2N) holds within 1e-10
 relative - bilinear interpolation reproduces a linear field, what remains is N <= 64 steps of a few eps each, about 1e-13."""
@@ -13,7 +14,8 @@ import ctypes
 
 import numpy as np
 import pytest
-from lcs_cases import DT, DX, install_ring, make_sim, strain_expectation, strain_rings, uniform_rings
+from lcs_cases import (DT, DX, LATTICE_CASES, LATTICE_DT, LATTICE_DX, LATTICE_RINGS, LATTICE_SUBSTEPS, install_ring, lattice_geometry, lattice_rings,
+                       make_sim, strain_expectation, strain_rings, uniform_rings)
 from lcs_ref import ALIVE, LEFT, UNSEEDED, WALL_HIT, assert_state_equal, fate_rings, flow_map_ref
 
 pytestmark = pytest.mark.gpu
@@ -268,5 +270,108 @@ def test_refusals_life_cycle_and_fields(hip_lib):
         assert sim._podr is None
         with pytest.raises(RuntimeError):
             sim.flow_map()
+    finally:
+        _close(sim)
+
+
+# ---- 6. boxed, refined lattices on a grid wider than one pitch unit -------------------------------------------------------------------------------------
+# What the cases above leave out (tests/lcs_cases.py lattice_rings, guarded by tests/test_lcs_cpu.py): refine 4 and 8; a box with x0, y0 != 0
+# that is advanced and differentiated - f.x0 + a / f.r and k % f.nx in the kernels, one-sided differences at lattice edges that are not domain
+# edges; 16 sub-steps bit for bit; a smooth sheared flow whose bilinear weights and corner indices all matter; 45,120 and 36,960 nodes - 177
+# and 145 workgroups, the last of 64 and 96 lanes; a (70, 40) grid whose rows span two 64-column pitch units.  Equality everywhere.
+_LATTICE = {}
+
+
+def _lattice_reference(dtype, box, refine, ring, direction, substeps):
+    """flow_map_ref on the ring as the device stores it in `dtype`: computed once per case."""
+    key = (dtype, box, refine, ring, direction, substeps)
+    if key not in _LATTICE:
+        mask, slots = lattice_rings(_np(dtype))
+        state = LATTICE_RINGS[ring]
+        _LATTICE[key] = flow_map_ref(slots, state["samples"], mask, 1, LATTICE_DT, LATTICE_DX, direction, refine, box, substeps, **state["window"])
+    return _LATTICE[key]
+
+
+@pytest.mark.parametrize("direction", ["forward", "backward"])
+@pytest.mark.parametrize("ring", sorted(LATTICE_RINGS))
+@pytest.mark.parametrize("box,refine", LATTICE_CASES)
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+def test_boxed_refined_lattice_equals_the_restatement(dtype, box, refine, ring, direction, hip_lib):
+    from fs.lcs import start_positions
+    mask, slots = lattice_rings(_np(dtype))
+    state = LATTICE_RINGS[ring]
+    nx, ny, groups, last = lattice_geometry(box, refine)
+    assert (nx * ny, groups, last) == {8: (45120, 177, 64), 4: (36960, 145, 96)}[refine]
+    sim = _sim(mask, dtype, dt=LATTICE_DT, dx=LATTICE_DX)
+    try:
+        install_ring(sim, slots, samples=state["samples"])
+        before = sim._dev.pod_get(sim._podr.pod)
+        assert before[0].dtype == _np(dtype) and np.array_equal(before[0], slots) and before[1:] == (state["samples"], state["samples"])
+        x0, y0 = start_positions(box, refine)
+        for substeps in LATTICE_SUBSTEPS:
+            what = f"{dtype} box={box} r={refine} {ring} {direction} S={substeps}: "
+            exp = _lattice_reference(dtype, box, refine, ring, direction, substeps)
+            fates = set(np.unique(exp["status"]).tolist())
+            assert fates == {ALIVE, LEFT, WALL_HIT, UNSEEDED} if ring == "full" else {ALIVE, WALL_HIT, UNSEEDED} <= fates, what
+            alive = exp["status"] == ALIVE
+            assert alive.sum() > 25000 and np.abs(exp["x"] - x0)[alive].min() > 0 and np.isfinite(exp["lam"]).sum() > 30000, what + "nothing moved"
+            m = sim.flow_map(direction, refine, box, substeps, **state["window"])
+            assert m["x"].shape == (nx, ny) and m["box"] == box and m["refine"] == refine, what
+            assert np.array_equal(m["x0"], x0) and np.array_equal(m["y0"], y0), what
+            assert_state_equal(m, exp, what)
+            assert m["sample_steps"].tolist() == ([1, 2, 3, 4] if ring == "full" else [4, 5, 6]), what
+        after = sim._dev.pod_get(sim._podr.pod)
+        assert np.array_equal(after[0], before[0]) and after[1:] == before[1:], "the flow map changed the ring"
+    finally:
+        _close(sim)
+
+
+def test_substep_counts_give_different_maps():
+    """S = 5 and S = 16 must not be interchangeable, nor the two directions: the cases above would otherwise check less than they say."""
+    box, refine = LATTICE_CASES[0]
+    a = _lattice_reference("f32", box, refine, "full", "forward", 5)
+    b = _lattice_reference("f32", box, refine, "full", "forward", 16)
+    c = _lattice_reference("f32", box, refine, "full", "backward", 16)
+    both = (a["status"] == ALIVE) & (b["status"] == ALIVE)
+    assert (a["x"][both] != b["x"][both]).mean() > 0.99 and not np.array_equal(a["status"], b["status"]) and not np.array_equal(b["status"], c["status"])
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+def test_reset_reseeds_a_boxed_refined_lattice(dtype, hip_lib):
+    """create, two launches on different slot pairs, reset, the same two launches: the second state is the first, and both are the
+    restatement's; the reset state is the seed - start positions, UNSEEDED over the wall block, lam NaN."""
+    from fs.lcs import start_positions
+    from lcs_ref import advance_ref, cauchy_green_ref, seed_ref
+    box, refine = LATTICE_CASES[0]
+    mask, slots = lattice_rings(_np(dtype))
+    sim = _sim(mask, dtype, dt=LATTICE_DT, dx=LATTICE_DX)
+    dev = sim._dev
+    try:
+        install_ring(sim, slots)
+        pod = sim._podr.pod
+        launches = ((0, 2, 2.5, 8), (3, 1, -0.625, 7))          # (from, to, h, substeps): forwards over 0 -> 2, then backwards over 3 -> 1
+        exp = seed_ref(mask, box, refine)
+        seed = {k: np.copy(v) for k, v in exp.items() if k in ("x", "y", "status", "lam")}
+        for a, b, h, s in launches:
+            advance_ref(exp, slots[a], slots[b], mask, h, s)
+        cauchy_green_ref(exp)
+        assert set(np.unique(exp["status"]).tolist()) == {ALIVE, LEFT, WALL_HIT, UNSEEDED}
+        fm = dev.flowmap_create(box, refine)
+        assert fm.shape == (376, 120)
+        states = []
+        for _ in range(2):
+            for a, b, h, s in launches:
+                dev.flowmap_advance(fm, pod, a, b, h, s)
+            dev.flowmap_cauchy_green(fm)
+            states.append(dict(zip(("x", "y", "status", "lam"), dev.flowmap_get(fm))))
+            dev.flowmap_reset(fm)
+            fresh = dict(zip(("x", "y", "status", "lam"), dev.flowmap_get(fm)))
+            assert_state_equal(fresh, seed, "after reset: ")
+        x0, y0 = start_positions(box, refine)
+        assert np.array_equal(seed["x"], x0) and np.array_equal(seed["y"], y0) and (seed["status"] == UNSEEDED).sum() == 6 * 8 * 64
+        assert_state_equal(states[0], exp, "first pass: ")
+        assert_state_equal(states[1], states[0], "second pass, after reset: ")
+        assert np.abs(states[0]["x"] - x0).max() > 1.0
+        dev.flowmap_free(fm)
     finally:
         _close(sim)

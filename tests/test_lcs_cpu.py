@@ -7,7 +7,8 @@ Bounds: the uniform, time-linear flow is integrated exactly (equality); the stea
 issue that introduced the feature: bilinear interpolation reproduces a linear field, what remains is N <= 64 steps of a few eps each)."""
 import numpy as np
 import pytest
-from lcs_cases import DT, DX, install_ring, make_sim, strain_expectation, strain_rings, uniform_rings
+from lcs_cases import (DT, DX, LATTICE_CASES, LATTICE_DT, LATTICE_DX, LATTICE_RINGS, LATTICE_SUBSTEPS, install_ring, lattice_geometry, lattice_rings,
+                       make_sim, missing_neighbours, strain_expectation, strain_rings, uniform_rings)
 from lcs_ref import ALIVE, LEFT, UNSEEDED, WALL_HIT, assert_state_equal, chronological, fate_rings, flow_map_ref
 
 
@@ -194,3 +195,51 @@ def test_refusals_change_nothing(standin):
     assert sim.flow_map()["x"].shape == (33, 16)               # a second call works, and stop_pod after it
     sim.stop_pod()
     assert sim._podr is None
+
+
+# ---- the boxed, refined lattices of tests/test_gpu_lcs.py: what each case must contain to reach what it is meant to reach ---------------------------
+@pytest.mark.parametrize("substeps", LATTICE_SUBSTEPS)
+@pytest.mark.parametrize("direction", ["forward", "backward"])
+@pytest.mark.parametrize("ring", sorted(LATTICE_RINGS))
+@pytest.mark.parametrize("box,refine", LATTICE_CASES)
+def test_boxed_lattice_cases_reach_every_branch(box, refine, ring, direction, substeps, standin):
+    from fs.lcs import start_positions
+    mask, slots = lattice_rings()
+    assert mask.shape == (70, 40) and -(-70 // 64) * 64 == 128          # two 64-column pitch units
+    nx, ny, groups, last = lattice_geometry(box, refine)
+    assert (nx * ny, groups, last) == {8: (45120, 177, 64), 4: (36960, 145, 96)}[refine]
+    assert box[0] > 0 and box[1] > 0 and box[2] < 70 and box[3] < 40     # no lattice edge is a domain edge
+    sim = make_sim(mask, dt=LATTICE_DT, dx=LATTICE_DX)
+    state = LATTICE_RINGS[ring]
+    install_ring(sim, slots, samples=state["samples"])
+    m = sim.flow_map(direction, refine, box, substeps, **state["window"])          # (the stand-in IS the restatement: tested above, with a box)
+    assert m["x"].shape == (nx, ny) and m["box"] == box and m["refine"] == refine
+    x0, y0 = start_positions(box, refine)
+    assert np.array_equal(m["x0"], x0) and np.array_equal(m["y0"], y0) and x0[0, 0] == box[0] + 0.5 / refine and y0[0, 0] == box[1] + 0.5 / refine
+    assert m["sample_steps"].tolist() == ([1, 2, 3, 4] if ring == "full" else [4, 5, 6])
+    fates = set(np.unique(m["status"]).tolist())
+    if ring == "full":
+        assert fates == {ALIVE, LEFT, WALL_HIT, UNSEEDED}
+    else:
+        assert {ALIVE, WALL_HIT, UNSEEDED} <= fates          # (the inner box loses LEFT forwards: two intervals do not reach the outflow)
+    # UNSEEDED is the wall block seen through the box offset and the refinement
+    block = np.repeat(np.repeat(mask[box[0]:box[2], box[1]:box[3]] == 1, refine, 0), refine, 1)
+    assert np.array_equal(m["status"] == UNSEEDED, block) and block.sum() == 6 * 8 * refine * refine
+    alive = m["status"] == ALIVE
+    assert np.abs(m["x"] - m["x0"])[alive].min() > 0 and np.abs(m["y"] - m["y0"])[alive].max() > 1.0, "the nodes hardly moved"
+    # all four quadrants of a cell: the four bilinear weights all vary
+    fx, fy = m["x"][alive] - np.floor(m["x"][alive]), m["y"][alive] - np.floor(m["y"][alive])
+    for lo_x in (True, False):
+        for lo_y in (True, False):
+            assert (((fx < 0.5) == lo_x) & ((fy < 0.5) == lo_y)).sum() > 1000
+    # one-sided differences on all four sides, at lattice edges that are not domain edges and around the block
+    finite = np.isfinite(m["lam"])
+    assert finite.sum() > 30000 and not finite[m["status"] == UNSEEDED].any()
+    beside = {"lower a": box[0] < 30, "upper a": box[2] > 36, "lower b": box[3] > 20, "upper b": box[1] < 12}      # fluid on that side of the block
+    for side, absent in zip(("lower a", "upper a", "lower b", "upper b"), missing_neighbours(m["status"])):
+        assert (absent & finite).sum() >= (ny if "a" in side else nx) // 2, side          # the lattice edge, which is not the domain's
+        inner = absent & finite
+        inner[0], inner[-1], inner[:, 0], inner[:, -1] = False, False, False, False
+        assert inner.sum() >= 6 * refine or not beside[side], f"{side}: no one-sided difference beside the block"
+    assert sum(beside.values()) >= 3
+    sim.stop_pod()
