@@ -80,5 +80,11 @@ class Averager(Rider):
         return {"mean.sums": sums, "mean.launches": np.array(launches), "mean.samples": np.array(samples),
                 "mean.every": np.array(self.every), "mean.start": np.array(self.start_step)}
 
+    @staticmethod
+    def held(z):
+        """-> (every, start), or None."""
+        return (int(z["mean.every"]), int(z["mean.start"])) if "mean.sums" in z else None
+
     def restore(self, z):
         self.dev.mean_write(self.mean, z["mean.sums"], int(z["mean.launches"]), int(z["mean.samples"]))
+        return int(z["mean.samples"])

@@ -168,6 +168,11 @@ class Distributions(Rider):
         return {"dist.tables": words, "dist.launches": np.array(launches), "dist.samples": np.array(samples), "dist.base": np.array(self.base),
                 "dist.channels": self._spec(), "dist.every": np.array(self.every), "dist.start": np.array(self.start_step)}
 
+    @staticmethod
+    def held(z):
+        """-> (channels array (n, 12), every, start), or None."""
+        return (np.asarray(z["dist.channels"], np.float64), int(z["dist.every"]), int(z["dist.start"])) if "dist.tables" in z else None
+
     def restore(self, z):
         """Refused (ValueError) before any device work when the checkpoint's channels, every or start_step are not the attached ones."""
         held = np.asarray(z["dist.channels"], np.float64)
@@ -178,3 +183,4 @@ class Distributions(Rider):
                              f"the attached ones every {self.every} from {self.start_step}")
         self.dev.dist_set(self.dist, z["dist.tables"], int(z["dist.launches"]), int(z["dist.samples"]))
         self.base = int(z["dist.base"])
+        return int(z["dist.samples"])

@@ -115,14 +115,21 @@ class Tracker(Rider):
                 "loads.box": np.array(self.box), "loads.center": np.array(self.centre, np.float64), "loads.every": np.array(self.every),
                 "loads.start": np.array(self.start_step)}
 
-    def restore(self, sums, launches=None, samples=None):
+    @staticmethod
+    def held(z):
+        """-> (box, centre, every, start), or None."""
+        if "loads.sums" not in z:
+            return None
+        return (tuple(int(b) for b in z["loads.box"]), tuple(float(c) for c in z["loads.center"]), int(z["loads.every"]), int(z["loads.start"]))
+
+    def restore(self, z):
         """Continue where a checkpoint stopped: its (4, F) sums and both counters go to the device; the records of this ring are numbered
-        on from `launches`.  restore(z): the three from the mapping checkpoint() wrote."""
-        if launches is None:
-            sums, launches, samples = sums["loads.sums"], int(sums["loads.launches"]), int(sums["loads.samples"])
-        self.dev.loads_sums(self.loads, write=sums, launches=launches, samples=samples)
-        self.issued = self.base = int(launches)
-        self.samples = int(samples)
+        on from its launches."""
+        launches, samples = int(z["loads.launches"]), int(z["loads.samples"])
+        self.dev.loads_sums(self.loads, write=z["loads.sums"], launches=launches, samples=samples)
+        self.issued = self.base = launches
+        self.samples = samples
+        return samples
 
     def sums(self):
         return self.dev.loads_sums(self.loads) if self._final is None else self._final[0]

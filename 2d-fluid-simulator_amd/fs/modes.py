@@ -179,5 +179,13 @@ class Modes(Rider):
         return {"modes.sums": sums, "modes.scalars": scalars, "modes.launches": np.array(launches), "modes.samples": np.array(samples),
                 "modes.frequencies": self.frequencies.copy(), "modes.every": np.array(self.every), "modes.start": np.array(self.start_step)}
 
+    @staticmethod
+    def held(z):
+        """-> (frequencies, every, start), or None."""
+        if "modes.sums" not in z:
+            return None
+        return (tuple(float(f) for f in z["modes.frequencies"]), int(z["modes.every"]), int(z["modes.start"]))
+
     def restore(self, z):
         self.dev.modes_write(self.modes, z["modes.sums"], z["modes.scalars"], int(z["modes.launches"]), int(z["modes.samples"]))
+        return int(z["modes.samples"])

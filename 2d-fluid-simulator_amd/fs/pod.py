@@ -121,7 +121,13 @@ class Pod(Rider):
         return {"pod.slots": slots, "pod.launches": np.array(launches), "pod.samples": np.array(samples), "pod.base": np.array(self.base),
                 "pod.snapshots": np.array(self.pod.slots), "pod.every": np.array(self.every), "pod.start": np.array(self.start_step)}
 
+    @staticmethod
+    def held(z):
+        """-> (snapshots, every, start), or None."""
+        return (int(z["pod.snapshots"]), int(z["pod.every"]), int(z["pod.start"])) if "pod.slots" in z else None
+
     def restore(self, z):
         self.dev.pod_set(self.pod, z["pod.slots"], int(z["pod.launches"]), int(z["pod.samples"]))
         self.base = int(z["pod.base"])
         self._cache = None
+        return int(z["pod.samples"])

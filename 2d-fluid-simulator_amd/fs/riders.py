@@ -69,5 +69,12 @@ class Rider:
         """{checkpoint key: array} of everything a resumed run needs."""
         return {}
 
+    @staticmethod
+    def held(z):
+        """The parameters the checkpoint mapping z holds under this rider's keys, or None when it holds none of its kind: what a caller
+        compares with its own before restore()."""
+        return None
+
     def restore(self, z):
-        """The inverse of checkpoint() on a freshly attached rider with the same parameters; z: the checkpoint's mapping."""
+        """The inverse of checkpoint() on a freshly attached rider with the same parameters; z: the checkpoint's mapping -> the samples
+        taken over."""

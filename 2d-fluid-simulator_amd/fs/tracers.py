@@ -183,11 +183,18 @@ class TracerAccumulation(Rider):
     def free(self):
         self.dev.tracer_accum_free(self.set)
 
+    @staticmethod
+    def held(z):
+        """-> (every, start), or None."""
+        return (int(z["tracer.accum.every"]), int(z["tracer.accum.start"])) if "tracer.accum.occupancy" in z else None
+
     def restore(self, z):
         """(After Tracers.restore, which sets the launch count the phase hangs on.)  A checkpoint without an accumulation: nothing."""
-        if "tracer.accum.occupancy" in z:
-            self.dev.tracer_accum_write(self.set, z["tracer.accum.occupancy"], z["tracer.accum.age_sum"], int(z["tracer.accum.steps"]),
-                                        int(z["tracer.accum.samples"]))
+        if "tracer.accum.occupancy" not in z:
+            return 0
+        self.dev.tracer_accum_write(self.set, z["tracer.accum.occupancy"], z["tracer.accum.age_sum"], int(z["tracer.accum.steps"]),
+                                    int(z["tracer.accum.samples"]))
+        return int(z["tracer.accum.samples"])
 
 
 class Tracers(Rider):
@@ -259,10 +266,28 @@ class Tracers(Rider):
                            "tracer.accum.start": np.array(acc.start_step)})
         return arrays
 
+    @staticmethod
+    def held(z):
+        """-> (respawn, max_age, N) of the set, or None."""
+        return (bool(z["tracer.respawn"]), int(z["tracer.max_age"]), len(z["tracer.x"])) if "tracer.x" in z else None
+
+    @staticmethod
+    def held_inertial(z):
+        """What the set holds beyond a passive one's: {"tau": (N,) array or None, "gravity": (gx, gy), "deposits": bool, "accumulate":
+        TracerAccumulation.held(z)}, or None without a set."""
+        if "tracer.x" not in z:
+            return None
+        inertial = "tracer.tau" in z
+        return {"tau": np.asarray(z["tracer.tau"], np.float64) if inertial else None,
+                "gravity": tuple(float(g) for g in z["tracer.gravity"]) if inertial else (0.0, 0.0),
+                "deposits": "tracer.deposits" in z, "accumulate": TracerAccumulation.held(z)}
+
     def restore(self, z):
-        """The state of the set itself, in seed order.  An accumulation is attached and restored after this (TracerAccumulation.restore)."""
+        """The state of the set itself, in seed order -> its particles.  An accumulation is attached and restored after this
+        (TracerAccumulation.restore)."""
         self.dev.tracer_write(self.set, {k: z[f"tracer.{k}"] for k in KEYS})
         if self.tau is not None:
             self.dev.tracer_write_vel(self.set, z["tracer.u"], z["tracer.w"])
             if self.deposits:
                 self.dev.tracer_deposits_write(self.set, z["tracer.deposits"])
+        return len(z["tracer.x"])

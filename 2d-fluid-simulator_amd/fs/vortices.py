@@ -238,6 +238,13 @@ class Vortices(Rider):
                 "vortex.exponent": np.array(vx.exponent), "vortex.min_area": np.array(vx.min_area), "vortex.max_vortices": np.array(vx.max_vortices),
                 "vortex.max_components": np.array(vx.max_components)}
 
+    @staticmethod
+    def held(z):
+        """-> (criterion, threshold, every, min_area, max_vortices), or None."""
+        if "vortex.words" not in z:
+            return None
+        return (str(z["vortex.criterion"]), float(z["vortex.threshold"]), int(z["vortex.every"]), int(z["vortex.min_area"]), int(z["vortex.max_vortices"]))
+
     def restore(self, z):
         """Continue where a checkpoint stopped: its samples are this tracker's first, the launch count goes to the device."""
         words = np.asarray(z["vortex.words"], np.int64)
@@ -248,3 +255,4 @@ class Vortices(Rider):
         self.issued = self.base = launches
         self.drained = 0
         self._words = [words] if len(words) else []
+        return len(words)

@@ -58,14 +58,14 @@ def test_flags_parse_and_refusals(tmp_path):
 def test_checkpoint_with_other_channels_is_refused(tmp_path, capsys):
     """--load-state of a checkpoint whose tables were accumulated with other channels, every or start: message and exit status 2, before any
     device work."""
-    from fs.dist import channels_array
+    from fs.dist import Distributions, channels_array
     cli = _cli()
     _, checked = cli.parse_dist(cli.build_parser(), [SPEED, JOINT], None, 2 * RES, RES)
     ck = tmp_path / "ck.npz"
     np.savez(str(ck), step=np.array(10), **{"dist.tables": np.zeros(64 + 4 + 16 * 32 + 4, np.int64), "dist.launches": np.array(10),
                                             "dist.samples": np.array(3), "dist.base": np.array(0), "dist.channels": channels_array(checked),
                                             "dist.every": np.array(3), "dist.start": np.array(1)})
-    held = cli.saved_dist(str(ck))
+    held = Distributions.held(np.load(str(ck)))
     assert held[1:] == (3, 1) and held[0].shape == (2, 12)
     same = ["--dist", SPEED, "--dist", JOINT]
     for argv in (same + ["--dist-every", "2", "--dist-start", "1"], same + ["--dist-every", "3"], ["--dist", SPEED, "--dist-every", "3", "--dist-start", "1"],
@@ -78,7 +78,7 @@ def test_checkpoint_with_other_channels_is_refused(tmp_path, capsys):
         assert "--dist speed:64:0.0:1.5 --dist u:16:-0.5:1.5,vorticity:32:-20.0:20.0 --dist-box 0,0,40,20 --dist-every 3 --dist-start 1" in err
     plain = tmp_path / "plain.npz"
     np.savez(str(plain), step=np.array(10))
-    assert cli.saved_dist(str(plain)) is None
+    assert Distributions.held(np.load(str(plain))) is None
 
 
 @pytest.mark.gpu

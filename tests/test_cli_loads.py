@@ -41,15 +41,16 @@ def test_flags_parse_and_refusals(tmp_path):
 
 
 def test_saved_loads_reads_the_checkpoint(tmp_path):
+    from fs.loads import Tracker
     cli = _cli()
     ck = tmp_path / "ck.npz"
     np.savez(str(ck), step=np.array(10), **{"loads.sums": np.zeros((4, 3)), "loads.launches": np.array(10), "loads.samples": np.array(3),
                                             "loads.box": np.array([1, 2, 3, 4]), "loads.center": np.array([2.0, 3.0]),
                                             "loads.every": np.array(3), "loads.start": np.array(1)})
-    assert cli.saved_loads(str(ck)) == ((1, 2, 3, 4), (2.0, 3.0), 3, 1)
+    assert Tracker.held(np.load(str(ck))) == ((1, 2, 3, 4), (2.0, 3.0), 3, 1)
     plain = tmp_path / "plain.npz"
     np.savez(str(plain), step=np.array(10))
-    assert cli.saved_loads(str(plain)) is None
+    assert Tracker.held(np.load(str(plain))) is None
 
 
 @pytest.mark.gpu

@@ -33,11 +33,12 @@ def test_flags_parse_and_refusals(tmp_path):
 
 def test_checkpoint_with_other_parameters_is_refused(tmp_path, capsys):
     """--load-state of a checkpoint whose average was taken with another every / start: message and exit status 2, before any device work."""
+    from fs.averages import Averager
     cli = _cli()
     ck = tmp_path / "ck.npz"
     np.savez(str(ck), step=np.array(10), **{"mean.sums": np.zeros((7, 4, 2)), "mean.launches": np.array(10), "mean.samples": np.array(3),
                                             "mean.every": np.array(3), "mean.start": np.array(1)})
-    assert cli.saved_mean(str(ck)) == (3, 1)
+    assert Averager.held(np.load(str(ck))) == (3, 1)
     for argv in (["--mean-every", "2", "--mean-start", "1"], ["--mean-every", "3"]):
         with pytest.raises(SystemExit) as e:
             cli.main(argv + ["--load-state", str(ck), "--out", str(tmp_path)])
@@ -45,7 +46,7 @@ def test_checkpoint_with_other_parameters_is_refused(tmp_path, capsys):
         assert "--mean-every 3 --mean-start 1" in capsys.readouterr().err
     plain = tmp_path / "plain.npz"
     np.savez(str(plain), step=np.array(10))
-    assert cli.saved_mean(str(plain)) is None
+    assert Averager.held(np.load(str(plain))) is None
 
 
 @pytest.mark.gpu

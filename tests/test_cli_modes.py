@@ -49,12 +49,13 @@ def test_flags_parse_and_refusals(tmp_path):
 def test_checkpoint_with_other_parameters_is_refused(tmp_path, capsys):
     """--load-state of a checkpoint whose modes were taken with other frequencies, every or start: message and exit status 2, before any
     device work."""
+    from fs.modes import Modes
     cli = _cli()
     ck = tmp_path / "ck.npz"
     np.savez(str(ck), step=np.array(10), **{"modes.sums": np.zeros((9, 4, 2)), "modes.scalars": np.zeros(8), "modes.launches": np.array(10),
                                             "modes.samples": np.array(3), "modes.frequencies": np.array([1.5]), "modes.every": np.array(3),
                                             "modes.start": np.array(1)})
-    assert cli.saved_modes(str(ck)) == ((1.5,), 3, 1)
+    assert Modes.held(np.load(str(ck))) == ((1.5,), 3, 1)
     for argv in (["--modes-freq", "1.5", "--modes-every", "2", "--modes-start", "1"], ["--modes-freq", "1.5", "--modes-every", "3"],
                  ["--modes-freq", "1.25", "--modes-every", "3", "--modes-start", "1"],
                  ["--modes-freq", "1.5,2.5", "--modes-every", "3", "--modes-start", "1"]):
@@ -64,7 +65,7 @@ def test_checkpoint_with_other_parameters_is_refused(tmp_path, capsys):
         assert "--modes-freq 1.5 --modes-every 3 --modes-start 1" in capsys.readouterr().err
     plain = tmp_path / "plain.npz"
     np.savez(str(plain), step=np.array(10))
-    assert cli.saved_modes(str(plain)) is None
+    assert Modes.held(np.load(str(plain))) is None
 
 
 ARRAYS = [f"{k}_{a}" for k in ("mean", "amplitude", "phase") for a in "uwp"]

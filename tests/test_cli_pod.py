@@ -43,11 +43,12 @@ def test_flags_parse_and_refusals(tmp_path):
 def test_checkpoint_with_other_parameters_is_refused(tmp_path, capsys):
     """--load-state of a checkpoint whose snapshots were taken with another M, every or start: message and exit status 2, before any device
     work."""
+    from fs.pod import Pod
     cli = _cli()
     ck = tmp_path / "ck.npz"
     np.savez(str(ck), step=np.array(10), **{"pod.slots": np.zeros((4, 3, 4, 2), np.float32), "pod.launches": np.array(10), "pod.samples": np.array(3),
                                             "pod.base": np.array(0), "pod.snapshots": np.array(4), "pod.every": np.array(3), "pod.start": np.array(1)})
-    assert cli.saved_pod(str(ck)) == (4, 3, 1)
+    assert Pod.held(np.load(str(ck))) == (4, 3, 1)
     for argv in (["--pod-snapshots", "4", "--pod-every", "2", "--pod-start", "1"], ["--pod-snapshots", "4", "--pod-every", "3"],
                  ["--pod-snapshots", "8", "--pod-every", "3", "--pod-start", "1"]):
         with pytest.raises(SystemExit) as e:
@@ -56,7 +57,7 @@ def test_checkpoint_with_other_parameters_is_refused(tmp_path, capsys):
         assert "--pod-snapshots 4 --pod-every 3 --pod-start 1" in capsys.readouterr().err
     plain = tmp_path / "plain.npz"
     np.savez(str(plain), step=np.array(10))
-    assert cli.saved_pod(str(plain)) is None
+    assert Pod.held(np.load(str(plain))) is None
 
 
 @pytest.mark.gpu

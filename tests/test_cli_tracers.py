@@ -58,6 +58,7 @@ def test_seeds_from_the_flags_and_dropped_wall_seeds():
 
 def test_checkpoint_with_other_parameters_is_refused(tmp_path, capsys):
     """--load-state of a checkpoint whose tracers ran with another respawn / max_age: message and exit status 2, before any device work."""
+    from fs.tracers import Tracers
     cli = _cli()
     ck = tmp_path / "ck.npz"
     n = 4
@@ -65,7 +66,7 @@ def test_checkpoint_with_other_parameters_is_refused(tmp_path, capsys):
                                             "tracer.status": np.zeros(n, np.int32), "tracer.respawns": np.zeros(n, np.int32),
                                             "tracer.seeds": np.ones((n, 2)), "tracer.steps": np.array(10), "tracer.respawn": np.array(True),
                                             "tracer.max_age": np.array(50)})
-    assert cli.saved_tracers(str(ck)) == (True, 50, 4)
+    assert Tracers.held(np.load(str(ck))) == (True, 50, 4)
     for argv in (["--tracers", "4"], ["--tracers", "4", "--tracer-max-age", "50", "--tracer-once"]):
         with pytest.raises(SystemExit) as e:
             cli.main(argv + ["--load-state", str(ck), "--out", str(tmp_path)])
@@ -73,7 +74,7 @@ def test_checkpoint_with_other_parameters_is_refused(tmp_path, capsys):
         assert "--tracer-max-age 50" in capsys.readouterr().err
     plain = tmp_path / "plain.npz"
     np.savez(str(plain), step=np.array(10))
-    assert cli.saved_tracers(str(plain)) is None
+    assert Tracers.held(np.load(str(plain))) is None
 
 
 @pytest.mark.gpu

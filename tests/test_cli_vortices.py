@@ -41,16 +41,17 @@ def test_flags_parse_and_refusals(tmp_path):
 
 
 def test_saved_parameters_are_read_from_a_checkpoint(tmp_path):
+    from fs.vortices import Vortices
     cli = _cli()
     ck = tmp_path / "ck.npz"
     np.savez(str(ck), step=np.array(10), **{"vortex.words": np.zeros((2, 8 + 16 * 64), np.int64), "vortex.launches": np.array(10),
                                             "vortex.every": np.array(3), "vortex.start": np.array(0), "vortex.criterion": np.array("swirl"),
                                             "vortex.threshold": np.array(0.25), "vortex.exponent": np.array(10), "vortex.min_area": np.array(4),
                                             "vortex.max_vortices": np.array(64), "vortex.max_components": np.array(65536)})
-    assert cli.saved_vortices(str(ck)) == ("swirl", 0.25, 3, 4, 64)
+    assert Vortices.held(np.load(str(ck))) == ("swirl", 0.25, 3, 4, 64)
     plain = tmp_path / "plain.npz"
     np.savez(str(plain), step=np.array(10))
-    assert cli.saved_vortices(str(plain)) is None
+    assert Vortices.held(np.load(str(plain))) is None
 
 
 @pytest.mark.gpu

@@ -153,7 +153,7 @@ def test_start_reset_stop_checkpoint_and_refusals(standin):
         assert np.array_equal(np.concatenate(sim._distr.dist._h.tables), before) and sim._distr.dist._h.launches == 0
         sim.stop_distributions()
     sim.start_distributions(CHANNELS, every=2, start_step=1)
-    sim._distr.restore(z)
+    assert sim._distr.restore(z) == sim.distributions()[0]["samples"] == 4          # (-> the samples taken over: the CLI's "samples so far")
     back = sim.distributions()
     for o, b in zip(out, back):
         assert np.array_equal(o["counts"], b["counts"]) and o["samples"] == b["samples"] and o["sample_steps"].tolist() == b["sample_steps"].tolist()

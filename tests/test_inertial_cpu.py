@@ -333,12 +333,13 @@ def _checkpoint(path, n=4, inertial=True, deposits=True, accum=True):
 
 def test_checkpoint_with_other_inertial_parameters_is_refused(tmp_path, capsys):
     """--load-state of a checkpoint whose set has another tau, gravity, deposit plane or accumulation schedule: exit status 2 before any
-    device work; saved_tracers keeps its return value."""
+    device work; Tracers.held keeps the return value the set always had."""
+    from fs.tracers import Tracers
     cli = _cli()
     ck = tmp_path / "ck.npz"
     _checkpoint(ck)
-    assert cli.saved_tracers(str(ck)) == (True, 0, 4)
-    more = cli.saved_inertial(str(ck))
+    assert Tracers.held(np.load(str(ck))) == (True, 0, 4)
+    more = Tracers.held_inertial(np.load(str(ck)))
     assert np.array_equal(more["tau"], [0.1, 0.2, 0.1, 0.2]) and more["gravity"] == (0.0, -1.0) and more["deposits"] is True and more["accumulate"] == (2, 0)
     right = ["--tracers", "4", "--tracer-tau", "0.1,0.2", "--tracer-gravity", "0,-1", "--tracer-deposits"]
     for argv in (["--tracers", "4"],                                                              # passive flags, inertial checkpoint
@@ -354,24 +355,27 @@ def test_checkpoint_with_other_inertial_parameters_is_refused(tmp_path, capsys):
         assert "--load-state" in capsys.readouterr().err
     passive = tmp_path / "passive.npz"
     _checkpoint(passive, inertial=False, accum=False)
-    assert cli.saved_tracers(str(passive)) == (True, 0, 4)
-    more = cli.saved_inertial(str(passive))
+    assert Tracers.held(np.load(str(passive))) == (True, 0, 4)
+    more = Tracers.held_inertial(np.load(str(passive)))
     assert more["tau"] is None and more["deposits"] is False and more["accumulate"] is None
     with pytest.raises(SystemExit) as e:
         cli.main(["--tracers", "4", "--tracer-tau", "0.1", "--load-state", str(passive), "--out", str(tmp_path)])
     assert e.value.code == 2 and "passive tracers" in capsys.readouterr().err
     plain = tmp_path / "plain.npz"
     np.savez(str(plain), step=np.array(10))
-    assert cli.saved_inertial(str(plain)) is None
+    assert Tracers.held_inertial(np.load(str(plain))) is None
 
 
 class _StateDev:
-    """Stands in for the device behind main.tracer_state_arrays."""
+    """Stands in for the device behind fs.tracers.Tracers.checkpoint."""
 
     def tracer_read(self, tr):
         n = 3
         return {"x": np.zeros(n), "y": np.zeros(n), "age": np.zeros(n, np.int32), "status": np.zeros(n, np.int32), "respawns": np.zeros(n, np.int32),
                 "seeds": np.zeros((n, 2)), "steps": 5}
+
+    def tracer_write(self, tr, arrays):
+        self.written = arrays
 
     def tracer_read_vel(self, tr):
         return np.zeros(3), np.zeros(3)
@@ -386,7 +390,6 @@ class _StateDev:
 def test_checkpoint_key_sets():
     """A passive set's checkpoint keeps exactly the keys it had; an inertial set, its deposits and an accumulation add theirs."""
     from fs.tracers import TracerAccumulation, Tracers
-    cli = _cli()
 
     class _Acc:
         serial = 3
@@ -395,16 +398,17 @@ def test_checkpoint_key_sets():
     accum_keys = {f"tracer.accum.{k}" for k in ("occupancy", "age_sum", "steps", "samples", "every", "start")}
     dev = _StateDev()
     t = Tracers(dev, object(), np.zeros((3, 2)), True, 0)
-    assert set(cli.tracer_state_arrays(t)) == passive_keys
+    assert set(t.checkpoint()) == passive_keys
+    assert t.restore(t.checkpoint()) == len(dev.written["seeds"]) == 3          # (-> the particles taken over: the CLI's "continuing" line)
     t.accumulation = TracerAccumulation(_Acc(), 2, 1)
-    got = cli.tracer_state_arrays(t)
+    got = t.checkpoint()
     assert set(got) == passive_keys | accum_keys and int(got["tracer.accum.every"]) == 2 and int(got["tracer.accum.start"]) == 1
     t = Tracers(dev, object(), np.zeros((3, 2)), True, 0, tau=np.array([0.1, 0.2, 0.3]), gravity=(0.0, -1.0))
-    got = cli.tracer_state_arrays(t)
+    got = t.checkpoint()
     assert set(got) == inertial_keys and np.array_equal(got["tracer.gravity"], [0.0, -1.0]) and got["tracer.tau"].dtype == np.float64
     t = Tracers(dev, object(), np.zeros((3, 2)), True, 0, tau=np.array([0.1, 0.2, 0.3]), deposits=True)
     t.accumulation = TracerAccumulation(_Acc(), 1, 0)
-    assert set(cli.tracer_state_arrays(t)) == inertial_keys | {"tracer.deposits"} | accum_keys
+    assert set(t.checkpoint()) == inertial_keys | {"tracer.deposits"} | accum_keys
 
 
 # ---- the binding table and the build ------------------------------------------------------------------------------------------------------

@@ -314,7 +314,7 @@ def test_checkpoint_and_restore(standin):
     assert z["modes.frequencies"].tolist() == FREQS
     b.run(20)
     b.start_modes(FREQS, every=3, start_step=2)
-    b._moder.restore(z)
+    assert b._moder.restore(z) == b._dev.modes_read_scalars(b._moder.modes)[3] == 6          # (-> the samples taken over: the CLI's "samples so far")
     a.run(11)
     b.run(11)
     ra, rb = a._dev.modes_read(a._moder.modes), b._dev.modes_read(b._moder.modes)

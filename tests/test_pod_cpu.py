@@ -293,7 +293,7 @@ def test_checkpoint_and_restore(standin):
     assert z["pod.slots"].shape == (4, 3) + np.asarray(a._solver._bc.mask).shape and z["pod.slots"].dtype == np.float32
     b.run(20)
     b.start_pod(4, every=3, start_step=2)
-    b._podr.restore(z)
+    assert b._podr.restore(z) == b._dev.pod_read(b._podr.pod)[1] == 4          # (-> the samples taken over: the CLI's "samples so far")
     a.run(11)
     b.run(11)
     ra, rb = a._dev.pod_get(a._podr.pod), b._dev.pod_get(b._podr.pod)

@@ -106,18 +106,23 @@ def test_launch_order_and_token_order(standin):
 
 
 def test_checkpoint_keys_and_resume(combined, tmp_path):
+    from fs.averages import Averager
+    from fs.loads import Tracker
     cli = _cli()
     sim, cfg = combined
     ck = str(tmp_path / "ck.npz")
     cli.save_state(sim, ck, 42)
     assert set(np.load(ck).files) == CHECKPOINT_KEYS
-    assert cli.saved_mean(ck) == (3, 4) and cli.saved_loads(ck)[2:] == (2, 0)
+    z = np.load(ck)
+    assert Averager.held(z) == (3, 4) and Tracker.held(z)[2:] == (2, 0)
     ref, _ = _sim(RIDERS)          # the uninterrupted run: the same 42 steps, then 12 more
     for n in CHUNKS:
         ref.run(n)
     new, _ = _sim(("mean", "loads"))
     assert cli.load_state(new, ck) == 42
-    assert cli.load_mean(new, ck) and cli.load_loads(new, ck)
+    # restore() answers the samples taken over: what the device and the tracker hold afterwards (the CLI's "samples so far")
+    assert new._averager.restore(z) == new._dev.mean_read(new._averager.mean)[2] == (42 - 4) // 3
+    assert new._tracker.restore(z) == new._tracker.samples == 21
     ref.run(12)
     new.run(12)
     _same(new.averages(), ref.averages(), "averages")
@@ -129,7 +134,7 @@ def test_checkpoint_keys_and_resume(combined, tmp_path):
     assert gs["samples"] == es["samples"] == 27 and np.array_equal(gs["sums"], es["sums"])
     plain = str(tmp_path / "plain.npz")
     cli.save_state(_sim(())[0], plain, 0)
-    assert not cli.load_mean(new, plain) and not cli.load_loads(new, plain)
+    assert Averager.held(np.load(plain)) is None and Tracker.held(np.load(plain)) is None
 
 
 def test_stop_methods_during_a_capture(standin):

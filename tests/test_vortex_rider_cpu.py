@@ -166,7 +166,7 @@ def test_checkpoint_and_restore(standin):
     assert int(z["vortex.launches"]) == 9 and len(z["vortex.words"]) == 2 and z["vortex.words"].dtype == np.int64
     a.stop_vortices()
     a.track_vortices(THR, every=every, start_step=start, capacity=2)
-    a._vortexr.restore(z)
+    assert a._vortexr.restore(z) == len(a._vortexr._words[0]) == 2          # (-> the samples taken over: the CLI's "samples so far")
     assert a._vortexr.room() == 6            # the samples of steps 10 and 13 fit the ring of 2; the launch of step 16 would find it full
     a.run(steps - 9)
     _assert_samples(a.vortices(), ref, e, dx, nx)
