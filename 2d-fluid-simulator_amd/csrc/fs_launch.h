@@ -1,6 +1,6 @@
 // fs_launch.h - host-side launch plumbing shared by the translation units behind the C-ABI (fs_core.hip: contexts, fields, scene upload,
 // boundary kernels, graphs / tapes / profiling; fs_transport.hip: K2 - K6, K10 - K13; fs_pressure.hip: K7 - K8, the Poisson residual;
-// fs_diag.hip: flow diagnostics, history, body loads, time averages, harmonic modes, snapshot POD, flow maps, vortices; fs_tracers.hip: tracer
+// fs_diag.hip: flow diagnostics, history, body loads, time averages, harmonic modes, snapshot POD, flow maps, vortices, distributions, spectra; fs_tracers.hip: tracer
 // particles; fs_multigrid.hip: the multigrid updater):
 // the launch wrapper (profiling events, tape recording), XCD-band launch geometry with compact tile lists, the typed kernel dispatch,
 // argument checks.

@@ -18,6 +18,7 @@ from .loads import Tracker, body_centroid, face_geometry
 from .modes import Modes, fit as fit_modes, gram_matrix, phasor_steps, reconstruct_weights
 from .pod import Pod
 from . import dist as _dist
+from . import spectra as _spectra
 from .vortices import VELOCITY_LIMIT, Vortices, assemble, omega_exponent
 from .pressure_updater import JacobiPressureUpdater, MultigridPressureUpdater, RedBlackSorPressureUpdater
 from .solver import CipMacSolver, DyeCipMacSolver, DyeMacSolver, MacSolver
@@ -97,6 +98,7 @@ class FluidSimulator:
         self._moder = None         # fs.modes.Modes while start_modes() is on
         self._podr = None          # fs.pod.Pod while start_pod() is on
         self._distr = None         # fs.dist.Distributions while start_distributions() is on
+        self._spectrar = None      # fs.spectra.Spectra while start_spectra() is on
         self._tracers = None       # fs.tracers.Tracers while seed_tracers() is on
         self._tracker = None       # fs.loads.Tracker while track_body() is on
         self._last_tracker = None  # ... and after stop_body(): what body_loads() / body_surface() still return
@@ -105,10 +107,10 @@ class FluidSimulator:
         self._found_planes = None  # the planes of the last find_vortices()
 
     def _riders(self):
-        """The attached riders (fs.riders.Rider) in their fixed order - history, averages, modes, pod, distributions, loads, tracers, vortices:
-        the order of their launches behind the solver step and of their tokens in _signature()."""
-        return [r for r in (self._recorder, self._averager, self._moder, self._podr, self._distr, self._tracker, self._tracers, self._vortexr)
-                if r is not None]
+        """The attached riders (fs.riders.Rider) in their fixed order - history, averages, modes, pod, distributions, spectra, loads, tracers,
+        vortices: the order of their launches behind the solver step and of their tokens in _signature()."""
+        return [r for r in (self._recorder, self._averager, self._moder, self._podr, self._distr, self._spectrar, self._tracker, self._tracers,
+                            self._vortexr) if r is not None]
 
     def _capturing(self):
         return getattr(self._dev, "capturing", False)
@@ -1000,6 +1002,75 @@ class FluidSimulator:
             found.update(zip(chunk, self.order_statistics(quantity, chunk, box)["values"].tolist()))
         out = np.array([_dist.interpolate(found[a], found[b], g, method) for a, b, g in pairs], np.float64)
         return float(out[0]) if np.ndim(q) == 0 else out
+
+    # -- energy spectra (new): the windowed FFT of the velocity over a box on the device, the power of every bin accumulated ------------------
+    def start_spectra(self, box, every=1, start_step=0, window="hann", detrend=True):
+        """From the next step on, accumulate the energy spectrum of the velocity over `box` on the device (csrc/fs_spec.h): after every step
+        k (counted from here) with k > start_step and (k - start_step) % every == 0 the box's (u + i w), windowed, goes through a 2-D FFT
+        in double and the power of every bin is added to a plane.  box = (x0, y0, x1, y1) in global cells, half-open, inside the grid, both
+        sides powers of two in 8 .. 4096 (ValueError otherwise, before any device call); wall cells count as zeros.  window: "hann"
+        (periodic) or "boxcar"; detrend: remove the window-weighted mean of u and w in spectral space (the DC bin and, under the Hann
+        window, its eight neighbours).  The launches are part of the step: they are captured into the replayed graphs, decide on the device
+        whether they sample, and run() is not cut into chunks by them.  A plane is a pure function of the fields: identical between eager
+        steps, replayed graphs and resumed runs.  40 bytes per cell of the box of device memory.  Changes no field and no trajectory.
+        spectra() returns the result.  Raises while a spectrum is attached already and during a graph capture; single-GPU contexts only
+        (FsError on slabs)."""
+        dev = self._dev
+        self._not_capturing("start_spectra")
+        self._make_way("_spectrar", "a spectrum is attached already: stop_spectra() first (or reset_spectra())")
+        every, start_step = self._cadence(every, start_step)
+        self._spectrar = _spectra.Spectra(dev, _spectra.create(dev, box, window, detrend, every, start_step), window, self._solver.dx)
+
+    def _spectra(self):
+        if self._spectrar is None:
+            raise RuntimeError("no spectrum: call start_spectra() first")
+        return self._spectrar
+
+    def spectra(self):
+        """The spectrum so far: {"power": float64 (Nx, Ny), the mean over the samples of (P[k] + P[-k]) / 2, indexed like np.fft.fft2;
+        "energy": power / 2 / (Nx Ny sum(wx^2) sum(wy^2)) - its sum over all bins is the window-weighted mean of (u'^2 + w'^2) / 2;
+        "kx", "ky": rad per length; "k", "E": the shell spectrum (fs.spectra.shell_spectrum); "samples", "sample_steps", "box", "window",
+        "detrend"; "sums": the device's plane as accumulated}.  fs.spectra.slope / line_spectrum work on it.  A download of the power
+        plane; not allowed during a graph capture."""
+        self._not_capturing("spectra")
+        return self._spectra().data()
+
+    def reset_spectra(self):
+        """Power plane and sample count back to zero; the step count and the phase of `every` / `start_step` run on."""
+        self._not_capturing("reset_spectra")
+        self._spectra().reset()
+
+    def stop_spectra(self):
+        """Detach the spectrum and free its device memory; the cached graphs that hold its launches are freed first.  Nothing is kept on
+        the host: call spectra() before.  Inside a graph capture the device memory is released when the capture ends."""
+        self._detach(self, "_spectrar", "stop_spectra")
+
+    def _spectrum_once(self, name, box, window, detrend, read):
+        dev = self._dev
+        self._not_capturing(name)
+        sp = _spectra.create(dev, box, window, detrend, 1, 0)
+        try:
+            saved, dev._oplog = getattr(dev, "_oplog", None), None      # (never part of a logged period)
+            try:
+                dev.spec_launch(sp, self._solver.get_fields()[0])
+            finally:
+                dev._oplog = saved
+            return read(sp)
+        finally:
+            dev.spec_free(sp)
+
+    def spectrum(self, box, window="hann", detrend=True):
+        """The spectrum of the fields as they are now: the dict spectra() returns, with "samples" 1 and "sample_steps" [0] (the call counts
+        no steps).  One temporary object, one eager launch, a read and a free: changes no field, no graph and no attached rider, and
+        leaves a deferred limit_field deferred.  Not allowed during a graph capture."""
+        sums, _, samples = self._spectrum_once("spectrum", box, window, detrend, self._dev.spec_read)
+        return _spectra.result(sums, samples, np.zeros(samples, np.int64), self._dev.spec_box(box), window, detrend, self._solver.dx)
+
+    def box_fft(self, box, window="hann", detrend=False):
+        """The transform itself: complex128 (Nx, Ny), Z' = FFT2((u + i w) wx wy) over the box as the device computes it (wall cells as
+        zeros; detrend as in start_spectra), indexed like np.fft.fft2.  fs.spectra.split gives the two components.  As spectrum():
+        temporary, eager, changes nothing."""
+        return self._spectrum_once("box_fft", box, window, detrend, self._dev.spec_plane)
 
     # -- flow maps and FTLE fields (new): a lattice of particles carried through the POD's resident snapshots on the device --------------
     def flow_map(self, direction="backward", refine=1, box=None, substeps=1, first=None, last=None):

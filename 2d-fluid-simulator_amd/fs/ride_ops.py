@@ -1,5 +1,5 @@
 """Device side of what rides the step and of the diagnostics (new; the reference has none): flow statistics, the per-step history, the
-body surface loads, the time averages, the harmonic modes, the snapshot POD, the flow maps through its snapshots, the field distributions and the tracer particles.  Two mixins: RideOps is the
+body surface loads, the time averages, the harmonic modes, the snapshot POD, the flow maps through its snapshots, the field distributions, the energy spectra and the tracer particles.  Two mixins: RideOps is the
 backend-agnostic host logic fs.runtime.DeviceBase inherits (slab partition, combination over ranks, argument checks, the op log of a logged period), NativeRideOps the `_p_*` primitives
 fs.runtime.Device binds to libfs_hip.so; the stand-in devices of the CPU tests override those.  fs.runtime re-exports every name here."""
 import collections
@@ -94,6 +94,15 @@ class DistChannel(collections.namedtuple("DistChannel", "quantity bins lo hi qua
         return (self.bins, self.bins_b) if self.joint else (self.bins,)
 
 
+class Spec(_Handle):
+    """Device planes of an energy spectrum (DeviceBase.spec_create): handle, the cell box, its sides (nx, ny), detrend, every, start."""
+
+    def __init__(self, h, box, detrend, every, start):
+        super().__init__(h)
+        self.box, self.detrend, self.every, self.start = tuple(box), bool(detrend), every, start
+        self.nx, self.ny = box[2] - box[0], box[3] - box[1]
+
+
 class FlowMap(_Handle):
     """A device lattice of flow-map nodes (DeviceBase.flowmap_create): handle, cell box, refine, and the lattice (nx, ny)."""
 
@@ -121,7 +130,7 @@ class History(_Handle):
 
 
 class RideOps:
-    """flow_stats and the history_* / loads_* / mean_* / modes_* / pod_* / flowmap_* / dist_* / tracer_* calls of DeviceBase."""
+    """flow_stats and the history_* / loads_* / mean_* / modes_* / pod_* / flowmap_* / dist_* / spec_* / tracer_* calls of DeviceBase."""
 
     # (The tracer calls reach these through the class - RideOps._host_only(self, ...) - as they always reached _tracer_host_call: the CPU
     #  tests check their refusals on objects that are no devices.)
@@ -777,6 +786,89 @@ class RideOps:
             raise ValueError(f"ranks must be >= 0 and ascending, got {ranks}")
         return self._p_dist_select(q, box, self._limit_of(v), float(dx), v._h, p._h, ranks)
 
+    # ---- energy spectra (include/fs_hip.h fs_spec_*): the windowed FFT of the velocity over a box, accumulated power; csrc/fs_spec.h ----
+    SPEC_MIN_N, SPEC_MAX_N = 8, 4096
+
+    def _spec_host_call(self, what):
+        RideOps._host_only(self, f"{what} during a graph capture")
+        if self.nranks > 1:
+            raise _lib.FsError("energy spectra need a single-GPU context: on slabs the transform along y crosses the ranks (not implemented)")
+
+    def spec_box(self, box):
+        """(x0, y0, x1, y1) in global cells, half-open, inside the grid, both sides powers of two in SPEC_MIN_N .. SPEC_MAX_N -> the tuple
+        of ints (ValueError)."""
+        try:
+            box = tuple(int(b) for b in box)
+        except TypeError:
+            raise ValueError(f"box must be (x0, y0, x1, y1), got {box!r}") from None
+        if len(box) != 4 or not (0 <= box[0] < box[2] <= self.nx and 0 <= box[1] < box[3] <= self.ny):
+            raise ValueError(f"box must be (x0, y0, x1, y1) with 0 <= x0 < x1 <= {self.nx} and 0 <= y0 < y1 <= {self.ny}, got {box}")
+        for n in (box[2] - box[0], box[3] - box[1]):
+            if n & (n - 1) or not RideOps.SPEC_MIN_N <= n <= RideOps.SPEC_MAX_N:
+                raise ValueError(f"the sides of a spectrum box must be powers of two in {RideOps.SPEC_MIN_N} .. {RideOps.SPEC_MAX_N}, "
+                                 f"got {box[2] - box[0]} x {box[3] - box[1]}")
+        return box
+
+    def spec_create(self, box, wx, wy, twx, twy, c1x=0.0, c1y=0.0, detrend=False, every=1, start=0):
+        """Device planes for FluidSimulator.start_spectra / spectrum / box_fft: wx (Nx,), wy (Ny,) the windows, twx (Nx / 2, 2), twy
+        (Ny / 2, 2) the twiddles (cos, -sin) of 2 pi k / N - fs.spectra.window_table / twiddles -, the detrend pair.  40 bytes per cell of
+        the box.  Launch n (from 0) of spec_launch samples when n + 1 > start and (n + 1 - start) % every == 0.  Box and sizes are checked
+        (ValueError) before any device call.  Single-context grids only (FsError on a slab); not allowed during a graph capture."""
+        box = RideOps.spec_box(self, box)
+        nx, ny = box[2] - box[0], box[3] - box[1]
+        tabs = [np.ascontiguousarray(t, np.float64) for t in (wx, wy, twx, twy)]
+        for t, shape, name in zip(tabs, ((nx,), (ny,), (nx // 2, 2), (ny // 2, 2)), ("wx", "wy", "twx", "twy")):
+            if t.shape != shape:
+                raise ValueError(f"{name} must have shape {shape}, got {t.shape}")
+        c1x, c1y = float(c1x), float(c1y)
+        if not (math.isfinite(c1x) and math.isfinite(c1y)):
+            raise ValueError("the detrend pair must be finite")
+        every, start = RideOps._check_cadence(every, start)
+        RideOps._spec_host_call(self, "spec_create")
+        h = self._p_spec_create(box, *tabs, c1x, c1y, bool(detrend), every, start)
+        return self._adopt(h, Spec(h, box, detrend, every, start))
+
+    def spec_launch(self, sp, v):
+        """The launches of one step: load and transform along x, transpose, transform along y, detrend and power, the tick - all but the
+        tick return at once unless this launch samples.  A limit_field v still owes stays deferred: the kernel limits the values it
+        reads.  Not a _run: no flush, no exchange, no ghost row (writes no field)."""
+        self._ride("spec_launch", (sp._h, self._limit_of(v), v._h))
+
+    def spec_read(self, sp, power=True):
+        """-> (power float64 (Nx, Ny): the sums of |Z'|^2 over the samples, not symmetrised - None with power=False -, launches, samples).
+        Not allowed during a graph capture."""
+        self._host_only("spec_read during a graph capture: the power plane is a download (read between captures / replays)")
+        plane, launches, samples = self._p_spec_read(sp._h, sp.nx * sp.ny if power else 0)
+        return (plane.reshape(sp.nx, sp.ny) if power else None), int(launches), int(samples)
+
+    def spec_plane(self, sp):
+        """-> Z' of the last sampling launch, complex128 (Nx, Ny) (zeros before the first).  Not allowed during a graph capture."""
+        self._host_only("spec_plane during a graph capture")
+        return self._p_spec_plane(sp._h, sp.nx * sp.ny).view(np.complex128).reshape(sp.nx, sp.ny)
+
+    def spec_get(self, sp):
+        """-> (the power plane float64 (Nx, Ny), launches, samples), for checkpoints."""
+        self._host_only("spec_get during a graph capture")
+        plane, launches, samples = self._p_spec_get(sp._h, sp.nx * sp.ny)
+        return plane.reshape(sp.nx, sp.ny), int(launches), int(samples)
+
+    def spec_set(self, sp, power, launches, samples):
+        """Restore what spec_get returned (resume)."""
+        self._host_only("spec_set during a graph capture")
+        power = np.ascontiguousarray(power, np.float64)
+        if power.shape != (sp.nx, sp.ny):
+            raise ValueError(f"expected a power plane of shape {(sp.nx, sp.ny)}, got {power.shape}")
+        launches, samples = self._check_counters(launches, samples)
+        self._p_spec_set(sp._h, power, launches, samples)
+
+    def spec_reset(self, sp):
+        """Power plane and sample count to zero; the launch count runs on.  Not allowed during a graph capture."""
+        self._host_only("spec_reset during a graph capture")
+        self._p_spec_reset(sp._h)
+
+    def spec_free(self, sp):
+        self._release(sp, self._p_spec_free)
+
     # ---- flow maps (include/fs_hip.h fs_flowmap_*): a lattice of particles carried through the resident snapshots of a POD; csrc/fs_lcs.h ----
     def flowmap_create(self, box=None, refine=1):
         """A device lattice for FluidSimulator.flow_map: refine x refine nodes per cell of the cell box (x0, y0, x1, y1) (None: the whole
@@ -1265,6 +1357,41 @@ class NativeRideOps:
                 raise ValueError(f"rank {ranks[-1]} >= n = {n.value}, the number of selected cells whose value is not NaN") from None
             raise
         return out, n.value, nan.value
+
+    def _p_spec_create(self, box, wx, wy, twx, twy, c1x, c1y, detrend, every, start):
+        h = ctypes.c_void_p()
+        dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        _lib.call("fs_spec_create", self._ctx, (ctypes.c_int * 4)(*box), dp(wx), dp(wy), dp(twx), dp(twy), c1x, c1y, int(detrend), every, start,
+                  ctypes.byref(h))
+        return h
+
+    def _p_spec_read(self, h, cells):
+        plane = np.empty(cells, np.float64)
+        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
+        _lib.call("fs_spec_read", self._ctx, h, plane.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if cells else None, ctypes.byref(launches),
+                  ctypes.byref(samples))
+        return plane, launches.value, samples.value
+
+    def _p_spec_plane(self, h, cells):
+        out = np.empty(2 * cells, np.float64)
+        _lib.call("fs_spec_plane", self._ctx, h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        return out
+
+    def _p_spec_get(self, h, cells):
+        plane = np.empty(cells, np.float64)
+        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
+        _lib.call("fs_spec_get", self._ctx, h, plane.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(launches), ctypes.byref(samples))
+        return plane, launches.value, samples.value
+
+    def _p_spec_set(self, h, power, launches, samples):
+        _lib.call("fs_spec_set", self._ctx, h, power.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), launches, samples)
+
+    def _p_spec_reset(self, h):
+        _lib.call("fs_spec_reset", self._ctx, h)
+
+    def _p_spec_free(self, h):
+        if self._ctx is not None:
+            _lib.call("fs_spec_free", self._ctx, h)
 
     def _p_flowmap_create(self, box, refine):
         h = ctypes.c_void_p()

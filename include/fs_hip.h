@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 24
+#define FS_ABI_VERSION 25
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -543,6 +543,38 @@ int fs_dist_reset(fs_ctx *ctx, fs_dist *d);
 int fs_dist_free(fs_ctx *ctx, fs_dist *d);
 int fs_dist_select(fs_ctx *ctx, int quantity, const int *box, double limit, double dx, const fs_field *v, const fs_field *p,
                    const long long *ranks, int nranks, double *values_out, long long *n, long long *nan);
+
+/* Energy spectra (new, ABI 25): the windowed 2-D FFT of the velocity over a box of cells and the accumulated power of every bin, by launches
+ * that can be captured in a hipGraph (the transform, the operation order and the kernels: csrc/fs_spec.h).  All doubles; a plane is a pure
+ * function of the field, the tables and the order of the samples - no atomics.  The box is half-open, x0, y0, x1, y1 of global cells inside the
+ * grid, its sides Nx = x1 - x0 and Ny = y1 - y0 powers of two in FS_SPEC_MIN_N .. FS_SPEC_MAX_N (else FS_ERR_ARG).  Planes are (Nx, Ny) in C
+ * order, bin (a, b) at a * Ny + b, indexed like a DFT: a and b are the wavenumber indices modulo N.  Single-GPU contexts: create returns
+ * FS_ERR_UNSUPPORTED on a slab context.
+ * create:  wx[Nx], wy[Ny]: the window of each axis; twx, twy: per axis N / 2 pairs (cos, -sin) of 2 pi k / N, N doubles - all four are copied;
+ *          the library calls no sin or cos.  detrend != 0: Z'[a, b] = Z[a, b] - (Z[0, 0] c[a]) c[b] with c[0] = 1, c[1] = c[N - 1] = c1x / c1y
+ *          and 0 elsewhere (nine bins).  every >= 1, start >= 0 (the sampling rule of fs_mean_create).  Power and counters start at zero.
+ *          Device memory: 40 bytes per cell of the box.
+ * launch:  five kernel launches, nothing else (no allocation, copy or synchronisation: capturable); all but the last return at once unless
+ *          this launch samples: Z = FFT2((u + i w) wx wy), wall cells as zeros, and power += |Z'|^2.  limit > 0: v still owes
+ *          limit_field(limit).  Needs the mask.
+ * read:    synchronises; power: Nx * Ny doubles, the sums over the samples, or NULL; launches, samples: may be NULL.  Resets nothing.
+ * plane:   the Z' of the last sampling launch, 2 * Nx * Ny doubles (re, im interleaved); zeros before the first.
+ * get / set: the power plane and the counters, for checkpoints; set: 0 <= samples <= launches.
+ * reset:   power and sample count to zero; the launch count runs on.
+ * free:    as fs_mean_free (during a capture the release is deferred to its end).
+ * Everything but launch and free returns FS_ERR_STATE during graph capture / tape recording.                                             */
+#define FS_SPEC_MIN_N 8
+#define FS_SPEC_MAX_N 4096
+typedef struct fs_spec fs_spec;
+int fs_spec_create(fs_ctx *ctx, const int *box, const double *wx, const double *wy, const double *twx, const double *twy, double c1x, double c1y,
+                   int detrend, long long every, long long start, fs_spec **out);
+int fs_spec_launch(fs_ctx *ctx, fs_spec *s, double limit, const fs_field *v);
+int fs_spec_read(fs_ctx *ctx, fs_spec *s, double *power, long long *launches, long long *samples);
+int fs_spec_plane(fs_ctx *ctx, fs_spec *s, double *plane);
+int fs_spec_get(fs_ctx *ctx, fs_spec *s, double *power, long long *launches, long long *samples);
+int fs_spec_set(fs_ctx *ctx, fs_spec *s, const double *power, long long launches, long long samples);
+int fs_spec_reset(fs_ctx *ctx, fs_spec *s);
+int fs_spec_free(fs_ctx *ctx, fs_spec *s);
 
 /* Multigrid pressure correction (new, ABI 19): one W-cycle (two coarse visits per level) on a mask-aware hierarchy of coarse levels, for the
  * third pressure updater (fs/pressure_updater.py MultigridPressureUpdater; kernels and operation order: csrc/fs_mg.h).  Single-GPU contexts.

@@ -1,0 +1,72 @@
+"""Cost of the energy spectrum: steps/s of FluidSimulator.run(graph=True) without and with start_spectra(box, every=K), alternated in one
+process so that clock drift hits both alike.  One JSON line per configuration; --out appends them to a text file
+(profiles/spectra_cost.txt).  --box x0,y0,x1,y1 (default: the largest power-of-two box that fits, from the grid's origin).
+
+  python tools/spectra_cost.py --bc 5 --res 4096 --box 0,0,4096,2048 --steps 300 --reps 3 --every 1 --out profiles/spectra_cost.txt
+  python tools/spectra_cost.py --bc 1 --res 400 --box 0,0,256,128 --steps 4000 --reps 3 --every 10 --out profiles/spectra_cost.txt
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "2d-fluid-simulator_amd"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--bc", type=int, default=1)
+    ap.add_argument("--res", type=int, default=400)
+    ap.add_argument("--box", default=None)
+    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--every", type=int, default=1)
+    ap.add_argument("--re", type=float, default=1e6)
+    ap.add_argument("--scheme", default="cip")
+    ap.add_argument("--vc", type=float, default=5.0)
+    ap.add_argument("--out", default=None, help="append the JSON line to this file")
+    a = ap.parse_args()
+    import fs
+    fs.runtime.init(gpu=0, dtype="f32")
+    res = a.res
+    sim = fs.FluidSimulator.create(a.bc, res, 0.05 / res, 1.0 / res, a.re, a.vc or None, a.scheme)
+    dev = sim._solver._bc.device
+    if a.box:
+        box = tuple(int(x) for x in a.box.split(","))
+    else:
+        box = (0, 0, min(4096, 1 << (dev.nx.bit_length() - 1)), min(4096, 1 << (dev.ny.bit_length() - 1)))
+    sim.run(64)
+    rates = {False: [], True: []}
+    for _ in range(a.reps):
+        for on in (False, True):
+            if on:
+                sim.start_spectra(box, every=a.every)
+            sim.run(64)                              # (captures the graphs of this mode)
+            dev.sync()
+            t0 = time.perf_counter()
+            sim.run(a.steps)
+            dev.sync()
+            rates[on].append(a.steps / (time.perf_counter() - t0))
+            if on:
+                n = sim.spectra()["samples"]
+                sim.stop_spectra()
+                assert n == (a.steps + 64) // a.every, n
+    off, on = np.median(rates[False]), np.median(rates[True])
+    out = {"tool": "spectra_cost", "bc": a.bc, "res": res, "box": list(box), "steps": a.steps, "every": a.every,
+           "off_steps_per_s": [round(r, 1) for r in rates[False]], "on_steps_per_s": [round(r, 1) for r in rates[True]],
+           "us_per_step_off": round(1e6 / off, 3), "us_per_step_on": round(1e6 / on, 3), "us_per_step_cost": round(1e6 / on - 1e6 / off, 3),
+           "cost_percent": round(100.0 * (off / on - 1.0), 2)}
+    line = json.dumps(out)
+    print(line, flush=True)
+    if a.out:
+        with open(a.out, "a") as fh:
+            fh.write(line + "\n")
+    dev.close()
+
+
+if __name__ == "__main__":
+    main()
