@@ -1,6 +1,6 @@
 // fs_diag.hip - C-ABI entry points of what reads the flow without changing it: the flow diagnostics (fs_stats.h), the per-step history ring
 // (fs_history.h), the body surface loads (fs_loads.h), the time averages (fs_mean.h), the harmonic modes (fs_modes.h), the snapshot POD
-// (fs_pod.h), the flow maps through its snapshots (fs_lcs.h), the vortex identification (fs_vortex.h), the field distributions (fs_dist.h) and the energy spectra (fs_spec.h).  Their objects live in the context's
+// (fs_pod.h), the flow maps through its snapshots (fs_lcs.h), the vortex identification (fs_vortex.h), the field distributions (fs_dist.h), the energy spectra (fs_spec.h) and the cross-spectra (fs_xspec.h).  Their objects live in the context's
 // registry (fs_host.h: FS_OBJECT, FS_HANDLE, FS_NO_CAPTURE, object_free).
 #include "fs_launch.h"
 #include "fs_stats.h"
@@ -12,6 +12,7 @@
 #include "fs_vortex.h"
 #include "fs_dist.h"
 #include "fs_spec.h"
+#include "fs_xspec.h"
 
 static_assert(fs::STATS_N == FS_FLOW_NSTAT, "fs_stats.h and include/fs_hip.h disagree on the slots");
 static_assert(fs::LOADS_REC == FS_LOADS_NREC && fs::LOADS_SUMS == FS_LOADS_NSUM, "fs_loads.h and include/fs_hip.h disagree on the record / the sums");
@@ -28,6 +29,7 @@ static_assert(fs::VX_NACC == FS_VORTEX_NACC && fs::VX_REC == FS_VORTEX_NREC && f
 static_assert(fs::DIST_MAX_BINS == FS_DIST_MAX_BINS && fs::DIST_MAX_CHANNELS == FS_DIST_MAX_CHANNELS && fs::DIST_MAX_RANKS == FS_DIST_MAX_RANKS && fs::DIST_TAILS == FS_DIST_NTAIL,
               "fs_dist.h and include/fs_hip.h disagree");
 static_assert(fs::SPEC_MIN_N == FS_SPEC_MIN_N && fs::SPEC_MAX_N == FS_SPEC_MAX_N, "fs_spec.h and include/fs_hip.h disagree");
+static_assert(fs::XSPEC_PLANES == FS_XSPEC_NPLANE && fs::XSPEC_NQ == fs::DIST_NQ, "fs_xspec.h, fs_dist.h and include/fs_hip.h disagree");
 
 FS_OBJECT(fs_history, OBJ_HISTORY, "history", "history from another context or freed");
 FS_OBJECT(fs_loads, OBJ_LOADS, "loads", "loads from another context or freed");
@@ -37,6 +39,7 @@ FS_OBJECT(fs_pod, OBJ_POD, "pod", "pod from another context or freed");
 FS_OBJECT(fs_vortex, OBJ_VORTEX, "vortex", "vortex tracker from another context or freed");
 FS_OBJECT(fs_dist, OBJ_DIST, "distributions", "distributions from another context or freed");
 FS_OBJECT(fs_spec, OBJ_SPEC, "spectrum", "spectrum from another context or freed");
+FS_OBJECT(fs_xspec, OBJ_XSPEC, "cross-spectrum", "cross-spectrum from another context or freed");
 FS_OBJECT(fs_flowmap, OBJ_FLOWMAP, "flow map", "flow map from another context or freed");
 
 using namespace fs;
@@ -1357,6 +1360,153 @@ int fs_spec_reset(fs_ctx *ctx, fs_spec *s)
 }
 
 int fs_spec_free(fs_ctx *ctx, fs_spec *s) { return object_free(ctx, s); }
+
+// ---- cross-spectra (fs_xspec.h) ----------------------------------------------------------------------------------------------------------------
+int fs_xspec_create(fs_ctx *ctx, const int *box, int qa, int qb, double dx, const double *wx, const double *wy, const double *twx, const double *twy,
+                    double c1x, double c1y, int detrend, long long every, long long start, fs_xspec **out)
+{
+    FS_REQUIRE(ctx && box && wx && wy && twx && twy && out, "null argument");
+    FS_REQUIRE(0 <= box[0] && box[0] < box[2] && box[2] <= ctx->X && 0 <= box[1] && box[1] < box[3] && box[3] <= ctx->Y,
+               "spectrum box must satisfy 0 <= x0 < x1 <= X and 0 <= y0 < y1 <= Y");
+    const int nx = box[2] - box[0], ny = box[3] - box[1];
+    FS_REQUIRE(spec_log2(nx) > 0 && spec_log2(ny) > 0, "the sides of a spectrum box must be powers of two in FS_SPEC_MIN_N .. FS_SPEC_MAX_N");
+    FS_REQUIRE(0 <= qa && qa < XSPEC_NQ && -1 <= qb && qb < XSPEC_NQ, "the quantities of a cross-spectrum must satisfy 0 <= qa <= 6 and -1 <= qb <= 6");
+    FS_REQUIRE(std::isfinite(dx) && dx > 0.0, "dx must be finite and > 0");
+    FS_REQUIRE(std::isfinite(c1x) && std::isfinite(c1y), "the detrend pair must be finite");
+    FS_EVERY_START(every, start);
+    FS_NO_CAPTURE(fs_xspec, "create");
+    if (ctx->halo != 0 || ctx->nyl != ctx->Y) {
+        set_error("cross-spectra need a single-GPU context: on a slab the transform along y crosses the ranks (not implemented)");
+        return FS_ERR_UNSUPPORTED;
+    }
+    FS_HIP(hipSetDevice(ctx->device));
+    auto s = std::make_unique<fs_xspec>();
+    for (int k = 0; k < 4; ++k) s->box[k] = box[k];
+    s->nx = nx; s->ny = ny; s->qa = qa; s->qb = qb; s->planes = qb >= 0 ? XSPEC_PLANES : 1; s->dx = dx;
+    s->detrend = detrend ? 1 : 0; s->c1x = c1x; s->c1y = c1y; s->every = every; s->start = start;
+    const size_t cells = (size_t)nx * ny, acc = cells * s->planes * sizeof(double);
+    hipError_t e = s->d_state.alloc(SPEC_STATE * sizeof(long long));
+    if (e == hipSuccess) e = s->d_wx.alloc(nx * sizeof(double));
+    if (e == hipSuccess) e = s->d_wy.alloc(ny * sizeof(double));
+    if (e == hipSuccess) e = s->d_twx.alloc(nx * sizeof(double));
+    if (e == hipSuccess) e = s->d_twy.alloc(ny * sizeof(double));
+    if (e == hipSuccess) e = s->d_a.alloc(cells * sizeof(double2));
+    if (e == hipSuccess) e = s->d_b.alloc(cells * sizeof(double2));
+    if (e == hipSuccess) e = s->d_acc.alloc(acc);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_wx, wx, nx * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_wy, wy, ny * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_twx, twx, nx * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_twy, twy, ny * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_state, 0, SPEC_STATE * sizeof(long long), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_a, 0, cells * sizeof(double2), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_b, 0, cells * sizeof(double2), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_acc, 0, acc, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);      // (the tables are the caller's memory: nothing is in flight past here)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return hip_fail(e, "fs_xspec_create", __FILE__, __LINE__);
+    *out = adopt(ctx, std::move(s));
+    return FS_OK;
+}
+
+int fs_xspec_launch(fs_ctx *ctx, fs_xspec *s, double limit, const fs_field *v, const fs_field *p)
+{
+    FS_REQUIRE(ctx && s, "null argument");
+    FS_HANDLE(s);
+    FS_FIELD(v, 2); FS_FIELD(p, 1);
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    // everything the launches need is in `s` and the fields: no allocation, copy or synchronisation here (the closures are captured / taped)
+    const int x0 = s->box[0], y0 = s->box[1], nx = s->nx, ny = s->ny, lognx = spec_log2(nx), logny = spec_log2(ny), detrend = s->detrend;
+    const int qa = s->qa, qb = s->qb, need = dist_need(qa) | dist_need(qb), pair = qb >= 0 ? 1 : 0;
+    const double c1x = s->c1x, c1y = s->c1y, two_dx = 2.0 * s->dx;
+    const long long every = s->every, start = s->start;
+    long long *state = s->d_state;
+    const SpecWhen when{state, start, every};
+    const size_t cells = (size_t)nx * ny;
+    const dim3 chunks((unsigned)((cells + SPEC_CHUNK - 1) / SPEC_CHUNK));
+    const double *wx = s->d_wx, *wy = s->d_wy, *twx = s->d_twx, *twy = s->d_twy;
+    double2 *A = s->d_a, *B = s->d_b;
+    double *acc = s->d_acc;
+    int rc = by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
+        return launch(ctx, "xspec_load_rows", [=] {
+            klaunch(k_xspec_load_rows<T>, chunks, dim3(256), ctx->stream, ctx->grid(), when, x0, y0, nx, ny, lognx, qa, qb, need, limit, two_dx,
+                    (const T *)v->d, (const T *)p->d, wx, wy, twx, A);
+        });
+    });
+    if (rc) return rc;
+    rc = launch(ctx, "spec_transpose", [=] {
+        klaunch(k_spec_transpose, dim3((nx + SPEC_TILE - 1) / SPEC_TILE, (ny + SPEC_TILE - 1) / SPEC_TILE), dim3(256), ctx->stream, when, ny, nx,
+                (const double2 *)A, B);
+    });
+    if (rc) return rc;
+    rc = launch(ctx, "spec_rows", [=] { klaunch(k_spec_rows, chunks, dim3(256), ctx->stream, when, ny, logny, cells, (const double2 *)B, twy, A); });
+    if (rc) return rc;
+    rc = launch(ctx, "xspec_accumulate", [=] {
+        klaunch(k_xspec_accumulate, dim3((unsigned)((cells + 255) / 256)), dim3(256), ctx->stream, when, nx, ny, logny, detrend, pair, c1x, c1y,
+                (const double2 *)A, B, acc);
+    });
+    if (rc) return rc;
+    return launch(ctx, "spec_tick", [=] { klaunch(k_spec_tick, dim3(1), dim3(64), ctx->stream, start, every, state); });
+}
+
+int fs_xspec_read(fs_ctx *ctx, fs_xspec *s, double *sums, long long *launches, long long *samples)
+{
+    FS_REQUIRE(ctx && s, "null argument");
+    FS_HANDLE(s);
+    FS_NO_CAPTURE(fs_xspec, "read");
+    long long st[SPEC_STATE];
+    if (int rc = read_counters(ctx, s->d_state, st)) return rc;
+    if (sums) {
+        FS_HIP(hipMemcpyAsync(sums, s->d_acc, (size_t)s->planes * s->nx * s->ny * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        FS_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    if (launches) *launches = st[0];
+    if (samples) *samples = st[1];
+    return FS_OK;
+}
+
+int fs_xspec_plane(fs_ctx *ctx, fs_xspec *s, double *plane)
+{
+    FS_REQUIRE(ctx && s && plane, "null argument");
+    FS_HANDLE(s);
+    FS_NO_CAPTURE(fs_xspec, "plane");
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemcpyAsync(plane, s->d_b, (size_t)s->nx * s->ny * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_xspec_get(fs_ctx *ctx, fs_xspec *s, double *sums, long long *launches, long long *samples)
+{
+    FS_REQUIRE(ctx && s && sums && launches && samples, "null argument");
+    return fs_xspec_read(ctx, s, sums, launches, samples);
+}
+
+int fs_xspec_set(fs_ctx *ctx, fs_xspec *s, const double *sums, long long launches, long long samples)
+{
+    FS_REQUIRE(ctx && s && sums, "null argument");
+    FS_HANDLE(s);
+    FS_COUNTERS(launches, samples);
+    FS_NO_CAPTURE(fs_xspec, "set");
+    FS_HIP(hipSetDevice(ctx->device));
+    const long long st[SPEC_STATE] = {launches, samples};
+    FS_HIP(hipMemcpyAsync(s->d_acc, sums, (size_t)s->planes * s->nx * s->ny * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipMemcpyAsync(s->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
+    return FS_OK;
+}
+
+int fs_xspec_reset(fs_ctx *ctx, fs_xspec *s)
+{
+    FS_REQUIRE(ctx && s, "null argument");
+    FS_HANDLE(s);
+    FS_NO_CAPTURE(fs_xspec, "reset");
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemsetAsync(s->d_acc, 0, (size_t)s->planes * s->nx * s->ny * sizeof(double), ctx->stream));
+    FS_HIP(hipMemsetAsync(s->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
+    return FS_OK;
+}
+
+int fs_xspec_free(fs_ctx *ctx, fs_xspec *s) { return object_free(ctx, s); }
 
 // ---- flow maps through the resident snapshots (fs_lcs.h) ----------------------------------------------------------------------------------
 

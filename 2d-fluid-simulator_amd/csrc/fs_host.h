@@ -290,6 +290,23 @@ struct fs_spec {
     fs::DevBuf<long long> d_state;   // [SPEC_STATE]
 };
 
+// cross-spectra (fs_xspec_*, fs_xspec.h): fs_spec's box, tables and work planes, the pair of quantities and the accumulator planes
+struct fs_xspec {
+    int box[4] = {0, 0, 0, 0};      // x0, y0, x1, y1 (cells)
+    int nx = 0, ny = 0;             // the box's sides, powers of two
+    int qa = 0, qb = -1;            // the quantities (fs_dist.h); qb -1: one scalar
+    int planes = 1;                 // accumulator planes: XSPEC_PLANES for a pair, 1 for one scalar
+    int detrend = 0;
+    double dx = 0.0;
+    double c1x = 0.0, c1y = 0.0;    // the detrend pair
+    long long every = 1, start = 0;
+    fs::DevBuf<double> d_wx, d_wy;   // [nx], [ny]: the windows
+    fs::DevBuf<double> d_twx, d_twy; // [nx], [ny]: N / 2 pairs (cos, -sin) per axis
+    fs::DevBuf<double2> d_a, d_b;    // [nx * ny] each: the work planes; after a sampling launch d_b holds Z', [a][b]
+    fs::DevBuf<double> d_acc;        // [planes][nx * ny]: Paa, Pbb, Cre, Cim, each [a][b]
+    fs::DevBuf<long long> d_state;   // [SPEC_STATE]
+};
+
 namespace fs { struct LoadFace; }      // fs_loads.h (included by fs_diag.hip alone)
 // body surface loads (fs_loads_*, fs_loads.h): the face list of this context's owned rows, the per-face sums, the ring and the device counters
 struct fs_loads {
@@ -331,7 +348,7 @@ struct fs_tracer {
 namespace fs {
 
 // ---- the objects behind the other handles: one registry (fs_ctx::objects, fs_objects.h), one guard, one no-capture check, one free -------------
-enum ObjKind { OBJ_HISTORY, OBJ_LOADS, OBJ_MEAN, OBJ_MODES, OBJ_POD, OBJ_VORTEX, OBJ_FLOWMAP, OBJ_TRACER, OBJ_MG, OBJ_DIST, OBJ_SPEC };
+enum ObjKind { OBJ_HISTORY, OBJ_LOADS, OBJ_MEAN, OBJ_MODES, OBJ_POD, OBJ_VORTEX, OBJ_FLOWMAP, OBJ_TRACER, OBJ_MG, OBJ_DIST, OBJ_SPEC, OBJ_XSPEC };
 // kind, noun and stale-handle text of an object type: FS_OBJECT(type, kind, noun, text), once, in the unit that implements the type
 template <typename T> struct ObjInfo;
 #define FS_OBJECT(T, KIND, NOUN, STALE) \

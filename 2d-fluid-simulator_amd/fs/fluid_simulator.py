@@ -99,6 +99,7 @@ class FluidSimulator:
         self._podr = None          # fs.pod.Pod while start_pod() is on
         self._distr = None         # fs.dist.Distributions while start_distributions() is on
         self._spectrar = None      # fs.spectra.Spectra while start_spectra() is on
+        self._xspectrar = None     # fs.spectra.CrossSpectra while start_cross_spectra() is on
         self._tracers = None       # fs.tracers.Tracers while seed_tracers() is on
         self._tracker = None       # fs.loads.Tracker while track_body() is on
         self._last_tracker = None  # ... and after stop_body(): what body_loads() / body_surface() still return
@@ -107,10 +108,10 @@ class FluidSimulator:
         self._found_planes = None  # the planes of the last find_vortices()
 
     def _riders(self):
-        """The attached riders (fs.riders.Rider) in their fixed order - history, averages, modes, pod, distributions, spectra, loads, tracers,
-        vortices: the order of their launches behind the solver step and of their tokens in _signature()."""
-        return [r for r in (self._recorder, self._averager, self._moder, self._podr, self._distr, self._spectrar, self._tracker, self._tracers,
-                            self._vortexr) if r is not None]
+        """The attached riders (fs.riders.Rider) in their fixed order - history, averages, modes, pod, distributions, spectra, cross-spectra,
+        loads, tracers, vortices: the order of their launches behind the solver step and of their tokens in _signature()."""
+        return [r for r in (self._recorder, self._averager, self._moder, self._podr, self._distr, self._spectrar, self._xspectrar, self._tracker,
+                            self._tracers, self._vortexr) if r is not None]
 
     def _capturing(self):
         return getattr(self._dev, "capturing", False)
@@ -1071,6 +1072,75 @@ class FluidSimulator:
         zeros; detrend as in start_spectra), indexed like np.fft.fft2.  fs.spectra.split gives the two components.  As spectrum():
         temporary, eager, changes nothing."""
         return self._spectrum_once("box_fft", box, window, detrend, self._dev.spec_plane)
+
+    # -- cross-spectra (new): the packed FFT of two flow quantities over a box, split on the device into both transforms -------------------
+    def start_cross_spectra(self, box, pair=("u", "w"), every=1, start_step=0, window="hann", detrend=True):
+        """From the next step on, accumulate the spectra and the cross-spectrum of two quantities over `box` on the device
+        (csrc/fs_xspec.h).  pair = (qa, qb) or (qa, None), names out of "u", "w", "p", "speed", "vorticity", "q", "swirl" (the quantities of
+        start_distributions, same definitions): the windowed plane a + i b goes through the transform of start_spectra, the device splits
+        it into the transforms A and B of the two real fields and adds |A|^2, |B|^2 and A conj(B) of every bin to four planes.  u, w, p and
+        speed count where the cell is no wall, vorticity, q and swirl on fluid cells; every other cell counts as zero.  box, every,
+        start_step, window and detrend as in start_spectra (ValueError before any device call); 64 bytes per cell of the box of device
+        memory, 40 for one scalar.  The launches are part of the step and of the replayed graphs; the planes are a pure function of the
+        fields.  Changes no field and no trajectory, and may be attached beside start_spectra.  cross_spectra() returns the result.
+        Raises while a cross-spectrum is attached already and during a graph capture; single-GPU contexts only (FsError on slabs)."""
+        dev = self._dev
+        self._not_capturing("start_cross_spectra")
+        self._make_way("_xspectrar", "a cross-spectrum is attached already: stop_cross_spectra() first (or reset_cross_spectra())")
+        every, start_step = self._cadence(every, start_step)
+        xs = _spectra.create_cross(dev, box, pair, self._solver.dx, window, detrend, every, start_step)
+        self._xspectrar = _spectra.CrossSpectra(dev, xs, window)
+
+    def _cross_spectra(self):
+        if self._xspectrar is None:
+            raise RuntimeError("no cross-spectrum: call start_cross_spectra() first")
+        return self._xspectrar
+
+    def cross_spectra(self):
+        """The cross-spectrum so far: the dict of fs.spectra.cross_result - "spectrum_a", "spectrum_b", "co", "quad" per bin, the shell sums
+        "k", "Sa", "Sb", "Co", "Quad", "coherence" and "phase" per shell, "quantities", "samples", "sample_steps", "box", "window",
+        "detrend" and the device's planes "sums".  A download of the planes; not allowed during a graph capture."""
+        self._not_capturing("cross_spectra")
+        return self._cross_spectra().data()
+
+    def reset_cross_spectra(self):
+        """Planes and sample count back to zero; the step count and the phase of `every` / `start_step` run on."""
+        self._not_capturing("reset_cross_spectra")
+        self._cross_spectra().reset()
+
+    def stop_cross_spectra(self):
+        """Detach the cross-spectrum and free its device memory; the cached graphs that hold its launches are freed first.  Nothing is
+        kept on the host: call cross_spectra() before.  Inside a graph capture the device memory is released when the capture ends."""
+        self._detach(self, "_xspectrar", "stop_cross_spectra")
+
+    def _cross_once(self, name, box, pair, window, detrend, read):
+        dev = self._dev
+        self._not_capturing(name)
+        xs = _spectra.create_cross(dev, box, pair, self._solver.dx, window, detrend, 1, 0)
+        try:
+            saved, dev._oplog = getattr(dev, "_oplog", None), None      # (never part of a logged period)
+            try:
+                v, p = self._solver.get_fields()[:2]
+                dev.xspec_launch(xs, v, p)
+            finally:
+                dev._oplog = saved
+            return read(xs), xs
+        finally:
+            dev.xspec_free(xs)
+
+    def cross_spectrum(self, box, pair=("u", "w"), window="hann", detrend=True):
+        """The cross-spectrum of the fields as they are now: the dict cross_spectra() returns, with "samples" 1 and "sample_steps" [0].
+        One temporary object, one eager launch, a read and a free: changes no field, no graph and no attached rider, and leaves a
+        deferred limit_field deferred.  Not allowed during a graph capture."""
+        (sums, _, samples), xs = self._cross_once("cross_spectrum", box, pair, window, detrend, self._dev.xspec_read)
+        return _spectra.cross_result(sums, samples, np.zeros(samples, np.int64), xs.box, _spectra.pair_names(xs.qa, xs.qb), window, detrend,
+                                     self._solver.dx)
+
+    def pair_fft(self, box, pair=("u", "w"), window="hann", detrend=False):
+        """The transform itself: complex128 (Nx, Ny), Z' = FFT2((a + i b) wx wy) over the box as the device computes it (detrend as in
+        start_cross_spectra), indexed like np.fft.fft2; fs.spectra.split gives the transforms of a and b.  For ("u", "w") it is box_fft(),
+        bit for bit.  As cross_spectrum(): temporary, eager, changes nothing."""
+        return self._cross_once("pair_fft", box, pair, window, detrend, self._dev.xspec_plane)[0]
 
     # -- flow maps and FTLE fields (new): a lattice of particles carried through the POD's resident snapshots on the device --------------
     def flow_map(self, direction="backward", refine=1, box=None, substeps=1, first=None, last=None):

@@ -103,6 +103,17 @@ class Spec(_Handle):
         self.nx, self.ny = box[2] - box[0], box[3] - box[1]
 
 
+class XSpec(_Handle):
+    """Device planes of a cross-spectrum (DeviceBase.xspec_create): handle, the cell box, its sides (nx, ny), the quantity indices (qa, qb; qb -1:
+    one scalar), the number of accumulator planes, dx, detrend, every, start."""
+
+    def __init__(self, h, box, qa, qb, dx, detrend, every, start):
+        super().__init__(h)
+        self.box, self.qa, self.qb, self.dx, self.detrend, self.every, self.start = tuple(box), qa, qb, dx, bool(detrend), every, start
+        self.nx, self.ny = box[2] - box[0], box[3] - box[1]
+        self.planes = RideOps.XSPEC_NPLANE if qb >= 0 else 1
+
+
 class FlowMap(_Handle):
     """A device lattice of flow-map nodes (DeviceBase.flowmap_create): handle, cell box, refine, and the lattice (nx, ny)."""
 
@@ -130,7 +141,7 @@ class History(_Handle):
 
 
 class RideOps:
-    """flow_stats and the history_* / loads_* / mean_* / modes_* / pod_* / flowmap_* / dist_* / spec_* / tracer_* calls of DeviceBase."""
+    """flow_stats and the history_* / loads_* / mean_* / modes_* / pod_* / flowmap_* / dist_* / spec_* / xspec_* / tracer_* calls of DeviceBase."""
 
     # (The tracer calls reach these through the class - RideOps._host_only(self, ...) - as they always reached _tracer_host_call: the CPU
     #  tests check their refusals on objects that are no devices.)
@@ -809,14 +820,11 @@ class RideOps:
                                  f"got {box[2] - box[0]} x {box[3] - box[1]}")
         return box
 
-    def spec_create(self, box, wx, wy, twx, twy, c1x=0.0, c1y=0.0, detrend=False, every=1, start=0):
-        """Device planes for FluidSimulator.start_spectra / spectrum / box_fft: wx (Nx,), wy (Ny,) the windows, twx (Nx / 2, 2), twy
-        (Ny / 2, 2) the twiddles (cos, -sin) of 2 pi k / N - fs.spectra.window_table / twiddles -, the detrend pair.  40 bytes per cell of
-        the box.  Launch n (from 0) of spec_launch samples when n + 1 > start and (n + 1 - start) % every == 0.  Box and sizes are checked
-        (ValueError) before any device call.  Single-context grids only (FsError on a slab); not allowed during a graph capture."""
+    def _spec_checked(self, box, tables, c1x, c1y, every, start):
+        """What spec_create and xspec_create check alike (ValueError) -> (box, the four tables as contiguous float64, c1x, c1y, every, start)."""
         box = RideOps.spec_box(self, box)
         nx, ny = box[2] - box[0], box[3] - box[1]
-        tabs = [np.ascontiguousarray(t, np.float64) for t in (wx, wy, twx, twy)]
+        tabs = [np.ascontiguousarray(t, np.float64) for t in tables]
         for t, shape, name in zip(tabs, ((nx,), (ny,), (nx // 2, 2), (ny // 2, 2)), ("wx", "wy", "twx", "twy")):
             if t.shape != shape:
                 raise ValueError(f"{name} must have shape {shape}, got {t.shape}")
@@ -824,6 +832,14 @@ class RideOps:
         if not (math.isfinite(c1x) and math.isfinite(c1y)):
             raise ValueError("the detrend pair must be finite")
         every, start = RideOps._check_cadence(every, start)
+        return box, tabs, c1x, c1y, every, start
+
+    def spec_create(self, box, wx, wy, twx, twy, c1x=0.0, c1y=0.0, detrend=False, every=1, start=0):
+        """Device planes for FluidSimulator.start_spectra / spectrum / box_fft: wx (Nx,), wy (Ny,) the windows, twx (Nx / 2, 2), twy
+        (Ny / 2, 2) the twiddles (cos, -sin) of 2 pi k / N - fs.spectra.window_table / twiddles -, the detrend pair.  40 bytes per cell of
+        the box.  Launch n (from 0) of spec_launch samples when n + 1 > start and (n + 1 - start) % every == 0.  Box and sizes are checked
+        (ValueError) before any device call.  Single-context grids only (FsError on a slab); not allowed during a graph capture."""
+        box, tabs, c1x, c1y, every, start = RideOps._spec_checked(self, box, (wx, wy, twx, twy), c1x, c1y, every, start)
         RideOps._spec_host_call(self, "spec_create")
         h = self._p_spec_create(box, *tabs, c1x, c1y, bool(detrend), every, start)
         return self._adopt(h, Spec(h, box, detrend, every, start))
@@ -868,6 +884,78 @@ class RideOps:
 
     def spec_free(self, sp):
         self._release(sp, self._p_spec_free)
+
+    # ---- cross-spectra (include/fs_hip.h fs_xspec_*): the packed FFT of two quantities over a box, split and accumulated; csrc/fs_xspec.h ----
+    XSPEC_NPLANE = 4
+
+    def xspec_pair(self, pair):
+        """(qa, qb) or (qa, None), names of DIST_QUANTITIES (a single name: (name, None)) -> the indices (qa, qb), qb -1 for None (ValueError)."""
+        if isinstance(pair, str):
+            pair = (pair, None)
+        try:
+            pair = tuple(pair)
+        except TypeError:
+            raise ValueError(f"pair must be (qa, qb) or (qa, None), got {pair!r}") from None
+        if len(pair) != 2:
+            raise ValueError(f"pair must be (qa, qb) or (qa, None), got {pair!r}")
+        qa = RideOps._dist_quantity(self, pair[0])
+        return qa, (-1 if pair[1] is None else RideOps._dist_quantity(self, pair[1]))
+
+    def xspec_create(self, box, pair, dx, wx, wy, twx, twy, c1x=0.0, c1y=0.0, detrend=False, every=1, start=0):
+        """Device planes for FluidSimulator.start_cross_spectra / cross_spectrum / pair_fft: box and tables as spec_create, pair as
+        xspec_pair, dx for the gradients.  64 bytes per cell of the box, 40 for one scalar.  Everything is checked (ValueError) before any
+        device call.  Single-context grids only (FsError on a slab); not allowed during a graph capture."""
+        box, tabs, c1x, c1y, every, start = RideOps._spec_checked(self, box, (wx, wy, twx, twy), c1x, c1y, every, start)
+        qa, qb = RideOps.xspec_pair(self, pair)
+        dx = float(dx)
+        if not (math.isfinite(dx) and dx > 0.0):
+            raise ValueError(f"dx must be finite and > 0, got {dx}")
+        RideOps._host_only(self, "xspec_create during a graph capture")
+        if self.nranks > 1:
+            raise _lib.FsError("cross-spectra need a single-GPU context: on slabs the transform along y crosses the ranks (not implemented)")
+        h = self._p_xspec_create(box, qa, qb, dx, *tabs, c1x, c1y, bool(detrend), every, start)
+        return self._adopt(h, XSpec(h, box, qa, qb, dx, detrend, every, start))
+
+    def xspec_launch(self, xs, v, p):
+        """The launches of one step: load the pair and transform along x, transpose, transform along y, split and accumulate, the tick - all
+        but the tick return at once unless this launch samples.  A limit_field v still owes stays deferred: the kernel limits the values
+        it reads.  Not a _run: no flush, no exchange, no ghost row (writes no field)."""
+        self._ride("xspec_launch", (xs._h, self._limit_of(v), v._h, p._h))
+
+    def xspec_read(self, xs, sums=True):
+        """-> (sums float64 (planes, Nx, Ny): Paa, Pbb, Cre, Cim over the samples (one scalar: Paa alone) - None with sums=False -, launches,
+        samples).  Not allowed during a graph capture."""
+        self._host_only("xspec_read during a graph capture: the planes are a download (read between captures / replays)")
+        planes, launches, samples = self._p_xspec_read(xs._h, xs.planes * xs.nx * xs.ny if sums else 0)
+        return (planes.reshape(xs.planes, xs.nx, xs.ny) if sums else None), int(launches), int(samples)
+
+    def xspec_plane(self, xs):
+        """-> Z' of the last sampling launch, complex128 (Nx, Ny) (zeros before the first).  Not allowed during a graph capture."""
+        self._host_only("xspec_plane during a graph capture")
+        return self._p_xspec_plane(xs._h, xs.nx * xs.ny).view(np.complex128).reshape(xs.nx, xs.ny)
+
+    def xspec_get(self, xs):
+        """-> (the accumulator planes float64 (planes, Nx, Ny), launches, samples), for checkpoints."""
+        self._host_only("xspec_get during a graph capture")
+        planes, launches, samples = self._p_xspec_get(xs._h, xs.planes * xs.nx * xs.ny)
+        return planes.reshape(xs.planes, xs.nx, xs.ny), int(launches), int(samples)
+
+    def xspec_set(self, xs, sums, launches, samples):
+        """Restore what xspec_get returned (resume)."""
+        self._host_only("xspec_set during a graph capture")
+        sums = np.ascontiguousarray(sums, np.float64)
+        if sums.shape != (xs.planes, xs.nx, xs.ny):
+            raise ValueError(f"expected accumulator planes of shape {(xs.planes, xs.nx, xs.ny)}, got {sums.shape}")
+        launches, samples = self._check_counters(launches, samples)
+        self._p_xspec_set(xs._h, sums, launches, samples)
+
+    def xspec_reset(self, xs):
+        """Accumulators and sample count to zero; the launch count runs on.  Not allowed during a graph capture."""
+        self._host_only("xspec_reset during a graph capture")
+        self._p_xspec_reset(xs._h)
+
+    def xspec_free(self, xs):
+        self._release(xs, self._p_xspec_free)
 
     # ---- flow maps (include/fs_hip.h fs_flowmap_*): a lattice of particles carried through the resident snapshots of a POD; csrc/fs_lcs.h ----
     def flowmap_create(self, box=None, refine=1):
@@ -1392,6 +1480,41 @@ class NativeRideOps:
     def _p_spec_free(self, h):
         if self._ctx is not None:
             _lib.call("fs_spec_free", self._ctx, h)
+
+    def _p_xspec_create(self, box, qa, qb, dx, wx, wy, twx, twy, c1x, c1y, detrend, every, start):
+        h = ctypes.c_void_p()
+        dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        _lib.call("fs_xspec_create", self._ctx, (ctypes.c_int * 4)(*box), qa, qb, dx, dp(wx), dp(wy), dp(twx), dp(twy), c1x, c1y, int(detrend),
+                  every, start, ctypes.byref(h))
+        return h
+
+    def _p_xspec_read(self, h, words):
+        planes = np.empty(words, np.float64)
+        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
+        _lib.call("fs_xspec_read", self._ctx, h, planes.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if words else None, ctypes.byref(launches),
+                  ctypes.byref(samples))
+        return planes, launches.value, samples.value
+
+    def _p_xspec_plane(self, h, cells):
+        out = np.empty(2 * cells, np.float64)
+        _lib.call("fs_xspec_plane", self._ctx, h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        return out
+
+    def _p_xspec_get(self, h, words):
+        planes = np.empty(words, np.float64)
+        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
+        _lib.call("fs_xspec_get", self._ctx, h, planes.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(launches), ctypes.byref(samples))
+        return planes, launches.value, samples.value
+
+    def _p_xspec_set(self, h, sums, launches, samples):
+        _lib.call("fs_xspec_set", self._ctx, h, sums.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), launches, samples)
+
+    def _p_xspec_reset(self, h):
+        _lib.call("fs_xspec_reset", self._ctx, h)
+
+    def _p_xspec_free(self, h):
+        if self._ctx is not None:
+            _lib.call("fs_xspec_free", self._ctx, h)
 
     def _p_flowmap_create(self, box, refine):
         h = ctypes.c_void_p()

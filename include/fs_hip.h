@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 25
+#define FS_ABI_VERSION 26
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -575,6 +575,35 @@ int fs_spec_get(fs_ctx *ctx, fs_spec *s, double *power, long long *launches, lon
 int fs_spec_set(fs_ctx *ctx, fs_spec *s, const double *power, long long launches, long long samples);
 int fs_spec_reset(fs_ctx *ctx, fs_spec *s);
 int fs_spec_free(fs_ctx *ctx, fs_spec *s);
+
+/* Cross-spectra of two flow quantities (new, ABI 26): the windowed 2-D FFT of the packed plane a + i b over a box of cells - a, b two of the
+ * seven quantities of fs_dist_spec (0 "u", 1 "w", 2 "p", 3 "speed", 4 "vorticity", 5 "q", 6 "swirl") -, split on the device into the transforms A
+ * and B of the two real fields, and the accumulated |A|^2, |B|^2 and A conj(B) of every bin, by launches that can be captured in a hipGraph
+ * (operation order and kernels: csrc/fs_xspec.h).  Box, tables, detrend, sampling rule, plane layout and refusals are those of fs_spec_*; all
+ * doubles, no atomics.  Single-GPU contexts: create returns FS_ERR_UNSUPPORTED on a slab context.
+ * create:  as fs_spec_create, and 0 <= qa <= 6, -1 <= qb <= 6 (-1: one scalar, the imaginary part of the packed plane is +0), dx finite and > 0
+ *          (the gradients).  u, w, p, speed contribute where mask != 1, vorticity, q, swirl where mask == 0; every other cell takes +0.
+ *          Device memory: 64 bytes per cell of the box (two work planes, FS_XSPEC_NPLANE accumulators); 40 with qb = -1 (one accumulator).
+ * launch:  five kernel launches, nothing else (capturable); all but the last return at once unless this launch samples.  limit > 0: v still
+ *          owes limit_field(limit).  Needs the mask.
+ * read:    synchronises; sums: the accumulator planes Paa, Pbb, Cre, Cim (C = A conj B), FS_XSPEC_NPLANE * Nx * Ny doubles - with qb = -1
+ *          Paa alone, Nx * Ny -, or NULL; launches, samples: may be NULL.  Resets nothing.
+ * plane:   the detrended packed plane Z' of the last sampling launch, 2 * Nx * Ny doubles (re, im interleaved); zeros before the first.
+ * get / set: the accumulators and the counters, for checkpoints; set: 0 <= samples <= launches.
+ * reset:   accumulators and sample count to zero; the launch count runs on.
+ * free:    as fs_mean_free.
+ * Everything but launch and free returns FS_ERR_STATE during graph capture / tape recording.                                             */
+#define FS_XSPEC_NPLANE 4
+typedef struct fs_xspec fs_xspec;
+int fs_xspec_create(fs_ctx *ctx, const int *box, int qa, int qb, double dx, const double *wx, const double *wy, const double *twx, const double *twy,
+                    double c1x, double c1y, int detrend, long long every, long long start, fs_xspec **out);
+int fs_xspec_launch(fs_ctx *ctx, fs_xspec *s, double limit, const fs_field *v, const fs_field *p);
+int fs_xspec_read(fs_ctx *ctx, fs_xspec *s, double *sums, long long *launches, long long *samples);
+int fs_xspec_plane(fs_ctx *ctx, fs_xspec *s, double *plane);
+int fs_xspec_get(fs_ctx *ctx, fs_xspec *s, double *sums, long long *launches, long long *samples);
+int fs_xspec_set(fs_ctx *ctx, fs_xspec *s, const double *sums, long long launches, long long samples);
+int fs_xspec_reset(fs_ctx *ctx, fs_xspec *s);
+int fs_xspec_free(fs_ctx *ctx, fs_xspec *s);
 
 /* Multigrid pressure correction (new, ABI 19): one W-cycle (two coarse visits per level) on a mask-aware hierarchy of coarse levels, for the
  * third pressure updater (fs/pressure_updater.py MultigridPressureUpdater; kernels and operation order: csrc/fs_mg.h).  Single-GPU contexts.
