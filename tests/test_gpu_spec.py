@@ -4,8 +4,9 @@ restatement (tests/spec_ref.py) fed with downloads of the same fields and the sa
 Part one, the transform: boxes on bc5 res 64 (grid 128 x 64) under a random velocity that is not zero inside the walls - the smallest box,
 16 x 8 and 8 x 16 (a transposition error shows), 64 x 32 at an odd offset over the slotted wall (wall cells take 0), the whole grid - and on
 grids made for them the rows of 1024, 2048 and 4096 points in both directions: a workgroup holds 4096 / N rows, the kernel has one form for
-every N, and 4096 is the row that fills the LDS planes on its own (there is no longer one to put beside it).  f32 and f64 fields, both
-windows, detrend on and off, a deferred limit_field.  Part two, the rider on bc1 res 32: eager steps against the NumPy loop over per-step
+every N, and 4096 is the row that fills the LDS planes on its own (there is no longer one to put beside it); and the rows of 512 and 256
+points (8 and 16 per workgroup) on grids of 512 x 256 and 256 x 512 - the whole grid, 32 workgroups and 16 x 8 transpose tiles, and a quarter
+of it at an odd offset.  f32 and f64 fields at every row length, both windows, detrend on and off, a deferred limit_field.  Part two, the rider on bc1 res 32: eager steps against the NumPy loop over per-step
 downloads, replayed graphs, a non-sampling launch, the checkpoint round trip, the unchanged trajectory, the refusals."""
 import ctypes
 import functools
@@ -21,6 +22,7 @@ pytestmark = pytest.mark.gpu
 
 EPS = np.finfo(np.float64).eps
 COMBOS = (("hann", True), ("hann", False), ("boxcar", True), ("boxcar", False))
+NP_DTYPE = {"f32": "float32", "f64": "float64"}
 
 
 @pytest.fixture(autouse=True)
@@ -83,14 +85,15 @@ def test_boxes_on_bc5_res64_equal_the_restatement(name, dtype, hip_lib):
         _close(sim)
 
 
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
 @pytest.mark.parametrize("grid,boxes", [((4096, 8), ((0, 0, 4096, 8), (1001, 0, 3049, 8), (5, 0, 1029, 8))),
                                         ((8, 4096), ((0, 0, 8, 4096), (0, 1001, 8, 3049), (0, 5, 8, 1029)))], ids=["4096x8", "8x4096"])
-def test_long_rows_in_both_directions(grid, boxes, hip_lib):
+def test_long_rows_in_both_directions(grid, boxes, dtype, hip_lib):
     """Rows of 4096 (one per workgroup: the full 64 KB of LDS), 2048 (two) and 1024 (four) points along x and along y."""
     from multigrid_cases import scene
-    sim, mask = _sim(scene(grid[0], grid[1], 0.1), 1.0 / max(grid), "f32")
+    sim, mask = _sim(scene(grid[0], grid[1], 0.1), 1.0 / max(grid), dtype)
     try:
-        v, _ = _load(sim, _velocity(mask.shape, "float32", seed=4))
+        v, _ = _load(sim, _velocity(mask.shape, NP_DTYPE[dtype], seed=4))
         assert (mask == 1).any()
         for box in boxes:
             _assert_box(sim, v, mask, box, combos=(("hann", True), ("boxcar", False)))
@@ -98,23 +101,64 @@ def test_long_rows_in_both_directions(grid, boxes, hip_lib):
         _close(sim)
 
 
+# rows of 512 and 256 points: 8 and 16 rows per workgroup, planes of 32 workgroups and 16 x 8 transpose tiles; and a quarter of each at an
+# odd offset (8 workgroups, rows of 256 and 128)
+MID_GRIDS = {"512x256": (512, 256), "256x512": (256, 512)}
+MID_BOXES = {("512x256", "whole grid"): (0, 0, 512, 256), ("512x256", "256x128 at an odd offset"): (129, 67, 385, 195),
+             ("256x512", "whole grid"): (0, 0, 256, 512), ("256x512", "128x256 at an odd offset"): (67, 129, 195, 385)}
+
+
+def _assert_walls_carry_values(mask, box, *fields):
+    walls = mask[box[0]:box[2], box[1]:box[3]] == 1
+    assert walls.any(), "no wall cell in the box"
+    for f in fields:
+        assert (f[box[0]:box[2], box[1]:box[3]][walls] != 0).any(), "no wall cell with a stored value in the box"
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+@pytest.mark.parametrize("grid,name", list(MID_BOXES), ids=[f"{g} {n}" for g, n in MID_BOXES])
+def test_rows_of_256_and_512(grid, name, dtype, hip_lib):
+    from multigrid_cases import scene
+    X, Y = MID_GRIDS[grid]
+    box = MID_BOXES[grid, name]
+    sim, mask = _sim(scene(X, Y, 0.1), 1.0 / max(X, Y), dtype)
+    try:
+        assert mask.shape == (X, Y) and 0 <= box[0] < box[2] <= X and 0 <= box[1] < box[3] <= Y
+        v, _ = _load(sim, _velocity(mask.shape, NP_DTYPE[dtype], seed=4))
+        _assert_walls_carry_values(mask, box, v)
+        _assert_box(sim, v, mask, box, combos=(("hann", True), ("boxcar", False)))
+    finally:
+        _close(sim)
+
+
+def _assert_fft2(sim, v, mask, box):
+    nx, ny = box[2] - box[0], box[3] - box[1]
+    wx, wy = _tabs(nx, ny, "hann")[:2]
+    z = (v[box[0]:box[2], box[1]:box[3], 0] + 1j * v[box[0]:box[2], box[1]:box[3], 1]) * wx[:, None] * wy[None, :]
+    z[mask[box[0]:box[2], box[1]:box[3]] == 1] = 0
+    want = np.fft.fft2(z)
+    got = sim.box_fft(box, window="hann", detrend=False)
+    err = np.linalg.norm(got - want) / np.linalg.norm(want)
+    print(box, "relative L2 error in eps:", err / EPS)
+    assert err <= 4 * EPS * np.log2(nx * ny), (box, err / EPS)
+
+
 def test_box_fft_agrees_with_numpy_fft2(hip_lib):
     """Against np.fft.fft2 of the downloaded, windowed field within 4 eps log2(Nx Ny) in relative L2 norm: the worst-case bound of a
-    radix-2 FFT with correctly rounded twiddles."""
+    radix-2 FFT with correctly rounded twiddles.  Boxes on bc5 res 64, and the whole of the 512 x 256 grid."""
+    from multigrid_cases import scene
     const, mask = _scene5()
     sim, mask = _sim((const, mask), 1.0 / 64, "f64")
     try:
         v, _ = _load(sim, _velocity(mask.shape, "float64"))
         for box in ((0, 0, 128, 64), (3, 5, 11, 13)):
-            nx, ny = box[2] - box[0], box[3] - box[1]
-            wx, wy = _tabs(nx, ny, "hann")[:2]
-            z = (v[box[0]:box[2], box[1]:box[3], 0] + 1j * v[box[0]:box[2], box[1]:box[3], 1]) * wx[:, None] * wy[None, :]
-            z[mask[box[0]:box[2], box[1]:box[3]] == 1] = 0
-            want = np.fft.fft2(z)
-            got = sim.box_fft(box, window="hann", detrend=False)
-            err = np.linalg.norm(got - want) / np.linalg.norm(want)
-            print(box, "relative L2 error in eps:", err / EPS)
-            assert err <= 4 * EPS * np.log2(nx * ny), (box, err / EPS)
+            _assert_fft2(sim, v, mask, box)
+    finally:
+        _close(sim)
+    sim, mask = _sim(scene(512, 256, 0.1), 1.0 / 512, "f64")
+    try:
+        v, _ = _load(sim, _velocity(mask.shape, "float64", seed=4))
+        _assert_fft2(sim, v, mask, (0, 0, 512, 256))
     finally:
         _close(sim)
 

@@ -4,7 +4,8 @@ between Paa + Pbb and the power of the packed plane.
 
 Part one, the planes: boxes on bc5 res 64 (grid 128 x 64) under a random velocity and pressure that are not zero inside the walls - the
 smallest box, 16 x 8 and 8 x 16, 64 x 32 at an odd offset over the slotted wall, the whole grid (the gradients clamp at its edges) - f32 and
-f64, five pairs that between them load every quantity, both windows; the mirror index at log2 N = 12 in each direction; a deferred
+f64, five pairs that between them load every quantity, both windows; the mirror index at log2 N = 12 in each direction, f32 and f64; rows
+of 512, 256 and 128 points on the grids 512 x 256 and 256 x 512 of tests/test_gpu_spec.py (32 and 8 workgroups), f32 and f64; a deferred
 limit_field.  Part two, the rider on bc1 res 32: eager steps against the NumPy loop, replayed graphs, a non-sampling launch, the checkpoint
 round trip, beside start_spectra, the unchanged trajectory, the refusals."""
 import ctypes
@@ -13,7 +14,7 @@ import functools
 import numpy as np
 import pytest
 from test_gpu_dist import _load, _sim
-from test_gpu_spec import BOXES_128x64, _make, _scene5, _tabs, _velocity
+from test_gpu_spec import BOXES_128x64, MID_BOXES, MID_GRIDS, NP_DTYPE, _assert_walls_carry_values, _make, _scene5, _tabs, _velocity
 from test_gpu_vortices import _close
 
 import spec_ref as S
@@ -103,16 +104,37 @@ def test_boxes_on_bc5_res64_equal_the_restatement(name, dtype, hip_lib):
         _close(sim)
 
 
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
 @pytest.mark.parametrize("grid", [(4096, 8), (8, 4096)], ids=["4096x8", "8x4096"])
-def test_mirror_index_on_the_longest_rows(grid, hip_lib):
+def test_mirror_index_on_the_longest_rows(grid, dtype, hip_lib):
     """The whole grid as the box: the mirror (N - a) mod N at log2 N = 12 along x and along y, and the gradient's clamped neighbours."""
     from multigrid_cases import scene
     dx = 1.0 / max(grid)
-    sim, mask = _sim(scene(grid[0], grid[1], 0.1), dx, "f32")
+    sim, mask = _sim(scene(grid[0], grid[1], 0.1), dx, dtype)
     try:
-        v, p = _load(sim, _velocity(mask.shape, "float32", seed=4), _pressure(mask.shape, "float32"))
+        v, p = _load(sim, _velocity(mask.shape, NP_DTYPE[dtype], seed=4), _pressure(mask.shape, NP_DTYPE[dtype]))
         assert (mask == 1).any()
         _assert_box(sim, v, p, mask, dx, (0, 0) + tuple(grid), ("vorticity", "u"), combos=(("hann", True),))
+    finally:
+        _close(sim)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+@pytest.mark.parametrize("grid,name", list(MID_BOXES), ids=[f"{g} {n}" for g, n in MID_BOXES])
+def test_rows_of_256_and_512(grid, name, dtype, hip_lib):
+    """The grids and boxes of tests/test_gpu_spec.py: rows of 512, 256 and 128 points, planes of 32 and of 8 workgroups; a pair that reads
+    the gradient and the pressure, and the pair that is box_fft."""
+    from multigrid_cases import scene
+    X, Y = MID_GRIDS[grid]
+    box = MID_BOXES[grid, name]
+    dx = 1.0 / max(X, Y)
+    sim, mask = _sim(scene(X, Y, 0.1), dx, dtype)
+    try:
+        assert mask.shape == (X, Y) and 0 <= box[0] < box[2] <= X and 0 <= box[1] < box[3] <= Y
+        v, p = _load(sim, _velocity(mask.shape, NP_DTYPE[dtype], seed=4), _pressure(mask.shape, NP_DTYPE[dtype]))
+        _assert_walls_carry_values(mask, box, v, p)
+        for pair in (("vorticity", "p"), ("u", "w")):
+            _assert_box(sim, v, p, mask, dx, box, pair)
     finally:
         _close(sim)
 
