@@ -1,6 +1,6 @@
 // fs_diag.hip - C-ABI entry points of what reads the flow without changing it: the flow diagnostics (fs_stats.h), the per-step history ring
 // (fs_history.h), the body surface loads (fs_loads.h), the time averages (fs_mean.h), the harmonic modes (fs_modes.h), the snapshot POD
-// (fs_pod.h), the flow maps through its snapshots (fs_lcs.h), the vortex identification (fs_vortex.h), the field distributions (fs_dist.h), the energy spectra (fs_spec.h) and the cross-spectra (fs_xspec.h).  Their objects live in the context's
+// (fs_pod.h), the flow maps through its snapshots (fs_lcs.h), the vortex identification (fs_vortex.h), the field distributions (fs_dist.h), the energy spectra (fs_spec.h), the cross-spectra (fs_xspec.h) and the scale-to-scale fluxes (fs_flux.h).  Their objects live in the context's
 // registry (fs_host.h: FS_OBJECT, FS_HANDLE, FS_NO_CAPTURE, object_free).
 #include "fs_launch.h"
 #include "fs_stats.h"
@@ -13,6 +13,7 @@
 #include "fs_dist.h"
 #include "fs_spec.h"
 #include "fs_xspec.h"
+#include "fs_flux.h"
 
 static_assert(fs::STATS_N == FS_FLOW_NSTAT, "fs_stats.h and include/fs_hip.h disagree on the slots");
 static_assert(fs::LOADS_REC == FS_LOADS_NREC && fs::LOADS_SUMS == FS_LOADS_NSUM, "fs_loads.h and include/fs_hip.h disagree on the record / the sums");
@@ -30,6 +31,8 @@ static_assert(fs::DIST_MAX_BINS == FS_DIST_MAX_BINS && fs::DIST_MAX_CHANNELS == 
               "fs_dist.h and include/fs_hip.h disagree");
 static_assert(fs::SPEC_MIN_N == FS_SPEC_MIN_N && fs::SPEC_MAX_N == FS_SPEC_MAX_N, "fs_spec.h and include/fs_hip.h disagree");
 static_assert(fs::XSPEC_PLANES == FS_XSPEC_NPLANE && fs::XSPEC_NQ == fs::DIST_NQ, "fs_xspec.h, fs_dist.h and include/fs_hip.h disagree");
+static_assert(fs::FLUX_NQ == FS_FLUX_NQ && fs::FLUX_SUMS == FS_FLUX_NSUM && fs::FLUX_MAX_WIDTHS == FS_FLUX_MAX_WIDTHS && fs::FLUX_MAX_R == FS_FLUX_MAX_R,
+              "fs_flux.h and include/fs_hip.h disagree");
 
 FS_OBJECT(fs_history, OBJ_HISTORY, "history", "history from another context or freed");
 FS_OBJECT(fs_loads, OBJ_LOADS, "loads", "loads from another context or freed");
@@ -40,6 +43,7 @@ FS_OBJECT(fs_vortex, OBJ_VORTEX, "vortex", "vortex tracker from another context 
 FS_OBJECT(fs_dist, OBJ_DIST, "distributions", "distributions from another context or freed");
 FS_OBJECT(fs_spec, OBJ_SPEC, "spectrum", "spectrum from another context or freed");
 FS_OBJECT(fs_xspec, OBJ_XSPEC, "cross-spectrum", "cross-spectrum from another context or freed");
+FS_OBJECT(fs_flux, OBJ_FLUX, "scale fluxes", "scale fluxes from another context or freed");
 FS_OBJECT(fs_flowmap, OBJ_FLOWMAP, "flow map", "flow map from another context or freed");
 
 using namespace fs;
@@ -1507,6 +1511,177 @@ int fs_xspec_reset(fs_ctx *ctx, fs_xspec *s)
 }
 
 int fs_xspec_free(fs_ctx *ctx, fs_xspec *s) { return object_free(ctx, s); }
+
+// ---- scale-to-scale fluxes (fs_flux.h) -------------------------------------------------------------------------------------------------------
+// the valid cells of half-width r inside the box, half-open (empty: x0 >= x1 or y0 >= y1)
+static void flux_valid(const fs_ctx *ctx, const int *box, int r, int *out)
+{
+    out[0] = std::max(box[0], r + 1); out[1] = std::max(box[1], r + 1);
+    out[2] = std::min(box[2], ctx->X - 1 - r); out[3] = std::min(box[3], ctx->Y - 1 - r);
+}
+
+int fs_flux_create(fs_ctx *ctx, const int *box, int nr, const int *half_widths, double dx, long long every, long long start, fs_flux **out)
+{
+    FS_REQUIRE(ctx && box && half_widths && out, "null argument");
+    FS_REQUIRE(0 <= box[0] && box[0] < box[2] && box[2] <= ctx->X && 0 <= box[1] && box[1] < box[3] && box[3] <= ctx->Y,
+               "flux box must satisfy 0 <= x0 < x1 <= X and 0 <= y0 < y1 <= Y");
+    FS_REQUIRE(1 <= nr && nr <= FLUX_MAX_WIDTHS, "the number of half-widths must be 1 .. FS_FLUX_MAX_WIDTHS");
+    for (int k = 0; k < nr; ++k) {
+        FS_REQUIRE(1 <= half_widths[k] && half_widths[k] <= FLUX_MAX_R, "a half-width must be 1 .. FS_FLUX_MAX_R");
+        FS_REQUIRE(k == 0 || half_widths[k] > half_widths[k - 1], "the half-widths must be strictly increasing");
+        int val[4];
+        flux_valid(ctx, box, half_widths[k], val);
+        FS_REQUIRE(val[0] < val[2] && val[1] < val[3], "a half-width has no valid cell inside the box (valid: r + 1 <= i <= X - 2 - r, r + 1 <= j <= Y - 2 - r)");
+    }
+    FS_REQUIRE(std::isfinite(dx) && dx > 0.0, "dx must be finite and > 0");
+    FS_EVERY_START(every, start);
+    FS_NO_CAPTURE(fs_flux, "create");
+    if (ctx->halo != 0 || ctx->nyl != ctx->Y) {
+        set_error("scale fluxes need a single-GPU context: on a slab the filter along y crosses the ranks (not implemented)");
+        return FS_ERR_UNSUPPORTED;
+    }
+    FS_HIP(hipSetDevice(ctx->device));
+    auto s = std::make_unique<fs_flux>();
+    for (int k = 0; k < 4; ++k) s->box[k] = box[k];
+    s->nx = box[2] - box[0]; s->ny = box[3] - box[1]; s->nr = nr; s->dx = dx; s->every = every; s->start = start;
+    for (int k = 0; k < nr; ++k) s->r[k] = half_widths[k];
+    const int d = half_widths[nr - 1] + 1;
+    s->dx0 = std::max(0, box[0] - d); s->dy0 = std::max(0, box[1] - d);
+    s->DW = std::min(ctx->X, box[2] + d) - s->dx0; s->DH = std::min(ctx->Y, box[3] + d) - s->dy0;
+    const size_t work = (size_t)FLUX_NQ * s->DW * s->DH * sizeof(double), acc = (size_t)nr * FLUX_SUMS * s->nx * s->ny * sizeof(double);
+    hipError_t e = s->d_state.alloc((SPEC_STATE + 1) * sizeof(long long));
+    if (e == hipSuccess) e = s->d_base.alloc(work);
+    if (e == hipSuccess) e = s->d_rows.alloc(work);
+    if (e == hipSuccess) e = s->d_filt.alloc(work);
+    if (e == hipSuccess) e = s->d_acc.alloc(acc);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_state, 0, (SPEC_STATE + 1) * sizeof(long long), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_base, 0, work, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_rows, 0, work, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_filt, 0, work, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_acc, 0, acc, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return hip_fail(e, "fs_flux_create", __FILE__, __LINE__);
+    *out = adopt(ctx, std::move(s));
+    return FS_OK;
+}
+
+// passes 2 and 3 of half-width r: base -> R -> F
+static int flux_filter(fs_ctx *ctx, const fs_flux *s, const SpecWhen when, int r)
+{
+    const int DW = s->DW, DH = s->DH, n = 2 * r + 1;
+    const double inv = 1.0 / (double)(n * n);
+    const double *base = s->d_base;
+    double *R = s->d_rows, *F = s->d_filt;
+    const int rx = (DW + FLUX_STRIP - 1) / FLUX_STRIP, cx = (DW + FLUX_COL_LANES - 1) / FLUX_COL_LANES;
+    const dim3 rows(rx, flux_groups_y(rx, (DH + FLUX_ROW_WAVES - 1) / FLUX_ROW_WAVES), FLUX_NQ);
+    const dim3 cols(cx, flux_groups_y(cx, (DH + FLUX_COL_V - 1) / FLUX_COL_V), FLUX_NQ);
+    int rc = launch(ctx, "flux_rows", [=] { klaunch(k_flux_rows, rows, dim3(64 * FLUX_ROW_WAVES), ctx->stream, when, DW, DH, r, base, R); });
+    if (rc) return rc;
+    return launch(ctx, "flux_cols", [=] {
+        klaunch(k_flux_cols, cols, dim3(FLUX_COL_LANES), ctx->stream, when, DW, DH, r, inv, (const double *)R, F);
+    });
+}
+
+int fs_flux_launch(fs_ctx *ctx, fs_flux *s, double limit, const fs_field *v)
+{
+    FS_REQUIRE(ctx && s, "null argument");
+    FS_HANDLE(s);
+    FS_FIELD(v, 2);
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    // everything the launches need is in `s` and the field: no allocation, copy or synchronisation here (the closures are captured / taped)
+    const FluxGeom f{s->dx0, s->dy0, s->DW, s->DH, s->box[0], s->box[1], s->nx, s->ny};
+    const double two_dx = 2.0 * s->dx;
+    const long long every = s->every, start = s->start;
+    long long *state = s->d_state;
+    const SpecWhen when{state, start, every};
+    const size_t dcells = (size_t)s->DW * s->DH, cells = (size_t)s->nx * s->ny;
+    const int X = ctx->X, Y = ctx->Y;
+    double *base = s->d_base, *F = s->d_filt;
+    int rc = by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
+        return launch(ctx, "flux_base", [=] {
+            klaunch(k_flux_base<T>, dim3(flux_groups(dcells)), dim3(256), ctx->stream, ctx->grid(), when, f, limit, two_dx, (const T *)v->d, base);
+        });
+    });
+    if (rc) return rc;
+    for (int k = 0; k < s->nr; ++k) {
+        const int r = s->r[k];
+        if ((rc = flux_filter(ctx, s, when, r))) return rc;
+        double *acc = s->d_acc + (size_t)k * FLUX_SUMS * cells;
+        rc = launch(ctx, "flux_accumulate", [=] {
+            klaunch(k_flux_accumulate, dim3(flux_groups(cells)), dim3(256), ctx->stream, when, f, X, Y, r, two_dx, (const double *)F, acc);
+        });
+        if (rc) return rc;
+    }
+    return launch(ctx, "spec_tick", [=] { klaunch(k_spec_tick, dim3(1), dim3(64), ctx->stream, start, every, state); });
+}
+
+int fs_flux_read(fs_ctx *ctx, fs_flux *s, double *sums, long long *launches, long long *samples)
+{
+    FS_REQUIRE(ctx && s, "null argument");
+    FS_HANDLE(s);
+    FS_NO_CAPTURE(fs_flux, "read");
+    long long st[SPEC_STATE];
+    if (int rc = read_counters(ctx, s->d_state, st)) return rc;
+    if (sums) {
+        FS_HIP(hipMemcpyAsync(sums, s->d_acc, (size_t)s->nr * FLUX_SUMS * s->nx * s->ny * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        FS_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    if (launches) *launches = st[0];
+    if (samples) *samples = st[1];
+    return FS_OK;
+}
+
+int fs_flux_filtered(fs_ctx *ctx, fs_flux *s, int width, double *planes)
+{
+    FS_REQUIRE(ctx && s && planes, "null argument");
+    FS_HANDLE(s);
+    FS_REQUIRE(0 <= width && width < s->nr, "width must be an index into the object's half-widths");
+    FS_NO_CAPTURE(fs_flux, "filtered");
+    FS_HIP(hipSetDevice(ctx->device));
+    const SpecWhen always{s->d_state + SPEC_STATE, 0, 1};      // (a word that stays 0: samples_at(0, 0, 1))
+    if (int rc = flux_filter(ctx, s, always, s->r[width])) return rc;
+    const size_t plane = (size_t)s->DW * s->DH, cells = (size_t)s->nx * s->ny;
+    const double *F = s->d_filt + (size_t)(s->box[1] - s->dy0) * s->DW + (s->box[0] - s->dx0);
+    for (int k = 0; k < FLUX_NQ; ++k)
+        FS_HIP(hipMemcpy2DAsync(planes + k * cells, s->nx * sizeof(double), F + k * plane, s->DW * sizeof(double), s->nx * sizeof(double), s->ny,
+                                hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+int fs_flux_get(fs_ctx *ctx, fs_flux *s, double *sums, long long *launches, long long *samples)
+{
+    FS_REQUIRE(ctx && s && sums && launches && samples, "null argument");
+    return fs_flux_read(ctx, s, sums, launches, samples);
+}
+
+int fs_flux_set(fs_ctx *ctx, fs_flux *s, const double *sums, long long launches, long long samples)
+{
+    FS_REQUIRE(ctx && s && sums, "null argument");
+    FS_HANDLE(s);
+    FS_COUNTERS(launches, samples);
+    FS_NO_CAPTURE(fs_flux, "set");
+    FS_HIP(hipSetDevice(ctx->device));
+    const long long st[SPEC_STATE] = {launches, samples};
+    FS_HIP(hipMemcpyAsync(s->d_acc, sums, (size_t)s->nr * FLUX_SUMS * s->nx * s->ny * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipMemcpyAsync(s->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
+    return FS_OK;
+}
+
+int fs_flux_reset(fs_ctx *ctx, fs_flux *s)
+{
+    FS_REQUIRE(ctx && s, "null argument");
+    FS_HANDLE(s);
+    FS_NO_CAPTURE(fs_flux, "reset");
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemsetAsync(s->d_acc, 0, (size_t)s->nr * FLUX_SUMS * s->nx * s->ny * sizeof(double), ctx->stream));
+    FS_HIP(hipMemsetAsync(s->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
+    return FS_OK;
+}
+
+int fs_flux_free(fs_ctx *ctx, fs_flux *s) { return object_free(ctx, s); }
 
 // ---- flow maps through the resident snapshots (fs_lcs.h) ----------------------------------------------------------------------------------
 

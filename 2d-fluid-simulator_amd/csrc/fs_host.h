@@ -307,6 +307,20 @@ struct fs_xspec {
     fs::DevBuf<long long> d_state;   // [SPEC_STATE]
 };
 
+// scale-to-scale fluxes (fs_flux_*, fs_flux.h): the box, the region D of the work planes, the half-widths, the three sets of eight work planes
+// and the accumulators
+struct fs_flux {
+    int box[4] = {0, 0, 0, 0};      // x0, y0, x1, y1 (cells)
+    int nx = 0, ny = 0;             // the box's sides
+    int dx0 = 0, dy0 = 0, DW = 0, DH = 0;      // D: the box dilated by r_max + 1, clipped to the grid
+    int nr = 0, r[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // the half-widths, increasing (FLUX_MAX_WIDTHS)
+    double dx = 0.0;
+    long long every = 1, start = 0;
+    fs::DevBuf<double> d_base, d_rows, d_filt;      // [FLUX_NQ][DW * DH] each: q, R and F of the last half-width that ran
+    fs::DevBuf<double> d_acc;        // [nr][FLUX_SUMS][nx * ny]: PI, ZF, K, each [b][a]
+    fs::DevBuf<long long> d_state;   // [SPEC_STATE + 1]: launches, samples, and a zero (the `when` of fs_flux_filtered)
+};
+
 namespace fs { struct LoadFace; }      // fs_loads.h (included by fs_diag.hip alone)
 // body surface loads (fs_loads_*, fs_loads.h): the face list of this context's owned rows, the per-face sums, the ring and the device counters
 struct fs_loads {
@@ -348,7 +362,7 @@ struct fs_tracer {
 namespace fs {
 
 // ---- the objects behind the other handles: one registry (fs_ctx::objects, fs_objects.h), one guard, one no-capture check, one free -------------
-enum ObjKind { OBJ_HISTORY, OBJ_LOADS, OBJ_MEAN, OBJ_MODES, OBJ_POD, OBJ_VORTEX, OBJ_FLOWMAP, OBJ_TRACER, OBJ_MG, OBJ_DIST, OBJ_SPEC, OBJ_XSPEC };
+enum ObjKind { OBJ_HISTORY, OBJ_LOADS, OBJ_MEAN, OBJ_MODES, OBJ_POD, OBJ_VORTEX, OBJ_FLOWMAP, OBJ_TRACER, OBJ_MG, OBJ_DIST, OBJ_SPEC, OBJ_XSPEC, OBJ_FLUX };
 // kind, noun and stale-handle text of an object type: FS_OBJECT(type, kind, noun, text), once, in the unit that implements the type
 template <typename T> struct ObjInfo;
 #define FS_OBJECT(T, KIND, NOUN, STALE) \

@@ -19,6 +19,7 @@ from .modes import Modes, fit as fit_modes, gram_matrix, phasor_steps, reconstru
 from .pod import Pod
 from . import dist as _dist
 from . import spectra as _spectra
+from . import fluxes as _fluxes
 from .vortices import VELOCITY_LIMIT, Vortices, assemble, omega_exponent
 from .pressure_updater import JacobiPressureUpdater, MultigridPressureUpdater, RedBlackSorPressureUpdater
 from .solver import CipMacSolver, DyeCipMacSolver, DyeMacSolver, MacSolver
@@ -100,6 +101,7 @@ class FluidSimulator:
         self._distr = None         # fs.dist.Distributions while start_distributions() is on
         self._spectrar = None      # fs.spectra.Spectra while start_spectra() is on
         self._xspectrar = None     # fs.spectra.CrossSpectra while start_cross_spectra() is on
+        self._fluxr = None         # fs.fluxes.ScaleFluxes while start_scale_fluxes() is on
         self._tracers = None       # fs.tracers.Tracers while seed_tracers() is on
         self._tracker = None       # fs.loads.Tracker while track_body() is on
         self._last_tracker = None  # ... and after stop_body(): what body_loads() / body_surface() still return
@@ -109,8 +111,8 @@ class FluidSimulator:
 
     def _riders(self):
         """The attached riders (fs.riders.Rider) in their fixed order - history, averages, modes, pod, distributions, spectra, cross-spectra,
-        loads, tracers, vortices: the order of their launches behind the solver step and of their tokens in _signature()."""
-        return [r for r in (self._recorder, self._averager, self._moder, self._podr, self._distr, self._spectrar, self._xspectrar, self._tracker,
+        scale fluxes, loads, tracers, vortices: the order of their launches behind the solver step and of their tokens in _signature()."""
+        return [r for r in (self._recorder, self._averager, self._moder, self._podr, self._distr, self._spectrar, self._xspectrar, self._fluxr, self._tracker,
                             self._tracers, self._vortexr) if r is not None]
 
     def _capturing(self):
@@ -1141,6 +1143,87 @@ class FluidSimulator:
         start_cross_spectra), indexed like np.fft.fft2; fs.spectra.split gives the transforms of a and b.  For ("u", "w") it is box_fft(),
         bit for bit.  As cross_spectrum(): temporary, eager, changes nothing."""
         return self._cross_once("pair_fft", box, pair, window, detrend, self._dev.xspec_plane)[0]
+
+    # -- scale-to-scale fluxes (new): box filters of the velocity and the vorticity on the device, PI, ZF and K of every cell accumulated -----
+    def _grid_shape(self):
+        return (self._dev.nx, self._dev.ny)
+
+    def start_scale_fluxes(self, box, half_widths, every=1, start_step=0):
+        """From the next step on, accumulate the scale-to-scale fluxes over `box` on the device (csrc/fs_flux.h): after every step k
+        (counted from here) with k > start_step and (k - start_step) % every == 0 the velocity and the vorticity are filtered with a box
+        of (2 r + 1)^2 cells for every half-width r, and per cell of the box and half-width the energy flux PI = -tau_ij S_ij towards the
+        scales below (2 r + 1) dx (tau the sub-filter stress, S the filtered rate of strain), the enstrophy flux ZF and the sub-filter
+        energy K are added to three planes.  box = (x0, y0, x1, y1) in global cells, half-open, inside the grid, any sides; half_widths: 1
+        to 8 integers in 1 .. 64, strictly increasing (ValueError otherwise, before any device call).  The filter reads outside the box,
+        never outside the grid: a cell is valid for r when it keeps r + 1 cells from every edge of the grid, the others stay zero, and a
+        half-width without a valid cell in the box is refused.  Solid cells count as fluid at rest.  The launches are part of the step:
+        they are captured into the replayed graphs, decide on the device whether they sample, and run() is not cut into chunks by them.
+        A plane is a pure function of the fields: identical between eager steps, replayed graphs and resumed runs.  Device memory: 192
+        bytes per cell of the box dilated by r_max + 1 and 24 per cell of the box and half-width.  Changes no field and no trajectory.
+        scale_fluxes() returns the result.  Raises while scale fluxes are attached already and during a graph capture; single-GPU
+        contexts only (FsError on slabs)."""
+        dev = self._dev
+        self._not_capturing("start_scale_fluxes")
+        self._make_way("_fluxr", "scale fluxes are attached already: stop_scale_fluxes() first (or reset_scale_fluxes())")
+        every, start_step = self._cadence(every, start_step)
+        self._fluxr = _fluxes.ScaleFluxes(dev, dev.flux_create(box, half_widths, self._solver.dx, every, start_step), self._grid_shape())
+
+    def _scale_fluxes(self):
+        if self._fluxr is None:
+            raise RuntimeError("no scale fluxes: call start_scale_fluxes() first")
+        return self._fluxr
+
+    def scale_fluxes(self):
+        """The fluxes so far: {"half_widths"; "widths": (2 r + 1) dx; "samples", "sample_steps", "box"; "valid": per half-width the
+        rectangle (x0, y0, x1, y1) of valid cells inside the box; "pi", "zf", "k": float64 (n_r, Nx, Ny), the means over the samples
+        (zero outside the valid rectangle); "sums": the device's planes (n_r, 3, Nx, Ny) as accumulated; "mean_pi", "mean_zf", "mean_k":
+        per half-width the mean over the COMMON valid rectangle - that of the largest half-width -, so that the widths are compared over
+        the same cells; "mean_own": {"pi", "zf", "k"}, the same means over each width's own rectangle}.  PI > 0: energy goes to the
+        smaller scales.  A download of the planes; not allowed during a graph capture."""
+        self._not_capturing("scale_fluxes")
+        return self._scale_fluxes().data()
+
+    def reset_scale_fluxes(self):
+        """Planes and sample count back to zero; the step count and the phase of `every` / `start_step` run on."""
+        self._not_capturing("reset_scale_fluxes")
+        self._scale_fluxes().reset()
+
+    def stop_scale_fluxes(self):
+        """Detach the scale fluxes and free their device memory; the cached graphs that hold their launches are freed first.  Nothing is
+        kept on the host: call scale_fluxes() before.  Inside a graph capture the device memory is released when the capture ends."""
+        self._detach(self, "_fluxr", "stop_scale_fluxes")
+
+    def _flux_once(self, name, box, half_widths, read):
+        dev = self._dev
+        self._not_capturing(name)
+        fx = dev.flux_create(box, half_widths, self._solver.dx, 1, 0)
+        try:
+            saved, dev._oplog = getattr(dev, "_oplog", None), None      # (never part of a logged period)
+            try:
+                dev.flux_launch(fx, self._solver.get_fields()[0])
+            finally:
+                dev._oplog = saved
+            return read(fx), fx
+        finally:
+            dev.flux_free(fx)
+
+    def scale_flux(self, box, half_widths):
+        """The fluxes of the fields as they are now: the dict scale_fluxes() returns, with "samples" 1 and "sample_steps" [0] (the call
+        counts no steps).  One temporary object, one eager launch, a read and a free: changes no field, no graph and no attached rider,
+        and leaves a deferred limit_field deferred.  Not allowed during a graph capture."""
+        (sums, _, samples), fx = self._flux_once("scale_flux", box, half_widths, self._dev.flux_read)
+        return _fluxes.flux_result(sums, samples, np.zeros(samples, np.int64), fx.box, fx.half_widths, fx.dx, self._grid_shape())
+
+    def filtered_fields(self, box, half_width):
+        """The stage before the fluxes: {"u", "w", "om", "uu", "uw", "ww", "uom", "wom"}, float64 (Nx, Ny) each - the box filter of
+        half-width `half_width` of u, w, the vorticity and their products over the box as the device computes it (zero where the window
+        leaves the grid) - and "defined": the rectangle where it does not.  As scale_flux(): temporary, eager, changes nothing."""
+        half_width = int(half_width) if isinstance(half_width, (int, np.integer)) and not isinstance(half_width, bool) else half_width
+        planes, fx = self._flux_once("filtered_fields", box, (half_width,), lambda fx: self._dev.flux_filtered(fx, half_width))
+        out = dict(zip(_fluxes.FILTERED, planes))
+        X, Y = self._grid_shape()
+        out["defined"] = (max(fx.box[0], half_width), max(fx.box[1], half_width), min(fx.box[2], X - half_width), min(fx.box[3], Y - half_width))
+        return out
 
     # -- flow maps and FTLE fields (new): a lattice of particles carried through the POD's resident snapshots on the device --------------
     def flow_map(self, direction="backward", refine=1, box=None, substeps=1, first=None, last=None):

@@ -1,5 +1,5 @@
 """Device side of what rides the step and of the diagnostics (new; the reference has none): flow statistics, the per-step history, the
-body surface loads, the time averages, the harmonic modes, the snapshot POD, the flow maps through its snapshots, the field distributions, the energy spectra and the tracer particles.  Two mixins: RideOps is the
+body surface loads, the time averages, the harmonic modes, the snapshot POD, the flow maps through its snapshots, the field distributions, the energy spectra, the cross-spectra, the scale-to-scale fluxes and the tracer particles.  Two mixins: RideOps is the
 backend-agnostic host logic fs.runtime.DeviceBase inherits (slab partition, combination over ranks, argument checks, the op log of a logged period), NativeRideOps the `_p_*` primitives
 fs.runtime.Device binds to libfs_hip.so; the stand-in devices of the CPU tests override those.  fs.runtime re-exports every name here."""
 import collections
@@ -114,6 +114,16 @@ class XSpec(_Handle):
         self.planes = RideOps.XSPEC_NPLANE if qb >= 0 else 1
 
 
+class Flux(_Handle):
+    """Device planes of the scale-to-scale fluxes (DeviceBase.flux_create): handle, the cell box, its sides (nx, ny), the half-widths, dx,
+    every, start."""
+
+    def __init__(self, h, box, half_widths, dx, every, start):
+        super().__init__(h)
+        self.box, self.half_widths, self.dx, self.every, self.start = tuple(box), tuple(half_widths), dx, every, start
+        self.nx, self.ny = box[2] - box[0], box[3] - box[1]
+
+
 class FlowMap(_Handle):
     """A device lattice of flow-map nodes (DeviceBase.flowmap_create): handle, cell box, refine, and the lattice (nx, ny)."""
 
@@ -141,7 +151,7 @@ class History(_Handle):
 
 
 class RideOps:
-    """flow_stats and the history_* / loads_* / mean_* / modes_* / pod_* / flowmap_* / dist_* / spec_* / xspec_* / tracer_* calls of DeviceBase."""
+    """flow_stats and the history_* / loads_* / mean_* / modes_* / pod_* / flowmap_* / dist_* / spec_* / xspec_* / flux_* / tracer_* calls of DeviceBase."""
 
     # (The tracer calls reach these through the class - RideOps._host_only(self, ...) - as they always reached _tracer_host_call: the CPU
     #  tests check their refusals on objects that are no devices.)
@@ -957,6 +967,114 @@ class RideOps:
     def xspec_free(self, xs):
         self._release(xs, self._p_xspec_free)
 
+    # ---- scale-to-scale fluxes (include/fs_hip.h fs_flux_*): box filters of u, w and the vorticity, the sub-filter stresses, accumulated
+    #      PI, ZF and K per cell of a box; csrc/fs_flux.h ----
+    FLUX_NQ, FLUX_NSUM, FLUX_MAX_WIDTHS, FLUX_MAX_R = 8, 3, 8, 64
+
+    def flux_box(self, box):
+        """(x0, y0, x1, y1) in global cells, half-open, inside the grid -> the tuple of ints (ValueError)."""
+        try:
+            box = tuple(int(b) for b in box)
+        except TypeError:
+            raise ValueError(f"box must be (x0, y0, x1, y1), got {box!r}") from None
+        if len(box) != 4 or not (0 <= box[0] < box[2] <= self.nx and 0 <= box[1] < box[3] <= self.ny):
+            raise ValueError(f"box must be (x0, y0, x1, y1) with 0 <= x0 < x1 <= {self.nx} and 0 <= y0 < y1 <= {self.ny}, got {box}")
+        return box
+
+    def flux_valid(self, box, r):
+        """The valid cells of half-width r inside the box, (x0, y0, x1, y1) half-open: r + 1 <= i <= X - 2 - r, r + 1 <= j <= Y - 2 - r."""
+        return (max(box[0], r + 1), max(box[1], r + 1), min(box[2], self.nx - 1 - r), min(box[3], self.ny - 1 - r))
+
+    def flux_half_widths(self, box, half_widths):
+        """1 .. FLUX_MAX_WIDTHS ints in 1 .. FLUX_MAX_R, strictly increasing, each with a valid cell inside the box -> the tuple (ValueError)."""
+        if isinstance(half_widths, (int, np.integer)):
+            half_widths = (half_widths,)
+        try:
+            hw = tuple(half_widths)
+        except TypeError:
+            raise ValueError(f"half_widths must be a sequence of integers, got {half_widths!r}") from None
+        if not 1 <= len(hw) <= RideOps.FLUX_MAX_WIDTHS:
+            raise ValueError(f"half_widths must hold 1 .. {RideOps.FLUX_MAX_WIDTHS} half-widths, got {len(hw)}")
+        for r in hw:
+            if not isinstance(r, (int, np.integer)) or isinstance(r, bool) or not 1 <= r <= RideOps.FLUX_MAX_R:
+                raise ValueError(f"a half-width must be an integer in 1 .. {RideOps.FLUX_MAX_R}, got {r!r}")
+        hw = tuple(int(r) for r in hw)
+        if any(b <= a for a, b in zip(hw, hw[1:])):
+            raise ValueError(f"half_widths must be strictly increasing, got {hw}")
+        for r in hw:
+            v = RideOps.flux_valid(self, box, r)
+            if v[0] >= v[2] or v[1] >= v[3]:
+                raise ValueError(f"half-width {r} has no valid cell inside the box {box}: a valid cell keeps {r} + 1 cells from every edge of "
+                                 f"the {self.nx} x {self.ny} grid")
+        return hw
+
+    def flux_create(self, box, half_widths, dx, every=1, start=0):
+        """Device planes for FluidSimulator.start_scale_fluxes / scale_flux / filtered_fields.  192 bytes per cell of the box dilated by
+        r_max + 1 (clipped to the grid) and 24 per cell of the box and half-width.  Everything is checked (ValueError) before any device
+        call.  Single-context grids only (FsError on a slab); not allowed during a graph capture."""
+        box = RideOps.flux_box(self, box)
+        hw = RideOps.flux_half_widths(self, box, half_widths)
+        dx = float(dx)
+        if not (math.isfinite(dx) and dx > 0.0):
+            raise ValueError(f"dx must be finite and > 0, got {dx}")
+        every, start = RideOps._check_cadence(every, start)
+        RideOps._host_only(self, "flux_create during a graph capture")
+        if self.nranks > 1:
+            raise _lib.FsError("scale fluxes need a single-GPU context: on slabs the filter along y crosses the ranks (not implemented)")
+        h = self._p_flux_create(box, hw, dx, every, start)
+        return self._adopt(h, Flux(h, box, hw, dx, every, start))
+
+    def flux_launch(self, fx, v):
+        """The launches of one step: the base planes, per half-width the row sums, the column sums and the stencil with its three sums, the
+        tick - all but the tick return at once unless this launch samples.  A limit_field v still owes stays deferred: the kernel limits
+        the values it reads.  Not a _run: no flush, no exchange, no ghost row (writes no field)."""
+        self._ride("flux_launch", (fx._h, self._limit_of(v), v._h))
+
+    def _flux_sums(self, fx, flat):
+        nr = len(fx.half_widths)
+        return np.ascontiguousarray(flat.reshape(nr, RideOps.FLUX_NSUM, fx.ny, fx.nx).transpose(0, 1, 3, 2))
+
+    def flux_read(self, fx, sums=True):
+        """-> (sums float64 (n_r, 3, Nx, Ny): PI, ZF, K over the samples per half-width - None with sums=False -, launches, samples).  Not
+        allowed during a graph capture."""
+        self._host_only("flux_read during a graph capture: the planes are a download (read between captures / replays)")
+        words = len(fx.half_widths) * RideOps.FLUX_NSUM * fx.nx * fx.ny
+        flat, launches, samples = self._p_flux_read(fx._h, words if sums else 0)
+        return (RideOps._flux_sums(self, fx, flat) if sums else None), int(launches), int(samples)
+
+    def flux_filtered(self, fx, half_width):
+        """-> the eight filtered planes of `half_width` (one of the object's) over the box from the last sampling launch, float64
+        (8, Nx, Ny); +0 where the window leaves the grid, zeros before the first sample.  Not allowed during a graph capture."""
+        self._host_only("flux_filtered during a graph capture")
+        if half_width not in fx.half_widths:
+            raise ValueError(f"half_width must be one of {fx.half_widths}, got {half_width!r}")
+        flat = self._p_flux_filtered(fx._h, fx.half_widths.index(half_width), RideOps.FLUX_NQ * fx.nx * fx.ny)
+        return np.ascontiguousarray(flat.reshape(RideOps.FLUX_NQ, fx.ny, fx.nx).transpose(0, 2, 1))
+
+    def flux_get(self, fx):
+        """-> (the sums float64 (n_r, 3, Nx, Ny), launches, samples), for checkpoints."""
+        self._host_only("flux_get during a graph capture")
+        flat, launches, samples = self._p_flux_get(fx._h, len(fx.half_widths) * RideOps.FLUX_NSUM * fx.nx * fx.ny)
+        return RideOps._flux_sums(self, fx, flat), int(launches), int(samples)
+
+    def flux_set(self, fx, sums, launches, samples):
+        """Restore what flux_get returned (resume)."""
+        self._host_only("flux_set during a graph capture")
+        sums = np.asarray(sums, np.float64)
+        shape = (len(fx.half_widths), RideOps.FLUX_NSUM, fx.nx, fx.ny)
+        if sums.shape != shape:
+            raise ValueError(f"expected sums of shape {shape}, got {sums.shape}")
+        launches, samples = self._check_counters(launches, samples)
+        self._p_flux_set(fx._h, np.ascontiguousarray(sums.transpose(0, 1, 3, 2)).ravel(), launches, samples)
+
+    def flux_reset(self, fx):
+        """Sums and sample count to zero; the launch count runs on.  Not allowed during a graph capture."""
+        self._host_only("flux_reset during a graph capture")
+        self._p_flux_reset(fx._h)
+
+    def flux_free(self, fx):
+        self._release(fx, self._p_flux_free)
+
     # ---- flow maps (include/fs_hip.h fs_flowmap_*): a lattice of particles carried through the resident snapshots of a POD; csrc/fs_lcs.h ----
     def flowmap_create(self, box=None, refine=1):
         """A device lattice for FluidSimulator.flow_map: refine x refine nodes per cell of the cell box (x0, y0, x1, y1) (None: the whole
@@ -1515,6 +1633,40 @@ class NativeRideOps:
     def _p_xspec_free(self, h):
         if self._ctx is not None:
             _lib.call("fs_xspec_free", self._ctx, h)
+
+    def _p_flux_create(self, box, half_widths, dx, every, start):
+        h = ctypes.c_void_p()
+        _lib.call("fs_flux_create", self._ctx, (ctypes.c_int * 4)(*box), len(half_widths), (ctypes.c_int * len(half_widths))(*half_widths), dx, every,
+                  start, ctypes.byref(h))
+        return h
+
+    def _p_flux_read(self, h, words):
+        flat = np.empty(words, np.float64)
+        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
+        _lib.call("fs_flux_read", self._ctx, h, flat.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if words else None, ctypes.byref(launches),
+                  ctypes.byref(samples))
+        return flat, launches.value, samples.value
+
+    def _p_flux_filtered(self, h, index, words):
+        out = np.empty(words, np.float64)
+        _lib.call("fs_flux_filtered", self._ctx, h, index, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        return out
+
+    def _p_flux_get(self, h, words):
+        flat = np.empty(words, np.float64)
+        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
+        _lib.call("fs_flux_get", self._ctx, h, flat.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(launches), ctypes.byref(samples))
+        return flat, launches.value, samples.value
+
+    def _p_flux_set(self, h, flat, launches, samples):
+        _lib.call("fs_flux_set", self._ctx, h, flat.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), launches, samples)
+
+    def _p_flux_reset(self, h):
+        _lib.call("fs_flux_reset", self._ctx, h)
+
+    def _p_flux_free(self, h):
+        if self._ctx is not None:
+            _lib.call("fs_flux_free", self._ctx, h)
 
     def _p_flowmap_create(self, box, refine):
         h = ctypes.c_void_p()

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 26
+#define FS_ABI_VERSION 27
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -604,6 +604,41 @@ int fs_xspec_get(fs_ctx *ctx, fs_xspec *s, double *sums, long long *launches, lo
 int fs_xspec_set(fs_ctx *ctx, fs_xspec *s, const double *sums, long long launches, long long samples);
 int fs_xspec_reset(fs_ctx *ctx, fs_xspec *s);
 int fs_xspec_free(fs_ctx *ctx, fs_xspec *s);
+
+/* Scale-to-scale fluxes by filtering (new, ABI 27): the velocity and the vorticity box-filtered at up to FS_FLUX_MAX_WIDTHS half-widths r (a
+ * square of (2 r + 1)^2 cells, direct ordered sums), the sub-filter stresses tau = filt(u_i u_j) - filt(u_i) filt(u_j), and per cell of a box the
+ * accumulated energy flux PI = -tau_ij S_ij, enstrophy flux ZF and sub-filter energy K, by launches that can be captured in a hipGraph (the
+ * quantities, the operation order and the kernels: csrc/fs_flux.h).  All doubles, no atomics; a plane is a pure function of the field and the
+ * order of the samples.  The box is half-open, x0, y0, x1, y1 of global cells inside the grid, any sides; the filter reads outside the box, never
+ * outside the grid; solid cells count as fluid at rest.  Planes are (Ny, Nx) in C order, cell (a, b) of the box at b * Nx + a.  Single-GPU
+ * contexts: create returns FS_ERR_UNSUPPORTED on a slab context.
+ * create:  nr half-widths, 1 .. FS_FLUX_MAX_WIDTHS of them, each 1 .. FS_FLUX_MAX_R, strictly increasing; a cell (i, j) is valid for r when
+ *          r + 1 <= i <= X - 2 - r and r + 1 <= j <= Y - 2 - r, and a half-width without a valid cell in the box is FS_ERR_ARG.  dx finite and > 0.
+ *          every >= 1, start >= 0 (the sampling rule of fs_mean_create).  Device memory: 192 bytes per cell of the box dilated by r_max + 1
+ *          (clipped to the grid) and 24 bytes per cell of the box and half-width.
+ * launch:  2 + 3 nr kernel launches, nothing else (capturable); all but the last return at once unless this launch samples.  limit > 0: v still
+ *          owes limit_field(limit).  Needs the mask.
+ * read:    synchronises; sums: nr * FS_FLUX_NSUM planes - per half-width PI, ZF, K, the sums over the samples; a cell that is not valid for
+ *          the half-width holds +0 -, or NULL; launches, samples: may be NULL.  Resets nothing.
+ * filtered: the FS_FLUX_NQ filtered planes (of U, W, OM, U U, U W, W W, U OM, W OM) of half-width number `width` over the box, from the
+ *          fields of the last sampling launch (zeros before the first): two kernel launches and a download.  +0 where the window leaves the grid.
+ * get / set: the sums and the counters, for checkpoints; set: 0 <= samples <= launches.
+ * reset:   sums and sample count to zero; the launch count runs on.
+ * free:    as fs_mean_free.
+ * Everything but launch and free returns FS_ERR_STATE during graph capture / tape recording.                                             */
+#define FS_FLUX_NQ 8
+#define FS_FLUX_NSUM 3
+#define FS_FLUX_MAX_WIDTHS 8
+#define FS_FLUX_MAX_R 64
+typedef struct fs_flux fs_flux;
+int fs_flux_create(fs_ctx *ctx, const int *box, int nr, const int *half_widths, double dx, long long every, long long start, fs_flux **out);
+int fs_flux_launch(fs_ctx *ctx, fs_flux *s, double limit, const fs_field *v);
+int fs_flux_read(fs_ctx *ctx, fs_flux *s, double *sums, long long *launches, long long *samples);
+int fs_flux_filtered(fs_ctx *ctx, fs_flux *s, int width, double *planes);
+int fs_flux_get(fs_ctx *ctx, fs_flux *s, double *sums, long long *launches, long long *samples);
+int fs_flux_set(fs_ctx *ctx, fs_flux *s, const double *sums, long long launches, long long samples);
+int fs_flux_reset(fs_ctx *ctx, fs_flux *s);
+int fs_flux_free(fs_ctx *ctx, fs_flux *s);
 
 /* Multigrid pressure correction (new, ABI 19): one W-cycle (two coarse visits per level) on a mask-aware hierarchy of coarse levels, for the
  * third pressure updater (fs/pressure_updater.py MultigridPressureUpdater; kernels and operation order: csrc/fs_mg.h).  Single-GPU contexts.
