@@ -1,7 +1,10 @@
 // fs_diag.hip - C-ABI entry points of what reads the flow without changing it: the flow diagnostics (fs_stats.h), the per-step history ring
 // (fs_history.h), the body surface loads (fs_loads.h), the time averages (fs_mean.h), the harmonic modes (fs_modes.h), the snapshot POD
 // (fs_pod.h), the flow maps through its snapshots (fs_lcs.h), the vortex identification (fs_vortex.h), the field distributions (fs_dist.h), the energy spectra (fs_spec.h), the cross-spectra (fs_xspec.h) and the scale-to-scale fluxes (fs_flux.h).  Their objects live in the context's
-// registry (fs_host.h: FS_OBJECT, FS_HANDLE, FS_NO_CAPTURE, object_free).
+// registry (fs_host.h: FS_OBJECT, FS_HANDLE, FS_NO_CAPTURE, object_free).  What the accumulators share on the host is there as well: fill_buffers
+// builds every object, counted_read / counted_set / counted_reset move a payload behind its counters, FS_BOX checks a cell box, and the two
+// spectral riders are one SpecPlan each (spec_plan_create, spec_forward, spec_finish below).  An entry point keeps its own argument checks, in its
+// own order, and its kernels.
 #include "fs_launch.h"
 #include "fs_stats.h"
 #include "fs_mean.h"
@@ -59,6 +62,11 @@ static int copy_planes(fs_ctx *ctx, int planes, size_t es, void *dev, size_t pla
         else FS_HIP(hipMemcpy2DAsync(d, wp, h, wx, wx, ny, kind, ctx->stream));
     }
     return FS_OK;
+}
+// ... as the callable of counted_read / counted_set
+static auto planes_copy(fs_ctx *ctx, int planes, size_t es, void *dev, size_t plane, const void *host, hipMemcpyKind kind)
+{
+    return [=] { return copy_planes(ctx, planes, es, dev, plane, const_cast<void *>(host), kind); };
 }
 
 extern "C" {
@@ -134,16 +142,11 @@ int fs_history_create(fs_ctx *ctx, int npoints, const int *points, int nfaces, c
     h->np = npoints; h->nf = nfaces; h->cap = capacity; h->every = every;
     h->nparts = nfaces > HIST_SPLIT ? (nfaces + HIST_FACES_PER_WG - 1) / HIST_FACES_PER_WG : 0;
     const size_t ring = (size_t)capacity * (2 + 3 * (size_t)npoints) * sizeof(double);
-    hipError_t e = h->d_state.alloc(HIST_STATE * sizeof(long long));
-    if (e == hipSuccess) e = h->d_ring.alloc(ring);
-    if (e == hipSuccess && h->nparts) e = h->d_partial.alloc(2 * (size_t)h->nparts * sizeof(double));
-    if (e == hipSuccess) e = h->d_probes.alloc(std::max<size_t>(1, hp.size()) * sizeof(HistProbe));
-    if (e == hipSuccess) e = h->d_faces.alloc(std::max<size_t>(1, hf.size()) * sizeof(HistFace));
-    if (e == hipSuccess) e = hipMemsetAsync(h->d_state, 0, HIST_STATE * sizeof(long long), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(h->d_ring, 0, ring, ctx->stream);
-    if (e == hipSuccess && npoints) e = hipMemcpyAsync(h->d_probes, hp.data(), hp.size() * sizeof(HistProbe), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && nfaces) e = hipMemcpyAsync(h->d_faces, hf.data(), hf.size() * sizeof(HistFace), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    // (an empty list still gets a buffer, of one zeroed entry)
+    const hipError_t e = fill_buffers(ctx, {{h->d_state, HIST_STATE * sizeof(long long)}, {h->d_ring, ring},
+                                            {h->d_partial, 2 * (size_t)h->nparts * sizeof(double)},
+                                            {h->d_probes, std::max<size_t>(1, hp.size()) * sizeof(HistProbe), npoints ? hp.data() : nullptr},
+                                            {h->d_faces, std::max<size_t>(1, hf.size()) * sizeof(HistFace), nfaces ? hf.data() : nullptr}});
     if (e != hipSuccess) return hip_fail(e, "fs_history_create", __FILE__, __LINE__);
     *out = adopt(ctx, std::move(h));
     return FS_OK;
@@ -225,17 +228,9 @@ int fs_loads_create(fs_ctx *ctx, int nfaces, const int *faces, const double *cen
     l->nf = nfaces; l->cap = capacity; l->every = every; l->start = start;
     l->nparts = nfaces > LOADS_SPLIT ? (nfaces + LOADS_WG - 1) / LOADS_WG : 0;
     const size_t ring = (size_t)capacity * LOADS_REC * sizeof(double), sums = (size_t)LOADS_SUMS * nfaces * sizeof(double);
-    hipError_t e = l->d_state.alloc(LOADS_STATE * sizeof(long long));
-    if (e == hipSuccess) e = l->d_ring.alloc(ring);
-    if (e == hipSuccess) e = l->d_sums.alloc(sums);
-    if (e == hipSuccess && l->nparts) e = l->d_partial.alloc((size_t)LOADS_REC * l->nparts * sizeof(double));
-    if (e == hipSuccess) e = l->d_faces.alloc(lf.size() * sizeof(LoadFace));
-    if (e == hipSuccess) e = hipMemsetAsync(l->d_state, 0, LOADS_STATE * sizeof(long long), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(l->d_ring, 0, ring, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(l->d_sums, 0, sums, ctx->stream);
-    if (e == hipSuccess && l->nparts) e = hipMemsetAsync(l->d_partial, 0, (size_t)LOADS_REC * l->nparts * sizeof(double), ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(l->d_faces, lf.data(), lf.size() * sizeof(LoadFace), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    const hipError_t e = fill_buffers(ctx, {{l->d_state, LOADS_STATE * sizeof(long long)}, {l->d_ring, ring}, {l->d_sums, sums},
+                                            {l->d_partial, (size_t)LOADS_REC * l->nparts * sizeof(double)},
+                                            {l->d_faces, lf.size() * sizeof(LoadFace), lf.data()}});
     if (e != hipSuccess) return hip_fail(e, "fs_loads_create", __FILE__, __LINE__);
     *out = adopt(ctx, std::move(l));
     return FS_OK;
@@ -305,12 +300,8 @@ int fs_loads_sums_write(fs_ctx *ctx, fs_loads *l, const double *sums_in, long lo
     FS_HANDLE(l);
     FS_COUNTERS(launches, samples);
     FS_NO_CAPTURE(fs_loads, "sums_write");
-    FS_HIP(hipSetDevice(ctx->device));
-    const long long st[2] = {launches, samples};
-    FS_HIP(hipMemcpyAsync(l->d_sums, sums_in, (size_t)LOADS_SUMS * l->nf * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipMemcpyAsync(l->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
-    return FS_OK;
+    return counted_set(ctx, l->d_state, launches, samples,
+                       dense_copy(ctx, l->d_sums, sums_in, (size_t)LOADS_SUMS * l->nf * sizeof(double), hipMemcpyHostToDevice));
 }
 
 int fs_loads_reset(fs_ctx *ctx, fs_loads *l)
@@ -318,10 +309,7 @@ int fs_loads_reset(fs_ctx *ctx, fs_loads *l)
     FS_REQUIRE(ctx && l, "null argument");
     FS_HANDLE(l);
     FS_NO_CAPTURE(fs_loads, "reset");
-    FS_HIP(hipSetDevice(ctx->device));
-    FS_HIP(hipMemsetAsync(l->d_sums, 0, (size_t)LOADS_SUMS * l->nf * sizeof(double), ctx->stream));
-    FS_HIP(hipMemsetAsync(l->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
-    return FS_OK;
+    return counted_reset(ctx, l->d_state, dense_zero(ctx, l->d_sums, (size_t)LOADS_SUMS * l->nf * sizeof(double)));
 }
 
 int fs_loads_free(fs_ctx *ctx, fs_loads *l) { return object_free(ctx, l); }
@@ -359,11 +347,7 @@ int fs_mean_create(fs_ctx *ctx, long long every, long long start, fs_mean **out)
     m->every = every; m->start = start;
     m->plane = (size_t)ctx->nyl * ctx->P + MEAN_PAD;
     const size_t bytes = MEAN_PLANES * m->plane * sizeof(double);
-    hipError_t e = m->d_state.alloc(MEAN_STATE * sizeof(long long));
-    if (e == hipSuccess) e = m->d_sums.alloc(bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(m->d_state, 0, MEAN_STATE * sizeof(long long), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(m->d_sums, 0, bytes, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    const hipError_t e = fill_buffers(ctx, {{m->d_state, MEAN_STATE * sizeof(long long)}, {m->d_sums, bytes}});
     if (e != hipSuccess) return hip_fail(e, "fs_mean_create", __FILE__, __LINE__);
     *out = adopt(ctx, std::move(m));
     return FS_OK;
@@ -425,14 +409,8 @@ int fs_mean_read(fs_ctx *ctx, fs_mean *m, double *sums_out, long long *launches,
     FS_REQUIRE(ctx && m, "null argument");
     FS_HANDLE(m);
     FS_NO_CAPTURE(fs_mean, "read");
-    long long st[MEAN_STATE];
-    if (int rc = read_counters(ctx, m->d_state, st)) return rc;
-    if (launches) *launches = st[0];
-    if (samples) *samples = st[1];
-    if (!sums_out) return FS_OK;
-    if (int rc = copy_planes(ctx, MEAN_PLANES, sizeof(double), m->d_sums, m->plane, sums_out, hipMemcpyDeviceToHost)) return rc;
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    return FS_OK;
+    return counted_read(ctx, m->d_state, launches, samples, sums_out != nullptr,
+                        planes_copy(ctx, MEAN_PLANES, sizeof(double), m->d_sums, m->plane, sums_out, hipMemcpyDeviceToHost));
 }
 
 int fs_mean_write(fs_ctx *ctx, fs_mean *m, const double *sums_in, long long launches, long long samples)
@@ -441,12 +419,8 @@ int fs_mean_write(fs_ctx *ctx, fs_mean *m, const double *sums_in, long long laun
     FS_HANDLE(m);
     FS_COUNTERS(launches, samples);
     FS_NO_CAPTURE(fs_mean, "write");
-    FS_HIP(hipSetDevice(ctx->device));
-    const long long st[MEAN_STATE] = {launches, samples};
-    if (int rc = copy_planes(ctx, MEAN_PLANES, sizeof(double), m->d_sums, m->plane, const_cast<double *>(sums_in), hipMemcpyHostToDevice)) return rc;
-    FS_HIP(hipMemcpyAsync(m->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
-    return FS_OK;
+    return counted_set(ctx, m->d_state, launches, samples,
+                       planes_copy(ctx, MEAN_PLANES, sizeof(double), m->d_sums, m->plane, sums_in, hipMemcpyHostToDevice));
 }
 
 int fs_mean_reset(fs_ctx *ctx, fs_mean *m)
@@ -454,10 +428,7 @@ int fs_mean_reset(fs_ctx *ctx, fs_mean *m)
     FS_REQUIRE(ctx && m, "null argument");
     FS_HANDLE(m);
     FS_NO_CAPTURE(fs_mean, "reset");
-    FS_HIP(hipSetDevice(ctx->device));
-    FS_HIP(hipMemsetAsync(m->d_sums, 0, MEAN_PLANES * m->plane * sizeof(double), ctx->stream));
-    FS_HIP(hipMemsetAsync(m->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
-    return FS_OK;
+    return counted_reset(ctx, m->d_state, dense_zero(ctx, m->d_sums, MEAN_PLANES * m->plane * sizeof(double)));
 }
 
 int fs_mean_free(fs_ctx *ctx, fs_mean *m) { return object_free(ctx, m); }
@@ -503,13 +474,8 @@ int fs_modes_create(fs_ctx *ctx, int nfreq, const double *cos_sin, long long eve
     const size_t bytes = 3 * (size_t)modes_basis(nfreq) * m->plane * sizeof(double);
     double sc[modes_scalars(MODES_MAX_FREQ)];
     modes_fresh_scalars(nfreq, sc);
-    hipError_t e = m->d_state.alloc(MODES_STATE * sizeof(long long));
-    if (e == hipSuccess) e = m->d_scal.alloc(modes_scalars(nfreq) * sizeof(double));
-    if (e == hipSuccess) e = m->d_sums.alloc(bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(m->d_state, 0, MODES_STATE * sizeof(long long), ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(m->d_scal, sc, modes_scalars(nfreq) * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(m->d_sums, 0, bytes, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    const hipError_t e = fill_buffers(ctx, {{m->d_state, MODES_STATE * sizeof(long long)}, {m->d_scal, modes_scalars(nfreq) * sizeof(double), sc},
+                                            {m->d_sums, bytes}});
     if (e != hipSuccess) return hip_fail(e, "fs_modes_create", __FILE__, __LINE__);
     *out = adopt(ctx, std::move(m));
     return FS_OK;
@@ -571,17 +537,10 @@ int fs_modes_read(fs_ctx *ctx, fs_modes *m, double *sums_out, double *scalars_ou
     FS_REQUIRE(ctx && m, "null argument");
     FS_HANDLE(m);
     FS_NO_CAPTURE(fs_modes, "read");
-    FS_HIP(hipSetDevice(ctx->device));
-    long long st[MODES_STATE];
-    FS_HIP(hipMemcpyAsync(st, m->d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
-    if (scalars_out)
-        FS_HIP(hipMemcpyAsync(scalars_out, m->d_scal, modes_scalars(m->nfreq) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (sums_out)
-        if (int rc = copy_planes(ctx, 3 * modes_basis(m->nfreq), sizeof(double), m->d_sums, m->plane, sums_out, hipMemcpyDeviceToHost)) return rc;
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    if (launches) *launches = st[0];
-    if (samples) *samples = st[1];
-    return FS_OK;
+    return counted_read(ctx, m->d_state, launches, samples, sums_out || scalars_out, [=]() -> int {
+        if (scalars_out) FS_HIP(hipMemcpyAsync(scalars_out, m->d_scal, modes_scalars(m->nfreq) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        return sums_out ? copy_planes(ctx, 3 * modes_basis(m->nfreq), sizeof(double), m->d_sums, m->plane, sums_out, hipMemcpyDeviceToHost) : FS_OK;
+    });
 }
 
 int fs_modes_write(fs_ctx *ctx, fs_modes *m, const double *sums_in, const double *scalars_in, long long launches, long long samples)
@@ -590,13 +549,10 @@ int fs_modes_write(fs_ctx *ctx, fs_modes *m, const double *sums_in, const double
     FS_HANDLE(m);
     FS_COUNTERS(launches, samples);
     FS_NO_CAPTURE(fs_modes, "write");
-    FS_HIP(hipSetDevice(ctx->device));
-    const long long st[MODES_STATE] = {launches, samples};
-    if (int rc = copy_planes(ctx, 3 * modes_basis(m->nfreq), sizeof(double), m->d_sums, m->plane, const_cast<double *>(sums_in), hipMemcpyHostToDevice)) return rc;
-    FS_HIP(hipMemcpyAsync(m->d_scal, scalars_in, modes_scalars(m->nfreq) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipMemcpyAsync(m->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));      // (the sources are the caller's / this frame's memory)
-    return FS_OK;
+    return counted_set(ctx, m->d_state, launches, samples, [=]() -> int {
+        FS_HIP(hipMemcpyAsync(m->d_scal, scalars_in, modes_scalars(m->nfreq) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        return copy_planes(ctx, 3 * modes_basis(m->nfreq), sizeof(double), m->d_sums, m->plane, const_cast<double *>(sums_in), hipMemcpyHostToDevice);
+    });
 }
 
 int fs_modes_reset(fs_ctx *ctx, fs_modes *m)
@@ -604,14 +560,13 @@ int fs_modes_reset(fs_ctx *ctx, fs_modes *m)
     FS_REQUIRE(ctx && m, "null argument");
     FS_HANDLE(m);
     FS_NO_CAPTURE(fs_modes, "reset");
-    FS_HIP(hipSetDevice(ctx->device));
     double sc[modes_scalars(MODES_MAX_FREQ)];
     modes_fresh_scalars(m->nfreq, sc);
-    FS_HIP(hipMemsetAsync(m->d_sums, 0, 3 * (size_t)modes_basis(m->nfreq) * m->plane * sizeof(double), ctx->stream));
-    FS_HIP(hipMemsetAsync(m->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
-    FS_HIP(hipMemcpyAsync(m->d_scal, sc, modes_scalars(m->nfreq) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));      // (the source is this frame's memory)
-    return FS_OK;
+    return counted_reset(ctx, m->d_state, [=, &sc]() -> int {
+        FS_HIP(hipMemsetAsync(m->d_sums, 0, 3 * (size_t)modes_basis(m->nfreq) * m->plane * sizeof(double), ctx->stream));
+        FS_HIP(hipMemcpyAsync(m->d_scal, sc, modes_scalars(m->nfreq) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        return FS_OK;
+    }, true);      // (sc is this frame's memory)
 }
 
 int fs_modes_free(fs_ctx *ctx, fs_modes *m) { return object_free(ctx, m); }
@@ -635,11 +590,7 @@ int fs_pod_create(fs_ctx *ctx, int M, long long every, long long start, fs_pod *
     p->M = M; p->every = every; p->start = start;
     p->plane = (size_t)ctx->nyl * ctx->P + MEAN_PAD;
     const size_t bytes = (size_t)M * pod_slot_bytes(ctx, p.get());
-    hipError_t e = p->d_state.alloc(POD_STATE * sizeof(long long));
-    if (e == hipSuccess) e = p->d_slots.alloc(bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(p->d_state, 0, POD_STATE * sizeof(long long), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(p->d_slots, 0, bytes, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    const hipError_t e = fill_buffers(ctx, {{p->d_state, POD_STATE * sizeof(long long)}, {p->d_slots, bytes}});
     if (e != hipSuccess) return hip_fail(e, "fs_pod_create", __FILE__, __LINE__);
     *out = adopt(ctx, std::move(p));
     return FS_OK;
@@ -766,12 +717,8 @@ int fs_pod_set(fs_ctx *ctx, fs_pod *pod, const void *slots_in, long long launche
     FS_HANDLE(pod);
     FS_COUNTERS(launches, samples);
     FS_NO_CAPTURE(fs_pod, "set");
-    FS_HIP(hipSetDevice(ctx->device));
-    const long long st[POD_STATE] = {launches, samples};
-    if (int rc = copy_planes(ctx, 3 * pod->M, ctx->esize, pod->d_slots, pod->plane, const_cast<void *>(slots_in), hipMemcpyHostToDevice)) return rc;
-    FS_HIP(hipMemcpyAsync(pod->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
-    return FS_OK;
+    return counted_set(ctx, pod->d_state, launches, samples,
+                       planes_copy(ctx, 3 * pod->M, ctx->esize, pod->d_slots, pod->plane, slots_in, hipMemcpyHostToDevice));
 }
 
 int fs_pod_reset(fs_ctx *ctx, fs_pod *pod)
@@ -779,10 +726,7 @@ int fs_pod_reset(fs_ctx *ctx, fs_pod *pod)
     FS_REQUIRE(ctx && pod, "null argument");
     FS_HANDLE(pod);
     FS_NO_CAPTURE(fs_pod, "reset");
-    FS_HIP(hipSetDevice(ctx->device));
-    FS_HIP(hipMemsetAsync(pod->d_slots, 0, (size_t)pod->M * pod_slot_bytes(ctx, pod), ctx->stream));
-    FS_HIP(hipMemsetAsync(pod->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
-    return FS_OK;
+    return counted_reset(ctx, pod->d_state, dense_zero(ctx, pod->d_slots, (size_t)pod->M * pod_slot_bytes(ctx, pod)));
 }
 
 int fs_pod_free(fs_ctx *ctx, fs_pod *pod) { return object_free(ctx, pod); }
@@ -840,22 +784,11 @@ int fs_vortex_create(fs_ctx *ctx, int criterion, double threshold, double scale,
     x->nblocks = (x->cells + VX_BLOCK - 1) / VX_BLOCK;
     x->words = VX_HEAD + VX_REC * max_vortices;
     const size_t n = (size_t)x->cells, table = (size_t)VX_NACC * max_components * sizeof(long long);
-    hipError_t e = x->d_state.alloc(VX_STATE * sizeof(long long));
-    if (e == hipSuccess) e = x->d_tmp.alloc(VX_TMP * sizeof(long long));
-    if (e == hipSuccess) e = x->d_flags.alloc(n);
-    if (e == hipSuccess) e = x->d_labels.alloc(n * sizeof(int));
-    if (e == hipSuccess) e = x->d_ids.alloc(n * sizeof(int));
-    if (e == hipSuccess) e = x->d_counts.alloc((size_t)x->nblocks * sizeof(int));
-    if (e == hipSuccess) e = x->d_table.alloc(table);
-    if (e == hipSuccess) e = x->d_ring.alloc((size_t)capacity * x->words * sizeof(long long));
-    if (e == hipSuccess) e = hipMemsetAsync(x->d_state, 0, VX_STATE * sizeof(long long), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(x->d_tmp, 0, VX_TMP * sizeof(long long), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(x->d_flags, 0, n, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(x->d_labels, 0xff, n * sizeof(int), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(x->d_ids, 0, n * sizeof(int), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(x->d_table, 0, table, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(x->d_ring, 0, (size_t)capacity * x->words * sizeof(long long), ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    // (the labels start at -1; the counts need no initial value and get zero)
+    const hipError_t e = fill_buffers(ctx, {{x->d_state, VX_STATE * sizeof(long long)}, {x->d_tmp, VX_TMP * sizeof(long long)}, {x->d_flags, n},
+                                            {x->d_labels, n * sizeof(int), nullptr, 0xff}, {x->d_ids, n * sizeof(int)},
+                                            {x->d_counts, (size_t)x->nblocks * sizeof(int)}, {x->d_table, table},
+                                            {x->d_ring, (size_t)capacity * x->words * sizeof(long long)}});
     if (e != hipSuccess) return hip_fail(e, "fs_vortex_create", __FILE__, __LINE__);
     *out = adopt(ctx, std::move(x));
     return FS_OK;
@@ -1012,9 +945,7 @@ int fs_vortex_free(fs_ctx *ctx, fs_vortex *vx) { return object_free(ctx, vx); }
         set_error("field distributions need a single-GPU context: on a slab the tables would have to be added across ranks (not implemented)"); \
         return FS_ERR_UNSUPPORTED; \
     }
-#define FS_DIST_BOX(box) \
-    FS_REQUIRE(0 <= (box)[0] && (box)[0] < (box)[2] && (box)[2] <= ctx->X && 0 <= (box)[1] && (box)[1] < (box)[3] && (box)[3] <= ctx->Y, \
-               "distribution box must satisfy 0 <= x0 < x1 <= X and 0 <= y0 < y1 <= Y")
+#define FS_DIST_BOX(box) FS_BOX(box, ctx->X, ctx->Y, "distribution box must satisfy 0 <= x0 < x1 <= X and 0 <= y0 < y1 <= Y")
 
 // the walk of a pass over `box`: the workgroups of the whole grid's tiling (256 columns, rows from diag_rows) that meet the box
 static DistWalk dist_walk_of(const fs_ctx *ctx, const int *box, int need, double dx, double limit, dim3 *grid)
@@ -1055,11 +986,7 @@ int fs_dist_create(fs_ctx *ctx, int nchan, const fs_dist_spec *specs, long long 
     FS_DIST_SINGLE_GPU()
     FS_HIP(hipSetDevice(ctx->device));
     const size_t bytes = d->offset[nchan] * sizeof(long long);
-    hipError_t e = d->d_state.alloc(DIST_STATE * sizeof(long long));
-    if (e == hipSuccess) e = d->d_tables.alloc(bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(d->d_state, 0, DIST_STATE * sizeof(long long), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d->d_tables, 0, bytes, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    const hipError_t e = fill_buffers(ctx, {{d->d_state, DIST_STATE * sizeof(long long)}, {d->d_tables, bytes}});
     if (e != hipSuccess) return hip_fail(e, "fs_dist_create", __FILE__, __LINE__);
     *out = adopt(ctx, std::move(d));
     return FS_OK;
@@ -1099,15 +1026,13 @@ int fs_dist_read(fs_ctx *ctx, fs_dist *d, int chan, long long *counts, long long
     FS_HANDLE(d);
     FS_REQUIRE(chan >= 0 && chan < d->nchan, "channel outside 0 .. nchan - 1");
     FS_NO_CAPTURE(fs_dist, "read");
-    long long st[DIST_STATE];
-    if (int rc = read_counters(ctx, d->d_state, st)) return rc;
     const size_t bins = d->offset[chan + 1] - d->offset[chan] - DIST_TAILS;
-    if (counts) FS_HIP(hipMemcpyAsync(counts, d->d_tables + d->offset[chan], bins * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    if (tails) FS_HIP(hipMemcpyAsync(tails, d->d_tables + d->offset[chan] + bins, DIST_TAILS * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    if (launches) *launches = st[0];
-    if (samples) *samples = st[1];
-    return FS_OK;
+    const long long *table = d->d_tables + d->offset[chan];
+    return counted_read(ctx, d->d_state, launches, samples, counts || tails, [=]() -> int {
+        if (counts) FS_HIP(hipMemcpyAsync(counts, table, bins * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+        if (tails) FS_HIP(hipMemcpyAsync(tails, table + bins, DIST_TAILS * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+        return FS_OK;
+    });
 }
 
 int fs_dist_get(fs_ctx *ctx, fs_dist *d, long long *words_out)
@@ -1127,12 +1052,8 @@ int fs_dist_set(fs_ctx *ctx, fs_dist *d, const long long *words_in, long long la
     FS_HANDLE(d);
     FS_COUNTERS(launches, samples);
     FS_NO_CAPTURE(fs_dist, "set");
-    FS_HIP(hipSetDevice(ctx->device));
-    const long long st[DIST_STATE] = {launches, samples};
-    FS_HIP(hipMemcpyAsync(d->d_tables, words_in, d->offset[d->nchan] * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipMemcpyAsync(d->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
-    return FS_OK;
+    return counted_set(ctx, d->d_state, launches, samples,
+                       dense_copy(ctx, d->d_tables, words_in, d->offset[d->nchan] * sizeof(long long), hipMemcpyHostToDevice));
 }
 
 int fs_dist_reset(fs_ctx *ctx, fs_dist *d)
@@ -1140,10 +1061,7 @@ int fs_dist_reset(fs_ctx *ctx, fs_dist *d)
     FS_REQUIRE(ctx && d, "null argument");
     FS_HANDLE(d);
     FS_NO_CAPTURE(fs_dist, "reset");
-    FS_HIP(hipSetDevice(ctx->device));
-    FS_HIP(hipMemsetAsync(d->d_tables, 0, d->offset[d->nchan] * sizeof(long long), ctx->stream));
-    FS_HIP(hipMemsetAsync(d->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
-    return FS_OK;
+    return counted_reset(ctx, d->d_state, dense_zero(ctx, d->d_tables, d->offset[d->nchan] * sizeof(long long)));
 }
 
 int fs_dist_free(fs_ctx *ctx, fs_dist *d) { return object_free(ctx, d); }
@@ -1224,46 +1142,90 @@ int fs_dist_select(fs_ctx *ctx, int quantity, const int *box, double limit, doub
     return FS_OK;
 }
 
-// ---- energy spectra (fs_spec.h) --------------------------------------------------------------------------------------------------------------
+// ---- energy spectra (fs_spec.h) and cross-spectra (fs_xspec.h): one plan each (fs_host.h SpecPlan) and an accumulator of their own ------------
+#define FS_SPEC_BOX(box)                                                                                             \
+    FS_BOX(box, ctx->X, ctx->Y, "spectrum box must satisfy 0 <= x0 < x1 <= X and 0 <= y0 < y1 <= Y");                \
+    FS_REQUIRE(spec_log2((box)[2] - (box)[0]) > 0 && spec_log2((box)[3] - (box)[1]) > 0,                             \
+               "the sides of a spectrum box must be powers of two in FS_SPEC_MIN_N .. FS_SPEC_MAX_N")
+
+static dim3 spec_chunks(size_t cells) { return dim3((unsigned)((cells + SPEC_CHUNK - 1) / SPEC_CHUNK)); }
+
+extern "C++" {
+// What both creates do behind the argument checks of their own: the checks they share, the plan's members, its buffers and `acc`, the kind's
+// accumulator.  `riders`: the kind as the slab refusal names it; `who`: the entry point, for a HIP error.
+template <typename T>
+static int spec_plan_create(fs_ctx *ctx, T &s, const char *riders, const char *who, const int *box, const double *wx, const double *wy, const double *twx,
+                            const double *twy, double c1x, double c1y, int detrend, long long every, long long start, Fill acc)
+{
+    FS_REQUIRE(std::isfinite(c1x) && std::isfinite(c1y), "the detrend pair must be finite");
+    FS_EVERY_START(every, start);
+    FS_NO_CAPTURE(T, "create");
+    if (ctx->halo != 0 || ctx->nyl != ctx->Y) {
+        set_error(std::string(riders) + " need a single-GPU context: on a slab the transform along y crosses the ranks (not implemented)");
+        return FS_ERR_UNSUPPORTED;
+    }
+    FS_HIP(hipSetDevice(ctx->device));
+    for (int k = 0; k < 4; ++k) s.box[k] = box[k];
+    const int nx = s.nx = box[2] - box[0], ny = s.ny = box[3] - box[1];
+    s.detrend = detrend ? 1 : 0; s.c1x = c1x; s.c1y = c1y; s.every = every; s.start = start;
+    const size_t plane = s.cells() * sizeof(double2);
+    const hipError_t e = fill_buffers(ctx, {{s.d_state, SPEC_STATE * sizeof(long long)}, {s.d_wx, nx * sizeof(double), wx}, {s.d_wy, ny * sizeof(double), wy},
+                                            {s.d_twx, nx * sizeof(double), twx}, {s.d_twy, ny * sizeof(double), twy}, {s.d_a, plane}, {s.d_b, plane}, acc});
+    return e == hipSuccess ? FS_OK : hip_fail(e, who, __FILE__, __LINE__);
+}
+
+// The launches both samplings share behind their first: `load` - the caller's kernel: the box's rows into d_a, transformed along x -, the transpose
+// into d_b, the transform along y back into d_a.  Every closure holds values copied out of the plan here: captured into graphs and tapes, it reads
+// nothing through the object when it is replayed.
+template <typename Load>
+static int spec_forward(fs_ctx *ctx, const SpecPlan &s, const SpecWhen when, Load load)
+{
+    const int nx = s.nx, ny = s.ny, logny = spec_log2(ny);
+    const size_t cells = s.cells();
+    const dim3 chunks = spec_chunks(cells);
+    const double *twy = s.d_twy;
+    double2 *A = s.d_a, *B = s.d_b;
+    int rc = load();
+    if (rc) return rc;
+    rc = launch(ctx, "spec_transpose", [=] {
+        klaunch(k_spec_transpose, dim3((nx + SPEC_TILE - 1) / SPEC_TILE, (ny + SPEC_TILE - 1) / SPEC_TILE), dim3(256), ctx->stream, when, ny, nx,
+                (const double2 *)A, B);
+    });
+    if (rc) return rc;
+    return launch(ctx, "spec_rows", [=] { klaunch(k_spec_rows, chunks, dim3(256), ctx->stream, when, ny, logny, cells, (const double2 *)B, twy, A); });
+}
+
+// Z' of the last sampling launch
+template <typename T>
+static int spec_plane(fs_ctx *ctx, T *s, double *plane)
+{
+    FS_REQUIRE(ctx && s && plane, "null argument");
+    FS_HANDLE(s);
+    FS_NO_CAPTURE(T, "plane");
+    FS_HIP(hipSetDevice(ctx->device));
+    FS_HIP(hipMemcpyAsync(plane, s->d_b, s->cells() * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+}  // extern "C++"
+
+// the last launch of a sampling (the fluxes' too): the counters advance
+static int spec_finish(fs_ctx *ctx, const SpecWhen when)
+{
+    long long *state = const_cast<long long *>(when.state);
+    const long long start = when.start, every = when.every;
+    return launch(ctx, "spec_tick", [=] { klaunch(k_spec_tick, dim3(1), dim3(64), ctx->stream, start, every, state); });
+}
+
 int fs_spec_create(fs_ctx *ctx, const int *box, const double *wx, const double *wy, const double *twx, const double *twy, double c1x, double c1y,
                    int detrend, long long every, long long start, fs_spec **out)
 {
     FS_REQUIRE(ctx && box && wx && wy && twx && twy && out, "null argument");
-    FS_REQUIRE(0 <= box[0] && box[0] < box[2] && box[2] <= ctx->X && 0 <= box[1] && box[1] < box[3] && box[3] <= ctx->Y,
-               "spectrum box must satisfy 0 <= x0 < x1 <= X and 0 <= y0 < y1 <= Y");
-    const int nx = box[2] - box[0], ny = box[3] - box[1];
-    FS_REQUIRE(spec_log2(nx) > 0 && spec_log2(ny) > 0, "the sides of a spectrum box must be powers of two in FS_SPEC_MIN_N .. FS_SPEC_MAX_N");
-    FS_REQUIRE(std::isfinite(c1x) && std::isfinite(c1y), "the detrend pair must be finite");
-    FS_EVERY_START(every, start);
-    FS_NO_CAPTURE(fs_spec, "create");
-    if (ctx->halo != 0 || ctx->nyl != ctx->Y) {
-        set_error("energy spectra need a single-GPU context: on a slab the transform along y crosses the ranks (not implemented)");
-        return FS_ERR_UNSUPPORTED;
-    }
-    FS_HIP(hipSetDevice(ctx->device));
+    FS_SPEC_BOX(box);
     auto s = std::make_unique<fs_spec>();
-    for (int k = 0; k < 4; ++k) s->box[k] = box[k];
-    s->nx = nx; s->ny = ny; s->detrend = detrend ? 1 : 0; s->c1x = c1x; s->c1y = c1y; s->every = every; s->start = start;
-    const size_t cells = (size_t)nx * ny;
-    hipError_t e = s->d_state.alloc(SPEC_STATE * sizeof(long long));
-    if (e == hipSuccess) e = s->d_wx.alloc(nx * sizeof(double));
-    if (e == hipSuccess) e = s->d_wy.alloc(ny * sizeof(double));
-    if (e == hipSuccess) e = s->d_twx.alloc(nx * sizeof(double));
-    if (e == hipSuccess) e = s->d_twy.alloc(ny * sizeof(double));
-    if (e == hipSuccess) e = s->d_a.alloc(cells * sizeof(double2));
-    if (e == hipSuccess) e = s->d_b.alloc(cells * sizeof(double2));
-    if (e == hipSuccess) e = s->d_power.alloc(cells * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_wx, wx, nx * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_wy, wy, ny * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_twx, twx, nx * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_twy, twy, ny * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_state, 0, SPEC_STATE * sizeof(long long), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_a, 0, cells * sizeof(double2), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_b, 0, cells * sizeof(double2), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_power, 0, cells * sizeof(double), ctx->stream);
-    const hipError_t es = hipStreamSynchronize(ctx->stream);      // (the tables are the caller's memory: nothing is in flight past here)
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return hip_fail(e, "fs_spec_create", __FILE__, __LINE__);
+    const size_t power = (size_t)(box[2] - box[0]) * (box[3] - box[1]) * sizeof(double);
+    if (int rc = spec_plan_create(ctx, *s, "energy spectra", "fs_spec_create", box, wx, wy, twx, twy, c1x, c1y, detrend, every, start, {s->d_power, power}))
+        return rc;
     *out = adopt(ctx, std::move(s));
     return FS_OK;
 }
@@ -1277,32 +1239,25 @@ int fs_spec_launch(fs_ctx *ctx, fs_spec *s, double limit, const fs_field *v)
     // everything the launches need is in `s` and the field: no allocation, copy or synchronisation here (the closures are captured / taped)
     const int x0 = s->box[0], y0 = s->box[1], nx = s->nx, ny = s->ny, lognx = spec_log2(nx), logny = spec_log2(ny), detrend = s->detrend;
     const double c1x = s->c1x, c1y = s->c1y;
-    const long long every = s->every, start = s->start;
-    long long *state = s->d_state;
-    const SpecWhen when{state, start, every};
-    const size_t cells = (size_t)nx * ny;
-    const dim3 chunks((unsigned)((cells + SPEC_CHUNK - 1) / SPEC_CHUNK));
-    const double *wx = s->d_wx, *wy = s->d_wy, *twx = s->d_twx, *twy = s->d_twy;
+    const SpecWhen when{s->d_state, s->start, s->every};
+    const size_t cells = s->cells();
+    const dim3 chunks = spec_chunks(cells);
+    const double *wx = s->d_wx, *wy = s->d_wy, *twx = s->d_twx;
     double2 *A = s->d_a, *B = s->d_b;
     double *P = s->d_power;
-    int rc = by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
-        return launch(ctx, "spec_load_rows", [=] {
-            klaunch(k_spec_load_rows<T>, chunks, dim3(256), ctx->stream, ctx->grid(), when, x0, y0, nx, ny, lognx, limit, (const T *)v->d, wx, wy, twx, A);
+    int rc = spec_forward(ctx, *s, when, [&] {
+        return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
+            return launch(ctx, "spec_load_rows", [=] {
+                klaunch(k_spec_load_rows<T>, chunks, dim3(256), ctx->stream, ctx->grid(), when, x0, y0, nx, ny, lognx, limit, (const T *)v->d, wx, wy, twx, A);
+            });
         });
     });
-    if (rc) return rc;
-    rc = launch(ctx, "spec_transpose", [=] {
-        klaunch(k_spec_transpose, dim3((nx + SPEC_TILE - 1) / SPEC_TILE, (ny + SPEC_TILE - 1) / SPEC_TILE), dim3(256), ctx->stream, when, ny, nx,
-                (const double2 *)A, B);
-    });
-    if (rc) return rc;
-    rc = launch(ctx, "spec_rows", [=] { klaunch(k_spec_rows, chunks, dim3(256), ctx->stream, when, ny, logny, cells, (const double2 *)B, twy, A); });
     if (rc) return rc;
     rc = launch(ctx, "spec_power", [=] {
         klaunch(k_spec_power, dim3((unsigned)((cells + 255) / 256)), dim3(256), ctx->stream, when, nx, ny, logny, detrend, c1x, c1y, (const double2 *)A, B, P);
     });
     if (rc) return rc;
-    return launch(ctx, "spec_tick", [=] { klaunch(k_spec_tick, dim3(1), dim3(64), ctx->stream, start, every, state); });
+    return spec_finish(ctx, when);
 }
 
 int fs_spec_read(fs_ctx *ctx, fs_spec *s, double *power, long long *launches, long long *samples)
@@ -1310,27 +1265,11 @@ int fs_spec_read(fs_ctx *ctx, fs_spec *s, double *power, long long *launches, lo
     FS_REQUIRE(ctx && s, "null argument");
     FS_HANDLE(s);
     FS_NO_CAPTURE(fs_spec, "read");
-    long long st[SPEC_STATE];
-    if (int rc = read_counters(ctx, s->d_state, st)) return rc;
-    if (power) {
-        FS_HIP(hipMemcpyAsync(power, s->d_power, (size_t)s->nx * s->ny * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        FS_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    if (launches) *launches = st[0];
-    if (samples) *samples = st[1];
-    return FS_OK;
+    return counted_read(ctx, s->d_state, launches, samples, power != nullptr,
+                        dense_copy(ctx, power, s->d_power, s->cells() * sizeof(double), hipMemcpyDeviceToHost));
 }
 
-int fs_spec_plane(fs_ctx *ctx, fs_spec *s, double *plane)
-{
-    FS_REQUIRE(ctx && s && plane, "null argument");
-    FS_HANDLE(s);
-    FS_NO_CAPTURE(fs_spec, "plane");
-    FS_HIP(hipSetDevice(ctx->device));
-    FS_HIP(hipMemcpyAsync(plane, s->d_b, (size_t)s->nx * s->ny * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    return FS_OK;
-}
+int fs_spec_plane(fs_ctx *ctx, fs_spec *s, double *plane) { return spec_plane(ctx, s, plane); }
 
 int fs_spec_get(fs_ctx *ctx, fs_spec *s, double *power, long long *launches, long long *samples)
 {
@@ -1344,12 +1283,7 @@ int fs_spec_set(fs_ctx *ctx, fs_spec *s, const double *power, long long launches
     FS_HANDLE(s);
     FS_COUNTERS(launches, samples);
     FS_NO_CAPTURE(fs_spec, "set");
-    FS_HIP(hipSetDevice(ctx->device));
-    const long long st[SPEC_STATE] = {launches, samples};
-    FS_HIP(hipMemcpyAsync(s->d_power, power, (size_t)s->nx * s->ny * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipMemcpyAsync(s->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
-    return FS_OK;
+    return counted_set(ctx, s->d_state, launches, samples, dense_copy(ctx, s->d_power, power, s->cells() * sizeof(double), hipMemcpyHostToDevice));
 }
 
 int fs_spec_reset(fs_ctx *ctx, fs_spec *s)
@@ -1357,57 +1291,23 @@ int fs_spec_reset(fs_ctx *ctx, fs_spec *s)
     FS_REQUIRE(ctx && s, "null argument");
     FS_HANDLE(s);
     FS_NO_CAPTURE(fs_spec, "reset");
-    FS_HIP(hipSetDevice(ctx->device));
-    FS_HIP(hipMemsetAsync(s->d_power, 0, (size_t)s->nx * s->ny * sizeof(double), ctx->stream));
-    FS_HIP(hipMemsetAsync(s->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
-    return FS_OK;
+    return counted_reset(ctx, s->d_state, dense_zero(ctx, s->d_power, s->cells() * sizeof(double)));
 }
 
 int fs_spec_free(fs_ctx *ctx, fs_spec *s) { return object_free(ctx, s); }
 
-// ---- cross-spectra (fs_xspec.h) ----------------------------------------------------------------------------------------------------------------
 int fs_xspec_create(fs_ctx *ctx, const int *box, int qa, int qb, double dx, const double *wx, const double *wy, const double *twx, const double *twy,
                     double c1x, double c1y, int detrend, long long every, long long start, fs_xspec **out)
 {
     FS_REQUIRE(ctx && box && wx && wy && twx && twy && out, "null argument");
-    FS_REQUIRE(0 <= box[0] && box[0] < box[2] && box[2] <= ctx->X && 0 <= box[1] && box[1] < box[3] && box[3] <= ctx->Y,
-               "spectrum box must satisfy 0 <= x0 < x1 <= X and 0 <= y0 < y1 <= Y");
-    const int nx = box[2] - box[0], ny = box[3] - box[1];
-    FS_REQUIRE(spec_log2(nx) > 0 && spec_log2(ny) > 0, "the sides of a spectrum box must be powers of two in FS_SPEC_MIN_N .. FS_SPEC_MAX_N");
+    FS_SPEC_BOX(box);
     FS_REQUIRE(0 <= qa && qa < XSPEC_NQ && -1 <= qb && qb < XSPEC_NQ, "the quantities of a cross-spectrum must satisfy 0 <= qa <= 6 and -1 <= qb <= 6");
     FS_REQUIRE(std::isfinite(dx) && dx > 0.0, "dx must be finite and > 0");
-    FS_REQUIRE(std::isfinite(c1x) && std::isfinite(c1y), "the detrend pair must be finite");
-    FS_EVERY_START(every, start);
-    FS_NO_CAPTURE(fs_xspec, "create");
-    if (ctx->halo != 0 || ctx->nyl != ctx->Y) {
-        set_error("cross-spectra need a single-GPU context: on a slab the transform along y crosses the ranks (not implemented)");
-        return FS_ERR_UNSUPPORTED;
-    }
-    FS_HIP(hipSetDevice(ctx->device));
     auto s = std::make_unique<fs_xspec>();
-    for (int k = 0; k < 4; ++k) s->box[k] = box[k];
-    s->nx = nx; s->ny = ny; s->qa = qa; s->qb = qb; s->planes = qb >= 0 ? XSPEC_PLANES : 1; s->dx = dx;
-    s->detrend = detrend ? 1 : 0; s->c1x = c1x; s->c1y = c1y; s->every = every; s->start = start;
-    const size_t cells = (size_t)nx * ny, acc = cells * s->planes * sizeof(double);
-    hipError_t e = s->d_state.alloc(SPEC_STATE * sizeof(long long));
-    if (e == hipSuccess) e = s->d_wx.alloc(nx * sizeof(double));
-    if (e == hipSuccess) e = s->d_wy.alloc(ny * sizeof(double));
-    if (e == hipSuccess) e = s->d_twx.alloc(nx * sizeof(double));
-    if (e == hipSuccess) e = s->d_twy.alloc(ny * sizeof(double));
-    if (e == hipSuccess) e = s->d_a.alloc(cells * sizeof(double2));
-    if (e == hipSuccess) e = s->d_b.alloc(cells * sizeof(double2));
-    if (e == hipSuccess) e = s->d_acc.alloc(acc);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_wx, wx, nx * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_wy, wy, ny * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_twx, twx, nx * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_twy, twy, ny * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_state, 0, SPEC_STATE * sizeof(long long), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_a, 0, cells * sizeof(double2), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_b, 0, cells * sizeof(double2), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_acc, 0, acc, ctx->stream);
-    const hipError_t es = hipStreamSynchronize(ctx->stream);      // (the tables are the caller's memory: nothing is in flight past here)
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return hip_fail(e, "fs_xspec_create", __FILE__, __LINE__);
+    s->qa = qa; s->qb = qb; s->planes = qb >= 0 ? XSPEC_PLANES : 1; s->dx = dx;
+    const size_t acc = (size_t)s->planes * (box[2] - box[0]) * (box[3] - box[1]) * sizeof(double);
+    if (int rc = spec_plan_create(ctx, *s, "cross-spectra", "fs_xspec_create", box, wx, wy, twx, twy, c1x, c1y, detrend, every, start, {s->d_acc, acc}))
+        return rc;
     *out = adopt(ctx, std::move(s));
     return FS_OK;
 }
@@ -1422,62 +1322,40 @@ int fs_xspec_launch(fs_ctx *ctx, fs_xspec *s, double limit, const fs_field *v, c
     const int x0 = s->box[0], y0 = s->box[1], nx = s->nx, ny = s->ny, lognx = spec_log2(nx), logny = spec_log2(ny), detrend = s->detrend;
     const int qa = s->qa, qb = s->qb, need = dist_need(qa) | dist_need(qb), pair = qb >= 0 ? 1 : 0;
     const double c1x = s->c1x, c1y = s->c1y, two_dx = 2.0 * s->dx;
-    const long long every = s->every, start = s->start;
-    long long *state = s->d_state;
-    const SpecWhen when{state, start, every};
-    const size_t cells = (size_t)nx * ny;
-    const dim3 chunks((unsigned)((cells + SPEC_CHUNK - 1) / SPEC_CHUNK));
-    const double *wx = s->d_wx, *wy = s->d_wy, *twx = s->d_twx, *twy = s->d_twy;
+    const SpecWhen when{s->d_state, s->start, s->every};
+    const size_t cells = s->cells();
+    const dim3 chunks = spec_chunks(cells);
+    const double *wx = s->d_wx, *wy = s->d_wy, *twx = s->d_twx;
     double2 *A = s->d_a, *B = s->d_b;
     double *acc = s->d_acc;
-    int rc = by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
-        return launch(ctx, "xspec_load_rows", [=] {
-            klaunch(k_xspec_load_rows<T>, chunks, dim3(256), ctx->stream, ctx->grid(), when, x0, y0, nx, ny, lognx, qa, qb, need, limit, two_dx,
-                    (const T *)v->d, (const T *)p->d, wx, wy, twx, A);
+    int rc = spec_forward(ctx, *s, when, [&] {
+        return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
+            return launch(ctx, "xspec_load_rows", [=] {
+                klaunch(k_xspec_load_rows<T>, chunks, dim3(256), ctx->stream, ctx->grid(), when, x0, y0, nx, ny, lognx, qa, qb, need, limit, two_dx,
+                        (const T *)v->d, (const T *)p->d, wx, wy, twx, A);
+            });
         });
     });
-    if (rc) return rc;
-    rc = launch(ctx, "spec_transpose", [=] {
-        klaunch(k_spec_transpose, dim3((nx + SPEC_TILE - 1) / SPEC_TILE, (ny + SPEC_TILE - 1) / SPEC_TILE), dim3(256), ctx->stream, when, ny, nx,
-                (const double2 *)A, B);
-    });
-    if (rc) return rc;
-    rc = launch(ctx, "spec_rows", [=] { klaunch(k_spec_rows, chunks, dim3(256), ctx->stream, when, ny, logny, cells, (const double2 *)B, twy, A); });
     if (rc) return rc;
     rc = launch(ctx, "xspec_accumulate", [=] {
         klaunch(k_xspec_accumulate, dim3((unsigned)((cells + 255) / 256)), dim3(256), ctx->stream, when, nx, ny, logny, detrend, pair, c1x, c1y,
                 (const double2 *)A, B, acc);
     });
     if (rc) return rc;
-    return launch(ctx, "spec_tick", [=] { klaunch(k_spec_tick, dim3(1), dim3(64), ctx->stream, start, every, state); });
+    return spec_finish(ctx, when);
 }
+
+static size_t xspec_bytes(const fs_xspec *s) { return (size_t)s->planes * s->cells() * sizeof(double); }
 
 int fs_xspec_read(fs_ctx *ctx, fs_xspec *s, double *sums, long long *launches, long long *samples)
 {
     FS_REQUIRE(ctx && s, "null argument");
     FS_HANDLE(s);
     FS_NO_CAPTURE(fs_xspec, "read");
-    long long st[SPEC_STATE];
-    if (int rc = read_counters(ctx, s->d_state, st)) return rc;
-    if (sums) {
-        FS_HIP(hipMemcpyAsync(sums, s->d_acc, (size_t)s->planes * s->nx * s->ny * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        FS_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    if (launches) *launches = st[0];
-    if (samples) *samples = st[1];
-    return FS_OK;
+    return counted_read(ctx, s->d_state, launches, samples, sums != nullptr, dense_copy(ctx, sums, s->d_acc, xspec_bytes(s), hipMemcpyDeviceToHost));
 }
 
-int fs_xspec_plane(fs_ctx *ctx, fs_xspec *s, double *plane)
-{
-    FS_REQUIRE(ctx && s && plane, "null argument");
-    FS_HANDLE(s);
-    FS_NO_CAPTURE(fs_xspec, "plane");
-    FS_HIP(hipSetDevice(ctx->device));
-    FS_HIP(hipMemcpyAsync(plane, s->d_b, (size_t)s->nx * s->ny * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    return FS_OK;
-}
+int fs_xspec_plane(fs_ctx *ctx, fs_xspec *s, double *plane) { return spec_plane(ctx, s, plane); }
 
 int fs_xspec_get(fs_ctx *ctx, fs_xspec *s, double *sums, long long *launches, long long *samples)
 {
@@ -1491,12 +1369,7 @@ int fs_xspec_set(fs_ctx *ctx, fs_xspec *s, const double *sums, long long launche
     FS_HANDLE(s);
     FS_COUNTERS(launches, samples);
     FS_NO_CAPTURE(fs_xspec, "set");
-    FS_HIP(hipSetDevice(ctx->device));
-    const long long st[SPEC_STATE] = {launches, samples};
-    FS_HIP(hipMemcpyAsync(s->d_acc, sums, (size_t)s->planes * s->nx * s->ny * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipMemcpyAsync(s->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
-    return FS_OK;
+    return counted_set(ctx, s->d_state, launches, samples, dense_copy(ctx, s->d_acc, sums, xspec_bytes(s), hipMemcpyHostToDevice));
 }
 
 int fs_xspec_reset(fs_ctx *ctx, fs_xspec *s)
@@ -1504,10 +1377,7 @@ int fs_xspec_reset(fs_ctx *ctx, fs_xspec *s)
     FS_REQUIRE(ctx && s, "null argument");
     FS_HANDLE(s);
     FS_NO_CAPTURE(fs_xspec, "reset");
-    FS_HIP(hipSetDevice(ctx->device));
-    FS_HIP(hipMemsetAsync(s->d_acc, 0, (size_t)s->planes * s->nx * s->ny * sizeof(double), ctx->stream));
-    FS_HIP(hipMemsetAsync(s->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
-    return FS_OK;
+    return counted_reset(ctx, s->d_state, dense_zero(ctx, s->d_acc, xspec_bytes(s)));
 }
 
 int fs_xspec_free(fs_ctx *ctx, fs_xspec *s) { return object_free(ctx, s); }
@@ -1523,8 +1393,7 @@ static void flux_valid(const fs_ctx *ctx, const int *box, int r, int *out)
 int fs_flux_create(fs_ctx *ctx, const int *box, int nr, const int *half_widths, double dx, long long every, long long start, fs_flux **out)
 {
     FS_REQUIRE(ctx && box && half_widths && out, "null argument");
-    FS_REQUIRE(0 <= box[0] && box[0] < box[2] && box[2] <= ctx->X && 0 <= box[1] && box[1] < box[3] && box[3] <= ctx->Y,
-               "flux box must satisfy 0 <= x0 < x1 <= X and 0 <= y0 < y1 <= Y");
+    FS_BOX(box, ctx->X, ctx->Y, "flux box must satisfy 0 <= x0 < x1 <= X and 0 <= y0 < y1 <= Y");
     FS_REQUIRE(1 <= nr && nr <= FLUX_MAX_WIDTHS, "the number of half-widths must be 1 .. FS_FLUX_MAX_WIDTHS");
     for (int k = 0; k < nr; ++k) {
         FS_REQUIRE(1 <= half_widths[k] && half_widths[k] <= FLUX_MAX_R, "a half-width must be 1 .. FS_FLUX_MAX_R");
@@ -1549,18 +1418,8 @@ int fs_flux_create(fs_ctx *ctx, const int *box, int nr, const int *half_widths, 
     s->dx0 = std::max(0, box[0] - d); s->dy0 = std::max(0, box[1] - d);
     s->DW = std::min(ctx->X, box[2] + d) - s->dx0; s->DH = std::min(ctx->Y, box[3] + d) - s->dy0;
     const size_t work = (size_t)FLUX_NQ * s->DW * s->DH * sizeof(double), acc = (size_t)nr * FLUX_SUMS * s->nx * s->ny * sizeof(double);
-    hipError_t e = s->d_state.alloc((SPEC_STATE + 1) * sizeof(long long));
-    if (e == hipSuccess) e = s->d_base.alloc(work);
-    if (e == hipSuccess) e = s->d_rows.alloc(work);
-    if (e == hipSuccess) e = s->d_filt.alloc(work);
-    if (e == hipSuccess) e = s->d_acc.alloc(acc);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_state, 0, (SPEC_STATE + 1) * sizeof(long long), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_base, 0, work, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_rows, 0, work, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_filt, 0, work, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_acc, 0, acc, ctx->stream);
-    const hipError_t es = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = es;
+    const hipError_t e = fill_buffers(ctx, {{s->d_state, (SPEC_STATE + 1) * sizeof(long long)}, {s->d_base, work}, {s->d_rows, work}, {s->d_filt, work},
+                                            {s->d_acc, acc}});
     if (e != hipSuccess) return hip_fail(e, "fs_flux_create", __FILE__, __LINE__);
     *out = adopt(ctx, std::move(s));
     return FS_OK;
@@ -1592,9 +1451,7 @@ int fs_flux_launch(fs_ctx *ctx, fs_flux *s, double limit, const fs_field *v)
     // everything the launches need is in `s` and the field: no allocation, copy or synchronisation here (the closures are captured / taped)
     const FluxGeom f{s->dx0, s->dy0, s->DW, s->DH, s->box[0], s->box[1], s->nx, s->ny};
     const double two_dx = 2.0 * s->dx;
-    const long long every = s->every, start = s->start;
-    long long *state = s->d_state;
-    const SpecWhen when{state, start, every};
+    const SpecWhen when{s->d_state, s->start, s->every};
     const size_t dcells = (size_t)s->DW * s->DH, cells = (size_t)s->nx * s->ny;
     const int X = ctx->X, Y = ctx->Y;
     double *base = s->d_base, *F = s->d_filt;
@@ -1613,23 +1470,17 @@ int fs_flux_launch(fs_ctx *ctx, fs_flux *s, double limit, const fs_field *v)
         });
         if (rc) return rc;
     }
-    return launch(ctx, "spec_tick", [=] { klaunch(k_spec_tick, dim3(1), dim3(64), ctx->stream, start, every, state); });
+    return spec_finish(ctx, when);
 }
+
+static size_t flux_bytes(const fs_flux *s) { return (size_t)s->nr * FLUX_SUMS * s->nx * s->ny * sizeof(double); }
 
 int fs_flux_read(fs_ctx *ctx, fs_flux *s, double *sums, long long *launches, long long *samples)
 {
     FS_REQUIRE(ctx && s, "null argument");
     FS_HANDLE(s);
     FS_NO_CAPTURE(fs_flux, "read");
-    long long st[SPEC_STATE];
-    if (int rc = read_counters(ctx, s->d_state, st)) return rc;
-    if (sums) {
-        FS_HIP(hipMemcpyAsync(sums, s->d_acc, (size_t)s->nr * FLUX_SUMS * s->nx * s->ny * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        FS_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    if (launches) *launches = st[0];
-    if (samples) *samples = st[1];
-    return FS_OK;
+    return counted_read(ctx, s->d_state, launches, samples, sums != nullptr, dense_copy(ctx, sums, s->d_acc, flux_bytes(s), hipMemcpyDeviceToHost));
 }
 
 int fs_flux_filtered(fs_ctx *ctx, fs_flux *s, int width, double *planes)
@@ -1662,12 +1513,7 @@ int fs_flux_set(fs_ctx *ctx, fs_flux *s, const double *sums, long long launches,
     FS_HANDLE(s);
     FS_COUNTERS(launches, samples);
     FS_NO_CAPTURE(fs_flux, "set");
-    FS_HIP(hipSetDevice(ctx->device));
-    const long long st[SPEC_STATE] = {launches, samples};
-    FS_HIP(hipMemcpyAsync(s->d_acc, sums, (size_t)s->nr * FLUX_SUMS * s->nx * s->ny * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipMemcpyAsync(s->d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
-    FS_HIP(hipStreamSynchronize(ctx->stream));      // (both sources are the caller's / this frame's memory)
-    return FS_OK;
+    return counted_set(ctx, s->d_state, launches, samples, dense_copy(ctx, s->d_acc, sums, flux_bytes(s), hipMemcpyHostToDevice));
 }
 
 int fs_flux_reset(fs_ctx *ctx, fs_flux *s)
@@ -1675,10 +1521,7 @@ int fs_flux_reset(fs_ctx *ctx, fs_flux *s)
     FS_REQUIRE(ctx && s, "null argument");
     FS_HANDLE(s);
     FS_NO_CAPTURE(fs_flux, "reset");
-    FS_HIP(hipSetDevice(ctx->device));
-    FS_HIP(hipMemsetAsync(s->d_acc, 0, (size_t)s->nr * FLUX_SUMS * s->nx * s->ny * sizeof(double), ctx->stream));
-    FS_HIP(hipMemsetAsync(s->d_state + 1, 0, sizeof(long long), ctx->stream));      // samples; the launch count runs on
-    return FS_OK;
+    return counted_reset(ctx, s->d_state, dense_zero(ctx, s->d_acc, flux_bytes(s)));
 }
 
 int fs_flux_free(fs_ctx *ctx, fs_flux *s) { return object_free(ctx, s); }
@@ -1702,8 +1545,7 @@ static int flowmap_seed(fs_ctx *ctx, fs_flowmap *fm)
 int fs_flowmap_create(fs_ctx *ctx, const int *box, int refine, fs_flowmap **out)
 {
     FS_REQUIRE(ctx && box && out, "null argument");
-    FS_REQUIRE(0 <= box[0] && box[0] < box[2] && box[2] <= ctx->X && 0 <= box[1] && box[1] < box[3] && box[3] <= ctx->Y,
-               "flow-map box must satisfy 0 <= x0 < x1 <= X and 0 <= y0 < y1 <= Y");
+    FS_BOX(box, ctx->X, ctx->Y, "flow-map box must satisfy 0 <= x0 < x1 <= X and 0 <= y0 < y1 <= Y");
     FS_REQUIRE(refine == 1 || refine == 2 || refine == 4 || refine == 8, "refine must be 1, 2, 4 or 8");
     const long long nx = (long long)refine * (box[2] - box[0]), ny = (long long)refine * (box[3] - box[1]);
     FS_REQUIRE(nx * ny <= (1LL << 30), "flow map of more than 2^30 nodes");
@@ -1718,7 +1560,7 @@ int fs_flowmap_create(fs_ctx *ctx, const int *box, int refine, fs_flowmap **out)
     f->r = refine; f->nx = (int)nx; f->ny = (int)ny;
     for (int k = 0; k < 4; ++k) f->box[k] = box[k];
     const size_t n = (size_t)(nx * ny);
-    hipError_t e = f->d_pos.alloc(3 * n * sizeof(double));
+    hipError_t e = f->d_pos.alloc(3 * n * sizeof(double));      // (no fill_buffers: the seeding launch below writes every node, and nothing waits)
     if (e == hipSuccess) e = f->d_status.alloc(n * sizeof(int));
     if (e != hipSuccess) return hip_fail(e, "fs_flowmap_create", __FILE__, __LINE__);
     if (int rc = flowmap_seed(ctx, f.get())) { hipStreamSynchronize(ctx->stream); return rc; }

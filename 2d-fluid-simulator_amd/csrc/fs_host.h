@@ -276,35 +276,33 @@ struct fs_dist {
     fs::DevBuf<long long> d_state;   // [DIST_STATE]
 };
 
-// energy spectra (fs_spec_*, fs_spec.h): the box, the uploaded tables, the two complex work planes, the power plane and the device counters
-struct fs_spec {
+// what the two spectral riders share (fs_spec.h): the box, the uploaded tables, the two complex work planes, the cadence and the device counters
+namespace fs {
+struct SpecPlan {
     int box[4] = {0, 0, 0, 0};      // x0, y0, x1, y1 (cells)
     int nx = 0, ny = 0;             // the box's sides, powers of two
     int detrend = 0;
     double c1x = 0.0, c1y = 0.0;    // the detrend pair
     long long every = 1, start = 0;
-    fs::DevBuf<double> d_wx, d_wy;   // [nx], [ny]: the windows
-    fs::DevBuf<double> d_twx, d_twy; // [nx], [ny]: N / 2 pairs (cos, -sin) per axis
-    fs::DevBuf<double2> d_a, d_b;    // [nx * ny] each: the work planes; after a sampling launch d_b holds Z', [a][b]
+    DevBuf<double> d_wx, d_wy;       // [nx], [ny]: the windows
+    DevBuf<double> d_twx, d_twy;     // [nx], [ny]: N / 2 pairs (cos, -sin) per axis
+    DevBuf<double2> d_a, d_b;        // [nx * ny] each: the work planes; after a sampling launch d_b holds Z', [a][b]
+    DevBuf<long long> d_state;       // [SPEC_STATE]
+    size_t cells() const { return (size_t)nx * ny; }
+};
+}  // namespace fs
+
+// energy spectra (fs_spec_*, fs_spec.h): a plan and the power plane
+struct fs_spec : fs::SpecPlan {
     fs::DevBuf<double> d_power;      // [nx * ny], [a][b]
-    fs::DevBuf<long long> d_state;   // [SPEC_STATE]
 };
 
-// cross-spectra (fs_xspec_*, fs_xspec.h): fs_spec's box, tables and work planes, the pair of quantities and the accumulator planes
-struct fs_xspec {
-    int box[4] = {0, 0, 0, 0};      // x0, y0, x1, y1 (cells)
-    int nx = 0, ny = 0;             // the box's sides, powers of two
+// cross-spectra (fs_xspec_*, fs_xspec.h): a plan, the pair of quantities and the accumulator planes
+struct fs_xspec : fs::SpecPlan {
     int qa = 0, qb = -1;            // the quantities (fs_dist.h); qb -1: one scalar
     int planes = 1;                 // accumulator planes: XSPEC_PLANES for a pair, 1 for one scalar
-    int detrend = 0;
     double dx = 0.0;
-    double c1x = 0.0, c1y = 0.0;    // the detrend pair
-    long long every = 1, start = 0;
-    fs::DevBuf<double> d_wx, d_wy;   // [nx], [ny]: the windows
-    fs::DevBuf<double> d_twx, d_twy; // [nx], [ny]: N / 2 pairs (cos, -sin) per axis
-    fs::DevBuf<double2> d_a, d_b;    // [nx * ny] each: the work planes; after a sampling launch d_b holds Z', [a][b]
     fs::DevBuf<double> d_acc;        // [planes][nx * ny]: Paa, Pbb, Cre, Cim, each [a][b]
-    fs::DevBuf<long long> d_state;   // [SPEC_STATE]
 };
 
 // scale-to-scale fluxes (fs_flux_*, fs_flux.h): the box, the region D of the work planes, the half-widths, the three sets of eight work planes
@@ -409,6 +407,83 @@ inline int read_counters(fs_ctx *ctx, const long long *d_state, long long (&st)[
     FS_HIP(hipSetDevice(ctx->device));
     FS_HIP(hipMemcpyAsync(st, d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
     FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+
+// the half-open cell box of an entry point: not empty, inside the X x Y grid
+#define FS_BOX(box, X, Y, msg) \
+    FS_REQUIRE(0 <= (box)[0] && (box)[0] < (box)[2] && (box)[2] <= (X) && 0 <= (box)[1] && (box)[1] < (box)[3] && (box)[3] <= (Y), msg)
+
+// One buffer of a create: `bytes` of device memory (0: none, the buffer stays null) filled from the host's `src` or, without one, with the byte `fill`.
+struct Fill {
+    void *buf;
+    hipError_t (*alloc)(void *buf, size_t bytes, void **dev);
+    size_t bytes;
+    const void *src;
+    int fill;
+    template <typename T>
+    Fill(DevBuf<T> &b, size_t bytes, const void *src = nullptr, int fill = 0)
+        : buf(&b), alloc([](void *b, size_t n, void **dev) { auto *d = (DevBuf<T> *)b; const hipError_t e = d->alloc(n); *dev = (void *)d->get(); return e; }),
+          bytes(bytes), src(src), fill(fill) {}
+};
+// The buffers of a create: allocated, their fills queued on the stream, one synchronisation (the sources are the caller's / the frame's memory);
+// -> the first error.  The caller's unique_ptr destroys what a failed create had built.
+inline hipError_t fill_buffers(fs_ctx *ctx, const std::vector<Fill> &list)
+{
+    hipError_t e = hipSuccess;
+    for (const Fill &f : list) {
+        void *dev = nullptr;
+        if (e == hipSuccess && f.bytes) e = f.alloc(f.buf, f.bytes, &dev);
+        if (e == hipSuccess && f.bytes)
+            e = f.src ? hipMemcpyAsync(dev, f.src, f.bytes, hipMemcpyHostToDevice, ctx->stream) : hipMemsetAsync(dev, f.fill, f.bytes, ctx->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? es : e;
+}
+
+// ---- an accumulator's payload behind its counters {launches, samples}: read, set and reset.  `copy` / `zero` queue the payload's transfer on the
+// stream and return an FS_* code: dense_copy / dense_zero, or a call of their own.  The argument checks stay with the entry points. ----------------
+inline auto dense_copy(fs_ctx *ctx, void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
+{
+    return [=]() -> int { FS_HIP(hipMemcpyAsync(dst, src, bytes, kind, ctx->stream)); return FS_OK; };
+}
+inline auto dense_zero(fs_ctx *ctx, void *dst, size_t bytes)
+{
+    return [=]() -> int { FS_HIP(hipMemsetAsync(dst, 0, bytes, ctx->stream)); return FS_OK; };
+}
+// the counters, and with `payload` what `copy` downloads
+template <typename F>
+inline int counted_read(fs_ctx *ctx, const long long *d_state, long long *launches, long long *samples, bool payload, F copy)
+{
+    long long st[2];
+    if (int rc = read_counters(ctx, d_state, st)) return rc;
+    if (payload) {
+        if (int rc = copy()) return rc;
+        FS_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    if (launches) *launches = st[0];
+    if (samples) *samples = st[1];
+    return FS_OK;
+}
+// what `copy` uploads, then the counters; synchronised: the sources are the caller's / this frame's memory
+template <typename F>
+inline int counted_set(fs_ctx *ctx, long long *d_state, long long launches, long long samples, F copy)
+{
+    FS_HIP(hipSetDevice(ctx->device));
+    const long long st[2] = {launches, samples};
+    if (int rc = copy()) return rc;
+    FS_HIP(hipMemcpyAsync(d_state, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    return FS_OK;
+}
+// what `zero` clears, and the samples; the launch count runs on.  Queued only, unless `sync`: for a `zero` that also copied from its caller's frame
+template <typename F>
+inline int counted_reset(fs_ctx *ctx, long long *d_state, F zero, bool sync = false)
+{
+    FS_HIP(hipSetDevice(ctx->device));
+    if (int rc = zero()) return rc;
+    FS_HIP(hipMemsetAsync(d_state + 1, 0, sizeof(long long), ctx->stream));
+    if (sync) FS_HIP(hipStreamSynchronize(ctx->stream));
     return FS_OK;
 }
 

@@ -36,19 +36,13 @@ int fs_tracer_create(fs_ctx *ctx, int n, const double *seeds_xy, int respawn, in
         pos[k] = pos[2 * (size_t)n + k] = x;
         pos[(size_t)n + k] = pos[3 * (size_t)n + k] = y;
     }
-    std::vector<int> ident((size_t)n);
-    for (int k = 0; k < n; ++k) ident[k] = k;
+    std::vector<int> ints(4 * (size_t)n);      // age, status, respawns 0; id the identity (with the set: a graph captured before the first sort stays valid)
+    for (int k = 0; k < n; ++k) ints[3 * (size_t)n + k] = k;
     FS_HIP(hipSetDevice(ctx->device));
     auto t = std::make_unique<fs_tracer>();
     t->n = n; t->respawn = respawn ? 1 : 0; t->max_age = max_age;
-    hipError_t e = t->d_pos.alloc(pos.size() * sizeof(double));
-    if (e == hipSuccess) e = t->d_int.alloc(4 * (size_t)n * sizeof(int));      // (id with the set: a graph captured before the first sort stays valid)
-    if (e == hipSuccess) e = t->d_count.alloc(sizeof(long long));
-    if (e == hipSuccess) e = hipMemcpyAsync(t->d_pos, pos.data(), pos.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->d_int, 0, 3 * (size_t)n * sizeof(int), ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(t->d_int + 3 * (size_t)n, ident.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->d_count, 0, sizeof(long long), ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // (the source is this frame's memory)
+    const hipError_t e = fill_buffers(ctx, {{t->d_pos, pos.size() * sizeof(double), pos.data()}, {t->d_int, ints.size() * sizeof(int), ints.data()},
+                                            {t->d_count, sizeof(long long)}});
     if (e != hipSuccess) return hip_fail(e, "fs_tracer_create", __FILE__, __LINE__);
     *out = adopt(ctx, std::move(t));
     return FS_OK;
@@ -316,11 +310,7 @@ int fs_tracer_create_inertial(fs_ctx *ctx, int n, const double *seeds_xy, const 
     std::vector<double> vel(4 * N, 0.0);
     std::copy(alpha, alpha + N, vel.begin() + 2 * N);
     std::copy(tau, tau + N, vel.begin() + 3 * N);
-    hipError_t e = t->d_vel.alloc(vel.size() * sizeof(double));
-    if (e == hipSuccess && deposits) e = t->d_dep.alloc(cells * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpyAsync(t->d_vel, vel.data(), vel.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && deposits) e = hipMemsetAsync(t->d_dep, 0, cells * sizeof(int), ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // (the source is this frame's memory)
+    const hipError_t e = fill_buffers(ctx, {{t->d_vel, vel.size() * sizeof(double), vel.data()}, {t->d_dep, deposits ? cells * sizeof(int) : 0}});
     if (e != hipSuccess) { object_free(ctx, t); return hip_fail(e, "fs_tracer_create_inertial", __FILE__, __LINE__); }
     t->inertial = true; t->gx = gx; t->gy = gy;
     t->h_resp.assign(vel.begin() + 2 * N, vel.end());
@@ -411,10 +401,7 @@ int fs_tracer_accum_create(fs_ctx *ctx, fs_tracer *t, long long every, long long
     if (t->d_acc) { set_error("the tracer set has an accumulator already: fs_tracer_accum_free first"); return FS_ERR_STATE; }
     FS_HIP(hipSetDevice(ctx->device));
     const size_t cells = (size_t)ctx->X * ctx->Y;
-    hipError_t e = t->d_acc.alloc(2 * cells * sizeof(unsigned long long));
-    if (e == hipSuccess) e = t->d_acc_state.alloc(2 * sizeof(long long));
-    if (e == hipSuccess) e = hipMemsetAsync(t->d_acc, 0, 2 * cells * sizeof(unsigned long long), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->d_acc_state, 0, 2 * sizeof(long long), ctx->stream);
+    hipError_t e = fill_buffers(ctx, {{t->d_acc, 2 * cells * sizeof(unsigned long long)}, {t->d_acc_state, 2 * sizeof(long long)}});
     if (e == hipSuccess) e = hipMemcpyAsync(t->d_acc_state, t->d_count, sizeof(long long), hipMemcpyDeviceToDevice, ctx->stream);      // base
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { t->d_acc.reset(); t->d_acc_state.reset(); return hip_fail(e, "fs_tracer_accum_create", __FILE__, __LINE__); }
@@ -485,11 +472,8 @@ int fs_tracer_accum_reset(fs_ctx *ctx, fs_tracer *t)
     FS_HANDLE(t);
     FS_TRACER_ACCUM(t);
     FS_NO_CAPTURE(fs_tracer, "accum_reset");
-    FS_HIP(hipSetDevice(ctx->device));
-    FS_HIP(hipMemsetAsync(t->d_acc, 0, 2 * (size_t)ctx->X * ctx->Y * sizeof(unsigned long long), ctx->stream));
-    FS_HIP(hipMemsetAsync(t->d_acc_state + 1, 0, sizeof(long long), ctx->stream));      // (the base stays: the phase runs on)
-    FS_HIP(hipStreamSynchronize(ctx->stream));
-    return FS_OK;
+    // (the base stays: the phase runs on; this reset returns with the stream idle)
+    return counted_reset(ctx, t->d_acc_state, dense_zero(ctx, t->d_acc, 2 * (size_t)ctx->X * ctx->Y * sizeof(unsigned long long)), true);
 }
 
 int fs_tracer_accum_free(fs_ctx *ctx, fs_tracer *t)

@@ -160,13 +160,29 @@ class RideOps:
         if getattr(self, "capturing", False):
             raise _lib.FsError(message)
 
-    def _single_gpu_only(self):
+    def _single_context(self, what, why):
+        """Refuse on slabs what only a single context does: FsError "`what` a single-GPU context: on slabs `why` (not implemented)"."""
         if self.nranks > 1:
-            raise _lib.FsError("tracer particles need a single-GPU context: on slabs they would have to migrate between ranks (not implemented)")
+            raise _lib.FsError(f"{what} a single-GPU context: on slabs {why} (not implemented)")
 
     def _tracer_host_call(self, what):
         RideOps._host_only(self, f"{what} during a graph capture")
-        RideOps._single_gpu_only(self)
+        RideOps._single_context(self, "tracer particles need", "they would have to migrate between ranks")
+
+    def _cell_box(self, box):
+        """(x0, y0, x1, y1) in global cells, half-open, inside the grid -> the tuple of ints (ValueError)."""
+        box = tuple(int(b) for b in box)
+        if len(box) != 4 or not (0 <= box[0] < box[2] <= self.nx and 0 <= box[1] < box[3] <= self.ny):
+            raise ValueError(f"box must be (x0, y0, x1, y1) with 0 <= x0 < x1 <= {self.nx} and 0 <= y0 < y1 <= {self.ny}, got {box}")
+        return box
+
+    def _overwritten(self, *fields):
+        """What a launch that stored every owned cell of `fields` leaves: nothing owed, on slabs stale ghost rows, a new identity."""
+        for f in fields:
+            f.pending_limit = f.pending_clamp = None
+            f.valid = 0 if self.nranks > 1 else self.halo
+            f.user_data = True
+            f.static_id = next(_serials)
 
     def _ride(self, name, args=None):
         """A rider's launch behind the step.  Not a _run: no flush, no exchange, no ghost row, writes no field - in a logged period a kernel
@@ -427,13 +443,8 @@ class RideOps:
         0, in the fields' precision.  Owned rows only: on slabs the targets' ghost rows are stale afterwards (valid = 0), and whatever reads
         them exchanges first.  Not allowed during a graph capture."""
         self._host_only("mean_finalize during a graph capture")
-        for f in (v_out, p_out):
-            f.pending_limit = f.pending_clamp = None      # (every owned cell is overwritten)
         self._p_mean_finalize(mean._h, v_out._h, p_out._h)
-        for f in (v_out, p_out):
-            f.valid = 0 if self.nranks > 1 else self.halo
-            f.user_data = True
-            f.static_id = next(_serials)
+        self._overwritten(v_out, p_out)
 
     def mean_free(self, mean):
         self._release(mean, self._p_mean_free)
@@ -519,13 +530,8 @@ class RideOps:
         weights = np.ascontiguousarray(weights, np.float64)
         if weights.shape != (3, 1 + 2 * modes.nfreq):
             raise ValueError(f"expected weights of shape {(3, 1 + 2 * modes.nfreq)}, got {weights.shape}")
-        for f in (v_out, p_out):
-            f.pending_limit = f.pending_clamp = None      # (every owned cell is overwritten)
         self._p_modes_combine(modes._h, weights, v_out._h, p_out._h)
-        for f in (v_out, p_out):
-            f.valid = 0 if self.nranks > 1 else self.halo
-            f.user_data = True
-            f.static_id = next(_serials)
+        self._overwritten(v_out, p_out)
 
     def modes_rows(self, nfreq):
         """{"accumulate", "combine"}: the rows per workgroup the next launches take on this context (fs_modes_rows; FS_DIAG_WGS moves them)."""
@@ -543,8 +549,7 @@ class RideOps:
         (n + 1 - start) % every == 0.  Single-context grids only (FsError on a slab: the Gram matrix would need a rank-ordered reduction of
         per-rank matrices); not allowed during a graph capture."""
         RideOps._host_only(self, "pod_create during a graph capture")      # (through the class, as the tracer calls: the tests ask objects that are no devices)
-        if self.nranks > 1:
-            raise _lib.FsError("snapshot POD needs a single-GPU context: on slabs the Gram matrix needs a rank-ordered reduction (not implemented)")
+        RideOps._single_context(self, "snapshot POD needs", "the Gram matrix needs a rank-ordered reduction")
         slots = int(slots)
         if not 2 <= slots <= self.POD_MAX:
             raise ValueError(f"snapshots must be 2 .. {self.POD_MAX}, got {slots}")
@@ -579,13 +584,8 @@ class RideOps:
         weights = np.ascontiguousarray(weights, np.float64)
         if weights.shape != (pod.slots,):
             raise ValueError(f"expected weights of shape {(pod.slots,)}, got {weights.shape}")
-        for f in (v_out, p_out):
-            f.pending_limit = f.pending_clamp = None      # (every owned cell is overwritten)
         self._p_pod_combine(pod._h, weights, v_out._h, p_out._h)
-        for f in (v_out, p_out):
-            f.valid = 0 if self.nranks > 1 else self.halo
-            f.user_data = True
-            f.static_id = next(_serials)
+        self._overwritten(v_out, p_out)
 
     def pod_get(self, pod):
         """-> (slots (M, 3, X, Y) in the fields' dtype: u, w, p of every slot; launches, samples) - the whole ring, for checkpoints."""
@@ -617,8 +617,7 @@ class RideOps:
 
     def _vortex_host_call(self, what):
         RideOps._host_only(self, f"{what} during a graph capture")
-        if self.nranks > 1:
-            raise _lib.FsError("vortex identification needs a single-GPU context: on slabs the components would have to be united across ranks (not implemented)")
+        RideOps._single_context(self, "vortex identification needs", "the components would have to be united across ranks")
 
     def _vortex_criterion(self, criterion):
         if criterion not in self.VORTEX_CRITERIA:
@@ -692,8 +691,7 @@ class RideOps:
 
     def _dist_host_call(self, what):
         RideOps._host_only(self, f"{what} during a graph capture")
-        if self.nranks > 1:
-            raise _lib.FsError("field distributions need a single-GPU context: on slabs the tables would have to be added across ranks (not implemented)")
+        RideOps._single_context(self, "field distributions need", "the tables would have to be added across ranks")
 
     def _dist_quantity(self, quantity):
         if quantity not in RideOps.DIST_QUANTITIES:
@@ -701,12 +699,7 @@ class RideOps:
         return RideOps.DIST_QUANTITIES.index(quantity)
 
     def _dist_box(self, box):
-        if box is None:
-            return (0, 0, self.nx, self.ny)
-        box = tuple(int(b) for b in box)
-        if len(box) != 4 or not (0 <= box[0] < box[2] <= self.nx and 0 <= box[1] < box[3] <= self.ny):
-            raise ValueError(f"box must be (x0, y0, x1, y1) with 0 <= x0 < x1 <= {self.nx} and 0 <= y0 < y1 <= {self.ny}, got {box}")
-        return box
+        return (0, 0, self.nx, self.ny) if box is None else RideOps._cell_box(self, box)
 
     def _dist_side(self, spec):
         q = RideOps._dist_quantity(self, spec.get("quantity"))
@@ -812,18 +805,12 @@ class RideOps:
 
     def _spec_host_call(self, what):
         RideOps._host_only(self, f"{what} during a graph capture")
-        if self.nranks > 1:
-            raise _lib.FsError("energy spectra need a single-GPU context: on slabs the transform along y crosses the ranks (not implemented)")
+        RideOps._single_context(self, "energy spectra need", "the transform along y crosses the ranks")
 
     def spec_box(self, box):
         """(x0, y0, x1, y1) in global cells, half-open, inside the grid, both sides powers of two in SPEC_MIN_N .. SPEC_MAX_N -> the tuple
         of ints (ValueError)."""
-        try:
-            box = tuple(int(b) for b in box)
-        except TypeError:
-            raise ValueError(f"box must be (x0, y0, x1, y1), got {box!r}") from None
-        if len(box) != 4 or not (0 <= box[0] < box[2] <= self.nx and 0 <= box[1] < box[3] <= self.ny):
-            raise ValueError(f"box must be (x0, y0, x1, y1) with 0 <= x0 < x1 <= {self.nx} and 0 <= y0 < y1 <= {self.ny}, got {box}")
+        box = RideOps.flux_box(self, box)
         for n in (box[2] - box[0], box[3] - box[1]):
             if n & (n - 1) or not RideOps.SPEC_MIN_N <= n <= RideOps.SPEC_MAX_N:
                 raise ValueError(f"the sides of a spectrum box must be powers of two in {RideOps.SPEC_MIN_N} .. {RideOps.SPEC_MAX_N}, "
@@ -921,8 +908,7 @@ class RideOps:
         if not (math.isfinite(dx) and dx > 0.0):
             raise ValueError(f"dx must be finite and > 0, got {dx}")
         RideOps._host_only(self, "xspec_create during a graph capture")
-        if self.nranks > 1:
-            raise _lib.FsError("cross-spectra need a single-GPU context: on slabs the transform along y crosses the ranks (not implemented)")
+        RideOps._single_context(self, "cross-spectra need", "the transform along y crosses the ranks")
         h = self._p_xspec_create(box, qa, qb, dx, *tabs, c1x, c1y, bool(detrend), every, start)
         return self._adopt(h, XSpec(h, box, qa, qb, dx, detrend, every, start))
 
@@ -974,12 +960,9 @@ class RideOps:
     def flux_box(self, box):
         """(x0, y0, x1, y1) in global cells, half-open, inside the grid -> the tuple of ints (ValueError)."""
         try:
-            box = tuple(int(b) for b in box)
-        except TypeError:
+            return RideOps._cell_box(self, box)
+        except TypeError:      # (what is no sequence of numbers; the distributions let this one through)
             raise ValueError(f"box must be (x0, y0, x1, y1), got {box!r}") from None
-        if len(box) != 4 or not (0 <= box[0] < box[2] <= self.nx and 0 <= box[1] < box[3] <= self.ny):
-            raise ValueError(f"box must be (x0, y0, x1, y1) with 0 <= x0 < x1 <= {self.nx} and 0 <= y0 < y1 <= {self.ny}, got {box}")
-        return box
 
     def flux_valid(self, box, r):
         """The valid cells of half-width r inside the box, (x0, y0, x1, y1) half-open: r + 1 <= i <= X - 2 - r, r + 1 <= j <= Y - 2 - r."""
@@ -1019,8 +1002,7 @@ class RideOps:
             raise ValueError(f"dx must be finite and > 0, got {dx}")
         every, start = RideOps._check_cadence(every, start)
         RideOps._host_only(self, "flux_create during a graph capture")
-        if self.nranks > 1:
-            raise _lib.FsError("scale fluxes need a single-GPU context: on slabs the filter along y crosses the ranks (not implemented)")
+        RideOps._single_context(self, "scale fluxes need", "the filter along y crosses the ranks")
         h = self._p_flux_create(box, hw, dx, every, start)
         return self._adopt(h, Flux(h, box, hw, dx, every, start))
 
@@ -1082,8 +1064,7 @@ class RideOps:
         node.  Single-context grids only (FsError on a slab); not allowed during a graph capture."""
         from .lcs import check_lattice
         RideOps._host_only(self, "flowmap_create during a graph capture")
-        if self.nranks > 1:
-            raise _lib.FsError("flow maps need a single-GPU context: on slabs the particles would have to migrate between ranks (not implemented)")
+        RideOps._single_context(self, "flow maps need", "the particles would have to migrate between ranks")
         box, refine, _ = check_lattice(box, refine, 1, (self.nx, self.ny))
         h = self._p_flowmap_create(box, refine)
         return self._adopt(h, FlowMap(h, box, refine))
@@ -1331,8 +1312,35 @@ class _DistSpec(ctypes.Structure):
                 ("lo", ctypes.c_double), ("hi", ctypes.c_double), ("lo_b", ctypes.c_double), ("hi_b", ctypes.c_double)]
 
 
+def _freer(symbol):
+    """A `_p_*_free`: the library's free of a handle, unless the context is gone already."""
+    def free(self, h):
+        if self._ctx is not None:
+            _lib.call(symbol, self._ctx, h)
+    return free
+
+
+def _caller(symbol):
+    """A primitive that hands the context, the handle and its arguments to the library and returns nothing."""
+    def call(self, h, *args):
+        _lib.call(symbol, self._ctx, h, *args)
+    return call
+
+
+def _counted_reader(symbol, optional=False):
+    """A `_p_*_read` / `_p_*_get` -> (payload float64 (words,), launches, samples); optional: words == 0 asks for the counters alone."""
+    def read(self, h, words):
+        out = np.empty(words, np.float64)
+        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
+        _lib.call(symbol, self._ctx, h, None if optional and not words else out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                  ctypes.byref(launches), ctypes.byref(samples))
+        return out, launches.value, samples.value
+    return read
+
+
 class NativeRideOps:
-    """The primitives of RideOps on libfs_hip.so (self._ctx: the library's context)."""
+    """The primitives of RideOps on libfs_hip.so (self._ctx: the library's context).  Those that differ only in the symbol they call come
+    from _freer, _caller and _counted_reader."""
 
     def _p_flow_stats(self, dx, vh, ph, box):
         out = (ctypes.c_double * len(self.STAT_SLOTS))()
@@ -1353,9 +1361,7 @@ class NativeRideOps:
                   ctypes.byref(launches), ctypes.byref(dropped))
         return out[:n.value], launches.value, dropped.value
 
-    def _p_history_free(self, h):
-        if self._ctx is not None:
-            _lib.call("fs_history_free", self._ctx, h)
+    _p_history_free = _freer("fs_history_free")
 
     def _p_loads_create(self, faces, centre, capacity, every, start):
         h = ctypes.c_void_p()
@@ -1380,12 +1386,8 @@ class NativeRideOps:
         a = np.ascontiguousarray(sums, np.float64)
         _lib.call("fs_loads_sums_write", self._ctx, h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), launches, samples)
 
-    def _p_loads_reset(self, h):
-        _lib.call("fs_loads_reset", self._ctx, h)
-
-    def _p_loads_free(self, h):
-        if self._ctx is not None:
-            _lib.call("fs_loads_free", self._ctx, h)
+    _p_loads_reset = _caller("fs_loads_reset")
+    _p_loads_free = _freer("fs_loads_free")
 
     def _p_mean_create(self, every, start):
         h = ctypes.c_void_p()
@@ -1402,15 +1404,9 @@ class NativeRideOps:
         a = np.ascontiguousarray(sums.transpose(0, 2, 1), np.float64)
         _lib.call("fs_mean_write", self._ctx, h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), launches, samples)
 
-    def _p_mean_reset(self, h):
-        _lib.call("fs_mean_reset", self._ctx, h)
-
-    def _p_mean_finalize(self, h, vh, ph):
-        _lib.call("fs_mean_finalize", self._ctx, h, vh, ph)
-
-    def _p_mean_free(self, h):
-        if self._ctx is not None:
-            _lib.call("fs_mean_free", self._ctx, h)
+    _p_mean_reset = _caller("fs_mean_reset")
+    _p_mean_finalize = _caller("fs_mean_finalize")      # (h, vh, ph)
+    _p_mean_free = _freer("fs_mean_free")
 
     def _p_modes_create(self, cos_sin, every, start):
         h = ctypes.c_void_p()
@@ -1430,8 +1426,7 @@ class NativeRideOps:
         dp = lambda x: x.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         _lib.call("fs_modes_write", self._ctx, h, dp(a), dp(scalars), launches, samples)
 
-    def _p_modes_reset(self, h):
-        _lib.call("fs_modes_reset", self._ctx, h)
+    _p_modes_reset = _caller("fs_modes_reset")
 
     def _p_modes_combine(self, h, weights, vh, ph):
         _lib.call("fs_modes_combine", self._ctx, h, weights.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), vh, ph)
@@ -1441,9 +1436,7 @@ class NativeRideOps:
         _lib.call("fs_modes_rows", self._ctx, nfreq, ctypes.byref(a), ctypes.byref(c))
         return a.value, c.value
 
-    def _p_modes_free(self, h):
-        if self._ctx is not None:
-            _lib.call("fs_modes_free", self._ctx, h)
+    _p_modes_free = _freer("fs_modes_free")
 
     def _p_pod_create(self, slots, every, start):
         h = ctypes.c_void_p()
@@ -1474,12 +1467,8 @@ class NativeRideOps:
         a = np.ascontiguousarray(slots.transpose(0, 1, 3, 2), self.dtype)
         _lib.call("fs_pod_set", self._ctx, h, a.ctypes.data_as(ctypes.c_void_p), launches, samples)
 
-    def _p_pod_reset(self, h):
-        _lib.call("fs_pod_reset", self._ctx, h)
-
-    def _p_pod_free(self, h):
-        if self._ctx is not None:
-            _lib.call("fs_pod_free", self._ctx, h)
+    _p_pod_reset = _caller("fs_pod_reset")
+    _p_pod_free = _freer("fs_pod_free")
 
     def _p_vortex_create(self, which, threshold, exponent, every, start, min_area, max_vortices, max_components, capacity):
         h = ctypes.c_void_p()
@@ -1500,8 +1489,7 @@ class NativeRideOps:
                   labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
         return np.ascontiguousarray(flags.T), np.ascontiguousarray(labels.T)
 
-    def _p_vortex_set(self, h, launches):
-        _lib.call("fs_vortex_set", self._ctx, h, launches)
+    _p_vortex_set = _caller("fs_vortex_set")      # (h, launches)
 
     def _p_vortex_label(self, flags):
         f = np.ascontiguousarray(flags.T)
@@ -1514,9 +1502,7 @@ class NativeRideOps:
         _lib.call("fs_vortex_criterion", self._ctx, which, limit, dx, vh, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
         return np.ascontiguousarray(out.T)
 
-    def _p_vortex_free(self, h):
-        if self._ctx is not None:
-            _lib.call("fs_vortex_free", self._ctx, h)
+    _p_vortex_free = _freer("fs_vortex_free")
 
     def _p_dist_create(self, chans, every, start):
         h = ctypes.c_void_p()
@@ -1544,12 +1530,8 @@ class NativeRideOps:
     def _p_dist_set(self, h, words, launches, samples):
         _lib.call("fs_dist_set", self._ctx, h, words.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), launches, samples)
 
-    def _p_dist_reset(self, h):
-        _lib.call("fs_dist_reset", self._ctx, h)
-
-    def _p_dist_free(self, h):
-        if self._ctx is not None:
-            _lib.call("fs_dist_free", self._ctx, h)
+    _p_dist_reset = _caller("fs_dist_reset")
+    _p_dist_free = _freer("fs_dist_free")
 
     def _p_dist_select(self, q, box, limit, dx, vh, ph, ranks):
         r = (ctypes.c_longlong * max(1, len(ranks)))(*ranks)
@@ -1571,33 +1553,20 @@ class NativeRideOps:
                   ctypes.byref(h))
         return h
 
-    def _p_spec_read(self, h, cells):
-        plane = np.empty(cells, np.float64)
-        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
-        _lib.call("fs_spec_read", self._ctx, h, plane.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if cells else None, ctypes.byref(launches),
-                  ctypes.byref(samples))
-        return plane, launches.value, samples.value
+    _p_spec_read = _counted_reader("fs_spec_read", optional=True)      # (h, cells)
 
     def _p_spec_plane(self, h, cells):
         out = np.empty(2 * cells, np.float64)
         _lib.call("fs_spec_plane", self._ctx, h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
         return out
 
-    def _p_spec_get(self, h, cells):
-        plane = np.empty(cells, np.float64)
-        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
-        _lib.call("fs_spec_get", self._ctx, h, plane.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(launches), ctypes.byref(samples))
-        return plane, launches.value, samples.value
+    _p_spec_get = _counted_reader("fs_spec_get")
 
     def _p_spec_set(self, h, power, launches, samples):
         _lib.call("fs_spec_set", self._ctx, h, power.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), launches, samples)
 
-    def _p_spec_reset(self, h):
-        _lib.call("fs_spec_reset", self._ctx, h)
-
-    def _p_spec_free(self, h):
-        if self._ctx is not None:
-            _lib.call("fs_spec_free", self._ctx, h)
+    _p_spec_reset = _caller("fs_spec_reset")
+    _p_spec_free = _freer("fs_spec_free")
 
     def _p_xspec_create(self, box, qa, qb, dx, wx, wy, twx, twy, c1x, c1y, detrend, every, start):
         h = ctypes.c_void_p()
@@ -1606,33 +1575,20 @@ class NativeRideOps:
                   every, start, ctypes.byref(h))
         return h
 
-    def _p_xspec_read(self, h, words):
-        planes = np.empty(words, np.float64)
-        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
-        _lib.call("fs_xspec_read", self._ctx, h, planes.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if words else None, ctypes.byref(launches),
-                  ctypes.byref(samples))
-        return planes, launches.value, samples.value
+    _p_xspec_read = _counted_reader("fs_xspec_read", optional=True)      # (h, words)
 
     def _p_xspec_plane(self, h, cells):
         out = np.empty(2 * cells, np.float64)
         _lib.call("fs_xspec_plane", self._ctx, h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
         return out
 
-    def _p_xspec_get(self, h, words):
-        planes = np.empty(words, np.float64)
-        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
-        _lib.call("fs_xspec_get", self._ctx, h, planes.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(launches), ctypes.byref(samples))
-        return planes, launches.value, samples.value
+    _p_xspec_get = _counted_reader("fs_xspec_get")
 
     def _p_xspec_set(self, h, sums, launches, samples):
         _lib.call("fs_xspec_set", self._ctx, h, sums.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), launches, samples)
 
-    def _p_xspec_reset(self, h):
-        _lib.call("fs_xspec_reset", self._ctx, h)
-
-    def _p_xspec_free(self, h):
-        if self._ctx is not None:
-            _lib.call("fs_xspec_free", self._ctx, h)
+    _p_xspec_reset = _caller("fs_xspec_reset")
+    _p_xspec_free = _freer("fs_xspec_free")
 
     def _p_flux_create(self, box, half_widths, dx, every, start):
         h = ctypes.c_void_p()
@@ -1640,44 +1596,28 @@ class NativeRideOps:
                   start, ctypes.byref(h))
         return h
 
-    def _p_flux_read(self, h, words):
-        flat = np.empty(words, np.float64)
-        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
-        _lib.call("fs_flux_read", self._ctx, h, flat.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if words else None, ctypes.byref(launches),
-                  ctypes.byref(samples))
-        return flat, launches.value, samples.value
+    _p_flux_read = _counted_reader("fs_flux_read", optional=True)      # (h, words)
 
     def _p_flux_filtered(self, h, index, words):
         out = np.empty(words, np.float64)
         _lib.call("fs_flux_filtered", self._ctx, h, index, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
         return out
 
-    def _p_flux_get(self, h, words):
-        flat = np.empty(words, np.float64)
-        launches, samples = ctypes.c_longlong(), ctypes.c_longlong()
-        _lib.call("fs_flux_get", self._ctx, h, flat.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(launches), ctypes.byref(samples))
-        return flat, launches.value, samples.value
+    _p_flux_get = _counted_reader("fs_flux_get")
 
     def _p_flux_set(self, h, flat, launches, samples):
         _lib.call("fs_flux_set", self._ctx, h, flat.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), launches, samples)
 
-    def _p_flux_reset(self, h):
-        _lib.call("fs_flux_reset", self._ctx, h)
-
-    def _p_flux_free(self, h):
-        if self._ctx is not None:
-            _lib.call("fs_flux_free", self._ctx, h)
+    _p_flux_reset = _caller("fs_flux_reset")
+    _p_flux_free = _freer("fs_flux_free")
 
     def _p_flowmap_create(self, box, refine):
         h = ctypes.c_void_p()
         _lib.call("fs_flowmap_create", self._ctx, (ctypes.c_int * 4)(*box), refine, ctypes.byref(h))
         return h
 
-    def _p_flowmap_advance(self, h, pod_h, slot_from, slot_to, step, substeps):
-        _lib.call("fs_flowmap_advance", self._ctx, h, pod_h, slot_from, slot_to, step, substeps)
-
-    def _p_flowmap_cauchy_green(self, h):
-        _lib.call("fs_flowmap_cauchy_green", self._ctx, h)
+    _p_flowmap_advance = _caller("fs_flowmap_advance")      # (h, pod_h, slot_from, slot_to, step, substeps)
+    _p_flowmap_cauchy_green = _caller("fs_flowmap_cauchy_green")
 
     def _p_flowmap_get(self, h, shape):
         nx, ny = shape
@@ -1687,12 +1627,8 @@ class NativeRideOps:
         _lib.call("fs_flowmap_get", self._ctx, h, dp(x), dp(y), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), dp(lam))
         return tuple(np.ascontiguousarray(a.T) for a in (x, y, status, lam))
 
-    def _p_flowmap_reset(self, h):
-        _lib.call("fs_flowmap_reset", self._ctx, h)
-
-    def _p_flowmap_free(self, h):
-        if self._ctx is not None:
-            _lib.call("fs_flowmap_free", self._ctx, h)
+    _p_flowmap_reset = _caller("fs_flowmap_reset")
+    _p_flowmap_free = _freer("fs_flowmap_free")
 
     def _p_tracer_create(self, seeds, respawn, max_age):
         h = ctypes.c_void_p()
@@ -1714,8 +1650,7 @@ class NativeRideOps:
         _lib.call("fs_tracer_write", self._ctx, h, pos.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                   ints.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), launches)
 
-    def _p_tracer_sort(self, h):
-        _lib.call("fs_tracer_sort", self._ctx, h)
+    _p_tracer_sort = _caller("fs_tracer_sort")
 
     def _p_tracer_order(self, h, n):
         ids = np.empty(n, np.int32)
@@ -1728,9 +1663,7 @@ class NativeRideOps:
                   age.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)))
         return np.ascontiguousarray(count.T), np.ascontiguousarray(age.T)
 
-    def _p_tracer_free(self, h):
-        if self._ctx is not None:
-            _lib.call("fs_tracer_free", self._ctx, h)
+    _p_tracer_free = _freer("fs_tracer_free")
 
     def _p_tracer_create_inertial(self, seeds, alpha, tau, gravity, respawn, max_age, deposits):
         h = ctypes.c_void_p()
