@@ -1,6 +1,6 @@
 // fs_diag.hip - C-ABI entry points of what reads the flow without changing it: the flow diagnostics (fs_stats.h), the per-step history ring
 // (fs_history.h), the body surface loads (fs_loads.h), the time averages (fs_mean.h), the harmonic modes (fs_modes.h), the snapshot POD
-// (fs_pod.h), the flow maps through its snapshots (fs_lcs.h), the vortex identification (fs_vortex.h), the field distributions (fs_dist.h), the energy spectra (fs_spec.h), the cross-spectra (fs_xspec.h) and the scale-to-scale fluxes (fs_flux.h).  Their objects live in the context's
+// (fs_pod.h), the flow maps through its snapshots (fs_lcs.h), the vortex identification (fs_vortex.h), the field distributions (fs_dist.h), the energy spectra (fs_spec.h), the cross-spectra (fs_xspec.h), the scale-to-scale fluxes (fs_flux.h) and the kinetic-energy budget (fs_budget.h).  Their objects live in the context's
 // registry (fs_host.h: FS_OBJECT, FS_HANDLE, FS_NO_CAPTURE, object_free).  What the accumulators share on the host is there as well: fill_buffers
 // builds every object, counted_read / counted_set / counted_reset move a payload behind its counters, FS_BOX checks a cell box, and the two
 // spectral riders are one SpecPlan each (spec_plan_create, spec_forward, spec_finish below).  An entry point keeps its own argument checks, in its
@@ -17,6 +17,7 @@
 #include "fs_spec.h"
 #include "fs_xspec.h"
 #include "fs_flux.h"
+#include "fs_budget.h"
 
 static_assert(fs::STATS_N == FS_FLOW_NSTAT, "fs_stats.h and include/fs_hip.h disagree on the slots");
 static_assert(fs::LOADS_REC == FS_LOADS_NREC && fs::LOADS_SUMS == FS_LOADS_NSUM, "fs_loads.h and include/fs_hip.h disagree on the record / the sums");
@@ -36,6 +37,7 @@ static_assert(fs::SPEC_MIN_N == FS_SPEC_MIN_N && fs::SPEC_MAX_N == FS_SPEC_MAX_N
 static_assert(fs::XSPEC_PLANES == FS_XSPEC_NPLANE && fs::XSPEC_NQ == fs::DIST_NQ, "fs_xspec.h, fs_dist.h and include/fs_hip.h disagree");
 static_assert(fs::FLUX_NQ == FS_FLUX_NQ && fs::FLUX_SUMS == FS_FLUX_NSUM && fs::FLUX_MAX_WIDTHS == FS_FLUX_MAX_WIDTHS && fs::FLUX_MAX_R == FS_FLUX_MAX_R,
               "fs_flux.h and include/fs_hip.h disagree");
+static_assert(fs::BUDGET_PLANES == FS_BUDGET_NPLANE, "fs_budget.h and include/fs_hip.h disagree on the planes");
 
 FS_OBJECT(fs_history, OBJ_HISTORY, "history", "history from another context or freed");
 FS_OBJECT(fs_loads, OBJ_LOADS, "loads", "loads from another context or freed");
@@ -47,6 +49,7 @@ FS_OBJECT(fs_dist, OBJ_DIST, "distributions", "distributions from another contex
 FS_OBJECT(fs_spec, OBJ_SPEC, "spectrum", "spectrum from another context or freed");
 FS_OBJECT(fs_xspec, OBJ_XSPEC, "cross-spectrum", "cross-spectrum from another context or freed");
 FS_OBJECT(fs_flux, OBJ_FLUX, "scale fluxes", "scale fluxes from another context or freed");
+FS_OBJECT(fs_budget, OBJ_BUDGET, "budget", "budget from another context or freed");
 FS_OBJECT(fs_flowmap, OBJ_FLOWMAP, "flow map", "flow map from another context or freed");
 
 using namespace fs;
@@ -1525,6 +1528,120 @@ int fs_flux_reset(fs_ctx *ctx, fs_flux *s)
 }
 
 int fs_flux_free(fs_ctx *ctx, fs_flux *s) { return object_free(ctx, s); }
+
+// ---- kinetic-energy budget (fs_budget.h) ---------------------------------------------------------------------------------------------------
+// columns per lane: W of k_budget_accumulate (16-byte plane accesses need rows of an even number of doubles)
+static int budget_width(const fs_budget *s) { return s->nx % 2 == 0 ? 2 : 1; }
+static dim3 budget_grid(const fs_ctx *ctx, const fs_budget *s, int *rpw)
+{
+    const int w = budget_width(s), gx = (s->nx + 256 * w - 1) / (256 * w);
+    const int r = diag_rows(ctx, gx, s->ny, BUDGET_ROWS0, BUDGET_ROWS);
+    *rpw = r;
+    return dim3(gx, (s->ny + r - 1) / r);
+}
+// the dense host planes [BUDGET_PLANES][ny][nx] <-> the staggered device planes; queued on the stream
+static auto budget_copy(fs_ctx *ctx, const fs_budget *s, const double *host, hipMemcpyKind kind)
+{
+    return [=]() -> int {
+        const size_t cells = (size_t)s->nx * s->ny;
+        for (int k = 0; k < BUDGET_PLANES; ++k) {
+            double *d = s->d_sums + k * s->plane, *h = const_cast<double *>(host) + k * cells;
+            if (kind == hipMemcpyDeviceToHost) FS_HIP(hipMemcpyAsync(h, d, cells * sizeof(double), kind, ctx->stream));
+            else FS_HIP(hipMemcpyAsync(d, h, cells * sizeof(double), kind, ctx->stream));
+        }
+        return FS_OK;
+    };
+}
+
+int fs_budget_create(fs_ctx *ctx, int x0, int y0, int x1, int y1, double dx, long long every, long long start, fs_budget **out)
+{
+    FS_REQUIRE(ctx && out, "null argument");
+    const int box[4] = {x0, y0, x1, y1};
+    FS_BOX(box, ctx->X, ctx->Y, "budget box must satisfy 0 <= x0 < x1 <= X and 0 <= y0 < y1 <= Y");
+    FS_REQUIRE(std::isfinite(dx) && dx > 0.0, "dx must be finite and > 0");
+    FS_EVERY_START(every, start);
+    FS_NO_CAPTURE(fs_budget, "create");
+    if (ctx->halo != 0 || ctx->nyl != ctx->Y) {
+        set_error("the budget needs a single-GPU context: on a slab the gradient along y crosses the ranks (not implemented)");
+        return FS_ERR_UNSUPPORTED;
+    }
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    FS_HIP(hipSetDevice(ctx->device));
+    const int nx = x1 - x0, ny = y1 - y0;
+    std::vector<uint8_t> mk((size_t)nx * ny);
+    FS_HIP(hipMemcpy2DAsync(mk.data(), nx, ctx->d_mask + (size_t)y0 * ctx->Pm + x0, ctx->Pm, nx, ny, hipMemcpyDeviceToHost, ctx->stream));
+    FS_HIP(hipStreamSynchronize(ctx->stream));
+    FS_REQUIRE(std::find(mk.begin(), mk.end(), (uint8_t)0) != mk.end(), "budget box holds no fluid cell (mask == 0)");
+    auto s = std::make_unique<fs_budget>();
+    for (int k = 0; k < 4; ++k) s->box[k] = box[k];
+    s->nx = nx; s->ny = ny; s->dx = dx; s->every = every; s->start = start;
+    s->plane = (size_t)nx * ny + BUDGET_PAD;
+    const hipError_t e = fill_buffers(ctx, {{s->d_state, BUDGET_STATE * sizeof(long long)}, {s->d_sums, BUDGET_PLANES * s->plane * sizeof(double)}});
+    if (e != hipSuccess) return hip_fail(e, "fs_budget_create", __FILE__, __LINE__);
+    *out = adopt(ctx, std::move(s));
+    return FS_OK;
+}
+
+int fs_budget_launch(fs_ctx *ctx, fs_budget *s, double limit, const fs_field *v, const fs_field *p)
+{
+    FS_REQUIRE(ctx && s, "null argument");
+    FS_HANDLE(s);
+    FS_FIELD(v, 2); FS_FIELD(p, 1);
+    if (!ctx->mask_set) { set_error("mask not uploaded"); return FS_ERR_STATE; }
+    // everything the launches need is in `s` and the fields: no allocation, copy or synchronisation here (the closure is captured / taped)
+    const int w = budget_width(s);
+    int rpw;
+    const dim3 grid = budget_grid(ctx, s, &rpw);
+    const BudgetBox b{s->box[0], s->box[1], s->nx, s->ny};
+    const double two_dx = 2.0 * s->dx;
+    const long long every = s->every, start = s->start;
+    long long *state = s->d_state;
+    double *sums = s->d_sums;
+    const size_t plane = s->plane;
+    return by_dtype(ctx, [&](auto tag) -> int { using T = typename decltype(tag)::type;
+        return launch(ctx, "budget_accumulate", [=] {
+            const bool found = pick<1, 2>(w, [&](auto W) {
+                klaunch(k_budget_accumulate<T, W>, grid, dim3(256), ctx->stream, ctx->grid(), b, rpw, limit, two_dx, start, every, (const long long *)state,
+                        (const T *)v->d, (const T *)p->d, sums, plane);
+            });
+            klaunch(k_budget_tick, dim3(1), dim3(64), ctx->stream, start, every, state);
+            return found;
+        });
+    });
+}
+
+int fs_budget_read(fs_ctx *ctx, fs_budget *s, double *sums, long long *launches, long long *samples)
+{
+    FS_REQUIRE(ctx && s, "null argument");
+    FS_HANDLE(s);
+    FS_NO_CAPTURE(fs_budget, "read");
+    return counted_read(ctx, s->d_state, launches, samples, sums != nullptr, budget_copy(ctx, s, sums, hipMemcpyDeviceToHost));
+}
+
+int fs_budget_get(fs_ctx *ctx, fs_budget *s, double *sums, long long *launches, long long *samples)
+{
+    FS_REQUIRE(ctx && s && sums && launches && samples, "null argument");
+    return fs_budget_read(ctx, s, sums, launches, samples);
+}
+
+int fs_budget_set(fs_ctx *ctx, fs_budget *s, const double *sums, long long launches, long long samples)
+{
+    FS_REQUIRE(ctx && s && sums, "null argument");
+    FS_HANDLE(s);
+    FS_COUNTERS(launches, samples);
+    FS_NO_CAPTURE(fs_budget, "set");
+    return counted_set(ctx, s->d_state, launches, samples, budget_copy(ctx, s, sums, hipMemcpyHostToDevice));
+}
+
+int fs_budget_reset(fs_ctx *ctx, fs_budget *s)
+{
+    FS_REQUIRE(ctx && s, "null argument");
+    FS_HANDLE(s);
+    FS_NO_CAPTURE(fs_budget, "reset");
+    return counted_reset(ctx, s->d_state, dense_zero(ctx, s->d_sums, BUDGET_PLANES * s->plane * sizeof(double)));
+}
+
+int fs_budget_free(fs_ctx *ctx, fs_budget *s) { return object_free(ctx, s); }
 
 // ---- flow maps through the resident snapshots (fs_lcs.h) ----------------------------------------------------------------------------------
 

@@ -319,6 +319,17 @@ struct fs_flux {
     fs::DevBuf<long long> d_state;   // [SPEC_STATE + 1]: launches, samples, and a zero (the `when` of fs_flux_filtered)
 };
 
+// kinetic-energy budget (fs_budget_*, fs_budget.h): the box, the staggered accumulator planes and the device counters
+struct fs_budget {
+    int box[4] = {0, 0, 0, 0};      // x0, y0, x1, y1 (cells)
+    int nx = 0, ny = 0;             // the box's sides
+    double dx = 0.0;
+    long long every = 1, start = 0;
+    size_t plane = 0;               // doubles from one plane to the next: nx * ny + BUDGET_PAD
+    fs::DevBuf<double> d_sums;       // [BUDGET_PLANES][plane], each [b][a]
+    fs::DevBuf<long long> d_state;   // [BUDGET_STATE]
+};
+
 namespace fs { struct LoadFace; }      // fs_loads.h (included by fs_diag.hip alone)
 // body surface loads (fs_loads_*, fs_loads.h): the face list of this context's owned rows, the per-face sums, the ring and the device counters
 struct fs_loads {
@@ -360,7 +371,7 @@ struct fs_tracer {
 namespace fs {
 
 // ---- the objects behind the other handles: one registry (fs_ctx::objects, fs_objects.h), one guard, one no-capture check, one free -------------
-enum ObjKind { OBJ_HISTORY, OBJ_LOADS, OBJ_MEAN, OBJ_MODES, OBJ_POD, OBJ_VORTEX, OBJ_FLOWMAP, OBJ_TRACER, OBJ_MG, OBJ_DIST, OBJ_SPEC, OBJ_XSPEC, OBJ_FLUX };
+enum ObjKind { OBJ_HISTORY, OBJ_LOADS, OBJ_MEAN, OBJ_MODES, OBJ_POD, OBJ_VORTEX, OBJ_FLOWMAP, OBJ_TRACER, OBJ_MG, OBJ_DIST, OBJ_SPEC, OBJ_XSPEC, OBJ_FLUX, OBJ_BUDGET };
 // kind, noun and stale-handle text of an object type: FS_OBJECT(type, kind, noun, text), once, in the unit that implements the type
 template <typename T> struct ObjInfo;
 #define FS_OBJECT(T, KIND, NOUN, STALE) \

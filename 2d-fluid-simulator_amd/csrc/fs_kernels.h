@@ -5,6 +5,7 @@
 // behaviour, SURVEY.md H5, is part of the algorithm).  Reference citations are per kernel.
 #pragma once
 #include "fs_device.h"
+#include "fs_cell.h"
 
 namespace fs {
 
@@ -380,17 +381,7 @@ __global__ __launch_bounds__(1024) void k_residual_final(const D *partial, int n
 // ------------------------------------------------------------------------------------------------
 // K9  limit_field, fs/solver.py:38-43 ;  K13  clamp_field, fs/solver.py:46-49   (all cells)
 // ------------------------------------------------------------------------------------------------
-// the per-cell function of limit_field: (x, y) scaled onto the circle of radius lim when it lies outside -> whether it did (also what
-// fs_history.h applies to a probe while v still owes a deferred pass, so that a record equals the download after the pass, bit for bit)
-template <typename T>
-__device__ __forceinline__ bool limit_cell(T &x, T &y, T lim)
-{
-    const T nrm = tsqrt(x * x + y * y);
-    if (!(nrm > lim)) return false;
-    x = lim * (x / nrm);
-    y = lim * (y / nrm);
-    return true;
-}
+// the per-cell function of limit_field is limit_cell (fs_cell.h: host-and-device text, so that the CPU tests can run it)
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_limit(Grid g, int jb, T lim, T *v)

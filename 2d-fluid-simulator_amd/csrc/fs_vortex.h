@@ -128,20 +128,7 @@ __device__ __forceinline__ bool vortex_on(const VxWhen &w)
     return !w.state || (samples_at(w.state[0], w.start, w.every) && w.state[1] < w.cap);
 }
 
-// the gradient terms of a cell from its four neighbours' (u, w), in the order of the header
-struct VxGrad { double ux, uy, wx, wy, om; };
-template <typename T>
-__device__ __forceinline__ VxGrad vortex_grad(T ul, T wl, T ur, T wr, T um, T wm, T un, T wn, T limit, double two_dx)
-{
-    if (limit > (T)0) { limit_cell(ul, wl, limit); limit_cell(ur, wr, limit); limit_cell(um, wm, limit); limit_cell(un, wn, limit); }
-    VxGrad d;
-    d.ux = ((double)ur - (double)ul) / two_dx;
-    d.uy = ((double)un - (double)um) / two_dx;
-    d.wx = ((double)wr - (double)wl) / two_dx;
-    d.wy = ((double)wn - (double)wm) / two_dx;
-    d.om = (((double)wr - (double)wl) - ((double)un - (double)um)) / two_dx;
-    return d;
-}
+// the gradient terms of a cell from its four neighbours' (u, w), in the order of the header: VxGrad and vortex_grad of fs_cell.h
 __device__ __forceinline__ double vortex_criterion(int which, const VxGrad &d)
 {
     if (which == 0) {

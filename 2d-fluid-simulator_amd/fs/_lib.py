@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FS_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libfs_hip.so")     # FS_LIB: A/B builds (tools/)
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 _lib = None
 
@@ -155,6 +155,13 @@ _PROTOS = {
     "fs_flux_set": [_c_vp, _c_vp, _P(_c_dbl), ctypes.c_longlong, ctypes.c_longlong],
     "fs_flux_reset": [_c_vp, _c_vp],
     "fs_flux_free": [_c_vp, _c_vp],
+    "fs_budget_create": [_c_vp, _c_int, _c_int, _c_int, _c_int, _c_dbl, ctypes.c_longlong, ctypes.c_longlong, _P(_c_vp)],
+    "fs_budget_launch": [_c_vp, _c_vp, _c_dbl, _c_vp, _c_vp],
+    "fs_budget_read": [_c_vp, _c_vp, _P(_c_dbl), _P(ctypes.c_longlong), _P(ctypes.c_longlong)],
+    "fs_budget_get": [_c_vp, _c_vp, _P(_c_dbl), _P(ctypes.c_longlong), _P(ctypes.c_longlong)],
+    "fs_budget_set": [_c_vp, _c_vp, _P(_c_dbl), ctypes.c_longlong, ctypes.c_longlong],
+    "fs_budget_reset": [_c_vp, _c_vp],
+    "fs_budget_free": [_c_vp, _c_vp],
     "fs_flowmap_create": [_c_vp, _P(_c_int), _c_int, _P(_c_vp)],
     "fs_flowmap_advance": [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_dbl, _c_int],
     "fs_flowmap_cauchy_green": [_c_vp, _c_vp],

@@ -20,6 +20,7 @@ from .pod import Pod
 from . import dist as _dist
 from . import spectra as _spectra
 from . import fluxes as _fluxes
+from . import budgets as _budgets
 from .vortices import VELOCITY_LIMIT, Vortices, assemble, omega_exponent
 from .pressure_updater import JacobiPressureUpdater, MultigridPressureUpdater, RedBlackSorPressureUpdater
 from .solver import CipMacSolver, DyeCipMacSolver, DyeMacSolver, MacSolver
@@ -102,6 +103,7 @@ class FluidSimulator:
         self._spectrar = None      # fs.spectra.Spectra while start_spectra() is on
         self._xspectrar = None     # fs.spectra.CrossSpectra while start_cross_spectra() is on
         self._fluxr = None         # fs.fluxes.ScaleFluxes while start_scale_fluxes() is on
+        self._budgetr = None       # fs.budgets.Budget while start_budget() is on
         self._tracers = None       # fs.tracers.Tracers while seed_tracers() is on
         self._tracker = None       # fs.loads.Tracker while track_body() is on
         self._last_tracker = None  # ... and after stop_body(): what body_loads() / body_surface() still return
@@ -111,8 +113,8 @@ class FluidSimulator:
 
     def _riders(self):
         """The attached riders (fs.riders.Rider) in their fixed order - history, averages, modes, pod, distributions, spectra, cross-spectra,
-        scale fluxes, loads, tracers, vortices: the order of their launches behind the solver step and of their tokens in _signature()."""
-        return [r for r in (self._recorder, self._averager, self._moder, self._podr, self._distr, self._spectrar, self._xspectrar, self._fluxr, self._tracker,
+        scale fluxes, budget, loads, tracers, vortices: the order of their launches behind the solver step and of their tokens in _signature()."""
+        return [r for r in (self._recorder, self._averager, self._moder, self._podr, self._distr, self._spectrar, self._xspectrar, self._fluxr, self._budgetr, self._tracker,
                             self._tracers, self._vortexr) if r is not None]
 
     def _capturing(self):
@@ -1224,6 +1226,82 @@ class FluidSimulator:
         X, Y = self._grid_shape()
         out["defined"] = (max(fx.box[0], half_width), max(fx.box[1], half_width), min(fx.box[2], X - half_width), min(fx.box[3], Y - half_width))
         return out
+
+    # -- kinetic-energy budget (new): 21 raw moments per fluid cell of a box accumulated on the device; the terms are host algebra ------------
+    def _budget_box(self, box):
+        """The box (None: the whole grid) as a tuple of ints, and its fluid cells (mask == 0); a box without one is refused (ValueError)."""
+        dev = self._dev
+        box = (0, 0, dev.nx, dev.ny) if box is None else dev.flux_box(box)
+        fluid = np.asarray(self._solver._bc.mask)[box[0]:box[2], box[1]:box[3]] == 0
+        if not fluid.any():
+            raise ValueError(f"the box {box} holds no fluid cell")
+        return box, fluid
+
+    def start_budget(self, box=None, every=1, start_step=0):
+        """From the next step on, accumulate the budget of the fluctuation kinetic energy k = (<u'u'> + <w'w'>) / 2 over `box` on the device
+        (csrc/fs_budget.h): after every step k (counted from here) with k > start_step and (k - start_step) % every == 0, every fluid cell
+        of the box adds u, w, p, their second and third moments, the pressure correlations, the velocity gradient (central differences) and
+        its squares to 21 planes of double.  box = (x0, y0, x1, y1) in global cells, half-open, anything inside the grid with at least one
+        fluid cell (ValueError otherwise, before any device call); None: the whole grid.  The launch is part of the step: captured into
+        the replayed graphs, it decides on the device whether it samples, and run() is not cut into chunks by it.  A plane is a pure
+        function of the fields: identical between eager steps, replayed graphs and resumed runs.  Device memory: 168 bytes per cell of
+        the box.  Changes no field and no trajectory.  budget() returns the result.  Raises while a budget is attached already and during
+        a graph capture; single-GPU contexts only (FsError on slabs)."""
+        dev = self._dev
+        self._not_capturing("start_budget")
+        self._make_way("_budgetr", "a budget is attached already: stop_budget() first (or reset_budget())")
+        every, start_step = self._cadence(every, start_step)
+        box, fluid = self._budget_box(box)
+        self._budgetr = _budgets.Budget(dev, dev.budget_create(box, self._solver.dx, every, start_step), fluid, self._solver.re)
+
+    def _budget(self):
+        if self._budgetr is None:
+            raise RuntimeError("no budget: call start_budget() first")
+        return self._budgetr
+
+    def budget(self):
+        """The budget so far (fs.budgets.derive_budget): float64 (Nx, Ny) arrays over the box - the means "U", "W", "P", the central moments
+        "uu", "ww", "uw", "k", "pu", "pw", "uuu", "uuw", "wwu", "www", the mean gradients "Ux", "Uy", "Wx", "Wy", and the terms "convection",
+        "production", "dissipation" (positive), "turbulent_transport", "pressure_diffusion", "pressure_dilatation", "viscous_diffusion",
+        "residual" -; "totals": each term summed over "valid" times dx^2; "fluid", "valid", "samples", "sample_steps", "box", "dx", "re"
+        and the raw "sums" (21, Nx, Ny).  In a statistically steady flow -residual is the rate at which the advection scheme, the
+        confinement, the velocity limit and the splitting change k.  Every array is there, all zeros, while no sample has been taken.
+        fs.budgets.momentum_balance gives the mean momentum equation from the same dict.  A download of the planes; not allowed during a
+        graph capture."""
+        self._not_capturing("budget")
+        return self._budget().data()
+
+    def reset_budget(self):
+        """Planes and sample count back to zero; the step count and the phase of `every` / `start_step` run on."""
+        self._not_capturing("reset_budget")
+        self._budget().reset()
+
+    def stop_budget(self):
+        """Detach the budget and free its device memory (168 bytes per cell of the box); the cached graphs that hold its launches are freed
+        first.  Nothing is kept on the host: call budget() before.  Inside a graph capture the device memory is released when the capture
+        ends."""
+        self._detach(self, "_budgetr", "stop_budget")
+
+    def budget_sample(self, box=None):
+        """The budget's planes of the fields as they are now: the dict budget() returns, with "samples" 1 and "sample_steps" [0] (the call
+        counts no steps; with one sample every fluctuation is zero - the use is the raw "sums" and the means).  One temporary object of
+        168 bytes per cell of the box, one eager launch, a read and a free: changes no field, no graph and no attached rider, and leaves a
+        deferred limit_field deferred.  Not allowed during a graph capture."""
+        dev = self._dev
+        self._not_capturing("budget_sample")
+        box, fluid = self._budget_box(box)
+        bg = dev.budget_create(box, self._solver.dx, 1, 0)
+        try:
+            saved, dev._oplog = getattr(dev, "_oplog", None), None      # (never part of a logged period)
+            try:
+                v, p = self._solver.get_fields()[:2]
+                dev.budget_launch(bg, v, p)
+            finally:
+                dev._oplog = saved
+            sums, _, samples = dev.budget_read(bg)
+        finally:
+            dev.budget_free(bg)
+        return _budgets.budget_result(sums, samples, np.zeros(samples, np.int64), box, fluid, self._solver.dx, self._solver.re)
 
     # -- flow maps and FTLE fields (new): a lattice of particles carried through the POD's resident snapshots on the device --------------
     def flow_map(self, direction="backward", refine=1, box=None, substeps=1, first=None, last=None):

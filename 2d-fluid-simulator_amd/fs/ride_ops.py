@@ -1,5 +1,5 @@
 """Device side of what rides the step and of the diagnostics (new; the reference has none): flow statistics, the per-step history, the
-body surface loads, the time averages, the harmonic modes, the snapshot POD, the flow maps through its snapshots, the field distributions, the energy spectra, the cross-spectra, the scale-to-scale fluxes and the tracer particles.  Two mixins: RideOps is the
+body surface loads, the time averages, the harmonic modes, the snapshot POD, the flow maps through its snapshots, the field distributions, the energy spectra, the cross-spectra, the scale-to-scale fluxes, the kinetic-energy budget and the tracer particles.  Two mixins: RideOps is the
 backend-agnostic host logic fs.runtime.DeviceBase inherits (slab partition, combination over ranks, argument checks, the op log of a logged period), NativeRideOps the `_p_*` primitives
 fs.runtime.Device binds to libfs_hip.so; the stand-in devices of the CPU tests override those.  fs.runtime re-exports every name here."""
 import collections
@@ -124,6 +124,15 @@ class Flux(_Handle):
         self.nx, self.ny = box[2] - box[0], box[3] - box[1]
 
 
+class Budget(_Handle):
+    """Device planes of the kinetic-energy budget (DeviceBase.budget_create): handle, the cell box, its sides (nx, ny), dx, every, start."""
+
+    def __init__(self, h, box, dx, every, start):
+        super().__init__(h)
+        self.box, self.dx, self.every, self.start = tuple(box), dx, every, start
+        self.nx, self.ny = box[2] - box[0], box[3] - box[1]
+
+
 class FlowMap(_Handle):
     """A device lattice of flow-map nodes (DeviceBase.flowmap_create): handle, cell box, refine, and the lattice (nx, ny)."""
 
@@ -151,7 +160,7 @@ class History(_Handle):
 
 
 class RideOps:
-    """flow_stats and the history_* / loads_* / mean_* / modes_* / pod_* / flowmap_* / dist_* / spec_* / xspec_* / flux_* / tracer_* calls of DeviceBase."""
+    """flow_stats and the history_* / loads_* / mean_* / modes_* / pod_* / flowmap_* / dist_* / spec_* / xspec_* / flux_* / budget_* / tracer_* calls of DeviceBase."""
 
     # (The tracer calls reach these through the class - RideOps._host_only(self, ...) - as they always reached _tracer_host_call: the CPU
     #  tests check their refusals on objects that are no devices.)
@@ -1057,6 +1066,65 @@ class RideOps:
     def flux_free(self, fx):
         self._release(fx, self._p_flux_free)
 
+    # ---- kinetic-energy budget (include/fs_hip.h fs_budget_*): 21 planes of raw moments over the fluid cells of a box, one launch per step;
+    #      csrc/fs_budget.h ----
+    BUDGET_NPLANE = 21
+
+    def budget_create(self, box, dx, every=1, start=0):
+        """Device planes for FluidSimulator.start_budget / budget_sample: 168 bytes per cell of the box (x0, y0, x1, y1), half-open, anything
+        inside the grid with at least one cell.  Everything is checked (ValueError) before any device call; a box without a fluid cell is
+        refused by the caller that knows the mask (FluidSimulator) and by the library.  Single-context grids only (FsError on a slab); not
+        allowed during a graph capture."""
+        box = RideOps.flux_box(self, box)
+        dx = float(dx)
+        if not (math.isfinite(dx) and dx > 0.0):
+            raise ValueError(f"dx must be finite and > 0, got {dx}")
+        every, start = RideOps._check_cadence(every, start)
+        RideOps._host_only(self, "budget_create during a graph capture")
+        RideOps._single_context(self, "the budget needs", "the gradient along y crosses the ranks")
+        h = self._p_budget_create(box, dx, every, start)
+        return self._adopt(h, Budget(h, box, dx, every, start))
+
+    def budget_launch(self, bg, v, p):
+        """The launches of one step: the accumulation - it returns at once unless this launch samples - and the tick.  A limit_field v still
+        owes stays deferred: the kernel limits the values it reads, the neighbours' too.  Not a _run: no flush, no exchange, no ghost row
+        (writes no field)."""
+        self._ride("budget_launch", (bg._h, self._limit_of(v), v._h, p._h))
+
+    def _budget_sums(self, bg, flat):
+        return np.ascontiguousarray(flat.reshape(RideOps.BUDGET_NPLANE, bg.ny, bg.nx).transpose(0, 2, 1))
+
+    def budget_read(self, bg, sums=True):
+        """-> (sums float64 (21, Nx, Ny) in the order of fs.budgets.PLANES - None with sums=False -, launches, samples).  Not allowed during
+        a graph capture."""
+        self._host_only("budget_read during a graph capture: the planes are a download (read between captures / replays)")
+        flat, launches, samples = self._p_budget_read(bg._h, RideOps.BUDGET_NPLANE * bg.nx * bg.ny if sums else 0)
+        return (RideOps._budget_sums(self, bg, flat) if sums else None), int(launches), int(samples)
+
+    def budget_get(self, bg):
+        """-> (the sums float64 (21, Nx, Ny), launches, samples), for checkpoints."""
+        self._host_only("budget_get during a graph capture")
+        flat, launches, samples = self._p_budget_get(bg._h, RideOps.BUDGET_NPLANE * bg.nx * bg.ny)
+        return RideOps._budget_sums(self, bg, flat), int(launches), int(samples)
+
+    def budget_set(self, bg, sums, launches, samples):
+        """Restore what budget_get returned (resume)."""
+        self._host_only("budget_set during a graph capture")
+        sums = np.asarray(sums, np.float64)
+        shape = (RideOps.BUDGET_NPLANE, bg.nx, bg.ny)
+        if sums.shape != shape:
+            raise ValueError(f"expected sums of shape {shape}, got {sums.shape}")
+        launches, samples = self._check_counters(launches, samples)
+        self._p_budget_set(bg._h, np.ascontiguousarray(sums.transpose(0, 2, 1)).ravel(), launches, samples)
+
+    def budget_reset(self, bg):
+        """Sums and sample count to zero; the launch count runs on.  Not allowed during a graph capture."""
+        self._host_only("budget_reset during a graph capture")
+        self._p_budget_reset(bg._h)
+
+    def budget_free(self, bg):
+        self._release(bg, self._p_budget_free)
+
     # ---- flow maps (include/fs_hip.h fs_flowmap_*): a lattice of particles carried through the resident snapshots of a POD; csrc/fs_lcs.h ----
     def flowmap_create(self, box=None, refine=1):
         """A device lattice for FluidSimulator.flow_map: refine x refine nodes per cell of the cell box (x0, y0, x1, y1) (None: the whole
@@ -1610,6 +1678,20 @@ class NativeRideOps:
 
     _p_flux_reset = _caller("fs_flux_reset")
     _p_flux_free = _freer("fs_flux_free")
+
+    def _p_budget_create(self, box, dx, every, start):
+        h = ctypes.c_void_p()
+        _lib.call("fs_budget_create", self._ctx, *box, dx, every, start, ctypes.byref(h))
+        return h
+
+    _p_budget_read = _counted_reader("fs_budget_read", optional=True)      # (h, words)
+    _p_budget_get = _counted_reader("fs_budget_get")
+
+    def _p_budget_set(self, h, flat, launches, samples):
+        _lib.call("fs_budget_set", self._ctx, h, flat.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), launches, samples)
+
+    _p_budget_reset = _caller("fs_budget_reset")
+    _p_budget_free = _freer("fs_budget_free")
 
     def _p_flowmap_create(self, box, refine):
         h = ctypes.c_void_p()

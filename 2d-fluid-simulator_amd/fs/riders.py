@@ -1,5 +1,5 @@
 """What rides the step (new; the reference has none): the protocol between FluidSimulator and the objects whose launches go behind every
-solver step - fs.history.Recorder, fs.averages.Averager, fs.modes.Modes, fs.pod.Pod, fs.dist.Distributions, fs.spectra.Spectra, fs.spectra.CrossSpectra, fs.fluxes.ScaleFluxes, fs.loads.Tracker, fs.tracers.Tracers, fs.vortices.Vortices - and the one host-side
+solver step - fs.history.Recorder, fs.averages.Averager, fs.modes.Modes, fs.pod.Pod, fs.dist.Distributions, fs.spectra.Spectra, fs.spectra.CrossSpectra, fs.fluxes.ScaleFluxes, fs.budgets.Budget, fs.loads.Tracker, fs.tracers.Tracers, fs.vortices.Vortices - and the one host-side
 sampling rule.
 DESIGN.md "Riders" says what a new rider has to implement."""
 
@@ -22,7 +22,7 @@ def ring_room(issued, every, start, capacity, gone):
 
 class Rider:
     """One attachment of a FluidSimulator.  FluidSimulator._riders() yields the attached ones in the fixed order history, averages, modes,
-    pod, distributions, spectra, cross-spectra, scale fluxes, loads, tracers, vortices: the order of their launches behind the solver step and of their tokens in _signature()."""
+    pod, distributions, spectra, cross-spectra, scale fluxes, budget, loads, tracers, vortices: the order of their launches behind the solver step and of their tokens in _signature()."""
     stop_in_capture = True       # stop_*() inside a graph capture: allowed (the device memory goes when the capture ends), or RuntimeError
     keeps_last = False           # stop_*() keeps the rider as sim._last_*: its readers go on returning what it gathered
     replaces_attached = False    # attaching while one of the kind is attached: stops that one first, or RuntimeError

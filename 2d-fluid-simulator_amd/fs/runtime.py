@@ -24,7 +24,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from .ride_ops import Dist, DistChannel, FlowMap, Flux, History, Loads, Mean, Modes, NativeRideOps, RideOps, Spec, TracerAccum, TracerSet, XSpec, _serials      # noqa: F401 (re-exported)
+from .ride_ops import Budget, Dist, DistChannel, FlowMap, Flux, History, Loads, Mean, Modes, NativeRideOps, RideOps, Spec, TracerAccum, TracerSet, XSpec, _serials      # noqa: F401 (re-exported)
 
 _DTYPES = {"f32": np.float32, "f64": np.float64, np.float32: np.float32, np.float64: np.float64,
            np.dtype("float32"): np.float32, np.dtype("float64"): np.float64}

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FS_ABI_VERSION 27
+#define FS_ABI_VERSION 28
 
 typedef struct fs_ctx fs_ctx;
 typedef struct fs_field fs_field;
@@ -639,6 +639,35 @@ int fs_flux_get(fs_ctx *ctx, fs_flux *s, double *sums, long long *launches, long
 int fs_flux_set(fs_ctx *ctx, fs_flux *s, const double *sums, long long launches, long long samples);
 int fs_flux_reset(fs_ctx *ctx, fs_flux *s);
 int fs_flux_free(fs_ctx *ctx, fs_flux *s);
+
+/* Kinetic-energy budget (new, ABI 28): the raw moments behind the budget of k = (<u'u'> + <w'w'>) / 2 - production, dissipation, turbulent and
+ * pressure transport, pressure dilatation -, accumulated per FLUID cell (mask == 0) of a box by a launch that can be captured in a hipGraph
+ * (the values, their order and the kernel: csrc/fs_budget.h; the algebra: fs/budgets.py).  FS_BUDGET_NPLANE planes of double:
+ *   0-2 S_u S_w S_p | 3-5 S_uu S_ww S_uw | 6-7 S_pu S_pw | 8-11 S_uuu S_uuw S_wwu S_www | 12-15 S_ux S_uy S_wx S_wy |
+ *   16-19 S_uxux S_uyuy S_wxwx S_wywy | 20 S_pd (p times ux + wy)
+ * with the gradient by central differences over 2 dx, neighbour indices clamped at the grid's edge, neighbours taken as stored.  All doubles, no
+ * atomics; one lane owns a cell, so a plane is a pure function of the fields and the order of the samples; planes 0 - 5 equal fs_mean's on the
+ * fluid cells bit for bit.  A cell of the box that is not fluid holds +0.  Planes are (Ny, Nx) in C order, cell (a, b) of the box at b * Nx + a.
+ * Single-GPU contexts: create returns FS_ERR_UNSUPPORTED on a slab context.
+ * create:  the half-open box x0, y0, x1, y1 of global cells, anything inside the grid with at least one cell; a box without a fluid cell is
+ *          FS_ERR_ARG (needs the mask).  dx finite and > 0; every >= 1, start >= 0 (the sampling rule of fs_mean_create).  Device memory: 168
+ *          bytes per cell of the box.
+ * launch:  two kernel launches, nothing else (capturable); the first returns at once unless this launch samples.  limit > 0: v still owes
+ *          limit_field(limit), and the kernel limits every value it reads, the neighbours' too.  Needs the mask.
+ * read:    synchronises; sums: the planes, or NULL; launches, samples: may be NULL.  Resets nothing.
+ * get / set: the planes and the counters, for checkpoints; set: 0 <= samples <= launches.
+ * reset:   planes and sample count to zero; the launch count runs on.
+ * free:    as fs_mean_free.
+ * Everything but launch and free returns FS_ERR_STATE during graph capture / tape recording.                                             */
+#define FS_BUDGET_NPLANE 21
+typedef struct fs_budget fs_budget;
+int fs_budget_create(fs_ctx *ctx, int x0, int y0, int x1, int y1, double dx, long long every, long long start, fs_budget **out);
+int fs_budget_launch(fs_ctx *ctx, fs_budget *s, double limit, const fs_field *v, const fs_field *p);
+int fs_budget_read(fs_ctx *ctx, fs_budget *s, double *sums, long long *launches, long long *samples);
+int fs_budget_get(fs_ctx *ctx, fs_budget *s, double *sums, long long *launches, long long *samples);
+int fs_budget_set(fs_ctx *ctx, fs_budget *s, const double *sums, long long launches, long long samples);
+int fs_budget_reset(fs_ctx *ctx, fs_budget *s);
+int fs_budget_free(fs_ctx *ctx, fs_budget *s);
 
 /* Multigrid pressure correction (new, ABI 19): one W-cycle (two coarse visits per level) on a mask-aware hierarchy of coarse levels, for the
  * third pressure updater (fs/pressure_updater.py MultigridPressureUpdater; kernels and operation order: csrc/fs_mg.h).  Single-GPU contexts.
