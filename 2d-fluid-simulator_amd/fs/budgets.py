@@ -8,7 +8,7 @@ Raw moments are differenced here (<ab> - <a><b>, and the third-moment expansions
 f32-sized values for that reason, and a central moment far below the product of the means carries the rounding of that difference."""
 import numpy as np
 
-from .riders import Rider, samples_after
+from .riders import BOX, CountedRider
 
 PLANES = ("u", "w", "p", "uu", "ww", "uw", "pu", "pw", "uuu", "uuw", "wwu", "www", "ux", "uy", "wx", "wy", "uxux", "uyuy", "wxwx", "wywy", "pd")
 NPLANE = len(PLANES)                 # FS_BUDGET_NPLANE
@@ -135,64 +135,23 @@ def budget_result(sums, samples, sample_steps, box, fluid, dx, re):
     return out
 
 
-class Budget(Rider):
-    """The accumulated kinetic-energy budget of a FluidSimulator (start_budget): the device planes and their parameters.  No ring: room()
-    is None and run() is not cut by it."""
+class Budget(CountedRider):
+    """The accumulated kinetic-energy budget of a FluidSimulator (start_budget): the device planes and their parameters.
+    held(z) -> (box, every, start), or None."""
+    kind, payload, noun = "budget", "sums", "budget"
+    params = (BOX,)
 
     def __init__(self, dev, budget, fluid, re):
-        self.dev, self.budget, self.fluid, self.re = dev, budget, np.asarray(fluid, bool), float(re)
-        self.every, self.start_step = int(budget.every), int(budget.start)
-        self.base = 0              # samples taken before the last reset (sample_steps)
+        super().__init__(dev, budget, budget.every, budget.start)
+        self.budget, self.fluid, self.re = budget, np.asarray(fluid, bool), float(re)
 
-    @property
-    def token(self):
-        return ("budget", self.budget.serial)
+    def attached(self):
+        return (tuple(self.budget.box),)
 
     def launch(self, sim):
         v, p = sim._solver.get_fields()[:2]
         self.dev.budget_launch(self.budget, v, p)
 
-    def free(self):
-        self.dev.budget_free(self.budget)
-
-    def sample_steps(self, samples):
-        """The step (counted from start_budget, from 1) of every sample in the planes, int64 (samples,)."""
-        k = self.base + np.arange(int(samples), dtype=np.int64)
-        return self.start_step + (k + 1) * self.every
-
     def data(self):
         sums, _, samples = self.dev.budget_read(self.budget)
         return budget_result(sums, samples, self.sample_steps(samples), self.budget.box, self.fluid, self.budget.dx, self.re)
-
-    def reset(self):
-        _, launches, _ = self.dev.budget_read(self.budget, sums=False)
-        self.dev.budget_reset(self.budget)
-        self.base = samples_after(launches, self.every, self.start_step)
-
-    def checkpoint(self):
-        sums, launches, samples = self.dev.budget_get(self.budget)
-        return {"budget.sums": sums, "budget.launches": np.array(launches), "budget.samples": np.array(samples), "budget.base": np.array(self.base),
-                "budget.box": np.array(self.budget.box, np.int64), "budget.every": np.array(self.every), "budget.start": np.array(self.start_step)}
-
-    @staticmethod
-    def held(z):
-        """-> (box, every, start), or None."""
-        if "budget.sums" not in z:
-            return None
-        return tuple(int(b) for b in np.asarray(z["budget.box"])), int(z["budget.every"]), int(z["budget.start"])
-
-    def restore(self, z):
-        """Refused (ValueError) before any device work when the checkpoint holds no budget, or its box, every or start_step are not the
-        attached ones."""
-        held = self.held(z)
-        if held is None:
-            raise ValueError("the checkpoint holds no budget")
-        box, every, start = held
-        if box != tuple(self.budget.box):
-            raise ValueError(f"the checkpoint's budget was accumulated over the box {box}, the attached one over {tuple(self.budget.box)}")
-        if (every, start) != (self.every, self.start_step):
-            raise ValueError(f"the checkpoint's budget samples every {every} from {start}, the attached one every {self.every} from "
-                             f"{self.start_step}")
-        self.dev.budget_set(self.budget, z["budget.sums"], int(z["budget.launches"]), int(z["budget.samples"]))
-        self.base = int(z["budget.base"])
-        return int(z["budget.samples"])

@@ -11,7 +11,7 @@ import math
 
 import numpy as np
 
-from .riders import Rider, samples_after
+from .riders import CountedRider, Param
 
 METHODS = ("lower", "higher", "nearest", "linear")
 
@@ -124,29 +124,24 @@ def channels_array(channels):
     return np.array([[c.quantity, c.bins, c.lo, c.hi, c.quantity_b, c.bins_b, c.lo_b, c.hi_b, *c.box] for c in channels], np.float64)
 
 
-class Distributions(Rider):
-    """The accumulated distributions of a FluidSimulator (start_distributions): the device tables and their parameters.  No ring: room()
-    is None and run() is not cut by it."""
+class Distributions(CountedRider):
+    """The accumulated distributions of a FluidSimulator (start_distributions): the device tables and their parameters.
+    held(z) -> (channels array (n, 12), every, start), or None."""
+    kind, payload, noun, plural = "dist", "tables", "distributions", True
+    params = (Param("channels", np.asarray, lambda a: np.asarray(a, np.float64), "{theirs} accumulated with other channels than {ours}",
+                    np.array_equal),)
+    refuses_missing = False
 
     def __init__(self, dev, dist, every, start_step):
-        self.dev, self.dist, self.every, self.start_step = dev, dist, int(every), int(start_step)
-        self.base = 0              # samples taken before the last reset (sample_steps)
+        super().__init__(dev, dist, every, start_step)
+        self.dist = dist
 
-    @property
-    def token(self):
-        return ("dist", self.dist.serial)
+    def attached(self):
+        return (channels_array(self.dist.channels),)
 
     def launch(self, sim):
         v, p = sim._solver.get_fields()[:2]
         self.dev.dist_launch(self.dist, sim._solver.dx, v, p)
-
-    def free(self):
-        self.dev.dist_free(self.dist)
-
-    def sample_steps(self, samples):
-        """The step (counted from start_distributions, from 1) of every sample in the tables, int64 (samples,)."""
-        k = self.base + np.arange(int(samples), dtype=np.int64)
-        return self.start_step + (k + 1) * self.every
 
     def data(self):
         out = []
@@ -155,32 +150,5 @@ class Distributions(Rider):
             out.append(result(self.dev, c, counts, tails, samples, self.sample_steps(samples)))
         return out
 
-    def reset(self):
-        _, _, launches, _ = self.dev.dist_read(self.dist, 0)
-        self.dev.dist_reset(self.dist)
-        self.base = samples_after(launches, self.every, self.start_step)
-
-    def _spec(self):
-        return channels_array(self.dist.channels)
-
-    def checkpoint(self):
-        words, launches, samples = self.dev.dist_get(self.dist)
-        return {"dist.tables": words, "dist.launches": np.array(launches), "dist.samples": np.array(samples), "dist.base": np.array(self.base),
-                "dist.channels": self._spec(), "dist.every": np.array(self.every), "dist.start": np.array(self.start_step)}
-
-    @staticmethod
-    def held(z):
-        """-> (channels array (n, 12), every, start), or None."""
-        return (np.asarray(z["dist.channels"], np.float64), int(z["dist.every"]), int(z["dist.start"])) if "dist.tables" in z else None
-
-    def restore(self, z):
-        """Refused (ValueError) before any device work when the checkpoint's channels, every or start_step are not the attached ones."""
-        held = np.asarray(z["dist.channels"], np.float64)
-        if held.shape != self._spec().shape or not np.array_equal(held, self._spec()):
-            raise ValueError("the checkpoint's distributions were accumulated with other channels than the attached ones")
-        if (int(z["dist.every"]), int(z["dist.start"])) != (self.every, self.start_step):
-            raise ValueError(f"the checkpoint's distributions sample every {int(z['dist.every'])} from {int(z['dist.start'])}, "
-                             f"the attached ones every {self.every} from {self.start_step}")
-        self.dev.dist_set(self.dist, z["dist.tables"], int(z["dist.launches"]), int(z["dist.samples"]))
-        self.base = int(z["dist.base"])
-        return int(z["dist.samples"])
+    def _launches(self):
+        return self.dev.dist_read(self.dist, 0)[2]      # (the read is per channel and has no form without the payload)

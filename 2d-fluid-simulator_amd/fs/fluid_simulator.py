@@ -7,6 +7,7 @@
 PressureUpdater factory.
 """
 import math
+import operator
 
 import numpy as np
 
@@ -28,6 +29,24 @@ from .tracers import TracerAccumulation, Tracers, check_seeds, response
 from .vorticity_confinement import VorticityConfinement
 
 _WALL_COLOR = (0.5, 0.7, 0.5)   # fs/fluid_simulator.py:17 (applied by the visualisation kernels, csrc/fs_kernels.h k_visualize)
+
+# The attributes of a FluidSimulator that hold its riders (fs.riders.Rider; None while the kind is not attached), in THE order of the
+# riders: that of their launches behind the solver step and of their tokens in _signature().
+RIDER_ATTRS = (
+    "_recorder",       # fs.history.Recorder while record_history() is on
+    "_averager",       # fs.averages.Averager while start_averaging() is on
+    "_moder",          # fs.modes.Modes while start_modes() is on
+    "_podr",           # fs.pod.Pod while start_pod() is on
+    "_distr",          # fs.dist.Distributions while start_distributions() is on
+    "_spectrar",       # fs.spectra.Spectra while start_spectra() is on
+    "_xspectrar",      # fs.spectra.CrossSpectra while start_cross_spectra() is on
+    "_fluxr",          # fs.fluxes.ScaleFluxes while start_scale_fluxes() is on
+    "_budgetr",        # fs.budgets.Budget while start_budget() is on
+    "_tracker",        # fs.loads.Tracker while track_body() is on
+    "_tracers",        # fs.tracers.Tracers while seed_tracers() is on
+    "_vortexr",        # fs.vortices.Vortices while track_vortices() is on
+)
+_rider_slots = operator.attrgetter(*RIDER_ATTRS)
 
 
 def _make_updater(spec, bc, dt, dx):
@@ -94,28 +113,16 @@ class FluidSimulator:
         self._eager_seen = False   # one step has run outside a capture (the library's compact launch lists exist)
         self._pending_after_step = (False, False)
         self._since_hot_check = 0
-        self._recorder = None      # fs.history.Recorder while record_history() is on
-        self._last_recorder = None  # ... and after stop_history(): what history() still returns
-        self._averager = None      # fs.averages.Averager while start_averaging() is on
-        self._moder = None         # fs.modes.Modes while start_modes() is on
-        self._podr = None          # fs.pod.Pod while start_pod() is on
-        self._distr = None         # fs.dist.Distributions while start_distributions() is on
-        self._spectrar = None      # fs.spectra.Spectra while start_spectra() is on
-        self._xspectrar = None     # fs.spectra.CrossSpectra while start_cross_spectra() is on
-        self._fluxr = None         # fs.fluxes.ScaleFluxes while start_scale_fluxes() is on
-        self._budgetr = None       # fs.budgets.Budget while start_budget() is on
-        self._tracers = None       # fs.tracers.Tracers while seed_tracers() is on
-        self._tracker = None       # fs.loads.Tracker while track_body() is on
-        self._last_tracker = None  # ... and after stop_body(): what body_loads() / body_surface() still return
-        self._vortexr = None       # fs.vortices.Vortices while track_vortices() is on
-        self._last_vortexr = None  # ... and after stop_vortices(): what vortices() / vortex_labels() still return
+        for attr in RIDER_ATTRS:
+            setattr(self, attr, None)
+        self._last_recorder = None  # the recorder after stop_history(): what history() still returns
+        self._last_tracker = None  # the body tracker after stop_body(): what body_loads() / body_surface() still return
+        self._last_vortexr = None  # the vortex tracker after stop_vortices(): what vortices() / vortex_labels() still return
         self._found_planes = None  # the planes of the last find_vortices()
 
     def _riders(self):
-        """The attached riders (fs.riders.Rider) in their fixed order - history, averages, modes, pod, distributions, spectra, cross-spectra,
-        scale fluxes, budget, loads, tracers, vortices: the order of their launches behind the solver step and of their tokens in _signature()."""
-        return [r for r in (self._recorder, self._averager, self._moder, self._podr, self._distr, self._spectrar, self._xspectrar, self._fluxr, self._budgetr, self._tracker,
-                            self._tracers, self._vortexr) if r is not None]
+        """The attached riders (fs.riders.Rider) in their fixed order, that of RIDER_ATTRS."""
+        return [r for r in _rider_slots(self) if r is not None]
 
     def _capturing(self):
         return getattr(self._dev, "capturing", False)
@@ -132,6 +139,30 @@ class FluidSimulator:
         if start_step < 0:
             raise ValueError("start_step must be >= 0")
         return every, start_step
+
+    def _attached(self, attr, what, start):
+        """The attached rider of a kind, or RuntimeError "no `what`: call `start`() first"."""
+        r = getattr(self, attr)
+        if r is None:
+            raise RuntimeError(f"no {what}: call {start}() first")
+        return r
+
+    def _once(self, name, create, launch, read, free):
+        """The one-shot calls (body_snapshot, find_vortices, histogram, spectrum, ...): refused during a graph capture under the caller's
+        `name`; then a temporary device object from create(), one eager launch(obj) that is never part of a logged period, read(obj), and
+        free(obj) whatever happened -> (what read returned, the freed object: its parameters stay readable)."""
+        dev = self._dev
+        self._not_capturing(name)
+        obj = create()
+        try:
+            saved, dev._oplog = getattr(dev, "_oplog", None), None
+            try:
+                launch(obj)
+            finally:
+                dev._oplog = saved
+            return read(obj), obj
+        finally:
+            free(obj)
 
     def _update(self):
         """One solver step, then the launches of every attached rider: what step(), the periods capture_period() captures and the slab
@@ -550,21 +581,16 @@ class FluidSimulator:
         graph and no attached tracker, and leaves a deferred limit_field deferred (the kernel limits the values it reads).  Not allowed
         during a graph capture."""
         dev, s = self._dev, self._solver
-        self._not_capturing("body_snapshot")
+        self._not_capturing("body_snapshot")      # (before the box is looked at)
         body_box, faces, centre = self._body_faces(body_box, center)
         v, p = s.get_fields()[:2]
-        lo = dev.loads_create(faces, centre, 1, 1, 0)
-        try:
+
+        def read(lo):
             one = Tracker(dev, lo, faces, body_box, centre, 1, 0, s.dt)
-            saved, dev._oplog = getattr(dev, "_oplog", None), None      # (never part of a logged period)
-            try:
-                dev.loads_record(lo, s.dx, 1.0 / s.re, v, p)
-            finally:
-                dev._oplog = saved
             one.drain()
-            data, sums = one.data(), one.sums()
-        finally:
-            dev.loads_free(lo)
+            return one.data(), one.sums()
+        (data, sums), _ = self._once("body_snapshot", lambda: dev.loads_create(faces, centre, 1, 1, 0),
+                                     lambda lo: dev.loads_record(lo, s.dx, 1.0 / s.re, v, p), read, dev.loads_free)
         out = {k: float(a[0]) for k, a in data.items() if k not in ("step", "time")}
         out["faces"] = faces.copy()
         out.update(face_geometry(faces, centre))
@@ -586,9 +612,7 @@ class FluidSimulator:
         self._averager = Averager(dev, dev.mean_create(every, start_step), every, start_step)
 
     def _avg(self):
-        if self._averager is None:
-            raise RuntimeError("no average: call start_averaging() first")
-        return self._averager
+        return self._attached("_averager", "average", "start_averaging")
 
     def averages(self, local=False):
         """The averages so far (a download of 56 bytes per cell): {"samples": int, "steps": int (steps since start_averaging), "u", "w",
@@ -657,9 +681,7 @@ class FluidSimulator:
         self._moder = Modes(dev, dev.modes_create(np.stack([cd, sd], axis=1), every, start_step), freqs, every, start_step)
 
     def _modes(self):
-        if self._moder is None:
-            raise RuntimeError("no modes: call start_modes() first")
-        return self._moder
+        return self._attached("_moder", "modes", "start_modes")
 
     def modes(self, local=False):
         """The fit so far (a download of 24 (1 + 2K) bytes per cell): {"frequencies", "samples": int, "steps": int (steps since start_modes),
@@ -732,9 +754,7 @@ class FluidSimulator:
         self._podr = Pod(dev, dev.pod_create(snapshots, every, start_step), every, start_step)
 
     def _pod(self):
-        if self._podr is None:
-            raise RuntimeError("no POD: call start_pod() first")
-        return self._podr
+        return self._attached("_podr", "POD", "start_pod")
 
     def pod(self, n_modes=None, subtract_mean=True):
         """The proper orthogonal decomposition of the n resident snapshots (fs.pod.decompose; the download is the n x n Gram matrix alone):
@@ -870,18 +890,13 @@ class FluidSimulator:
         no graph and no attached tracker, and leaves a deferred limit_field deferred.  vortex_labels() returns its planes until the next
         call.  Not allowed during a graph capture."""
         dev, s = self._dev, self._solver
-        self._not_capturing("find_vortices")
-        vx = self._vortex_create(threshold, criterion, 1, 0, min_area, max_vortices, max_components, omega_max, 1)
-        try:
-            saved, dev._oplog = getattr(dev, "_oplog", None), None      # (never part of a logged period)
-            try:
-                dev.vortex_launch(vx, s.dx, s.get_fields()[0])
-            finally:
-                dev._oplog = saved
+
+        def read(vx):
             words, _, _ = dev.vortex_read(vx)
             self._found_planes = dev.vortex_labels(vx)
-        finally:
-            dev.vortex_free(vx)
+            return words
+        words, vx = self._once("find_vortices", lambda: self._vortex_create(threshold, criterion, 1, 0, min_area, max_vortices, max_components, omega_max, 1),
+                               lambda vx: dev.vortex_launch(vx, s.dx, s.get_fields()[0]), read, dev.vortex_free)
         return assemble(words, vx.max_vortices, vx.exponent, s.dx, dev.nx, np.zeros(len(words), np.int64), s.dt)
 
     def vortex_labels(self):
@@ -923,9 +938,7 @@ class FluidSimulator:
         self._distr = _dist.Distributions(dev, dev.dist_create(channels, every, start_step), every, start_step)
 
     def _dist(self):
-        if self._distr is None:
-            raise RuntimeError("no distributions: call start_distributions() first")
-        return self._distr
+        return self._attached("_distr", "distributions", "start_distributions")
 
     def distributions(self):
         """The tables so far, one dict per channel: {"counts": int64 (B,) or (Ba, Bb), "below", "above" (joint: "outside"), "nan",
@@ -951,7 +964,7 @@ class FluidSimulator:
         (order_statistics ranks 0 and n - 1) give [min, nextafter(max, +inf)) - ValueError when either is infinite or no value is there.
         Not allowed during a graph capture."""
         dev, s = self._dev, self._solver
-        self._not_capturing("histogram")
+        self._not_capturing("histogram")      # (before order_statistics would refuse under its own name)
         if range is None:
             if against is not None:
                 raise ValueError("range=None is for 1-D histograms: a joint table needs both ranges")
@@ -963,17 +976,8 @@ class FluidSimulator:
                 raise ValueError(f"the values of {quantity!r} reach ({lo}, {hi}): give a finite range")
             range = (float(lo), math.nextafter(float(hi), math.inf))
         spec = {"quantity": quantity, "bins": bins, "range": range, "box": box, "against": against}
-        d = dev.dist_create(spec, 1, 0)
-        try:
-            saved, dev._oplog = getattr(dev, "_oplog", None), None      # (never part of a logged period)
-            try:
-                v, p = s.get_fields()[:2]
-                dev.dist_launch(d, s.dx, v, p)
-            finally:
-                dev._oplog = saved
-            counts, tails, _, samples = dev.dist_read(d, 0)
-        finally:
-            dev.dist_free(d)
+        (counts, tails, _, samples), d = self._once("histogram", lambda: dev.dist_create(spec, 1, 0), lambda d: dev.dist_launch(d, s.dx, *s.get_fields()[:2]),
+                                                    lambda d: dev.dist_read(d, 0), dev.dist_free)
         return _dist.result(dev, d.channels[0], counts, tails, samples, np.zeros(samples, np.int64))
 
     def order_statistics(self, quantity, ranks, box=None):
@@ -1027,9 +1031,7 @@ class FluidSimulator:
         self._spectrar = _spectra.Spectra(dev, _spectra.create(dev, box, window, detrend, every, start_step), window, self._solver.dx)
 
     def _spectra(self):
-        if self._spectrar is None:
-            raise RuntimeError("no spectrum: call start_spectra() first")
-        return self._spectrar
+        return self._attached("_spectrar", "spectrum", "start_spectra")
 
     def spectra(self):
         """The spectrum so far: {"power": float64 (Nx, Ny), the mean over the samples of (P[k] + P[-k]) / 2, indexed like np.fft.fft2;
@@ -1052,17 +1054,8 @@ class FluidSimulator:
 
     def _spectrum_once(self, name, box, window, detrend, read):
         dev = self._dev
-        self._not_capturing(name)
-        sp = _spectra.create(dev, box, window, detrend, 1, 0)
-        try:
-            saved, dev._oplog = getattr(dev, "_oplog", None), None      # (never part of a logged period)
-            try:
-                dev.spec_launch(sp, self._solver.get_fields()[0])
-            finally:
-                dev._oplog = saved
-            return read(sp)
-        finally:
-            dev.spec_free(sp)
+        return self._once(name, lambda: _spectra.create(dev, box, window, detrend, 1, 0), lambda sp: dev.spec_launch(sp, self._solver.get_fields()[0]),
+                          read, dev.spec_free)[0]
 
     def spectrum(self, box, window="hann", detrend=True):
         """The spectrum of the fields as they are now: the dict spectra() returns, with "samples" 1 and "sample_steps" [0] (the call counts
@@ -1096,9 +1089,7 @@ class FluidSimulator:
         self._xspectrar = _spectra.CrossSpectra(dev, xs, window)
 
     def _cross_spectra(self):
-        if self._xspectrar is None:
-            raise RuntimeError("no cross-spectrum: call start_cross_spectra() first")
-        return self._xspectrar
+        return self._attached("_xspectrar", "cross-spectrum", "start_cross_spectra")
 
     def cross_spectra(self):
         """The cross-spectrum so far: the dict of fs.spectra.cross_result - "spectrum_a", "spectrum_b", "co", "quad" per bin, the shell sums
@@ -1118,19 +1109,9 @@ class FluidSimulator:
         self._detach(self, "_xspectrar", "stop_cross_spectra")
 
     def _cross_once(self, name, box, pair, window, detrend, read):
-        dev = self._dev
-        self._not_capturing(name)
-        xs = _spectra.create_cross(dev, box, pair, self._solver.dx, window, detrend, 1, 0)
-        try:
-            saved, dev._oplog = getattr(dev, "_oplog", None), None      # (never part of a logged period)
-            try:
-                v, p = self._solver.get_fields()[:2]
-                dev.xspec_launch(xs, v, p)
-            finally:
-                dev._oplog = saved
-            return read(xs), xs
-        finally:
-            dev.xspec_free(xs)
+        dev, s = self._dev, self._solver
+        return self._once(name, lambda: _spectra.create_cross(dev, box, pair, s.dx, window, detrend, 1, 0),
+                          lambda xs: dev.xspec_launch(xs, *s.get_fields()[:2]), read, dev.xspec_free)
 
     def cross_spectrum(self, box, pair=("u", "w"), window="hann", detrend=True):
         """The cross-spectrum of the fields as they are now: the dict cross_spectra() returns, with "samples" 1 and "sample_steps" [0].
@@ -1171,9 +1152,7 @@ class FluidSimulator:
         self._fluxr = _fluxes.ScaleFluxes(dev, dev.flux_create(box, half_widths, self._solver.dx, every, start_step), self._grid_shape())
 
     def _scale_fluxes(self):
-        if self._fluxr is None:
-            raise RuntimeError("no scale fluxes: call start_scale_fluxes() first")
-        return self._fluxr
+        return self._attached("_fluxr", "scale fluxes", "start_scale_fluxes")
 
     def scale_fluxes(self):
         """The fluxes so far: {"half_widths"; "widths": (2 r + 1) dx; "samples", "sample_steps", "box"; "valid": per half-width the
@@ -1196,18 +1175,9 @@ class FluidSimulator:
         self._detach(self, "_fluxr", "stop_scale_fluxes")
 
     def _flux_once(self, name, box, half_widths, read):
-        dev = self._dev
-        self._not_capturing(name)
-        fx = dev.flux_create(box, half_widths, self._solver.dx, 1, 0)
-        try:
-            saved, dev._oplog = getattr(dev, "_oplog", None), None      # (never part of a logged period)
-            try:
-                dev.flux_launch(fx, self._solver.get_fields()[0])
-            finally:
-                dev._oplog = saved
-            return read(fx), fx
-        finally:
-            dev.flux_free(fx)
+        dev, s = self._dev, self._solver
+        return self._once(name, lambda: dev.flux_create(box, half_widths, s.dx, 1, 0), lambda fx: dev.flux_launch(fx, s.get_fields()[0]), read,
+                          dev.flux_free)
 
     def scale_flux(self, box, half_widths):
         """The fluxes of the fields as they are now: the dict scale_fluxes() returns, with "samples" 1 and "sample_steps" [0] (the call
@@ -1255,9 +1225,7 @@ class FluidSimulator:
         self._budgetr = _budgets.Budget(dev, dev.budget_create(box, self._solver.dx, every, start_step), fluid, self._solver.re)
 
     def _budget(self):
-        if self._budgetr is None:
-            raise RuntimeError("no budget: call start_budget() first")
-        return self._budgetr
+        return self._attached("_budgetr", "budget", "start_budget")
 
     def budget(self):
         """The budget so far (fs.budgets.derive_budget): float64 (Nx, Ny) arrays over the box - the means "U", "W", "P", the central moments
@@ -1287,20 +1255,11 @@ class FluidSimulator:
         counts no steps; with one sample every fluctuation is zero - the use is the raw "sums" and the means).  One temporary object of
         168 bytes per cell of the box, one eager launch, a read and a free: changes no field, no graph and no attached rider, and leaves a
         deferred limit_field deferred.  Not allowed during a graph capture."""
-        dev = self._dev
-        self._not_capturing("budget_sample")
+        dev, s = self._dev, self._solver
+        self._not_capturing("budget_sample")      # (before the box is looked at)
         box, fluid = self._budget_box(box)
-        bg = dev.budget_create(box, self._solver.dx, 1, 0)
-        try:
-            saved, dev._oplog = getattr(dev, "_oplog", None), None      # (never part of a logged period)
-            try:
-                v, p = self._solver.get_fields()[:2]
-                dev.budget_launch(bg, v, p)
-            finally:
-                dev._oplog = saved
-            sums, _, samples = dev.budget_read(bg)
-        finally:
-            dev.budget_free(bg)
+        (sums, _, samples), _ = self._once("budget_sample", lambda: dev.budget_create(box, s.dx, 1, 0), lambda bg: dev.budget_launch(bg, *s.get_fields()[:2]),
+                                           dev.budget_read, dev.budget_free)
         return _budgets.budget_result(sums, samples, np.zeros(samples, np.int64), box, fluid, self._solver.dx, self._solver.re)
 
     # -- flow maps and FTLE fields (new): a lattice of particles carried through the POD's resident snapshots on the device --------------
@@ -1420,9 +1379,7 @@ class FluidSimulator:
         self._tracers = Tracers(dev, tset, seeds, respawn, max_age, sort_every, tau=tau.copy(), gravity=gravity, deposits=deposits)
 
     def _trc(self):
-        if self._tracers is None:
-            raise RuntimeError("no tracers: call seed_tracers() first")
-        return self._tracers
+        return self._attached("_tracers", "tracers", "seed_tracers")
 
     def tracers(self):
         """The particles now (one download): {"x", "y": float64 (N,) in cell units, "age": int32 steps since the seed or the last respawn

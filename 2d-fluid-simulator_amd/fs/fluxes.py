@@ -7,7 +7,7 @@ count as fluid at rest.  This module holds the rider and the result dict.  Drive
 reset_scale_fluxes / stop_scale_fluxes / scale_flux / filtered_fields."""
 import numpy as np
 
-from .riders import Rider, samples_after
+from .riders import BOX, CountedRider, Param
 
 PLANES = ("pi", "zf", "k")
 FILTERED = ("u", "w", "om", "uu", "uw", "ww", "uom", "wom")
@@ -45,68 +45,22 @@ def flux_result(sums, samples, sample_steps, box, half_widths, dx, shape):
     return out
 
 
-class ScaleFluxes(Rider):
-    """The accumulated scale-to-scale fluxes of a FluidSimulator (start_scale_fluxes): the device planes and their parameters.  No ring:
-    room() is None and run() is not cut by it."""
+class ScaleFluxes(CountedRider):
+    """The accumulated scale-to-scale fluxes of a FluidSimulator (start_scale_fluxes): the device planes and their parameters.
+    held(z) -> (box, half_widths, every, start), or None."""
+    kind, payload, noun, plural = "flux", "sums", "scale fluxes", True
+    params = (BOX, Param("half_widths", BOX.write, BOX.read, "{theirs} accumulated with the half_widths {0}, {ours} with {1}"))
 
     def __init__(self, dev, flux, shape):
-        self.dev, self.flux, self.shape = dev, flux, tuple(shape)
-        self.every, self.start_step = int(flux.every), int(flux.start)
-        self.base = 0              # samples taken before the last reset (sample_steps)
+        super().__init__(dev, flux, flux.every, flux.start)
+        self.flux, self.shape = flux, tuple(shape)
 
-    @property
-    def token(self):
-        return ("flux", self.flux.serial)
+    def attached(self):
+        return tuple(self.flux.box), tuple(self.flux.half_widths)
 
     def launch(self, sim):
         self.dev.flux_launch(self.flux, sim._solver.get_fields()[0])
 
-    def free(self):
-        self.dev.flux_free(self.flux)
-
-    def sample_steps(self, samples):
-        """The step (counted from start_scale_fluxes, from 1) of every sample in the planes, int64 (samples,)."""
-        k = self.base + np.arange(int(samples), dtype=np.int64)
-        return self.start_step + (k + 1) * self.every
-
     def data(self):
         sums, _, samples = self.dev.flux_read(self.flux)
         return flux_result(sums, samples, self.sample_steps(samples), self.flux.box, self.flux.half_widths, self.flux.dx, self.shape)
-
-    def reset(self):
-        _, launches, _ = self.dev.flux_read(self.flux, sums=False)
-        self.dev.flux_reset(self.flux)
-        self.base = samples_after(launches, self.every, self.start_step)
-
-    def checkpoint(self):
-        sums, launches, samples = self.dev.flux_get(self.flux)
-        return {"flux.sums": sums, "flux.launches": np.array(launches), "flux.samples": np.array(samples), "flux.base": np.array(self.base),
-                "flux.box": np.array(self.flux.box, np.int64), "flux.half_widths": np.array(self.flux.half_widths, np.int64),
-                "flux.every": np.array(self.every), "flux.start": np.array(self.start_step)}
-
-    @staticmethod
-    def held(z):
-        """-> (box, half_widths, every, start), or None."""
-        if "flux.sums" not in z:
-            return None
-        return (tuple(int(b) for b in np.asarray(z["flux.box"])), tuple(int(r) for r in np.asarray(z["flux.half_widths"])),
-                int(z["flux.every"]), int(z["flux.start"]))
-
-    def restore(self, z):
-        """Refused (ValueError) before any device work when the checkpoint's box, half-widths, every or start_step are not the attached
-        ones."""
-        held = self.held(z)
-        if held is None:
-            raise ValueError("the checkpoint holds no scale fluxes")
-        box, half_widths, every, start = held
-        if box != tuple(self.flux.box):
-            raise ValueError(f"the checkpoint's scale fluxes were accumulated over the box {box}, the attached ones over {tuple(self.flux.box)}")
-        if half_widths != tuple(self.flux.half_widths):
-            raise ValueError(f"the checkpoint's scale fluxes were accumulated with the half_widths {half_widths}, the attached ones with "
-                             f"{tuple(self.flux.half_widths)}")
-        if (every, start) != (self.every, self.start_step):
-            raise ValueError(f"the checkpoint's scale fluxes sample every {every} from {start}, the attached ones every {self.every} from "
-                             f"{self.start_step}")
-        self.dev.flux_set(self.flux, z["flux.sums"], int(z["flux.launches"]), int(z["flux.samples"]))
-        self.base = int(z["flux.base"])
-        return int(z["flux.samples"])

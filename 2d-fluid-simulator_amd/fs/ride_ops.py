@@ -94,43 +94,65 @@ class DistChannel(collections.namedtuple("DistChannel", "quantity bins lo hi qua
         return (self.bins, self.bins_b) if self.joint else (self.bins,)
 
 
-class Spec(_Handle):
+class _Planes(_Handle):
+    """A device object that accumulates float64 planes over a cell box (RideOps._planes_*): `kind`, the stem of its calls and `_p_*`
+    primitives; the box and its sides (nx, ny); `shape`, that of the planes on the host, (..., nx, ny); `y_major`: the device keeps every
+    plane (ny, nx) and hands them over flat."""
+    kind, y_major = None, False
+
+    def __init__(self, h, box, lead=()):
+        super().__init__(h)
+        self.box = tuple(box)
+        self.nx, self.ny = box[2] - box[0], box[3] - box[1]
+        self.shape = tuple(lead) + (self.nx, self.ny)
+        self.words = math.prod(self.shape)
+
+    def to_host(self, flat):
+        if self.y_major:
+            return np.ascontiguousarray(flat.reshape(self.shape[:-2] + (self.ny, self.nx)).swapaxes(-1, -2))
+        return flat.reshape(self.shape)
+
+    def to_device(self, planes):
+        return np.ascontiguousarray(planes.swapaxes(-1, -2)).ravel() if self.y_major else np.ascontiguousarray(planes)
+
+
+class Spec(_Planes):
     """Device planes of an energy spectrum (DeviceBase.spec_create): handle, the cell box, its sides (nx, ny), detrend, every, start."""
+    kind = "spec"
 
     def __init__(self, h, box, detrend, every, start):
-        super().__init__(h)
-        self.box, self.detrend, self.every, self.start = tuple(box), bool(detrend), every, start
-        self.nx, self.ny = box[2] - box[0], box[3] - box[1]
+        super().__init__(h, box)
+        self.detrend, self.every, self.start = bool(detrend), every, start
 
 
-class XSpec(_Handle):
+class XSpec(_Planes):
     """Device planes of a cross-spectrum (DeviceBase.xspec_create): handle, the cell box, its sides (nx, ny), the quantity indices (qa, qb; qb -1:
     one scalar), the number of accumulator planes, dx, detrend, every, start."""
+    kind = "xspec"
 
     def __init__(self, h, box, qa, qb, dx, detrend, every, start):
-        super().__init__(h)
-        self.box, self.qa, self.qb, self.dx, self.detrend, self.every, self.start = tuple(box), qa, qb, dx, bool(detrend), every, start
-        self.nx, self.ny = box[2] - box[0], box[3] - box[1]
         self.planes = RideOps.XSPEC_NPLANE if qb >= 0 else 1
+        super().__init__(h, box, (self.planes,))
+        self.qa, self.qb, self.dx, self.detrend, self.every, self.start = qa, qb, dx, bool(detrend), every, start
 
 
-class Flux(_Handle):
+class Flux(_Planes):
     """Device planes of the scale-to-scale fluxes (DeviceBase.flux_create): handle, the cell box, its sides (nx, ny), the half-widths, dx,
     every, start."""
+    kind, y_major = "flux", True
 
     def __init__(self, h, box, half_widths, dx, every, start):
-        super().__init__(h)
-        self.box, self.half_widths, self.dx, self.every, self.start = tuple(box), tuple(half_widths), dx, every, start
-        self.nx, self.ny = box[2] - box[0], box[3] - box[1]
+        super().__init__(h, box, (len(half_widths), RideOps.FLUX_NSUM))
+        self.half_widths, self.dx, self.every, self.start = tuple(half_widths), dx, every, start
 
 
-class Budget(_Handle):
+class Budget(_Planes):
     """Device planes of the kinetic-energy budget (DeviceBase.budget_create): handle, the cell box, its sides (nx, ny), dx, every, start."""
+    kind, y_major = "budget", True
 
     def __init__(self, h, box, dx, every, start):
-        super().__init__(h)
-        self.box, self.dx, self.every, self.start = tuple(box), dx, every, start
-        self.nx, self.ny = box[2] - box[0], box[3] - box[1]
+        super().__init__(h, box, (RideOps.BUDGET_NPLANE,))
+        self.dx, self.every, self.start = dx, every, start
 
 
 class FlowMap(_Handle):
@@ -809,6 +831,39 @@ class RideOps:
             raise ValueError(f"ranks must be >= 0 and ascending, got {ranks}")
         return self._p_dist_select(q, box, self._limit_of(v), float(dx), v._h, p._h, ranks)
 
+    # ---- what the plane accumulators share (_Planes: spec_*, xspec_*, flux_*, budget_*): read, get, set, reset, free ---------------------------
+    @staticmethod
+    def _check_dx(dx):
+        dx = float(dx)
+        if not (math.isfinite(dx) and dx > 0.0):
+            raise ValueError(f"dx must be finite and > 0, got {dx}")
+        return dx
+
+    def _planes_read(self, obj, payload, what):
+        self._host_only(f"{obj.kind}_read during a graph capture: {what} a download (read between captures / replays)")
+        flat, launches, samples = getattr(self, f"_p_{obj.kind}_read")(obj._h, obj.words if payload else 0)
+        return (obj.to_host(flat) if payload else None), int(launches), int(samples)
+
+    def _planes_get(self, obj):
+        self._host_only(f"{obj.kind}_get during a graph capture")
+        flat, launches, samples = getattr(self, f"_p_{obj.kind}_get")(obj._h, obj.words)
+        return obj.to_host(flat), int(launches), int(samples)
+
+    def _planes_set(self, obj, planes, launches, samples, noun):
+        self._host_only(f"{obj.kind}_set during a graph capture")
+        planes = np.asarray(planes, np.float64)
+        if planes.shape != obj.shape:
+            raise ValueError(f"expected {noun} of shape {obj.shape}, got {planes.shape}")
+        launches, samples = self._check_counters(launches, samples)
+        getattr(self, f"_p_{obj.kind}_set")(obj._h, obj.to_device(planes), launches, samples)
+
+    def _planes_reset(self, obj):
+        self._host_only(f"{obj.kind}_reset during a graph capture")
+        getattr(self, f"_p_{obj.kind}_reset")(obj._h)
+
+    def _planes_free(self, obj):
+        self._release(obj, getattr(self, f"_p_{obj.kind}_free"))
+
     # ---- energy spectra (include/fs_hip.h fs_spec_*): the windowed FFT of the velocity over a box, accumulated power; csrc/fs_spec.h ----
     SPEC_MIN_N, SPEC_MAX_N = 8, 4096
 
@@ -859,9 +914,7 @@ class RideOps:
     def spec_read(self, sp, power=True):
         """-> (power float64 (Nx, Ny): the sums of |Z'|^2 over the samples, not symmetrised - None with power=False -, launches, samples).
         Not allowed during a graph capture."""
-        self._host_only("spec_read during a graph capture: the power plane is a download (read between captures / replays)")
-        plane, launches, samples = self._p_spec_read(sp._h, sp.nx * sp.ny if power else 0)
-        return (plane.reshape(sp.nx, sp.ny) if power else None), int(launches), int(samples)
+        return self._planes_read(sp, power, "the power plane is")
 
     def spec_plane(self, sp):
         """-> Z' of the last sampling launch, complex128 (Nx, Ny) (zeros before the first).  Not allowed during a graph capture."""
@@ -870,26 +923,18 @@ class RideOps:
 
     def spec_get(self, sp):
         """-> (the power plane float64 (Nx, Ny), launches, samples), for checkpoints."""
-        self._host_only("spec_get during a graph capture")
-        plane, launches, samples = self._p_spec_get(sp._h, sp.nx * sp.ny)
-        return plane.reshape(sp.nx, sp.ny), int(launches), int(samples)
+        return self._planes_get(sp)
 
     def spec_set(self, sp, power, launches, samples):
         """Restore what spec_get returned (resume)."""
-        self._host_only("spec_set during a graph capture")
-        power = np.ascontiguousarray(power, np.float64)
-        if power.shape != (sp.nx, sp.ny):
-            raise ValueError(f"expected a power plane of shape {(sp.nx, sp.ny)}, got {power.shape}")
-        launches, samples = self._check_counters(launches, samples)
-        self._p_spec_set(sp._h, power, launches, samples)
+        self._planes_set(sp, power, launches, samples, "a power plane")
 
     def spec_reset(self, sp):
         """Power plane and sample count to zero; the launch count runs on.  Not allowed during a graph capture."""
-        self._host_only("spec_reset during a graph capture")
-        self._p_spec_reset(sp._h)
+        self._planes_reset(sp)
 
     def spec_free(self, sp):
-        self._release(sp, self._p_spec_free)
+        self._planes_free(sp)
 
     # ---- cross-spectra (include/fs_hip.h fs_xspec_*): the packed FFT of two quantities over a box, split and accumulated; csrc/fs_xspec.h ----
     XSPEC_NPLANE = 4
@@ -913,9 +958,7 @@ class RideOps:
         device call.  Single-context grids only (FsError on a slab); not allowed during a graph capture."""
         box, tabs, c1x, c1y, every, start = RideOps._spec_checked(self, box, (wx, wy, twx, twy), c1x, c1y, every, start)
         qa, qb = RideOps.xspec_pair(self, pair)
-        dx = float(dx)
-        if not (math.isfinite(dx) and dx > 0.0):
-            raise ValueError(f"dx must be finite and > 0, got {dx}")
+        dx = RideOps._check_dx(dx)
         RideOps._host_only(self, "xspec_create during a graph capture")
         RideOps._single_context(self, "cross-spectra need", "the transform along y crosses the ranks")
         h = self._p_xspec_create(box, qa, qb, dx, *tabs, c1x, c1y, bool(detrend), every, start)
@@ -930,9 +973,7 @@ class RideOps:
     def xspec_read(self, xs, sums=True):
         """-> (sums float64 (planes, Nx, Ny): Paa, Pbb, Cre, Cim over the samples (one scalar: Paa alone) - None with sums=False -, launches,
         samples).  Not allowed during a graph capture."""
-        self._host_only("xspec_read during a graph capture: the planes are a download (read between captures / replays)")
-        planes, launches, samples = self._p_xspec_read(xs._h, xs.planes * xs.nx * xs.ny if sums else 0)
-        return (planes.reshape(xs.planes, xs.nx, xs.ny) if sums else None), int(launches), int(samples)
+        return self._planes_read(xs, sums, "the planes are")
 
     def xspec_plane(self, xs):
         """-> Z' of the last sampling launch, complex128 (Nx, Ny) (zeros before the first).  Not allowed during a graph capture."""
@@ -941,26 +982,18 @@ class RideOps:
 
     def xspec_get(self, xs):
         """-> (the accumulator planes float64 (planes, Nx, Ny), launches, samples), for checkpoints."""
-        self._host_only("xspec_get during a graph capture")
-        planes, launches, samples = self._p_xspec_get(xs._h, xs.planes * xs.nx * xs.ny)
-        return planes.reshape(xs.planes, xs.nx, xs.ny), int(launches), int(samples)
+        return self._planes_get(xs)
 
     def xspec_set(self, xs, sums, launches, samples):
         """Restore what xspec_get returned (resume)."""
-        self._host_only("xspec_set during a graph capture")
-        sums = np.ascontiguousarray(sums, np.float64)
-        if sums.shape != (xs.planes, xs.nx, xs.ny):
-            raise ValueError(f"expected accumulator planes of shape {(xs.planes, xs.nx, xs.ny)}, got {sums.shape}")
-        launches, samples = self._check_counters(launches, samples)
-        self._p_xspec_set(xs._h, sums, launches, samples)
+        self._planes_set(xs, sums, launches, samples, "accumulator planes")
 
     def xspec_reset(self, xs):
         """Accumulators and sample count to zero; the launch count runs on.  Not allowed during a graph capture."""
-        self._host_only("xspec_reset during a graph capture")
-        self._p_xspec_reset(xs._h)
+        self._planes_reset(xs)
 
     def xspec_free(self, xs):
-        self._release(xs, self._p_xspec_free)
+        self._planes_free(xs)
 
     # ---- scale-to-scale fluxes (include/fs_hip.h fs_flux_*): box filters of u, w and the vorticity, the sub-filter stresses, accumulated
     #      PI, ZF and K per cell of a box; csrc/fs_flux.h ----
@@ -1006,9 +1039,7 @@ class RideOps:
         call.  Single-context grids only (FsError on a slab); not allowed during a graph capture."""
         box = RideOps.flux_box(self, box)
         hw = RideOps.flux_half_widths(self, box, half_widths)
-        dx = float(dx)
-        if not (math.isfinite(dx) and dx > 0.0):
-            raise ValueError(f"dx must be finite and > 0, got {dx}")
+        dx = RideOps._check_dx(dx)
         every, start = RideOps._check_cadence(every, start)
         RideOps._host_only(self, "flux_create during a graph capture")
         RideOps._single_context(self, "scale fluxes need", "the filter along y crosses the ranks")
@@ -1021,17 +1052,10 @@ class RideOps:
         the values it reads.  Not a _run: no flush, no exchange, no ghost row (writes no field)."""
         self._ride("flux_launch", (fx._h, self._limit_of(v), v._h))
 
-    def _flux_sums(self, fx, flat):
-        nr = len(fx.half_widths)
-        return np.ascontiguousarray(flat.reshape(nr, RideOps.FLUX_NSUM, fx.ny, fx.nx).transpose(0, 1, 3, 2))
-
     def flux_read(self, fx, sums=True):
         """-> (sums float64 (n_r, 3, Nx, Ny): PI, ZF, K over the samples per half-width - None with sums=False -, launches, samples).  Not
         allowed during a graph capture."""
-        self._host_only("flux_read during a graph capture: the planes are a download (read between captures / replays)")
-        words = len(fx.half_widths) * RideOps.FLUX_NSUM * fx.nx * fx.ny
-        flat, launches, samples = self._p_flux_read(fx._h, words if sums else 0)
-        return (RideOps._flux_sums(self, fx, flat) if sums else None), int(launches), int(samples)
+        return self._planes_read(fx, sums, "the planes are")
 
     def flux_filtered(self, fx, half_width):
         """-> the eight filtered planes of `half_width` (one of the object's) over the box from the last sampling launch, float64
@@ -1044,27 +1068,18 @@ class RideOps:
 
     def flux_get(self, fx):
         """-> (the sums float64 (n_r, 3, Nx, Ny), launches, samples), for checkpoints."""
-        self._host_only("flux_get during a graph capture")
-        flat, launches, samples = self._p_flux_get(fx._h, len(fx.half_widths) * RideOps.FLUX_NSUM * fx.nx * fx.ny)
-        return RideOps._flux_sums(self, fx, flat), int(launches), int(samples)
+        return self._planes_get(fx)
 
     def flux_set(self, fx, sums, launches, samples):
         """Restore what flux_get returned (resume)."""
-        self._host_only("flux_set during a graph capture")
-        sums = np.asarray(sums, np.float64)
-        shape = (len(fx.half_widths), RideOps.FLUX_NSUM, fx.nx, fx.ny)
-        if sums.shape != shape:
-            raise ValueError(f"expected sums of shape {shape}, got {sums.shape}")
-        launches, samples = self._check_counters(launches, samples)
-        self._p_flux_set(fx._h, np.ascontiguousarray(sums.transpose(0, 1, 3, 2)).ravel(), launches, samples)
+        self._planes_set(fx, sums, launches, samples, "sums")
 
     def flux_reset(self, fx):
         """Sums and sample count to zero; the launch count runs on.  Not allowed during a graph capture."""
-        self._host_only("flux_reset during a graph capture")
-        self._p_flux_reset(fx._h)
+        self._planes_reset(fx)
 
     def flux_free(self, fx):
-        self._release(fx, self._p_flux_free)
+        self._planes_free(fx)
 
     # ---- kinetic-energy budget (include/fs_hip.h fs_budget_*): 21 planes of raw moments over the fluid cells of a box, one launch per step;
     #      csrc/fs_budget.h ----
@@ -1076,9 +1091,7 @@ class RideOps:
         refused by the caller that knows the mask (FluidSimulator) and by the library.  Single-context grids only (FsError on a slab); not
         allowed during a graph capture."""
         box = RideOps.flux_box(self, box)
-        dx = float(dx)
-        if not (math.isfinite(dx) and dx > 0.0):
-            raise ValueError(f"dx must be finite and > 0, got {dx}")
+        dx = RideOps._check_dx(dx)
         every, start = RideOps._check_cadence(every, start)
         RideOps._host_only(self, "budget_create during a graph capture")
         RideOps._single_context(self, "the budget needs", "the gradient along y crosses the ranks")
@@ -1091,39 +1104,25 @@ class RideOps:
         (writes no field)."""
         self._ride("budget_launch", (bg._h, self._limit_of(v), v._h, p._h))
 
-    def _budget_sums(self, bg, flat):
-        return np.ascontiguousarray(flat.reshape(RideOps.BUDGET_NPLANE, bg.ny, bg.nx).transpose(0, 2, 1))
-
     def budget_read(self, bg, sums=True):
         """-> (sums float64 (21, Nx, Ny) in the order of fs.budgets.PLANES - None with sums=False -, launches, samples).  Not allowed during
         a graph capture."""
-        self._host_only("budget_read during a graph capture: the planes are a download (read between captures / replays)")
-        flat, launches, samples = self._p_budget_read(bg._h, RideOps.BUDGET_NPLANE * bg.nx * bg.ny if sums else 0)
-        return (RideOps._budget_sums(self, bg, flat) if sums else None), int(launches), int(samples)
+        return self._planes_read(bg, sums, "the planes are")
 
     def budget_get(self, bg):
         """-> (the sums float64 (21, Nx, Ny), launches, samples), for checkpoints."""
-        self._host_only("budget_get during a graph capture")
-        flat, launches, samples = self._p_budget_get(bg._h, RideOps.BUDGET_NPLANE * bg.nx * bg.ny)
-        return RideOps._budget_sums(self, bg, flat), int(launches), int(samples)
+        return self._planes_get(bg)
 
     def budget_set(self, bg, sums, launches, samples):
         """Restore what budget_get returned (resume)."""
-        self._host_only("budget_set during a graph capture")
-        sums = np.asarray(sums, np.float64)
-        shape = (RideOps.BUDGET_NPLANE, bg.nx, bg.ny)
-        if sums.shape != shape:
-            raise ValueError(f"expected sums of shape {shape}, got {sums.shape}")
-        launches, samples = self._check_counters(launches, samples)
-        self._p_budget_set(bg._h, np.ascontiguousarray(sums.transpose(0, 2, 1)).ravel(), launches, samples)
+        self._planes_set(bg, sums, launches, samples, "sums")
 
     def budget_reset(self, bg):
         """Sums and sample count to zero; the launch count runs on.  Not allowed during a graph capture."""
-        self._host_only("budget_reset during a graph capture")
-        self._p_budget_reset(bg._h)
+        self._planes_reset(bg)
 
     def budget_free(self, bg):
-        self._release(bg, self._p_budget_free)
+        self._planes_free(bg)
 
     # ---- flow maps (include/fs_hip.h fs_flowmap_*): a lattice of particles carried through the resident snapshots of a POD; csrc/fs_lcs.h ----
     def flowmap_create(self, box=None, refine=1):

@@ -13,7 +13,7 @@ One complex transform carries both components: with Z = FFT2(u + i w), U[k] = (Z
 (split), so |U[k]|^2 + |W[k]|^2 = (|Z[k]|^2 + |Z[-k]|^2) / 2.  Planes are (Nx, Ny), indexed like np.fft.fft2 of an array whose first axis is x."""
 import numpy as np
 
-from .riders import Rider, samples_after
+from .riders import BOX, CountedRider, Param
 
 WINDOWS = ("hann", "boxcar")
 
@@ -113,68 +113,30 @@ def result(sums, samples, sample_steps, box, window, detrend, dx):
             "box": tuple(box), "window": window, "detrend": bool(detrend), "sums": sums}
 
 
-class Spectra(Rider):
-    """The accumulated spectrum of a FluidSimulator (start_spectra): the device planes and their parameters.  No ring: room() is None
-    and run() is not cut by it."""
+WINDOW = Param("window", np.array, lambda a: str(np.asarray(a)), "{theirs} accumulated with the window {0!r}, {ours} with {1!r}")
+DETREND = Param("detrend", np.array, lambda a: bool(np.asarray(a)), "{theirs} accumulated with detrend={0}, {ours} with detrend={1}")
+
+
+class Spectra(CountedRider):
+    """The accumulated spectrum of a FluidSimulator (start_spectra): the device planes and their parameters.
+    held(z) -> (box, window, detrend, every, start), or None."""
+    kind, payload, noun = "spec", "power", "spectrum"
+    params = (BOX, WINDOW, DETREND)
+    refuses_missing = False
 
     def __init__(self, dev, spec, window, dx):
-        self.dev, self.spec, self.window, self.dx = dev, spec, window, float(dx)
-        self.every, self.start_step = int(spec.every), int(spec.start)
-        self.base = 0              # samples taken before the last reset (sample_steps)
+        super().__init__(dev, spec, spec.every, spec.start)
+        self.spec, self.window, self.dx = spec, window, float(dx)
 
-    @property
-    def token(self):
-        return ("spec", self.spec.serial)
+    def attached(self):
+        return tuple(self.spec.box), self.window, bool(self.spec.detrend)
 
     def launch(self, sim):
         self.dev.spec_launch(self.spec, sim._solver.get_fields()[0])
 
-    def free(self):
-        self.dev.spec_free(self.spec)
-
-    def sample_steps(self, samples):
-        """The step (counted from start_spectra, from 1) of every sample in the plane, int64 (samples,)."""
-        k = self.base + np.arange(int(samples), dtype=np.int64)
-        return self.start_step + (k + 1) * self.every
-
     def data(self):
         sums, _, samples = self.dev.spec_read(self.spec)
         return result(sums, samples, self.sample_steps(samples), self.spec.box, self.window, self.spec.detrend, self.dx)
-
-    def reset(self):
-        _, launches, _ = self.dev.spec_read(self.spec, power=False)
-        self.dev.spec_reset(self.spec)
-        self.base = samples_after(launches, self.every, self.start_step)
-
-    def checkpoint(self):
-        power, launches, samples = self.dev.spec_get(self.spec)
-        return {"spec.power": power, "spec.launches": np.array(launches), "spec.samples": np.array(samples), "spec.base": np.array(self.base),
-                "spec.box": np.array(self.spec.box, np.int64), "spec.window": np.array(self.window), "spec.detrend": np.array(self.spec.detrend),
-                "spec.every": np.array(self.every), "spec.start": np.array(self.start_step)}
-
-    @staticmethod
-    def held(z):
-        """-> (box, window, detrend, every, start), or None."""
-        if "spec.power" not in z:
-            return None
-        return (tuple(int(b) for b in np.asarray(z["spec.box"])), str(np.asarray(z["spec.window"])), bool(np.asarray(z["spec.detrend"])),
-                int(z["spec.every"]), int(z["spec.start"]))
-
-    def restore(self, z):
-        """Refused (ValueError) before any device work when the checkpoint's box, window, detrend, every or start_step are not the
-        attached ones."""
-        box, window, detrend, every, start = self.held(z)
-        if box != tuple(self.spec.box):
-            raise ValueError(f"the checkpoint's spectrum was accumulated over the box {box}, the attached one over {tuple(self.spec.box)}")
-        if window != self.window:
-            raise ValueError(f"the checkpoint's spectrum was accumulated with the window {window!r}, the attached one with {self.window!r}")
-        if detrend != bool(self.spec.detrend):
-            raise ValueError(f"the checkpoint's spectrum was accumulated with detrend={detrend}, the attached one with detrend={bool(self.spec.detrend)}")
-        if (every, start) != (self.every, self.start_step):
-            raise ValueError(f"the checkpoint's spectrum samples every {every} from {start}, the attached one every {self.every} from {self.start_step}")
-        self.dev.spec_set(self.spec, z["spec.power"], int(z["spec.launches"]), int(z["spec.samples"]))
-        self.base = int(z["spec.base"])
-        return int(z["spec.samples"])
 
 
 def create(dev, box, window, detrend, every=1, start=0):
@@ -240,87 +202,42 @@ def cross_result(sums, samples, sample_steps, box, quantities, window, detrend, 
     return out
 
 
-class CrossSpectra(Rider):
-    """The accumulated cross-spectrum of a FluidSimulator (start_cross_spectra): the device planes and their parameters.  No ring: room()
-    is None and run() is not cut by it."""
+def _pair_indices(names):
+    from .ride_ops import RideOps
+    return np.array([-1 if n is None else RideOps.DIST_QUANTITIES.index(n) for n in names], np.int64)
+
+
+def _pair_held(a):
+    from .ride_ops import RideOps
+    qa, qb = (int(q) for q in np.asarray(a))
+    nq = len(RideOps.DIST_QUANTITIES)
+    if not (0 <= qa < nq and -1 <= qb < nq):
+        raise ValueError(f"the checkpoint's cross-spectrum names the quantities {qa}, {qb}: not indices of this build's quantities")
+    return pair_names(qa, qb)
+
+
+class CrossSpectra(CountedRider):
+    """The accumulated cross-spectrum of a FluidSimulator (start_cross_spectra): the device planes and their parameters.
+    held(z) -> (box, quantities (name_a, name_b or None), window, detrend, every, start), or None."""
+    kind, payload, noun = "xspec", "sums", "cross-spectrum"
+    params = (BOX, Param("quantities", _pair_indices, _pair_held, "{theirs} accumulated for the pair {0}, {ours} for {1}"), WINDOW, DETREND)
 
     def __init__(self, dev, xspec, window):
-        self.dev, self.xspec, self.window = dev, xspec, window
-        self.every, self.start_step = int(xspec.every), int(xspec.start)
-        self.base = 0              # samples taken before the last reset (sample_steps)
+        super().__init__(dev, xspec, xspec.every, xspec.start)
+        self.xspec, self.window = xspec, window
+        self.quantities = pair_names(xspec.qa, xspec.qb)
 
-    @property
-    def token(self):
-        return ("xspec", self.xspec.serial)
-
-    @property
-    def quantities(self):
-        return pair_names(self.xspec.qa, self.xspec.qb)
+    def attached(self):
+        return tuple(self.xspec.box), self.quantities, self.window, bool(self.xspec.detrend)
 
     def launch(self, sim):
         v, p = sim._solver.get_fields()[:2]
         self.dev.xspec_launch(self.xspec, v, p)
 
-    def free(self):
-        self.dev.xspec_free(self.xspec)
-
-    def sample_steps(self, samples):
-        """The step (counted from start_cross_spectra, from 1) of every sample in the planes, int64 (samples,)."""
-        k = self.base + np.arange(int(samples), dtype=np.int64)
-        return self.start_step + (k + 1) * self.every
-
     def data(self):
         sums, _, samples = self.dev.xspec_read(self.xspec)
         return cross_result(sums, samples, self.sample_steps(samples), self.xspec.box, self.quantities, self.window, self.xspec.detrend,
                             self.xspec.dx)
-
-    def reset(self):
-        _, launches, _ = self.dev.xspec_read(self.xspec, sums=False)
-        self.dev.xspec_reset(self.xspec)
-        self.base = samples_after(launches, self.every, self.start_step)
-
-    def checkpoint(self):
-        sums, launches, samples = self.dev.xspec_get(self.xspec)
-        return {"xspec.sums": sums, "xspec.launches": np.array(launches), "xspec.samples": np.array(samples), "xspec.base": np.array(self.base),
-                "xspec.box": np.array(self.xspec.box, np.int64), "xspec.quantities": np.array([self.xspec.qa, self.xspec.qb], np.int64),
-                "xspec.window": np.array(self.window), "xspec.detrend": np.array(self.xspec.detrend), "xspec.every": np.array(self.every),
-                "xspec.start": np.array(self.start_step)}
-
-    @staticmethod
-    def held(z):
-        """-> (box, quantities (name_a, name_b or None), window, detrend, every, start), or None."""
-        if "xspec.sums" not in z:
-            return None
-        qa, qb = (int(q) for q in np.asarray(z["xspec.quantities"]))
-        from .ride_ops import RideOps
-        nq = len(RideOps.DIST_QUANTITIES)
-        if not (0 <= qa < nq and -1 <= qb < nq):
-            raise ValueError(f"the checkpoint's cross-spectrum names the quantities {qa}, {qb}: not indices of this build's quantities")
-        return (tuple(int(b) for b in np.asarray(z["xspec.box"])), pair_names(qa, qb), str(np.asarray(z["xspec.window"])),
-                bool(np.asarray(z["xspec.detrend"])), int(z["xspec.every"]), int(z["xspec.start"]))
-
-    def restore(self, z):
-        """Refused (ValueError) before any device work when the checkpoint's box, quantities, window, detrend, every or start_step are
-        not the attached ones."""
-        held = self.held(z)
-        if held is None:
-            raise ValueError("the checkpoint holds no cross-spectrum")
-        box, quantities, window, detrend, every, start = held
-        if box != tuple(self.xspec.box):
-            raise ValueError(f"the checkpoint's cross-spectrum was accumulated over the box {box}, the attached one over {tuple(self.xspec.box)}")
-        if quantities != self.quantities:
-            raise ValueError(f"the checkpoint's cross-spectrum was accumulated for the pair {quantities}, the attached one for {self.quantities}")
-        if window != self.window:
-            raise ValueError(f"the checkpoint's cross-spectrum was accumulated with the window {window!r}, the attached one with {self.window!r}")
-        if detrend != bool(self.xspec.detrend):
-            raise ValueError(f"the checkpoint's cross-spectrum was accumulated with detrend={detrend}, the attached one with "
-                             f"detrend={bool(self.xspec.detrend)}")
-        if (every, start) != (self.every, self.start_step):
-            raise ValueError(f"the checkpoint's cross-spectrum samples every {every} from {start}, the attached one every {self.every} from "
-                             f"{self.start_step}")
-        self.dev.xspec_set(self.xspec, z["xspec.sums"], int(z["xspec.launches"]), int(z["xspec.samples"]))
-        self.base = int(z["xspec.base"])
-        return int(z["xspec.samples"])
 
 
 def create_cross(dev, box, pair, dx, window, detrend, every=1, start=0):

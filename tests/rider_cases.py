@@ -1,7 +1,7 @@
 """The scene, the cadences and the readers of the test that attaches every rider of the step at once (tests/test_gpu_riders.py): bc3 res
-64 under the CIP solver - a body and a 6-step buffer rotation - with eleven kinds of rider whose cadences and starts are pairwise different,
+64 under the CIP solver - a body and a 6-step buffer rotation - with twelve kinds of rider whose cadences and starts are pairwise different,
 so that no two of them sample on the same set of steps.  Shared so that the combined simulator, the eager one, the downloading one and the
-eleven that carry one kind each are attached by the same code."""
+twelve that carry one kind each are attached by the same code."""
 import numpy as np
 
 RES = 64
@@ -9,9 +9,9 @@ DT, DX, RE, VC = 0.05 / RES, 1.0 / RES, 1.0e6, 5.0
 STEPS, MORE = 100, 20
 
 # the documented order of FluidSimulator._riders(), and the kinds of the tokens they put into a signature, in that order
-RIDER_ORDER = ["Recorder", "Averager", "Modes", "Pod", "Distributions", "Spectra", "CrossSpectra", "ScaleFluxes", "Tracker", "Tracers", "Vortices"]
-TOKEN_KINDS = ["history", "mean", "modes", "pod", "dist", "spec", "xspec", "flux", "loads", "tracer", "tracer_accum", "vortices"]
-KINDS = ("history", "mean", "modes", "pod", "dist", "spec", "xspec", "flux", "loads", "tracers", "vortices")
+RIDER_ORDER = ["Recorder", "Averager", "Modes", "Pod", "Distributions", "Spectra", "CrossSpectra", "ScaleFluxes", "Budget", "Tracker", "Tracers", "Vortices"]
+TOKEN_KINDS = ["history", "mean", "modes", "pod", "dist", "spec", "xspec", "flux", "budget", "loads", "tracer", "tracer_accum", "vortices"]
+KINDS = ("history", "mean", "modes", "pod", "dist", "spec", "xspec", "flux", "budget", "loads", "tracers", "vortices")
 
 PROBES = [(5, 30)]
 HISTORY = dict(every=1, capacity=20)
@@ -29,6 +29,7 @@ XSPEC = dict(every=3, start_step=2)
 FLUX_BOX = (20, 24, 36, 40)             # 16 x 16 inside the box of the spectra
 FLUX_WIDTHS = (1, 3)
 FLUX = dict(every=5, start_step=2)
+BUDGET = dict(every=7, start_step=1)    # over SPEC_BOX: wall cells and fluid cells; steps 8, 15, ..., 99
 LOADS = dict(every=2, capacity=10)
 N_TRACERS, SORT_EVERY = 256, 32
 TRACER_ACCUM = dict(every=3)
@@ -87,6 +88,8 @@ def attach(sim, kinds=KINDS, capacities=None):
         sim.start_cross_spectra(SPEC_BOX, XSPEC_PAIR, **XSPEC)
     if "flux" in kinds:
         sim.start_scale_fluxes(FLUX_BOX, FLUX_WIDTHS, **FLUX)
+    if "budget" in kinds:
+        sim.start_budget(SPEC_BOX, **BUDGET)
     if "loads" in kinds:
         sim.track_body(box, **LOADS)
     if "tracers" in kinds:
@@ -123,6 +126,8 @@ def read(sim, kind):
         return {"cross_spectra": sim.cross_spectra(), "plane": dev.xspec_plane(sim._xspectrar.xspec)}
     if kind == "flux":
         return {"scale_fluxes": sim.scale_fluxes(), "filtered": {r: dev.flux_filtered(sim._fluxr.flux, r) for r in FLUX_WIDTHS}}
+    if kind == "budget":
+        return {"budget": sim.budget()}
     if kind == "loads":
         return {"body_loads": sim.body_loads(), "body_surface.sums": sim.body_surface()["sums"]}
     if kind == "tracers":

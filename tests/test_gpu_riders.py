@@ -4,9 +4,9 @@ The first test: the history recorder, time averages, body tracker, tracer partic
 graphs, cut into chunks by the two rings and the sort schedule, gathers bit for bit what eager steps gather, and after the stop_* calls no
 cached graph holds a rider's launch.
 
-The second, in f32 and f64: all the kinds - eleven since the scale fluxes joined; the test names still say ten - (tests/rider_cases.py:
-history, averages, modes, POD with the FTLE over its snapshots, distributions, spectra, cross-spectra, scale fluxes with their filtered
-planes, body tracker, inertial tracers with deposits and accumulated occupancy, vortex tracker) at pairwise
+The second, in f32 and f64: all the kinds - twelve since the scale fluxes and the budget joined; the test names still say ten -
+(tests/rider_cases.py: history, averages, modes, POD with the FTLE over its snapshots, distributions, spectra, cross-spectra, scale fluxes
+with their filtered planes, the kinetic-energy budget, body tracker, inertial tracers with deposits and accumulated occupancy, vortex tracker) at pairwise
 different cadences, the run cut by three rings and the sort schedule.  Every reader returns on replayed graphs what it returns after eager
 steps and what the simulator that carries that kind alone returns; the mean, the modes, the distributions and both spectra of eager steps
 equal their NumPy restatements on per-step downloads; the trajectory is that of the simulator without a rider; every cached signature holds
@@ -215,6 +215,13 @@ def _assert_not_empty(r, mask):
     assert f["samples"] == len(RC.samples(**RC.FLUX)) and f["sample_steps"].tolist() == RC.samples(**RC.FLUX)
     assert all(np.abs(f["sums"][k, n]).max() > 0 for k in range(len(RC.FLUX_WIDTHS)) for n in range(3))
     assert all(np.abs(r["flux"]["filtered"][w]).max() > 0 for w in RC.FLUX_WIDTHS)
+    g = r["budget"]["budget"]
+    assert g["samples"] == len(RC.samples(**RC.BUDGET)) == 14 and g["sample_steps"].tolist() == RC.samples(**RC.BUDGET)
+    fluid = mask[RC.SPEC_BOX[0]:RC.SPEC_BOX[2], RC.SPEC_BOX[1]:RC.SPEC_BOX[3]] == 0
+    assert fluid.any() and not fluid.all() and np.array_equal(g["fluid"], fluid)
+    assert g["sums"].shape == (21,) + fluid.shape
+    for n in range(21):
+        assert g["sums"][n][fluid].any() and not g["sums"][n][~fluid].any(), f"budget plane {n}"
     b = r["loads"]["body_loads"]
     assert b["step"].tolist() == RC.samples(**RC.LOADS) and np.abs(b["pressure_x"]).max() > 0 and np.abs(b["viscous_x"]).max() > 0
     assert np.abs(r["loads"]["body_surface.sums"]).max() > 0
@@ -278,6 +285,7 @@ def test_all_ten_kinds_on_graphs_equal_eager_steps_each_alone_and_the_restatemen
             sim.stop_spectra()
             sim.stop_cross_spectra()
             sim.stop_scale_fluxes()
+            sim.stop_budget()
             sim.stop_body()
             sim.stop_tracer_accumulation()
             sim.stop_tracers()
